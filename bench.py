@@ -66,11 +66,45 @@ def parse_args(argv=None):
                          "config5: block Hamiltonian N=5e7 (sectors of 10, dense blocks), thick-restart Lanczos m=128 "
                          "(one GPU; parity-test configs with their own CPU baseline, not the driver's bench line)")
     ap.add_argument("--seeded-start", action="store_true", help="numpy-seeded N(0,1) start vector instead of the reference default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float64; see dump_outputs)")
     # launcher self-test (CPU, tests/test_bench_launcher.py): every rank reports its environment and exits before
     # anything touches a GPU; --launch-check-fail R makes rank R exit with status 3 while its peers would wait
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launch-check-fail", type=int, default=-1, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_MAX_ENTRIES = 1 << 20  # per array (8 MB in float64): a longer array is written as a fixed sample of its rows
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, results: dict) -> None:
+    """--dump-outputs: every non-empty floating-point array of a solver's results() (alpha, beta, eigenvalues, Hessenberg
+    matrix, eigenvectors, ...) as out_dir/<name>.npy in float64, a complex array as <name>_real.npy and <name>_imag.npy.  An
+    array of more than DUMP_MAX_ENTRIES entries keeps the rows np.random.default_rng(0) picks (sorted), so that two runs
+    with the same arguments write the same entries and two builds can be compared file for file."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in sorted(results.items()):
+        if not isinstance(a, np.ndarray) or a.size == 0 or a.dtype.kind not in "fc":
+            continue
+        if a.size > DUMP_MAX_ENTRIES:
+            keep = max(1, DUMP_MAX_ENTRIES // (a.size // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        parts = {name + "_real": a.real, name + "_imag": a.imag} if a.dtype.kind == "c" else {name: a}
+        for part, v in parts.items():
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            total += v.nbytes
+            if total > DUMP_MAX_BYTES:
+                raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs at {part}")
+            np.save(os.path.join(out_dir, part + ".npy"), v)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -303,6 +337,10 @@ def other_config(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     ctx.profile_enable(False)
+    r = es.results()  # what the last timed step returned
+    assert r[its_from] == its, (r[its_from], its)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r)
     dt_plain = None
     if dt / args.steps < 0.5:  # as for the Laplacian: the same steps once more without the per-launch events, reported next to `value`
         torch.cuda.synchronize()
@@ -312,8 +350,6 @@ def other_config(args):
         ctx.sync()
         torch.cuda.synchronize()
         dt_plain = time.perf_counter() - t1
-    r = es.results()
-    assert r[its_from] == its, (r[its_from], its)
     prof = {k: ctx.profile_get(v) for k, v in kinds.items()}
     if total_bytes is None:
         total_bytes = sum(v[2] for v in prof.values()) / args.steps
@@ -532,6 +568,10 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     ctx.profile_enable(False)
+    r = es.results()  # what the last timed step returned
+    assert r["iterations"] == m and r["nvec"] == m + 1, (r["iterations"], r["nvec"])
+    if args.dump_outputs and rank == 0:  # alpha, beta and the eigenvalues are global: every rank holds the same
+        dump_outputs(args.dump_outputs, r)
 
     # the same steps once more WITHOUT the per-launch HIP events (they are free at 2 s per solve and cost a launch-bound solve
     # 15-25 %: 128^3 runs at 12.5 ms with them and 10.4 ms without): reported next to `value`, never instead of it
@@ -544,8 +584,6 @@ def main():
         barrier()
         dt_plain = time.perf_counter() - t1
 
-    r = es.results()
-    assert r["iterations"] == m and r["nvec"] == m + 1, (r["iterations"], r["nvec"])
     nnz_global = 7 * N - 6 * n * n
     total_bytes = lanczos_bytes(N, nnz_global, m) * args.steps
 

@@ -1,4 +1,4 @@
-import sys; sys.path.insert(0, "/root/repo")
+import sys; sys.path.insert(0, ".")
 import numpy as np
 from cmpt_eigenex_amd import capi
 from oracle import cref
