@@ -492,10 +492,11 @@ __device__ __forceinline__ TileRange spmv_tiles(int64_t ntiles, int xcd_sliced) 
 // InlineArnoldiBegin: returns true if the step must not run (the same test in every workgroup); *scale = 1/residue.
 // With tail_k >= 0 the previous step is finished first (k_arnoldi_tail): every workgroup forms the same residue from the
 // second pass's partial sums (or takes the first pass's norm) and the step index from the argument -- it reads nothing that
-// workgroup 0 changes; *res_out / *k_out are what the record needs.
-__device__ __forceinline__ bool arnoldi_begin_inline(const InlineArnoldiBegin& ab, double* scale, double* lds4, double* res_out, int* k_out) {
+// workgroup 0 changes; *res_out / *nrm2_out / *k_out are what the record needs (*nrm2_out only with tail_k >= 0).
+__device__ __forceinline__ bool arnoldi_begin_inline(const InlineArnoldiBegin& ab, double* scale, double* lds4, double* res_out, double* nrm2_out,
+                                                      int* k_out) {
   int k;
-  double res;
+  double res, nrm2 = 0.0;
   if (ab.tail_k >= 0) {
     const bool second = ab.pass2->stopped == 0;
     double s = 0.0;
@@ -506,7 +507,7 @@ __device__ __forceinline__ bool arnoldi_begin_inline(const InlineArnoldiBegin& a
     if ((threadIdx.x & 63) == 0 && threadIdx.x < kBlock) lds4[threadIdx.x >> 6] = s;
     __syncthreads();
     s = (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-    const double nrm2 = second ? s : *ab.nrm2_first;
+    nrm2 = second ? s : *ab.nrm2_first;
     res = sqrt(nrm2);  // arnoldi.hpp:348, :385
     k = ab.tail_k + 1;
   } else {
@@ -516,11 +517,12 @@ __device__ __forceinline__ bool arnoldi_begin_inline(const InlineArnoldiBegin& a
   const bool stop = (int64_t)k == ab.n_global || res <= ab.threshold || k >= ab.cap;  // arnoldiStepIsUtmost  arnoldi.hpp:277-288
   *scale = 1.0 / res;                                                                   // arnoldi.hpp:365
   *res_out = res;
+  *nrm2_out = nrm2;
   *k_out = k;
   return stop;
 }
-// workgroup 0, all threads (the copy of h into H is spread over them); `stop`, `scale`, `res`, `k` as derived above
-__device__ __forceinline__ void arnoldi_begin_record(const InlineArnoldiBegin& ab, bool stop, double scale, double res, int k) {
+// workgroup 0, all threads (the copy of h into H is spread over them); `stop`, `scale`, `res`, `nrm2`, `k` as derived above
+__device__ __forceinline__ void arnoldi_begin_record(const InlineArnoldiBegin& ab, bool stop, double scale, double res, double nrm2, int k) {
   if (ab.tail_k >= 0) {  // k_arnoldi_tail for the vector with index tail_k = k - 1
     const bool second = ab.pass2->stopped == 0;
     const int kk = ab.tail_k;
@@ -532,7 +534,7 @@ __device__ __forceinline__ void arnoldi_begin_record(const InlineArnoldiBegin& a
     if (second)
       for (int i = (kk + 1) * ab.es + threadIdx.x; i < ab.ncoef; i += blockDim.x) ab.h[i] += ab.h2[i];  // coefficients of the orthogonalizing vectors
     if (threadIdx.x == 0) {
-      *ab.nrm2_final = res * res;
+      *ab.nrm2_final = nrm2;  // as k_arnoldi_tail stores it (not res * res: the round trip through sqrt can move an ulp)
       for (int e = 0; e < ab.es; ++e) ab.H[((int64_t)kk * ab.ldh + kk + 1) * ab.es + e] = 0.0;  // arnoldi.hpp:384
       ab.ctrl->residue = res;
       ab.ctrl->nvec = kk + 1;
@@ -571,11 +573,11 @@ __global__ __launch_bounds__(kBlock) void k_spmv(const OFF* __restrict__ rowptr,
   if (ctrl->stopped) return;
   double scale = (scale_ptr && !ab.ctrl) ? *scale_ptr : 1.0;
   if (ab.ctrl) {
-    double res;
+    double res, nrm2b;
     int kb;
-    const bool stop = arnoldi_begin_inline(ab, &scale, lds4, &res, &kb);
+    const bool stop = arnoldi_begin_inline(ab, &scale, lds4, &res, &nrm2b, &kb);
     __syncthreads();  // everybody has read the control block before workgroup 0 changes it (other workgroups: the values written are the ones they derived)
-    if (blockIdx.x == 0) arnoldi_begin_record(ab, stop, scale, res, kb);
+    if (blockIdx.x == 0) arnoldi_begin_record(ab, stop, scale, res, nrm2b, kb);
     if (stop) return;
   }
   if (fin.partials) {  // beta_k, the breakdown test and the scale of the operator input (lanczos.hpp:429-439), taken here
@@ -931,11 +933,11 @@ __global__ __launch_bounds__(kSplitBlock) void k_spmv_split(SplitOperatorView op
   if (ctrl->stopped) return;
   double scale = (scale_ptr && !ab.ctrl) ? *scale_ptr : 1.0;
   if (ab.ctrl) {  // the second kernel (k_split_combine) reads the control block after workgroup 0 of this one has recorded
-    double res;
+    double res, nrm2b;
     int kb;
-    const bool stop = arnoldi_begin_inline(ab, &scale, lds4b, &res, &kb);
+    const bool stop = arnoldi_begin_inline(ab, &scale, lds4b, &res, &nrm2b, &kb);
     __syncthreads();
-    if (blockIdx.x == 0) arnoldi_begin_record(ab, stop, scale, res, kb);
+    if (blockIdx.x == 0) arnoldi_begin_record(ab, stop, scale, res, nrm2b, kb);
     if (stop) return;
   }
   const int tid = threadIdx.x, T = op.tile_rows;

@@ -1787,7 +1787,13 @@ void drop_step_graphs(eigenex_basis_s* b) {
 
 int enqueue_steps(eigenex_basis_s* b, int ncalls, int kind) {
   auto plain = [&]() -> int {
-    for (int i = 0; i < ncalls; ++i) CHK(kind == 0 ? lanczos_call(b, i == ncalls - 1) : arnoldi_call(b, i == ncalls - 1));
+    for (int i = 0; i < ncalls; ++i) {
+      const int rc = kind == 0 ? lanczos_call(b, i == ncalls - 1) : arnoldi_call(b, i == ncalls - 1);
+      if (rc != 0) {
+        b->tail_pending = false;  // a deferred step end is never handed to a later batch (its tail_k would be stale)
+        return rc;
+      }
+    }
     return 0;
   };
   eigenex_context_s* c = b->ctx;
@@ -1809,8 +1815,8 @@ int enqueue_steps(eigenex_basis_s* b, int ncalls, int kind) {
       return 0;
     }
   // record: nothing executes during the capture; the host-side counters advance as in a plain run
-  const bool started0 = b->started;
-  const int h_nvec0 = b->h_nvec;
+  const bool started0 = b->started, tail_pending0 = b->tail_pending;
+  const int h_nvec0 = b->h_nvec, tail_ncoef0 = b->tail_ncoef;
   if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
     (void)hipGetLastError();
     return plain();
@@ -1845,6 +1851,8 @@ int enqueue_steps(eigenex_basis_s* b, int ncalls, int kind) {
   (void)hipGetLastError();
   b->started = started0;
   b->h_nvec = h_nvec0;
+  b->tail_pending = tail_pending0;
+  b->tail_ncoef = tail_ncoef0;
   if (rc != 0) {
     g_err = err;
     return rc;  // the same argument/state error a plain run reports, before anything was launched
