@@ -92,6 +92,7 @@ SIGNATURES = {
     "eigenex_csr_upload_ex": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _ip, _ip, _dp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_csr_column_blocks": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "eigenex_csr_layout": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "eigenex_csr_encoding": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "eigenex_csr_upload_device": (C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "eigenex_block_upload": (C.c_int, [_vp, C.c_int64, C.c_int, _lp, C.c_int, _lp, C.c_int64, _lp, _lp, C.POINTER(C.c_void_p), C.POINTER(_vp)]),
     "eigenex_block_upload_z": (C.c_int, [_vp, C.c_int64, C.c_int, _lp, C.c_int, _lp, C.c_int64, _lp, _lp, C.POINTER(C.c_void_p), C.POINTER(_vp)]),
@@ -494,6 +495,12 @@ class Csr:
         v = C.c_int()
         _chk(lib().eigenex_csr_layout(self.h, C.byref(v)))
         return ("csr", "column_blocked", "sorted_tiles", "dense_blocks", "split_tiles")[v.value]
+
+    def encoding(self) -> str:
+        """"plain" or "row_codes" (include/eigenex_hip.h: eigenex_csr_encoding)"""
+        v = C.c_int()
+        _chk(lib().eigenex_csr_encoding(self.h, C.byref(v)))
+        return ("plain", "row_codes")[v.value]
 
     def column_blocks(self) -> int:
         k = C.c_int()

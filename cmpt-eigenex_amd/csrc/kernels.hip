@@ -715,6 +715,103 @@ __global__ __launch_bounds__(kBlock) void k_spmv(const OFF* __restrict__ rowptr,
 }
 
 // ---------------------------------------------------------------------------
+// Row-coded operator (row_codes.hpp): one 8- or 16-byte record per row instead of rowptr / col / val.  k_spmv's tiles,
+// persistent grid, tile order and tile lists, its prologue (InlineFin, InlineArnoldiBegin) and its epilogue, so that the
+// partial dots are the same numbers; one thread per row.  The row walks its slots in slot order (= stored order):
+// x = x_ext[r + d_s] * scale, prod = pal[code] * x, sum = sum + prod from 0.0 -- the plain kernel's products and sums.
+// REC = record bytes (8 or 16).  The palette sits in LDS; the records are read once (non-temporal, one tile ahead).
+// Operators in one pass only: of the pass bits, kPassSelfNorm alone.
+// ---------------------------------------------------------------------------
+typedef unsigned long long v2u64_t __attribute__((ext_vector_type(2)));
+template <int REC>
+__device__ __forceinline__ void row_code_load(const uint64_t* __restrict__ rec, int64_t row, uint64_t* w) {
+  if constexpr (REC == 8) {
+    w[0] = __builtin_nontemporal_load(reinterpret_cast<const unsigned long long*>(rec) + row);
+  } else {
+    const v2u64_t v = __builtin_nontemporal_load(reinterpret_cast<const v2u64_t*>(rec) + row);
+    w[0] = v.x, w[1] = v.y;
+  }
+}
+
+template <int REC>
+__global__ __launch_bounds__(kBlock) void k_spmv_rows(RowCodeView op, const double* __restrict__ x_ext,
+                                                      const double* __restrict__ scale_ptr, double shift,
+                                                      double* __restrict__ y, double* __restrict__ u_out, int64_t n,
+                                                      int64_t ntiles, double* __restrict__ partials, int spmv_flags,
+                                                      int pass, const Ctrl* ctrl, InlineFin fin, InlineArnoldiBegin ab,
+                                                      const int32_t* __restrict__ tile_list) {  // no __restrict__ on ctrl: fin.ctrl / ab.ctrl alias it
+  constexpr int W = REC / 8, S = REC;  // 64-bit words and slots per record
+  __shared__ double pal[kRowCodeMaxValues];
+  __shared__ double lds4[4];
+  if (ctrl->stopped) return;
+  for (int i = threadIdx.x; i < op.npal; i += kBlock) pal[i] = op.pal[i];
+  double scale = (scale_ptr && !ab.ctrl) ? *scale_ptr : 1.0;
+  if (ab.ctrl) {
+    double res, nrm2b;
+    int kb;
+    const bool stop = arnoldi_begin_inline(ab, &scale, lds4, &res, &nrm2b, &kb);
+    __syncthreads();
+    if (blockIdx.x == 0) arnoldi_begin_record(ab, stop, scale, res, nrm2b, kb);
+    if (stop) return;
+  }
+  if (fin.partials) {  // as in k_spmv
+    const double nrm2 = inline_fin_sum(fin, lds4);
+    const double nrm = sqrt(nrm2);
+    const bool stop = fin.mode == kFinInit ? nrm < fin.threshold : nrm <= fin.threshold;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      fin.out[0] = nrm2;
+      fin_norm_apply(fin.ctrl, nrm2, fin.threshold, fin.mode, fin.series);
+    }
+    if (stop) return;
+    scale = 1.0 / nrm;
+  }
+  __syncthreads();  // the palette
+  const int tid = threadIdx.x;
+  double dot = 0.0;
+  const TileRange tr = spmv_tiles(ntiles, spmv_flags & 1);
+  auto tile_of = [&](int64_t slot) { return tile_list ? (int64_t)tile_list[slot] : slot; };
+  // records exist for every row of every tile (rows behind n: all slots absent), so the loads need no row test
+  uint64_t rec[W], nrec[W];
+  int64_t tile = tr.first < tr.end ? tile_of(tr.first) : 0;
+  if (tr.first < tr.end) row_code_load<REC>(op.rec, tile * kSpmvRows + tid, rec);
+  for (int64_t slot = tr.first; slot < tr.end; slot += tr.step) {
+    const int64_t r = tile * kSpmvRows + tid;
+    // branch-free, so that all gathers are in flight at once: an absent slot (also every slot behind the table's) loads
+    // x_ext[0] and its sum is dropped
+    double xs[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) xs[s] = x_ext[row_code_byte(rec, s) != kRowCodeAbsent ? r + op.slots.off[s] : 0];
+    // the next tile's record, behind the gathers
+    const int64_t nslot = slot + tr.step;
+    const int64_t ntile = nslot < tr.end ? tile_of(nslot) : 0;
+    if (nslot < tr.end) row_code_load<REC>(op.rec, ntile * kSpmvRows + tid, nrec);
+    double sum = 0.0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {  // stored order, multiply then add
+      const unsigned c = row_code_byte(rec, s);
+      const bool here = c != kRowCodeAbsent;
+      const double t = add_product_nofma(sum, pal[here ? c : 0], xs[s] * scale);
+      sum = here ? t : sum;
+    }
+    if (r < n) {
+      const double xr = x_ext[r] * scale;
+      double yr = sum;
+      if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
+      __builtin_nontemporal_store(yr, &y[r]);
+      if (u_out) __builtin_nontemporal_store(xr, &u_out[r]);
+      dot = (pass & kPassSelfNorm) ? fma(yr, yr, dot) : fma(xr, yr, dot);
+    }
+#pragma unroll
+    for (int w = 0; w < W; ++w) rec[w] = nrec[w];
+    tile = ntile;
+  }
+  if (partials) {
+    dot = block_sum(dot, lds4);
+    if (tid == 0) partials[blockIdx.x] = dot;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // CSR SpMV for operators whose gathers are scattered over an input larger than L2 (BASELINE config 3: 10^6 rows,
 // 32 random columns each), "column-sorted row tiles".  Measured on the stream form above (rocprofv3 PMC,
 // profiles/r02_config3_pmc.md): every gather is its own L2 request (8.8e6 TCP->TCC reads for 8.0e6 gathers per
@@ -1999,6 +2096,53 @@ void launch_spmv64(hipStream_t s, const int64_t* rowptr, const int32_t* col, con
                    const Ctrl* ctrl, int spmv_flags, int pass, const InlineFin* fin, const InlineArnoldiBegin* begin,
                    const int32_t* tile_list, int64_t list_len) {
   launch_spmv_t(s, rowptr, col, val, x_ext, scale, shift, y, u_out, n, partials, grid, ctrl, spmv_flags, pass, fin, begin, tile_list, list_len);
+}
+void launch_spmv_rows(hipStream_t s, const RowCodeView& op, const double* x_ext, const double* scale, double shift, double* y,
+                      double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int spmv_flags, int pass,
+                      const InlineFin* fin, const InlineArnoldiBegin* begin, const int32_t* tile_list, int64_t list_len) {
+  const int64_t ntiles = tile_list ? list_len : (n + kSpmvRows - 1) / kSpmvRows;
+  if (ntiles <= 0) return;
+  const InlineFin nofin{nullptr, 0, 0, 0.0, nullptr, nullptr, nullptr};
+  const InlineArnoldiBegin nobegin{nullptr, 0.0, 0, 0, nullptr, 0, 0, -1, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
+  if (op.rec_bytes == 8)
+    hipLaunchKernelGGL(k_spmv_rows<8>, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, y, u_out, n, ntiles, partials,
+                       spmv_flags, pass, ctrl, fin ? *fin : nofin, begin ? *begin : nobegin, tile_list);
+  else
+    hipLaunchKernelGGL(k_spmv_rows<16>, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, y, u_out, n, ntiles, partials,
+                       spmv_flags, pass, ctrl, fin ? *fin : nofin, begin ? *begin : nobegin, tile_list);
+}
+
+// Device encoder of a generated CSR shard (row_code_encode, the host's function): records for rows [0, nrec_rows), rows >= n all
+// absent; a row that does not fit the tables sets *bad
+template <class OFF>
+__global__ __launch_bounds__(kBlock) void k_encode_rows(const OFF* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                        const double* __restrict__ val, int64_t n, int64_t nrec_rows, RowCodeSlots slots,
+                                                        int nslots, RowCodePalette pal, int rec_bytes, uint8_t* __restrict__ rec,
+                                                        unsigned int* bad) {
+  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < nrec_rows; r += (int64_t)gridDim.x * kBlock) {
+    uint8_t b[kRowCodeMaxSlots];
+    bool ok = true;
+    if (r < n) {
+      const OFF p = rowptr[r];
+      ok = row_code_encode(r, col + p, val + p, (int64_t)(rowptr[r + 1] - p), slots.off, nslots, pal.bits, pal.n, b, rec_bytes);
+    } else {
+      for (int i = 0; i < rec_bytes; ++i) b[i] = (uint8_t)kRowCodeAbsent;
+    }
+    if (!ok) atomicAdd(bad, 1u);
+    for (int i = 0; i < rec_bytes; ++i) rec[r * rec_bytes + i] = b[i];
+  }
+}
+void launch_encode_rows(hipStream_t s, const int32_t* rowptr, const int64_t* rowptr64, const int32_t* col, const double* val, int64_t n,
+                        int64_t nrec_rows, const RowCodeSlots& slots, int nslots, const RowCodePalette& pal, int rec_bytes, uint8_t* rec,
+                        unsigned int* bad) {
+  const int grid = (int)std::min<int64_t>((nrec_rows + kBlock - 1) / kBlock, 65536);
+  if (grid <= 0) return;
+  if (rowptr64)
+    hipLaunchKernelGGL(k_encode_rows<int64_t>, dim3(grid), dim3(kBlock), 0, s, rowptr64, col, val, n, nrec_rows, slots, nslots, pal,
+                       rec_bytes, rec, bad);
+  else
+    hipLaunchKernelGGL(k_encode_rows<int32_t>, dim3(grid), dim3(kBlock), 0, s, rowptr, col, val, n, nrec_rows, slots, nslots, pal,
+                       rec_bytes, rec, bad);
 }
 
 void launch_spmv_sorted(hipStream_t s, const SortedOperatorView& op, const double* x_ext, const double* scale, double shift, double* y,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "row_codes.hpp"
 #include "split_layout.hpp"
 #include "spmv_index.hpp"
 
@@ -149,6 +150,27 @@ void launch_spmv64(hipStream_t s, const int64_t* rowptr, const int32_t* col, con
                    const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                    const Ctrl* ctrl, int spmv_flags = 0, int pass = 0, const InlineFin* fin = nullptr,
                    const InlineArnoldiBegin* begin = nullptr, const int32_t* tile_list = nullptr, int64_t list_len = 0);
+// Row-coded operator (real fp64 in one pass; row_codes.hpp, kernels.hip: k_spmv_rows): rec = one record of rec_bytes (8 or 16)
+// per row of every 256-row tile, pal = npal values, slots = the offsets.  Same tiles, grid, partial dots and hooks as launch_spmv.
+struct RowCodeView {
+  const uint64_t* rec;
+  const double* pal;
+  int npal, rec_bytes;
+  RowCodeSlots slots;
+};
+void launch_spmv_rows(hipStream_t s, const RowCodeView& op, const double* x_ext, const double* scale, double shift, double* y,
+                      double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int spmv_flags = 0, int pass = 0,
+                      const InlineFin* fin = nullptr, const InlineArnoldiBegin* begin = nullptr, const int32_t* tile_list = nullptr,
+                      int64_t list_len = 0);
+// records of a device-resident CSR shard (rowptr or rowptr64) for rows [0, nrec_rows) with given tables; *bad counts rows that
+// do not fit them
+struct RowCodePalette {
+  uint64_t bits[kRowCodeMaxValues];
+  int n;
+};
+void launch_encode_rows(hipStream_t s, const int32_t* rowptr, const int64_t* rowptr64, const int32_t* col, const double* val, int64_t n,
+                        int64_t nrec_rows, const RowCodeSlots& slots, int nslots, const RowCodePalette& pal, int rec_bytes, uint8_t* rec,
+                        unsigned int* bad);
 // Column-sorted row tiles (real fp64; kernels.hip: k_spmv_sorted): tile t = rows [t*T, (t+1)*T), T = tile_rows, slice k =
 // the k-th range of the operator input (global column order).  Segment (t, k) = entries base[t*(K+1)+k] .. base[t*(K+1)+k+1)
 // of cp/val, sorted by column, padded to a multiple of 4 (val 0, a spare slot); slot = place of the entry in row order

@@ -227,6 +227,12 @@ struct CsrShard {
   int32_t *sp_wg = nullptr, *sp_chunk = nullptr;
   uint32_t* sp_cp = nullptr;
   double* sp_part = nullptr;
+  // row codes (row_codes.hpp; kernels.hpp: RowCodeView) instead of rowptr/col/val: a real shard in one pass whose rows fit
+  // <= 16 column offsets and <= 255 values; one record per row of every 256-row tile.  Still EIGENEX_LAYOUT_CSR.
+  uint64_t* rc_rec = nullptr;
+  double* rc_pal = nullptr;
+  int rc_npal = 0, rc_bytes = 0;
+  RowCodeSlots rc_slots{};
   // block-sparse format (eigenex_block_upload; kernels.hpp: BlockOperatorView) instead of rowptr/col/val
   bool blocked = false;
   double* bval = nullptr;
@@ -412,7 +418,8 @@ void free_csr_shard(CsrShard& s) {
   if (s.send_idx) (void)hipFree(s.send_idx);
   if (s.sendbuf) (void)hipFree(s.sendbuf);
   for (void* p : {(void*)s.bval, (void*)s.gent, (void*)s.gcol, (void*)s.cols, (void*)s.grow0, (void*)s.rowgrp, (void*)s.s_base,
-                  (void*)s.s_cp, (void*)s.s_off, (void*)s.sp_wg, (void*)s.sp_chunk, (void*)s.sp_cp, (void*)s.sp_part})
+                  (void*)s.s_cp, (void*)s.s_off, (void*)s.sp_wg, (void*)s.sp_chunk, (void*)s.sp_cp, (void*)s.sp_part, (void*)s.rc_rec,
+                  (void*)s.rc_pal})
     if (p) (void)hipFree(p);
   s = CsrShard();
 }
@@ -717,6 +724,37 @@ bool build_sorted_layout_t(const CsrShard& s, const std::vector<int32_t>& lcol, 
   return true;
 }
 
+// Row codes (row_codes.hpp): read per upload, so that one process can hold a coded and a plain copy of one operator
+// (EIGENEX_FORCE_WIDE_ROWPTR, the tests' way to run the 64-bit CSR kernel on small operators, keeps the plain form too)
+bool row_codes_allowed() { return std::getenv("EIGENEX_NO_ROW_CODES") == nullptr && std::getenv("EIGENEX_FORCE_WIDE_ROWPTR") == nullptr; }
+int row_code_threads() { return (int)std::max<unsigned>(1, std::min<unsigned>(16, std::thread::hardware_concurrency())); }
+int64_t row_code_rows(int64_t nloc) { return (nloc + kSpmvRows - 1) / kSpmvRows * kSpmvRows; }  // records: whole tiles
+
+void set_row_code_tables(CsrShard& s, const RowCodeTables& T) {
+  s.rc_bytes = T.record_bytes();
+  s.rc_npal = (int)T.pal.size();
+  for (int i = 0; i < kRowCodeMaxSlots; ++i) s.rc_slots.off[i] = i < T.nslots ? T.off[i] : 0;
+}
+
+// Host shards (eigenex_csr_upload / upload64): detect and encode on the host; *done = false (nothing allocated) if the shard does not fit
+template <class OFF>
+int try_row_codes_host(eigenex_context_s* c, CsrShard& s, const OFF* lrp, const int32_t* lcol, const double* val, bool* done) {
+  *done = false;
+  RowCodeTables T;
+  const int nth = row_code_threads();
+  if (!row_codes_detect(s.nloc, lrp, lcol, val, nth, T)) return 0;
+  const int64_t nrec = row_code_rows(s.nloc);
+  std::vector<uint8_t> rec((size_t)(nrec * T.record_bytes()));
+  if (!row_codes_encode(s.nloc, nrec, lrp, lcol, val, T, nth, rec.data())) return 0;
+  set_row_code_tables(s, T);
+  CHK(upload_vec(c, &s.rc_pal, T.pal, 1));
+  HIPCHK(hipMalloc(&s.rc_rec, rec.size()));
+  HIPCHK(hipMemcpyAsync(s.rc_rec, rec.data(), rec.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *done = true;
+  return 0;
+}
+
 // The host-only half of a row shard: ranges, halo slots, local column numbering, receive segments.  No device call:
 // eigenex_plan_create exposes exactly this to hosts without a GPU (the gloo tests drive it across real processes).
 // col: the shard's stored entries (already offset to its first one), nnz of them; may exceed 2^31 (64-bit row pointers)
@@ -775,6 +813,11 @@ int build_shard_host_wide(eigenex_context_s* c, int64_t n_global, int gshard, co
   std::vector<int64_t> lrp((size_t)nloc + 1);
   for (int64_t i = 0; i <= nloc; ++i) lrp[(size_t)i] = rowptr[i] - p0;
   if (c->P > 1 && nloc > 0) CHK(upload_tile_lists(c, s, boundary_tile_flags(nloc, s.npad, lrp, lcol)));
+  if (row_codes_allowed()) {
+    bool coded;
+    CHK(try_row_codes_host(c, s, lrp.data(), lcol.data(), val + p0, &coded));
+    if (coded) return 0;
+  }
   HIPCHK(hipMalloc(&s.rowptr64, sizeof(int64_t) * (size_t)(nloc + 1)));
   HIPCHK(hipMalloc(&s.col, sizeof(int32_t) * (size_t)(s.nnz + kCsrTailPad)));
   HIPCHK(hipMalloc(&s.val, sizeof(double) * (size_t)(s.nnz + kCsrTailPad)));
@@ -876,6 +919,11 @@ int build_shard_host(eigenex_context_s* c, int64_t n_global, int gshard, const i
     vsrc = bval.data();
   }
   if (s.passes == 1 && es == 1 && c->P > 1 && s.nloc > 0) CHK(upload_tile_lists(c, s, boundary_tile_flags(s.nloc, s.npad, lrp, lcol)));
+  if (s.passes == 1 && es == 1 && column_blocks == -1 && row_codes_allowed()) {  // where the automatic choice is plain CSR
+    bool coded;
+    CHK(try_row_codes_host(c, s, lrp.data(), lcol.data(), vsrc, &coded));
+    if (coded) return 0;
+  }
   const size_t nrp = (size_t)s.passes * (s.nloc + 1);
   HIPCHK(hipMalloc(&s.rowptr, sizeof(int32_t) * nrp));
   HIPCHK(hipMalloc(&s.col, sizeof(int32_t) * (s.nnz + kCsrTailPad)));
@@ -1371,6 +1419,14 @@ int enq_orthogonalize(eigenex_basis_s* b, int src_ref, int dst_ref, bool three_t
   return 0;
 }
 
+RowCodeView row_code_view(const CsrShard* m) { return RowCodeView{m->rc_rec, m->rc_pal, m->rc_npal, m->rc_bytes, m->rc_slots}; }
+// bytes of the operator itself that one application reads (the profile's per-kernel traffic)
+double operator_bytes(const CsrShard* m, int es) {
+  if (m->rc_rec) return (double)m->rc_bytes * row_code_rows(m->nloc) + 8.0 * m->rc_npal;
+  if (m->blocked) return 8.0 * es * m->nnz + 4.0 * m->nstripcols + 4.0 * m->nloc;
+  return (4.0 + 8.0 * es) * m->nnz + 4.0 * (m->nloc + 1);
+}
+
 // one operator application on one shard: a launch per column-block pass, the row sums carried in y
 // grid_int > 0 (operators with interior / boundary tile lists): two launches, grid_int and grid - grid_int workgroups, their partial
 // dots side by side; halo_done: the second launch waits for it (the halo exchange is on its way on the other stream)
@@ -1383,7 +1439,9 @@ void launch_operator(hipStream_t st, const CsrShard* m, int es, const double* x_
     const int g2 = grid - grid_int;
     auto go = [&](const int32_t* list, int64_t len, int g, double* part) {
       if (len <= 0 || g <= 0) return;
-      if (m->rowptr64)
+      if (m->rc_rec)
+        launch_spmv_rows(st, row_code_view(m), x_ext, scale, shift, y, u_out, m->nloc, part, g, ctrl, fl, last_pass_flags, nullptr, nullptr, list, len);
+      else if (m->rowptr64)
         launch_spmv64(st, m->rowptr64, m->col, m->val, x_ext, scale, shift, y, u_out, m->nloc, part, g, ctrl, fl, last_pass_flags, nullptr, nullptr, list, len);
       else
         launch_spmv(st, m->rowptr, m->col, m->val, x_ext, scale, shift, y, u_out, m->nloc, part, g, ctrl, fl, last_pass_flags, nullptr, nullptr, list, len);
@@ -1414,6 +1472,10 @@ void launch_operator(hipStream_t st, const CsrShard* m, int es, const double* x_
       launch_block_spmv_z(st, op, x_ext, scale, shift, shift_im, y, u_out, m->nloc, partials, pstride, grid, ctrl, last_pass_flags);
     else
       launch_block_spmv(st, op, x_ext, scale, shift, y, u_out, m->nloc, partials, grid, ctrl, last_pass_flags);
+    return;
+  }
+  if (m->rc_rec) {  // one pass, real
+    launch_spmv_rows(st, row_code_view(m), x_ext, scale, shift, y, u_out, m->nloc, partials, grid, ctrl, flags, last_pass_flags, nullptr, begin);
     return;
   }
   for (int k = 0; k < m->passes; ++k) {
@@ -1468,7 +1530,7 @@ int enq_apply(eigenex_basis_s* b, int ucol, bool want_dot, bool self_norm = fals
       CsrShard* m = s.csr;
       if (self_norm) {
         {
-          ProfScope ps(c, EIGENEX_K_SPMV, (m->blocked ? 8.0 * b->es * m->nnz + 4.0 * m->nstripcols + 4.0 * m->nloc : (4.0 + 8.0 * b->es) * m->nnz + 4.0 * (m->nloc + 1)) + 32.0 * s.nd);
+          ProfScope ps(c, EIGENEX_K_SPMV, operator_bytes(m, b->es) + 32.0 * s.nd);
           launch_operator(c->stream, m, b->es, s.w, &s.ctrl->scale, b->shift, b->shift_im, s.v, s.V + (int64_t)ucol * s.ldd,
                           defer_self_norm ? s.palpha : s.partials, s.pstride, s.g_spmv, s.ctrl, s.spmv_flags, kPassSelfNorm, begin, s.g_spmv_int, halo_done);
         }
@@ -1478,7 +1540,7 @@ int enq_apply(eigenex_basis_s* b, int ucol, bool want_dot, bool self_norm = fals
         continue;
       }
       {
-        const double opbytes = m->blocked ? 8.0 * b->es * m->nnz + 4.0 * m->nstripcols + 4.0 * m->nloc : (4.0 + 8.0 * b->es) * m->nnz + 4.0 * (m->nloc + 1);
+        const double opbytes = operator_bytes(m, b->es);
         ProfScope ps(c, EIGENEX_K_SPMV, opbytes + 32.0 * s.nd + (want_dot ? 16.0 * s.nd : 0.0));
         launch_operator(c->stream, m, b->es, s.w, &s.ctrl->scale, b->shift, b->shift_im, s.v, s.V + (int64_t)ucol * s.ldd,
                         want_dot ? s.partials : nullptr, s.pstride, s.g_spmv, s.ctrl, s.spmv_flags, 0, begin, s.g_spmv_int, halo_done);
@@ -1606,8 +1668,11 @@ int lanczos_step_inline(eigenex_basis_s* b, int k, int first, int stride, int co
   // operator: beta_k, breakdown test and scale from the update's partials inside the kernel; alpha_{k+1} partials to palpha
   {
     InlineFin fn{s.pnorm, s.g_vec, kFinLanczos, b->threshold, s.beta, s.ctrl, s.hbuf + b->slot_nrm()};
-    ProfScope ps(c, EIGENEX_K_SPMV, 12.0 * m->nnz + 4.0 * (m->nloc + 1) + 32.0 * s.nd + 16.0 * s.nd);
-    if (m->rowptr64)
+    ProfScope ps(c, EIGENEX_K_SPMV, operator_bytes(m, 1) + 32.0 * s.nd + 16.0 * s.nd);
+    if (m->rc_rec)
+      launch_spmv_rows(st, row_code_view(m), s.w, nullptr, b->shift, s.v, s.V + (int64_t)(k + 1) * s.ldd, m->nloc, s.palpha, s.g_spmv, s.ctrl,
+                       s.spmv_flags, 0, &fn);
+    else if (m->rowptr64)
       launch_spmv64(st, m->rowptr64, m->col, m->val, s.w, nullptr, b->shift, s.v, s.V + (int64_t)(k + 1) * s.ldd, m->nloc, s.palpha, s.g_spmv, s.ctrl,
                     s.spmv_flags | (m->nnz >= 16 * m->nloc ? 4 : 0), 0, &fn);
     else
@@ -2591,6 +2656,14 @@ int eigenex_csr_layout(eigenex_csr_t m, int* layout) {
   return 0;
 }
 
+int eigenex_csr_encoding(eigenex_csr_t m, int* encoding) {
+  if (!m || !encoding) return fail(EIGENEX_ERR_ARG, "eigenex_csr_encoding: NULL argument");
+  *encoding = EIGENEX_ENCODING_PLAIN;
+  for (auto& s : m->sh)
+    if (s.rc_rec) *encoding = EIGENEX_ENCODING_ROW_CODES;
+  return 0;
+}
+
 int eigenex_csr_column_blocks(eigenex_csr_t m, int* passes) {
   if (!m || !passes) return fail(EIGENEX_ERR_ARG, "eigenex_csr_column_blocks: NULL argument");
   *passes = 1;
@@ -2601,6 +2674,68 @@ int eigenex_csr_column_blocks(eigenex_csr_t m, int* passes) {
 int eigenex_csr_upload_z(eigenex_context_t c, int64_t n_global, int64_t row_begin, int64_t n_rows, const int32_t* rowptr,
                          const int32_t* col_global, const double* val_interleaved, eigenex_csr_t* out) {
   return csr_upload_impl(c, n_global, row_begin, n_rows, rowptr, col_global, val_interleaved, 2, -1, out);
+}
+
+// The generator's shard in row codes.  Tables: the detection of a host upload (row_codes.hpp) on the rows that show every kind
+// of row the shard holds -- its first and last 2 n^2 rows (the rows that read the halo, and one full plane of rows behind
+// them; every row between is like a row of that plane: both z neighbours local) -- built here the way k_laplacian3d builds
+// them.  Records: the device encoder on the generated CSR, which is freed afterwards.  A shard that does not fit stays plain.
+int laplacian_row_codes(eigenex_context_s* c, int64_t n, CsrShard& s, int64_t lower_start, int64_t n_lower) {
+  const int64_t n2 = n * n;
+  RowCodeScan sc;
+  int last = -1;
+  auto sample = [&](int64_t a, int64_t b) {
+    for (int64_t r = a; r < b && sc.ok; ++r) {
+      int32_t cols[7];
+      double vals[7];
+      int len = 0;
+      auto emit = [&](int64_t cg, double v) {
+        cols[len] = (int32_t)(cg >= s.rb && cg < s.re ? cg - s.rb : cg < s.rb ? s.npad + (cg - lower_start) : s.npad + n_lower + (cg - s.re));
+        vals[len++] = v;
+      };
+      const int64_t x = r % n, yy = (r / n) % n, z = r / n2;
+      if (z > 0) emit(r - n2, -1.0);
+      if (yy > 0) emit(r - n, -1.0);
+      if (x > 0) emit(r - 1, -1.0);
+      emit(r, 6.0);
+      if (x < n - 1) emit(r + 1, -1.0);
+      if (yy < n - 1) emit(r + n, -1.0);
+      if (z < n - 1) emit(r + n2, -1.0);
+      sc.row(r - s.rb, cols, vals, len, last);
+    }
+  };
+  const int64_t head_end = std::min(s.re, s.rb + 2 * n2);
+  sample(s.rb, head_end);
+  sample(std::max(head_end, s.re - 2 * n2), s.re);
+  RowCodeTables T;
+  if (!row_code_tables(sc, T)) return 0;
+  RowCodePalette pal{};
+  pal.n = (int)T.pal_bits.size();
+  for (int i = 0; i < pal.n; ++i) pal.bits[i] = T.pal_bits[(size_t)i];
+  RowCodeSlots slots{};
+  for (int i = 0; i < T.nslots; ++i) slots.off[i] = T.off[i];
+  const int64_t nrec = row_code_rows(s.nloc);
+  unsigned int* bad = nullptr;
+  unsigned int bad_h = 0;
+  HIPCHK(hipMalloc(&bad, sizeof(unsigned int)));
+  HIPCHK(hipMemsetAsync(bad, 0, sizeof(unsigned int), c->stream));
+  HIPCHK(hipMalloc(&s.rc_rec, (size_t)(nrec * T.record_bytes())));
+  launch_encode_rows(c->stream, s.rowptr, s.rowptr64, s.col, s.val, s.nloc, nrec, slots, T.nslots, pal, T.record_bytes(),
+                     reinterpret_cast<uint8_t*>(s.rc_rec), bad);
+  HIPCHK(hipMemcpyAsync(&bad_h, bad, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  (void)hipFree(bad);
+  if (bad_h) {  // cannot happen for the stencil; the shard stays plain
+    (void)hipFree(s.rc_rec);
+    s.rc_rec = nullptr;
+    return 0;
+  }
+  set_row_code_tables(s, T);
+  CHK(upload_vec(c, &s.rc_pal, T.pal, 1));
+  for (void* p : {(void*)s.rowptr, (void*)s.rowptr64, (void*)s.col, (void*)s.val})
+    if (p) HIPCHK(hipFree(p));
+  s.rowptr = nullptr, s.rowptr64 = nullptr, s.col = nullptr, s.val = nullptr;
+  return 0;
 }
 
 int eigenex_csr_laplacian3d(eigenex_context_t c, int64_t n, eigenex_csr_t* out) {
@@ -2653,6 +2788,8 @@ int eigenex_csr_laplacian3d(eigenex_context_t c, int64_t n, eigenex_csr_t* out) 
         }())
       return cleanup(rc);
     launch_laplacian3d(c->stream, n, s.rb, s.re, lo, n_lower, s.npad, s.rowptr, s.rowptr64, s.col, s.val);
+    if (row_codes_allowed())
+      if (int rc = laplacian_row_codes(c, n, s, lo, n_lower)) return cleanup(rc);
     if (c->P > 1 && s.nloc > 0) {  // rows that read below the shard: r - n^2 < rb (and r >= n^2); above: r + n^2 >= re (and < N)
       std::vector<uint8_t> bnd((size_t)((s.nloc + kSpmvRows - 1) / kSpmvRows), 0);
       const int64_t low_end = std::min(s.re, std::max(s.rb, std::min(s.rb + n2, s.re)));            // rows [rb, low_end) may read [lo, rb)
@@ -3084,7 +3221,7 @@ int eigenex_apply(eigenex_basis_t b, int x_ref, int y_ref, double shift, double*
   CHK(halo_exchange(b, false));
   for (auto& s : b->sh) {
     CsrShard* m = s.csr;
-    ProfScope ps(c, EIGENEX_K_SPMV, (4.0 + 8.0 * b->es) * m->nnz + 4.0 * (m->nloc + 1) + 16.0 * s.nd);
+    ProfScope ps(c, EIGENEX_K_SPMV, (m->rc_rec ? operator_bytes(m, b->es) : (4.0 + 8.0 * b->es) * m->nnz + 4.0 * (m->nloc + 1)) + 16.0 * s.nd);
     launch_operator(c->stream, m, b->es, s.w, nullptr, shift, 0.0, vec_ptr(s, b->cap, b->nq, y_ref), nullptr,
                     dot ? s.partials : nullptr, s.pstride, s.g_spmv, s.ctrl_zero, s.spmv_flags, 0, nullptr, s.g_spmv_int);
     if (dot) launch_reduce(c->stream, s.partials, s.pstride, s.g_spmv, b->es, s.hbuf + b->slot_alpha(), s.ctrl_zero);

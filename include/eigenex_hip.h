@@ -262,6 +262,15 @@ int eigenex_csr_column_blocks(eigenex_csr_t csr, int* passes);
 enum { EIGENEX_LAYOUT_CSR = 0, EIGENEX_LAYOUT_COLUMN_BLOCKED = 1, EIGENEX_LAYOUT_SORTED_TILES = 2, EIGENEX_LAYOUT_DENSE_BLOCKS = 3,
        EIGENEX_LAYOUT_SPLIT_TILES = 4 };
 int eigenex_csr_layout(eigenex_csr_t csr, int* layout);
+/* how the entries of an EIGENEX_LAYOUT_CSR operator are encoded.  EIGENEX_ENCODING_ROW_CODES: a real operator in one pass
+ * whose rows use at most 16 column offsets (col - row, halo columns in local numbering) and at most 255 bitwise-distinct
+ * values -- constant-coefficient stencils, graph Laplacians, adjacency matrices -- is stored as one 8- or 16-byte record per
+ * row (a palette index per offset) instead of row pointers, columns and values; rows are still applied whole, in stored
+ * order, with the same results bit for bit.  Chosen per shard by eigenex_csr_upload / eigenex_csr_upload64 (where the
+ * automatic choice is plain CSR) and eigenex_csr_laplacian3d, never by eigenex_csr_upload_device; the environment variable
+ * EIGENEX_NO_ROW_CODES, read per upload, keeps the plain form.  Reports ROW_CODES if any local shard is row-coded. */
+enum { EIGENEX_ENCODING_PLAIN = 0, EIGENEX_ENCODING_ROW_CODES = 1 };
+int eigenex_csr_encoding(eigenex_csr_t csr, int* encoding);
 /* synthetic 7-point Laplacian on an n^3 grid generated on the device (BASELINE configs 2 and 4) */
 int eigenex_csr_laplacian3d(eigenex_context_t ctx, int64_t n, eigenex_csr_t* out);
 int eigenex_csr_destroy(eigenex_csr_t csr);
