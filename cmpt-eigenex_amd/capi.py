@@ -646,22 +646,44 @@ class Basis:
         m = min(st.nalpha, self.n_global)
         return st, H[:m, :m].T.copy()
 
-    def ritz_vectors(self, nvec: int, S):
-        """X = V S, normalised and phase-fixed.  Real S: X has the basis dtype; complex S: X is complex."""
+    @staticmethod
+    def _padded(A, ld, dtype):
+        """A (rows x cols) copied into the top of a column-major (ld x cols) array whose other rows are NaN"""
+        P = np.full((max(ld, A.shape[0]), A.shape[1]), np.nan, dtype, order="F")
+        P[: A.shape[0]] = A
+        return P
+
+    def _combine(self, nvec, S, lds, ldx, raw):
         nev = S.shape[1]
-        if np.iscomplexobj(S):
-            S = np.asfortranarray(S, np.complex128)
-            Sr, Si = np.asfortranarray(S.real), np.asfortranarray(S.imag)
-            X = np.zeros((self.n_rows, nev), np.complex128, order="F")
-            if nev:
-                _chk(lib().eigenex_ritz_vectors_complex(self.h, nvec, nev, _d(Sr), _d(Si), S.shape[0],
-                                                        X.ctypes.data_as(_dp), self.n_rows))
-            return X
-        S = np.asfortranarray(S, np.float64)
-        X = np.zeros((self.n_rows, nev), self.dtype, order="F")
+        cplx = np.iscomplexobj(S)
+        S = self._padded(S, S.shape[0] if lds is None else lds, np.complex128 if cplx else np.float64)
+        ldx = self.n_rows if ldx is None else ldx
+        # the rows n_rows..ldx of each column are a gap the library must not write: NaN sentinels (X.base holds them)
+        X = self._padded(np.zeros((self.n_rows, nev)), ldx, np.complex128 if cplx else self.dtype)
         if nev:
-            _chk(lib().eigenex_ritz_vectors(self.h, nvec, nev, _d(S), S.shape[0], X.ctypes.data_as(_dp), self.n_rows))
-        return X
+            if cplx:
+                Sr, Si = np.asfortranarray(S.real), np.asfortranarray(S.imag)
+                if raw:
+                    _chk(lib().eigenex_krylov_combine(self.h, nvec, nev, _d(Sr), _d(Si), S.shape[0], X.ctypes.data_as(_dp), ldx))
+                else:
+                    _chk(lib().eigenex_ritz_vectors_complex(self.h, nvec, nev, _d(Sr), _d(Si), S.shape[0],
+                                                            X.ctypes.data_as(_dp), ldx))
+            elif raw:
+                _chk(lib().eigenex_krylov_combine(self.h, nvec, nev, _d(S), None, S.shape[0], X.ctypes.data_as(_dp), ldx))
+            else:
+                _chk(lib().eigenex_ritz_vectors(self.h, nvec, nev, _d(S), S.shape[0], X.ctypes.data_as(_dp), ldx))
+        return X if ldx == self.n_rows else X[: self.n_rows]
+
+    def ritz_vectors(self, nvec: int, S, lds: int | None = None, ldx: int | None = None):
+        """X = V S, normalised and phase-fixed.  Real S: X has the basis dtype; complex S: X is complex.
+        lds / ldx: column strides handed to the library (default: S's rows, n_rows).  S is passed with NaN in its rows
+        past S.shape[0]; X is returned as the top n_rows of an ldx-row array whose gap rows were filled with NaN."""
+        return self._combine(nvec, S, lds, ldx, False)
+
+    def krylov_combine(self, nvec: int, C, ldc: int | None = None, ldx: int | None = None):
+        """X = V C as it is (eigenex_krylov_combine: no normalisation, no phase).  Real C: X has the basis dtype;
+        complex C: X is complex."""
+        return self._combine(nvec, C, ldc, ldx, True)
 
     def close(self):
         if self.h:
