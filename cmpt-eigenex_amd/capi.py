@@ -68,6 +68,8 @@ SIGNATURES = {
     "eigenex_context_trace": (C.c_int, [_vp, C.c_int]),
     "eigenex_context_set_halo_overlap": (C.c_int, [_vp, C.c_int]),
     "eigenex_context_trace_get": (C.c_int, [_vp, _ip, _ip, C.c_int, C.POINTER(C.c_int)]),
+    "eigenex_debug_allocations": (C.c_int, [_lp, _lp, _lp]),
+    "eigenex_debug_fail_allocation": (C.c_int, [C.c_int64]),
     "eigenex_plan_create": (C.c_int, [C.c_int64, C.c_int, C.c_int, _ip, _ip, C.POINTER(_vp)]),
     "eigenex_plan_destroy": (C.c_int, [_vp]),
     "eigenex_plan_tiles": (C.c_int, [_vp, _ip, C.POINTER(C.c_int64), _ip, C.POINTER(C.c_int64)]),

@@ -175,6 +175,11 @@ int eigenex_context_comm_info(eigenex_context_t ctx, int* comm_ranks, int* comm_
  * read the record back: same encoding as eigenex_lanczos_collectives */
 int eigenex_context_trace(eigenex_context_t ctx, int on);
 int eigenex_context_trace_get(eigenex_context_t ctx, int* ops, int* counts, int cap, int* n);
+/* test hooks, process-wide: the device and pinned-host buffers the library holds now (count, bytes) and the allocations it
+ * has made since the process started; eigenex_debug_fail_allocation(n) makes the n-th allocation from now fail with
+ * hipErrorOutOfMemory without calling the runtime (0: disarm) */
+int eigenex_debug_allocations(int64_t* live, int64_t* live_bytes, int64_t* made);
+int eigenex_debug_fail_allocation(int64_t nth);
 /* the context's hipStream_t (as void*) */
 void* eigenex_context_stream(eigenex_context_t ctx);
 
