@@ -2041,7 +2041,7 @@ void launch_spmv_z(hipStream_t s, const int32_t* rowptr, const int32_t* col, con
                    const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n,
                    double* partials, int pstride, int grid, const Ctrl* ctrl, int spmv_flags, int pass) {
   const int64_t ntiles = (n + kSpmvRows - 1) / kSpmvRows;
-  if (spmv_flags & 4)  // bit 2: long rows
+  if (spmv_flags & kSpmvLongRows)
     hipLaunchKernelGGL(k_spmv_z<true>, dim3(grid), dim3(kBlock), 0, s, rowptr, col, reinterpret_cast<const double2*>(val),
                        reinterpret_cast<const double2*>(x_ext), scale, shift_re, shift_im, reinterpret_cast<double2*>(y),
                        reinterpret_cast<double2*>(u_out), n, ntiles, partials, pstride, spmv_flags, pass, ctrl);
@@ -2076,7 +2076,7 @@ static void launch_spmv_t(hipStream_t s, const OFF* rowptr, const int32_t* col, 
 #define EIGENEX_LAUNCH_SPMV(LONG, NTV)                                                                                              \
   hipLaunchKernelGGL((k_spmv<LONG, OFF, NTV>), dim3(grid), dim3(kBlock), 0, s, rowptr, col, val, x_ext, scale, shift, y, u_out, n, \
                      ntiles, partials, spmv_flags, pass, ctrl, fin ? *fin : nofin, begin ? *begin : nobegin, tile_list)
-  if (spmv_flags & 4) {  // bit 2: long rows
+  if (spmv_flags & kSpmvLongRows) {
     if (nt) EIGENEX_LAUNCH_SPMV(true, true);
     else EIGENEX_LAUNCH_SPMV(true, false);
   } else {

@@ -139,6 +139,9 @@ void launch_reduce(hipStream_t s, const double* partials, int pstride, int nbloc
 // the previous pass), bit 1 (kPassNotLast) = store the raw row sums only (no shift, u_out, dot).
 // bit 2 (kPassSelfNorm): the partials hold ||y||^2 instead of (x*scale).y (adaptive Gram-Schmidt of the Arnoldi step)
 enum { kPassCarry = 1, kPassNotLast = 2, kPassSelfNorm = 4 };
+// `spmv_flags`: bit 0 = XCD-contiguous tiles, bit 1 = non-temporal val/col loads (both the caller's tuning), bit 2
+// (kSpmvLongRows) = the kernel variant for long rows; the host-side launchers of the CSR kernels choose it by this bit
+enum { kSpmvLongRows = 4 };
 // fin: beta_k = sqrt(sum of the update kernel's partials), breakdown test and scale = 1/beta_k taken inside this kernel
 void launch_spmv(hipStream_t s, const int32_t* rowptr, const int32_t* col, const double* val, const double* x_ext,
                  const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -364,6 +365,16 @@ struct BasisShard {
 
 // A batch of step calls recorded as a hipGraph (see enqueue_steps): replayed when the same batch is asked for again
 // from the same state with the same settings -- repeated solves of one size, e.g. Krylov time stepping.
+// where the host is in the step calls it has ENQUEUED (the device counts in Ctrl): saved, restored, copied and recorded as a whole
+struct StepCursor {
+  bool started = false;
+  int h_nvec = 0;
+  // Lanczos, alpha of the newest vector: between shards hbuf[base_fused()] holds a local, not yet all-reduced sum that travels with
+  // the next step's dots (lanczos_call); `inline` (one shard): the operator kernel's partials wait in palpha for the next dots kernel
+  bool alpha_pending = false, alpha_pending_first = false, alpha_pending_inline = false;
+  bool tail_pending = false;  // Arnoldi, one shard: the end of the last enqueued step (k_arnoldi_tail) is left to the next step's operator kernel
+  int tail_ncoef = 0;         //   number of doubles of that step's coefficient vector
+};
 struct StepGraphKey {
   int kind, started, h_nvec, ncalls, ortho_mode, nq, flags, g_vec, g_spmv, cap;
   int64_t interval;
@@ -373,15 +384,12 @@ struct StepGraphKey {
 struct StepGraph {
   StepGraphKey key;
   hipGraphExec_t exec = nullptr;
-  bool started_after = false;
-  int h_nvec_after = 0;
+  StepCursor cur_after;  // the host-side cursor behind the batch
   uint64_t last_use = 0;
   int64_t nodes = 0;
 };
 
 struct eigenex_basis_s {
-  bool tail_pending = false;  // Arnoldi, one shard: the end of the last enqueued step (k_arnoldi_tail) is left to the next step's operator kernel
-  int tail_ncoef = 0;         //   number of doubles of that step's coefficient vector
   eigenex_context_s* ctx = nullptr;
   eigenex_csr_s* csr = nullptr;
   int64_t n_global = 0;
@@ -391,18 +399,14 @@ struct eigenex_basis_s {
   int64_t interval = 1;
   int ortho_mode = EIGENEX_ORTHO_BATCHED;
   std::vector<BasisShard> sh;
-  bool started = false;
-  int h_nvec = 0;
+  StepCursor cur;
   eigenex_matvec_fn fn = nullptr;
   void* fn_user = nullptr;
   PinnedBuffer<double> pin_in, pin_out;
   PinnedBuffer<Ctrl> pin_ctrl;
   std::vector<StepGraph> graphs;
   uint64_t graph_clock = 0;
-  // Lanczos on more than one shard: alpha of the newest vector travels with the next step's dots (lanczos_call)
-  bool fuse_alpha = true;
-  bool alpha_pending = false, alpha_pending_first = false;  // hbuf[base_fused()] holds a local, not yet all-reduced alpha
-  bool alpha_pending_inline = false;  // one shard: the operator kernel's alpha partials wait in palpha for the next dots kernel
+  bool fuse_alpha = true;  // Lanczos on more than one shard: alpha of the newest vector travels with the next step's dots (lanczos_call)
   int hbuf_len() const { return 8 * maxcols + 64; }
   int base_fused() const { return 4 * maxcols + 16; }  // [alpha (2 slots), g (es*ncols), G (es*ncols)]: one all-reduce
   // offsets (in doubles) into hbuf behind the es*maxcols coefficient entries
@@ -439,10 +443,14 @@ int allreduce(eigenex_basis_s* b, int off, int n) {
   return 0;
 }
 
+// the control block a launch obeys: always zero (stand-alone primitives), the state's, the adaptive Gram-Schmidt's second pass
+enum class CtrlBlock { Zero, State, Pass2 };
+inline const Ctrl* pick_ctrl(const BasisShard& s, CtrlBlock cb) { return cb == CtrlBlock::Pass2 ? s.ctrl_pass2 : cb == CtrlBlock::State ? s.ctrl : s.ctrl_zero; }
+
 // fill the halo region of every local shard's operator-input vector
 // on_halo_stream: the exchange is issued on the context's second stream, behind ev_w_ready (the operator input is complete) and
 // followed by ev_halo_done, which the boundary launch of the operator waits for (enq_apply); else on the compute stream
-int halo_exchange(eigenex_basis_s* b, bool use_ctrl = true, bool on_halo_stream = false) {
+int halo_exchange(eigenex_basis_s* b, CtrlBlock ctrl, bool on_halo_stream = false) {
   eigenex_context_s* c = b->ctx;
   if (c->P == 1 || !b->csr) return 0;
   if (c->tracing) c->trace.push_back({EIGENEX_COLL_HALO, 0});
@@ -463,7 +471,7 @@ int halo_exchange(eigenex_basis_s* b, bool use_ctrl = true, bool on_halo_stream 
     for (auto& sg : cs->send)
       if (sg.contig_start < 0)
         launch_pack(st, bs.w, cs->send_idx + sg.offset, sg.count, bs.es, cs->sendbuf + sg.offset * bs.es,
-                    use_ctrl ? bs.ctrl : bs.ctrl_zero);
+                    pick_ctrl(bs, ctrl));
   }
   if (c->loopback) {
     for (auto& bs : b->sh) {
@@ -1171,17 +1179,28 @@ double* vec_ptr(BasisShard& s, int cap, int nq, int ref) {
   return nullptr;
 }
 
-ColumnSet colset(BasisShard& s, int first, int stride, int count, int qfirst, int nq) {
-  ColumnSet cs;
-  cs.V = s.V;
-  cs.ldv = s.ldd;
-  cs.first = first;
-  cs.stride = stride;
-  cs.count = count;
-  cs.Q = s.Q ? s.Q + (int64_t)qfirst * s.ldd : nullptr;
-  cs.ldq = s.ldd;
-  cs.nq = nq;
-  return cs;
+// Which vectors a dots/update pass runs over: basis columns first, first+stride, ... (count of them), then the
+// orthogonalizingVectors_ qfirst .. qfirst+nq
+struct Cols {
+  int first = 0, stride = 1, count = 0, qfirst = 0, nq = 0;
+  int total() const { return count + nq; }
+};
+
+ColumnSet colset(BasisShard& s, const Cols& c) {
+  return ColumnSet{s.V, s.ldd, c.first, c.stride, c.count, s.Q ? s.Q + (int64_t)c.qfirst * s.ldd : nullptr, s.ldd, c.nq};
+}
+
+// A column set swept `budget` vectors at a time: chunk(c0, sub) for every piece of the combined list (basis columns, then
+// orthogonalizing vectors), c0 = the place of its first vector in that list
+template <class F>
+int for_each_chunk(const Cols& c, int budget, F&& chunk) {
+  for (int c0 = 0; c0 < c.total(); c0 += budget) {
+    const int nc = std::min(budget, c.total() - c0);
+    const int v0 = std::min(c0, c.count), v1 = std::min(c0 + nc, c.count);
+    const int q0 = std::max(c0 - c.count, 0), q1 = std::max(c0 + nc - c.count, 0);
+    CHK(chunk(c0, Cols{c.first + v0 * c.stride, c.stride, v1 - v0, c.qfirst + q0, q1 - q0}));
+  }
+  return 0;
 }
 
 // Placement of the work vector that k_update writes in every step.  Measured (tests/probes/probe_update_placement.py,
@@ -1210,7 +1229,7 @@ int place_work_vector(eigenex_context_s* c, BasisShard& s, int capacity) {
     for (int rep = 0; rep < 2; ++rep) {
       hipError_t e = hipEventRecord(e0, c->stream);
       if (e != hipSuccess) return e;
-      launch_update(c->stream, s.start, cand, ThreeTerm{nullptr, nullptr, nullptr, nullptr}, colset(s, 0, 1, ncols, 0, 0), s.hbuf, s.nd, s.partials,
+      launch_update(c->stream, s.start, cand, ThreeTerm{nullptr, nullptr, nullptr, nullptr}, colset(s, Cols{.count = ncols}), s.hbuf, s.nd, s.partials,
                     s.g_vec, s.ctrl_zero, s.es == 2);
       if ((e = hipEventRecord(e1, c->stream)) != hipSuccess) return e;
       if ((e = hipEventSynchronize(e1)) != hipSuccess) return e;
@@ -1268,45 +1287,53 @@ int place_work_vector(eigenex_context_s* c, BasisShard& s, int capacity) {
 }
 
 // ---- enqueue helpers (all local shards, then the collective) -----------------
-// h[slot .. slot+ncols) = all-reduced dots of w0(src, tt) with the column set
-// use_ctrl: 0 = the always-zero control block (stand-alone primitives), 1 = the state's control block,
-// 2 = the second-pass control block of the adaptive Gram-Schmidt
-inline const Ctrl* pick_ctrl(const BasisShard& s, int use_ctrl) { return use_ctrl == 2 ? s.ctrl_pass2 : use_ctrl ? s.ctrl : s.ctrl_zero; }
 
-// dec (one shard): this pass is the conditional second one and its first launch takes the decision itself (InlineDecide): it runs
-// under the state's control block, later chunks under the second-pass block that it has set.  skip_reduce: the consumer kernel
-// forms the second-stage sums (InlineReduce).
-int enq_dots(eigenex_basis_s* b, int src_ref, bool three_term, int k, int first, int stride, int count, int qfirst,
-             int nq, int slot, int use_ctrl, int base = 0, const InlineDecide* dec = nullptr, bool skip_reduce = false) {
+// the recurrence of Lanczos step k, w0 = src - alpha_k u_k - beta_{k-1} u_{k-1}  (lanczos.hpp:403-408); no step: w0 = src
+ThreeTerm three_term(BasisShard& s, std::optional<int> step) {
+  if (!step) return ThreeTerm{nullptr, nullptr, nullptr, nullptr};
+  const int k = *step;
+  return ThreeTerm{s.V + (int64_t)k * s.ldd, k > 0 ? s.V + (int64_t)(k - 1) * s.ldd : nullptr, s.alpha + k, s.beta + (k > 0 ? k - 1 : 0)};
+}
+
+// hbuf[base + slot*es ..) = all-reduced dots of w0(src, step) with the column set
+struct DotsPass {
+  int src;                  // vector reference (EIGENEX_VEC_* or a basis column)
+  std::optional<int> step;  // three_term
+  Cols cols;
+  int slot = 0, base = 0;
+  CtrlBlock ctrl = CtrlBlock::State;
+  // one shard, hooks of the pass's first launch: a pending alpha is finalised inside it; this pass is the conditional second one
+  // and its first launch takes the decision itself, under the state's control block (later chunks: the block it has set)
+  const InlineFin* fin = nullptr;
+  const InlineDecide* decide = nullptr;
+  bool skip_reduce = false;  // the consumer kernel forms the second-stage sums (InlineReduce)
+};
+int enq_dots(eigenex_basis_s* b, const DotsPass& p) {
   eigenex_context_s* c = b->ctx;
-  const int ncols = count + nq;
+  const int ncols = p.cols.total();
   if (ncols <= 0) return 0;
+  const int hoff = p.base + p.slot * b->es;
   for (auto& s : b->sh) {
-    ThreeTerm tt{nullptr, nullptr, nullptr, nullptr};
-    if (three_term) tt = ThreeTerm{s.V + (int64_t)k * s.ldd, k > 0 ? s.V + (int64_t)(k - 1) * s.ldd : nullptr, s.alpha + k, s.beta + (k > 0 ? k - 1 : 0)};
-    const Ctrl* ctl = pick_ctrl(s, use_ctrl);
+    const ThreeTerm tt = three_term(s, p.step);
+    const Ctrl* ctl = pick_ctrl(s, p.ctrl);
     // k_dots keeps four per-wave accumulators per coefficient in LDS (32 B per real column, 64 B per complex one):
-    // a column set beyond kDotsMaxAcc accumulators is swept in chunks of the combined list (basis columns, then
-    // orthogonalizing vectors), each chunk writing its partials at its own offset; every h_c is an independent sum,
-    // so chunking does not touch the results
-    const int chunk = kDotsMaxAcc / b->es;
-    for (int c0 = 0; c0 < ncols; c0 += chunk) {
-      const int nc = std::min(chunk, ncols - c0);
-      const int v0 = std::min(c0, count), v1 = std::min(c0 + nc, count);
-      const int q0 = std::max(c0 - count, 0), q1 = std::max(c0 + nc - count, 0);
-      ProfScope ps(c, EIGENEX_K_DOTS, use_ctrl == 2 ? 0.0 : 8.0 * s.nd * nc + 8.0 * s.nd);  // a conditional pass books no bytes
+    // a column set beyond kDotsMaxAcc accumulators is swept in chunks, each chunk writing its partials at its own
+    // offset; every h_c is an independent sum, so chunking does not touch the results
+    CHK(for_each_chunk(p.cols, kDotsMaxAcc / b->es, [&](int c0, const Cols& sub) -> int {
+      ProfScope ps(c, EIGENEX_K_DOTS, p.ctrl == CtrlBlock::Pass2 ? 0.0 : 8.0 * s.nd * sub.total() + 8.0 * s.nd);  // a conditional pass books no bytes
       LAUNCH_BEGIN();
-      const bool decides = dec && c0 == 0;
-      launch_dots(c->stream, vec_ptr(s, b->cap, b->nq, src_ref), tt, colset(s, first + v0 * stride, stride, v1 - v0, qfirst + q0, q1 - q0),
-                  s.nd, s.partials + (int64_t)c0 * b->es * s.pstride, s.pstride, s.g_vec, decides ? s.ctrl : ctl, b->es == 2, nullptr, nullptr,
-                  nullptr, decides ? dec : nullptr);
+      const bool head = c0 == 0;
+      launch_dots(c->stream, vec_ptr(s, b->cap, b->nq, p.src), tt, colset(s, sub), s.nd, s.partials + (int64_t)c0 * b->es * s.pstride,
+                  s.pstride, s.g_vec, head && p.decide ? s.ctrl : ctl, b->es == 2, nullptr, nullptr, head ? p.fin : nullptr,
+                  head ? p.decide : nullptr);
       LAUNCHCHK("k_dots");
-    }
-    if (skip_reduce) continue;
+      return 0;
+    }));
+    if (p.skip_reduce) continue;
     ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
-    launch_reduce(c->stream, s.partials, s.pstride, s.g_vec, ncols * b->es, s.hbuf + base + slot * b->es, ctl);
+    launch_reduce(c->stream, s.partials, s.pstride, s.g_vec, ncols * b->es, s.hbuf + hoff, ctl);
   }
-  return allreduce(b, base + slot * b->es, ncols * b->es);
+  return allreduce(b, hoff, ncols * b->es);
 }
 
 // Fused-alpha Lanczos step, dots half (one collective fewer per step).  On entry hbuf[base_fused()] holds
@@ -1315,267 +1342,305 @@ int enq_dots(eigenex_basis_s* b, int src_ref, bool three_term, int k, int first,
 // are all-reduced together, then h = g - alpha_k G = V^H w0 (w0 = v - alpha_k u_k - beta_{k-1} u_{k-1},
 // lanczos.hpp:403-408) without w0 ever needing the global alpha_k before the pass.  G is computed, not assumed to be
 // e_k: dropping the alpha_k (u_c . u_k) terms would let the loss of orthogonality grow by alpha/beta per step.
-// Afterwards hbuf[0 ..) = h and alpha[k] is set, exactly what enq_update(three_term) expects.
-int enq_fused_dots(eigenex_basis_s* b, int k, int first, int stride, int count, int nq) {
+// Afterwards hbuf[0 ..) = h and alpha[k] is set, exactly what an update pass of step k expects.
+int enq_fused_dots(eigenex_basis_s* b, int k, const Cols& cols) {
   eigenex_context_s* c = b->ctx;
-  const int ncols = count + nq, es = b->es, ncoef = ncols * es;
+  const int es = b->es, ncoef = cols.total() * es;
   const int off = b->base_fused();
   for (auto& s : b->sh) {
     ThreeTerm tt{nullptr, nullptr, nullptr, nullptr};
     if (k > 0) tt = ThreeTerm{s.V + (int64_t)(k - 1) * s.ldd, nullptr, s.beta + (k - 1), s.beta + (k - 1)};  // v - beta_{k-1} u_{k-1}
-    const int chunk = kDotsMaxAcc / (2 * es);
-    for (int c0 = 0; c0 < ncols; c0 += chunk) {
-      const int nc = std::min(chunk, ncols - c0);
-      const int v0 = std::min(c0, count), v1 = std::min(c0 + nc, count);
-      const int q0 = std::max(c0 - count, 0), q1 = std::max(c0 + nc - count, 0);
-      ProfScope ps(c, EIGENEX_K_DOTS, 8.0 * s.nd * nc + 8.0 * s.nd);
+    CHK(for_each_chunk(cols, kDotsMaxAcc / (2 * es), [&](int c0, const Cols& sub) -> int {
+      ProfScope ps(c, EIGENEX_K_DOTS, 8.0 * s.nd * sub.total() + 8.0 * s.nd);
       LAUNCH_BEGIN();
-      launch_dots(c->stream, s.v, tt, colset(s, first + v0 * stride, stride, v1 - v0, q0, q1 - q0), s.nd,
-                  s.partials + (int64_t)c0 * es * s.pstride, s.pstride, s.g_vec, s.ctrl, es == 2, s.V + (int64_t)k * s.ldd,
-                  s.partials + (int64_t)(ncoef + c0 * es) * s.pstride);
+      launch_dots(c->stream, s.v, tt, colset(s, sub), s.nd, s.partials + (int64_t)c0 * es * s.pstride, s.pstride, s.g_vec, s.ctrl, es == 2,
+                  s.V + (int64_t)k * s.ldd, s.partials + (int64_t)(ncoef + c0 * es) * s.pstride);
       LAUNCHCHK("k_dots (two sources)");
-    }
+      return 0;
+    }));
     ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
     launch_reduce(c->stream, s.partials, s.pstride, s.g_vec, 2 * ncoef, s.hbuf + off + 2, s.ctrl);
   }
   CHK(allreduce(b, off, 2 + 2 * ncoef));
   for (auto& s : b->sh) {
     ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
-    launch_form_h(c->stream, s.ctrl, s.hbuf + off, ncoef, s.hbuf, s.alpha, b->alpha_pending_first ? 1 : 0);
+    launch_form_h(c->stream, s.ctrl, s.hbuf + off, ncoef, s.hbuf, s.alpha, b->cur.alpha_pending_first ? 1 : 0);
   }
-  b->alpha_pending = false;
+  b->cur.alpha_pending = false;
   return 0;
 }
 
-// dst = w0(src, tt) - sum h[slot+c]*col_c ; hbuf[slot_nrm] = all-reduced ||dst||^2 (if want_norm)
 // one shard and no communicator: nothing is all-reduced between a partial sum and the decision taken from it, so the
 // second-stage sum and the decision share one launch (k_reduce_fin)
 inline bool decides_locally(const eigenex_basis_s* b) { return b->ctx->P == 1 && !b->ctx->comm; }
 
-// fin_mode >= 0 (a FinNormMode; only with want_norm, the state's control block and decides_locally): the norm's
-// second-stage sum also takes the step decision
-// norm_to_pnorm (one shard): the ||dst||^2 partial sums go to the hand-over buffer pnorm instead of the dots partials' buffer (a
-// consumer kernel adds them itself while the next dots pass is already writing its partials); reduce_inline: the second-stage
-// sums of the preceding dots pass are formed inside the kernel (InlineReduce) -- the caller has skipped k_reduce
-int enq_update(eigenex_basis_s* b, int src_ref, int dst_ref, bool three_term, int k, int first, int stride, int count,
-               int qfirst, int nq, int slot, bool want_norm, int use_ctrl, int base = 0, int nrm_slot = -1, int fin_mode = -1,
-               bool norm_to_pnorm = false, bool reduce_inline = false) {
-  if (nrm_slot < 0) nrm_slot = b->slot_nrm();
+// What becomes of ||dst||^2, which the update kernel leaves as per-workgroup partial sums.  Slot: second-stage sum into
+// hbuf[nrm_slot], all-reduced.  Decide (decides_locally, the state's control block): the second-stage sum also takes the step
+// decision `decide`.  Partials (one shard): they go to the hand-over buffer pnorm instead of the dots partials' buffer; a
+// consumer kernel adds them itself while the next dots pass is already writing its partials.
+enum class NormOut { None, Slot, Decide, Partials };
+// dst = w0(src, step) - sum h[slot+c]*col_c, h = hbuf + base
+struct UpdatePass {
+  int src, dst;
+  std::optional<int> step;
+  Cols cols;
+  int slot = 0, base = 0;
+  CtrlBlock ctrl = CtrlBlock::State;
+  NormOut norm = NormOut::None;
+  std::optional<int> nrm_slot;    // Slot, Decide: where the sum goes (default: slot_nrm())
+  FinNormMode decide = kFinInit;  // Decide
+  bool reduce_inline = false;  // the preceding dots pass skipped k_reduce: its second-stage sums are formed inside the kernel (InlineReduce)
+};
+int enq_update(eigenex_basis_s* b, const UpdatePass& p) {
   eigenex_context_s* c = b->ctx;
-  const int ncols = count + nq;
+  const int nrm_slot = p.nrm_slot.value_or(b->slot_nrm());
+  const int ncols = p.cols.total(), hoff = p.base + p.slot * b->es;
   for (auto& s : b->sh) {
-    ThreeTerm tt{nullptr, nullptr, nullptr, nullptr};
-    if (three_term) tt = ThreeTerm{s.V + (int64_t)k * s.ldd, k > 0 ? s.V + (int64_t)(k - 1) * s.ldd : nullptr, s.alpha + k, s.beta + (k > 0 ? k - 1 : 0)};
-    const Ctrl* ctl = pick_ctrl(s, use_ctrl);
+    const Ctrl* ctl = pick_ctrl(s, p.ctrl);
     {
-      ProfScope ps(c, EIGENEX_K_UPDATE, use_ctrl == 2 ? 0.0 : 8.0 * s.nd * ncols + 24.0 * s.nd + (three_term ? 32.0 * s.nd : 0.0));
+      ProfScope ps(c, EIGENEX_K_UPDATE, p.ctrl == CtrlBlock::Pass2 ? 0.0 : 8.0 * s.nd * ncols + 24.0 * s.nd + (p.step ? 32.0 * s.nd : 0.0));
       LAUNCH_BEGIN();
-      const InlineReduce red{s.partials, s.pstride, s.g_vec, ncols * b->es, s.hbuf + base + slot * b->es};
-      launch_update(c->stream, vec_ptr(s, b->cap, b->nq, src_ref), vec_ptr(s, b->cap, b->nq, dst_ref), tt,
-                    colset(s, first, stride, count, qfirst, nq), s.hbuf + base + slot * b->es, s.nd, norm_to_pnorm ? s.pnorm : s.partials, s.g_vec, ctl,
-                    b->es == 2, reduce_inline ? &red : nullptr);
+      const InlineReduce red{s.partials, s.pstride, s.g_vec, ncols * b->es, s.hbuf + hoff};
+      launch_update(c->stream, vec_ptr(s, b->cap, b->nq, p.src), vec_ptr(s, b->cap, b->nq, p.dst), three_term(s, p.step), colset(s, p.cols),
+                    s.hbuf + hoff, s.nd, p.norm == NormOut::Partials ? s.pnorm : s.partials, s.g_vec, ctl, b->es == 2,
+                    p.reduce_inline ? &red : nullptr);
       LAUNCHCHK("k_update");
     }
-    if (want_norm) {
-      ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
-      if (fin_mode >= 0)
-        launch_reduce_fin(c->stream, s.partials, s.pstride, s.g_vec, 1, s.hbuf + nrm_slot, s.ctrl, fin_mode, s.beta, b->threshold);
-      else
-        launch_reduce(c->stream, s.partials, s.pstride, s.g_vec, 1, s.hbuf + nrm_slot, ctl);
-    }
+    if (p.norm != NormOut::Slot && p.norm != NormOut::Decide) continue;
+    ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
+    if (p.norm == NormOut::Decide)
+      launch_reduce_fin(c->stream, s.partials, s.pstride, s.g_vec, 1, s.hbuf + nrm_slot, s.ctrl, p.decide, s.beta, b->threshold);
+    else
+      launch_reduce(c->stream, s.partials, s.pstride, s.g_vec, 1, s.hbuf + nrm_slot, ctl);
   }
-  return want_norm && fin_mode < 0 ? allreduce(b, nrm_slot, 1) : 0;
+  return p.norm == NormOut::Slot ? allreduce(b, nrm_slot, 1) : 0;
+}
+
+// the start of an Arnoldi step as the operator kernel takes it, behind the end of the step that added vector tail_k (if any);
+// the one place that knows where k_arnoldi_tail's operands are
+InlineArnoldiBegin arnoldi_hook(eigenex_basis_s* b, std::optional<int> tail_k) {
+  BasisShard& s = b->sh[0];
+  return InlineArnoldiBegin{s.ctrl, b->threshold, b->n_global, b->cap, s.H, b->ldh, b->es, tail_k.value_or(-1), s.pnorm, s.g_vec,
+                            s.ctrl_pass2, s.hbuf, s.hbuf + b->base_h2(), b->cur.tail_ncoef, s.hbuf + b->slot_nrm_first(), s.hbuf + b->slot_nrm()};
+}
+// the end of an Arnoldi step of the adaptive scheme on one shard as a launch of its own
+void launch_tail(eigenex_basis_s* b, int ncoef) {
+  const InlineArnoldiBegin a = arnoldi_hook(b, std::nullopt);
+  launch_arnoldi_tail(b->ctx->stream, a.tail_partials, a.tail_nblocks, a.ctrl, a.pass2, a.h, a.h2, ncoef, a.nrm2_first, a.nrm2_final, a.H, a.ldh, a.es);
 }
 
 // Gram-Schmidt of the vector in src against the selected columns, result in dst,
 // ||dst||^2 in hbuf[slot_nrm].  Batched: one dots pass + one update pass.
-// Sequential: the reference's order, one vector at a time; q_first: orthogonalizing
-// vectors before the basis vectors (Arnoldi, arnoldi.hpp:373-383) or after (Lanczos,
-// lanczos.hpp:416-425).
-// norm_before: hbuf[slot_nrm_before] holds the all-reduced ||src||^2 (adaptive scheme only)
-// fin_mode (a FinNormMode) names the decision the caller takes from the norm; when it can ride on the norm's second
-// stage (*fin_merged = true) the caller must not launch k_fin_norm itself
-int enq_orthogonalize(eigenex_basis_s* b, int src_ref, int dst_ref, bool three_term, int k, int first, int stride,
-                      int count, int nq, bool q_first, bool norm_before = false, int fin_mode = -1, bool* fin_merged = nullptr,
-                      bool fused_alpha = false, bool before_in_palpha = false, bool defer_tail = false) {
-  const int merge = (fin_mode >= 0 && fin_merged && decides_locally(b)) ? fin_mode : -1;
+// Sequential: the reference's order, one vector at a time.
+struct OrthoPass {
+  int src, dst;
+  std::optional<int> step;  // Lanczos: the recurrence of step k (three_term) is folded into the first pass
+  Cols cols;
+  bool q_first = false;  // sequential: orthogonalizing vectors first (Arnoldi, arnoldi.hpp:373-383) or last (Lanczos, lanczos.hpp:416-425)
+  // the decision the caller takes from the norm; when it rides on the norm's second stage (*fin_merged = true) the caller
+  // must not launch k_fin_norm itself
+  std::optional<FinNormMode> decide;
+  bool fused_alpha = false;  // Lanczos on several shards: alpha_k rides on the dots' all-reduce (enq_fused_dots)
+  // adaptive scheme only, ||src||^2: all-reduced in hbuf[slot_nrm_before], or (one shard) still the operator's partial sums in palpha
+  enum class Before { Unknown, Slot, Palpha } before = Before::Unknown;
+  bool defer_tail = false;  // adaptive Arnoldi on one shard: the next call's operator kernel may take the end of this step
+};
+int enq_orthogonalize(eigenex_basis_s* b, const OrthoPass& p, bool* fin_merged = nullptr) {
+  const Cols& cols = p.cols;
+  const bool local = fin_merged && decides_locally(b);
+  const std::optional<FinNormMode> merge = local ? p.decide : std::nullopt;
   if (fin_merged) *fin_merged = false;
+  // the update that leaves the final norm, with the caller's decision riding on its second stage where it can
+  auto closing = [&](UpdatePass u) {
+    u.norm = merge ? NormOut::Decide : NormOut::Slot, u.decide = merge.value_or(kFinInit);
+    return u;
+  };
   int mode = b->ortho_mode;
-  if (mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE && (three_term || count + nq == 0)) mode = EIGENEX_ORTHO_BATCHED;
-  if (mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE && !norm_before) mode = EIGENEX_ORTHO_BATCHED_TWICE;
-  if (mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE && fin_mode == kFinArnoldi && fin_merged && decides_locally(b)) {
+  if (mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE && (p.step || cols.total() == 0)) mode = EIGENEX_ORTHO_BATCHED;
+  if (mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE && p.before == OrthoPass::Before::Unknown) mode = EIGENEX_ORTHO_BATCHED_TWICE;
+  const int h2 = b->base_h2();
+  if (mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE) {
     // one shard: the tiny launches around the conditional second pass are taken by their consumers (r3: 12 -> 10 -> 6/7 launches
     // per step): the decision by the second pass's dots kernel (InlineDecide), that pass's second-stage sums by its update kernel
     // (InlineReduce), the end of the step (k_arnoldi_tail) by the NEXT step's operator kernel (InlineArnoldiBegin.tail_k) unless
     // this is the last call of a batch or the next call cannot take it.  The caller launches neither k_fin_norm nor k_arnoldi_end.
+    const bool small_merged = p.decide == kFinArnoldi && local;
     hipStream_t st = b->ctx->stream;
-    BasisShard& s = b->sh[0];
-    const int ncoef = (count + nq) * b->es;
+    BasisShard& s0 = b->sh[0];
+    const int ncoef = cols.total() * b->es;
     static const bool inline_off = std::getenv("EIGENEX_NO_INLINE_FIN") != nullptr;
-    const bool inline_small = ncoef <= kInlineReduceMaxCoef && !inline_off;
-    CHK(enq_dots(b, src_ref, false, 0, first, stride, count, 0, nq, 0, 1));
-    CHK(enq_update(b, src_ref, dst_ref, false, 0, first, stride, count, 0, nq, 0, false, 1, 0, -1, -1, /*norm_to_pnorm=*/true));
-    if (inline_small) {
-      const InlineDecide dec{s.ctrl_pass2, s.pnorm, s.g_vec, before_in_palpha ? s.palpha : nullptr, s.g_spmv, 0.5,
-                             s.hbuf + b->slot_nrm_first(), s.hbuf + b->slot_nrm_before()};
-      CHK(enq_dots(b, dst_ref, false, 0, first, stride, count, 0, nq, 0, 2, b->base_h2(), &dec, /*skip_reduce=*/true));
-      CHK(enq_update(b, dst_ref, dst_ref, false, 0, first, stride, count, 0, nq, 0, false, 2, b->base_h2(), -1, -1, true, /*reduce_inline=*/true));
-    } else {
-      launch_reduce_decide(st, s.pnorm, s.g_vec, s.hbuf + b->slot_nrm_first(), s.ctrl, s.ctrl_pass2, s.hbuf + b->slot_nrm_before(), 0.5,
-                           before_in_palpha ? s.palpha : nullptr, s.g_spmv);
-      CHK(enq_dots(b, dst_ref, false, 0, first, stride, count, 0, nq, 0, 2, b->base_h2()));
-      CHK(enq_update(b, dst_ref, dst_ref, false, 0, first, stride, count, 0, nq, 0, false, 2, b->base_h2(), -1, -1, true));
-    }
-    if (defer_tail && inline_small) {
-      b->tail_pending = true;
-      b->tail_ncoef = ncoef;
-    } else {
-      launch_arnoldi_tail(st, s.pnorm, s.g_vec, s.ctrl, s.ctrl_pass2, s.hbuf, s.hbuf + b->base_h2(), ncoef,
-                          s.hbuf + b->slot_nrm_first(), s.hbuf + b->slot_nrm(), s.H, b->ldh, b->es);
-    }
-    *fin_merged = true;
-    return 0;
-  }
-  if (mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE) {
-    hipStream_t st = b->ctx->stream;
-    CHK(enq_dots(b, src_ref, false, 0, first, stride, count, 0, nq, 0, 1));
-    CHK(enq_update(b, src_ref, dst_ref, false, 0, first, stride, count, 0, nq, 0, true, 1, 0, b->slot_nrm_first()));
-    for (auto& s : b->sh)
-      launch_decide_second_pass(st, s.ctrl, s.ctrl_pass2, s.hbuf + b->slot_nrm_before(), s.hbuf + b->slot_nrm_first(), 0.5);
+    const bool inline_small = small_merged && ncoef <= kInlineReduceMaxCoef && !inline_off;
+    const NormOut norm = small_merged ? NormOut::Partials : NormOut::Slot;
+    CHK(enq_dots(b, {.src = p.src, .cols = cols}));
+    CHK(enq_update(b, {.src = p.src, .dst = p.dst, .cols = cols, .norm = norm, .nrm_slot = b->slot_nrm_first()}));
     // second pass: enqueued always, executed only when the criterion asked for it (its collectives run on stale
     // data otherwise and their results are ignored)
-    CHK(enq_dots(b, dst_ref, false, 0, first, stride, count, 0, nq, 0, 2, b->base_h2()));
-    CHK(enq_update(b, dst_ref, dst_ref, false, 0, first, stride, count, 0, nq, 0, true, 2, b->base_h2(), b->slot_nrm_second()));
-    for (auto& s : b->sh) {
-      launch_add_small(st, s.hbuf, s.hbuf + b->base_h2(), (count + nq) * b->es, s.ctrl_pass2);
-      launch_select_norm(st, s.ctrl_pass2, s.hbuf + b->slot_nrm_first(), s.hbuf + b->slot_nrm_second(), s.hbuf + b->slot_nrm());
+    DotsPass dots2{.src = p.dst, .cols = cols, .base = h2, .ctrl = CtrlBlock::Pass2};
+    UpdatePass update2{.src = p.dst, .dst = p.dst, .cols = cols, .base = h2, .ctrl = CtrlBlock::Pass2, .norm = norm, .nrm_slot = b->slot_nrm_second()};
+    const InlineDecide dec{s0.ctrl_pass2, s0.pnorm, s0.g_vec, p.before == OrthoPass::Before::Palpha ? s0.palpha : nullptr, s0.g_spmv, 0.5,
+                           s0.hbuf + b->slot_nrm_first(), s0.hbuf + b->slot_nrm_before()};
+    if (inline_small)
+      dots2.decide = &dec, dots2.skip_reduce = true, update2.reduce_inline = true;
+    else if (small_merged)
+      launch_reduce_decide(st, dec.after_partials, dec.after_n, dec.nrm2_first, s0.ctrl, dec.pass2, dec.nrm2_before, dec.eta2, dec.before_partials, dec.before_n);
+    else
+      for (auto& s : b->sh) launch_decide_second_pass(st, s.ctrl, s.ctrl_pass2, s.hbuf + b->slot_nrm_before(), s.hbuf + b->slot_nrm_first(), dec.eta2);
+    CHK(enq_dots(b, dots2));
+    CHK(enq_update(b, update2));
+    if (!small_merged) {
+      for (auto& s : b->sh) {
+        launch_add_small(st, s.hbuf, s.hbuf + h2, ncoef, s.ctrl_pass2);
+        launch_select_norm(st, s.ctrl_pass2, s.hbuf + b->slot_nrm_first(), s.hbuf + b->slot_nrm_second(), s.hbuf + b->slot_nrm());
+      }
+    } else if (p.defer_tail && inline_small) {
+      b->cur.tail_pending = true;
+      b->cur.tail_ncoef = ncoef;
+    } else {
+      launch_tail(b, ncoef);
     }
+    if (small_merged) *fin_merged = true;
     return 0;
   }
   if (mode == EIGENEX_ORTHO_BATCHED || mode == EIGENEX_ORTHO_BATCHED_TWICE) {
-    const bool twice = mode == EIGENEX_ORTHO_BATCHED_TWICE && count + nq > 0;
-    if (fused_alpha)  // Lanczos on several shards: alpha_k rides on this all-reduce (enq_fused_dots)
-      CHK(enq_fused_dots(b, k, first, stride, count, nq));
+    const bool twice = mode == EIGENEX_ORTHO_BATCHED_TWICE && cols.total() > 0;
+    if (p.fused_alpha)
+      CHK(enq_fused_dots(b, *p.step, cols));
     else
-      CHK(enq_dots(b, src_ref, three_term, k, first, stride, count, 0, nq, 0, true));
-    CHK(enq_update(b, src_ref, dst_ref, three_term, k, first, stride, count, 0, nq, 0, !twice, true, 0, -1, twice ? -1 : merge));
+      CHK(enq_dots(b, {.src = p.src, .step = p.step, .cols = cols}));
+    const UpdatePass first{.src = p.src, .dst = p.dst, .step = p.step, .cols = cols};
     if (!twice) {
-      if (merge >= 0) *fin_merged = true;
+      CHK(enq_update(b, closing(first)));
+      if (merge) *fin_merged = true;
       return 0;
     }
+    CHK(enq_update(b, first));
     // second pass on the result itself ("twice is enough"): h += V^H w, w -= V (V^H w)
-    CHK(enq_dots(b, dst_ref, false, 0, first, stride, count, 0, nq, 0, true, b->base_h2()));
-    CHK(enq_update(b, dst_ref, dst_ref, false, 0, first, stride, count, 0, nq, 0, true, true, b->base_h2()));
-    for (auto& s : b->sh) launch_add_small(b->ctx->stream, s.hbuf, s.hbuf + b->base_h2(), (count + nq) * b->es, s.ctrl);
+    CHK(enq_dots(b, {.src = p.dst, .cols = cols, .base = h2}));
+    CHK(enq_update(b, {.src = p.dst, .dst = p.dst, .cols = cols, .base = h2, .norm = NormOut::Slot}));
+    for (auto& s : b->sh) launch_add_small(b->ctx->stream, s.hbuf, s.hbuf + h2, cols.total() * b->es, s.ctrl);
     return 0;
   }
-  // sequential modified Gram-Schmidt
-  const int total = count + nq;
-  CHK(enq_update(b, src_ref, dst_ref, three_term, k, 0, 1, 0, 0, 0, 0, total == 0, true, 0, -1, total == 0 ? merge : -1));
-  if (merge >= 0) *fin_merged = true;  // the last update below (or the one above) carries the decision
-  int done = 0;
-  auto one_q = [&](int q) -> int {
-    const int slot = count + q;
-    CHK(enq_dots(b, dst_ref, false, 0, 0, 1, 0, q, 1, slot, true));
-    ++done;
-    return enq_update(b, dst_ref, dst_ref, false, 0, 0, 1, 0, q, 1, slot, done == total, true, 0, -1, done == total ? merge : -1);
+  // sequential modified Gram-Schmidt: the last update (or the recurrence alone) leaves the norm and carries the decision
+  int left = cols.total();
+  const UpdatePass recurrence{.src = p.src, .dst = p.dst, .step = p.step};
+  CHK(enq_update(b, left == 0 ? closing(recurrence) : recurrence));
+  if (merge) *fin_merged = true;
+  auto one = [&](const Cols& vec, int slot) -> int {
+    CHK(enq_dots(b, {.src = p.dst, .cols = vec, .slot = slot}));
+    const UpdatePass u{.src = p.dst, .dst = p.dst, .cols = vec, .slot = slot};
+    return enq_update(b, --left == 0 ? closing(u) : u);
   };
-  auto one_v = [&](int i) -> int {
-    const int slot = i;
-    CHK(enq_dots(b, dst_ref, false, 0, first + i * stride, 1, 1, 0, 0, slot, true));
-    ++done;
-    return enq_update(b, dst_ref, dst_ref, false, 0, first + i * stride, 1, 1, 0, 0, slot, done == total, true, 0, -1, done == total ? merge : -1);
+  auto all_q = [&]() -> int {
+    for (int q = 0; q < cols.nq; ++q) CHK(one(Cols{.qfirst = q, .nq = 1}, cols.count + q));
+    return 0;
   };
-  if (q_first)
-    for (int q = 0; q < nq; ++q) CHK(one_q(q));
-  for (int i = 0; i < count; ++i) CHK(one_v(i));
-  if (!q_first)
-    for (int q = 0; q < nq; ++q) CHK(one_q(q));
-  return 0;
+  if (p.q_first) CHK(all_q());
+  for (int i = 0; i < cols.count; ++i) CHK(one(Cols{.first = cols.first + i * cols.stride, .count = 1}, i));
+  return p.q_first ? 0 : all_q();
 }
 
 RowCodeView row_code_view(const CsrShard* m) { return RowCodeView{m->rc_rec, m->rc_pal, m->rc_npal, m->rc_bytes, m->rc_slots}; }
 // bytes of the operator itself that one application reads (the profile's per-kernel traffic)
+double csr_bytes(const CsrShard* m, int es) { return (4.0 + 8.0 * es) * m->nnz + 4.0 * (m->nloc + 1); }
 double operator_bytes(const CsrShard* m, int es) {
   if (m->rc_rec) return (double)m->rc_bytes * row_code_rows(m->nloc) + 8.0 * m->rc_npal;
   if (m->blocked) return 8.0 * es * m->nnz + 4.0 * m->nstripcols + 4.0 * m->nloc;
-  return (4.0 + 8.0 * es) * m->nnz + 4.0 * (m->nloc + 1);
+  return csr_bytes(m, es);
+}
+// long rows (16 stored entries per row or more on average): the CSR kernels have a variant for them (kSpmvLongRows) and
+// the operator gets twice the workgroups per CU (eigenex_basis_create)
+inline bool has_long_rows(const CsrShard* m) { return m->nnz >= 16 * m->nloc; }
+inline int long_rows_flag(const CsrShard* m) { return has_long_rows(m) ? kSpmvLongRows : 0; }
+
+// one operator application on one shard, y = (A + shift) (x*scale)
+struct OperatorPass {
+  const double* x;      // operator input, halo slots filled
+  const double* scale;  // device factor applied to it (nullptr: none, or InlineFin supplies it)
+  double shift = 0.0, shift_im = 0.0;
+  double* y;
+  double* u_out = nullptr;     // x*scale, optional
+  double* partials = nullptr;  // per-workgroup partial dots (x*scale).y, optional
+  const Ctrl* ctrl;
+  int pass_flags = 0;  // of the last pass: 0 or kPassSelfNorm
+  const InlineFin* fin = nullptr;             // one-pass real CSR only (inlines_fin)
+  const InlineArnoldiBegin* begin = nullptr;  // operator kernels that have the hook only (inline_begin_ok)
+  hipEvent_t halo_done = nullptr;  // the launches that read halo slots wait for it (the halo exchange is on its way on the other stream)
+};
+
+struct TileList {  // the 256-row tiles one launch covers (none: all)
+  const int32_t* tiles;
+  int64_t len;
+};
+// A one-pass real CSR shard, all tiles or a list of them: row codes, 64-bit or 32-bit row pointers.
+// The long-rows bit as it has always been passed: k_spmv_rows has no long-rows variant and never reads it; its launch gets the
+// bit with a tile list and does not get it without one.
+void launch_csr_one_pass(hipStream_t st, const BasisShard& s, const OperatorPass& p, int grid, double* partials, TileList tl = {nullptr, 0}) {
+  const CsrShard* m = s.csr;
+  const int flags = s.spmv_flags | (!m->rc_rec || tl.tiles ? long_rows_flag(m) : 0);
+  if (m->rc_rec)
+    launch_spmv_rows(st, row_code_view(m), p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, partials, grid, p.ctrl, flags, p.pass_flags, p.fin,
+                     p.begin, tl.tiles, tl.len);
+  else if (m->rowptr64)
+    launch_spmv64(st, m->rowptr64, m->col, m->val, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, partials, grid, p.ctrl, flags, p.pass_flags,
+                  p.fin, p.begin, tl.tiles, tl.len);
+  else
+    launch_spmv(st, m->rowptr, m->col, m->val, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, partials, grid, p.ctrl, flags, p.pass_flags, p.fin,
+                p.begin, tl.tiles, tl.len);
 }
 
-// one operator application on one shard: a launch per column-block pass, the row sums carried in y
-// grid_int > 0 (operators with interior / boundary tile lists): two launches, grid_int and grid - grid_int workgroups, their partial
-// dots side by side; halo_done: the second launch waits for it (the halo exchange is on its way on the other stream)
-void launch_operator(hipStream_t st, const CsrShard* m, int es, const double* x_ext, const double* scale, double shift,
-                     double shift_im, double* y, double* u_out, double* partials, int pstride, int grid, const Ctrl* ctrl,
-                     int flags, int last_pass_flags = 0, const InlineArnoldiBegin* begin = nullptr, int grid_int = 0,
-                     hipEvent_t halo_done = nullptr) {
+// a launch per column-block pass, the row sums carried in y; s.g_spmv workgroups = partial dots.  Operators with interior /
+// boundary tile lists: two launches, s.g_spmv_int and the remaining workgroups, their partial dots side by side
+void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p) {
+  const CsrShard* m = s.csr;
+  const int es = s.es, grid = s.g_spmv;
   if (m->tiles_split && !m->split && !m->sorted && !m->blocked && m->passes == 1 && es == 1) {
-    const int fl = flags | (m->nnz >= 16 * m->nloc ? 4 : 0);
-    const int g2 = grid - grid_int;
-    auto go = [&](const int32_t* list, int64_t len, int g, double* part) {
-      if (len <= 0 || g <= 0) return;
-      if (m->rc_rec)
-        launch_spmv_rows(st, row_code_view(m), x_ext, scale, shift, y, u_out, m->nloc, part, g, ctrl, fl, last_pass_flags, nullptr, nullptr, list, len);
-      else if (m->rowptr64)
-        launch_spmv64(st, m->rowptr64, m->col, m->val, x_ext, scale, shift, y, u_out, m->nloc, part, g, ctrl, fl, last_pass_flags, nullptr, nullptr, list, len);
-      else
-        launch_spmv(st, m->rowptr, m->col, m->val, x_ext, scale, shift, y, u_out, m->nloc, part, g, ctrl, fl, last_pass_flags, nullptr, nullptr, list, len);
-    };
-    go(m->tile_int, m->n_tile_int, grid_int, partials);
-    if (halo_done) (void)hipStreamWaitEvent(st, halo_done, 0);
-    go(m->tile_bnd, m->n_tile_bnd, g2, partials ? partials + grid_int : nullptr);
+    // (tile lists exist between shards only, the InlineFin / InlineArnoldiBegin hooks on one shard only: none is set here)
+    const int g_int = s.g_spmv_int, g_bnd = grid - g_int;
+    if (m->n_tile_int > 0 && g_int > 0) launch_csr_one_pass(st, s, p, g_int, p.partials, {m->tile_int, m->n_tile_int});
+    if (p.halo_done) (void)hipStreamWaitEvent(st, p.halo_done, 0);
+    if (m->n_tile_bnd > 0 && g_bnd > 0) launch_csr_one_pass(st, s, p, g_bnd, p.partials ? p.partials + g_int : nullptr, {m->tile_bnd, m->n_tile_bnd});
     return;
   }
-  if (halo_done) (void)hipStreamWaitEvent(st, halo_done, 0);  // layouts that are not split: everything behind the exchange
+  if (p.halo_done) (void)hipStreamWaitEvent(st, p.halo_done, 0);  // layouts that are not split: everything behind the exchange
   if (m->split) {
     const SplitOperatorView op{m->sp_wg, reinterpret_cast<const int4*>(m->sp_chunk.get()), m->sp_cp, m->val, m->sp_groups, m->tile_rows,
                                m->s_nlow, m->npad, m->nloc, m->sp_part, m->npad};
     if (es == 2)
-      launch_spmv_split_z(st, op, x_ext, scale, shift, shift_im, y, u_out, m->nloc, partials, pstride, ctrl, last_pass_flags);
+      launch_spmv_split_z(st, op, p.x, p.scale, p.shift, p.shift_im, p.y, p.u_out, m->nloc, p.partials, s.pstride, p.ctrl, p.pass_flags);
     else
-      launch_spmv_split(st, op, x_ext, scale, shift, y, u_out, m->nloc, partials, ctrl, last_pass_flags, begin);
+      launch_spmv_split(st, op, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, p.ctrl, p.pass_flags, p.begin);
     return;
   }
   if (m->sorted) {
     const SortedOperatorView op{m->s_base, m->s_cp, m->val, m->s_off, m->nslices, m->tile_rows, m->s_width, m->s_nlow, m->npad, m->nloc};
-    launch_spmv_sorted(st, op, x_ext, scale, shift, y, u_out, m->nloc, partials, ctrl, last_pass_flags);
+    launch_spmv_sorted(st, op, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, p.ctrl, p.pass_flags);
     return;
   }
   if (m->blocked) {
     const BlockOperatorView op{m->bval, m->gent, m->gcol, m->cols, m->grow0, m->rowgrp};
     if (es == 2)
-      launch_block_spmv_z(st, op, x_ext, scale, shift, shift_im, y, u_out, m->nloc, partials, pstride, grid, ctrl, last_pass_flags);
+      launch_block_spmv_z(st, op, p.x, p.scale, p.shift, p.shift_im, p.y, p.u_out, m->nloc, p.partials, s.pstride, grid, p.ctrl, p.pass_flags);
     else
-      launch_block_spmv(st, op, x_ext, scale, shift, y, u_out, m->nloc, partials, grid, ctrl, last_pass_flags);
+      launch_block_spmv(st, op, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid, p.ctrl, p.pass_flags);
     return;
   }
-  if (m->rc_rec) {  // one pass, real
-    launch_spmv_rows(st, row_code_view(m), x_ext, scale, shift, y, u_out, m->nloc, partials, grid, ctrl, flags, last_pass_flags, nullptr, begin);
+  if (m->rc_rec || (m->passes == 1 && es == 1)) {
+    launch_csr_one_pass(st, s, p, grid, p.partials);
     return;
   }
-  for (int k = 0; k < m->passes; ++k) {
+  const int flags = s.spmv_flags | long_rows_flag(m);
+  for (int k = 0; k < m->passes; ++k) {  // complex, or real in several column blocks
     const bool last = k == m->passes - 1;
-    const int pass = (k > 0 ? kPassCarry : 0) | (last ? last_pass_flags : kPassNotLast);
+    const int pass = (k > 0 ? kPassCarry : 0) | (last ? p.pass_flags : kPassNotLast);
     const int32_t* rp = m->rowptr + (int64_t)k * (m->nloc + 1);
     if (es == 2)
-      launch_spmv_z(st, rp, m->col, m->val, x_ext, scale, shift, shift_im, y, u_out, m->nloc, last ? partials : nullptr, pstride,
-                    grid, ctrl, flags | (m->nnz >= 16 * m->nloc ? 4 : 0), pass);
-    else if (m->rowptr64)
-      launch_spmv64(st, m->rowptr64, m->col, m->val, x_ext, scale, shift, y, u_out, m->nloc, partials, grid, ctrl,
-                    flags | (m->nnz >= 16 * m->nloc ? 4 : 0), pass, nullptr, begin);
+      launch_spmv_z(st, rp, m->col, m->val, p.x, p.scale, p.shift, p.shift_im, p.y, p.u_out, m->nloc, last ? p.partials : nullptr, s.pstride,
+                    grid, p.ctrl, flags, pass);
     else
-      launch_spmv(st, rp, m->col, m->val, x_ext, scale, shift, y, u_out, m->nloc, last ? partials : nullptr, grid, ctrl,
-                  flags | (m->nnz >= 16 * m->nloc ? 4 : 0), pass, nullptr, m->passes == 1 ? begin : nullptr);
+      launch_spmv(st, rp, m->col, m->val, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, last ? p.partials : nullptr, grid, p.ctrl, flags, pass);
   }
 }
 
-// v = (A + shift) * (w*scale), basis column `ucol` = w*scale, optional alpha = u.v -> hbuf[slot_alpha]
-// Returns 1 in *skipped if the device had already stopped (host-operator path only).
-// self_norm (instead of want_dot, device operators only): hbuf[slot_nrm_before] = all-reduced ||v||^2
-// alpha_mode (a FinAlphaMode, with want_dot): as for enq_orthogonalize, *fin_merged tells the caller that k_fin_alpha
-// has been taken care of
-// defer_alpha (with want_dot, several shards): the shard's partial alpha is only summed locally into hbuf[base_fused()];
-// the all-reduce and k_fin_alpha happen with the next step's dots (enq_fused_dots)
 // can the operator kernel of this state take the start of an Arnoldi step itself (InlineArnoldiBegin)?  One shard that decides
 // locally, and an operator kernel that has the hook: plain real CSR in one pass, or split tiles
 bool inline_begin_ok(const eigenex_basis_s* b) {
@@ -1585,13 +1650,30 @@ bool inline_begin_ok(const eigenex_basis_s* b) {
   return !off && b->es == 1 && !m.blocked && !m.sorted && (m.split || m.passes == 1);
 }
 
-// defer_self_norm (with self_norm, one shard that decides locally): the partial sums of ||v||^2 stay in palpha for
-// k_reduce_decide, which adds them itself; begin: see InlineArnoldiBegin (only when inline_begin_ok)
-int enq_apply(eigenex_basis_s* b, int ucol, bool want_dot, bool self_norm = false, int alpha_mode = -1, bool* fin_merged = nullptr,
-              bool defer_alpha = false, bool defer_self_norm = false, const InlineArnoldiBegin* begin = nullptr) {
+// The scalar an operator application forms besides v, and where it goes.  Alpha: u.v, all-reduced into hbuf[slot_alpha].
+// AlphaLocal (several shards): only summed locally into hbuf[base_fused()]; the all-reduce and k_fin_alpha happen with the
+// next step's dots (enq_fused_dots).  AlphaPartials (one shard): the partial sums stay in palpha for the next dots kernel
+// (InlineFin).  Norm (device operators): ||v||^2, all-reduced into hbuf[slot_nrm_before].  NormPartials (one shard that
+// decides locally): its partial sums stay in palpha for k_reduce_decide, which adds them itself.
+enum class ApplyOut { None, Alpha, AlphaLocal, AlphaPartials, Norm, NormPartials };
+// v = (A + shift) * (w*scale), basis column `ucol` = w*scale (host-operator path: nothing happens if the device had stopped)
+struct ApplyPass {
+  int ucol;
+  ApplyOut out = ApplyOut::None;
+  std::optional<FinAlphaMode> decide;  // with Alpha; as for enq_orthogonalize, *fin_merged: k_fin_alpha has been taken care of
+  // one shard (inlines_fin): beta_k, the breakdown test and the scale 1/beta_k are taken from the update's partial sums inside
+  // the operator kernel, which then gets no device scale
+  const InlineFin* fin = nullptr;
+  const InlineArnoldiBegin* begin = nullptr;  // only when inline_begin_ok
+};
+int enq_apply(eigenex_basis_s* b, const ApplyPass& p, bool* fin_merged = nullptr) {
   eigenex_context_s* c = b->ctx;
-  const int merge = (want_dot && alpha_mode >= 0 && fin_merged && b->csr && decides_locally(b)) ? alpha_mode : -1;
-  if (fin_merged) *fin_merged = merge >= 0;
+  const bool want_alpha = p.out == ApplyOut::Alpha || p.out == ApplyOut::AlphaLocal || p.out == ApplyOut::AlphaPartials;
+  const bool want_norm = p.out == ApplyOut::Norm || p.out == ApplyOut::NormPartials;
+  const bool stays = p.out == ApplyOut::AlphaPartials || p.out == ApplyOut::NormPartials;
+  const bool can_merge = p.out == ApplyOut::Alpha && fin_merged && b->csr && decides_locally(b);
+  const std::optional<FinAlphaMode> merge = can_merge ? p.decide : std::nullopt;
+  if (fin_merged) *fin_merged = merge.has_value();
   if (b->csr) {
     // between shards: the neighbour exchange goes to the halo stream behind ev_w_ready (recorded here: everything that wrote the
     // operator input is in front of it on the compute stream), the interior tiles run meanwhile, the boundary tiles behind
@@ -1599,43 +1681,31 @@ int enq_apply(eigenex_basis_s* b, int ucol, bool want_dot, bool self_norm = fals
     // the norm; not done: other writers of the operator input -- copies, restarts -- would have to re-record it.)
     const bool overlap = c->halo_overlap && c->P > 1;
     if (overlap) HIPCHK(hipEventRecord(c->ev_w_ready, c->stream));
-    CHK(halo_exchange(b, true, overlap));
-    hipEvent_t halo_done = overlap ? c->ev_halo_done : nullptr;
+    CHK(halo_exchange(b, CtrlBlock::State, overlap));
     for (auto& s : b->sh) {
-      CsrShard* m = s.csr;
-      if (self_norm) {
-        {
-          ProfScope ps(c, EIGENEX_K_SPMV, operator_bytes(m, b->es) + 32.0 * s.nd);
-          launch_operator(c->stream, m, b->es, s.w, &s.ctrl->scale, b->shift, b->shift_im, s.v, s.V + (int64_t)ucol * s.ldd,
-                          defer_self_norm ? s.palpha : s.partials, s.pstride, s.g_spmv, s.ctrl, s.spmv_flags, kPassSelfNorm, begin, s.g_spmv_int, halo_done);
-        }
-        if (defer_self_norm) continue;
-        ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
-        launch_reduce(c->stream, s.partials, s.pstride, s.g_spmv, 1, s.hbuf + b->slot_nrm_before(), s.ctrl);
-        continue;
-      }
       {
-        const double opbytes = operator_bytes(m, b->es);
-        ProfScope ps(c, EIGENEX_K_SPMV, opbytes + 32.0 * s.nd + (want_dot ? 16.0 * s.nd : 0.0));
-        launch_operator(c->stream, m, b->es, s.w, &s.ctrl->scale, b->shift, b->shift_im, s.v, s.V + (int64_t)ucol * s.ldd,
-                        want_dot ? s.partials : nullptr, s.pstride, s.g_spmv, s.ctrl, s.spmv_flags, 0, begin, s.g_spmv_int, halo_done);
+        ProfScope ps(c, EIGENEX_K_SPMV, operator_bytes(s.csr, b->es) + 32.0 * s.nd + (want_alpha ? 16.0 * s.nd : 0.0));
+        launch_operator(c->stream, s, {.x = s.w, .scale = p.fin ? nullptr : &s.ctrl->scale, .shift = b->shift, .shift_im = b->shift_im, .y = s.v,
+                                       .u_out = s.V + (int64_t)p.ucol * s.ldd, .partials = p.out == ApplyOut::None ? nullptr : stays ? s.palpha : s.partials.get(),
+                                       .ctrl = s.ctrl, .pass_flags = want_norm ? kPassSelfNorm : 0, .fin = p.fin, .begin = p.begin,
+                                       .halo_done = overlap ? c->ev_halo_done : nullptr});
       }
-      if (want_dot) {
-        ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
-        if (merge >= 0)
-          launch_reduce_fin(c->stream, s.partials, s.pstride, s.g_spmv, b->es, s.hbuf + b->slot_alpha(), s.ctrl, merge, s.alpha, 0.0);
-        else
-          launch_reduce(c->stream, s.partials, s.pstride, s.g_spmv, b->es, s.hbuf + (defer_alpha ? b->base_fused() : b->slot_alpha()), s.ctrl);
-      }
+      if (p.out == ApplyOut::None || stays) continue;
+      ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
+      if (want_norm)
+        launch_reduce(c->stream, s.partials, s.pstride, s.g_spmv, 1, s.hbuf + b->slot_nrm_before(), s.ctrl);
+      else if (merge)
+        launch_reduce_fin(c->stream, s.partials, s.pstride, s.g_spmv, b->es, s.hbuf + b->slot_alpha(), s.ctrl, *merge, s.alpha, 0.0);
+      else
+        launch_reduce(c->stream, s.partials, s.pstride, s.g_spmv, b->es, s.hbuf + (p.out == ApplyOut::AlphaLocal ? b->base_fused() : b->slot_alpha()), s.ctrl);
     }
-    if (self_norm) return defer_self_norm ? 0 : allreduce(b, b->slot_nrm_before(), 1);
-    if (want_dot && defer_alpha) return 0;
-    return want_dot && merge < 0 ? allreduce(b, b->slot_alpha(), b->es) : 0;
+    if (p.out == ApplyOut::Norm) return allreduce(b, b->slot_nrm_before(), 1);
+    return p.out == ApplyOut::Alpha && !merge ? allreduce(b, b->slot_alpha(), b->es) : 0;
   }
   // operator lives in host code (MatMulFunction, lanczos.hpp:116): stage through pinned memory
   if (!b->fn) return fail(EIGENEX_ERR_STATE, "no operator: neither a CSR handle nor a host callback is set");
   BasisShard& s = b->sh[0];
-  double* u = s.V + (int64_t)ucol * s.ldd;
+  double* u = s.V + (int64_t)p.ucol * s.ldd;
   launch_scale(c->stream, s.w, &s.ctrl->scale, 1.0, u, s.nd, s.ctrl);
   HIPCHK(hipMemcpyAsync(b->pin_in, u, sizeof(double) * s.nd, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipMemcpyAsync(b->pin_ctrl, s.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, c->stream));
@@ -1643,7 +1713,7 @@ int enq_apply(eigenex_basis_s* b, int ucol, bool want_dot, bool self_norm = fals
   if (b->pin_ctrl->stopped) return 0;  // the reference would not have called the operator
   b->fn(b->pin_in, b->pin_out, b->fn_user);
   HIPCHK(hipMemcpyAsync(s.v, b->pin_out, sizeof(double) * s.nd, hipMemcpyHostToDevice, c->stream));
-  if (want_dot || b->shift != 0.0 || b->shift_im != 0.0) {
+  if (want_alpha || b->shift != 0.0 || b->shift_im != 0.0) {
     if (b->es == 2)
       launch_shift_dot_z(c->stream, s.v, u, b->shift, b->shift_im, s.nloc, s.partials, s.pstride, s.g_vec, s.ctrl);
     else
@@ -1657,22 +1727,23 @@ int enq_apply(eigenex_basis_s* b, int ucol, bool want_dot, bool self_norm = fals
 // the start vector sits in W; deflate by orthogonalizingVectors_, norm, fail or scale = 1/norm.
 int enq_initial_vector(eigenex_basis_s* b) {
   bool merged = false;
-  CHK(enq_orthogonalize(b, EIGENEX_VEC_W, EIGENEX_VEC_W, false, 0, 0, 1, 0, b->nq, true, false, kFinInit, &merged));
+  CHK(enq_orthogonalize(b, {.src = EIGENEX_VEC_W, .dst = EIGENEX_VEC_W, .cols = {.nq = b->nq}, .q_first = true, .decide = kFinInit}, &merged));
   if (!merged)
     for (auto& s : b->sh) launch_fin_norm(b->ctx->stream, s.ctrl, s.hbuf + b->slot_nrm(), b->threshold, kFinInit, s.beta);
   return 0;
 }
 
 // columns a Lanczos step with k+1 existing vectors re-orthogonalises against  (lanczos.hpp:411-426)
-inline void lanczos_columns(int k, int64_t interval, int nq_total, int* first, int* stride, int* count, int* nq) {
-  *first = 0, *stride = 1, *count = 0, *nq = 0;
-  if (interval <= 0) return;
+inline Cols lanczos_columns(int k, int64_t interval, int nq_total) {
+  Cols c;
+  if (interval <= 0) return c;
   const int64_t nk = k + 2;  // lanczosvectors_.size() after the push_back
   const int64_t kmod = (nk - 1) % interval;
-  *first = (int)kmod;
-  *stride = (int)std::min<int64_t>(interval, 1 << 30);
-  *count = kmod < nk - 1 ? (int)((nk - 1 - kmod + interval - 1) / interval) : 0;
-  *nq = kmod == 0 ? nq_total : 0;
+  c.first = (int)kmod;
+  c.stride = (int)std::min<int64_t>(interval, 1 << 30);
+  c.count = kmod < nk - 1 ? (int)((nk - 1 - kmod + interval - 1) / interval) : 0;
+  c.nq = kmod == 0 ? nq_total : 0;
+  return c;
 }
 
 // Can the alpha of the vector a call adds stay un-reduced until the next call's dots?  Only between shards (one shard
@@ -1683,17 +1754,18 @@ inline bool fuses_alpha(const eigenex_basis_s* b) {
 
 // all-reduce and record an alpha that was left pending (a step without columns to orthogonalise against follows)
 int close_pending_alpha(eigenex_basis_s* b) {
-  if (!b->alpha_pending) return 0;
-  if (b->alpha_pending_inline) {  // one shard: the partials of the operator kernel are still waiting for their second stage
+  StepCursor& cur = b->cur;
+  if (!cur.alpha_pending) return 0;
+  if (cur.alpha_pending_inline) {  // one shard: the partials of the operator kernel are still waiting for their second stage
     BasisShard& s = b->sh[0];
     launch_reduce_fin(b->ctx->stream, s.palpha, s.pstride, s.g_spmv, b->es, s.hbuf + b->slot_alpha(), s.ctrl,
-                      b->alpha_pending_first ? kFinishAlphaFirst : kFinishAlpha, s.alpha, 0.0);
-    b->alpha_pending = b->alpha_pending_inline = false;
+                      cur.alpha_pending_first ? kFinishAlphaFirst : kFinishAlpha, s.alpha, 0.0);
+    cur.alpha_pending = cur.alpha_pending_inline = false;
     return 0;
   }
   CHK(allreduce(b, b->base_fused(), b->es));
-  for (auto& s : b->sh) launch_fin_alpha(b->ctx->stream, s.ctrl, s.hbuf + b->base_fused(), s.alpha, b->alpha_pending_first ? 1 : 0, b->cap);
-  b->alpha_pending = false;
+  for (auto& s : b->sh) launch_fin_alpha(b->ctx->stream, s.ctrl, s.hbuf + b->base_fused(), s.alpha, cur.alpha_pending_first ? 1 : 0, b->cap);
+  cur.alpha_pending = false;
   return 0;
 }
 
@@ -1708,60 +1780,26 @@ inline bool inlines_fin(const eigenex_basis_s* b) {
   return !m.blocked && !m.sorted && !m.split && m.passes == 1 && (b->ortho_mode == EIGENEX_ORTHO_BATCHED || b->ortho_mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE);
 }
 
-int lanczos_step_inline(eigenex_basis_s* b, int k, int first, int stride, int count, int nq, bool last_in_batch) {
-  eigenex_context_s* c = b->ctx;
-  hipStream_t st = c->stream;
+// the same passes as the general step, with the hand-overs as hooks: no second-stage launch for the norm or for alpha
+int lanczos_step_inline(eigenex_basis_s* b, int k, const Cols& cols, bool last_in_batch) {
   BasisShard& s = b->sh[0];
-  const CsrShard* m = s.csr;
-  const int ncols = count + nq;
-  const ThreeTerm tt{s.V + (int64_t)k * s.ldd, k > 0 ? s.V + (int64_t)(k - 1) * s.ldd : nullptr, s.alpha + k, s.beta + (k > 0 ? k - 1 : 0)};
+  StepCursor& cur = b->cur;
   // dots of w0 = v - alpha_k u_k - beta_{k-1} u_{k-1}; a pending alpha_k is finalised inside the (first) dots launch
-  const int chunk = kDotsMaxAcc;
-  for (int c0 = 0; c0 < ncols; c0 += chunk) {
-    const int nc = std::min(chunk, ncols - c0);
-    const int v0 = std::min(c0, count), v1 = std::min(c0 + nc, count);
-    const int q0 = std::max(c0 - count, 0), q1 = std::max(c0 + nc - count, 0);
-    InlineFin fa{s.palpha, s.g_spmv, b->alpha_pending_first ? kFinishAlphaFirst : kFinishAlpha, 0.0, s.alpha, s.ctrl, s.hbuf + b->slot_alpha()};
-    const bool take_alpha = b->alpha_pending && c0 == 0;
-    ProfScope ps(c, EIGENEX_K_DOTS, 8.0 * s.nd * nc + 8.0 * s.nd);
-    LAUNCH_BEGIN();
-    launch_dots(st, s.v, tt, colset(s, first + v0 * stride, stride, v1 - v0, q0, q1 - q0), s.nd, s.partials + (int64_t)c0 * s.pstride, s.pstride,
-                s.g_vec, s.ctrl, false, nullptr, nullptr, take_alpha ? &fa : nullptr);
-    LAUNCHCHK("k_dots");
-    if (take_alpha) b->alpha_pending = b->alpha_pending_inline = false;
-  }
-  {
-    ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
-    launch_reduce(st, s.partials, s.pstride, s.g_vec, ncols, s.hbuf, s.ctrl);
-  }
-  {
-    ProfScope ps(c, EIGENEX_K_UPDATE, 8.0 * s.nd * ncols + 24.0 * s.nd + 32.0 * s.nd);
-    LAUNCH_BEGIN();
-    launch_update(st, s.v, s.w, tt, colset(s, first, stride, count, 0, nq), s.hbuf, s.nd, s.pnorm, s.g_vec, s.ctrl, false);
-    LAUNCHCHK("k_update");
-  }
+  const InlineFin fin_alpha{s.palpha, s.g_spmv, cur.alpha_pending_first ? kFinishAlphaFirst : kFinishAlpha, 0.0, s.alpha, s.ctrl, s.hbuf + b->slot_alpha()};
+  CHK(enq_dots(b, {.src = EIGENEX_VEC_V, .step = k, .cols = cols, .fin = cur.alpha_pending ? &fin_alpha : nullptr}));
+  cur.alpha_pending = cur.alpha_pending_inline = false;
+  CHK(enq_update(b, {.src = EIGENEX_VEC_V, .dst = EIGENEX_VEC_W, .step = k, .cols = cols, .norm = NormOut::Partials}));
   // operator: beta_k, breakdown test and scale from the update's partials inside the kernel; alpha_{k+1} partials to palpha
-  {
-    InlineFin fn{s.pnorm, s.g_vec, kFinLanczos, b->threshold, s.beta, s.ctrl, s.hbuf + b->slot_nrm()};
-    ProfScope ps(c, EIGENEX_K_SPMV, operator_bytes(m, 1) + 32.0 * s.nd + 16.0 * s.nd);
-    if (m->rc_rec)
-      launch_spmv_rows(st, row_code_view(m), s.w, nullptr, b->shift, s.v, s.V + (int64_t)(k + 1) * s.ldd, m->nloc, s.palpha, s.g_spmv, s.ctrl,
-                       s.spmv_flags, 0, &fn);
-    else if (m->rowptr64)
-      launch_spmv64(st, m->rowptr64, m->col, m->val, s.w, nullptr, b->shift, s.v, s.V + (int64_t)(k + 1) * s.ldd, m->nloc, s.palpha, s.g_spmv, s.ctrl,
-                    s.spmv_flags | (m->nnz >= 16 * m->nloc ? 4 : 0), 0, &fn);
-    else
-      launch_spmv(st, m->rowptr, m->col, m->val, s.w, nullptr, b->shift, s.v, s.V + (int64_t)(k + 1) * s.ldd, m->nloc, s.palpha, s.g_spmv, s.ctrl,
-                  s.spmv_flags | (m->nnz >= 16 * m->nloc ? 4 : 0), 0, &fn);
-  }
+  const InlineFin fin_norm{s.pnorm, s.g_vec, kFinLanczos, b->threshold, s.beta, s.ctrl, s.hbuf + b->slot_nrm()};
+  CHK(enq_apply(b, {.ucol = k + 1, .out = ApplyOut::AlphaPartials, .fin = &fin_norm}));
   if (last_in_batch) {
-    ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
-    launch_reduce_fin(st, s.palpha, s.pstride, s.g_spmv, 1, s.hbuf + b->slot_alpha(), s.ctrl, kFinishAlpha, s.alpha, 0.0);
+    ProfScope ps(b->ctx, EIGENEX_K_SMALL, 0.0);
+    launch_reduce_fin(b->ctx->stream, s.palpha, s.pstride, s.g_spmv, 1, s.hbuf + b->slot_alpha(), s.ctrl, kFinishAlpha, s.alpha, 0.0);
   } else {
-    b->alpha_pending = b->alpha_pending_inline = true;
-    b->alpha_pending_first = false;
+    cur.alpha_pending = cur.alpha_pending_inline = true;
+    cur.alpha_pending_first = false;
   }
-  b->h_nvec++;
+  cur.h_nvec++;
   return 0;
 }
 
@@ -1771,59 +1809,54 @@ int lanczos_step_inline(eigenex_basis_s* b, int k, int first, int stride, int co
 // its own alpha, so that every batch leaves a complete state behind (nalpha == nvec).
 int lanczos_call(eigenex_basis_s* b, bool last_in_batch) {
   hipStream_t st = b->ctx->stream;
+  StepCursor& cur = b->cur;
   const bool defer = fuses_alpha(b) && !last_in_batch;
-  if (!b->started) {
-    b->started = true;
-    CHK(enq_initial_vector(b));
-    bool merged = false;
-    CHK(enq_apply(b, 0, true, false, kFinishAlphaFirst, &merged, defer));  // :389-392
-    if (defer)
-      b->alpha_pending = b->alpha_pending_first = true;
-    else if (!merged)
-      for (auto& s : b->sh) launch_fin_alpha(st, s.ctrl, s.hbuf + b->slot_alpha(), s.alpha, 1, b->cap);  // :395
-    b->h_nvec = 1;
-    return 0;
-  }
-  const int k = b->h_nvec - 1;
-  if (b->h_nvec >= b->cap) return fail(EIGENEX_ERR_STATE, "basis capacity exhausted");
-  int first, stride, count, nq;
-  lanczos_columns(k, b->interval, b->nq, &first, &stride, &count, &nq);
-  if (inlines_fin(b) && count + nq > 0) return lanczos_step_inline(b, k, first, stride, count, nq, last_in_batch);
-  if (b->alpha_pending && (count + nq == 0 || b->alpha_pending_inline)) CHK(close_pending_alpha(b));  // no dots pass to ride on
-  const bool fused = b->alpha_pending;
+  const ApplyOut alpha_out = defer ? ApplyOut::AlphaLocal : ApplyOut::Alpha;
+  const int first_call = cur.started ? 0 : 1;  // k_fin_alpha: alpha_0 does not count an iteration
   bool merged = false;
-  CHK(enq_orthogonalize(b, EIGENEX_VEC_V, EIGENEX_VEC_W, true, k, first, stride, count, nq, false, false, kFinLanczos, &merged, fused));
-  if (!merged)
-    for (auto& s : b->sh) launch_fin_norm(st, s.ctrl, s.hbuf + b->slot_nrm(), b->threshold, kFinLanczos, s.beta);  // :429-437
-  CHK(enq_apply(b, k + 1, true, false, kFinishAlpha, &merged, defer));  // :439-445
-  if (defer) {
-    b->alpha_pending = true;
-    b->alpha_pending_first = false;
-  } else if (!merged) {
-    for (auto& s : b->sh) launch_fin_alpha(st, s.ctrl, s.hbuf + b->slot_alpha(), s.alpha, 0, b->cap);  // :448-450
+  if (!cur.started) {
+    cur.started = true;
+    cur.h_nvec = 0;
+    CHK(enq_initial_vector(b));
+    CHK(enq_apply(b, {.ucol = 0, .out = alpha_out, .decide = kFinishAlphaFirst}, &merged));  // :389-392
+  } else {
+    const int k = cur.h_nvec - 1;
+    if (cur.h_nvec >= b->cap) return fail(EIGENEX_ERR_STATE, "basis capacity exhausted");
+    const Cols cols = lanczos_columns(k, b->interval, b->nq);
+    if (inlines_fin(b) && cols.total() > 0) return lanczos_step_inline(b, k, cols, last_in_batch);
+    if (cur.alpha_pending && (cols.total() == 0 || cur.alpha_pending_inline)) CHK(close_pending_alpha(b));  // no dots pass to ride on
+    CHK(enq_orthogonalize(b, {.src = EIGENEX_VEC_V, .dst = EIGENEX_VEC_W, .step = k, .cols = cols, .decide = kFinLanczos, .fused_alpha = cur.alpha_pending},
+                          &merged));
+    if (!merged)
+      for (auto& s : b->sh) launch_fin_norm(st, s.ctrl, s.hbuf + b->slot_nrm(), b->threshold, kFinLanczos, s.beta);  // :429-437
+    CHK(enq_apply(b, {.ucol = k + 1, .out = alpha_out, .decide = kFinishAlpha}, &merged));  // :439-445
   }
-  b->h_nvec++;
+  if (defer) {
+    cur.alpha_pending = true;
+    cur.alpha_pending_first = first_call != 0;
+  } else if (!merged) {
+    for (auto& s : b->sh) launch_fin_alpha(st, s.ctrl, s.hbuf + b->slot_alpha(), s.alpha, first_call, b->cap);  // :395, :448-450
+  }
+  cur.h_nvec++;
   return 0;
 }
 
 // one call of ArnoldiBase::updateArnoldiSteps()  (arnoldi.hpp:312-392)
 int arnoldi_call(eigenex_basis_s* b, bool last_in_batch) {
   hipStream_t st = b->ctx->stream;
-  int k;
+  StepCursor& cur = b->cur;
+  int k = 0;
   bool begin_inline = false;
-  if (!b->started) {
-    b->started = true;
+  if (!cur.started) {
+    cur.started = true;
     CHK(enq_initial_vector(b));
-    k = 0;
   } else {
-    k = b->h_nvec;
+    k = cur.h_nvec;
     // :357-365.  One shard with an operator kernel that has the hook: the operator kernel does this itself (one launch less)
     begin_inline = k < b->cap && inline_begin_ok(b);
-    if (b->tail_pending && !begin_inline) {  // (cannot happen: a tail is only left behind when the next call can take it)
-      BasisShard& s = b->sh[0];
-      launch_arnoldi_tail(st, s.pnorm, s.g_vec, s.ctrl, s.ctrl_pass2, s.hbuf, s.hbuf + b->base_h2(), b->tail_ncoef,
-                          s.hbuf + b->slot_nrm_first(), s.hbuf + b->slot_nrm(), s.H, b->ldh, b->es);
-      b->tail_pending = false;
+    if (cur.tail_pending && !begin_inline) {  // (cannot happen: a tail is only left behind when the next call can take it)
+      launch_tail(b, cur.tail_ncoef);
+      cur.tail_pending = false;
     }
     if (k >= b->cap && (int64_t)k < b->n_global) return fail(EIGENEX_ERR_STATE, "basis capacity exhausted");
     if (!begin_inline)
@@ -1833,30 +1866,26 @@ int arnoldi_call(eigenex_basis_s* b, bool last_in_batch) {
   const bool adaptive = b->ortho_mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE && b->csr != nullptr;
   // one shard that decides locally: ||v||^2 stays as the operator's partial sums until k_reduce_decide (one launch less)
   const bool small_merged = adaptive && decides_locally(b);
-  BasisShard& s0 = b->sh[0];
-  const bool take_tail = begin_inline && b->tail_pending;  // the previous call left its end to this call's operator kernel
-  const InlineArnoldiBegin ab{s0.ctrl, b->threshold, b->n_global, b->cap, s0.H, b->ldh, b->es,
-                              take_tail ? k - 1 : -1, s0.pnorm, s0.g_vec, s0.ctrl_pass2, s0.hbuf, s0.hbuf + b->base_h2(), b->tail_ncoef,
-                              s0.hbuf + b->slot_nrm_first(), s0.hbuf + b->slot_nrm()};
-  b->tail_pending = false;
-  CHK(enq_apply(b, k, false, adaptive, -1, nullptr, false, small_merged, begin_inline ? &ab : nullptr));  // :333-336, :369-372
-  if (!b->csr && b->shift != 0.0) { /* shift applied inside enq_apply's host path */ }
+  const InlineArnoldiBegin hook = arnoldi_hook(b, begin_inline && cur.tail_pending ? std::optional<int>(k - 1) : std::nullopt);
+  cur.tail_pending = false;
+  CHK(enq_apply(b, {.ucol = k, .out = !adaptive ? ApplyOut::None : small_merged ? ApplyOut::NormPartials : ApplyOut::Norm,
+                    .begin = begin_inline ? &hook : nullptr}));  // :333-336, :369-372
   // :337-345, :373-383
+  OrthoPass ortho{.src = EIGENEX_VEC_V, .dst = EIGENEX_VEC_W, .cols = {.count = k + 1, .nq = b->nq}, .q_first = true};
   bool tail_done = false;  // only the adaptive scheme on one shard folds k_fin_norm and k_arnoldi_end into its last launch
   if (adaptive) {
+    ortho.decide = kFinArnoldi;
+    ortho.before = small_merged ? OrthoPass::Before::Palpha : OrthoPass::Before::Slot;
     // the end of this step can wait for the next call's operator kernel if there will be one in this batch that has the hook
-    const bool defer_tail = small_merged && !last_in_batch && k + 1 < b->cap && (int64_t)(k + 1) < b->n_global && inline_begin_ok(b);
-    CHK(enq_orthogonalize(b, EIGENEX_VEC_V, EIGENEX_VEC_W, false, 0, 0, 1, k + 1, b->nq, true, true, kFinArnoldi, &tail_done, false,
-                          small_merged, defer_tail));
-  } else {
-    CHK(enq_orthogonalize(b, EIGENEX_VEC_V, EIGENEX_VEC_W, false, 0, 0, 1, k + 1, b->nq, true));
+    ortho.defer_tail = small_merged && !last_in_batch && k + 1 < b->cap && (int64_t)(k + 1) < b->n_global && inline_begin_ok(b);
   }
+  CHK(enq_orthogonalize(b, ortho, adaptive ? &tail_done : nullptr));
   if (!tail_done)
     for (auto& s : b->sh) {
       launch_fin_norm(st, s.ctrl, s.hbuf + b->slot_nrm(), b->threshold, kFinArnoldi, s.beta);  // :348, :385
       launch_arnoldi_end(st, s.ctrl, s.hbuf, s.H, b->ldh, b->es);
     }
-  b->h_nvec = k + 1;
+  cur.h_nvec = k + 1;
   return 0;
 }
 
@@ -1907,7 +1936,7 @@ int64_t launches_upper_bound(const eigenex_basis_s* b, int ncalls) {
   if (b->csr)
     for (auto& s : b->csr->sh) passes = std::max(passes, s.split ? 2 : s.passes);  // split tiles: two launches per application
   int64_t total = 0;
-  int nvec = b->h_nvec;
+  int nvec = b->cur.h_nvec;
   for (int i = 0; i < ncalls; ++i) {
     const int64_t cols = (int64_t)nvec + b->nq + 1;
     const int64_t dots_chunks = cols * b->es * 2 / kDotsMaxAcc + 1;
@@ -1940,7 +1969,7 @@ int enqueue_steps(eigenex_basis_s* b, int ncalls, int kind) {
     for (int i = 0; i < ncalls; ++i) {
       const int rc = kind == 0 ? lanczos_call(b, i == ncalls - 1) : arnoldi_call(b, i == ncalls - 1);
       if (rc != 0) {
-        b->tail_pending = false;  // a deferred step end is never handed to a later batch (its tail_k would be stale)
+        b->cur.tail_pending = false;  // a deferred step end is never handed to a later batch (its tail_k would be stale)
         return rc;
       }
     }
@@ -1953,20 +1982,18 @@ int enqueue_steps(eigenex_basis_s* b, int ncalls, int kind) {
     return plain();  // (the loopback transport multiplies the launches by its shard count and is for verification anyway)
   StepGraphKey key;
   std::memset(&key, 0, sizeof(key));
-  key.kind = kind, key.started = b->started ? 1 : 0, key.h_nvec = b->h_nvec, key.ncalls = ncalls, key.ortho_mode = b->ortho_mode;
+  key.kind = kind, key.started = b->cur.started ? 1 : 0, key.h_nvec = b->cur.h_nvec, key.ncalls = ncalls, key.ortho_mode = b->ortho_mode;
   key.nq = b->nq, key.flags = b->sh[0].spmv_flags, key.g_vec = b->sh[0].g_vec, key.g_spmv = b->sh[0].g_spmv, key.cap = b->cap;
   key.interval = b->interval, key.threshold = b->threshold, key.shift = b->shift, key.shift_im = b->shift_im, key.slab = b->sh[0].V;
   for (auto& g : b->graphs)
     if (std::memcmp(&g.key, &key, sizeof(key)) == 0) {
       HIPCHK(hipGraphLaunch(g.exec, c->stream));
-      b->started = g.started_after;
-      b->h_nvec = g.h_nvec_after;
+      b->cur = g.cur_after;
       g.last_use = ++b->graph_clock;
       return 0;
     }
   // record: nothing executes during the capture; the host-side counters advance as in a plain run
-  const bool started0 = b->started, tail_pending0 = b->tail_pending;
-  const int h_nvec0 = b->h_nvec, tail_ncoef0 = b->tail_ncoef;
+  const StepCursor before = b->cur;
   if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
     (void)hipGetLastError();
     return plain();
@@ -1991,7 +2018,7 @@ int enqueue_steps(eigenex_basis_s* b, int ncalls, int kind) {
     }
     StepGraph g;
     g.nodes = (int64_t)nodes;
-    g.key = key, g.exec = exec, g.started_after = b->started, g.h_nvec_after = b->h_nvec, g.last_use = ++b->graph_clock;
+    g.key = key, g.exec = exec, g.cur_after = b->cur, g.last_use = ++b->graph_clock;
     b->graphs.push_back(g);
     HIPCHK(hipGraphLaunch(exec, c->stream));
     return 0;
@@ -1999,10 +2026,7 @@ int enqueue_steps(eigenex_basis_s* b, int ncalls, int kind) {
   // the batch could not be recorded (or a call failed while recording): nothing has run yet, so rewind and run it plainly
   if (graph) (void)hipGraphDestroy(graph);
   (void)hipGetLastError();
-  b->started = started0;
-  b->h_nvec = h_nvec0;
-  b->tail_pending = tail_pending0;
-  b->tail_ncoef = tail_ncoef0;
+  b->cur = before;
   if (rc != 0) {
     g_err = err;
     return rc;  // the same argument/state error a plain run reports, before anything was launched
@@ -2015,7 +2039,7 @@ int sync_ctrl(eigenex_basis_s* b, Ctrl* out) {
   HIPCHK(hipMemcpyAsync(b->pin_ctrl, b->sh[0].ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   *out = *b->pin_ctrl;
-  b->h_nvec = out->nvec;
+  b->cur.h_nvec = out->nvec;
   return 0;
 }
 
@@ -2227,13 +2251,12 @@ int eigenex_lanczos_collectives(int call_index, int last_in_batch, int* alpha_pe
   if (call_index == 0) {
     ortho(n_ortho, false, false);  // start vector against orthogonalizingVectors_, norm
   } else {
-    int first, stride, count, nq;
-    lanczos_columns(call_index - 1, interval, n_ortho, &first, &stride, &count, &nq);
-    if (*alpha_pending && count + nq == 0) {
+    const int ncols = lanczos_columns(call_index - 1, interval, n_ortho).total();
+    if (*alpha_pending && ncols == 0) {
       allred(es);
       *alpha_pending = 0;
     }
-    ortho(count + nq, true, *alpha_pending != 0);
+    ortho(ncols, true, *alpha_pending != 0);
   }
   out.push_back({EIGENEX_COLL_HALO, 0});
   if (defer)
@@ -2940,7 +2963,7 @@ int eigenex_basis_create_ex(eigenex_context_t c, eigenex_csr_t csr, int64_t n_gl
     // long rows: 8 workgroups per CU measured 7-8 % ahead of 4 (tests/probes/probe_spmv_flags.py); the stencils: equal.  Dense blocks (r3:
     // k_block_spmv stages the input in 16 KB of LDS, nine workgroups fit a CU): 12 -- more workgroups than fit, so that CUs that
     // finish early take another -- 234.7 / 216.7 / 238.7 / 217.6 / 217.6 us at 4 / 6 / 8 / 12 / 16 (scripts/block_apply.py 10 --sweep)
-    s.g_spmv = operator_partials(s.csr, s.nloc, (s.csr && s.csr->blocked) ? 12 : (s.csr && s.csr->nnz >= 16 * s.csr->nloc) ? 2 * kDefaultSpmvBlocksPerCu : kDefaultSpmvBlocksPerCu, &s.g_spmv_int);
+    s.g_spmv = operator_partials(s.csr, s.nloc, (s.csr && s.csr->blocked) ? 12 : (s.csr && has_long_rows(s.csr)) ? 2 * kDefaultSpmvBlocksPerCu : kDefaultSpmvBlocksPerCu, &s.g_spmv_int);
     // room for eigenex_basis_tune up to kMaxBlocksPerCu workgroups per CU
     s.pstride = std::max(grid_for_tiles((s.nd + kTileRows - 1) / kTileRows, kMaxBlocksPerCu),
                          grid_for_tiles((s.nloc + kSpmvRows - 1) / kSpmvRows, kMaxBlocksPerCu) * ((s.csr && s.csr->tiles_split) ? 2 : 1));  // two launches: two sets of partial dots
@@ -2989,8 +3012,8 @@ int eigenex_basis_clone(eigenex_basis_t src, eigenex_basis_t* out) {
   CHK(eigenex_basis_create_ex(c, src->csr, src->n_global, src->cap, src->nq, src->es == 2, &made));
   std::unique_ptr<eigenex_basis_s> b(made);
   b->shift = src->shift, b->shift_im = src->shift_im, b->threshold = src->threshold, b->interval = src->interval;
-  b->ortho_mode = src->ortho_mode, b->started = src->started, b->h_nvec = src->h_nvec, b->fn = src->fn, b->fn_user = src->fn_user;
-  b->fuse_alpha = src->fuse_alpha, b->alpha_pending = src->alpha_pending, b->alpha_pending_first = src->alpha_pending_first;
+  b->ortho_mode = src->ortho_mode, b->cur = src->cur, b->fn = src->fn, b->fn_user = src->fn_user;
+  b->fuse_alpha = src->fuse_alpha;
   for (size_t i = 0; i < b->sh.size(); ++i) {
     BasisShard &d = b->sh[i], &s = src->sh[i];
     d.g_vec = s.g_vec, d.g_spmv = s.g_spmv, d.g_spmv_int = s.g_spmv_int, d.spmv_flags = s.spmv_flags;
@@ -3109,10 +3132,8 @@ int eigenex_basis_clear(eigenex_basis_t b) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
   HIPCHK(hipSetDevice(b->ctx->device));
   for (auto& s : b->sh) HIPCHK(hipMemsetAsync(s.ctrl, 0, sizeof(Ctrl), b->ctx->stream));
-  b->started = false;
-  b->h_nvec = 0;
-  b->alpha_pending = b->alpha_pending_inline = false;
-  b->tail_pending = false;
+  StepCursor& cur = b->cur;
+  cur.started = false, cur.h_nvec = 0, cur.alpha_pending = cur.alpha_pending_inline = false, cur.tail_pending = false;
   return 0;
 }
 
@@ -3216,12 +3237,13 @@ int eigenex_apply(eigenex_basis_t b, int x_ref, int y_ref, double shift, double*
     if (!x || !y || x == y) return fail(EIGENEX_ERR_ARG, "bad vector reference");
     if (x != s.w) HIPCHK(hipMemcpyAsync(s.w, x, sizeof(double) * s.nd, hipMemcpyDeviceToDevice, c->stream));
   }
-  CHK(halo_exchange(b, false));
+  CHK(halo_exchange(b, CtrlBlock::Zero));
   for (auto& s : b->sh) {
     CsrShard* m = s.csr;
-    ProfScope ps(c, EIGENEX_K_SPMV, (m->rc_rec ? operator_bytes(m, b->es) : (4.0 + 8.0 * b->es) * m->nnz + 4.0 * (m->nloc + 1)) + 16.0 * s.nd);
-    launch_operator(c->stream, m, b->es, s.w, nullptr, shift, 0.0, vec_ptr(s, b->cap, b->nq, y_ref), nullptr,
-                    dot ? s.partials : nullptr, s.pstride, s.g_spmv, s.ctrl_zero, s.spmv_flags, 0, nullptr, s.g_spmv_int);
+    // (a block operator is booked as its CSR form here, as it always was)
+    ProfScope ps(c, EIGENEX_K_SPMV, (m->blocked ? csr_bytes(m, b->es) : operator_bytes(m, b->es)) + 16.0 * s.nd);
+    launch_operator(c->stream, s, {.x = s.w, .scale = nullptr, .shift = shift, .y = vec_ptr(s, b->cap, b->nq, y_ref),
+                                   .partials = dot ? s.partials.get() : nullptr, .ctrl = s.ctrl_zero});
     if (dot) launch_reduce(c->stream, s.partials, s.pstride, s.g_spmv, b->es, s.hbuf + b->slot_alpha(), s.ctrl_zero);
   }
   if (dot) {
@@ -3237,7 +3259,7 @@ int eigenex_dots(eigenex_basis_t b, int w_ref, int first, int stride, int count,
   if (!cols_ok(b, first, stride, count, n_ortho_used)) return fail(EIGENEX_ERR_ARG, "bad column selection");
   if (!vec_ptr(b->sh[0], b->cap, b->nq, w_ref)) return fail(EIGENEX_ERR_ARG, "bad vector reference");
   HIPCHK(hipSetDevice(b->ctx->device));
-  CHK(enq_dots(b, w_ref, false, 0, first, stride, count, 0, n_ortho_used, 0, false));
+  CHK(enq_dots(b, {.src = w_ref, .cols = {.first = first, .stride = stride, .count = count, .nq = n_ortho_used}, .ctrl = CtrlBlock::Zero}));
   return fetch_h(b, 0, (count + n_ortho_used) * b->es, h);
 }
 
@@ -3249,7 +3271,7 @@ int eigenex_update(eigenex_basis_t b, int w_ref, int first, int stride, int coun
   if (!vec_ptr(b->sh[0], b->cap, b->nq, w_ref)) return fail(EIGENEX_ERR_ARG, "bad vector reference");
   HIPCHK(hipSetDevice(b->ctx->device));
   if (count + n_ortho_used > 0) CHK(push_h(b, 0, (count + n_ortho_used) * b->es, h));
-  CHK(enq_update(b, w_ref, w_ref, false, 0, first, stride, count, 0, n_ortho_used, 0, true, false));
+  CHK(enq_update(b, {.src = w_ref, .dst = w_ref, .cols = {.first = first, .stride = stride, .count = count, .nq = n_ortho_used}, .ctrl = CtrlBlock::Zero, .norm = NormOut::Slot}));
   if (nrm2) return fetch_h(b, b->slot_nrm(), 1, nrm2);
   HIPCHK(hipStreamSynchronize(b->ctx->stream));
   return 0;
@@ -3267,7 +3289,7 @@ int eigenex_axpy2(eigenex_basis_t b, int z_ref, int x_ref, double a, int p_ref, 
     if (!z || !x || !p || !q) return fail(EIGENEX_ERR_ARG, "bad vector reference");
     ThreeTerm tt{p, bcoef != 0.0 ? q : nullptr, s.hbuf + b->slot_a(), s.hbuf + b->slot_b()};
     ProfScope ps(c, EIGENEX_K_UPDATE, 32.0 * s.nd);
-    launch_update(c->stream, x, z, tt, colset(s, 0, 1, 0, 0, 0), s.hbuf, s.nd, s.partials, s.g_vec, s.ctrl_zero, b->es == 2);
+    launch_update(c->stream, x, z, tt, colset(s, Cols{}), s.hbuf, s.nd, s.partials, s.g_vec, s.ctrl_zero, b->es == 2);
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
@@ -3329,7 +3351,7 @@ int eigenex_lanczos_restart(eigenex_basis_t b, int nkeep, const double* S, int l
     HIPCHK(hipMemcpyAsync(s.V + (size_t)nkeep * s.ldd, s.V + (size_t)m * s.ldd, vb, hipMemcpyDeviceToDevice, c->stream));
     launch_restart_fix(c->stream, s.ctrl, s.alpha, s.beta, m, nkeep, coupling_last);
   }
-  b->h_nvec = nkeep + 1;
+  b->cur.h_nvec = nkeep + 1;
   return 0;
 }
 
