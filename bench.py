@@ -2,7 +2,8 @@
 """Benchmark of the Krylov hot path on MI355X (BASELINE.json: "Lanczos iters/sec + achieved HBM
 GB/s, 3-D Laplacian N=10^8, fp64, 1/2/4/8 GPUs").
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W            the headline figure and nothing that costs time beside it
+  python bench.py --gpus N --steps K --warmup W --full     + everything else this file measures or checks (below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Called plainly with --gpus N > 1 (no launcher, WORLD_SIZE unset) it starts its own N rank processes -- one per GPU,
@@ -17,13 +18,20 @@ minIterations = maxIterations = 100 (101 basis vectors), the reference's default
 One "step" = one complete solve through LanczosEigenSolver<double>::compute() (the header-only
 C++ class with the reference's API); value = Krylov iterations per second over the timed steps.
 
-The JSON line also carries
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  Its line also carries what
+the timed steps themselves recorded, at no run of its own:
   roofline      HIP-event timing (on the library's stream) of the dominant kernel over the timed
                 region: algorithmic bytes (SURVEY 8d / DESIGN.md) / duration vs the 8 TB/s HBM peak
+  multi_gpu     (N > 1) what the RCCL communicator reports, per-rank kernel times, collectives, halo bytes
+With --full the same run goes on, after the timed steps and the dump, to
   cpu_baseline  the CPU oracle (oracle/krylov_ref.c, a port of the reference's step function)
                 timed on this host on a bounded sample (rank 0, N=1 only): the first iterations of the
-                SAME 512^3 input when the host has the memory for it, else a 256^3 grid
-  multi_gpu     (N > 1) what the RCCL communicator reports, per-rank kernel times, collectives, halo bytes
+                SAME 512^3 input when the host has the memory for it, else a 256^3 grid, with the oracle's
+                coefficients compared with the device's (--no-cpu-baseline leaves it out of a --full run)
+  without_per_launch_events   a launch-bound solve (under 0.5 s): the same steps once more with the per-launch events off
+  roofline.traffic*           the recorded PMC traffic of the dominant kernel (profiles/hbm_traffic.json) and whether
+                              it belongs to the sources that ran
+The timed steps, `value` and `ms_per_step` are the same with and without --full.
 """
 from __future__ import annotations
 
@@ -57,7 +65,10 @@ def parse_args(argv=None):
     ap.add_argument("--grid-edge", "--n", dest="n", type=int, default=512, help="grid edge (default 512: the BASELINE metric's workload)")
     ap.add_argument("--krylov-steps", "--m", dest="m", type=int, default=100, help="Lanczos iterations per solve")
     ap.add_argument("--sequential", action="store_true", help="reference-order sequential Gram-Schmidt instead of batched")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what is not needed for the headline figure: the CPU baseline and its comparison with "
+                         "the device, the repeat of a launch-bound solve without per-launch events, the recorded PMC traffic and its provenance")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--halo-overlap", action="store_true",
                     help="N > 1: neighbour exchange on a second stream / communicator beside the interior rows (opt-in between real ranks)")
     ap.add_argument("--workload", choices=("laplacian", "config3", "config1", "config5"), default="laplacian",
@@ -342,7 +353,7 @@ def other_config(args):
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, r)
     dt_plain = None
-    if dt / args.steps < 0.5:  # as for the Laplacian: the same steps once more without the per-launch events, reported next to `value`
+    if args.full and dt / args.steps < 0.5:  # as for the Laplacian: the same steps once more without the per-launch events, reported next to `value`
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -361,7 +372,7 @@ def other_config(args):
     out = {
         "metric": metric, "value": args.steps * its / dt, "unit": "iterations/s", "n_gpus": 1, "steps": args.steps, "warmup": max(args.warmup, 1),
         "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic", "config": {"workload": workload, "step": step, "iterations_per_step": its,
+        "data": "synthetic", "full": args.full, "config": {"workload": workload, "step": step, "iterations_per_step": its,
                                         "start_vector": "reference default: std::mt19937() + std::normal_distribution, normalised (lanczos.hpp:214-218)",
                                         "note": "per-launch HIP events are on in the timed region (they cost launch-bound solves 15-25 %)"},
         "algorithmic_gbs_per_gpu": total_bytes * args.steps / dt / 1e9,
@@ -376,7 +387,7 @@ def other_config(args):
         out["without_per_launch_events"] = {"value": args.steps * its / dt_plain, "ms_per_step": dt_plain / args.steps * 1e3,
                                             "hbm_roofline_frac_whole_step": total_bytes * args.steps / dt_plain / 1e9 / HBM_PEAK_GBS,
                                             "note": "the same steps repeated with the per-launch HIP events off"}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import cref
         from oracle import krylov_oracle as ko
 
@@ -576,7 +587,7 @@ def main():
     # the same steps once more WITHOUT the per-launch HIP events (they are free at 2 s per solve and cost a launch-bound solve
     # 15-25 %: 128^3 runs at 12.5 ms with them and 10.4 ms without): reported next to `value`, never instead of it
     dt_plain = None
-    if dt / args.steps < 0.5:
+    if args.full and dt / args.steps < 0.5:
         barrier()
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -633,7 +644,7 @@ def main():
     # commit after the recorded one changes those files (`git diff --quiet <commit> HEAD -- ...`; None without a repository).
     traffic = traffic_src = traffic_commit = traffic_is_current = traffic_is_head = None
     tfile = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    if os.path.exists(tfile):
+    if args.full and os.path.exists(tfile):
         try:
             t = json.load(open(tfile))
             key = f"laplacian3d_{n}_m{m}_gpus{world}"
@@ -665,6 +676,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": f"7-pt Laplacian {n}^3 (N={N}, nnz={nnz_global}) CSR int32/fp64, Lanczos m={m} "
                             f"full re-orthogonalisation ({'sequential' if args.sequential else 'batched'} Gram-Schmidt), "
@@ -705,7 +717,7 @@ def main():
             out["multi_gpu"] = multi
         if rehearsal:
             out["rehearsal"] = "BENCH_REHEARSAL=1: ranks share device 0, gloo process group: NOT a measurement"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, same_input = cpu_baseline(n, m, init, N, nnz_global, m)
             if same_input is not None:
                 # the same input on both sides: the oracle's coefficients next to the device's (a check, not a number)

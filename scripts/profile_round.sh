@@ -16,12 +16,15 @@ L1="TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_s
 scripts/profile_passes.sh headline "FETCH_SIZE;WRITE_SIZE" python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline || exit $?
 scripts/profile_passes.sh config3 "FETCH_SIZE;WRITE_SIZE;$L2;$L1" python3 scripts/run_config3.py 1000000 80 2 || exit $?
 PASS_TIMEOUT=600 scripts/profile_passes.sh config5 "FETCH_SIZE;WRITE_SIZE;$L2" python3 scripts/run_config5.py 20000000 10 4 6 || exit $?
+OUT=$(sed -n 's/^OUT=//p' scripts/profile_passes.sh)  # the folder the passes above wrote to: one place names it
+[ -d "$OUT" ] || exit 1
 run() { echo "== $*" >&2; timeout -k 10 500 "$@" || exit $?; }
-run python3 bench.py --steps 5 --warmup 2 > gpurun_out/${RND}_bench.json 2> gpurun_out/${RND}_bench.err
-run python3 bench.py --grid-edge 128 --krylov-steps 50 --steps 20 --warmup 5 > gpurun_out/${RND}_bench_128cubed.json 2> gpurun_out/${RND}_bench_128cubed.err
-run python3 bench.py --workload config3 --steps 5 --warmup 2 > gpurun_out/${RND}_bench_config3.json 2> gpurun_out/${RND}_bench_config3.err
-run python3 bench.py --workload config1 --steps 5 --warmup 2 > gpurun_out/${RND}_bench_config1.json 2> gpurun_out/${RND}_bench_config1.err
-run python3 bench.py --workload config5 --steps 2 --warmup 1 > gpurun_out/${RND}_bench_config5.json 2> gpurun_out/${RND}_bench_config5.err
-run python3 scripts/run_config3.py 1000000 80 3 --no-profile --json gpurun_out/${RND}_config3_1gpu.json > gpurun_out/${RND}_config3.log 2>&1
-run python3 scripts/run_config5.py --json gpurun_out/${RND}_config5_1gpu.json > gpurun_out/${RND}_config5.log 2>&1
-tail -c 400 gpurun_out/${RND}_bench.json
+# the bench lines for the record carry the CPU baselines and the repeat without per-launch events: --full
+run python3 bench.py --full --steps 5 --warmup 2 > $OUT/${RND}_bench.json 2> $OUT/${RND}_bench.err
+run python3 bench.py --full --grid-edge 128 --krylov-steps 50 --steps 20 --warmup 5 > $OUT/${RND}_bench_128cubed.json 2> $OUT/${RND}_bench_128cubed.err
+run python3 bench.py --full --workload config3 --steps 5 --warmup 2 > $OUT/${RND}_bench_config3.json 2> $OUT/${RND}_bench_config3.err
+run python3 bench.py --full --workload config1 --steps 5 --warmup 2 > $OUT/${RND}_bench_config1.json 2> $OUT/${RND}_bench_config1.err
+run python3 bench.py --full --workload config5 --steps 2 --warmup 1 > $OUT/${RND}_bench_config5.json 2> $OUT/${RND}_bench_config5.err
+run python3 scripts/run_config3.py 1000000 80 3 --no-profile --json $OUT/${RND}_config3_1gpu.json > $OUT/${RND}_config3.log 2>&1
+run python3 scripts/run_config5.py --json $OUT/${RND}_config5_1gpu.json > $OUT/${RND}_config5.log 2>&1
+tail -c 400 $OUT/${RND}_bench.json
