@@ -126,6 +126,7 @@ SIGNATURES = {
     "eigenex_basis_graph_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "eigenex_arnoldi_enqueue": (C.c_int, [_vp, C.c_int]),
     "eigenex_lanczos_restart": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double]),
+    "eigenex_arnoldi_restart": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int]),
     "eigenex_lanczos_state": (C.c_int, [_vp, C.POINTER(State), _dp, _dp]),
     "eigenex_arnoldi_state": (C.c_int, [_vp, C.POINTER(State), _dp, C.c_int]),
     "eigenex_ritz_vectors": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int64]),
@@ -632,6 +633,22 @@ class Basis:
 
     def arnoldi_enqueue(self, ncalls: int):
         _chk(lib().eigenex_arnoldi_enqueue(self.h, ncalls))
+
+    def arnoldi_restart(self, Q, B, nkeep: int | None = None, ldq: int | None = None, ldb: int | None = None):
+        """Krylov-Schur restart: keep V_m Q (Q: m x nkeep) with the projected matrix B ((nkeep+1) x nkeep), both in the
+        basis' scalar type.  nkeep / ldq / ldb default to the arrays' shapes (given explicitly by the argument tests)."""
+        Q = np.asfortranarray(Q, self.dtype)
+        B = np.asfortranarray(B, self.dtype)
+        _chk(lib().eigenex_arnoldi_restart(self.h, Q.shape[1] if nkeep is None else nkeep, _d(Q), Q.shape[0] if ldq is None else ldq, _d(B),
+                                           B.shape[0] if ldb is None else ldb))
+
+    def arnoldi_projected(self):
+        """state and the (nalpha + 1) x nalpha projected matrix as the device stores it, coupling row included"""
+        st = State()
+        ldh = self.capacity + 2
+        H = np.zeros((self.capacity + 1, ldh), self.dtype)  # row c = column c of H
+        _chk(lib().eigenex_arnoldi_state(self.h, C.byref(st), _d(H.view(np.float64)), ldh))
+        return st, H[: st.nalpha, : st.nalpha + 1].T.copy()
 
     def lanczos_state(self):
         st = State()

@@ -548,7 +548,10 @@ __device__ __forceinline__ void arnoldi_begin_record(const InlineArnoldiBegin& a
     ab.ctrl->stopped = 1;
     return;
   }
-  ab.H[((int64_t)(k - 1) * ab.ldh + k) * ab.es] = res;  // arnoldi.hpp:363 (imaginary part stays 0)
+  if (ab.ctrl->keep_coupling)
+    ab.ctrl->keep_coupling = 0;  // first step after a Krylov-Schur restart: H[k][k-1] = residue * Q[m-1][k-1] is already there
+  else
+    ab.H[((int64_t)(k - 1) * ab.ldh + k) * ab.es] = res;  // arnoldi.hpp:363 (imaginary part stays 0)
   ab.ctrl->scale = scale;
 }
 
@@ -1665,7 +1668,10 @@ __global__ void k_arnoldi_begin(Ctrl* ctrl, double threshold, int64_t n_global, 
     ctrl->stopped = 1;
     return;
   }
-  H[((int64_t)(k - 1) * ldh + k) * es] = ctrl->residue;  // arnoldi.hpp:363 (imaginary part stays 0)
+  if (ctrl->keep_coupling)
+    ctrl->keep_coupling = 0;  // first step after a Krylov-Schur restart (see arnoldi_begin_record)
+  else
+    H[((int64_t)(k - 1) * ldh + k) * es] = ctrl->residue;  // arnoldi.hpp:363 (imaginary part stays 0)
   ctrl->scale = 1.0 / ctrl->residue;                     // arnoldi.hpp:365
 }
 
@@ -1766,6 +1772,22 @@ __global__ void k_restart_fix(Ctrl* ctrl, double* alpha, double* beta, int m, in
   ctrl->nvec = nkeep + 1;
   ctrl->nalpha = nkeep + 1;
   ctrl->nbeta = nkeep;
+}
+
+// Krylov-Schur restart: the kept vectors V_m Q sit in columns 0..nkeep-1 and A (V_m Q) = (V_m Q) B_top + w b^T with
+// b = residue * Q[m-1, :], so the projected matrix is B: full in rows 0..nkeep-1, the coupling row b in row nkeep, nothing below.
+// The next step would store the residue at H[nkeep][nkeep-1] (k_arnoldi_begin); keep_coupling tells it to leave b's last entry.
+// Everything of H outside B is zeroed: the steps that follow write the Hessenberg part of their columns only.
+__global__ __launch_bounds__(kBlock) void k_arnoldi_restart_fix(Ctrl* ctrl, double* __restrict__ H, int ldh, int ncols, int es,
+                                                                const double* __restrict__ B, int ldb, int nkeep) {
+  const int rows = ldh * es, brows = (nkeep + 1) * es;
+  for (int c = 0; c < ncols; ++c)
+    for (int i = threadIdx.x; i < rows; i += kBlock) H[(int64_t)c * rows + i] = (c < nkeep && i < brows) ? B[(int64_t)c * ldb * es + i] : 0.0;
+  if (threadIdx.x != 0) return;
+  ctrl->stopped = 0;
+  ctrl->nvec = nkeep;
+  ctrl->nalpha = nkeep;
+  ctrl->keep_coupling = 1;
 }
 
 __global__ void k_accept_vector(Ctrl* ctrl) {
@@ -1893,6 +1915,49 @@ __global__ __launch_bounds__(kBlock) void k_ritz(const double* __restrict__ V, i
       if (e < nev) {
         const double t = block_sum(nrm[e], lds4);
         if (threadIdx.x == 0) partials[(int64_t)e * pstride + blockIdx.x] = t;
+      }
+    }
+  }
+}
+
+// ---- compression of a complex basis with complex coefficients: X = V * C, up to 8 columns per pass ----
+// The Krylov-Schur restart of a complex Arnoldi run (library.hip: eigenex_arnoldi_restart).  Same streaming shape as k_ritz: a
+// persistent grid over tiles, one 16-byte non-temporal load = one complex entry per lane, two entries per thread and column,
+// the m loop unrolled by 4 so that 8 independent loads are in flight per lane; the 8 complex coefficients of a basis column
+// (Ct packed [nvec][NE], zero-padded behind nev) sit at a wave-uniform address: one scalar load burst.  Each output entry is
+// summed in registers over m ascending, so nothing is shared between workgroups.  n counts complex entries; ldv, ldx doubles.
+template <int NE>
+__global__ __launch_bounds__(kBlock) void k_compress_z(const double* __restrict__ V, int64_t ldv, int nvec,
+                                                       const double* __restrict__ Ct, int nev, double* __restrict__ X,
+                                                       int64_t ldx, int64_t n, int64_t ntiles) {
+  constexpr int kRows = 2 * kBlock;  // complex entries per tile
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r0 = tile * kRows + threadIdx.x, r1 = r0 + kBlock;
+    const bool in0 = r0 < n, in1 = r1 < n;
+    double2 a0[NE], a1[NE];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) a0[e] = a1[e] = make_double2(0.0, 0.0);
+    const double* vp = V;
+#pragma unroll 4
+    for (int m = 0; m < nvec; ++m, vp += ldv) {
+      const double2 v0 = in0 ? nt_ld_d2(vp + 2 * r0) : make_double2(0.0, 0.0);
+      const double2 v1 = in1 ? nt_ld_d2(vp + 2 * r1) : make_double2(0.0, 0.0);
+      const double* cp = Ct + (int64_t)m * (2 * NE);
+#pragma unroll
+      for (int e = 0; e < NE; ++e) {
+        const double cr = cp[2 * e], ci = cp[2 * e + 1];
+        a0[e].x = fma(-ci, v0.y, fma(cr, v0.x, a0[e].x));  // (cr + i ci)(vx + i vy), m ascending
+        a0[e].y = fma(ci, v0.x, fma(cr, v0.y, a0[e].y));
+        a1[e].x = fma(-ci, v1.y, fma(cr, v1.x, a1[e].x));
+        a1[e].y = fma(ci, v1.x, fma(cr, v1.y, a1[e].y));
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+      if (e < nev) {
+        double* xp = X + (int64_t)e * ldx;
+        if (in0) st2(xp + 2 * r0, a0[e]);
+        if (in1) st2(xp + 2 * r1, a1[e]);
       }
     }
   }
@@ -2293,6 +2358,10 @@ void launch_restart_fix(hipStream_t s, Ctrl* ctrl, double* alpha, double* beta, 
   hipLaunchKernelGGL(k_restart_fix, dim3(1), dim3(64), 0, s, ctrl, alpha, beta, m, nkeep, coupling_last);
 }
 
+void launch_arnoldi_restart_fix(hipStream_t s, Ctrl* ctrl, double* H, int ldh, int ncols, int es, const double* B_dev, int ldb, int nkeep) {
+  hipLaunchKernelGGL(k_arnoldi_restart_fix, dim3(1), dim3(kBlock), 0, s, ctrl, H, ldh, ncols, es, B_dev, ldb, nkeep);
+}
+
 void launch_accept_vector(hipStream_t s, Ctrl* ctrl) {
   hipLaunchKernelGGL(k_accept_vector, dim3(1), dim3(64), 0, s, ctrl);
 }
@@ -2314,6 +2383,12 @@ void launch_ritz(hipStream_t s, const double* V, int64_t ldv, int nvec, const do
     hipLaunchKernelGGL((k_ritz<16, false>), dim3(grid), dim3(kBlock), 0, s, V, ldv, nvec, St_dev, nev, X, ldx, n, ntiles, partials, pstride);
   else
     hipLaunchKernelGGL((k_ritz<8, true>), dim3(grid), dim3(kBlock), 0, s, V, ldv, nvec, St_dev, nev, X, ldx, n, ntiles, partials, pstride);
+}
+
+void launch_compress_z(hipStream_t s, const double* V, int64_t ldv, int nvec, const double* Ct_dev, int nev, double* X, int64_t ldx,
+                       int64_t n, int grid) {
+  const int64_t ntiles = (n + 2 * kBlock - 1) / (2 * kBlock);
+  hipLaunchKernelGGL((k_compress_z<8>), dim3(grid), dim3(kBlock), 0, s, V, ldv, nvec, Ct_dev, nev, X, ldx, n, ntiles);
 }
 
 void launch_check_csr(hipStream_t s, const int32_t* rowptr, const int32_t* col, int64_t n, int64_t nnz, int64_t ncols, unsigned int* bad) {

@@ -19,7 +19,9 @@ struct Ctrl {
   int nbeta;       // beta_.size()
   int iterations;  // iterations_
   int calls_true;  // calls that returned true
-  int pad0, pad1;
+  int keep_coupling;  // set by a Krylov-Schur restart (k_arnoldi_restart_fix): the next Arnoldi begin leaves H[k][k-1] as the
+                      // restart wrote it instead of storing the residue there, and clears the flag.  0 everywhere else.
+  int pad1;
   double scale;    // 1/beta_k or 1/residue_: factor applied to the operator input
   double residue;  // Arnoldi residue_
 };
@@ -287,6 +289,9 @@ void launch_reduce_decide(hipStream_t s, const double* partials, int nblocks, do
 void launch_arnoldi_tail(hipStream_t s, const double* partials, int nblocks, Ctrl* ctrl, const Ctrl* pass2, double* h, const double* h2,
                          int ncoef, const double* nrm2_first, double* nrm2_final, double* H, int ldh, int es);
 void launch_restart_fix(hipStream_t s, Ctrl* ctrl, double* alpha, double* beta, int m, int nkeep, double coupling_last);
+// Krylov-Schur restart of an Arnoldi state: columns 0..nkeep-1 of H (ldh x ncols) = B ((nkeep+1) x nkeep, leading dimension ldb
+// entries, es doubles per entry), everything else of H zeroed; nvec = nalpha = nkeep, stopped = 0, keep_coupling = 1
+void launch_arnoldi_restart_fix(hipStream_t s, Ctrl* ctrl, double* H, int ldh, int ncols, int es, const double* B_dev, int ldb, int nkeep);
 // vector accepted into the basis: ++nvec  (after the operator has been applied with `scale`)
 void launch_accept_vector(hipStream_t s, Ctrl* ctrl);
 
@@ -303,6 +308,10 @@ void launch_laplacian3d(hipStream_t s, int64_t n, int64_t rb, int64_t re, int64_
 // stride of the basis (rows behind n are written as zeros).
 void launch_ritz(hipStream_t s, const double* V, int64_t ldv, int nvec, const double* St_dev, int ne_pack, int nev,
                  double* X, int64_t ldx, int64_t n, double* partials, int pstride, int grid);
+// Compression of a COMPLEX basis with COMPLEX coefficients in one pass (Krylov-Schur restart): X[:, e] = sum_m Ct[m*8 + e] * V[:, m],
+// e < nev <= 8; V, X and Ct hold (re, im) pairs, Ct is packed [nvec][8] and zero-padded, n counts complex entries, ldv / ldx doubles.
+void launch_compress_z(hipStream_t s, const double* V, int64_t ldv, int nvec, const double* Ct_dev, int nev, double* X, int64_t ldx,
+                       int64_t n, int grid);
 // per column: first local ENTRY with |z| > 0 (n if none) and its value: out[3e] = index, out[3e+1..2] = (re, im);
 // es = doubles per entry, ldx in doubles
 void launch_first_nonzero(hipStream_t s, const double* X, int64_t ldx, int ncol, int64_t n, int es, double* out);

@@ -406,6 +406,8 @@ struct eigenex_basis_s {
   PinnedBuffer<Ctrl> pin_ctrl;
   std::vector<StepGraph> graphs;
   uint64_t graph_clock = 0;
+  bool h_restarted = false;  // a Krylov-Schur restart has left a full block in H: eigenex_basis_clear zeroes H again (Arnoldi steps only
+                             // ever write the Hessenberg part, and eigenex_arnoldi_state hands out whole columns)
   bool fuse_alpha = true;  // Lanczos on more than one shard: alpha of the newest vector travels with the next step's dots (lanczos_call)
   int hbuf_len() const { return 8 * maxcols + 64; }
   int base_fused() const { return 4 * maxcols + 16; }  // [alpha (2 slots), g (es*ncols), G (es*ncols)]: one all-reduce
@@ -3014,6 +3016,7 @@ int eigenex_basis_clone(eigenex_basis_t src, eigenex_basis_t* out) {
   b->shift = src->shift, b->shift_im = src->shift_im, b->threshold = src->threshold, b->interval = src->interval;
   b->ortho_mode = src->ortho_mode, b->cur = src->cur, b->fn = src->fn, b->fn_user = src->fn_user;
   b->fuse_alpha = src->fuse_alpha;
+  b->h_restarted = src->h_restarted;
   for (size_t i = 0; i < b->sh.size(); ++i) {
     BasisShard &d = b->sh[i], &s = src->sh[i];
     d.g_vec = s.g_vec, d.g_spmv = s.g_spmv, d.g_spmv_int = s.g_spmv_int, d.spmv_flags = s.spmv_flags;
@@ -3132,6 +3135,9 @@ int eigenex_basis_clear(eigenex_basis_t b) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
   HIPCHK(hipSetDevice(b->ctx->device));
   for (auto& s : b->sh) HIPCHK(hipMemsetAsync(s.ctrl, 0, sizeof(Ctrl), b->ctx->stream));
+  if (b->h_restarted)
+    for (auto& s : b->sh) HIPCHK(hipMemsetAsync(s.H, 0, sizeof(double) * (size_t)b->ldh * (b->cap + 1) * s.es, b->ctx->stream));
+  b->h_restarted = false;
   StepCursor& cur = b->cur;
   cur.started = false, cur.h_nvec = 0, cur.alpha_pending = cur.alpha_pending_inline = false, cur.tail_pending = false;
   return 0;
@@ -3359,6 +3365,61 @@ int eigenex_arnoldi_enqueue(eigenex_basis_t b, int ncalls) {
   if (!b || ncalls < 0) return fail(EIGENEX_ERR_ARG, "bad argument");
   HIPCHK(hipSetDevice(b->ctx->device));
   return enqueue_steps(b, ncalls, 1);
+}
+
+// Krylov-Schur restart (Stewart, SIAM J. Matrix Anal. Appl. 23 (2001) 601): with A V_m = V_m H_m + w e_m^T on the device, any
+// orthonormal Q whose span is invariant under H_m gives the Krylov decomposition A (V_m Q) = (V_m Q) B_top + (w / |w|) b^T with b =
+// residue * Q[m-1, :]: the basis becomes V_m Q, the projected matrix B = [B_top; b^T], and w, residue and the scale stay what
+// they are, so the next Arnoldi step normalises w into column nkeep and orthogonalises A w against the new basis as usual.
+// The products are formed in the free columns m.. of the slab (capacity >= m + nkeep) and copied down.  Synchronises.
+int eigenex_arnoldi_restart(eigenex_basis_t b, int nkeep, const double* Q, int ldq, const double* B, int ldb) {
+  if (!b || nkeep < 1 || !Q || !B) return fail(EIGENEX_ERR_ARG, "eigenex_arnoldi_restart: bad argument");
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  Ctrl ct;
+  CHK(sync_ctrl(b, &ct));
+  const int m = ct.nvec;
+  if (ct.stopped || m < 1 || ct.nalpha != m || ct.nbeta != 0) return fail(EIGENEX_ERR_STATE, "eigenex_arnoldi_restart: no complete Arnoldi state to restart from");
+  if (nkeep >= m || ldq < m || ldb < nkeep + 1) return fail(EIGENEX_ERR_ARG, "eigenex_arnoldi_restart: nkeep/ldq/ldb out of range");
+  if (b->cap < m + nkeep) return fail(EIGENEX_ERR_STATE, "eigenex_arnoldi_restart: capacity must be >= nvec + nkeep (scratch columns)");
+  const int es = b->es;
+  // all coefficient blocks at once: block ch holds columns [E ch, E ch + E) of Q, packed [m][E] entries, zero-padded.
+  // Real basis: k_ritz, 16 columns per pass; complex basis: k_compress_z, 8 complex columns per pass.
+  const int E = es == 2 ? 8 : 16;
+  const int nchunk = (nkeep + E - 1) / E;
+  const size_t block = (size_t)m * E * es;
+  std::vector<double> Qt(nchunk * block, 0.0);
+  for (int e = 0; e < nkeep; ++e)
+    for (int j = 0; j < m; ++j)
+      for (int p = 0; p < es; ++p) Qt[(e / E) * block + ((size_t)j * E + e % E) * es + p] = Q[((size_t)e * ldq + j) * es + p];
+  std::vector<double> Bt((size_t)(nkeep + 1) * nkeep * es);
+  for (int e = 0; e < nkeep; ++e)
+    std::memcpy(&Bt[(size_t)e * (nkeep + 1) * es], B + (size_t)e * ldb * es, sizeof(double) * (nkeep + 1) * es);
+  DeviceBuffer<double> d_Q, d_B;
+  HIPCHK(d_Q.alloc(Qt.size()));
+  HIPCHK(d_B.alloc(Bt.size()));
+  HIPCHK(hipMemcpyAsync(d_Q, Qt.data(), sizeof(double) * Qt.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_B, Bt.data(), sizeof(double) * Bt.size(), hipMemcpyHostToDevice, c->stream));
+  for (int ch = 0; ch < nchunk; ++ch) {
+    const int e0 = ch * E, ne = std::min(E, nkeep - e0);
+    for (auto& s : b->sh) {
+      ProfScope ps(c, EIGENEX_K_RITZ, 8.0 * s.nd * m + 8.0 * s.nd * ne);
+      double* out = s.V + (size_t)(m + e0) * s.ldd;
+      if (es == 2)
+        launch_compress_z(c->stream, s.V, s.ldd, m, d_Q + ch * block, ne, out, s.ldd, s.nloc, s.g_vec);
+      else
+        launch_ritz(c->stream, s.V, s.ldd, m, d_Q + ch * block, E, ne, out, s.ldd, s.nd, s.partials, s.pstride, s.g_vec);
+    }
+  }
+  for (auto& s : b->sh) {
+    HIPCHK(hipMemcpyAsync(s.V, s.V + (size_t)m * s.ldd, sizeof(double) * (size_t)s.ldd * nkeep, hipMemcpyDeviceToDevice, c->stream));
+    launch_arnoldi_restart_fix(c->stream, s.ctrl, s.H, b->ldh, b->cap + 1, es, d_B, nkeep + 1, nkeep);
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));  // the staging buffers are released behind this
+  b->cur.h_nvec = nkeep;
+  b->cur.tail_pending = false;
+  b->h_restarted = true;
+  return 0;
 }
 
 int eigenex_lanczos_state(eigenex_basis_t b, eigenex_state_t* st, double* alpha, double* beta) {

@@ -9,6 +9,7 @@
 //   eigenex_zlanczos_solver_*  LanczosEigenSolver<std::complex<double>>
 //   eigenex_arnoldi_solver_*   ArnoldiEigenSolver<double>
 //   eigenex_zarnoldi_solver_*  ArnoldiEigenSolver<std::complex<double>>
+// plus eigenex_[z]trlanczos_solver_* (ThickRestartLanczosEigenSolver) and eigenex_[z]kschur_solver_* (KrylovSchurEigenSolver).
 // Complex data cross this boundary as interleaved (re, im) doubles.
 #include <complex>
 #include <cstring>
@@ -18,6 +19,7 @@
 
 #include "cmpt/eigen_ex/arnoldi.hpp"
 #include "cmpt/eigen_ex/block_operator.hpp"
+#include "cmpt/eigen_ex/krylov_schur.hpp"
 #include "cmpt/eigen_ex/lanczos.hpp"
 #include "cmpt/eigen_ex/lanczos_function.hpp"
 #include "cmpt/eigen_ex/thick_restart_lanczos.hpp"
@@ -278,6 +280,70 @@ int tr_get(void* p, double* eigenvalues, double* residuals, double* eigenvectors
     if (residuals) std::copy(es.residuals().begin(), es.residuals().end(), residuals);
     if (eigenvectors && es.eigenvectors().size())
       std::memcpy(eigenvectors, es.eigenvectors().data(), sizeof(S) * (size_t)es.eigenvectors().size());
+  });
+}
+
+// ---- Krylov-Schur (krylov_schur.hpp) ---------------------------------------------------------------
+template <class S>
+int ks_set(void* p, const char* key, double v, double v_im) {
+  return guard([&] {
+    auto& es = static_cast<Box<KrylovSchurEigenSolver<S>>*>(p)->es;
+    const std::string k(key);
+    if (k == "numberOfEigenvalues") es.setNumberOfEigenvalues((Index)v);
+    else if (k == "maxBasisSize") es.setMaxBasisSize((Index)v);
+    else if (k == "keepSize") es.setKeepSize((Index)v);
+    else if (k == "tolerance") es.setTolerance(v);
+    else if (k == "maxRestarts") es.setMaxRestarts((Index)v);
+    else if (k == "computeEigenvectorsOn") es.setComputeEigenvectorsOn(v != 0.0);
+    else if (k == "eigenvalueShift") {
+      S sh;
+      assign_shift(sh, v, v_im);
+      es.setEigenvalueShift(sh);
+    }
+    else if (k == "threshold") es.setThreshold(v);
+    else throw LanczosException("unknown setting: " + k);
+  });
+}
+// sizes: [neigenvalues, eigvec_rows, eigvec_cols, restarts, operatorApplications, nlog, info]
+template <class S>
+int ks_sizes(void* p, int64_t* out) {
+  return guard([&] {
+    auto& es = static_cast<Box<KrylovSchurEigenSolver<S>>*>(p)->es;
+    out[0] = es.eigenvalues().size();
+    out[1] = es.eigenvectors().rows();
+    out[2] = es.eigenvectors().cols();
+    out[3] = es.restarts();
+    out[4] = es.operatorApplications();
+    out[5] = (int64_t)es.log().size();
+    out[6] = (int64_t)es.info();
+  });
+}
+// eigenvalues and eigenvectors: (re, im) pairs for either instantiation
+template <class S>
+int ks_get(void* p, double* eigenvalues, double* residuals, double* eigenvectors) {
+  return guard([&] {
+    auto& es = static_cast<Box<KrylovSchurEigenSolver<S>>*>(p)->es;
+    if (eigenvalues && es.eigenvalues().size())
+      std::memcpy(eigenvalues, es.eigenvalues().data(), sizeof(std::complex<double>) * (size_t)es.eigenvalues().size());
+    if (residuals) std::copy(es.residuals().begin(), es.residuals().end(), residuals);
+    if (eigenvectors && es.eigenvectors().size())
+      std::memcpy(eigenvectors, es.eigenvectors().data(), sizeof(std::complex<double>) * (size_t)es.eigenvectors().size());
+  });
+}
+// the host part of one restart on its own (no GPU): see eigenex_solver_krylov_schur_basis
+template <class T>
+int ks_basis(const double* H, int ldh, int m, int keep, double residue, int* keep_out, double* Q, double* B, double* theta) {
+  return guard([&] {
+    if (m < 2 || ldh < m || keep < 1) throw LanczosException("krylov_schur_basis: m >= 2, ldh >= m and keep >= 1 are required");
+    const T* h = reinterpret_cast<const T*>(H);
+    std::vector<small_eigen::cplx> th, S;
+    if (!small_eigen::ritz_pairs_by_magnitude(h, ldh, m, th, S)) throw LanczosException("QR iteration did not converge");
+    std::vector<T> q, b;
+    const int k = small_eigen::krylov_schur_basis<T>(h, ldh, m, keep, residue, th, S, q, b);
+    *keep_out = k;
+    std::memcpy(Q, q.data(), sizeof(T) * q.size());
+    std::memcpy(B, b.data(), sizeof(T) * b.size());
+    if (theta) std::memcpy(theta, th.data(), sizeof(small_eigen::cplx) * th.size());
   });
 }
 
@@ -581,6 +647,42 @@ int eigenex_solver_hessenberg_values_real(int n, const double* H, double* values
   int PFX##get(void* p, double* ev, double* res, double* X) { return tr_get<S>(p, ev, res, X); }                        \
   const char* PFX##log_line(void* p, int64_t i) { return sv_log_line<ThickRestartLanczosEigenSolver<S>>(p, i); }
 
+#define EIGENEX_KSCHUR_FAMILY(PFX, S)                                                                                   \
+  void* PFX##create(void) {                                                                                             \
+    try {                                                                                                               \
+      return new Box<KrylovSchurEigenSolver<S>>();                                                                      \
+    } catch (const std::exception& e) {                                                                                 \
+      g_serr = e.what();                                                                                                \
+      return nullptr;                                                                                                   \
+    }                                                                                                                   \
+  }                                                                                                                     \
+  void PFX##destroy(void* p) { delete static_cast<Box<KrylovSchurEigenSolver<S>>*>(p); }                                \
+  int PFX##set_device_operator(void* p, eigenex_context_t ctx, eigenex_csr_t csr) {                                     \
+    return sv_set_device_operator<KrylovSchurEigenSolver<S>>(p, ctx, csr);                                              \
+  }                                                                                                                     \
+  int PFX##set_host_operator(void* p, eigenex_context_t ctx, eigenex_matvec_fn fn, void* user, int64_t height) {        \
+    return sv_set_host_operator<KrylovSchurEigenSolver<S>>(p, ctx, fn, user, height);                                   \
+  }                                                                                                                     \
+  int PFX##set_initial_vector(void* p, const double* v, int64_t n) {                                                    \
+    return guard([&] { static_cast<Box<KrylovSchurEigenSolver<S>>*>(p)->es.setInitialVector(make_vector<S>(v, n)); });  \
+  }                                                                                                                     \
+  int PFX##set(void* p, const char* key, double v, double v_im) { return ks_set<S>(p, key, v, v_im); }                  \
+  int PFX##compute(void* p) { return guard([&] { static_cast<Box<KrylovSchurEigenSolver<S>>*>(p)->es.compute(); }); }   \
+  int PFX##sizes(void* p, int64_t* out) { return ks_sizes<S>(p, out); }                                                 \
+  int PFX##get(void* p, double* ev, double* res, double* X) { return ks_get<S>(p, ev, res, X); }                        \
+  const char* PFX##log_line(void* p, int64_t i) { return sv_log_line<KrylovSchurEigenSolver<S>>(p, i); }
+
+// The dense host part of one Krylov-Schur restart (small_eigen::krylov_schur_basis), callable without a GPU.  H: the projected
+// matrix, column-major m x m with leading dimension ldh (is_complex: (re, im) pairs), Hessenberg or with a full leading block.
+// Out: *keep_out (keep, or keep + 1 when a real matrix's conjugate pair would have been split), Q (m x *keep_out, leading
+// dimension m), B ((*keep_out + 1) x *keep_out, leading dimension *keep_out + 1; last row = residue * Q[m-1, :]) -- room for
+// keep + 1 columns each -- and theta (optional): all m Ritz values as (re, im) pairs, |theta| descending.
+int eigenex_solver_krylov_schur_basis(int is_complex, const double* H, int ldh, int m, int keep, double residue, int* keep_out,
+                                      double* Q, double* B, double* theta) {
+  return is_complex ? ks_basis<std::complex<double>>(H, ldh, m, keep, residue, keep_out, Q, B, theta)
+                    : ks_basis<double>(H, ldh, m, keep, residue, keep_out, Q, B, theta);
+}
+
 int eigenex_solver_exp_eigens(int is_complex, double x_re, double x_im, int64_t n, int64_t nev, const double* eivals,
                               const double* eivecs, int64_t max_expand, const double* in, double* out) {
   return is_complex ? fn_exp_eigens<std::complex<double>>(x_re, x_im, n, nev, eivals, eivecs, max_expand, in, out)
@@ -596,6 +698,8 @@ int eigenex_solver_exp_taylor(int is_complex, eigenex_context_t ctx, eigenex_csr
 
 EIGENEX_TRLANCZOS_FAMILY(eigenex_trlanczos_solver_, double)
 EIGENEX_TRLANCZOS_FAMILY(eigenex_ztrlanczos_solver_, std::complex<double>)
+EIGENEX_KSCHUR_FAMILY(eigenex_kschur_solver_, double)
+EIGENEX_KSCHUR_FAMILY(eigenex_zkschur_solver_, std::complex<double>)
 EIGENEX_LANCZOS_FAMILY(eigenex_lanczos_solver_, double)
 EIGENEX_LANCZOS_FAMILY(eigenex_zlanczos_solver_, std::complex<double>)
 EIGENEX_ARNOLDI_FAMILY(eigenex_arnoldi_solver_, double)

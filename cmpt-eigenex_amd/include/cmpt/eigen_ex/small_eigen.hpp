@@ -15,6 +15,7 @@
 #include <cmath>
 #include <complex>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 namespace cmpt {
@@ -437,6 +438,211 @@ inline bool hessenberg_real_values(std::vector<double>& H, int n, std::vector<cp
     } while (l < nn - 1);
   }
   return ok;
+}
+
+// Eigen-decomposition of a GENERAL complex matrix A (column-major n x n, overwritten): Householder reduction to
+// Hessenberg form U^H A U, the QR iteration above, vectors = U X (unit-norm columns).  A matrix that is already
+// Hessenberg passes through untouched (no reflector is applied), so this is hessenberg() for the first cycle of a
+// Krylov-Schur run and the general case for the later ones, whose leading block is full.
+inline bool general(std::vector<cplx>& A, int n, std::vector<cplx>& values, std::vector<cplx>* vectors) {
+  auto a = [&](int r, int c) -> cplx& { return A[static_cast<std::size_t>(r) + static_cast<std::size_t>(c) * n]; };
+  std::vector<cplx> U;
+  bool reflected = false;
+  std::vector<cplx> v(static_cast<std::size_t>(n));
+  for (int k = 0; k + 2 < n; ++k) {
+    double tail2 = 0.0;
+    for (int i = k + 2; i < n; ++i) tail2 += std::norm(a(i, k));
+    if (tail2 == 0.0) continue;  // column already Hessenberg
+    const double nrm = std::sqrt(tail2 + std::norm(a(k + 1, k)));
+    const double a0 = std::abs(a(k + 1, k));
+    const cplx alpha = a0 > 0.0 ? -(a(k + 1, k) / a0) * nrm : cplx(-nrm);
+    double vn = 0.0;
+    for (int i = k + 1; i < n; ++i) {
+      v[static_cast<std::size_t>(i)] = a(i, k) - (i == k + 1 ? alpha : cplx(0.0));
+      vn += std::norm(v[static_cast<std::size_t>(i)]);
+    }
+    vn = std::sqrt(vn);
+    for (int i = k + 1; i < n; ++i) v[static_cast<std::size_t>(i)] /= vn;
+    // A <- P A P with P = I - 2 v v^H (Hermitian, unitary)
+    for (int c = k; c < n; ++c) {
+      cplx d = 0.0;
+      for (int i = k + 1; i < n; ++i) d += std::conj(v[static_cast<std::size_t>(i)]) * a(i, c);
+      d *= 2.0;
+      for (int i = k + 1; i < n; ++i) a(i, c) -= d * v[static_cast<std::size_t>(i)];
+    }
+    for (int r = 0; r < n; ++r) {
+      cplx d = 0.0;
+      for (int j = k + 1; j < n; ++j) d += a(r, j) * v[static_cast<std::size_t>(j)];
+      d *= 2.0;
+      for (int j = k + 1; j < n; ++j) a(r, j) -= d * std::conj(v[static_cast<std::size_t>(j)]);
+    }
+    a(k + 1, k) = alpha;
+    for (int i = k + 2; i < n; ++i) a(i, k) = 0.0;
+    if (vectors) {  // U <- U P
+      if (!reflected) {
+        U.assign(static_cast<std::size_t>(n) * n, cplx(0.0));
+        for (int i = 0; i < n; ++i) U[static_cast<std::size_t>(i) * n + i] = 1.0;
+      }
+      for (int r = 0; r < n; ++r) {
+        cplx d = 0.0;
+        for (int j = k + 1; j < n; ++j) d += U[static_cast<std::size_t>(r) + static_cast<std::size_t>(j) * n] * v[static_cast<std::size_t>(j)];
+        d *= 2.0;
+        for (int j = k + 1; j < n; ++j) U[static_cast<std::size_t>(r) + static_cast<std::size_t>(j) * n] -= d * std::conj(v[static_cast<std::size_t>(j)]);
+      }
+    }
+    reflected = true;
+  }
+  std::vector<cplx> X;
+  const bool ok = hessenberg(A, n, values, vectors ? &X : nullptr);
+  if (!vectors) return ok;
+  if (!reflected) {
+    vectors->swap(X);
+    return ok;
+  }
+  vectors->assign(static_cast<std::size_t>(n) * n, cplx(0.0));
+  for (int c = 0; c < n; ++c)
+    for (int j = 0; j < n; ++j) {
+      const cplx x = X[static_cast<std::size_t>(j) + static_cast<std::size_t>(c) * n];
+      for (int r = 0; r < n; ++r) (*vectors)[static_cast<std::size_t>(r) + static_cast<std::size_t>(c) * n] += U[static_cast<std::size_t>(r) + static_cast<std::size_t>(j) * n] * x;
+    }
+  return ok;
+}
+
+// Ritz pairs of a projected matrix H (column-major m x m, leading dimension ldh, T = double or cplx; Hessenberg or with a full
+// leading block), ordered by |theta| descending with the stable sort of arnoldi.hpp:813-822.  S: column-major m x m.
+template <class T>
+bool ritz_pairs_by_magnitude(const T* H, int ldh, int m, std::vector<cplx>& theta, std::vector<cplx>& S) {
+  std::vector<cplx> A(static_cast<std::size_t>(m) * m), vals, vecs;
+  for (int c = 0; c < m; ++c)
+    for (int r = 0; r < m; ++r) A[static_cast<std::size_t>(r) + static_cast<std::size_t>(c) * m] = H[static_cast<std::size_t>(r) + static_cast<std::size_t>(c) * ldh];
+  const bool ok = general(A, m, vals, &vecs);
+  std::vector<std::size_t> order(static_cast<std::size_t>(m));
+  for (std::size_t i = 0; i < order.size(); ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&vals](std::size_t x, std::size_t y) { return std::abs(vals[x]) > std::abs(vals[y]); });
+  theta.resize(static_cast<std::size_t>(m));
+  S.resize(static_cast<std::size_t>(m) * m);
+  for (int i = 0; i < m; ++i) {
+    theta[static_cast<std::size_t>(i)] = vals[order[static_cast<std::size_t>(i)]];
+    std::copy(vecs.begin() + static_cast<std::ptrdiff_t>(order[static_cast<std::size_t>(i)] * m),
+              vecs.begin() + static_cast<std::ptrdiff_t>((order[static_cast<std::size_t>(i)] + 1) * m), S.begin() + static_cast<std::ptrdiff_t>(i) * m);
+  }
+  return ok;
+}
+
+namespace ks_detail {
+inline double conj_of(double x) { return x; }
+inline cplx conj_of(const cplx& x) { return std::conj(x); }
+template <class T>
+struct Candidate {
+  std::vector<T> v, fallback;  // fallback (may be empty): tried when v adds no new direction
+};
+// T = double: s is multiplied by the phase that makes Re s and Im s orthogonal with |Re s| >= |Im s| (any phase spans the same
+// plane; this one is the best conditioned for the Gram-Schmidt that follows).  A conjugate pair adds both as directions of their
+// own; a real Ritz value adds Re s and keeps Im s (rounding noise, or the missing direction if the value was half of an
+// unrecognised pair) as the fallback.
+inline void push_candidates(const cplx* s, int m, bool pair, std::vector<Candidate<double>>& out) {
+  double aa = 0.0, bb = 0.0, ab = 0.0;
+  for (int i = 0; i < m; ++i) aa += s[i].real() * s[i].real(), bb += s[i].imag() * s[i].imag(), ab += s[i].real() * s[i].imag();
+  const double phi = 0.5 * std::atan2(-2.0 * ab, aa - bb);  // Re(e^{i phi} s) . Im(e^{i phi} s) = 0, |Re| maximal
+  const cplx ph = std::polar(1.0, phi);
+  std::vector<double> re(static_cast<std::size_t>(m)), im(static_cast<std::size_t>(m));
+  for (int i = 0; i < m; ++i) re[static_cast<std::size_t>(i)] = (s[i] * ph).real(), im[static_cast<std::size_t>(i)] = (s[i] * ph).imag();
+  if (pair) {
+    out.push_back({re, {}});
+    out.push_back({im, {}});
+  } else {
+    out.push_back({re, im});
+  }
+}
+inline void push_candidates(const cplx* s, int m, bool, std::vector<Candidate<cplx>>& out) { out.push_back({std::vector<cplx>(s, s + m), {}}); }
+}  // namespace ks_detail
+
+// Restart basis of a Krylov-Schur cycle (Stewart 2001) from the sorted Ritz pairs of H (ritz_pairs_by_magnitude): an
+// orthonormal Q (m x keep) spanning the invariant subspace of the first `keep` Ritz values, B_top = Q^H H Q formed
+// explicitly (it is not assumed triangular) and the coupling row residue * Q[m-1, :] below it: B is (keep+1) x keep.
+// T = double: Q must be real, so a complex-conjugate pair is never split -- `keep` grows by one if the cut falls
+// between the two (shrinks by one if that would reach m) -- and a pair contributes Re s and Im s, a real Ritz value
+// its (real) vector.  Orthonormalisation: modified Gram-Schmidt applied twice; a direction that vanishes against the ones
+// before it (the second member of an unrecognised pair) is replaced by its imaginary part or dropped.  Returns the final keep
+// (0 only for m = 2 holding one conjugate pair: nothing real can be kept).
+template <class T>
+int krylov_schur_basis(const T* H, int ldh, int m, int keep, double residue, const std::vector<cplx>& theta,
+                       const std::vector<cplx>& S, std::vector<T>& Q, std::vector<T>& B) {
+  constexpr bool real = std::is_same<T, double>::value;
+  keep = std::max(1, std::min(keep, m - 1));
+  double tmax = 0.0;
+  for (int i = 0; i < m; ++i) tmax = std::max(tmax, std::abs(theta[static_cast<std::size_t>(i)]));
+  auto paired = [&](int i) { return real && std::abs(theta[static_cast<std::size_t>(i)].imag()) > 1e-10 * tmax; };
+  std::vector<int> partner(static_cast<std::size_t>(m), -1);
+  std::vector<char> taken(static_cast<std::size_t>(m), 0);
+  for (int i = 0; i < keep; ++i) taken[static_cast<std::size_t>(i)] = 1;
+  int count = keep;
+  for (int i = 0; i < m; ++i) {
+    if (!paired(i)) continue;
+    const cplx want = std::conj(theta[static_cast<std::size_t>(i)]);
+    int best = -1;
+    for (int j = 0; j < m; ++j)
+      if (j != i && paired(j) && (best < 0 || std::abs(theta[static_cast<std::size_t>(j)] - want) < std::abs(theta[static_cast<std::size_t>(best)] - want))) best = j;
+    partner[static_cast<std::size_t>(i)] = best;
+  }
+  for (int i = 0; i < keep; ++i) {
+    const int j = partner[static_cast<std::size_t>(i)];
+    if (j < 0 || taken[static_cast<std::size_t>(j)] || !taken[static_cast<std::size_t>(i)]) continue;
+    if (count + 1 <= m - 1)
+      taken[static_cast<std::size_t>(j)] = 1, ++count;
+    else
+      taken[static_cast<std::size_t>(i)] = 0, --count;
+  }
+  std::vector<ks_detail::Candidate<T>> cand;
+  for (int i = 0; i < m; ++i) {
+    if (!taken[static_cast<std::size_t>(i)]) continue;
+    const int j = partner[static_cast<std::size_t>(i)];
+    if (j >= 0 && j < i && taken[static_cast<std::size_t>(j)]) continue;  // Re s and Im s of the pair are there already
+    ks_detail::push_candidates(S.data() + static_cast<std::size_t>(i) * m, m, j >= 0, cand);
+  }
+  Q.clear();
+  int nq = 0;
+  auto orthonormalise = [&](std::vector<T> v) {
+    double n0 = 0.0;
+    for (const T& x : v) n0 += std::norm(x);
+    for (int pass = 0; pass < 2; ++pass)
+      for (int c = 0; c < nq; ++c) {
+        const T* q = Q.data() + static_cast<std::size_t>(c) * m;
+        T d = T(0.0);
+        for (int r = 0; r < m; ++r) d += ks_detail::conj_of(q[r]) * v[static_cast<std::size_t>(r)];
+        for (int r = 0; r < m; ++r) v[static_cast<std::size_t>(r)] -= d * q[r];
+      }
+    double n1 = 0.0;
+    for (const T& x : v) n1 += std::norm(x);
+    if (!(n1 > 1e-16 * n0) || n1 == 0.0) return false;  // |v| fell by 1e-8: no new direction
+    const double inv = 1.0 / std::sqrt(n1);
+    for (const T& x : v) Q.push_back(x * inv);
+    ++nq;
+    return true;
+  };
+  for (const auto& c : cand) {
+    if (nq == m - 1) break;
+    if (!orthonormalise(c.v) && !c.fallback.empty()) orthonormalise(c.fallback);
+  }
+  keep = nq;
+  B.assign(static_cast<std::size_t>(keep + 1) * keep, T(0.0));
+  std::vector<T> HQ(static_cast<std::size_t>(m));
+  for (int c = 0; c < keep; ++c) {
+    const T* qc = Q.data() + static_cast<std::size_t>(c) * m;
+    for (int r = 0; r < m; ++r) {
+      T acc = T(0.0);
+      for (int j = 0; j < m; ++j) acc += H[static_cast<std::size_t>(r) + static_cast<std::size_t>(j) * ldh] * qc[j];
+      HQ[static_cast<std::size_t>(r)] = acc;
+    }
+    for (int r = 0; r < keep; ++r) {
+      const T* qr = Q.data() + static_cast<std::size_t>(r) * m;
+      T acc = T(0.0);
+      for (int j = 0; j < m; ++j) acc += ks_detail::conj_of(qr[j]) * HQ[static_cast<std::size_t>(j)];
+      B[static_cast<std::size_t>(r) + static_cast<std::size_t>(c) * (keep + 1)] = acc;
+    }
+    B[static_cast<std::size_t>(keep) + static_cast<std::size_t>(c) * (keep + 1)] = residue * qc[m - 1];
+  }
+  return keep;
 }
 
 }  // namespace small_eigen

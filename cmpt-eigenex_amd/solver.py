@@ -46,7 +46,8 @@ def lib():
         L.eigenex_solver_triplets_to_csr.argtypes = [C.c_int64, C.c_int64, _lp, _lp, _dp, C.c_int, _ip32, _ip32, _dp, _lp]
         L.eigenex_solver_gershgorin_range.argtypes = [C.c_int64, C.c_int64, _lp, _lp, _dp, C.c_int, _dp]
         L.eigenex_solver_blocks_to_csr.argtypes = [C.c_int, _lp, C.c_int, _lp, C.c_int, _lp, _lp, _dp, _ip32, _ip32, _dp, _lp]
-        for kind in ("trlanczos", "ztrlanczos"):
+        L.eigenex_solver_krylov_schur_basis.argtypes = [C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), _dp, _dp, _dp]
+        for kind in ("trlanczos", "ztrlanczos", "kschur", "zkschur"):
             p = f"eigenex_{kind}_solver_"
             getattr(L, p + "create").restype = _vp
             getattr(L, p + "destroy").argtypes = [_vp]
@@ -171,6 +172,24 @@ def symmetric_eigen(A):
     vecs = np.empty((n, n), order="F")
     _chk(lib().eigenex_solver_symmetric_eigen(n, _d(A), _d(vals), _d(vecs)))
     return vals, vecs
+
+
+def krylov_schur_basis(H, keep: int, residue: float):
+    """small_eigen::krylov_schur_basis on the projected matrix H (m x m, real or complex; Hessenberg or with a full leading
+    block): the restart basis of a Krylov-Schur cycle.  Returns keep (grown by one if a real matrix's conjugate pair would
+    have been split), Q (m x keep, orthonormal), B ((keep+1) x keep: Q^H H Q over the row residue * Q[m-1, :]) and all m
+    Ritz values, |theta| descending."""
+    cplx = bool(np.iscomplexobj(H))
+    dt = np.complex128 if cplx else np.float64
+    H = np.asfortranarray(H, dt)
+    m = H.shape[0]
+    Q = np.zeros((m, keep + 1), dt, order="F")
+    B = np.zeros((keep + 2) * (keep + 1), dt)
+    theta = np.zeros(m, np.complex128)
+    k = C.c_int(0)
+    _chk(lib().eigenex_solver_krylov_schur_basis(int(cplx), _d(H), m, m, int(keep), float(residue), C.byref(k), _d(Q), _d(B), _d(theta)))
+    k = k.value
+    return k, Q[:, :k].copy(), B[: (k + 1) * k].reshape((k + 1, k), order="F").copy(), theta
 
 
 def triplets_to_csr(n, rows, cols, vals):
@@ -434,6 +453,27 @@ class ThickRestartLanczosEigenSolver(_SolverBase):
         s = self._sizes()
         ev, res = np.zeros(s["neig"]), np.zeros(s["neig"])
         X = np.zeros((s["vec_rows"], s["vec_cols"]), self.dtype, order="F")
+        _chk(self._f("get")(self.h, _d(ev), _d(res), _d(X) if X.size else None))
+        s.update(eigenvalues=ev, residuals=res, eigenvectors=X, info_name=INFO[s["info"]])
+        return s
+
+
+class KrylovSchurEigenSolver(_SolverBase):
+    """KrylovSchurEigenSolver<S> (krylov_schur.hpp): eigenvalues of largest magnitude of a general operator from a basis of
+    fixed size (thick-restart Arnoldi).  Eigenvalues and eigenvectors are complex for either scalar type."""
+
+    _base = "kschur"
+    _names = ("neig", "vec_rows", "vec_cols", "restarts", "operatorApplications", "nlog", "info")
+
+    def _sizes(self):
+        out = np.zeros(len(self._names), np.int64)
+        _chk(self._f("sizes")(self.h, out.ctypes.data_as(_lp)))
+        return dict(zip(self._names, (int(x) for x in out)))
+
+    def results(self):
+        s = self._sizes()
+        ev, res = np.zeros(s["neig"], np.complex128), np.zeros(s["neig"])
+        X = np.zeros((s["vec_rows"], s["vec_cols"]), np.complex128, order="F")
         _chk(self._f("get")(self.h, _d(ev), _d(res), _d(X) if X.size else None))
         s.update(eigenvalues=ev, residuals=res, eigenvectors=X, info_name=INFO[s["info"]])
         return s

@@ -366,6 +366,17 @@ int eigenex_arnoldi_enqueue(eigenex_basis_t b, int ncalls);
  * (= beta_{m-1} * S[m-1, nkeep-1]); the next eigenex_lanczos_enqueue continues from there (full
  * re-orthogonalisation supplies the remaining couplings).  Needs capacity >= (m+1) + nkeep. Synchronises. */
 int eigenex_lanczos_restart(eigenex_basis_t b, int nkeep, const double* S, int lds, double coupling_last);
+/* Krylov-Schur restart of an Arnoldi run (not in the reference, which has no restart: SURVEY F6).  Precondition: a complete
+ * Arnoldi state of m = nvec vectors (nalpha == m, not stopped), i.e.  A V_m = V_m H_m + w e_m^T  with the unnormalised residual
+ * in W and residue = |w|.
+ * Q: m x nkeep, column-major, orthonormal columns spanning an invariant subspace of H_m, in the basis' scalar type (complex
+ *    basis: (re, im) pairs; ldq in entries).
+ * B: (nkeep+1) x nkeep, same scalar type: rows 0..nkeep-1 = Q^H H_m Q, row nkeep = residue * Q[m-1, :]; ldb in entries.
+ * Afterwards columns 0..nkeep-1 hold V_m Q, nvec = nalpha = nkeep, the stored projected matrix is B, W / residue / scale
+ * are untouched, and the next eigenex_arnoldi_enqueue continues from there.  Needs capacity >= m + nkeep.  Synchronises.
+ * EIGENEX_ERR_STATE: incomplete or stopped state, capacity too small; EIGENEX_ERR_ARG: nkeep < 1, nkeep >= m, ldq < m,
+ * ldb < nkeep + 1. */
+int eigenex_arnoldi_restart(eigenex_basis_t b, int nkeep, const double* Q, int ldq, const double* B, int ldb);
 
 typedef struct {
   int32_t nvec;        /* lanczosvectors_.size() / arnoldivectors_.size() */
