@@ -116,6 +116,8 @@ SIGNATURES = {
     "eigenex_ritz_vectors_complex": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int64]),
     "eigenex_krylov_combine": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int64]),
     "eigenex_apply": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _dp]),
+    "eigenex_basis_set_filter": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double]),
+    "eigenex_filter_apply": (C.c_int, [_vp, C.c_int, C.c_int]),
     "eigenex_dots": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "eigenex_update": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "eigenex_axpy2": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int]),
@@ -604,6 +606,19 @@ class Basis:
         d = np.zeros(1, self.dtype)
         _chk(lib().eigenex_apply(self.h, x_ref, y_ref, shift, _d(d.view(np.float64)) if want_dot else None))
         return d[0] if want_dot else None
+
+    def set_filter(self, mu, center=0.0, halfwidth=1.0, degree=None):
+        """Chebyshev filter p(A) = sum_k mu[k] T_k((A - center)/halfwidth) for the Lanczos steps and filter_apply; mu = None
+        (or degree = 0) removes it.  degree defaults to len(mu) - 1 (given explicitly by the argument tests)."""
+        if mu is None:
+            _chk(lib().eigenex_basis_set_filter(self.h, 0 if degree is None else degree, None, center, halfwidth))
+            return
+        mu = np.ascontiguousarray(mu, np.float64)
+        _chk(lib().eigenex_basis_set_filter(self.h, mu.size - 1 if degree is None else degree, _d(mu), center, halfwidth))
+
+    def filter_apply(self, x_ref, y_ref):
+        """y = p(A) x with the filter of set_filter"""
+        _chk(lib().eigenex_filter_apply(self.h, x_ref, y_ref))
 
     def dots(self, w_ref, first, stride, count, n_ortho_used=0):
         h = np.zeros(count + n_ortho_used, self.dtype)

@@ -53,6 +53,17 @@ __device__ __forceinline__ double add_product_nofma(double a, double b, double c
   return a + p;
 }
 
+// One row of a Chebyshev step (kernels.hpp: ChebStep), every product rounded before it is added: returns t_next, *acc_out = acc
+__device__ __forceinline__ double cheb_row_nofma(double a, double t_prev, double acc, const ChebStep& ch, double* acc_out) {
+#pragma clang fp contract(off)
+  const double ca = ch.c * a;
+  const double t = ch.first ? ca : ca - t_prev;
+  const double head = ch.first ? ch.mu0 * t_prev : acc;
+  const double term = ch.mu * t;
+  *acc_out = head + term;
+  return t;
+}
+
 __device__ __forceinline__ void fin_norm_apply(Ctrl* ctrl, double nrm2, double threshold, int mode, double* beta);
 __device__ __forceinline__ void fin_alpha_apply(Ctrl* ctrl, double val, double* alpha, int first);
 
@@ -463,6 +474,59 @@ __global__ __launch_bounds__(kBlock) void k_reduce(const double* __restrict__ pa
 }
 
 // ---------------------------------------------------------------------------
+// Chebyshev filter step (kernels.hpp: ChebStep).  cheb_store: one row, in the epilogue of the one-pass real CSR kernels (a =
+// the row sum with the shift -center applied, x = the row's own operator input = t_k).  k_cheb_combine: the same arithmetic
+// behind any other operator kernel, which has stored a as y: a stream over y, t_prev and acc with k_update's tiles and
+// persistent grid, 16-byte accesses, non-temporal stores of the two vectors it writes in full.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void cheb_store(const ChebStep& ch, int64_t r, double a, double x) {
+  const double tp = ch.first ? x : ch.t_prev[r];
+  const double acc = ch.first ? 0.0 : ch.acc[r];
+  double acc_new;
+  const double t = cheb_row_nofma(a, tp, acc, ch, &acc_new);
+  __builtin_nontemporal_store(t, &ch.t_next[r]);
+  __builtin_nontemporal_store(acc_new, &ch.acc[r]);
+}
+
+template <bool FULL>
+__device__ __forceinline__ void cheb_tile(const double* __restrict__ y, const ChebStep& ch, int64_t base, int64_t n) {
+  double2 a[4], tp[4], ac[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t row = base + i * (2 * kBlock);
+    a[i] = tp[i] = ac[i] = make_double2(0.0, 0.0);
+    if (FULL || row < n) {
+      a[i] = nt_ld_d2(y + row);
+      tp[i] = ld2(ch.t_prev + row);
+      if (!ch.first) ac[i] = ld2(ch.acc + row);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t row = base + i * (2 * kBlock);
+    if (FULL || row < n) {
+      double2 t, an;
+      t.x = cheb_row_nofma(a[i].x, tp[i].x, ac[i].x, ch, &an.x);
+      t.y = cheb_row_nofma(a[i].y, tp[i].y, ac[i].y, ch, &an.y);
+      nt_st2(ch.t_next + row, t);
+      nt_st2(ch.acc + row, an);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_cheb_combine(const double* __restrict__ y, ChebStep ch, int64_t n, int64_t ntiles,
+                                                         const Ctrl* __restrict__ ctrl) {
+  if (ctrl->stopped) return;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t base = tile * kTileRows + 2 * threadIdx.x;
+    if ((tile + 1) * kTileRows <= n)
+      cheb_tile<true>(y, ch, base, n);
+    else
+      cheb_tile<false>(y, ch, base, n);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // CSR SpMV, "stream" formulation: a tile of 256 rows owns a contiguous range of
 // stored entries.  Phase 1 streams val/col with aligned 16-B loads (4 entries per
 // lane), gathers x (L2/MALL-served) and parks the rounded products in LDS
@@ -569,152 +633,25 @@ __global__ __launch_bounds__(kBlock) void k_spmv(const OFF* __restrict__ rowptr,
                                                  int64_t ntiles, double* __restrict__ partials, int spmv_flags,
                                                  int pass, const Ctrl* ctrl, InlineFin fin, InlineArnoldiBegin ab,
                                                  const int32_t* __restrict__ tile_list) {  // no __restrict__ on ctrl: fin.ctrl / ab.ctrl alias it
-  // tile_list != nullptr: the launch covers the ntiles tiles tile_list[0 .. ntiles) instead of 0 .. ntiles (r3: the interior
-  // rows of a shard run while the halo is still on its way, the tiles that read halo columns afterwards; library.hip)
-  __shared__ double prod[kSpmvProdSlots];
-  __shared__ double lds4[4];
-  if (ctrl->stopped) return;
-  double scale = (scale_ptr && !ab.ctrl) ? *scale_ptr : 1.0;
-  if (ab.ctrl) {
-    double res, nrm2b;
-    int kb;
-    const bool stop = arnoldi_begin_inline(ab, &scale, lds4, &res, &nrm2b, &kb);
-    __syncthreads();  // everybody has read the control block before workgroup 0 changes it (other workgroups: the values written are the ones they derived)
-    if (blockIdx.x == 0) arnoldi_begin_record(ab, stop, scale, res, nrm2b, kb);
-    if (stop) return;
-  }
-  if (fin.partials) {  // beta_k, the breakdown test and the scale of the operator input (lanczos.hpp:429-439), taken here
-    const double nrm2 = inline_fin_sum(fin, lds4);
-    const double nrm = sqrt(nrm2);
-    const bool stop = fin.mode == kFinInit ? nrm < fin.threshold : nrm <= fin.threshold;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      fin.out[0] = nrm2;
-      fin_norm_apply(fin.ctrl, nrm2, fin.threshold, fin.mode, fin.series);
-    }
-    if (stop) return;
-    scale = 1.0 / nrm;
-  }
-  const int tid = threadIdx.x;
-  double dot = 0.0;
-  constexpr bool nt = NT;  // flags: bit 0 = XCD-contiguous tiles, bit 1 = cache policy of the val/col streams (NT, chosen by the launcher)
-  const TileRange tr = spmv_tiles(ntiles, spmv_flags & 1);
-  // row pointers of a tile: fetched one tile ahead, so that their latency is not part of the chain
-  // rowptr -> val/col -> x that every tile otherwise pays in sequence
-  constexpr bool kWide = sizeof(OFF) > 4;
-  auto tile_rows = [&](int64_t slot, int& rs, int& re, int& p0, int& p1, int64_t& base, int64_t& tile) {
-    rs = re = p0 = p1 = 0;
-    base = 0;
-    tile = slot;
-    if (slot >= tr.end) return;
-    if (tile_list) tile = tile_list[slot];
-    const int64_t r0 = tile * kSpmvRows, r = r0 + tid;
-    const OFF first = rowptr[r0];
-    if (kWide) base = (int64_t)first & ~(int64_t)3;
-    if (r < n) {
-      rs = (int)(rowptr[r] - (OFF)base);
-      re = (int)(rowptr[r + 1] - (OFF)base);
-    }
-    const int64_t rend = (r0 + kSpmvRows < n) ? r0 + kSpmvRows : n;
-    p0 = (int)(first - (OFF)base);
-    p1 = (int)(rowptr[rend] - (OFF)base);
-  };
-  int rs, re, p0, p1;
-  int64_t base, tile;
-  tile_rows(tr.first, rs, re, p0, p1, base, tile);
-  for (int64_t slot = tr.first; slot < tr.end; slot += tr.step) {
-    const int64_t r = tile * kSpmvRows + tid;
-    int nrs, nre, np0, np1;
-    int64_t nbase, ntile;
-    tile_rows(slot + tr.step, nrs, nre, np0, np1, nbase, ntile);
-    const int32_t* __restrict__ col = col_all + base;
-    const double* __restrict__ val = val_all + base;
-    const int pa = spmv_aligned_start(p0);  // int4 / double2 loads
-    double sum = ((pass & kPassCarry) && r < n) ? y[r] : 0.0;  // column-blocked: carry the row sum from pass to pass
-    for (int cb = pa; cb < p1; cb += kSpmvChunk) {
-      const int cend = spmv_chunk_end(cb, p1);
-      // phase 1: a chunk is two rounds of 4 entries per lane; all six 16-byte loads are issued before
-      // the first use, then the eight gathers.  Entries outside [p0, p1) are valid neighbours' entries
-      // or the zero padding behind nnz; their products are written but never read.
-      const SpmvLaneLoads ll = spmv_lane_loads(cb, cend, tid);
-      const int q0 = ll.q0, q1 = ll.q1;
-      const bool in0 = ll.in0, in1 = ll.in1;
-      int4 ca = make_int4(0, 0, 0, 0), cbv = make_int4(0, 0, 0, 0);
-      double2 a01 = make_double2(0.0, 0.0), a23 = a01, b01 = a01, b23 = a01;
-      if (nt) {  // compile-time: a run-time branch here cost the plain path 6-8 % through its register allocation (r3)
-        if (in0) {
-          ca = nt_ld_i4(col + q0);
-          a01 = nt_ld_d2(val + q0);
-          a23 = nt_ld_d2(val + q0 + 2);
-        }
-        if (in1) {
-          cbv = nt_ld_i4(col + q1);
-          b01 = nt_ld_d2(val + q1);
-          b23 = nt_ld_d2(val + q1 + 2);
-        }
-      } else {
-        if (in0) {
-          ca = *reinterpret_cast<const int4*>(col + q0);
-          a01 = ld2(val + q0);
-          a23 = ld2(val + q0 + 2);
-        }
-        if (in1) {
-          cbv = *reinterpret_cast<const int4*>(col + q1);
-          b01 = ld2(val + q1);
-          b23 = ld2(val + q1 + 2);
-        }
-      }
-      if (in0) {
-        const double x0 = x_ext[ca.x] * scale, x1 = x_ext[ca.y] * scale;
-        const double x2 = x_ext[ca.z] * scale, x3 = x_ext[ca.w] * scale;
-        const int li = skew(q0 - cb);  // 4 consecutive entries never straddle a multiple of 32
-        prod[li + 0] = a01.x * x0;
-        prod[li + 1] = a01.y * x1;
-        prod[li + 2] = a23.x * x2;
-        prod[li + 3] = a23.y * x3;
-      }
-      if (in1) {
-        const double x0 = x_ext[cbv.x] * scale, x1 = x_ext[cbv.y] * scale;
-        const double x2 = x_ext[cbv.z] * scale, x3 = x_ext[cbv.w] * scale;
-        const int li = skew(q1 - cb);
-        prod[li + 0] = b01.x * x0;
-        prod[li + 1] = b01.y * x1;
-        prod[li + 2] = b23.x * x2;
-        prod[li + 3] = b23.y * x3;
-      }
-      __syncthreads();
-      // phase 2: stored order, multiply-then-add
-      int lo, hi;
-      spmv_row_window(rs, re, cb, cend, &lo, &hi);
-      int p = lo;
-      // long rows: sixteen LDS reads in flight, then the sixteen adds in stored order (a row of 256 entries spent its time waiting
-      // for one read after the other: 413 -> 156 us at 30,000 rows x 256 contiguous columns, 41 -> 25 us at 100,000 x 64); rows
-      // shorter than 16 entries in the chunk -- the stencils -- take the plain loop below as before
-      for (; LONG_ROWS && p + 16 <= hi; p += 16) {
-        double t[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) t[i] = prod[skew(p + i - cb)];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sum = sum + t[i];
-      }
-      for (; p < hi; ++p) sum = sum + prod[skew(p - cb)];
-      __syncthreads();
-    }
-    if ((pass & kPassNotLast) && r < n) {
-      y[r] = sum;
-    } else if (r < n) {
-      const double xr = x_ext[r] * scale;
-      double yr = sum;
-      if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
-      __builtin_nontemporal_store(yr, &y[r]);  // results of a pass over the whole operator: nothing here reads them again
-      if (u_out) __builtin_nontemporal_store(xr, &u_out[r]);
-      dot = (pass & kPassSelfNorm) ? fma(yr, yr, dot) : fma(xr, yr, dot);
-    }
-    rs = nrs, re = nre, p0 = np0, p1 = np1, base = nbase, tile = ntile;
-  }
-  if (partials) {
-    dot = block_sum(dot, lds4);
-    if (tid == 0) partials[blockIdx.x] = dot;
-  }
+  constexpr bool CHEB = false;
+  const ChebStep ch{};
+#include "spmv_body.hpp"
+}
+// the same rows with a Chebyshev step in the epilogue (no hooks, no partial dots): the body is compiled a second time, so that
+// k_spmv keeps its arguments and, instruction for instruction, its code
+template <bool LONG_ROWS, class OFF, bool NT>
+__global__ __launch_bounds__(kBlock) void k_spmv_cheb(const OFF* __restrict__ rowptr, const int32_t* __restrict__ col_all,
+                                                      const double* __restrict__ val_all, const double* __restrict__ x_ext,
+                                                      const double* __restrict__ scale_ptr, double shift, double* __restrict__ u_out,
+                                                      int64_t n, int64_t ntiles, int spmv_flags, const Ctrl* __restrict__ ctrl,
+                                                      const int32_t* __restrict__ tile_list, ChebStep ch) {
+  constexpr bool CHEB = true;
+  constexpr int pass = 0;
+  double* const y = nullptr;
+  double* const partials = nullptr;
+  const InlineFin fin{};
+  const InlineArnoldiBegin ab{};
+#include "spmv_body.hpp"
 }
 
 // ---------------------------------------------------------------------------
@@ -743,75 +680,21 @@ __global__ __launch_bounds__(kBlock) void k_spmv_rows(RowCodeView op, const doub
                                                       int64_t ntiles, double* __restrict__ partials, int spmv_flags,
                                                       int pass, const Ctrl* ctrl, InlineFin fin, InlineArnoldiBegin ab,
                                                       const int32_t* __restrict__ tile_list) {  // no __restrict__ on ctrl: fin.ctrl / ab.ctrl alias it
-  constexpr int W = REC / 8, S = REC;  // 64-bit words and slots per record
-  __shared__ double pal[kRowCodeMaxValues];
-  __shared__ double lds4[4];
-  if (ctrl->stopped) return;
-  for (int i = threadIdx.x; i < op.npal; i += kBlock) pal[i] = op.pal[i];
-  double scale = (scale_ptr && !ab.ctrl) ? *scale_ptr : 1.0;
-  if (ab.ctrl) {
-    double res, nrm2b;
-    int kb;
-    const bool stop = arnoldi_begin_inline(ab, &scale, lds4, &res, &nrm2b, &kb);
-    __syncthreads();
-    if (blockIdx.x == 0) arnoldi_begin_record(ab, stop, scale, res, nrm2b, kb);
-    if (stop) return;
-  }
-  if (fin.partials) {  // as in k_spmv
-    const double nrm2 = inline_fin_sum(fin, lds4);
-    const double nrm = sqrt(nrm2);
-    const bool stop = fin.mode == kFinInit ? nrm < fin.threshold : nrm <= fin.threshold;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      fin.out[0] = nrm2;
-      fin_norm_apply(fin.ctrl, nrm2, fin.threshold, fin.mode, fin.series);
-    }
-    if (stop) return;
-    scale = 1.0 / nrm;
-  }
-  __syncthreads();  // the palette
-  const int tid = threadIdx.x;
-  double dot = 0.0;
-  const TileRange tr = spmv_tiles(ntiles, spmv_flags & 1);
-  auto tile_of = [&](int64_t slot) { return tile_list ? (int64_t)tile_list[slot] : slot; };
-  // records exist for every row of every tile (rows behind n: all slots absent), so the loads need no row test
-  uint64_t rec[W], nrec[W];
-  int64_t tile = tr.first < tr.end ? tile_of(tr.first) : 0;
-  if (tr.first < tr.end) row_code_load<REC>(op.rec, tile * kSpmvRows + tid, rec);
-  for (int64_t slot = tr.first; slot < tr.end; slot += tr.step) {
-    const int64_t r = tile * kSpmvRows + tid;
-    // branch-free, so that all gathers are in flight at once: an absent slot (also every slot behind the table's) loads
-    // x_ext[0] and its sum is dropped
-    double xs[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) xs[s] = x_ext[row_code_byte(rec, s) != kRowCodeAbsent ? r + op.slots.off[s] : 0];
-    // the next tile's record, behind the gathers
-    const int64_t nslot = slot + tr.step;
-    const int64_t ntile = nslot < tr.end ? tile_of(nslot) : 0;
-    if (nslot < tr.end) row_code_load<REC>(op.rec, ntile * kSpmvRows + tid, nrec);
-    double sum = 0.0;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {  // stored order, multiply then add
-      const unsigned c = row_code_byte(rec, s);
-      const bool here = c != kRowCodeAbsent;
-      const double t = add_product_nofma(sum, pal[here ? c : 0], xs[s] * scale);
-      sum = here ? t : sum;
-    }
-    if (r < n) {
-      const double xr = x_ext[r] * scale;
-      double yr = sum;
-      if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
-      __builtin_nontemporal_store(yr, &y[r]);
-      if (u_out) __builtin_nontemporal_store(xr, &u_out[r]);
-      dot = (pass & kPassSelfNorm) ? fma(yr, yr, dot) : fma(xr, yr, dot);
-    }
-#pragma unroll
-    for (int w = 0; w < W; ++w) rec[w] = nrec[w];
-    tile = ntile;
-  }
-  if (partials) {
-    dot = block_sum(dot, lds4);
-    if (tid == 0) partials[blockIdx.x] = dot;
-  }
+  constexpr bool CHEB = false;
+  const ChebStep ch{};
+#include "spmv_rows_body.hpp"
+}
+template <int REC>  // as k_spmv_cheb
+__global__ __launch_bounds__(kBlock) void k_spmv_rows_cheb(RowCodeView op, const double* __restrict__ x_ext, const double* __restrict__ scale_ptr,
+                                                           double shift, double* __restrict__ u_out, int64_t n, int64_t ntiles, int spmv_flags,
+                                                           const Ctrl* __restrict__ ctrl, const int32_t* __restrict__ tile_list, ChebStep ch) {
+  constexpr bool CHEB = true;
+  constexpr int pass = 0;
+  double* const y = nullptr;
+  double* const partials = nullptr;
+  const InlineFin fin{};
+  const InlineArnoldiBegin ab{};
+#include "spmv_rows_body.hpp"
 }
 
 // ---------------------------------------------------------------------------
@@ -2132,12 +2015,26 @@ template <class OFF>
 static void launch_spmv_t(hipStream_t s, const OFF* rowptr, const int32_t* col, const double* val, const double* x_ext,
                           const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                           const Ctrl* ctrl, int spmv_flags, int pass, const InlineFin* fin, const InlineArnoldiBegin* begin,
-                          const int32_t* tile_list, int64_t list_len) {
+                          const int32_t* tile_list, int64_t list_len, const ChebStep* cheb) {
   const int64_t ntiles = tile_list ? list_len : (n + kSpmvRows - 1) / kSpmvRows;
   if (ntiles <= 0) return;
   const InlineFin nofin{nullptr, 0, 0, 0.0, nullptr, nullptr, nullptr};
   const InlineArnoldiBegin nobegin{nullptr, 0.0, 0, 0, nullptr, 0, 0, -1, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
   const bool nt = (spmv_flags & 2) != 0;
+  if (cheb) {  // the Chebyshev epilogue: no hooks, no partial dots
+#define EIGENEX_LAUNCH_SPMV_CHEB(LONG, NTV)                                                                                                \
+  hipLaunchKernelGGL((k_spmv_cheb<LONG, OFF, NTV>), dim3(grid), dim3(kBlock), 0, s, rowptr, col, val, x_ext, scale, shift, u_out, n, ntiles, \
+                     spmv_flags, ctrl, tile_list, *cheb)
+    if (spmv_flags & kSpmvLongRows) {
+      if (nt) EIGENEX_LAUNCH_SPMV_CHEB(true, true);
+      else EIGENEX_LAUNCH_SPMV_CHEB(true, false);
+    } else {
+      if (nt) EIGENEX_LAUNCH_SPMV_CHEB(false, true);
+      else EIGENEX_LAUNCH_SPMV_CHEB(false, false);
+    }
+#undef EIGENEX_LAUNCH_SPMV_CHEB
+    return;
+  }
 #define EIGENEX_LAUNCH_SPMV(LONG, NTV)                                                                                              \
   hipLaunchKernelGGL((k_spmv<LONG, OFF, NTV>), dim3(grid), dim3(kBlock), 0, s, rowptr, col, val, x_ext, scale, shift, y, u_out, n, \
                      ntiles, partials, spmv_flags, pass, ctrl, fin ? *fin : nofin, begin ? *begin : nobegin, tile_list)
@@ -2153,23 +2050,28 @@ static void launch_spmv_t(hipStream_t s, const OFF* rowptr, const int32_t* col, 
 void launch_spmv(hipStream_t s, const int32_t* rowptr, const int32_t* col, const double* val, const double* x_ext,
                  const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                  const Ctrl* ctrl, int spmv_flags, int pass, const InlineFin* fin, const InlineArnoldiBegin* begin,
-                 const int32_t* tile_list, int64_t list_len) {
-  launch_spmv_t(s, rowptr, col, val, x_ext, scale, shift, y, u_out, n, partials, grid, ctrl, spmv_flags, pass, fin, begin, tile_list, list_len);
+                 const int32_t* tile_list, int64_t list_len, const ChebStep* cheb) {
+  launch_spmv_t(s, rowptr, col, val, x_ext, scale, shift, y, u_out, n, partials, grid, ctrl, spmv_flags, pass, fin, begin, tile_list, list_len, cheb);
 }
 void launch_spmv64(hipStream_t s, const int64_t* rowptr, const int32_t* col, const double* val, const double* x_ext,
                    const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                    const Ctrl* ctrl, int spmv_flags, int pass, const InlineFin* fin, const InlineArnoldiBegin* begin,
-                   const int32_t* tile_list, int64_t list_len) {
-  launch_spmv_t(s, rowptr, col, val, x_ext, scale, shift, y, u_out, n, partials, grid, ctrl, spmv_flags, pass, fin, begin, tile_list, list_len);
+                   const int32_t* tile_list, int64_t list_len, const ChebStep* cheb) {
+  launch_spmv_t(s, rowptr, col, val, x_ext, scale, shift, y, u_out, n, partials, grid, ctrl, spmv_flags, pass, fin, begin, tile_list, list_len, cheb);
 }
 void launch_spmv_rows(hipStream_t s, const RowCodeView& op, const double* x_ext, const double* scale, double shift, double* y,
                       double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int spmv_flags, int pass,
-                      const InlineFin* fin, const InlineArnoldiBegin* begin, const int32_t* tile_list, int64_t list_len) {
+                      const InlineFin* fin, const InlineArnoldiBegin* begin, const int32_t* tile_list, int64_t list_len,
+                      const ChebStep* cheb) {
   const int64_t ntiles = tile_list ? list_len : (n + kSpmvRows - 1) / kSpmvRows;
   if (ntiles <= 0) return;
   const InlineFin nofin{nullptr, 0, 0, 0.0, nullptr, nullptr, nullptr};
   const InlineArnoldiBegin nobegin{nullptr, 0.0, 0, 0, nullptr, 0, 0, -1, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-  if (op.rec_bytes == 8)
+  if (cheb && op.rec_bytes == 8)
+    hipLaunchKernelGGL(k_spmv_rows_cheb<8>, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, u_out, n, ntiles, spmv_flags, ctrl, tile_list, *cheb);
+  else if (cheb)
+    hipLaunchKernelGGL(k_spmv_rows_cheb<16>, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, u_out, n, ntiles, spmv_flags, ctrl, tile_list, *cheb);
+  else if (op.rec_bytes == 8)
     hipLaunchKernelGGL(k_spmv_rows<8>, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, y, u_out, n, ntiles, partials,
                        spmv_flags, pass, ctrl, fin ? *fin : nofin, begin ? *begin : nobegin, tile_list);
   else
@@ -2292,6 +2194,11 @@ void launch_scale(hipStream_t s, const double* x, const double* scale_dev, doubl
 void launch_shift_dot(hipStream_t s, double* y, const double* u, double shift, int64_t n, double* partials, int grid,
                       const Ctrl* ctrl) {
   hipLaunchKernelGGL(k_shift_dot, dim3(grid), dim3(kBlock), 0, s, y, u, shift, n, partials, ctrl);
+}
+
+void launch_cheb_combine(hipStream_t s, const double* y, const ChebStep& step, int64_t n, int grid, const Ctrl* ctrl) {
+  const int64_t ntiles = (n + kTileRows - 1) / kTileRows;
+  hipLaunchKernelGGL(k_cheb_combine, dim3(grid), dim3(kBlock), 0, s, y, step, n, ntiles, ctrl);
 }
 
 void launch_pack(hipStream_t s, const double* x, const int32_t* idx, int64_t count, int es, double* out,

@@ -110,6 +110,21 @@ struct InlineReduce {
   double* out;
 };
 
+// One degree of a Chebyshev filter  p(A) x = sum_k mu[k] T_k((A - center)/halfwidth) x  for the rows of a launch.  With
+// a = (A t_k - center t_k)[row], the operator kernels' row sum and shift epilogue (shift = -center):
+//   first:  t_1 = c*a (c = 1/halfwidth),                 acc = mu0*t_0 + mu*t_1      (mu = mu[1]; t_prev = t_0 = x)
+//   later:  t_{k+1} = c*a - t_{k-1} (c = 2/halfwidth),   acc = acc + mu*t_{k+1}      (mu = mu[k+1])
+// every product rounded before it is added (no FMA), so that the operator kernels that take the step in their epilogue and
+// k_cheb_combine behind any other operator kernel give the same bits.  t_next may be t_prev (each row is read before it is
+// written, by one thread); neither may be the operator input, which is gathered from meanwhile.
+struct ChebStep {
+  const double* t_prev;  // the fused operator kernels take t_0 from their own input instead (first step)
+  double* t_next;
+  double* acc;
+  double c, mu0, mu;
+  int first;
+};
+
 int grid_for_tiles(int64_t ntiles, int blocks_per_cu);
 void set_num_cu(int n);
 
@@ -148,13 +163,16 @@ enum { kSpmvLongRows = 4 };
 void launch_spmv(hipStream_t s, const int32_t* rowptr, const int32_t* col, const double* val, const double* x_ext,
                  const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                  const Ctrl* ctrl, int spmv_flags = 0, int pass = 0, const InlineFin* fin = nullptr,
-                 const InlineArnoldiBegin* begin = nullptr, const int32_t* tile_list = nullptr, int64_t list_len = 0);
+                 const InlineArnoldiBegin* begin = nullptr, const int32_t* tile_list = nullptr, int64_t list_len = 0,
+                 const ChebStep* cheb = nullptr);
+// (cheb: the kernel takes a Chebyshev step in its epilogue instead of storing y -- y, partials and the hooks are unused then)
 // (tile_list: the launch covers the 256-row tiles tile_list[0 .. list_len) only -- interior / boundary launches of a shard)
 // the same with 64-bit row pointers (plain real CSR in one pass): a shard may hold >= 2^31 stored entries; col stays int32
 void launch_spmv64(hipStream_t s, const int64_t* rowptr, const int32_t* col, const double* val, const double* x_ext,
                    const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                    const Ctrl* ctrl, int spmv_flags = 0, int pass = 0, const InlineFin* fin = nullptr,
-                   const InlineArnoldiBegin* begin = nullptr, const int32_t* tile_list = nullptr, int64_t list_len = 0);
+                   const InlineArnoldiBegin* begin = nullptr, const int32_t* tile_list = nullptr, int64_t list_len = 0,
+                   const ChebStep* cheb = nullptr);
 // Row-coded operator (real fp64 in one pass; row_codes.hpp, kernels.hip: k_spmv_rows): rec = one record of rec_bytes (8 or 16)
 // per row of every 256-row tile, pal = npal values, slots = the offsets.  Same tiles, grid, partial dots and hooks as launch_spmv.
 struct RowCodeView {
@@ -166,7 +184,7 @@ struct RowCodeView {
 void launch_spmv_rows(hipStream_t s, const RowCodeView& op, const double* x_ext, const double* scale, double shift, double* y,
                       double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int spmv_flags = 0, int pass = 0,
                       const InlineFin* fin = nullptr, const InlineArnoldiBegin* begin = nullptr, const int32_t* tile_list = nullptr,
-                      int64_t list_len = 0);
+                      int64_t list_len = 0, const ChebStep* cheb = nullptr);
 // records of a device-resident CSR shard (rowptr or rowptr64) for rows [0, nrec_rows) with given tables; *bad counts rows that
 // do not fit them
 struct RowCodePalette {
@@ -249,6 +267,9 @@ void launch_scale(hipStream_t s, const double* x, const double* scale_dev, doubl
 // host-operator path: y += shift*u ; partials[block] = partial u.y
 void launch_shift_dot(hipStream_t s, double* y, const double* u, double shift, int64_t n, double* partials, int grid,
                       const Ctrl* ctrl);
+// the Chebyshev step behind an operator kernel that has stored y = (A - center) t_k: n in DOUBLES (complex vectors: 2N, the
+// coefficients are real); reads y, t_prev and acc, writes t_next and acc
+void launch_cheb_combine(hipStream_t s, const double* y, const ChebStep& step, int64_t n, int grid, const Ctrl* ctrl);
 // gather send buffer: out[i] = x[idx[i]]
 void launch_pack(hipStream_t s, const double* x, const int32_t* idx, int64_t count, int es, double* out,
                  const Ctrl* ctrl);

@@ -350,6 +350,9 @@ struct BasisShard {
   int64_t nd = 0, ldd = 0;  // vector length / column stride in doubles (= nloc*es, ldv*es)
   CsrShard* csr = nullptr;
   DeviceBuffer<double> V, Q, v, w, start;
+  // Chebyshev filter (eigenex_basis_set_filter; made by the first call): w2 = a second operator input with halo slots -- t_k is
+  // gathered from one while t_{k+1} is written to the other --, fy = the operator's output where the step is not taken in its epilogue
+  DeviceBuffer<double> w2, fy;
   DeviceBuffer<double> partials, hbuf, alpha, beta, H;
   DeviceBuffer<double> pnorm;  // partial sums handed from a producer kernel to the consumer that finalises them (InlineFin)
   double* palpha = nullptr;    // pnorm + pstride
@@ -408,6 +411,12 @@ struct eigenex_basis_s {
   uint64_t graph_clock = 0;
   bool h_restarted = false;  // a Krylov-Schur restart has left a full block in H: eigenex_basis_clear zeroes H again (Arnoldi steps only
                              // ever write the Hessenberg part, and eigenex_arnoldi_state hands out whole columns)
+  // Chebyshev filter: the Lanczos step driver applies p(A) = sum_k f_mu[k] T_k((A - f_center)/f_half) instead of A; 0: none.
+  // f_fused: operators that have the step in their kernel's epilogue use it (EIGENEX_NO_FUSED_FILTER, read per set_filter call)
+  int f_degree = 0;
+  std::vector<double> f_mu;
+  double f_center = 0.0, f_half = 1.0;
+  bool f_fused = true;
   bool fuse_alpha = true;  // Lanczos on more than one shard: alpha of the newest vector travels with the next step's dots (lanczos_call)
   int hbuf_len() const { return 8 * maxcols + 64; }
   int base_fused() const { return 4 * maxcols + 16; }  // [alpha (2 slots), g (es*ncols), G (es*ncols)]: one all-reduce
@@ -449,10 +458,11 @@ int allreduce(eigenex_basis_s* b, int off, int n) {
 enum class CtrlBlock { Zero, State, Pass2 };
 inline const Ctrl* pick_ctrl(const BasisShard& s, CtrlBlock cb) { return cb == CtrlBlock::Pass2 ? s.ctrl_pass2 : cb == CtrlBlock::State ? s.ctrl : s.ctrl_zero; }
 
-// fill the halo region of every local shard's operator-input vector
+// fill the halo region of every local shard's operator-input vector `vec` (w, or w2 inside a Chebyshev filter)
 // on_halo_stream: the exchange is issued on the context's second stream, behind ev_w_ready (the operator input is complete) and
 // followed by ev_halo_done, which the boundary launch of the operator waits for (enq_apply); else on the compute stream
-int halo_exchange(eigenex_basis_s* b, CtrlBlock ctrl, bool on_halo_stream = false) {
+using WorkVector = DeviceBuffer<double> BasisShard::*;
+int halo_exchange(eigenex_basis_s* b, CtrlBlock ctrl, bool on_halo_stream = false, WorkVector vec = &BasisShard::w) {
   eigenex_context_s* c = b->ctx;
   if (c->P == 1 || !b->csr) return 0;
   if (c->tracing) c->trace.push_back({EIGENEX_COLL_HALO, 0});
@@ -472,7 +482,7 @@ int halo_exchange(eigenex_basis_s* b, CtrlBlock ctrl, bool on_halo_stream = fals
     CsrShard* cs = bs.csr;
     for (auto& sg : cs->send)
       if (sg.contig_start < 0)
-        launch_pack(st, bs.w, cs->send_idx + sg.offset, sg.count, bs.es, cs->sendbuf + sg.offset * bs.es,
+        launch_pack(st, bs.*vec, cs->send_idx + sg.offset, sg.count, bs.es, cs->sendbuf + sg.offset * bs.es,
                     pick_ctrl(bs, ctrl));
   }
   if (c->loopback) {
@@ -484,8 +494,8 @@ int halo_exchange(eigenex_basis_s* b, CtrlBlock ctrl, bool on_halo_stream = fals
         for (auto& x : src.csr->send)
           if (x.peer == bs.gshard) sg = &x;
         if (!sg || sg->count != rg.count) return fail(EIGENEX_ERR_STATE, "halo plan mismatch");
-        const double* sp = sg->contig_start >= 0 ? src.w + sg->contig_start * src.es : src.csr->sendbuf + sg->offset * src.es;
-        HIPCHK(hipMemcpyAsync(bs.w + (bs.ldv + rg.offset) * bs.es, sp, sizeof(double) * rg.count * bs.es,
+        const double* sp = sg->contig_start >= 0 ? (src.*vec) + sg->contig_start * src.es : src.csr->sendbuf + sg->offset * src.es;
+        HIPCHK(hipMemcpyAsync((bs.*vec) + (bs.ldv + rg.offset) * bs.es, sp, sizeof(double) * rg.count * bs.es,
                               hipMemcpyDeviceToDevice, st));
       }
     }
@@ -497,11 +507,11 @@ int halo_exchange(eigenex_basis_s* b, CtrlBlock ctrl, bool on_halo_stream = fals
   RcclGroup group;
   NCCLCHK(group.start());
   for (auto& sg : cs->send) {
-    const double* sp = sg.contig_start >= 0 ? bs.w + sg.contig_start * bs.es : cs->sendbuf + sg.offset * bs.es;
+    const double* sp = sg.contig_start >= 0 ? (bs.*vec) + sg.contig_start * bs.es : cs->sendbuf + sg.offset * bs.es;
     NCCLCHK(ncclSend(sp, (size_t)sg.count * bs.es, ncclDouble, sg.peer, comm, st));
   }
   for (auto& rg : cs->recv)
-    NCCLCHK(ncclRecv(bs.w + (bs.ldv + rg.offset) * bs.es, (size_t)rg.count * bs.es, ncclDouble, rg.peer, comm, st));
+    NCCLCHK(ncclRecv((bs.*vec) + (bs.ldv + rg.offset) * bs.es, (size_t)rg.count * bs.es, ncclDouble, rg.peer, comm, st));
   NCCLCHK(group.end());
   return 0;
 }
@@ -1567,6 +1577,7 @@ struct OperatorPass {
   const InlineFin* fin = nullptr;             // one-pass real CSR only (inlines_fin)
   const InlineArnoldiBegin* begin = nullptr;  // operator kernels that have the hook only (inline_begin_ok)
   hipEvent_t halo_done = nullptr;  // the launches that read halo slots wait for it (the halo exchange is on its way on the other stream)
+  const ChebStep* cheb = nullptr;  // one-pass real CSR only (filter_in_epilogue): a Chebyshev step instead of the store of y
 };
 
 struct TileList {  // the 256-row tiles one launch covers (none: all)
@@ -1581,13 +1592,13 @@ void launch_csr_one_pass(hipStream_t st, const BasisShard& s, const OperatorPass
   const int flags = s.spmv_flags | (!m->rc_rec || tl.tiles ? long_rows_flag(m) : 0);
   if (m->rc_rec)
     launch_spmv_rows(st, row_code_view(m), p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, partials, grid, p.ctrl, flags, p.pass_flags, p.fin,
-                     p.begin, tl.tiles, tl.len);
+                     p.begin, tl.tiles, tl.len, p.cheb);
   else if (m->rowptr64)
     launch_spmv64(st, m->rowptr64, m->col, m->val, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, partials, grid, p.ctrl, flags, p.pass_flags,
-                  p.fin, p.begin, tl.tiles, tl.len);
+                  p.fin, p.begin, tl.tiles, tl.len, p.cheb);
   else
     launch_spmv(st, m->rowptr, m->col, m->val, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, partials, grid, p.ctrl, flags, p.pass_flags, p.fin,
-                p.begin, tl.tiles, tl.len);
+                p.begin, tl.tiles, tl.len, p.cheb);
 }
 
 // a launch per column-block pass, the row sums carried in y; s.g_spmv workgroups = partial dots.  Operators with interior /
@@ -1643,6 +1654,54 @@ void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p)
   }
 }
 
+// Does this shard's operator kernel take a Chebyshev step in its epilogue?  The kernels behind launch_csr_one_pass.
+inline bool filter_in_epilogue(const BasisShard& s) {
+  const CsrShard* m = s.csr;
+  return s.es == 1 && !m->split && !m->sorted && !m->blocked && (m->rc_rec || m->passes == 1);
+}
+
+// acc = p(A) x with the state's Chebyshev filter, x = w*scale (the operator input, as for an operator application): `degree`
+// operator applications, each with its neighbour exchange and followed by the three-term update -- in the operator kernel's
+// epilogue where it has one (y is then never written), else by k_cheb_combine from the operator's output in fy.  t_k alternates
+// between w and w2 (t_{k+1} takes the place of t_{k-1}); ucol: basis column that receives x (then t_0 is read from there and
+// w, which holds the unscaled input, is free from the second degree on); without it w itself is x.
+struct FilterPass {
+  CtrlBlock ctrl;
+  std::optional<int> ucol;
+  int acc_ref;
+};
+int enq_filter(eigenex_basis_s* b, const FilterPass& p) {
+  eigenex_context_s* c = b->ctx;
+  const int d = b->f_degree;
+  const double c1 = 1.0 / b->f_half, c2 = 2.0 / b->f_half;
+  const bool overlap = c->halo_overlap && c->P > 1;
+  for (int j = 0; j < d; ++j) {
+    const WorkVector in = (j & 1) ? &BasisShard::w2 : &BasisShard::w, out = (j & 1) ? &BasisShard::w : &BasisShard::w2;
+    if (overlap) HIPCHK(hipEventRecord(c->ev_w_ready, c->stream));
+    CHK(halo_exchange(b, p.ctrl, overlap, in));
+    for (auto& s : b->sh) {
+      double* u = p.ucol ? s.V + (int64_t)*p.ucol * s.ldd : nullptr;
+      const double* t0 = u ? u : s.w.get();
+      const bool first = j == 0;
+      const ChebStep step{j < 2 ? t0 : (s.*out).get(), s.*out, vec_ptr(s, b->cap, b->nq, p.acc_ref), first ? c1 : c2, b->f_mu[0], b->f_mu[(size_t)j + 1], first ? 1 : 0};
+      const bool fused = b->f_fused && filter_in_epilogue(s);
+      const Ctrl* ctrl = pick_ctrl(s, p.ctrl);
+      const double stream_bytes = (first ? 24.0 : 40.0) * s.nd + (first && u ? 8.0 * s.nd : 0.0);  // t_k, (t_{k-1}, acc,) t_{k+1}, acc(, u)
+      {
+        ProfScope ps(c, EIGENEX_K_SPMV, operator_bytes(s.csr, b->es) + (fused ? stream_bytes : 16.0 * s.nd + (first && u ? 8.0 * s.nd : 0.0)));
+        launch_operator(c->stream, s, {.x = s.*in, .scale = first && p.ucol ? &s.ctrl->scale : nullptr, .shift = -b->f_center, .y = fused ? nullptr : s.fy.get(),
+                                       .u_out = first ? u : nullptr, .ctrl = ctrl, .halo_done = overlap ? c->ev_halo_done : nullptr,
+                                       .cheb = fused ? &step : nullptr});
+      }
+      if (!fused) {
+        ProfScope ps(c, EIGENEX_K_SPMV, (first ? 32.0 : 40.0) * s.nd);
+        launch_cheb_combine(c->stream, s.fy, step, s.nd, s.g_vec, ctrl);
+      }
+    }
+  }
+  return 0;
+}
+
 // can the operator kernel of this state take the start of an Arnoldi step itself (InlineArnoldiBegin)?  One shard that decides
 // locally, and an operator kernel that has the hook: plain real CSR in one pass, or split tiles
 bool inline_begin_ok(const eigenex_basis_s* b) {
@@ -1676,6 +1735,25 @@ int enq_apply(eigenex_basis_s* b, const ApplyPass& p, bool* fin_merged = nullptr
   const bool can_merge = p.out == ApplyOut::Alpha && fin_merged && b->csr && decides_locally(b);
   const std::optional<FinAlphaMode> merge = can_merge ? p.decide : std::nullopt;
   if (fin_merged) *fin_merged = merge.has_value();
+  if (b->csr && b->f_degree > 0) {
+    // a filtered state: v = p(A) u, then alpha = u.v in a pass of its own, the shape of the host-operator branch below
+    if (fin_merged) *fin_merged = false;
+    CHK(enq_filter(b, {.ctrl = CtrlBlock::State, .ucol = p.ucol, .acc_ref = EIGENEX_VEC_V}));
+    if (!want_alpha) return 0;
+    for (auto& s : b->sh) {
+      const double* u = s.V + (int64_t)p.ucol * s.ldd;
+      {
+        ProfScope ps(c, EIGENEX_K_DOTS, 16.0 * s.nd);
+        if (b->es == 2)
+          launch_shift_dot_z(c->stream, s.v, u, 0.0, 0.0, s.nloc, s.partials, s.pstride, s.g_vec, s.ctrl);
+        else
+          launch_shift_dot(c->stream, s.v, u, 0.0, s.nloc, s.partials, s.g_vec, s.ctrl);
+      }
+      ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
+      launch_reduce(c->stream, s.partials, s.pstride, s.g_vec, b->es, s.hbuf + b->slot_alpha(), s.ctrl);
+    }
+    return allreduce(b, b->slot_alpha(), b->es);
+  }
   if (b->csr) {
     // between shards: the neighbour exchange goes to the halo stream behind ev_w_ready (recorded here: everything that wrote the
     // operator input is in front of it on the compute stream), the interior tiles run meanwhile, the boundary tiles behind
@@ -1751,7 +1829,7 @@ inline Cols lanczos_columns(int k, int64_t interval, int nq_total) {
 // Can the alpha of the vector a call adds stay un-reduced until the next call's dots?  Only between shards (one shard
 // merges its tiny launches instead), with a device operator and a batched scheme.
 inline bool fuses_alpha(const eigenex_basis_s* b) {
-  return b->fuse_alpha && !decides_locally(b) && b->csr && b->ortho_mode != EIGENEX_ORTHO_SEQUENTIAL;
+  return b->fuse_alpha && !decides_locally(b) && b->csr && b->f_degree == 0 && b->ortho_mode != EIGENEX_ORTHO_SEQUENTIAL;
 }
 
 // all-reduce and record an alpha that was left pending (a step without columns to orthogonalise against follows)
@@ -1777,7 +1855,7 @@ int close_pending_alpha(eigenex_basis_s* b) {
 // order, same decisions.  Matters where a step is launch-bound (32^3: 29 -> 21 us per step); nothing at 512^3.
 inline bool inlines_fin(const eigenex_basis_s* b) {
   static const bool off = std::getenv("EIGENEX_NO_INLINE_FIN") != nullptr;
-  if (off || !decides_locally(b) || !b->csr || b->es != 1) return false;
+  if (off || !decides_locally(b) || !b->csr || b->es != 1 || b->f_degree > 0) return false;  // (a filtered state applies p(A) in many launches)
   const CsrShard& m = b->csr->sh[0];
   return !m.blocked && !m.sorted && !m.split && m.passes == 1 && (b->ortho_mode == EIGENEX_ORTHO_BATCHED || b->ortho_mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE);
 }
@@ -1944,6 +2022,7 @@ int64_t launches_upper_bound(const eigenex_basis_s* b, int ncalls) {
     const int64_t dots_chunks = cols * b->es * 2 / kDotsMaxAcc + 1;
     int64_t per = 24 + 2 * passes + 4 * dots_chunks;  // batched / twice / adaptive: <= 2 passes of dots+reduce+update+reduce, finalisers, operator
     if (b->ortho_mode == EIGENEX_ORTHO_SEQUENTIAL) per += 4 * cols;  // dot, reduce, update (+ reduce) per vector
+    per += (int64_t)b->f_degree * (passes + 1);  // a filtered state: per degree the operator's launches and k_cheb_combine
     total += per;
     if (nvec < b->cap) ++nvec;
   }
@@ -3017,6 +3096,10 @@ int eigenex_basis_clone(eigenex_basis_t src, eigenex_basis_t* out) {
   b->ortho_mode = src->ortho_mode, b->cur = src->cur, b->fn = src->fn, b->fn_user = src->fn_user;
   b->fuse_alpha = src->fuse_alpha;
   b->h_restarted = src->h_restarted;
+  if (src->f_degree > 0) {
+    CHK(eigenex_basis_set_filter(b.get(), src->f_degree, src->f_mu.data(), src->f_center, src->f_half));
+    b->f_fused = src->f_fused;
+  }
   for (size_t i = 0; i < b->sh.size(); ++i) {
     BasisShard &d = b->sh[i], &s = src->sh[i];
     d.g_vec = s.g_vec, d.g_spmv = s.g_spmv, d.g_spmv_int = s.g_spmv_int, d.spmv_flags = s.spmv_flags;
@@ -3260,6 +3343,53 @@ int eigenex_apply(eigenex_basis_t b, int x_ref, int y_ref, double shift, double*
   return 0;
 }
 
+int eigenex_basis_set_filter(eigenex_basis_t b, int degree, const double* mu, double center, double halfwidth) {
+  if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  if (degree < 0 || (degree > 0 && (!mu || !(halfwidth > 0.0) || !std::isfinite(halfwidth) || !std::isfinite(center))))
+    return fail(EIGENEX_ERR_ARG, "eigenex_basis_set_filter: degree >= 0, mu[degree + 1] and halfwidth > 0 are needed");
+  if (degree > 0 && !b->csr) return fail(EIGENEX_ERR_STATE, "eigenex_basis_set_filter: a filter needs a device operator");
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  if (degree > 0) {  // the second operator input and the operator's output, once per state; all or nothing
+    std::vector<DeviceBuffer<double>> w2(b->sh.size()), fy(b->sh.size());
+    for (size_t i = 0; i < b->sh.size(); ++i) {
+      const BasisShard& s = b->sh[i];
+      if (s.w2) continue;
+      const size_t nw = (size_t)(s.ldv + s.nhalo + 8) * s.es;
+      HIPCHK(w2[i].alloc(nw));
+      HIPCHK(fy[i].alloc((size_t)s.ldd));
+      HIPCHK(hipMemsetAsync(w2[i], 0, sizeof(double) * nw, c->stream));
+      HIPCHK(hipMemsetAsync(fy[i], 0, sizeof(double) * (size_t)s.ldd, c->stream));
+    }
+    for (size_t i = 0; i < b->sh.size(); ++i)
+      if (w2[i]) b->sh[i].w2 = std::move(w2[i]), b->sh[i].fy = std::move(fy[i]);
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  drop_step_graphs(b);  // recorded batches hold the coefficients (and the launches) of the filter they were recorded with
+  b->f_degree = degree;
+  b->f_mu.assign(mu, mu + (degree > 0 ? degree + 1 : 0));
+  b->f_center = center, b->f_half = halfwidth;
+  b->f_fused = std::getenv("EIGENEX_NO_FUSED_FILTER") == nullptr;
+  return 0;
+}
+
+int eigenex_filter_apply(eigenex_basis_t b, int x_ref, int y_ref) {
+  if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  if (b->f_degree < 1 || !b->csr) return fail(EIGENEX_ERR_STATE, "eigenex_filter_apply: no filter is set (eigenex_basis_set_filter)");
+  if (y_ref == EIGENEX_VEC_W) return fail(EIGENEX_ERR_ARG, "y may not be the operator input vector");
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  for (auto& s : b->sh) {
+    double* x = vec_ptr(s, b->cap, b->nq, x_ref);
+    double* y = vec_ptr(s, b->cap, b->nq, y_ref);
+    if (!x || !y || x == y) return fail(EIGENEX_ERR_ARG, "bad vector reference");
+    if (x != s.w) HIPCHK(hipMemcpyAsync(s.w, x, sizeof(double) * s.nd, hipMemcpyDeviceToDevice, c->stream));
+  }
+  CHK(enq_filter(b, {.ctrl = CtrlBlock::Zero, .ucol = std::nullopt, .acc_ref = y_ref}));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 int eigenex_dots(eigenex_basis_t b, int w_ref, int first, int stride, int count, int n_ortho_used, double* h) {
   if (!b || !h) return fail(EIGENEX_ERR_ARG, "NULL argument");
   if (!cols_ok(b, first, stride, count, n_ortho_used)) return fail(EIGENEX_ERR_ARG, "bad column selection");
@@ -3317,6 +3447,8 @@ int eigenex_scale(eigenex_basis_t b, int dst_ref, int src_ref, double sc) {
 // ---- fused steps ---------------------------------------------------------------------
 int eigenex_lanczos_enqueue(eigenex_basis_t b, int ncalls) {
   if (!b || ncalls < 0) return fail(EIGENEX_ERR_ARG, "bad argument");
+  if (b->f_degree > 0 && (b->shift != 0.0 || b->shift_im != 0.0))
+    return fail(EIGENEX_ERR_STATE, "eigenex_lanczos_enqueue: a filtered state takes no eigenvalue shift");
   HIPCHK(hipSetDevice(b->ctx->device));
   return enqueue_steps(b, ncalls, 0);
 }
@@ -3363,6 +3495,7 @@ int eigenex_lanczos_restart(eigenex_basis_t b, int nkeep, const double* S, int l
 
 int eigenex_arnoldi_enqueue(eigenex_basis_t b, int ncalls) {
   if (!b || ncalls < 0) return fail(EIGENEX_ERR_ARG, "bad argument");
+  if (b->f_degree > 0) return fail(EIGENEX_ERR_STATE, "eigenex_arnoldi_enqueue: the filter of this state is for Hermitian operators (Lanczos steps)");
   HIPCHK(hipSetDevice(b->ctx->device));
   return enqueue_steps(b, ncalls, 1);
 }

@@ -9,7 +9,8 @@
 //   eigenex_zlanczos_solver_*  LanczosEigenSolver<std::complex<double>>
 //   eigenex_arnoldi_solver_*   ArnoldiEigenSolver<double>
 //   eigenex_zarnoldi_solver_*  ArnoldiEigenSolver<std::complex<double>>
-// plus eigenex_[z]trlanczos_solver_* (ThickRestartLanczosEigenSolver) and eigenex_[z]kschur_solver_* (KrylovSchurEigenSolver).
+// plus eigenex_[z]trlanczos_solver_* (ThickRestartLanczosEigenSolver), eigenex_[z]kschur_solver_* (KrylovSchurEigenSolver) and
+// eigenex_[z]flanczos_solver_* (FilteredLanczosEigenSolver).
 // Complex data cross this boundary as interleaved (re, im) doubles.
 #include <complex>
 #include <cstring>
@@ -19,6 +20,7 @@
 
 #include "cmpt/eigen_ex/arnoldi.hpp"
 #include "cmpt/eigen_ex/block_operator.hpp"
+#include "cmpt/eigen_ex/filtered_lanczos.hpp"
 #include "cmpt/eigen_ex/krylov_schur.hpp"
 #include "cmpt/eigen_ex/lanczos.hpp"
 #include "cmpt/eigen_ex/lanczos_function.hpp"
@@ -242,11 +244,22 @@ int ar_get(void* p, double* hess, double* eigenvalues, double* eigenvectors, dou
 }
 
 // ---- thick-restart Lanczos -----------------------------------------------------------------
+inline bool tr_set_extra(ThickRestartLanczosEigenSolver<double>&, const std::string&, double, double) { return false; }
+inline bool tr_set_extra(ThickRestartLanczosEigenSolver<std::complex<double>>&, const std::string&, double, double) { return false; }
 template <class S>
-int tr_set(void* p, const char* key, double v) {
+bool tr_set_extra(FilteredLanczosEigenSolver<S>& es, const std::string& k, double v, double v2) {
+  if (k == "target") es.setTarget(v);
+  else if (k == "filterDegree") es.setFilterDegree((Index)v);
+  else if (k == "spectralRange") es.setSpectralRange(v, v2);  // (lo, hi) travel as the (re, im) pair of the value
+  else return false;
+  return true;
+}
+template <class Solver>
+int tr_set(void* p, const char* key, double v, double v2) {
   return guard([&] {
-    auto& es = static_cast<Box<ThickRestartLanczosEigenSolver<S>>*>(p)->es;
+    auto& es = static_cast<Box<Solver>*>(p)->es;
     const std::string k(key);
+    if (tr_set_extra(es, k, v, v2)) return;
     if (k == "numberOfEigenvalues") es.setNumberOfEigenvalues((Index)v);
     else if (k == "maxBasisSize") es.setMaxBasisSize((Index)v);
     else if (k == "keepSize") es.setKeepSize((Index)v);
@@ -259,10 +272,10 @@ int tr_set(void* p, const char* key, double v) {
   });
 }
 // sizes: [neigenvalues, eigvec_rows, eigvec_cols, restarts, operatorApplications, nlog, info]
-template <class S>
+template <class Solver>
 int tr_sizes(void* p, int64_t* out) {
   return guard([&] {
-    auto& es = static_cast<Box<ThickRestartLanczosEigenSolver<S>>*>(p)->es;
+    auto& es = static_cast<Box<Solver>*>(p)->es;
     out[0] = es.eigenvalues().size();
     out[1] = es.eigenvectors().rows();
     out[2] = es.eigenvectors().cols();
@@ -272,10 +285,11 @@ int tr_sizes(void* p, int64_t* out) {
     out[6] = (int64_t)es.info();
   });
 }
-template <class S>
+template <class Solver>
 int tr_get(void* p, double* eigenvalues, double* residuals, double* eigenvectors) {
+  using S = typename Solver::Scalar;
   return guard([&] {
-    auto& es = static_cast<Box<ThickRestartLanczosEigenSolver<S>>*>(p)->es;
+    auto& es = static_cast<Box<Solver>*>(p)->es;
     if (eigenvalues) std::copy(es.eigenvalues().begin(), es.eigenvalues().end(), eigenvalues);
     if (residuals) std::copy(es.residuals().begin(), es.residuals().end(), residuals);
     if (eigenvectors && es.eigenvectors().size())
@@ -622,30 +636,30 @@ int eigenex_solver_hessenberg_values_real(int n, const double* H, double* values
   int PFX##get(void* p, double* H, double* ev, double* X, double* res) { return ar_get<S>(p, H, ev, X, res); }              \
   int64_t PFX##convergence_log(void* p, int64_t i, double* out, int64_t cap) { return ar_convergence_log<S>(p, i, out, cap); }
 
-#define EIGENEX_TRLANCZOS_FAMILY(PFX, S)                                                                                \
+#define EIGENEX_TRLANCZOS_FAMILY(PFX, SOLVER)                                                                           \
   void* PFX##create(void) {                                                                                             \
     try {                                                                                                               \
-      return new Box<ThickRestartLanczosEigenSolver<S>>();                                                              \
+      return new Box<SOLVER>();                                                                                         \
     } catch (const std::exception& e) {                                                                                 \
       g_serr = e.what();                                                                                                \
       return nullptr;                                                                                                   \
     }                                                                                                                   \
   }                                                                                                                     \
-  void PFX##destroy(void* p) { delete static_cast<Box<ThickRestartLanczosEigenSolver<S>>*>(p); }                        \
+  void PFX##destroy(void* p) { delete static_cast<Box<SOLVER>*>(p); }                                                   \
   int PFX##set_device_operator(void* p, eigenex_context_t ctx, eigenex_csr_t csr) {                                     \
-    return sv_set_device_operator<ThickRestartLanczosEigenSolver<S>>(p, ctx, csr);                                      \
+    return sv_set_device_operator<SOLVER>(p, ctx, csr);                                                                 \
   }                                                                                                                     \
   int PFX##set_host_operator(void* p, eigenex_context_t ctx, eigenex_matvec_fn fn, void* user, int64_t height) {        \
-    return sv_set_host_operator<ThickRestartLanczosEigenSolver<S>>(p, ctx, fn, user, height);                           \
+    return sv_set_host_operator<SOLVER>(p, ctx, fn, user, height);                                                      \
   }                                                                                                                     \
   int PFX##set_initial_vector(void* p, const double* v, int64_t n) {                                                    \
-    return guard([&] { static_cast<Box<ThickRestartLanczosEigenSolver<S>>*>(p)->es.setInitialVector(make_vector<S>(v, n)); }); \
+    return guard([&] { static_cast<Box<SOLVER>*>(p)->es.setInitialVector(make_vector<SOLVER::Scalar>(v, n)); });        \
   }                                                                                                                     \
-  int PFX##set(void* p, const char* key, double v, double) { return tr_set<S>(p, key, v); }                             \
-  int PFX##compute(void* p) { return guard([&] { static_cast<Box<ThickRestartLanczosEigenSolver<S>>*>(p)->es.compute(); }); } \
-  int PFX##sizes(void* p, int64_t* out) { return tr_sizes<S>(p, out); }                                                 \
-  int PFX##get(void* p, double* ev, double* res, double* X) { return tr_get<S>(p, ev, res, X); }                        \
-  const char* PFX##log_line(void* p, int64_t i) { return sv_log_line<ThickRestartLanczosEigenSolver<S>>(p, i); }
+  int PFX##set(void* p, const char* key, double v, double v2) { return tr_set<SOLVER>(p, key, v, v2); }                 \
+  int PFX##compute(void* p) { return guard([&] { static_cast<Box<SOLVER>*>(p)->es.compute(); }); }                      \
+  int PFX##sizes(void* p, int64_t* out) { return tr_sizes<SOLVER>(p, out); }                                            \
+  int PFX##get(void* p, double* ev, double* res, double* X) { return tr_get<SOLVER>(p, ev, res, X); }                   \
+  const char* PFX##log_line(void* p, int64_t i) { return sv_log_line<SOLVER>(p, i); }
 
 #define EIGENEX_KSCHUR_FAMILY(PFX, S)                                                                                   \
   void* PFX##create(void) {                                                                                             \
@@ -683,6 +697,16 @@ int eigenex_solver_krylov_schur_basis(int is_complex, const double* H, int ldh, 
                     : ks_basis<double>(H, ldh, m, keep, residue, keep_out, Q, B, theta);
 }
 
+// Coefficients of FilteredLanczosEigenSolver's filter (chebyshevDeltaCoefficients): mu[degree + 1] of the Jackson-damped delta
+// peak at tau on [center - halfwidth, center + halfwidth], p(tau) = 1.  Host only.
+int eigenex_solver_chebyshev_delta(double tau, double center, double halfwidth, int degree, double* mu) {
+  return guard([&] {
+    if (degree < 0 || !mu || !(halfwidth > 0.0)) throw LanczosException("chebyshev_delta: degree >= 0, halfwidth > 0 and mu are required");
+    const std::vector<double> c = chebyshevDeltaCoefficients(tau, center, halfwidth, degree);
+    std::copy(c.begin(), c.end(), mu);
+  });
+}
+
 int eigenex_solver_exp_eigens(int is_complex, double x_re, double x_im, int64_t n, int64_t nev, const double* eivals,
                               const double* eivecs, int64_t max_expand, const double* in, double* out) {
   return is_complex ? fn_exp_eigens<std::complex<double>>(x_re, x_im, n, nev, eivals, eivecs, max_expand, in, out)
@@ -696,8 +720,11 @@ int eigenex_solver_exp_taylor(int is_complex, eigenex_context_t ctx, eigenex_csr
                     : fn_exp_taylor<double>(ctx, csr, fn, user, height, x_re, x_im, radius, in, n_in, out, error, max_expansion, auto_division);
 }
 
-EIGENEX_TRLANCZOS_FAMILY(eigenex_trlanczos_solver_, double)
-EIGENEX_TRLANCZOS_FAMILY(eigenex_ztrlanczos_solver_, std::complex<double>)
+EIGENEX_TRLANCZOS_FAMILY(eigenex_trlanczos_solver_, ThickRestartLanczosEigenSolver<double>)
+EIGENEX_TRLANCZOS_FAMILY(eigenex_ztrlanczos_solver_, ThickRestartLanczosEigenSolver<std::complex<double>>)
+// FilteredLanczosEigenSolver: the same entry points; _set also takes "target", "filterDegree" and "spectralRange" (lo, hi)
+EIGENEX_TRLANCZOS_FAMILY(eigenex_flanczos_solver_, FilteredLanczosEigenSolver<double>)
+EIGENEX_TRLANCZOS_FAMILY(eigenex_zflanczos_solver_, FilteredLanczosEigenSolver<std::complex<double>>)
 EIGENEX_KSCHUR_FAMILY(eigenex_kschur_solver_, double)
 EIGENEX_KSCHUR_FAMILY(eigenex_zkschur_solver_, std::complex<double>)
 EIGENEX_LANCZOS_FAMILY(eigenex_lanczos_solver_, double)

@@ -148,6 +148,7 @@ class ThickRestartLanczosEigenSolver {
       device::check(eigenex_basis_set_host_operator(dev_.handle(), &detail::HostOperatorThunk<Scalar>::call, &thunk_), "eigenex_basis_set_host_operator");
     }
     configure_(EIGENEX_ORTHO_BATCHED);
+    stateReady_();
     dev_.upload(EIGENEX_VEC_W, initial_);
 
     std::vector<double> T(static_cast<std::size_t>(m) * m, 0.0);  // projected matrix, column-major
@@ -240,6 +241,9 @@ class ThickRestartLanczosEigenSolver {
   }
 
  protected:
+  // the device state of this compute() exists and is configured: FilteredLanczosEigenSolver (filtered_lanczos.hpp), which runs
+  // this cycle on a polynomial of the operator, sets its filter here
+  virtual void stateReady_() {}
   void configure_(int mode) {
     device::check(eigenex_basis_configure(dev_.handle(), shift_, threshold_, 1, mode), "eigenex_basis_configure");
   }

@@ -47,7 +47,8 @@ def lib():
         L.eigenex_solver_gershgorin_range.argtypes = [C.c_int64, C.c_int64, _lp, _lp, _dp, C.c_int, _dp]
         L.eigenex_solver_blocks_to_csr.argtypes = [C.c_int, _lp, C.c_int, _lp, C.c_int, _lp, _lp, _dp, _ip32, _ip32, _dp, _lp]
         L.eigenex_solver_krylov_schur_basis.argtypes = [C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), _dp, _dp, _dp]
-        for kind in ("trlanczos", "ztrlanczos", "kschur", "zkschur"):
+        L.eigenex_solver_chebyshev_delta.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, _dp]
+        for kind in ("trlanczos", "ztrlanczos", "kschur", "zkschur", "flanczos", "zflanczos"):
             p = f"eigenex_{kind}_solver_"
             getattr(L, p + "create").restype = _vp
             getattr(L, p + "destroy").argtypes = [_vp]
@@ -190,6 +191,13 @@ def krylov_schur_basis(H, keep: int, residue: float):
     _chk(lib().eigenex_solver_krylov_schur_basis(int(cplx), _d(H), m, m, int(keep), float(residue), C.byref(k), _d(Q), _d(B), _d(theta)))
     k = k.value
     return k, Q[:, :k].copy(), B[: (k + 1) * k].reshape((k + 1, k), order="F").copy(), theta
+
+
+def chebyshev_delta(tau: float, center: float, halfwidth: float, degree: int) -> np.ndarray:
+    """chebyshevDeltaCoefficients (filtered_lanczos.hpp): mu[degree + 1] of the Jackson-damped delta peak at tau, p(tau) = 1"""
+    mu = np.zeros(int(degree) + 1)
+    _chk(lib().eigenex_solver_chebyshev_delta(float(tau), float(center), float(halfwidth), int(degree), _d(mu)))
+    return mu
 
 
 def triplets_to_csr(n, rows, cols, vals):
@@ -456,6 +464,20 @@ class ThickRestartLanczosEigenSolver(_SolverBase):
         _chk(self._f("get")(self.h, _d(ev), _d(res), _d(X) if X.size else None))
         s.update(eigenvalues=ev, residuals=res, eigenvectors=X, info_name=INFO[s["info"]])
         return s
+
+
+class FilteredLanczosEigenSolver(ThickRestartLanczosEigenSolver):
+    """FilteredLanczosEigenSolver<S> (filtered_lanczos.hpp): the eigenpairs of a Hermitian device operator nearest
+    `target`, by thick-restart Lanczos on a Chebyshev delta filter of the operator.  Settings of the thick-restart solver
+    plus target, filterDegree and spectralRange=(lo, hi) (required).  residuals are the true ||A x - lambda x||."""
+
+    _base = "flanczos"
+
+    def set(self, **kw):
+        if "spectralRange" in kw:
+            lo, hi = kw.pop("spectralRange")
+            _chk(self._f("set")(self.h, b"spectralRange", float(lo), float(hi)))
+        return super().set(**kw)
 
 
 class KrylovSchurEigenSolver(_SolverBase):

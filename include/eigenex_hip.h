@@ -339,6 +339,23 @@ int eigenex_vec_copy(eigenex_basis_t b, int dst_ref, int src_ref);
  * y = A*x + shift*x ; if dot != NULL also *dot = x . y      (a1, a2, a3 of SURVEY 8a); works with a CSR/block
  * handle or, on an unsharded context, with the host callback of eigenex_basis_set_host_operator */
 int eigenex_apply(eigenex_basis_t b, int x_ref, int y_ref, double shift, double* dot);
+/* Chebyshev polynomial filter of a Hermitian device operator:  p(A) = sum_k mu[k] T_k((A - center)/halfwidth),  k <= degree,
+ * mu real (mu[degree + 1] is copied).  While a filter is set, eigenex_lanczos_enqueue builds the Krylov space of p(A) instead of
+ * A (alpha, beta and the basis are those of p(A): with a Jackson-damped delta peak at a target energy the eigenvalues of A
+ * nearest the target become the largest of p(A)); eigenex_apply keeps meaning A itself.  [center - halfwidth, center +
+ * halfwidth] must contain the spectrum of A.  degree = 0 removes the filter (mu may be NULL).  Setting or removing a filter
+ * drops the recorded step batches of the state.  The first call allocates two more work vectors.
+ * Per row and degree, every product rounded before it is added:  a = (A t_k)[i] + (-center) t_k[i];  t_1 = (1/halfwidth) a,
+ * t_{k+1} = (2/halfwidth) a - t_{k-1};  acc_1 = mu[0] x + mu[1] t_1,  acc_{k+1} = acc_k + mu[k+1] t_{k+1}.  One-pass real CSR
+ * operators (plain or row-coded) take this in the operator kernel's epilogue, all others in a streaming kernel behind the
+ * operator: the same bits.  EIGENEX_NO_FUSED_FILTER in the environment, read by every call, selects the second form everywhere.
+ * Between shards one application of p(A) issues `degree` neighbour exchanges.
+ * EIGENEX_ERR_ARG: degree < 0, mu == NULL, halfwidth <= 0;  EIGENEX_ERR_STATE: the operator is a host callback.
+ * With a filter set, eigenex_arnoldi_enqueue and a Lanczos step with a non-zero eigenvalue shift return EIGENEX_ERR_STATE. */
+int eigenex_basis_set_filter(eigenex_basis_t b, int degree, const double* mu, double center, double halfwidth);
+/* y = p(A) x with the filter of the state; synchronises; vector references as for eigenex_apply (x is copied into the operator
+ * input vector W, y may not be W or x) */
+int eigenex_filter_apply(eigenex_basis_t b, int x_ref, int y_ref);
 /* h[i] = col(first + i*stride) . w, i < count, then h[count + q] = ortho(q) . w, q < n_ortho_used   (a5 dot half) */
 int eigenex_dots(eigenex_basis_t b, int w_ref, int first, int stride, int count, int n_ortho_used, double* h);
 /* w -= sum_i h[i]*col(first+i*stride) + sum_q h[count+q]*ortho(q); *nrm2 = ||w||^2   (a5 axpy half, a6) */
