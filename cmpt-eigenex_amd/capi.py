@@ -118,6 +118,9 @@ SIGNATURES = {
     "eigenex_apply": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _dp]),
     "eigenex_basis_set_filter": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double]),
     "eigenex_filter_apply": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "eigenex_kpm_moments": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_double, _dp]),
+    "eigenex_kpm_trace_moments": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_double, C.c_double, _dp]),
+    "eigenex_vec_random_signs": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_uint64]),
     "eigenex_dots": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "eigenex_update": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "eigenex_axpy2": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int]),
@@ -619,6 +622,21 @@ class Basis:
     def filter_apply(self, x_ref, y_ref):
         """y = p(A) x with the filter of set_filter"""
         _chk(lib().eigenex_filter_apply(self.h, x_ref, y_ref))
+
+    def kpm_moments(self, x_ref, n_moments, center, halfwidth):
+        """mu[k] = <x| T_k((A - center)/halfwidth) |x>, k < n_moments; VEC_V then holds the last Chebyshev vector"""
+        mu = np.zeros(max(int(n_moments), 0), np.float64)
+        _chk(lib().eigenex_kpm_moments(self.h, x_ref, n_moments, center, halfwidth, _d(mu) if mu.size else None))
+        return mu
+
+    def kpm_trace_moments(self, n_moments, n_vectors, seed, first_stream, center, halfwidth):
+        """the moments of n_vectors random-sign vectors (streams first_stream ..), divided by N: array [n_vectors, n_moments]"""
+        mu = np.zeros((max(int(n_vectors), 0), max(int(n_moments), 0)), np.float64)
+        _chk(lib().eigenex_kpm_trace_moments(self.h, n_moments, n_vectors, seed, first_stream, center, halfwidth, _d(mu) if mu.size else None))
+        return mu
+
+    def random_signs(self, x_ref, seed, stream):
+        _chk(lib().eigenex_vec_random_signs(self.h, x_ref, seed, stream))
 
     def dots(self, w_ref, first, stride, count, n_ortho_used=0):
         h = np.zeros(count + n_ortho_used, self.dtype)

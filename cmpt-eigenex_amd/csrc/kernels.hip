@@ -527,6 +527,86 @@ __global__ __launch_bounds__(kBlock) void k_cheb_combine(const double* __restric
 }
 
 // ---------------------------------------------------------------------------
+// Chebyshev moments step (kernels.hpp: MomentStep): the recurrence of the filter step without the accumulator, and the two
+// dot products of a kernel-polynomial step, <t_{k+1}, t_{k+1}> and <t_{k+1}, t_k>, as per-workgroup partial sums (fixed order:
+// per-thread fma chains over the thread's rows, block_sum).  moment_store: one row, in the epilogue of the one-pass real CSR
+// kernels (x = the row's own operator input = t_k).  k_cheb_moments: behind any other operator kernel, which has stored a as y;
+// k_cheb_combine's tiles and grid.  t_{k-1} is read once and t_{k+1} written once with the loads / stores cheb_store uses.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ double moment_row_nofma(double a, double t_prev, const MomentStep& mo) {
+#pragma clang fp contract(off)
+  const double ca = mo.c * a;
+  return mo.first ? ca : ca - t_prev;
+}
+__device__ __forceinline__ double moment_store(const MomentStep& mo, int64_t r, double a) {
+  const double tp = mo.first ? 0.0 : mo.t_prev[r];
+  const double t = moment_row_nofma(a, tp, mo);
+  __builtin_nontemporal_store(t, &mo.t_next[r]);
+  return t;
+}
+
+template <bool FULL>
+__device__ __forceinline__ void moments_tile(const double* __restrict__ y, const MomentStep& mo, int64_t base, int64_t n, double* tt, double* tx) {
+  double2 a[4], tp[4], x[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t row = base + i * (2 * kBlock);
+    a[i] = tp[i] = x[i] = make_double2(0.0, 0.0);
+    if (FULL || row < n) {
+      a[i] = nt_ld_d2(y + row);
+      x[i] = ld2(mo.t_cur + row);
+      if (!mo.first) tp[i] = ld2(mo.t_prev + row);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t row = base + i * (2 * kBlock);
+    if (FULL || row < n) {
+      double2 t;
+      t.x = moment_row_nofma(a[i].x, tp[i].x, mo);
+      t.y = moment_row_nofma(a[i].y, tp[i].y, mo);
+      nt_st2(mo.t_next + row, t);
+      *tt = fma(t.x, t.x, *tt);
+      *tt = fma(t.y, t.y, *tt);
+      *tx = fma(t.x, x[i].x, *tx);
+      *tx = fma(t.y, x[i].y, *tx);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_cheb_moments(const double* __restrict__ y, MomentStep mo, int64_t n, int64_t ntiles,
+                                                         double* __restrict__ partials, const Ctrl* __restrict__ ctrl) {
+  __shared__ double lds4[4];
+  if (ctrl->stopped) return;
+  double tt = 0.0, tx = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t base = tile * kTileRows + 2 * threadIdx.x;
+    if ((tile + 1) * kTileRows <= n)
+      moments_tile<true>(y, mo, base, n, &tt, &tx);
+    else
+      moments_tile<false>(y, mo, base, n, &tt, &tx);
+  }
+  tt = block_sum(tt, lds4);
+  tx = block_sum(tx, lds4);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = tt;
+    partials[mo.pstride + blockIdx.x] = tx;
+  }
+}
+
+// out[r] = +1 or -1 from random_sign_bit(seed, stream, row0 + r) (kernels.hpp), r < n; es = 2: (+-1, 0) pairs
+__global__ __launch_bounds__(kBlock) void k_random_signs(double* __restrict__ out, int64_t n, int64_t row0, int es, uint64_t seed, uint64_t stream) {
+  const uint64_t key = random_sign_key(seed, stream);
+  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < n; r += (int64_t)gridDim.x * kBlock) {
+    const double v = random_sign_bit(key, (uint64_t)(row0 + r)) ? -1.0 : 1.0;
+    if (es == 2)
+      st2(out + 2 * r, make_double2(v, 0.0));
+    else
+      out[r] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // CSR SpMV, "stream" formulation: a tile of 256 rows owns a contiguous range of
 // stored entries.  Phase 1 streams val/col with aligned 16-B loads (4 entries per
 // lane), gathers x (L2/MALL-served) and parks the rounded products in LDS
@@ -633,8 +713,9 @@ __global__ __launch_bounds__(kBlock) void k_spmv(const OFF* __restrict__ rowptr,
                                                  int64_t ntiles, double* __restrict__ partials, int spmv_flags,
                                                  int pass, const Ctrl* ctrl, InlineFin fin, InlineArnoldiBegin ab,
                                                  const int32_t* __restrict__ tile_list) {  // no __restrict__ on ctrl: fin.ctrl / ab.ctrl alias it
-  constexpr bool CHEB = false;
+  constexpr bool CHEB = false, MOM = false;
   const ChebStep ch{};
+  const MomentStep mo{};
 #include "spmv_body.hpp"
 }
 // the same rows with a Chebyshev step in the epilogue (no hooks, no partial dots): the body is compiled a second time, so that
@@ -645,12 +726,30 @@ __global__ __launch_bounds__(kBlock) void k_spmv_cheb(const OFF* __restrict__ ro
                                                       const double* __restrict__ scale_ptr, double shift, double* __restrict__ u_out,
                                                       int64_t n, int64_t ntiles, int spmv_flags, const Ctrl* __restrict__ ctrl,
                                                       const int32_t* __restrict__ tile_list, ChebStep ch) {
-  constexpr bool CHEB = true;
+  constexpr bool CHEB = true, MOM = false;
   constexpr int pass = 0;
   double* const y = nullptr;
   double* const partials = nullptr;
   const InlineFin fin{};
   const InlineArnoldiBegin ab{};
+  const MomentStep mo{};
+#include "spmv_body.hpp"
+}
+// a third compile: the moments step (moment_store) in the epilogue, its two partial dots in partials[block] and
+// partials[mo.pstride + block]; no hooks, y never written
+template <bool LONG_ROWS, class OFF, bool NT>
+__global__ __launch_bounds__(kBlock) void k_spmv_moments(const OFF* __restrict__ rowptr, const int32_t* __restrict__ col_all,
+                                                         const double* __restrict__ val_all, const double* __restrict__ x_ext,
+                                                         const double* __restrict__ scale_ptr, double shift, double* __restrict__ partials,
+                                                         int64_t n, int64_t ntiles, int spmv_flags, const Ctrl* __restrict__ ctrl,
+                                                         const int32_t* __restrict__ tile_list, MomentStep mo) {
+  constexpr bool CHEB = false, MOM = true;
+  constexpr int pass = 0;
+  double* const y = nullptr;
+  double* const u_out = nullptr;
+  const InlineFin fin{};
+  const InlineArnoldiBegin ab{};
+  const ChebStep ch{};
 #include "spmv_body.hpp"
 }
 
@@ -680,20 +779,35 @@ __global__ __launch_bounds__(kBlock) void k_spmv_rows(RowCodeView op, const doub
                                                       int64_t ntiles, double* __restrict__ partials, int spmv_flags,
                                                       int pass, const Ctrl* ctrl, InlineFin fin, InlineArnoldiBegin ab,
                                                       const int32_t* __restrict__ tile_list) {  // no __restrict__ on ctrl: fin.ctrl / ab.ctrl alias it
-  constexpr bool CHEB = false;
+  constexpr bool CHEB = false, MOM = false;
   const ChebStep ch{};
+  const MomentStep mo{};
 #include "spmv_rows_body.hpp"
 }
 template <int REC>  // as k_spmv_cheb
 __global__ __launch_bounds__(kBlock) void k_spmv_rows_cheb(RowCodeView op, const double* __restrict__ x_ext, const double* __restrict__ scale_ptr,
                                                            double shift, double* __restrict__ u_out, int64_t n, int64_t ntiles, int spmv_flags,
                                                            const Ctrl* __restrict__ ctrl, const int32_t* __restrict__ tile_list, ChebStep ch) {
-  constexpr bool CHEB = true;
+  constexpr bool CHEB = true, MOM = false;
   constexpr int pass = 0;
   double* const y = nullptr;
   double* const partials = nullptr;
   const InlineFin fin{};
   const InlineArnoldiBegin ab{};
+  const MomentStep mo{};
+#include "spmv_rows_body.hpp"
+}
+template <int REC>  // as k_spmv_moments
+__global__ __launch_bounds__(kBlock) void k_spmv_rows_moments(RowCodeView op, const double* __restrict__ x_ext, const double* __restrict__ scale_ptr,
+                                                              double shift, double* __restrict__ partials, int64_t n, int64_t ntiles, int spmv_flags,
+                                                              const Ctrl* __restrict__ ctrl, const int32_t* __restrict__ tile_list, MomentStep mo) {
+  constexpr bool CHEB = false, MOM = true;
+  constexpr int pass = 0;
+  double* const y = nullptr;
+  double* const u_out = nullptr;
+  const InlineFin fin{};
+  const InlineArnoldiBegin ab{};
+  const ChebStep ch{};
 #include "spmv_rows_body.hpp"
 }
 
@@ -2015,12 +2129,26 @@ template <class OFF>
 static void launch_spmv_t(hipStream_t s, const OFF* rowptr, const int32_t* col, const double* val, const double* x_ext,
                           const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                           const Ctrl* ctrl, int spmv_flags, int pass, const InlineFin* fin, const InlineArnoldiBegin* begin,
-                          const int32_t* tile_list, int64_t list_len, const ChebStep* cheb) {
+                          const int32_t* tile_list, int64_t list_len, const ChebStep* cheb, const MomentStep* mom) {
   const int64_t ntiles = tile_list ? list_len : (n + kSpmvRows - 1) / kSpmvRows;
   if (ntiles <= 0) return;
   const InlineFin nofin{nullptr, 0, 0, 0.0, nullptr, nullptr, nullptr};
   const InlineArnoldiBegin nobegin{nullptr, 0.0, 0, 0, nullptr, 0, 0, -1, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
   const bool nt = (spmv_flags & 2) != 0;
+  if (mom) {  // the moments epilogue: no hooks, two partial dots
+#define EIGENEX_LAUNCH_SPMV_MOM(LONG, NTV)                                                                                                     \
+  hipLaunchKernelGGL((k_spmv_moments<LONG, OFF, NTV>), dim3(grid), dim3(kBlock), 0, s, rowptr, col, val, x_ext, scale, shift, partials, n, ntiles, \
+                     spmv_flags, ctrl, tile_list, *mom)
+    if (spmv_flags & kSpmvLongRows) {
+      if (nt) EIGENEX_LAUNCH_SPMV_MOM(true, true);
+      else EIGENEX_LAUNCH_SPMV_MOM(true, false);
+    } else {
+      if (nt) EIGENEX_LAUNCH_SPMV_MOM(false, true);
+      else EIGENEX_LAUNCH_SPMV_MOM(false, false);
+    }
+#undef EIGENEX_LAUNCH_SPMV_MOM
+    return;
+  }
   if (cheb) {  // the Chebyshev epilogue: no hooks, no partial dots
 #define EIGENEX_LAUNCH_SPMV_CHEB(LONG, NTV)                                                                                                \
   hipLaunchKernelGGL((k_spmv_cheb<LONG, OFF, NTV>), dim3(grid), dim3(kBlock), 0, s, rowptr, col, val, x_ext, scale, shift, u_out, n, ntiles, \
@@ -2050,24 +2178,28 @@ static void launch_spmv_t(hipStream_t s, const OFF* rowptr, const int32_t* col, 
 void launch_spmv(hipStream_t s, const int32_t* rowptr, const int32_t* col, const double* val, const double* x_ext,
                  const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                  const Ctrl* ctrl, int spmv_flags, int pass, const InlineFin* fin, const InlineArnoldiBegin* begin,
-                 const int32_t* tile_list, int64_t list_len, const ChebStep* cheb) {
-  launch_spmv_t(s, rowptr, col, val, x_ext, scale, shift, y, u_out, n, partials, grid, ctrl, spmv_flags, pass, fin, begin, tile_list, list_len, cheb);
+                 const int32_t* tile_list, int64_t list_len, const ChebStep* cheb, const MomentStep* mom) {
+  launch_spmv_t(s, rowptr, col, val, x_ext, scale, shift, y, u_out, n, partials, grid, ctrl, spmv_flags, pass, fin, begin, tile_list, list_len, cheb, mom);
 }
 void launch_spmv64(hipStream_t s, const int64_t* rowptr, const int32_t* col, const double* val, const double* x_ext,
                    const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                    const Ctrl* ctrl, int spmv_flags, int pass, const InlineFin* fin, const InlineArnoldiBegin* begin,
-                   const int32_t* tile_list, int64_t list_len, const ChebStep* cheb) {
-  launch_spmv_t(s, rowptr, col, val, x_ext, scale, shift, y, u_out, n, partials, grid, ctrl, spmv_flags, pass, fin, begin, tile_list, list_len, cheb);
+                   const int32_t* tile_list, int64_t list_len, const ChebStep* cheb, const MomentStep* mom) {
+  launch_spmv_t(s, rowptr, col, val, x_ext, scale, shift, y, u_out, n, partials, grid, ctrl, spmv_flags, pass, fin, begin, tile_list, list_len, cheb, mom);
 }
 void launch_spmv_rows(hipStream_t s, const RowCodeView& op, const double* x_ext, const double* scale, double shift, double* y,
                       double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int spmv_flags, int pass,
                       const InlineFin* fin, const InlineArnoldiBegin* begin, const int32_t* tile_list, int64_t list_len,
-                      const ChebStep* cheb) {
+                      const ChebStep* cheb, const MomentStep* mom) {
   const int64_t ntiles = tile_list ? list_len : (n + kSpmvRows - 1) / kSpmvRows;
   if (ntiles <= 0) return;
   const InlineFin nofin{nullptr, 0, 0, 0.0, nullptr, nullptr, nullptr};
   const InlineArnoldiBegin nobegin{nullptr, 0.0, 0, 0, nullptr, 0, 0, -1, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-  if (cheb && op.rec_bytes == 8)
+  if (mom && op.rec_bytes == 8)
+    hipLaunchKernelGGL(k_spmv_rows_moments<8>, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, partials, n, ntiles, spmv_flags, ctrl, tile_list, *mom);
+  else if (mom)
+    hipLaunchKernelGGL(k_spmv_rows_moments<16>, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, partials, n, ntiles, spmv_flags, ctrl, tile_list, *mom);
+  else if (cheb && op.rec_bytes == 8)
     hipLaunchKernelGGL(k_spmv_rows_cheb<8>, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, u_out, n, ntiles, spmv_flags, ctrl, tile_list, *cheb);
   else if (cheb)
     hipLaunchKernelGGL(k_spmv_rows_cheb<16>, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, u_out, n, ntiles, spmv_flags, ctrl, tile_list, *cheb);
@@ -2199,6 +2331,17 @@ void launch_shift_dot(hipStream_t s, double* y, const double* u, double shift, i
 void launch_cheb_combine(hipStream_t s, const double* y, const ChebStep& step, int64_t n, int grid, const Ctrl* ctrl) {
   const int64_t ntiles = (n + kTileRows - 1) / kTileRows;
   hipLaunchKernelGGL(k_cheb_combine, dim3(grid), dim3(kBlock), 0, s, y, step, n, ntiles, ctrl);
+}
+
+void launch_cheb_moments(hipStream_t s, const double* y, const MomentStep& step, int64_t n, double* partials, int grid, const Ctrl* ctrl) {
+  const int64_t ntiles = (n + kTileRows - 1) / kTileRows;
+  hipLaunchKernelGGL(k_cheb_moments, dim3(grid), dim3(kBlock), 0, s, y, step, n, ntiles, partials, ctrl);
+}
+
+void launch_random_signs(hipStream_t s, double* out, int64_t n, int64_t row0, int es, uint64_t seed, uint64_t stream) {
+  if (n <= 0) return;
+  const int grid = grid_for_tiles((n + kBlock - 1) / kBlock, 8);
+  hipLaunchKernelGGL(k_random_signs, dim3(grid), dim3(kBlock), 0, s, out, n, row0, es, seed, stream);
 }
 
 void launch_pack(hipStream_t s, const double* x, const int32_t* idx, int64_t count, int es, double* out,

@@ -125,6 +125,38 @@ struct ChebStep {
   int first;
 };
 
+// One degree of a Chebyshev moments run (kernel polynomial method): the recurrence of ChebStep without the accumulator,
+//   first:  t_1 = c*a (c = 1/halfwidth);   later:  t_{k+1} = c*a - t_{k-1} (c = 2/halfwidth),
+// products rounded before they are added, and per workgroup the partial sums of <t_{k+1}, t_{k+1}> (partials[block]) and
+// <t_{k+1}, t_k> (partials[pstride + block]); t_k is the operator input.  t_next may be t_prev, neither may be the operator input.
+struct MomentStep {
+  const double* t_prev;  // unused in the first step
+  double* t_next;
+  const double* t_cur;   // t_k for k_cheb_moments; the fused operator kernels take it from their own input
+  double c;
+  int first;
+  int pstride;
+};
+
+// Random signs: entry `row` (GLOBAL row number) of vector `stream` of the family `seed` is -1 if the top bit of
+//   key = mix((mix(seed + G) ^ stream) + G),   h = mix((key ^ row) + G)            (arithmetic modulo 2^64)
+// is set, else +1, with G = 0x9E3779B97F4A7C15 and the splitmix64 finaliser
+//   mix(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31.
+// A function of (seed, stream, row) alone: the same vector under every sharding.  tests/density_reference.py restates it.
+__host__ __device__ inline uint64_t random_sign_mix(uint64_t z) {
+  z ^= z >> 30;
+  z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27;
+  z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
+__host__ __device__ inline uint64_t random_sign_key(uint64_t seed, uint64_t stream) {
+  const uint64_t G = 0x9E3779B97F4A7C15ull;
+  return random_sign_mix((random_sign_mix(seed + G) ^ stream) + G);
+}
+__host__ __device__ inline bool random_sign_bit(uint64_t key, uint64_t row) { return (random_sign_mix((key ^ row) + 0x9E3779B97F4A7C15ull) >> 63) != 0; }
+
 int grid_for_tiles(int64_t ntiles, int blocks_per_cu);
 void set_num_cu(int n);
 
@@ -164,7 +196,8 @@ void launch_spmv(hipStream_t s, const int32_t* rowptr, const int32_t* col, const
                  const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                  const Ctrl* ctrl, int spmv_flags = 0, int pass = 0, const InlineFin* fin = nullptr,
                  const InlineArnoldiBegin* begin = nullptr, const int32_t* tile_list = nullptr, int64_t list_len = 0,
-                 const ChebStep* cheb = nullptr);
+                 const ChebStep* cheb = nullptr, const MomentStep* mom = nullptr);
+// (mom: the kernel takes a moments step in its epilogue: only x_ext, scale, shift, partials (two sets, mom->pstride apart) are used)
 // (cheb: the kernel takes a Chebyshev step in its epilogue instead of storing y -- y, partials and the hooks are unused then)
 // (tile_list: the launch covers the 256-row tiles tile_list[0 .. list_len) only -- interior / boundary launches of a shard)
 // the same with 64-bit row pointers (plain real CSR in one pass): a shard may hold >= 2^31 stored entries; col stays int32
@@ -172,7 +205,7 @@ void launch_spmv64(hipStream_t s, const int64_t* rowptr, const int32_t* col, con
                    const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                    const Ctrl* ctrl, int spmv_flags = 0, int pass = 0, const InlineFin* fin = nullptr,
                    const InlineArnoldiBegin* begin = nullptr, const int32_t* tile_list = nullptr, int64_t list_len = 0,
-                   const ChebStep* cheb = nullptr);
+                   const ChebStep* cheb = nullptr, const MomentStep* mom = nullptr);
 // Row-coded operator (real fp64 in one pass; row_codes.hpp, kernels.hip: k_spmv_rows): rec = one record of rec_bytes (8 or 16)
 // per row of every 256-row tile, pal = npal values, slots = the offsets.  Same tiles, grid, partial dots and hooks as launch_spmv.
 struct RowCodeView {
@@ -184,7 +217,7 @@ struct RowCodeView {
 void launch_spmv_rows(hipStream_t s, const RowCodeView& op, const double* x_ext, const double* scale, double shift, double* y,
                       double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int spmv_flags = 0, int pass = 0,
                       const InlineFin* fin = nullptr, const InlineArnoldiBegin* begin = nullptr, const int32_t* tile_list = nullptr,
-                      int64_t list_len = 0, const ChebStep* cheb = nullptr);
+                      int64_t list_len = 0, const ChebStep* cheb = nullptr, const MomentStep* mom = nullptr);
 // records of a device-resident CSR shard (rowptr or rowptr64) for rows [0, nrec_rows) with given tables; *bad counts rows that
 // do not fit them
 struct RowCodePalette {
@@ -270,6 +303,11 @@ void launch_shift_dot(hipStream_t s, double* y, const double* u, double shift, i
 // the Chebyshev step behind an operator kernel that has stored y = (A - center) t_k: n in DOUBLES (complex vectors: 2N, the
 // coefficients are real); reads y, t_prev and acc, writes t_next and acc
 void launch_cheb_combine(hipStream_t s, const double* y, const ChebStep& step, int64_t n, int grid, const Ctrl* ctrl);
+// the moments step behind an operator kernel that has stored y = (A - center) t_k: n in DOUBLES (a complex vector's plain real dot
+// over 2N doubles is Re<t_k, t_{k+1}>); reads y, step.t_cur and step.t_prev, writes step.t_next and the two partial sums per workgroup
+void launch_cheb_moments(hipStream_t s, const double* y, const MomentStep& step, int64_t n, double* partials, int grid, const Ctrl* ctrl);
+// out[r*es] = +-1 (random_sign_bit of the global row row0 + r), imaginary parts 0, r < n
+void launch_random_signs(hipStream_t s, double* out, int64_t n, int64_t row0, int es, uint64_t seed, uint64_t stream);
 // gather send buffer: out[i] = x[idx[i]]
 void launch_pack(hipStream_t s, const double* x, const int32_t* idx, int64_t count, int es, double* out,
                  const Ctrl* ctrl);

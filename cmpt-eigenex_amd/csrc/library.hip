@@ -353,6 +353,10 @@ struct BasisShard {
   // Chebyshev filter (eigenex_basis_set_filter; made by the first call): w2 = a second operator input with halo slots -- t_k is
   // gathered from one while t_{k+1} is written to the other --, fy = the operator's output where the step is not taken in its epilogue
   DeviceBuffer<double> w2, fy;
+  // Chebyshev moments (eigenex_kpm_moments): the raw dot products of a call, (<t_j, t_j>, <t_j, t_{j-1}>) per degree j and run;
+  // grown by the call that needs more
+  DeviceBuffer<double> kmom;
+  size_t kmom_len = 0;
   DeviceBuffer<double> partials, hbuf, alpha, beta, H;
   DeviceBuffer<double> pnorm;  // partial sums handed from a producer kernel to the consumer that finalises them (InlineFin)
   double* palpha = nullptr;    // pnorm + pstride
@@ -437,19 +441,19 @@ namespace {
 // ---------------------------------------------------------------------------
 // transports
 // ---------------------------------------------------------------------------
-// in-place sum over all shards of hbuf[off .. off+n) on every shard
-int allreduce(eigenex_basis_s* b, int off, int n) {
+// in-place sum over all shards of buf[off .. off+n) on every shard (buf: hbuf, or kmom at the end of a moments run)
+int allreduce(eigenex_basis_s* b, int off, int n, DeviceBuffer<double> BasisShard::*buf = &BasisShard::hbuf) {
   eigenex_context_s* c = b->ctx;
   if ((c->P == 1 && !c->comm) || n <= 0) return 0;  // a 1-rank communicator (self-test) still goes through RCCL
   if (c->tracing) c->trace.push_back({EIGENEX_COLL_ALLREDUCE, n});
   ProfScope ps(c, EIGENEX_K_COMM, 0.0);
   if (c->loopback) {
     PtrPack pk;
-    for (size_t s = 0; s < b->sh.size(); ++s) pk.p[s] = b->sh[s].hbuf + off;
+    for (size_t s = 0; s < b->sh.size(); ++s) pk.p[s] = (b->sh[s].*buf) + off;
     launch_sum_shards(c->stream, pk, (int)b->sh.size(), n);
     return 0;
   }
-  double* p = b->sh[0].hbuf + off;
+  double* p = (b->sh[0].*buf) + off;
   NCCLCHK(ncclAllReduce(p, p, (size_t)n, ncclDouble, ncclSum, c->comm, c->stream));
   return 0;
 }
@@ -1578,6 +1582,7 @@ struct OperatorPass {
   const InlineArnoldiBegin* begin = nullptr;  // operator kernels that have the hook only (inline_begin_ok)
   hipEvent_t halo_done = nullptr;  // the launches that read halo slots wait for it (the halo exchange is on its way on the other stream)
   const ChebStep* cheb = nullptr;  // one-pass real CSR only (filter_in_epilogue): a Chebyshev step instead of the store of y
+  const MomentStep* mom = nullptr;  // the same kernels: a moments step instead, its two partial dots in `partials`
 };
 
 struct TileList {  // the 256-row tiles one launch covers (none: all)
@@ -1592,13 +1597,13 @@ void launch_csr_one_pass(hipStream_t st, const BasisShard& s, const OperatorPass
   const int flags = s.spmv_flags | (!m->rc_rec || tl.tiles ? long_rows_flag(m) : 0);
   if (m->rc_rec)
     launch_spmv_rows(st, row_code_view(m), p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, partials, grid, p.ctrl, flags, p.pass_flags, p.fin,
-                     p.begin, tl.tiles, tl.len, p.cheb);
+                     p.begin, tl.tiles, tl.len, p.cheb, p.mom);
   else if (m->rowptr64)
     launch_spmv64(st, m->rowptr64, m->col, m->val, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, partials, grid, p.ctrl, flags, p.pass_flags,
-                  p.fin, p.begin, tl.tiles, tl.len, p.cheb);
+                  p.fin, p.begin, tl.tiles, tl.len, p.cheb, p.mom);
   else
     launch_spmv(st, m->rowptr, m->col, m->val, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, partials, grid, p.ctrl, flags, p.pass_flags, p.fin,
-                p.begin, tl.tiles, tl.len, p.cheb);
+                p.begin, tl.tiles, tl.len, p.cheb, p.mom);
 }
 
 // a launch per column-block pass, the row sums carried in y; s.g_spmv workgroups = partial dots.  Operators with interior /
@@ -1697,6 +1702,55 @@ int enq_filter(eigenex_basis_s* b, const FilterPass& p) {
         ProfScope ps(c, EIGENEX_K_SPMV, (first ? 32.0 : 40.0) * s.nd);
         launch_cheb_combine(c->stream, s.fy, step, s.nd, s.g_vec, ctrl);
       }
+    }
+  }
+  return 0;
+}
+
+// Chebyshev moments of x = w (kernel polynomial method): `degree` operator applications with the filter's recurrence, halo
+// exchange and work vectors, no accumulator; application j leaves (<t_{j+1}, t_{j+1}>, <t_{j+1}, t_j>) in kmom[off + 2(j+1) ..],
+// <t_0, t_0> goes to kmom[off].  The step is taken in the operator kernel's epilogue where it has one (fused), else by
+// k_cheb_moments from the operator's output in fy.  The last application writes t_d to v.  Nothing comes back to the host, and
+// nothing is all-reduced: the caller sums kmom over the shards once.
+struct MomentsPass {
+  int degree;
+  double center, half;
+  bool fused;
+  int off;
+};
+int enq_moments(eigenex_basis_s* b, const MomentsPass& p) {
+  eigenex_context_s* c = b->ctx;
+  const double c1 = 1.0 / p.half, c2 = 2.0 / p.half;
+  const bool overlap = c->halo_overlap && c->P > 1;
+  for (auto& s : b->sh) {
+    {
+      ProfScope ps(c, EIGENEX_K_DOTS, 8.0 * s.nd);
+      launch_shift_dot(c->stream, s.w, s.w, 0.0, s.nd, s.partials, s.g_vec, s.ctrl_zero);
+    }
+    ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
+    launch_reduce(c->stream, s.partials, s.pstride, s.g_vec, 1, s.kmom + p.off, s.ctrl_zero);
+  }
+  for (int j = 0; j < p.degree; ++j) {
+    const WorkVector in = (j & 1) ? &BasisShard::w2 : &BasisShard::w, out = (j & 1) ? &BasisShard::w : &BasisShard::w2;
+    if (overlap) HIPCHK(hipEventRecord(c->ev_w_ready, c->stream));
+    CHK(halo_exchange(b, CtrlBlock::Zero, overlap, in));
+    for (auto& s : b->sh) {
+      const bool first = j == 0, last = j == p.degree - 1;
+      const bool fused = p.fused && filter_in_epilogue(s);
+      const MomentStep step{s.*out, last ? s.v.get() : (s.*out).get(), s.*in, first ? c1 : c2, first ? 1 : 0, s.pstride};
+      const double stream_bytes = (first ? 16.0 : 24.0) * s.nd;  // t_k, (t_{k-1},) t_{k+1}
+      {
+        ProfScope ps(c, EIGENEX_K_SPMV, operator_bytes(s.csr, b->es) + (fused ? stream_bytes : 16.0 * s.nd));
+        launch_operator(c->stream, s, {.x = s.*in, .scale = nullptr, .shift = -p.center, .y = fused ? nullptr : s.fy.get(),
+                                       .partials = fused ? s.partials.get() : nullptr, .ctrl = s.ctrl_zero,
+                                       .halo_done = overlap ? c->ev_halo_done : nullptr, .mom = fused ? &step : nullptr});
+      }
+      if (!fused) {
+        ProfScope ps(c, EIGENEX_K_SPMV, (first ? 24.0 : 32.0) * s.nd);
+        launch_cheb_moments(c->stream, s.fy, step, s.nd, s.partials, s.g_vec, s.ctrl_zero);
+      }
+      ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
+      launch_reduce(c->stream, s.partials, s.pstride, fused ? s.g_spmv : s.g_vec, 2, s.kmom + p.off + 2 * (j + 1), s.ctrl_zero);
     }
   }
   return 0;
@@ -3343,6 +3397,29 @@ int eigenex_apply(eigenex_basis_t b, int x_ref, int y_ref, double shift, double*
   return 0;
 }
 
+// the second operator input (and, with_fy, the operator's output) of the Chebyshev recurrences, once per state; all or nothing
+static int ensure_cheb_buffers(eigenex_basis_s* b, bool with_fy) {
+  eigenex_context_s* c = b->ctx;
+  std::vector<DeviceBuffer<double>> w2(b->sh.size()), fy(b->sh.size());
+  for (size_t i = 0; i < b->sh.size(); ++i) {
+    const BasisShard& s = b->sh[i];
+    const size_t nw = (size_t)(s.ldv + s.nhalo + 8) * s.es;
+    if (!s.w2) {
+      HIPCHK(w2[i].alloc(nw));
+      HIPCHK(hipMemsetAsync(w2[i], 0, sizeof(double) * nw, c->stream));
+    }
+    if (with_fy && !s.fy) {
+      HIPCHK(fy[i].alloc((size_t)s.ldd));
+      HIPCHK(hipMemsetAsync(fy[i], 0, sizeof(double) * (size_t)s.ldd, c->stream));
+    }
+  }
+  for (size_t i = 0; i < b->sh.size(); ++i) {
+    if (w2[i]) b->sh[i].w2 = std::move(w2[i]);
+    if (fy[i]) b->sh[i].fy = std::move(fy[i]);
+  }
+  return 0;
+}
+
 int eigenex_basis_set_filter(eigenex_basis_t b, int degree, const double* mu, double center, double halfwidth) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
   if (degree < 0 || (degree > 0 && (!mu || !(halfwidth > 0.0) || !std::isfinite(halfwidth) || !std::isfinite(center))))
@@ -3350,20 +3427,7 @@ int eigenex_basis_set_filter(eigenex_basis_t b, int degree, const double* mu, do
   if (degree > 0 && !b->csr) return fail(EIGENEX_ERR_STATE, "eigenex_basis_set_filter: a filter needs a device operator");
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
-  if (degree > 0) {  // the second operator input and the operator's output, once per state; all or nothing
-    std::vector<DeviceBuffer<double>> w2(b->sh.size()), fy(b->sh.size());
-    for (size_t i = 0; i < b->sh.size(); ++i) {
-      const BasisShard& s = b->sh[i];
-      if (s.w2) continue;
-      const size_t nw = (size_t)(s.ldv + s.nhalo + 8) * s.es;
-      HIPCHK(w2[i].alloc(nw));
-      HIPCHK(fy[i].alloc((size_t)s.ldd));
-      HIPCHK(hipMemsetAsync(w2[i], 0, sizeof(double) * nw, c->stream));
-      HIPCHK(hipMemsetAsync(fy[i], 0, sizeof(double) * (size_t)s.ldd, c->stream));
-    }
-    for (size_t i = 0; i < b->sh.size(); ++i)
-      if (w2[i]) b->sh[i].w2 = std::move(w2[i]), b->sh[i].fy = std::move(fy[i]);
-  }
+  if (degree > 0) CHK(ensure_cheb_buffers(b, true));
   HIPCHK(hipStreamSynchronize(c->stream));
   drop_step_graphs(b);  // recorded batches hold the coefficients (and the launches) of the filter they were recorded with
   b->f_degree = degree;
@@ -3386,6 +3450,109 @@ int eigenex_filter_apply(eigenex_basis_t b, int x_ref, int y_ref) {
     if (x != s.w) HIPCHK(hipMemcpyAsync(s.w, x, sizeof(double) * s.nd, hipMemcpyDeviceToDevice, c->stream));
   }
   CHK(enq_filter(b, {.ctrl = CtrlBlock::Zero, .ucol = std::nullopt, .acc_ref = y_ref}));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---- Chebyshev moments (kernel polynomial method) ----
+static int kpm_applications(int n_moments) { return n_moments / 2; }  // ceil((n_moments - 1) / 2)
+
+// what a moments call needs besides the arguments' checks: work vectors, the dots array (runs * 2 (d + 1) doubles, zeroed)
+static int kpm_prepare(eigenex_basis_s* b, int d, int runs, bool fused) {
+  eigenex_context_s* c = b->ctx;
+  bool streaming = false;
+  for (auto& s : b->sh) streaming = streaming || !(fused && filter_in_epilogue(s));
+  if (d > 0) CHK(ensure_cheb_buffers(b, streaming));
+  const size_t len = (size_t)runs * 2 * ((size_t)d + 1);
+  if (len > (size_t)INT32_MAX) return fail(EIGENEX_ERR_ARG, "eigenex_kpm_moments: n_moments * n_vectors is too large");
+  for (auto& s : b->sh) {
+    if (s.kmom_len < len) {
+      DeviceBuffer<double> m;
+      HIPCHK(m.alloc(len));
+      s.kmom = std::move(m), s.kmom_len = len;
+    }
+    HIPCHK(hipMemsetAsync(s.kmom, 0, sizeof(double) * len, c->stream));
+  }
+  return 0;
+}
+
+// the dots of `runs` runs from the device (one all-reduce, one synchronisation) -> mu[run * n_moments + k], divided by `divisor`:
+// mu_0 = <t_0,t_0>, mu_1 = <t_1,t_0>, mu_2k = 2 <t_k,t_k> - mu_0, mu_2k+1 = 2 <t_k+1,t_k> - mu_1
+static int kpm_collect(eigenex_basis_s* b, int d, int runs, int n_moments, double divisor, double* mu) {
+  const int L = 2 * (d + 1);
+  CHK(allreduce(b, 0, runs * L, &BasisShard::kmom));
+  std::vector<double> raw((size_t)runs * L);
+  HIPCHK(hipMemcpyAsync(raw.data(), b->sh[0].kmom, sizeof(double) * raw.size(), hipMemcpyDeviceToHost, b->ctx->stream));
+  HIPCHK(hipStreamSynchronize(b->ctx->stream));
+  for (int i = 0; i < runs; ++i) {
+    const double* D = raw.data() + (size_t)i * L;
+    double* m = mu + (size_t)i * n_moments;
+    const double mu0 = D[0], mu1 = d > 0 ? D[3] : 0.0;
+    for (int k = 0; k < n_moments; ++k) {
+      double v;
+      if (k == 0)
+        v = mu0;
+      else if (k == 1)
+        v = mu1;
+      else if (k % 2 == 0)
+        v = 2.0 * D[2 * (k / 2)] - mu0;
+      else
+        v = 2.0 * D[2 * (k / 2 + 1) + 1] - mu1;
+      m[k] = v / divisor;
+    }
+  }
+  return 0;
+}
+
+int eigenex_kpm_moments(eigenex_basis_t b, int x_ref, int n_moments, double center, double halfwidth, double* mu) {
+  if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  if (n_moments < 1 || !mu || !(halfwidth > 0.0) || !std::isfinite(halfwidth) || !std::isfinite(center))
+    return fail(EIGENEX_ERR_ARG, "eigenex_kpm_moments: n_moments >= 1, mu[n_moments] and halfwidth > 0 are needed");
+  if (!b->csr) return fail(EIGENEX_ERR_STATE, "eigenex_kpm_moments: the moments need a device operator");
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  for (auto& s : b->sh)
+    if (!vec_ptr(s, b->cap, b->nq, x_ref)) return fail(EIGENEX_ERR_ARG, "bad vector reference");
+  const int d = kpm_applications(n_moments);
+  const bool fused = std::getenv("EIGENEX_NO_FUSED_FILTER") == nullptr;
+  CHK(kpm_prepare(b, d, 1, fused));
+  for (auto& s : b->sh) {
+    const double* x = vec_ptr(s, b->cap, b->nq, x_ref);
+    if (x != s.w) HIPCHK(hipMemcpyAsync(s.w, x, sizeof(double) * s.nd, hipMemcpyDeviceToDevice, c->stream));
+    if (d == 0 && x != s.v) HIPCHK(hipMemcpyAsync(s.v, x, sizeof(double) * s.nd, hipMemcpyDeviceToDevice, c->stream));
+  }
+  CHK(enq_moments(b, {.degree = d, .center = center, .half = halfwidth, .fused = fused, .off = 0}));
+  return kpm_collect(b, d, 1, n_moments, 1.0, mu);
+}
+
+int eigenex_kpm_trace_moments(eigenex_basis_t b, int n_moments, int n_vectors, uint64_t seed, uint64_t first_stream, double center,
+                              double halfwidth, double* mu_each) {
+  if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  if (n_moments < 1 || n_vectors < 1 || !mu_each || !(halfwidth > 0.0) || !std::isfinite(halfwidth) || !std::isfinite(center))
+    return fail(EIGENEX_ERR_ARG, "eigenex_kpm_trace_moments: n_moments >= 1, n_vectors >= 1, mu_each[n_vectors * n_moments] and halfwidth > 0 are needed");
+  if (!b->csr) return fail(EIGENEX_ERR_STATE, "eigenex_kpm_trace_moments: the moments need a device operator");
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const int d = kpm_applications(n_moments);
+  const bool fused = std::getenv("EIGENEX_NO_FUSED_FILTER") == nullptr;
+  CHK(kpm_prepare(b, d, n_vectors, fused));
+  for (int i = 0; i < n_vectors; ++i) {
+    for (auto& s : b->sh) {
+      launch_random_signs(c->stream, s.w, s.nloc, s.rb, s.es, seed, first_stream + (uint64_t)i);
+      if (d == 0) HIPCHK(hipMemcpyAsync(s.v, s.w, sizeof(double) * s.nd, hipMemcpyDeviceToDevice, c->stream));
+    }
+    CHK(enq_moments(b, {.degree = d, .center = center, .half = halfwidth, .fused = fused, .off = i * 2 * (d + 1)}));
+  }
+  return kpm_collect(b, d, n_vectors, n_moments, (double)b->n_global, mu_each);
+}
+
+int eigenex_vec_random_signs(eigenex_basis_t b, int x_ref, uint64_t seed, uint64_t stream) {
+  if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  for (auto& s : b->sh)
+    if (!vec_ptr(s, b->cap, b->nq, x_ref)) return fail(EIGENEX_ERR_ARG, "bad vector reference");
+  for (auto& s : b->sh) launch_random_signs(c->stream, vec_ptr(s, b->cap, b->nq, x_ref), s.nloc, s.rb, s.es, seed, stream);
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }

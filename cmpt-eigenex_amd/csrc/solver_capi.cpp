@@ -10,7 +10,7 @@
 //   eigenex_arnoldi_solver_*   ArnoldiEigenSolver<double>
 //   eigenex_zarnoldi_solver_*  ArnoldiEigenSolver<std::complex<double>>
 // plus eigenex_[z]trlanczos_solver_* (ThickRestartLanczosEigenSolver), eigenex_[z]kschur_solver_* (KrylovSchurEigenSolver) and
-// eigenex_[z]flanczos_solver_* (FilteredLanczosEigenSolver).
+// eigenex_[z]flanczos_solver_* (FilteredLanczosEigenSolver); eigenex_[z]density_solver_* (SpectralDensitySolver).
 // Complex data cross this boundary as interleaved (re, im) doubles.
 #include <complex>
 #include <cstring>
@@ -24,6 +24,7 @@
 #include "cmpt/eigen_ex/krylov_schur.hpp"
 #include "cmpt/eigen_ex/lanczos.hpp"
 #include "cmpt/eigen_ex/lanczos_function.hpp"
+#include "cmpt/eigen_ex/spectral_density.hpp"
 #include "cmpt/eigen_ex/thick_restart_lanczos.hpp"
 #include "cmpt/eigen_ex/triplets_operator.hpp"
 
@@ -433,6 +434,42 @@ int fn_exp_taylor(eigenex_context_t ctx, eigenex_csr_t csr, eigenex_matvec_fn fn
   });
 }
 
+// ---- spectral density (spectral_density.hpp) -----------------------------------------------------
+template <class Solver>
+int sd_set(void* p, const char* key, double v, double v2) {
+  return guard([&] {
+    auto& es = static_cast<Box<Solver>*>(p)->es;
+    const std::string k(key);
+    if (k == "spectralRange") es.setSpectralRange(v, v2);
+    else if (k == "moments") es.setMoments((Index)v);
+    else if (k == "randomVectors") es.setRandomVectors((Index)v);
+    else throw LanczosException("unknown setting: " + k);
+  });
+}
+template <class Solver>
+int sd_sizes(void* p, int64_t* out) {
+  return guard([&] {
+    auto& es = static_cast<Box<Solver>*>(p)->es;
+    out[0] = (int64_t)es.moments().size();
+    out[1] = (int64_t)es.randomVectors();
+    out[2] = (int64_t)es.operatorApplications();
+    out[3] = (int64_t)es.log().size();
+    out[4] = (int64_t)es.info();
+  });
+}
+// mean[M], standard error[M], each[R*M] (any may be NULL); range[2] = (center, halfwidth)
+template <class Solver>
+int sd_get(void* p, double* mean, double* se, double* each, double* range) {
+  return guard([&] {
+    auto& es = static_cast<Box<Solver>*>(p)->es;
+    if (mean) std::copy(es.moments().begin(), es.moments().end(), mean);
+    if (se) std::copy(es.momentsStandardError().begin(), es.momentsStandardError().end(), se);
+    if (each)
+      for (const auto& m : es.momentsOfEachVector()) each = std::copy(m.begin(), m.end(), each);
+    if (range) range[0] = es.center(), range[1] = es.halfwidth();
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -720,6 +757,78 @@ int eigenex_solver_exp_taylor(int is_complex, eigenex_context_t ctx, eigenex_csr
                     : fn_exp_taylor<double>(ctx, csr, fn, user, height, x_re, x_im, radius, in, n_in, out, error, max_expansion, auto_division);
 }
 
+// SpectralDensitySolver: the entry points of the family above as far as they apply (no host operator, no eigenpairs); _set takes
+// "spectralRange" (lo, hi), "moments", "randomVectors"; the results are moments and functions of an energy
+#define EIGENEX_DENSITY_FAMILY(PFX, SOLVER)                                                                             \
+  void* PFX##create(void) {                                                                                             \
+    try {                                                                                                               \
+      return new Box<SOLVER>();                                                                                         \
+    } catch (const std::exception& e) {                                                                                 \
+      g_serr = e.what();                                                                                                \
+      return nullptr;                                                                                                   \
+    }                                                                                                                   \
+  }                                                                                                                     \
+  void PFX##destroy(void* p) { delete static_cast<Box<SOLVER>*>(p); }                                                   \
+  int PFX##set_device_operator(void* p, eigenex_context_t ctx, eigenex_csr_t csr) {                                     \
+    return sv_set_device_operator<SOLVER>(p, ctx, csr);                                                                 \
+  }                                                                                                                     \
+  int PFX##set_initial_vector(void* p, const double* v, int64_t n) {                                                    \
+    return guard([&] {                                                                                                  \
+      if (v) static_cast<Box<SOLVER>*>(p)->es.setInitialVector(make_vector<SOLVER::Scalar>(v, n));                      \
+      else static_cast<Box<SOLVER>*>(p)->es.setInitialVector();                                                         \
+    });                                                                                                                 \
+  }                                                                                                                     \
+  int PFX##set(void* p, const char* key, double v, double v2) { return sd_set<SOLVER>(p, key, v, v2); }                 \
+  int PFX##set_seed(void* p, uint64_t seed) { return guard([&] { static_cast<Box<SOLVER>*>(p)->es.setSeed(seed); }); }  \
+  int PFX##compute(void* p) { return guard([&] { static_cast<Box<SOLVER>*>(p)->es.compute(); }); }                      \
+  int PFX##continue(void* p) { return guard([&] { static_cast<Box<SOLVER>*>(p)->es.continueToCompute(); }); }           \
+  int PFX##sizes(void* p, int64_t* out) { return sd_sizes<SOLVER>(p, out); }                                            \
+  int PFX##get(void* p, double* mean, double* se, double* each, double* range) { return sd_get<SOLVER>(p, mean, se, each, range); } \
+  int PFX##density(void* p, const double* E, int64_t n, double* out) {                                                  \
+    return guard([&] {                                                                                                  \
+      for (int64_t i = 0; i < n; ++i) out[i] = static_cast<Box<SOLVER>*>(p)->es.density(E[i]);                          \
+    });                                                                                                                 \
+  }                                                                                                                     \
+  int PFX##eigenvalue_count(void* p, double a, double b, double* count, double* standard_error) {                       \
+    return guard([&] {                                                                                                  \
+      if (count) *count = static_cast<Box<SOLVER>*>(p)->es.eigenvalueCount(a, b);                                       \
+      if (standard_error) *standard_error = static_cast<Box<SOLVER>*>(p)->es.eigenvalueCountStandardError(a, b);        \
+    });                                                                                                                 \
+  }                                                                                                                     \
+  int PFX##energy_window(void* p, double tau, double count, double* halfwidth) {                                        \
+    return guard([&] { *halfwidth = static_cast<Box<SOLVER>*>(p)->es.energyWindow(tau, count); });                      \
+  }                                                                                                                     \
+  const char* PFX##log_line(void* p, int64_t i) { return sv_log_line<SOLVER>(p, i); }
+
+// The host arithmetic behind SpectralDensitySolver's results (kpmDensity, kpmCount, kpmWindow, jacksonFactor) for given
+// normalised moments mu[M].  Host only.
+int eigenex_solver_jackson_factors(int M, double* g) {
+  return guard([&] {
+    if (M < 1 || !g) throw LanczosException("jackson_factors: M >= 1 and g are required");
+    for (int k = 0; k < M; ++k) g[k] = jacksonFactor(k, M);
+  });
+}
+int eigenex_solver_kpm_density(const double* mu, int M, double center, double halfwidth, const double* E, int64_t n, double* out) {
+  return guard([&] {
+    if (M < 1 || !mu || !(halfwidth > 0.0)) throw LanczosException("kpm_density: mu[M], M >= 1 and halfwidth > 0 are required");
+    for (int64_t i = 0; i < n; ++i) out[i] = kpmDensity(mu, M, center, halfwidth, E[i]);
+  });
+}
+int eigenex_solver_kpm_count(const double* mu, int M, double center, double halfwidth, double a, double b, double N, double* out) {
+  return guard([&] {
+    if (M < 1 || !mu || !(halfwidth > 0.0)) throw LanczosException("kpm_count: mu[M], M >= 1 and halfwidth > 0 are required");
+    *out = kpmCount(mu, M, center, halfwidth, a, b, N);
+  });
+}
+int eigenex_solver_kpm_window(const double* mu, int M, double center, double halfwidth, double tau, double count, double N, double* out) {
+  return guard([&] {
+    if (M < 1 || !mu || !(halfwidth > 0.0)) throw LanczosException("kpm_window: mu[M], M >= 1 and halfwidth > 0 are required");
+    *out = kpmWindow(mu, M, center, halfwidth, tau, count, N);
+  });
+}
+
+EIGENEX_DENSITY_FAMILY(eigenex_density_solver_, SpectralDensitySolver<double>)
+EIGENEX_DENSITY_FAMILY(eigenex_zdensity_solver_, SpectralDensitySolver<std::complex<double>>)
 EIGENEX_TRLANCZOS_FAMILY(eigenex_trlanczos_solver_, ThickRestartLanczosEigenSolver<double>)
 EIGENEX_TRLANCZOS_FAMILY(eigenex_ztrlanczos_solver_, ThickRestartLanczosEigenSolver<std::complex<double>>)
 // FilteredLanczosEigenSolver: the same entry points; _set also takes "target", "filterDegree" and "spectralRange" (lo, hi)

@@ -1,4 +1,4 @@
-// Body of k_spmv and k_spmv_cheb (kernels.hip), a list of statements #included inside both kernels.
+// Body of k_spmv, k_spmv_cheb and k_spmv_moments (kernels.hip), a list of statements #included inside these kernels.
 // The includer defines, as parameters or as constants in front of the #include, every name the body uses:
 //   LONG_ROWS, OFF, NT (template parameters)          -- as documented at k_spmv
 //   rowptr, col_all, val_all,
@@ -7,8 +7,12 @@
 //   CHEB (constexpr bool), ch (ChebStep)              -- CHEB: the epilogue takes a Chebyshev step from the row sum (cheb_store)
 //                                                        instead of storing it to y and adding to the partial dot; ch is read
 //                                                        only then
+//   MOM (constexpr bool), mo (MomentStep)             -- MOM: the epilogue takes a moments step from the row sum (moment_store)
+//                                                        and adds its two partial dots, partials[block] and
+//                                                        partials[mo.pstride + block]; mo is read only then
 // k_spmv_cheb passes y = partials = nullptr, pass = 0 and empty fin / ab as constants: the hooks, the carry and the partial dots
-// fold away at compile time.  A name added to the body has to be added to BOTH includers (and to this list).
+// fold away at compile time; k_spmv_moments passes y = u_out = nullptr, pass = 0 and empty fin / ab likewise.  A name added to the
+// body has to be added to ALL includers (and to this list).
   // tile_list != nullptr: the launch covers the ntiles tiles tile_list[0 .. ntiles) instead of 0 .. ntiles (r3: the interior
   // rows of a shard run while the halo is still on its way, the tiles that read halo columns afterwards; library.hip)
   __shared__ double prod[kSpmvProdSlots];
@@ -35,7 +39,7 @@
     scale = 1.0 / nrm;
   }
   const int tid = threadIdx.x;
-  double dot = 0.0;
+  double dot = 0.0, dot2 = 0.0;  // dot2: MOM only
   constexpr bool nt = NT;  // flags: bit 0 = XCD-contiguous tiles, bit 1 = cache policy of the val/col streams (NT, chosen by the launcher)
   const TileRange tr = spmv_tiles(ntiles, spmv_flags & 1);
   // row pointers of a tile: fetched one tile ahead, so that their latency is not part of the chain
@@ -145,7 +149,11 @@
       const double xr = x_ext[r] * scale;
       double yr = sum;
       if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
-      if constexpr (CHEB) {
+      if constexpr (MOM) {
+        const double t = moment_store(mo, r, yr);
+        dot = fma(t, t, dot);
+        dot2 = fma(t, xr, dot2);
+      } else if constexpr (CHEB) {
         cheb_store(ch, r, yr, xr);
         if (u_out) __builtin_nontemporal_store(xr, &u_out[r]);
       } else {
@@ -159,4 +167,8 @@
   if (partials) {
     dot = block_sum(dot, lds4);
     if (tid == 0) partials[blockIdx.x] = dot;
+    if constexpr (MOM) {
+      dot2 = block_sum(dot2, lds4);
+      if (tid == 0) partials[mo.pstride + blockIdx.x] = dot2;
+    }
   }

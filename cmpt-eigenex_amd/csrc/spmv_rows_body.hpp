@@ -1,4 +1,4 @@
-// Body of k_spmv_rows and k_spmv_rows_cheb (kernels.hip), a list of statements #included inside both kernels.
+// Body of k_spmv_rows, k_spmv_rows_cheb and k_spmv_rows_moments (kernels.hip), a list of statements #included inside these kernels.
 // The includer defines, as parameters or as constants in front of the #include, every name the body uses:
 //   REC (template parameter: record bytes, 8 or 16), op (RowCodeView),
 //   x_ext, scale_ptr, shift, y, u_out, n, ntiles, partials, spmv_flags, pass, ctrl, fin (InlineFin), ab (InlineArnoldiBegin),
@@ -6,8 +6,12 @@
 //   CHEB (constexpr bool), ch (ChebStep)              -- CHEB: the epilogue takes a Chebyshev step from the row sum (cheb_store)
 //                                                        instead of storing it to y and adding to the partial dot; ch is read
 //                                                        only then
+//   MOM (constexpr bool), mo (MomentStep)             -- MOM: the epilogue takes a moments step from the row sum (moment_store)
+//                                                        and adds its two partial dots, partials[block] and
+//                                                        partials[mo.pstride + block]; mo is read only then
 // k_spmv_rows_cheb passes y = partials = nullptr, pass = 0 and empty fin / ab as constants: the hooks, the carry and the partial dots
-// fold away at compile time.  A name added to the body has to be added to BOTH includers (and to this list).
+// fold away at compile time; k_spmv_rows_moments passes y = u_out = nullptr, pass = 0 and empty fin / ab likewise.  A name added to the
+// body has to be added to ALL includers (and to this list).
   constexpr int W = REC / 8, S = REC;  // 64-bit words and slots per record
   __shared__ double pal[kRowCodeMaxValues];
   __shared__ double lds4[4];
@@ -35,7 +39,7 @@
   }
   __syncthreads();  // the palette
   const int tid = threadIdx.x;
-  double dot = 0.0;
+  double dot = 0.0, dot2 = 0.0;  // dot2: MOM only
   const TileRange tr = spmv_tiles(ntiles, spmv_flags & 1);
   auto tile_of = [&](int64_t slot) { return tile_list ? (int64_t)tile_list[slot] : slot; };
   // records exist for every row of every tile (rows behind n: all slots absent), so the loads need no row test
@@ -65,7 +69,11 @@
       const double xr = x_ext[r] * scale;
       double yr = sum;
       if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
-      if constexpr (CHEB) {
+      if constexpr (MOM) {
+        const double t = moment_store(mo, r, yr);
+        dot = fma(t, t, dot);
+        dot2 = fma(t, xr, dot2);
+      } else if constexpr (CHEB) {
         cheb_store(ch, r, yr, xr);
         if (u_out) __builtin_nontemporal_store(xr, &u_out[r]);
       } else {
@@ -81,4 +89,8 @@
   if (partials) {
     dot = block_sum(dot, lds4);
     if (tid == 0) partials[blockIdx.x] = dot;
+    if constexpr (MOM) {
+      dot2 = block_sum(dot2, lds4);
+      if (tid == 0) partials[mo.pstride + blockIdx.x] = dot2;
+    }
   }

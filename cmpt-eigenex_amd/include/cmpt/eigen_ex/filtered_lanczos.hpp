@@ -24,17 +24,23 @@
 namespace cmpt {
 namespace EigenEx {
 
+// g_k of the Jackson kernel for an expansion of N moments, k < N (Weisse et al., eq. 71); shared with spectral_density.hpp
+inline double jacksonFactor(int k, int N) {
+  const double pi = 3.14159265358979323846;
+  const double q = pi / (N + 1);
+  return ((N - k + 1) * std::cos(q * k) + std::sin(q * k) / std::tan(q)) / (N + 1);
+}
+
 // mu_0..mu_degree of the Jackson-damped delta peak at tau on [center - halfwidth, center + halfwidth], p(tau) = 1
 inline std::vector<double> chebyshevDeltaCoefficients(double tau, double center, double halfwidth, int degree) {
-  const double pi = 3.14159265358979323846;
   const int N = degree + 1;  // number of moments
   const double a = std::min(1.0, std::max(-1.0, (tau - center) / halfwidth));
-  const double th = std::acos(a), q = pi / (N + 1);
+  const double th = std::acos(a);
   std::vector<double> mu(static_cast<std::size_t>(N));
   double at_tau = 0.0, lost = 0.0;  // p(tau) before normalisation, summed with Neumaier's compensation
   for (int k = 0; k < N; ++k) {
-    const double g = ((N - k + 1) * std::cos(q * k) + std::sin(q * k) / std::tan(q)) / (N + 1);  // Jackson kernel
-    const double t = std::cos(k * th);                                                            // T_k(a)
+    const double g = jacksonFactor(k, N);
+    const double t = std::cos(k * th);  // T_k(a)
     mu[static_cast<std::size_t>(k)] = (k == 0 ? 1.0 : 2.0) * g * t;
     const double term = mu[static_cast<std::size_t>(k)] * t, sum = at_tau + term;
     lost += std::abs(at_tau) >= std::abs(term) ? (at_tau - sum) + term : (term - sum) + at_tau;

@@ -62,6 +62,28 @@ def lib():
             getattr(L, p + "get").argtypes = [_vp, _dp, _dp, _dp]
             getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
             getattr(L, p + "log_line").restype = C.c_char_p
+        L.eigenex_solver_jackson_factors.argtypes = [C.c_int, _dp]
+        L.eigenex_solver_kpm_density.argtypes = [_dp, C.c_int, C.c_double, C.c_double, _dp, C.c_int64, _dp]
+        L.eigenex_solver_kpm_count.argtypes = [_dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp]
+        L.eigenex_solver_kpm_window.argtypes = [_dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp]
+        for kind in ("density", "zdensity"):
+            p = f"eigenex_{kind}_solver_"
+            getattr(L, p + "create").restype = _vp
+            getattr(L, p + "destroy").argtypes = [_vp]
+            getattr(L, p + "destroy").restype = None
+            getattr(L, p + "set_device_operator").argtypes = [_vp, _vp, _vp]
+            getattr(L, p + "set").argtypes = [_vp, C.c_char_p, C.c_double, C.c_double]
+            getattr(L, p + "set_seed").argtypes = [_vp, C.c_uint64]
+            getattr(L, p + "set_initial_vector").argtypes = [_vp, _dp, C.c_int64]
+            getattr(L, p + "compute").argtypes = [_vp]
+            getattr(L, p + "continue").argtypes = [_vp]
+            getattr(L, p + "sizes").argtypes = [_vp, _lp]
+            getattr(L, p + "get").argtypes = [_vp, _dp, _dp, _dp, _dp]
+            getattr(L, p + "density").argtypes = [_vp, _dp, C.c_int64, _dp]
+            getattr(L, p + "eigenvalue_count").argtypes = [_vp, C.c_double, C.c_double, _dp, _dp]
+            getattr(L, p + "energy_window").argtypes = [_vp, C.c_double, C.c_double, _dp]
+            getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
+            getattr(L, p + "log_line").restype = C.c_char_p
         for kind in FAMILIES:
             p = f"eigenex_{kind}_solver_"
             getattr(L, p + "create").restype = _vp
@@ -297,6 +319,35 @@ def gershgorin_range(n, rows, cols, vals):
     return out[0], out[1]
 
 
+def jackson_factors(M: int) -> np.ndarray:
+    """g_0..g_{M-1} of the Jackson kernel (jacksonFactor, filtered_lanczos.hpp)"""
+    g = np.zeros(M)
+    _chk(lib().eigenex_solver_jackson_factors(M, _d(g)))
+    return g
+
+
+def kpm_density(mu, center, halfwidth, E) -> np.ndarray:
+    """kpmDensity (spectral_density.hpp) of normalised moments mu at the energies E"""
+    mu, E = np.ascontiguousarray(mu, np.float64), np.ascontiguousarray(np.atleast_1d(E), np.float64)
+    out = np.zeros(E.size)
+    _chk(lib().eigenex_solver_kpm_density(_d(mu), mu.size, center, halfwidth, _d(E), E.size, _d(out)))
+    return out
+
+
+def kpm_count(mu, center, halfwidth, a, b, N) -> float:
+    mu = np.ascontiguousarray(mu, np.float64)
+    out = C.c_double()
+    _chk(lib().eigenex_solver_kpm_count(_d(mu), mu.size, center, halfwidth, a, b, N, C.byref(out)))
+    return out.value
+
+
+def kpm_window(mu, center, halfwidth, tau, count, N) -> float:
+    mu = np.ascontiguousarray(mu, np.float64)
+    out = C.c_double()
+    _chk(lib().eigenex_solver_kpm_window(_d(mu), mu.size, center, halfwidth, tau, count, N, C.byref(out)))
+    return out.value
+
+
 class _SolverBase:
     _base = ""
 
@@ -499,3 +550,63 @@ class KrylovSchurEigenSolver(_SolverBase):
         _chk(self._f("get")(self.h, _d(ev), _d(res), _d(X) if X.size else None))
         s.update(eigenvalues=ev, residuals=res, eigenvectors=X, info_name=INFO[s["info"]])
         return s
+
+
+class SpectralDensitySolver(_SolverBase):
+    """SpectralDensitySolver<S> (spectral_density.hpp): Chebyshev moments of a Hermitian device operator by the kernel
+    polynomial method, and from them the Jackson-damped density of states, eigenvalue counts of energy windows and the
+    window that holds a wanted number of levels.  Settings: spectralRange=(lo, hi) (required), moments, randomVectors, seed,
+    initialVector (the local density of that vector instead; None returns to random vectors)."""
+
+    _base = "density"
+    _names = ("nmoments", "nvectors", "operatorApplications", "nlog", "info")
+
+    def set(self, **kw):
+        for k, v in kw.items():
+            if k == "spectralRange":
+                _chk(self._f("set")(self.h, b"spectralRange", float(v[0]), float(v[1])))
+            elif k == "seed":
+                _chk(self._f("set_seed")(self.h, int(v)))
+            elif k == "initialVector":
+                if v is None:
+                    _chk(self._f("set_initial_vector")(self.h, None, 0))
+                else:
+                    a = np.ascontiguousarray(v, self.dtype)
+                    _chk(self._f("set_initial_vector")(self.h, _d(a), a.size))
+            else:
+                _chk(self._f("set")(self.h, k.encode(), float(v), 0.0))
+        return self
+
+    def _sizes(self):
+        out = np.zeros(len(self._names), np.int64)
+        _chk(self._f("sizes")(self.h, out.ctypes.data_as(_lp)))
+        return dict(zip(self._names, (int(x) for x in out)))
+
+    def results(self):
+        s = self._sizes()
+        M, R = s["nmoments"], s["nvectors"]
+        mean, se, each, rng = np.zeros(M), np.zeros(M), np.zeros((R, M)), np.zeros(2)
+        _chk(self._f("get")(self.h, _d(mean), _d(se), _d(each) if each.size else None, _d(rng)))
+        s.update(moments=mean, momentsStandardError=se, momentsOfEachVector=each, center=rng[0], halfwidth=rng[1], info_name=INFO[s["info"]])
+        return s
+
+    def density(self, E):
+        E = np.ascontiguousarray(np.atleast_1d(E), np.float64)
+        out = np.zeros(E.size)
+        _chk(self._f("density")(self.h, _d(E), E.size, _d(out)))
+        return out
+
+    def eigenvalueCount(self, a, b):
+        c = C.c_double()
+        _chk(self._f("eigenvalue_count")(self.h, a, b, C.byref(c), None))
+        return c.value
+
+    def eigenvalueCountStandardError(self, a, b):
+        e = C.c_double()
+        _chk(self._f("eigenvalue_count")(self.h, a, b, None, C.byref(e)))
+        return e.value
+
+    def energyWindow(self, tau, count):
+        d = C.c_double()
+        _chk(self._f("energy_window")(self.h, tau, count, C.byref(d)))
+        return d.value

@@ -356,6 +356,27 @@ int eigenex_basis_set_filter(eigenex_basis_t b, int degree, const double* mu, do
 /* y = p(A) x with the filter of the state; synchronises; vector references as for eigenex_apply (x is copied into the operator
  * input vector W, y may not be W or x) */
 int eigenex_filter_apply(eigenex_basis_t b, int x_ref, int y_ref);
+/* Chebyshev moments of a Hermitian device operator (kernel polynomial method; Weisse et al., Rev. Mod. Phys. 78 (2006) 275):
+ * mu[k] = <x| T_k((A - center)/halfwidth) |x>, k < n_moments (unnormalised; mu[0] = <x|x>).  ceil((n_moments-1)/2) operator
+ * applications: with the recurrence of eigenex_basis_set_filter (t_0 = x, no accumulator) every application yields two
+ * moments, mu_2k = 2 <t_k,t_k> - mu_0 and mu_2k+1 = 2 <t_k+1,t_k> - mu_1.  x is copied into W as for eigenex_filter_apply.  On
+ * return EIGENEX_VEC_V holds t_d, the last Chebyshev vector formed (d applications).  The dot products stay on the device until
+ * the end: one synchronisation.  Between shards: one neighbour exchange per application and ONE all-reduce of the moments
+ * array at the end.  Independent of, and without effect on, a filter set on the state.  The two forms of the step (operator
+ * kernel's epilogue / streaming kernel, EIGENEX_NO_FUSED_FILTER as for the filter) give the same bits in t_k; their moments are
+ * each reproducible from run to run and differ from each other by rounding (other partial sums).  The first call allocates the
+ * filter's second work vector (and the operator's output where the streaming form runs).
+ * EIGENEX_ERR_ARG: n_moments < 1, mu == NULL, halfwidth <= 0, n_vectors < 1;  EIGENEX_ERR_STATE: the operator is a host callback. */
+int eigenex_kpm_moments(eigenex_basis_t b, int x_ref, int n_moments, double center, double halfwidth, double* mu);
+/* n_vectors runs of the above from +-1 vectors (seed, stream = first_stream + i): mu_each[i*n_moments + k], divided by N; one
+ * synchronisation and one all-reduce for all of them */
+int eigenex_kpm_trace_moments(eigenex_basis_t b, int n_moments, int n_vectors, uint64_t seed, uint64_t first_stream,
+                              double center, double halfwidth, double* mu_each);
+/* x[row] = +1 or -1 (imaginary part 0) from a counter-based hash of (seed, stream, global row): the same vector under every
+ * sharding.  key = mix((mix(seed + G) ^ stream) + G), h = mix((key ^ row) + G) modulo 2^64, -1 where bit 63 of h is set;
+ * G = 0x9E3779B97F4A7C15, mix = the splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
+ * z *= 0x94D049BB133111EB, z ^= z >> 31). */
+int eigenex_vec_random_signs(eigenex_basis_t b, int x_ref, uint64_t seed, uint64_t stream);
 /* h[i] = col(first + i*stride) . w, i < count, then h[count + q] = ortho(q) . w, q < n_ortho_used   (a5 dot half) */
 int eigenex_dots(eigenex_basis_t b, int w_ref, int first, int stride, int count, int n_ortho_used, double* h);
 /* w -= sum_i h[i]*col(first+i*stride) + sum_q h[count+q]*ortho(q); *nrm2 = ||w||^2   (a5 axpy half, a6) */
