@@ -41,6 +41,24 @@ def csr_rowsum_matmul(rowptr, col, val, dtype):
     return matmul
 
 
+def csr_rowsum_matmul_any_rows(rowptr, col, val, dtype):
+    """csr_rowsum_matmul for matrices that may have rows without entries (their result is 0): the same products and the same
+    sum of every non-empty row, np.add.reduceat over the starts of the non-empty rows alone (an empty row's start is the next
+    non-empty row's, so leaving it out cuts the products at the same places)"""
+    rowptr = np.asarray(rowptr, np.int64)
+    v = np.asarray(val).astype(dtype)
+    filled = np.diff(rowptr) > 0
+    starts = rowptr[:-1][filled]
+
+    def matmul(x):
+        out = np.zeros(filled.size, np.result_type(v.dtype, x.dtype))
+        if starts.size:
+            out[filled] = np.add.reduceat(v * x[col], starts)
+        return out
+
+    return matmul
+
+
 def apply_filter(matmul, x, mu, center, halfwidth):
     """p(A) x by the recurrence of eigenex_basis_set_filter, one rounded operation at a time, in the precision of x and matmul:
     a = A t_k - center t_k;  t_1 = (1/h) a,  t_{k+1} = (2/h) a - t_{k-1};  acc_1 = mu0 x + mu1 t_1,  acc_{k+1} = acc_k + mu_{k+1} t_{k+1}."""

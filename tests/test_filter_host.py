@@ -68,6 +68,42 @@ def test_recurrence_in_double_follows_long_double():
         np.testing.assert_allclose(yl.astype(np.float64), dense, rtol=0, atol=1e-12)
 
 
+def test_long_double_matmul_with_empty_rows():
+    """fr.csr_rowsum_matmul_any_rows on a 40-row matrix with empty rows (a run of them, the first and the last row) against the
+    dense long double product: equal where every operation is exact (small integers), else within the two sums' rounding, a row
+    of k products: 2 k eps sum|a||x|; empty rows give 0; without empty rows the bits of fr.csr_rowsum_matmul"""
+    import scipy.sparse as sp
+
+    rng = np.random.RandomState(4)
+    n = 40
+    D = np.where(rng.rand(n, n) < 0.2, rng.standard_normal((n, n)), 0.0)
+    gone = [0, 7, 39] + list(range(16, 24))
+    D[gone, :] = 0.0
+    x = rng.standard_normal(n)
+    eps = np.finfo(np.longdouble).eps
+    for dense, v in ((np.rint(8 * D), np.rint(8 * x)), (D, x)):
+        A = sp.csr_matrix(dense)
+        A.sort_indices()
+        assert np.all(np.diff(A.indptr)[gone] == 0) and A.nnz > n
+        for dtype, xv in ((np.longdouble, v), (np.float64, v), (np.clongdouble, v + 1j * v[::-1])):
+            y = fr.csr_rowsum_matmul_any_rows(A.indptr, A.indices, A.data, dtype)(xv.astype(dtype))
+            assert y.dtype == dtype and np.all(y[gone] == 0)
+            ld = np.clongdouble if np.iscomplexobj(xv) else np.longdouble
+            want = dense.astype(np.longdouble) @ xv.astype(ld)
+            if dense is not D:
+                np.testing.assert_array_equal(y.astype(ld), want)
+            elif dtype != np.float64:
+                k = np.diff(A.indptr)
+                bound = 2 * k * eps * (np.abs(dense).astype(np.longdouble) @ np.abs(xv).astype(np.longdouble)) * (2 if ld is np.clongdouble else 1)
+                assert np.all(np.abs(y - want) <= bound)
+    keep = np.setdiff1d(np.arange(n), gone)
+    B = sp.csr_matrix(D[np.ix_(keep, keep)] + np.eye(keep.size))
+    B.sort_indices()
+    xl = x[keep].astype(np.longdouble)
+    np.testing.assert_array_equal(fr.csr_rowsum_matmul_any_rows(B.indptr, B.indices, B.data, np.longdouble)(xl),
+                                  fr.csr_rowsum_matmul(B.indptr, B.indices, B.data, np.longdouble)(xl))
+
+
 @pytest.mark.parametrize("model", ["chain", "grid"])
 def test_restatement_finds_the_interior_pairs(model):
     """the two CPU results of the design: the 1000-site chain (degree 200) and the 6 x 7 x 8 model (degree 100), m = 60"""
