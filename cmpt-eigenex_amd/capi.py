@@ -99,6 +99,8 @@ SIGNATURES = {
     "eigenex_block_upload": (C.c_int, [_vp, C.c_int64, C.c_int, _lp, C.c_int, _lp, C.c_int64, _lp, _lp, C.POINTER(C.c_void_p), C.POINTER(_vp)]),
     "eigenex_block_upload_z": (C.c_int, [_vp, C.c_int64, C.c_int, _lp, C.c_int, _lp, C.c_int64, _lp, _lp, C.POINTER(C.c_void_p), C.POINTER(_vp)]),
     "eigenex_csr_info": (C.c_int, [_vp, _lp, _lp, _lp, _lp]),
+    "eigenex_spin_upload": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
+    "eigenex_spin_csr": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.c_int64, C.c_int64, _lp, _ip, _dp, _lp]),
     "eigenex_basis_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_create_ex": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_is_complex": (C.c_int, [_vp, C.POINTER(C.c_int)]),
@@ -253,6 +255,39 @@ def lanczos_collectives(call_index: int, last_in_batch: bool, alpha_pending: boo
     _chk(lib().eigenex_lanczos_collectives(call_index, int(last_in_batch), C.byref(pend), interval, n_ortho, ortho_mode, int(alpha_fusion),
                                            int(is_complex), _i(ops), _i(cnt), ops.size, C.byref(n)))
     return [(int(ops[i]), int(cnt[i])) for i in range(n.value)], bool(pend.value)
+
+
+def _spin_model(n_sites, bonds, hz, hx):
+    """ctypes arguments of the spin-1/2 model (include/eigenex_hip.h: eigenex_spin_upload): bonds = [(i, j, Jz, Jxy), ...],
+    hz / hx = n_sites fields or None.  Returns (keep-alive arrays, argument tuple)."""
+    bonds = list(bonds)
+    si = np.ascontiguousarray([b[0] for b in bonds], np.int32)
+    sj = np.ascontiguousarray([b[1] for b in bonds], np.int32)
+    jz = np.ascontiguousarray([b[2] for b in bonds], np.float64)
+    jxy = np.ascontiguousarray([b[3] for b in bonds], np.float64)
+    fields = []
+    for h in (hz, hx):
+        if h is not None:
+            h = np.ascontiguousarray(h, np.float64)
+            if h.shape != (n_sites,):
+                raise ValueError("a site field needs n_sites entries")
+        fields.append(h)
+    keep = (si, sj, jz, jxy, *fields)
+    return keep, (int(n_sites), len(bonds), _i(si), _i(sj), _d(jz), _d(jxy), *[_d(h) if h is not None else None for h in fields])
+
+
+def spin_csr(n_sites: int, bonds, hz=None, hx=None, row_begin: int = 0, n_rows: int | None = None):
+    """eigenex_spin_csr: rows [row_begin, row_begin + n_rows) of the spin-1/2 Hamiltonian as CSR (host code, no GPU needed), in
+    the stored order the matrix-free kernel adds them in.  Returns rowptr (int64, starting at 0), col (int32, global), val."""
+    keep, args = _spin_model(n_sites, bonds, hz, hx)
+    if n_rows is None:
+        n_rows = (1 << n_sites) - row_begin if 2 <= n_sites <= 30 else 0  # (the library refuses any other n_sites)
+    rowptr = np.zeros(max(int(n_rows), 0) + 1, np.int64)
+    nnz = C.c_int64()
+    _chk(lib().eigenex_spin_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), None, None, C.byref(nnz)))
+    col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value, np.float64)
+    _chk(lib().eigenex_spin_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), _i(col), _d(val), C.byref(nnz)))
+    return rowptr, col, val
 
 
 class ShardPlan:
@@ -494,6 +529,17 @@ class Csr:
         return obj
 
     @classmethod
+    def spin_half(cls, ctx: Context, n_sites: int, bonds, hz=None, hx=None):
+        """eigenex_spin_upload: the spin-1/2 Hamiltonian on n_sites sites, applied matrix-free (nothing is stored).
+        bonds = [(i, j, Jz, Jxy), ...]; hz, hx = n_sites fields or None."""
+        keep, args = _spin_model(n_sites, bonds, hz, hx)
+        h = _vp()
+        _chk(lib().eigenex_spin_upload(ctx.h, *args, C.byref(h)))
+        obj = cls(ctx, h)
+        obj.is_complex = False
+        return obj
+
+    @classmethod
     def laplacian3d(cls, ctx: Context, n: int):
         h = _vp()
         _chk(lib().eigenex_csr_laplacian3d(ctx.h, n, C.byref(h)))
@@ -502,7 +548,7 @@ class Csr:
     def layout(self) -> str:
         v = C.c_int()
         _chk(lib().eigenex_csr_layout(self.h, C.byref(v)))
-        return ("csr", "column_blocked", "sorted_tiles", "dense_blocks", "split_tiles")[v.value]
+        return ("csr", "column_blocked", "sorted_tiles", "dense_blocks", "split_tiles", "matrix_free_spin")[v.value]
 
     def encoding(self) -> str:
         """"plain" or "row_codes" (include/eigenex_hip.h: eigenex_csr_encoding)"""

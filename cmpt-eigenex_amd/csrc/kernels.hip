@@ -1410,6 +1410,61 @@ __global__ __launch_bounds__(kBlock) void k_block_spmv(BlockOperatorView op, con
   }
 }
 
+// ---------------------------------------------------------------------------
+// Matrix-free spin-1/2 operator (spin_model.hpp: SpinOperatorView), one row per lane: row s follows from the bits of s, so the
+// kernel streams no operator at all -- the tables are a few hundred bytes that every lane reads at the same index (scalar
+// loads).  The diagonal is ALU work.  A flip reads x[s ^ mask], which keeps the lane's low bits: a mask above bit 5 moves a
+// wave's 512 contiguous bytes to another place as a whole, one inside bits 0..5 permutes the wave's own 512 bytes, bits 6..7
+// stay in the tile.  The flips are taken kSpinBatch at a time with every load issued before the first product is added; a lane
+// whose two spins are equal has no entry there and reads its own element instead (a line the wave has fetched anyway), so the
+// loads are not branched around where half the lanes diverge.  No LDS staging.  Products are rounded, then added, in table
+// order: the sums of the CSR row loop over eigenex_spin_csr's rows.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_spin_spmv(const SpinOperatorView* __restrict__ op, const double* __restrict__ x_ext,
+                                                      const double* __restrict__ scale_ptr, double shift, double* __restrict__ y,
+                                                      double* __restrict__ u_out, int64_t n, int64_t ntiles,
+                                                      double* __restrict__ partials, int pass, const Ctrl* __restrict__ ctrl) {
+  __shared__ double lds4[4];
+  if (ctrl->stopped) return;
+  const double scale = scale_ptr ? *scale_ptr : 1.0;
+  const int ndiag = op->ndiag, nflip = op->nflip;
+  double dot = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + threadIdx.x;
+    if (r < n) {
+      const uint32_t s = (uint32_t)r;
+      double d = 0.0;
+      for (int t = 0; t < ndiag; ++t) {
+        const double k = op->dval[t];
+        d += (__popc(s & op->dmask[t]) & 1) ? -k : k;
+      }
+      const double xr = x_ext[r] * scale;
+      double yr = add_product_nofma(0.0, d, xr);
+      for (int t0 = 0; t0 < nflip; t0 += kSpinBatch) {
+        bool on[kSpinBatch];
+        double xv[kSpinBatch];
+#pragma unroll
+        for (int t = 0; t < kSpinBatch; ++t) {
+          const uint32_t m = op->fmask[t0 + t];
+          on[t] = m != 0 && ((m & (m - 1)) == 0 || (__popc(s & m) & 1));
+          xv[t] = x_ext[on[t] ? s ^ m : s];
+        }
+#pragma unroll
+        for (int t = 0; t < kSpinBatch; ++t)
+          if (on[t]) yr = add_product_nofma(yr, op->fval[t0 + t], xv[t] * scale);
+      }
+      if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
+      y[r] = yr;
+      if (u_out) u_out[r] = xr;
+      dot = (pass & kPassSelfNorm) ? fma(yr, yr, dot) : fma(xr, yr, dot);
+    }
+  }
+  if (partials) {
+    dot = block_sum(dot, lds4);
+    if (threadIdx.x == 0) partials[blockIdx.x] = dot;
+  }
+}
+
 // complex blocks: entries, input and sums are (re, im) pairs; products without contraction and added part by
 // part, exactly like k_spmv_z
 template <int NB, bool STAGED>
@@ -2315,6 +2370,12 @@ void launch_block_spmv_z(hipStream_t s, const BlockOperatorView& op, const doubl
   hipLaunchKernelGGL(k_block_spmv_z, dim3(grid), dim3(kBlock), 0, s, op, reinterpret_cast<const double2*>(x_ext), scale, shift_re,
                      shift_im, reinterpret_cast<double2*>(y), reinterpret_cast<double2*>(u_out), n, (n + kBlock - 1) / kBlock, partials,
                      pstride, pass, ctrl);
+}
+
+void launch_spin_spmv(hipStream_t s, const SpinOperatorView* op, const double* x_ext, const double* scale, double shift, double* y,
+                      double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int pass) {
+  hipLaunchKernelGGL(k_spin_spmv, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, y, u_out, n, (n + kBlock - 1) / kBlock,
+                     partials, pass, ctrl);
 }
 
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,

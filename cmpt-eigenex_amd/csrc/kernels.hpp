@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "row_codes.hpp"
+#include "spin_model.hpp"
 #include "split_layout.hpp"
 #include "spmv_index.hpp"
 
@@ -294,6 +295,12 @@ void launch_block_spmv(hipStream_t s, const BlockOperatorView& op, const double*
 void launch_block_spmv_z(hipStream_t s, const BlockOperatorView& op, const double* x_ext, const double* scale, double shift_re,
                          double shift_im, double* y, double* u_out, int64_t n, double* partials, int pstride, int grid,
                          const Ctrl* ctrl, int pass = 0);
+// Matrix-free spin-1/2 operator (eigenex_spin_upload; spin_model.hpp has the row definition and SpinOperatorView, which lives
+// in device memory): row s is its diagonal entry followed by its flips, products rounded before they are added, in table
+// order -- the rows eigenex_spin_csr writes, so bit-identical to k_spmv on that CSR.
+// same contract as launch_block_spmv (n = 2^n_sites rows, one row per lane, 256-row tiles)
+void launch_spin_spmv(hipStream_t s, const SpinOperatorView* op, const double* x_ext, const double* scale, double shift, double* y,
+                      double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int pass = 0);
 // host-operator path: u_out = x*scale
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,
                   const Ctrl* ctrl);

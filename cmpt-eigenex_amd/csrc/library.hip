@@ -320,6 +320,10 @@ struct CsrShard {
   DeviceBuffer<int64_t> gent, gcol;
   DeviceBuffer<int32_t> cols, grow0, rowgrp;
   int64_t nstripcols = 0;  // entries of cols
+  // matrix-free spin-1/2 operator (eigenex_spin_upload; spin_model.hpp: SpinOperatorView) instead of any stored form: nnz = 0,
+  // no halo, one pass; the table is all there is
+  bool spin = false;
+  DeviceBuffer<SpinOperatorView> spin_view;
   std::vector<Segment> recv, send;
   DeviceBuffer<int32_t> send_idx;  // concatenated local row indices
   DeviceBuffer<double> sendbuf;
@@ -1561,6 +1565,7 @@ double csr_bytes(const CsrShard* m, int es) { return (4.0 + 8.0 * es) * m->nnz +
 double operator_bytes(const CsrShard* m, int es) {
   if (m->rc_rec) return (double)m->rc_bytes * row_code_rows(m->nloc) + 8.0 * m->rc_npal;
   if (m->blocked) return 8.0 * es * m->nnz + 4.0 * m->nstripcols + 4.0 * m->nloc;
+  if (m->spin) return (double)sizeof(SpinOperatorView);
   return csr_bytes(m, es);
 }
 // long rows (16 stored entries per row or more on average): the CSR kernels have a variant for them (kSpmvLongRows) and
@@ -1611,7 +1616,7 @@ void launch_csr_one_pass(hipStream_t st, const BasisShard& s, const OperatorPass
 void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p) {
   const CsrShard* m = s.csr;
   const int es = s.es, grid = s.g_spmv;
-  if (m->tiles_split && !m->split && !m->sorted && !m->blocked && m->passes == 1 && es == 1) {
+  if (m->tiles_split && !m->split && !m->sorted && !m->blocked && !m->spin && m->passes == 1 && es == 1) {
     // (tile lists exist between shards only, the InlineFin / InlineArnoldiBegin hooks on one shard only: none is set here)
     const int g_int = s.g_spmv_int, g_bnd = grid - g_int;
     if (m->n_tile_int > 0 && g_int > 0) launch_csr_one_pass(st, s, p, g_int, p.partials, {m->tile_int, m->n_tile_int});
@@ -1642,6 +1647,10 @@ void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p)
       launch_block_spmv(st, op, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid, p.ctrl, p.pass_flags);
     return;
   }
+  if (m->spin) {
+    launch_spin_spmv(st, m->spin_view, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid, p.ctrl, p.pass_flags);
+    return;
+  }
   if (m->rc_rec || (m->passes == 1 && es == 1)) {
     launch_csr_one_pass(st, s, p, grid, p.partials);
     return;
@@ -1662,7 +1671,7 @@ void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p)
 // Does this shard's operator kernel take a Chebyshev step in its epilogue?  The kernels behind launch_csr_one_pass.
 inline bool filter_in_epilogue(const BasisShard& s) {
   const CsrShard* m = s.csr;
-  return s.es == 1 && !m->split && !m->sorted && !m->blocked && (m->rc_rec || m->passes == 1);
+  return s.es == 1 && !m->split && !m->sorted && !m->blocked && !m->spin && (m->rc_rec || m->passes == 1);
 }
 
 // acc = p(A) x with the state's Chebyshev filter, x = w*scale (the operator input, as for an operator application): `degree`
@@ -1762,7 +1771,7 @@ bool inline_begin_ok(const eigenex_basis_s* b) {
   if (!b->csr || !decides_locally(b) || b->sh.size() != 1) return false;
   static const bool off = std::getenv("EIGENEX_NO_INLINE_FIN") != nullptr;
   const CsrShard& m = b->csr->sh[0];
-  return !off && b->es == 1 && !m.blocked && !m.sorted && (m.split || m.passes == 1);
+  return !off && b->es == 1 && !m.blocked && !m.sorted && !m.spin && (m.split || m.passes == 1);
 }
 
 // The scalar an operator application forms besides v, and where it goes.  Alpha: u.v, all-reduced into hbuf[slot_alpha].
@@ -1911,7 +1920,7 @@ inline bool inlines_fin(const eigenex_basis_s* b) {
   static const bool off = std::getenv("EIGENEX_NO_INLINE_FIN") != nullptr;
   if (off || !decides_locally(b) || !b->csr || b->es != 1 || b->f_degree > 0) return false;  // (a filtered state applies p(A) in many launches)
   const CsrShard& m = b->csr->sh[0];
-  return !m.blocked && !m.sorted && !m.split && m.passes == 1 && (b->ortho_mode == EIGENEX_ORTHO_BATCHED || b->ortho_mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE);
+  return !m.blocked && !m.sorted && !m.split && !m.spin && m.passes == 1 && (b->ortho_mode == EIGENEX_ORTHO_BATCHED || b->ortho_mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE);
 }
 
 // the same passes as the general step, with the hand-overs as hooks: no second-stage launch for the norm or for alpha
@@ -2838,11 +2847,52 @@ int eigenex_block_upload_z(eigenex_context_t c, int64_t n_global, int n_row_sect
   return block_upload_impl(c, n_global, n_row_sectors, row_sizes, n_col_sectors, col_sizes, nblocks, qr, qc, blocks_interleaved, 2, out);
 }
 
+int eigenex_spin_csr(int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz, const double* jxy,
+                     const double* hz_or_null, const double* hx_or_null, int64_t row_begin, int64_t n_rows, int64_t* rowptr, int32_t* col,
+                     double* val, int64_t* nnz) {
+  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null};
+  if (const char* why = spin_model_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_csr: ") + why);
+  if (!rowptr || !nnz || (col == nullptr) != (val == nullptr)) return fail(EIGENEX_ERR_ARG, "eigenex_spin_csr: rowptr and nnz are needed, col and val together or neither");
+  if (row_begin < 0 || n_rows < 0 || row_begin + n_rows > (int64_t(1) << n_sites)) return fail(EIGENEX_ERR_ARG, "eigenex_spin_csr: rows outside 0..2^n_sites");
+  spin_write_rows(a, row_begin, n_rows, rowptr, col, val, nnz);
+  return 0;
+}
+
+int eigenex_spin_upload(eigenex_context_t c, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz,
+                        const double* jxy, const double* hz_or_null, const double* hx_or_null, eigenex_csr_t* out) {
+  if (!c || !out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_upload: NULL argument");
+  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null};
+  if (const char* why = spin_model_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_upload: ") + why);
+  if (c->P != 1)
+    return fail(EIGENEX_ERR_ARG, "eigenex_spin_upload: a matrix-free spin operator needs a context with one shard in total; sharding it takes an "
+                                 "exchange of whole vectors for the bonds on the top bits, which is not built");
+  HIPCHK(hipSetDevice(c->device));
+  std::unique_ptr<eigenex_csr_s> m(new eigenex_csr_s());
+  m->ctx = c;
+  m->n_global = int64_t(1) << n_sites;
+  m->es = 1;
+  m->sh.resize(1);
+  CsrShard& s = m->sh[0];
+  s.gshard = c->local[0];
+  s.spin = true;
+  partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
+  s.nloc = s.re - s.rb;
+  s.npad = pad_rows(s.nloc);
+  SpinOperatorView v;
+  spin_build_view(a, v);
+  HIPCHK(s.spin_view.alloc(1));
+  HIPCHK(hipMemcpyAsync(s.spin_view, &v, sizeof(v), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // v is a stack-lifetime staging buffer
+  *out = m.release();
+  return 0;
+}
+
 int eigenex_csr_layout(eigenex_csr_t m, int* layout) {
   if (!m || !layout) return fail(EIGENEX_ERR_ARG, "eigenex_csr_layout: NULL argument");
   *layout = EIGENEX_LAYOUT_CSR;
   for (auto& s : m->sh) {
     if (s.blocked) *layout = EIGENEX_LAYOUT_DENSE_BLOCKS;
+    else if (s.spin) *layout = EIGENEX_LAYOUT_MATRIX_FREE_SPIN;
     else if (s.split) *layout = EIGENEX_LAYOUT_SPLIT_TILES;
     else if (s.sorted) *layout = EIGENEX_LAYOUT_SORTED_TILES;
     else if (s.passes > 1 && *layout == EIGENEX_LAYOUT_CSR) *layout = EIGENEX_LAYOUT_COLUMN_BLOCKED;
@@ -3053,6 +3103,8 @@ int eigenex_basis_is_complex(eigenex_basis_t b, int* is_complex) {
 int eigenex_basis_create_ex(eigenex_context_t c, eigenex_csr_t csr, int64_t n_global, int capacity, int n_ortho,
                             int is_complex, eigenex_basis_t* out) {
   if (!c || !out || n_global <= 0 || capacity < 1 || n_ortho < 0) return fail(EIGENEX_ERR_ARG, "eigenex_basis_create: bad argument");
+  if (csr && is_complex && !csr->sh.empty() && csr->sh[0].spin)
+    return fail(EIGENEX_ERR_ARG, "a matrix-free spin operator is real: it cannot back a complex state");
   if (csr && (csr->es == 2) != (is_complex != 0)) return fail(EIGENEX_ERR_ARG, "scalar type of the basis and of the CSR operator differ");
   if (csr && (csr->ctx != c || csr->n_global != n_global)) return fail(EIGENEX_ERR_ARG, "csr belongs to another context or has another size");
   if (!csr && c->P != 1) return fail(EIGENEX_ERR_ARG, "a host-callback operator needs a single-shard context");

@@ -255,6 +255,30 @@ int eigenex_block_upload(eigenex_context_t ctx, int64_t n_global, int n_row_sect
 int eigenex_block_upload_z(eigenex_context_t ctx, int64_t n_global, int n_row_sectors, const int64_t* row_sizes,
                            int n_col_sectors, const int64_t* col_sizes, int64_t nblocks, const int64_t* qr,
                            const int64_t* qc, const double* const* blocks_interleaved, eigenex_csr_t* out);
+/* Matrix-free spin-1/2 Hamiltonian on n_sites sites (2..30), full Hilbert space n = 2^n_sites: nothing is stored but a table
+ * of a few hundred bytes, row s is worked out from the bits of s by the kernel.  Basis state s has site i up iff bit i of
+ * s is set, sigma_i(s) = +1 for up, -1 for down.
+ *   H = sum_b [ jz[b] Sz_i Sz_j + (jxy[b]/2)(S+_i S-_j + S-_i S+_j) ] + sum_i hz[i] Sz_i + sum_i hx[i] Sx_i
+ * with bond b = (site_i[b], site_j[b]), 0 <= n_bonds <= 64, site_i[b] != site_j[b] (a pair may appear more than once), hz and
+ * hx n_sites entries each or NULL.  Row s is this list of entries, in this (summation) order:
+ *   1. the diagonal, always stored, column s: d = 0.0; for b ascending d += (sigma_i sigma_j > 0 ? +1 : -1) * (jz[b] * 0.25);
+ *      then for i ascending d += sigma_i * (hz[i] * 0.5) -- plain double additions of sign-flipped constants
+ *   2. for b ascending with jxy[b] != 0 and different spins on the bond: value jxy[b] * 0.5, column s ^ (1<<i_b | 1<<j_b)
+ *   3. for i ascending with hx[i] != 0: value hx[i] * 0.5, column s ^ (1<<i)
+ * Products are rounded before they are added, so eigenex_apply is bit-identical to eigenex_csr_upload of eigenex_spin_csr's rows.
+ * The handle is used like any other operator handle (layout EIGENEX_LAYOUT_MATRIX_FREE_SPIN, real states only).  Errors
+ * (n_sites or n_bonds out of range, a site index out of range, a bond from a site to itself, a coupling or field that is not
+ * finite, a context with more than one shard in total) are returned, with a message in eigenex_last_error.  Sharding a
+ * matrix-free spin operator needs an exchange of whole vectors for bonds on the top bits: not built, the message says so. */
+int eigenex_spin_upload(eigenex_context_t ctx, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                        const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null,
+                        eigenex_csr_t* out);
+/* The rows [row_begin, row_begin + n_rows) of the same model as CSR, in the stored order above: host code, no context, no
+ * GPU.  rowptr[n_rows + 1] starts at 0, col holds global columns, *nnz = rowptr[n_rows].  col == val == NULL: only rowptr
+ * and *nnz are filled.  This function is the definition the matrix-free kernel is held against. */
+int eigenex_spin_csr(int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz,
+                     const double* jxy, const double* hz_or_null, const double* hx_or_null, int64_t row_begin,
+                     int64_t n_rows, int64_t* rowptr, int32_t* col, double* val, int64_t* nnz);
 /* CSR that already lives in device memory of this context's GPU (e.g. tensors of a GPU framework: pass their
  * data pointers): copied device-to-device, never through the host, after a device-side check of the row pointers
  * and column indices.  Unsharded contexts only; rowptr_dev[0] = 0; columns are global = local indices. */
@@ -265,7 +289,7 @@ int eigenex_csr_column_blocks(eigenex_csr_t csr, int* passes);
 /* how the operator is stored on the device.  A layout chosen automatically never changes a result, with one exception:
  * EIGENEX_LAYOUT_SPLIT_TILES adds a row's products in another association (see column_blocks = -3) */
 enum { EIGENEX_LAYOUT_CSR = 0, EIGENEX_LAYOUT_COLUMN_BLOCKED = 1, EIGENEX_LAYOUT_SORTED_TILES = 2, EIGENEX_LAYOUT_DENSE_BLOCKS = 3,
-       EIGENEX_LAYOUT_SPLIT_TILES = 4 };
+       EIGENEX_LAYOUT_SPLIT_TILES = 4, EIGENEX_LAYOUT_MATRIX_FREE_SPIN = 5 /* eigenex_spin_upload: nothing stored */ };
 int eigenex_csr_layout(eigenex_csr_t csr, int* layout);
 /* how the entries of an EIGENEX_LAYOUT_CSR operator are encoded.  EIGENEX_ENCODING_ROW_CODES: a real operator in one pass
  * whose rows use at most 16 column offsets (col - row, halo columns in local numbering) and at most 255 bitwise-distinct
@@ -279,6 +303,7 @@ int eigenex_csr_encoding(eigenex_csr_t csr, int* encoding);
 /* synthetic 7-point Laplacian on an n^3 grid generated on the device (BASELINE configs 2 and 4) */
 int eigenex_csr_laplacian3d(eigenex_context_t ctx, int64_t n, eigenex_csr_t* out);
 int eigenex_csr_destroy(eigenex_csr_t csr);
+/* nnz_local counts STORED entries: 0 for a matrix-free spin operator */
 int eigenex_csr_info(eigenex_csr_t csr, int64_t* n_global, int64_t* n_local, int64_t* nnz_local, int64_t* n_halo_local);
 
 /* ---- Krylov state ------------------------------------------------------ */
