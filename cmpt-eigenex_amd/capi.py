@@ -131,6 +131,7 @@ SIGNATURES = {
     "eigenex_basis_set_alpha_fusion": (C.c_int, [_vp, C.c_int]),
     "eigenex_basis_clone": (C.c_int, [_vp, C.POINTER(_vp)]),
     "eigenex_basis_graph_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "eigenex_basis_repairs": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "eigenex_arnoldi_enqueue": (C.c_int, [_vp, C.c_int]),
     "eigenex_lanczos_restart": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double]),
     "eigenex_arnoldi_restart": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int]),
@@ -626,6 +627,12 @@ class Basis:
         n, t, lim = C.c_int(), C.c_int64(), C.c_int64()
         _chk(lib().eigenex_basis_graph_info(self.h, C.byref(n), C.byref(t), C.byref(lim)))
         return dict(graphs=n.value, nodes=t.value, node_limit=lim.value)
+
+    def repairs(self) -> int:
+        """one-sweep Lanczos steps since the last clear whose pending vector the guard re-orthogonalised with the two-sweep pass"""
+        n = C.c_int()
+        _chk(lib().eigenex_basis_repairs(self.h, C.byref(n)))
+        return n.value
 
     def set_alpha_fusion(self, on: bool):
         _chk(lib().eigenex_basis_set_alpha_fusion(self.h, int(bool(on))))

@@ -474,6 +474,210 @@ __global__ __launch_bounds__(kBlock) void k_reduce(const double* __restrict__ pa
 }
 
 // ---------------------------------------------------------------------------
+// One-sweep Lanczos step (kernels.hpp: SweepStep; lag_terms.hpp has the scheme): the dots of k_dots and the subtraction
+// of k_update over ONE pass of the slab -- 8N(k+4) bytes per step instead of 8N(2k+5).  Same tiles, persistent grid,
+// non-temporal 16-byte column loads, per-wave LDS sums and partials layout as k_dots; four columns in flight beside the
+// four vectors a lane carries (w0, w, u_k, u_{k-1}).  Columns are visited in ascending order, which fixes the bits of u and w.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void lag_apply8(double2 (&u)[4], double2 (&w)[4], double cj, double fj, bool with_w, const double2 (&x)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    u[i].x = fma(-cj, x[i].x, u[i].x);
+    u[i].y = fma(-cj, x[i].y, u[i].y);
+    if (with_w) {
+      w[i].x = fma(-fj, x[i].x, w[i].x);
+      w[i].y = fma(-fj, x[i].y, w[i].y);
+    }
+  }
+}
+
+template <bool FULL, bool CORRECT>
+__device__ __forceinline__ double sweep_tile(const SweepStep& st, double scale, double a, double b, const double* cl, const double* fl,
+                                             double* wave_acc, int64_t base, int64_t n) {
+  const int lane = threadIdx.x & 63;
+  const int k = st.k;
+  const double* ukm1 = st.V + (int64_t)(k - 1) * st.ldv;  // only dereferenced for k > 0
+  double* ukcol = const_cast<double*>(st.V) + (int64_t)k * st.ldv;
+  double2 w0[4], w[4], u[4], um[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t row = base + i * (2 * kBlock);
+    u[i] = w0[i] = w[i] = um[i] = make_double2(0.0, 0.0);
+    if (FULL || row < n) {
+      const double2 t = ld2(st.w + row);
+      u[i] = make_double2(t.x * scale, t.y * scale);  // the operator's product, the same bits as the column it stored
+      if (!CORRECT) {
+        double2 s = ld2(st.v + row);
+        s.x = fma(-a, u[i].x, s.x);
+        s.y = fma(-a, u[i].y, s.y);
+        if (k > 0) {
+          um[i] = ld2(ukm1 + row);
+          s.x = fma(-b, um[i].x, s.x);
+          s.y = fma(-b, um[i].y, s.y);
+        }
+        w0[i] = w[i] = s;
+      }
+    }
+  }
+  // columns [0, nv) stream from HBM; column k-1 is still in registers from the recurrence (not in the closing pass)
+  const int nv = CORRECT ? k : (k > 0 ? k - 1 : 0);
+  int ci = 0;
+  for (; ci + 4 <= nv; ci += 4) {
+    double2 x0[4], x1[4], x2[4], x3[4];
+    load_col<FULL>(x0, st.V + (int64_t)(ci + 0) * st.ldv, base, n);
+    load_col<FULL>(x1, st.V + (int64_t)(ci + 1) * st.ldv, base, n);
+    load_col<FULL>(x2, st.V + (int64_t)(ci + 2) * st.ldv, base, n);
+    load_col<FULL>(x3, st.V + (int64_t)(ci + 3) * st.ldv, base, n);
+    if (!CORRECT) {
+      double r0, r1, r2, r3, im;
+      dotc8<false>(w0, x0, r0, im);
+      dotc8<false>(w0, x1, r1, im);
+      dotc8<false>(w0, x2, r2, im);
+      dotc8<false>(w0, x3, r3, im);
+      const double kr = wave_sum4(r0, r1, r2, r3, lane);
+      if ((lane & 15) == 0) wave_acc[ci + (lane >> 4)] += kr;
+    }
+    lag_apply8(u, w, cl[ci + 0], CORRECT ? 0.0 : fl[ci + 0], !CORRECT, x0);
+    lag_apply8(u, w, cl[ci + 1], CORRECT ? 0.0 : fl[ci + 1], !CORRECT, x1);
+    lag_apply8(u, w, cl[ci + 2], CORRECT ? 0.0 : fl[ci + 2], !CORRECT, x2);
+    lag_apply8(u, w, cl[ci + 3], CORRECT ? 0.0 : fl[ci + 3], !CORRECT, x3);
+  }
+  for (; ci < nv; ++ci) {
+    double2 x0[4];
+    load_col<FULL>(x0, st.V + (int64_t)ci * st.ldv, base, n);
+    if (!CORRECT) {
+      double r0, im;
+      dotc8<false>(w0, x0, r0, im);
+      r0 = wave_sum(r0);
+      if (lane == 0) wave_acc[ci] += r0;
+    }
+    lag_apply8(u, w, cl[ci], CORRECT ? 0.0 : fl[ci], !CORRECT, x0);
+  }
+  double nrm = 0.0;
+  if (!CORRECT) {
+    double r0, r1 = 0.0, im;
+    if (k > 0) {
+      dotc8<false>(w0, um, r1, im);
+      lag_apply8(u, w, cl[k - 1], fl[k - 1], true, um);
+    }
+    dotc8<false>(w0, u, r0, im);  // the corrected tile of column k is in registers
+    const double fk = fl[k];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      w[i].x = fma(-fk, u[i].x, w[i].x);
+      w[i].y = fma(-fk, u[i].y, w[i].y);
+    }
+    r0 = wave_sum(r0);
+    if (k > 0) r1 = wave_sum(r1);
+    if (lane == 0) {
+      wave_acc[k] += r0;
+      if (k > 0) wave_acc[k - 1] += r1;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t row = base + i * (2 * kBlock);
+    if (FULL || row < n) {
+      nt_st2(ukcol + row, u[i]);
+      if (!CORRECT) {
+        nt_st2(st.w + row, w[i]);  // in place: this lane has read these rows of the pending vector above
+        nrm = fma(w[i].x, w[i].x, nrm);
+        nrm = fma(w[i].y, w[i].y, nrm);
+      }
+    }
+  }
+  return nrm;
+}
+
+template <bool CORRECT>
+__global__ __launch_bounds__(kBlock) void k_sweep(SweepStep st, InlineFin fin, int64_t n, int64_t ntiles, double* __restrict__ dpartials,
+                                                  int pstride, double* __restrict__ npartials, const Ctrl* ctrl) {  // no __restrict__: fin.ctrl aliases it
+  extern __shared__ double lds[];  // [4 waves][k+1] sums of d, then c (k+1, c[k] = 0), then f (k+1)
+  __shared__ double lds4[4];
+  if (ctrl->stopped) return;
+  const int k = st.k, nacc = k + 1;
+  double* cl = lds + 4 * nacc;
+  double* fl = cl + nacc;
+  for (int i = threadIdx.x; i < 4 * nacc; i += kBlock) lds[i] = 0.0;
+  for (int i = threadIdx.x; i < nacc; i += kBlock) cl[i] = i < k ? st.lag[kLagC + i] : 0.0;
+  // a' (lanczos.hpp:448, of the raw column): the operator's partials in k_reduce_fin's order, or the slot the host names
+  const double a = fin.partials ? inline_fin_sum(fin, lds4) : *st.a_raw;
+  __syncthreads();
+  const double da = lag_alpha_correction(k, st.beta, cl);
+  if (!CORRECT) {  // the same O(k) arithmetic in every workgroup; workgroup 0 leaves f for k_lag_terms
+    for (int i = threadIdx.x; i < nacc; i += kBlock) {
+      const double fi = lag_f_entry(i, k, st.alpha, st.beta, cl, a, da);
+      fl[i] = fi;
+      if (blockIdx.x == 0) st.lag[st.f_off + i] = fi;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    st.lag[0] = a;
+    if (fin.partials) {
+      fin.out[0] = a;
+      fin_alpha_apply(fin.ctrl, a - da, fin.series, fin.mode == kFinishAlphaFirst);
+    } else if (k > 0) {
+      st.alpha[k] = a - da;  // the series holds the raw a' (k_reduce_fin) or this very value (a batch closed before this step)
+    }
+  }
+  __syncthreads();
+  const double scale = *st.scale;
+  const double b = k > 0 ? st.beta[k - 1] : 0.0;
+  double* wave_acc = lds + (threadIdx.x >> 6) * nacc;
+  double nrm = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t base = tile * kTileRows + 2 * threadIdx.x;
+    if ((tile + 1) * kTileRows <= n)
+      nrm += sweep_tile<true, CORRECT>(st, scale, a, b, cl, fl, wave_acc, base, n);
+    else
+      nrm += sweep_tile<false, CORRECT>(st, scale, a, b, cl, fl, wave_acc, base, n);
+  }
+  if (CORRECT) return;
+  __syncthreads();
+  for (int c = threadIdx.x; c < nacc; c += kBlock)
+    dpartials[(int64_t)c * pstride + blockIdx.x] = (lds[c] + lds[nacc + c]) + (lds[2 * nacc + c] + lds[3 * nacc + c]);
+  nrm = block_sum(nrm, lds4);
+  if (threadIdx.x == 0) npartials[blockIdx.x] = nrm;
+}
+
+// behind the full sweep (kernels.hpp: launch_lag_terms), one workgroup: a wave per coefficient, lanes strided over the partials
+__global__ __launch_bounds__(kBlock) void k_lag_terms(int k, const double* __restrict__ dpartials, int pstride, int nblocks,
+                                                      const double* __restrict__ npartials, double* lag, int f_off, double threshold,
+                                                      Ctrl* ctrl, Ctrl* repair) {
+  __shared__ double lds4[4];
+  __shared__ double wmax[4];
+  if (ctrl->stopped) {
+    if (threadIdx.x == 0) repair->stopped = 1;
+    return;
+  }
+  double s = 0.0;
+  for (int b = threadIdx.x; b < nblocks; b += kBlock) s += npartials[b];
+  const double beta = sqrt(block_sum(s, lds4));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double m = 0.0;
+  for (int c = wave; c <= k; c += 4) {
+    const double* p = dpartials + (int64_t)c * pstride;
+    double d = 0.0;
+    for (int b = lane; b < nblocks; b += 64) d += p[b];
+    d = wave_sum(d);
+    if (lane == 0) {
+      const double cc = lag_next_coefficient(d, lag[f_off + c], beta, threshold);
+      lag[kLagC + c] = cc;
+      m = fmax(m, fabs(cc));
+    }
+  }
+  if (lane == 0) wmax[wave] = m;
+  __syncthreads();
+  const bool armed = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3])) > kLagGuard;
+  if (armed)
+    for (int c = threadIdx.x; c <= k; c += kBlock) lag[kLagC + c] = 0.0;  // the repair leaves nothing pending
+  if (threadIdx.x == 0) {
+    repair->stopped = armed ? 0 : 1;
+    if (armed) ctrl->repairs++;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Chebyshev filter step (kernels.hpp: ChebStep).  cheb_store: one row, in the epilogue of the one-pass real CSR kernels (a =
 // the row sum with the shift -center applied, x = the row's own operator input = t_k).  k_cheb_combine: the same arithmetic
 // behind any other operator kernel, which has stored a as y: a stream over y, t_prev and acc with k_update's tiles and
@@ -2152,6 +2356,23 @@ void launch_update(hipStream_t s, const double* src, double* dst, ThreeTerm tt, 
     hipLaunchKernelGGL((k_update<true, false>), dim3(grid), dim3(kBlock), 0, s, src, dst, tt, cs, h, n, ntiles, partials, ctrl, r);
   else
     hipLaunchKernelGGL((k_update<false, false>), dim3(grid), dim3(kBlock), 0, s, src, dst, tt, cs, h, n, ntiles, partials, ctrl, r);
+}
+
+void launch_sweep(hipStream_t s, const SweepStep& st, const InlineFin* fin, int64_t n, double* dpartials, int pstride, double* npartials,
+                  int grid, const Ctrl* ctrl) {
+  const int64_t ntiles = (n + kTileRows - 1) / kTileRows;
+  const size_t shmem = sizeof(double) * 6 * (size_t)(st.k + 1);
+  const InlineFin nofin{nullptr, 0, 0, 0.0, nullptr, nullptr, nullptr};
+  const InlineFin f = fin ? *fin : nofin;
+  if (st.correct_only)
+    hipLaunchKernelGGL(k_sweep<true>, dim3(grid), dim3(kBlock), shmem, s, st, f, n, ntiles, dpartials, pstride, npartials, ctrl);
+  else
+    hipLaunchKernelGGL(k_sweep<false>, dim3(grid), dim3(kBlock), shmem, s, st, f, n, ntiles, dpartials, pstride, npartials, ctrl);
+}
+
+void launch_lag_terms(hipStream_t s, int k, const double* dpartials, int pstride, int nblocks, const double* npartials, double* lag,
+                      int f_off, double threshold, Ctrl* ctrl, Ctrl* repair) {
+  hipLaunchKernelGGL(k_lag_terms, dim3(1), dim3(kBlock), 0, s, k, dpartials, pstride, nblocks, npartials, lag, f_off, threshold, ctrl, repair);
 }
 
 void launch_spmv_z(hipStream_t s, const int32_t* rowptr, const int32_t* col, const double* val, const double* x_ext,

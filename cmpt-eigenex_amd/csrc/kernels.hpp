@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lag_terms.hpp"
 #include "row_codes.hpp"
 #include "spin_model.hpp"
 #include "split_layout.hpp"
@@ -22,7 +23,7 @@ struct Ctrl {
   int calls_true;  // calls that returned true
   int keep_coupling;  // set by a Krylov-Schur restart (k_arnoldi_restart_fix): the next Arnoldi begin leaves H[k][k-1] as the
                       // restart wrote it instead of storing the residue there, and clears the flag.  0 everywhere else.
-  int pad1;
+  int repairs;     // one-sweep Lanczos steps whose pending vector the guard sent through the two-sweep pass (sticky until the state is cleared)
   double scale;    // 1/beta_k or 1/residue_: factor applied to the operator input
   double residue;  // Arnoldi residue_
 };
@@ -157,6 +158,38 @@ __host__ __device__ inline uint64_t random_sign_key(uint64_t seed, uint64_t stre
   return random_sign_mix((random_sign_mix(seed + G) ^ stream) + G);
 }
 __host__ __device__ inline bool random_sign_bit(uint64_t key, uint64_t row) { return (random_sign_mix((key ^ row) + 0x9E3779B97F4A7C15ull) >> 63) != 0; }
+
+// One-sweep Lanczos step k (lag_terms.hpp has the scheme; kernels.hip: k_sweep).  The pending raw vector in w made column k
+// as u~ = w*scale, the product the operator formed and stored; the sweep recomputes it from w, so that the stored column may
+// already hold its corrected form (the end of a batch) without the sweep seeing a difference.
+//   full:          w0 = (v - a' u~) - beta_{k-1} u_{k-1};  per row tile, j ascending over columns 0..k-1:  d_j = x_j . w0,
+//                  u -= c_j x_j,  w -= f_j x_j;  then d_k = u . w0,  w -= f_k u;  column k = u,  w stored in place of the pending
+//                  vector, partial ||w||^2.  Workgroup 0 records alpha_k = a' - da, a' (lag[0]) and f (lag + f_off).
+//   correct_only:  column k = u~ - sum_j c_j x_j, nothing else is read or written; workgroup 0 records a' and alpha_k.  Closes a batch.
+// a' = the sum of the operator's partials (fin, which then appends alpha_k to the series as k_dots does), or *a_raw.
+constexpr int kLagC = 8;  // lag[kLagC + j] = c_j
+struct SweepStep {
+  int k;
+  const double* V;  // basis slab, column j at V + j*ldv
+  int64_t ldv;
+  const double* v;
+  double* w;
+  const double* scale;
+  const double* a_raw;
+  double* alpha;       // series: alpha[0..k) read, alpha[k] written (fin == nullptr, k > 0)
+  const double* beta;  // series: beta[0..k)
+  double* lag;
+  int f_off;
+  int correct_only;
+};
+// d partials: dpartials[j*pstride + block], j <= k (k_dots' layout); ||w||^2 partials: npartials[block]
+void launch_sweep(hipStream_t s, const SweepStep& st, const InlineFin* fin, int64_t n, double* dpartials, int pstride, double* npartials,
+                  int grid, const Ctrl* ctrl);
+// behind the full sweep of step k, one workgroup: d_j = sum of its partials (fixed order), beta_k^2 = sum of the norm partials in
+// inline_fin_sum's order (the number the operator kernel will take), c_j = (d_j - f_j)/beta_k into lag[kLagC + j], j <= k.
+// max |c| > kLagGuard: c = 0, repair->stopped = 0 (the kernels of the repair pass run), ++ctrl->repairs; else repair->stopped = 1.
+void launch_lag_terms(hipStream_t s, int k, const double* dpartials, int pstride, int nblocks, const double* npartials, double* lag,
+                      int f_off, double threshold, Ctrl* ctrl, Ctrl* repair);
 
 int grid_for_tiles(int64_t ntiles, int blocks_per_cu);
 void set_num_cu(int n);

@@ -368,6 +368,10 @@ struct BasisShard {
   DeviceBuffer<Ctrl> ctrl;
   DeviceBuffer<Ctrl> ctrl_zero;   // always-zero control block for the stand-alone primitives
   DeviceBuffer<Ctrl> ctrl_pass2;  // obeyed by the kernels of an adaptive second Gram-Schmidt pass
+  // one-sweep Lanczos step (lag_terms.hpp): lag[0] = the raw a' of the newest column, lag[kLagC + j] = the coefficients c still
+  // missing from it, lag[kLagC + cap + 2 + j] = f of the running step (only alive between k_sweep and k_lag_terms)
+  DeviceBuffer<double> lag;
+  DeviceBuffer<Ctrl> ctrl_repair;  // obeyed by the kernels of the guard's repair pass; armed by k_lag_terms
   int g_vec = 1, g_spmv = 1, pstride = 1, spmv_flags = 0;  // XCD-contiguous SpMV tiles measured 7 % slower at 512^3
   int g_spmv_int = 0;  // operators launched as interior + boundary tiles: grid (= partial dots) of the interior launch, g_spmv - it of the other
 };
@@ -385,9 +389,13 @@ struct StepCursor {
   bool alpha_pending = false, alpha_pending_first = false, alpha_pending_inline = false;
   bool tail_pending = false;  // Arnoldi, one shard: the end of the last enqueued step (k_arnoldi_tail) is left to the next step's operator kernel
   int tail_ncoef = 0;         //   number of doubles of that step's coefficient vector
+  // one-sweep Lanczos: lag holds the coefficients that belong to the state with lag_nvec vectors (anything else: none are pending);
+  // lag_closed: the last enqueued call closed its batch, so the raw a' of the newest column is in lag[0]
+  int lag_nvec = -1;
+  bool lag_closed = false;
 };
 struct StepGraphKey {
-  int kind, started, h_nvec, ncalls, ortho_mode, nq, flags, g_vec, g_spmv, cap;
+  int kind, started, h_nvec, ncalls, ortho_mode, nq, flags, g_vec, g_spmv, cap, lag;
   int64_t interval;
   double threshold, shift, shift_im;
   const void* slab;
@@ -426,6 +434,7 @@ struct eigenex_basis_s {
   double f_center = 0.0, f_half = 1.0;
   bool f_fused = true;
   bool fuse_alpha = true;  // Lanczos on more than one shard: alpha of the newest vector travels with the next step's dots (lanczos_call)
+  bool t_restarted = false;  // a thick restart has left an arrowhead in T: the one-sweep step needs a tridiagonal T (sweeps_once)
   int hbuf_len() const { return 8 * maxcols + 64; }
   int base_fused() const { return 4 * maxcols + 16; }  // [alpha (2 slots), g (es*ncols), G (es*ncols)]: one all-reduce
   // offsets (in doubles) into hbuf behind the es*maxcols coefficient entries
@@ -463,8 +472,12 @@ int allreduce(eigenex_basis_s* b, int off, int n, DeviceBuffer<double> BasisShar
 }
 
 // the control block a launch obeys: always zero (stand-alone primitives), the state's, the adaptive Gram-Schmidt's second pass
-enum class CtrlBlock { Zero, State, Pass2 };
-inline const Ctrl* pick_ctrl(const BasisShard& s, CtrlBlock cb) { return cb == CtrlBlock::Pass2 ? s.ctrl_pass2 : cb == CtrlBlock::State ? s.ctrl : s.ctrl_zero; }
+// or the repair pass of the one-sweep Lanczos step
+enum class CtrlBlock { Zero, State, Pass2, Repair };
+inline const Ctrl* pick_ctrl(const BasisShard& s, CtrlBlock cb) {
+  return cb == CtrlBlock::Repair ? s.ctrl_repair : cb == CtrlBlock::Pass2 ? s.ctrl_pass2 : cb == CtrlBlock::State ? s.ctrl : s.ctrl_zero;
+}
+inline bool conditional(CtrlBlock cb) { return cb == CtrlBlock::Pass2 || cb == CtrlBlock::Repair; }  // normally returns at once: books no bytes
 
 // fill the halo region of every local shard's operator-input vector `vec` (w, or w2 inside a Chebyshev filter)
 // on_halo_stream: the exchange is issued on the context's second stream, behind ev_w_ready (the operator input is complete) and
@@ -1340,7 +1353,7 @@ int enq_dots(eigenex_basis_s* b, const DotsPass& p) {
     // a column set beyond kDotsMaxAcc accumulators is swept in chunks, each chunk writing its partials at its own
     // offset; every h_c is an independent sum, so chunking does not touch the results
     CHK(for_each_chunk(p.cols, kDotsMaxAcc / b->es, [&](int c0, const Cols& sub) -> int {
-      ProfScope ps(c, EIGENEX_K_DOTS, p.ctrl == CtrlBlock::Pass2 ? 0.0 : 8.0 * s.nd * sub.total() + 8.0 * s.nd);  // a conditional pass books no bytes
+      ProfScope ps(c, EIGENEX_K_DOTS, conditional(p.ctrl) ? 0.0 : 8.0 * s.nd * sub.total() + 8.0 * s.nd);  // a conditional pass books no bytes
       LAUNCH_BEGIN();
       const bool head = c0 == 0;
       launch_dots(c->stream, vec_ptr(s, b->cap, b->nq, p.src), tt, colset(s, sub), s.nd, s.partials + (int64_t)c0 * b->es * s.pstride,
@@ -1393,6 +1406,7 @@ int enq_fused_dots(eigenex_basis_s* b, int k, const Cols& cols) {
 // one shard and no communicator: nothing is all-reduced between a partial sum and the decision taken from it, so the
 // second-stage sum and the decision share one launch (k_reduce_fin)
 inline bool decides_locally(const eigenex_basis_s* b) { return b->ctx->P == 1 && !b->ctx->comm; }
+inline size_t lag_len(int capacity) { return (size_t)kLagC + 2 * ((size_t)capacity + 2); }
 
 // What becomes of ||dst||^2, which the update kernel leaves as per-workgroup partial sums.  Slot: second-stage sum into
 // hbuf[nrm_slot], all-reduced.  Decide (decides_locally, the state's control block): the second-stage sum also takes the step
@@ -1418,7 +1432,7 @@ int enq_update(eigenex_basis_s* b, const UpdatePass& p) {
   for (auto& s : b->sh) {
     const Ctrl* ctl = pick_ctrl(s, p.ctrl);
     {
-      ProfScope ps(c, EIGENEX_K_UPDATE, p.ctrl == CtrlBlock::Pass2 ? 0.0 : 8.0 * s.nd * ncols + 24.0 * s.nd + (p.step ? 32.0 * s.nd : 0.0));
+      ProfScope ps(c, EIGENEX_K_UPDATE, conditional(p.ctrl) ? 0.0 : 8.0 * s.nd * ncols + 24.0 * s.nd + (p.step ? 32.0 * s.nd : 0.0));
       LAUNCH_BEGIN();
       const InlineReduce red{s.partials, s.pstride, s.g_vec, ncols * b->es, s.hbuf + hoff};
       launch_update(c->stream, vec_ptr(s, b->cap, b->nq, p.src), vec_ptr(s, b->cap, b->nq, p.dst), three_term(s, p.step), colset(s, p.cols),
@@ -1946,6 +1960,86 @@ int lanczos_step_inline(eigenex_basis_s* b, int k, const Cols& cols, bool last_i
   return 0;
 }
 
+// Does a Lanczos step of this state sweep the basis once (lanczos_step_one_sweep) instead of twice?  One shard, a device operator
+// of any layout, real data, the batched scheme against every column, nothing to deflate, no filter, a tridiagonal T.  Not a
+// question of EIGENEX_NO_INLINE_FIN, of graphs or of where a batch ends: those change launches, never numbers.
+// EIGENEX_TWO_SWEEPS=1 keeps the two-sweep step everywhere.
+inline bool sweeps_once(const eigenex_basis_s* b) {
+  static const bool off = std::getenv("EIGENEX_TWO_SWEEPS") != nullptr;
+  return !off && decides_locally(b) && b->csr && b->sh.size() == 1 && b->es == 1 && b->ortho_mode == EIGENEX_ORTHO_BATCHED && b->interval == 1 &&
+         b->nq == 0 && b->f_degree == 0 && !b->t_restarted && b->cap + 1 <= kSweepMaxCols;
+}
+
+// Step k in one sweep of the basis (lag_terms.hpp; kernels.hpp: SweepStep): k_sweep, k_lag_terms, the guard's repair pass (the
+// two-sweep pass on the pending vector under a control block of its own, which k_lag_terms arms; its launches return at once
+// otherwise, like the adaptive second pass of an Arnoldi step), the operator.  With inline finalisers alpha' and beta travel as
+// partial sums into their consumer kernels, without them through k_reduce_fin: the same sums in the same order.
+// The last call of a batch corrects the newest column and its alpha too (the closing pass), so that every batch leaves a complete
+// state; the next batch's first sweep recomputes both from the pending vector and the kept a', bit for bit.
+int lanczos_step_one_sweep(eigenex_basis_s* b, int k, bool last_in_batch) {
+  eigenex_context_s* c = b->ctx;
+  hipStream_t st = c->stream;
+  BasisShard& s = b->sh[0];
+  StepCursor& cur = b->cur;
+  const bool inl = inlines_fin(b);
+  const int f_off = kLagC + b->cap + 2;
+  if (cur.lag_nvec != cur.h_nvec) {  // the state did not come from a one-sweep step: nothing is pending
+    HIPCHK(hipMemsetAsync(s.lag + kLagC, 0, sizeof(double) * (b->cap + 2), st));
+    cur.lag_closed = false;
+  }
+  const InlineFin fin_alpha{s.palpha, s.g_spmv, cur.alpha_pending_first ? kFinishAlphaFirst : kFinishAlpha, 0.0, s.alpha, s.ctrl, s.hbuf + b->slot_alpha()};
+  // alpha_0 has no correction and is in the series; a closed batch kept a' in lag[0]; else k_reduce_fin has just left it in its slot
+  const double* a_slot = k == 0 ? s.alpha.get() : cur.lag_closed ? s.lag.get() : s.hbuf + b->slot_alpha();
+  SweepStep sw{k, s.V, s.ldd, s.v, s.w, &s.ctrl->scale, a_slot, s.alpha, s.beta, s.lag, f_off, 0};
+  {
+    ProfScope ps(c, EIGENEX_K_UPDATE, 8.0 * s.nd * (k + 4));
+    LAUNCH_BEGIN();
+    launch_sweep(st, sw, cur.alpha_pending ? &fin_alpha : nullptr, s.nd, s.partials, s.pstride, s.pnorm, s.g_vec, s.ctrl);
+    LAUNCHCHK("k_sweep");
+  }
+  cur.alpha_pending = cur.alpha_pending_inline = false;
+  {
+    ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
+    launch_lag_terms(st, k, s.partials, s.pstride, s.g_vec, s.pnorm, s.lag, f_off, b->threshold, s.ctrl, s.ctrl_repair);
+  }
+  const Cols cols{.count = k + 1};
+  const bool merged_sums = cols.total() <= kInlineReduceMaxCoef;  // k_update forms the repair's second-stage sums itself: one launch less
+  CHK(enq_dots(b, {.src = EIGENEX_VEC_W, .cols = cols, .ctrl = CtrlBlock::Repair, .skip_reduce = merged_sums}));
+  CHK(enq_update(b, {.src = EIGENEX_VEC_W, .dst = EIGENEX_VEC_W, .cols = cols, .ctrl = CtrlBlock::Repair, .norm = NormOut::Partials, .reduce_inline = merged_sums}));
+  if (inl) {
+    const InlineFin fin_norm{s.pnorm, s.g_vec, kFinLanczos, b->threshold, s.beta, s.ctrl, s.hbuf + b->slot_nrm()};
+    CHK(enq_apply(b, {.ucol = k + 1, .out = ApplyOut::AlphaPartials, .fin = &fin_norm}));
+    if (last_in_batch) {
+      ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
+      launch_reduce_fin(st, s.palpha, s.pstride, s.g_spmv, 1, s.hbuf + b->slot_alpha(), s.ctrl, kFinishAlpha, s.alpha, 0.0);
+    } else {
+      cur.alpha_pending = cur.alpha_pending_inline = true;
+      cur.alpha_pending_first = false;
+    }
+  } else {
+    {
+      ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
+      launch_reduce_fin(st, s.pnorm, s.pstride, s.g_vec, 1, s.hbuf + b->slot_nrm(), s.ctrl, kFinLanczos, s.beta, b->threshold);
+    }
+    bool merged = false;
+    CHK(enq_apply(b, {.ucol = k + 1, .out = ApplyOut::Alpha, .decide = kFinishAlpha}, &merged));
+    if (!merged) launch_fin_alpha(st, s.ctrl, s.hbuf + b->slot_alpha(), s.alpha, 0, b->cap);
+  }
+  cur.lag_closed = false;
+  if (last_in_batch) {  // close: column k+1 and alpha_{k+1} corrected, a' kept
+    SweepStep cl = sw;
+    cl.k = k + 1, cl.a_raw = s.hbuf + b->slot_alpha(), cl.correct_only = 1;
+    ProfScope ps(c, EIGENEX_K_UPDATE, 8.0 * s.nd * (k + 3));
+    LAUNCH_BEGIN();
+    launch_sweep(st, cl, nullptr, s.nd, s.partials, s.pstride, s.pnorm, s.g_vec, s.ctrl);
+    LAUNCHCHK("k_sweep (closing)");
+    cur.lag_closed = true;
+  }
+  cur.h_nvec++;
+  cur.lag_nvec = cur.h_nvec;
+  return 0;
+}
+
 // one call of LanczosBase::updateLanczosSteps()  (lanczos.hpp:371-457).
 // Collectives per call between shards: all-reduce of the dots, of ||w||^2, halo exchange, all-reduce of alpha.  With
 // alpha fusion (default) the last one is folded into the next call's first all-reduce; the last call of a batch closes
@@ -1966,6 +2060,7 @@ int lanczos_call(eigenex_basis_s* b, bool last_in_batch) {
     const int k = cur.h_nvec - 1;
     if (cur.h_nvec >= b->cap) return fail(EIGENEX_ERR_STATE, "basis capacity exhausted");
     const Cols cols = lanczos_columns(k, b->interval, b->nq);
+    if (sweeps_once(b)) return lanczos_step_one_sweep(b, k, last_in_batch);
     if (inlines_fin(b) && cols.total() > 0) return lanczos_step_inline(b, k, cols, last_in_batch);
     if (cur.alpha_pending && (cols.total() == 0 || cur.alpha_pending_inline)) CHK(close_pending_alpha(b));  // no dots pass to ride on
     CHK(enq_orthogonalize(b, {.src = EIGENEX_VEC_V, .dst = EIGENEX_VEC_W, .step = k, .cols = cols, .decide = kFinLanczos, .fused_alpha = cur.alpha_pending},
@@ -2127,6 +2222,7 @@ int enqueue_steps(eigenex_basis_s* b, int ncalls, int kind) {
   StepGraphKey key;
   std::memset(&key, 0, sizeof(key));
   key.kind = kind, key.started = b->cur.started ? 1 : 0, key.h_nvec = b->cur.h_nvec, key.ncalls = ncalls, key.ortho_mode = b->ortho_mode;
+  key.lag = (b->cur.lag_nvec == b->cur.h_nvec ? 1 : 0) | (b->cur.lag_closed ? 2 : 0) | (b->t_restarted ? 4 : 0);
   key.nq = b->nq, key.flags = b->sh[0].spmv_flags, key.g_vec = b->sh[0].g_vec, key.g_spmv = b->sh[0].g_spmv, key.cap = b->cap;
   key.interval = b->interval, key.threshold = b->threshold, key.shift = b->shift, key.shift_im = b->shift_im, key.slab = b->sh[0].V;
   for (auto& g : b->graphs)
@@ -2186,6 +2282,19 @@ int sync_ctrl(eigenex_basis_s* b, Ctrl* out) {
   b->cur.h_nvec = out->nvec;
   return 0;
 }
+
+}  // namespace
+
+int eigenex_basis_repairs(eigenex_basis_t b, int* repairs) {
+  if (!b || !repairs) return fail(EIGENEX_ERR_ARG, "NULL argument");
+  HIPCHK(hipSetDevice(b->ctx->device));
+  Ctrl ct;
+  CHK(sync_ctrl(b, &ct));
+  *repairs = ct.repairs;
+  return 0;
+}
+
+namespace {
 
 void fill_state(const Ctrl& ct, eigenex_state_t* st) {
   if (!st) return;
@@ -3172,6 +3281,10 @@ int eigenex_basis_create_ex(eigenex_context_t c, eigenex_csr_t csr, int64_t n_gl
     HIPCHK(hipMemsetAsync(s.ctrl_zero, 0, sizeof(Ctrl), c->stream));
     HIPCHK(s.ctrl_pass2.alloc(1));
     HIPCHK(hipMemsetAsync(s.ctrl_pass2, 0, sizeof(Ctrl), c->stream));
+    HIPCHK(s.ctrl_repair.alloc(1));
+    HIPCHK(hipMemsetAsync(s.ctrl_repair, 0, sizeof(Ctrl), c->stream));
+    HIPCHK(s.lag.alloc(lag_len(capacity)));
+    HIPCHK(hipMemsetAsync(s.lag, 0, sizeof(double) * lag_len(capacity), c->stream));
   }
   for (auto& s : b->sh) CHK(place_work_vector(c, s, capacity));
   if (std::getenv("EIGENEX_DEBUG_POINTERS"))  // allocation placement, for timing investigations
@@ -3202,6 +3315,7 @@ int eigenex_basis_clone(eigenex_basis_t src, eigenex_basis_t* out) {
   b->ortho_mode = src->ortho_mode, b->cur = src->cur, b->fn = src->fn, b->fn_user = src->fn_user;
   b->fuse_alpha = src->fuse_alpha;
   b->h_restarted = src->h_restarted;
+  b->t_restarted = src->t_restarted;
   if (src->f_degree > 0) {
     CHK(eigenex_basis_set_filter(b.get(), src->f_degree, src->f_mu.data(), src->f_center, src->f_half));
     b->f_fused = src->f_fused;
@@ -3222,6 +3336,7 @@ int eigenex_basis_clone(eigenex_basis_t src, eigenex_basis_t* out) {
     HIPCHK(cp(d.H, s.H, sizeof(double) * (size_t)src->ldh * (src->cap + 1) * s.es));
     HIPCHK(cp(d.ctrl, s.ctrl, sizeof(Ctrl)));
     HIPCHK(cp(d.ctrl_pass2, s.ctrl_pass2, sizeof(Ctrl)));
+    HIPCHK(cp(d.lag, s.lag, sizeof(double) * lag_len(src->cap)));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   *out = b.release();
@@ -3256,7 +3371,7 @@ int eigenex_basis_reserve(eigenex_basis_t b, int capacity) {
   const int newmax = capacity + b->nq, newldh = capacity + 2;
   // all or nothing: the new arrays of every shard first, then the copies; the state changes only once all of them succeeded
   struct Grown {
-    DeviceBuffer<double> V, partials, hbuf, alpha, beta, H;
+    DeviceBuffer<double> V, partials, hbuf, alpha, beta, H, lag;
   };
   std::vector<Grown> g(b->sh.size());
   for (size_t i = 0; i < b->sh.size(); ++i) {
@@ -3267,6 +3382,7 @@ int eigenex_basis_reserve(eigenex_basis_t b, int capacity) {
     HIPCHK(g[i].alpha.alloc(capacity + 2));
     HIPCHK(g[i].beta.alloc(capacity + 2));
     HIPCHK(g[i].H.alloc((size_t)newldh * (capacity + 1) * s.es));
+    HIPCHK(g[i].lag.alloc(lag_len(capacity)));
   }
   for (size_t i = 0; i < b->sh.size(); ++i) {
     const BasisShard& s = b->sh[i];
@@ -3280,6 +3396,8 @@ int eigenex_basis_reserve(eigenex_basis_t b, int capacity) {
     HIPCHK(hipMemcpyAsync(n.alpha, s.alpha, sizeof(double) * (oldcap + 2), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(n.beta, s.beta, sizeof(double) * (oldcap + 2), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipMemsetAsync(n.H, 0, sizeof(double) * (size_t)newldh * (capacity + 1) * s.es, c->stream));
+    HIPCHK(hipMemsetAsync(n.lag, 0, sizeof(double) * lag_len(capacity), c->stream));
+    HIPCHK(hipMemcpyAsync(n.lag, s.lag, sizeof(double) * (kLagC + oldcap + 2), hipMemcpyDeviceToDevice, c->stream));  // a' and c; f lives inside a step
     HIPCHK(hipMemcpy2DAsync(n.H, sizeof(double) * newldh * s.es, s.H, sizeof(double) * oldldh * s.es, sizeof(double) * oldldh * s.es,
                             oldcap + 1, hipMemcpyDeviceToDevice, c->stream));
   }
@@ -3287,7 +3405,7 @@ int eigenex_basis_reserve(eigenex_basis_t b, int capacity) {
   for (size_t i = 0; i < b->sh.size(); ++i) {  // moving in frees the old arrays
     BasisShard& s = b->sh[i];
     s.V = std::move(g[i].V), s.partials = std::move(g[i].partials), s.hbuf = std::move(g[i].hbuf);
-    s.alpha = std::move(g[i].alpha), s.beta = std::move(g[i].beta), s.H = std::move(g[i].H);
+    s.alpha = std::move(g[i].alpha), s.beta = std::move(g[i].beta), s.H = std::move(g[i].H), s.lag = std::move(g[i].lag);
   }
   b->cap = capacity;
   b->maxcols = newmax;
@@ -3327,8 +3445,10 @@ int eigenex_basis_clear(eigenex_basis_t b) {
   if (b->h_restarted)
     for (auto& s : b->sh) HIPCHK(hipMemsetAsync(s.H, 0, sizeof(double) * (size_t)b->ldh * (b->cap + 1) * s.es, b->ctx->stream));
   b->h_restarted = false;
+  b->t_restarted = false;
   StepCursor& cur = b->cur;
   cur.started = false, cur.h_nvec = 0, cur.alpha_pending = cur.alpha_pending_inline = false, cur.tail_pending = false;
+  cur.lag_nvec = -1, cur.lag_closed = false;
   return 0;
 }
 
@@ -3709,6 +3829,7 @@ int eigenex_lanczos_restart(eigenex_basis_t b, int nkeep, const double* S, int l
     launch_restart_fix(c->stream, s.ctrl, s.alpha, s.beta, m, nkeep, coupling_last);
   }
   b->cur.h_nvec = nkeep + 1;
+  b->t_restarted = true;
   return 0;
 }
 

@@ -351,6 +351,10 @@ int eigenex_basis_set_alpha_fusion(eigenex_basis_t b, int on);
  * on the calling thread (hipGraphInstantiate recurses over a linear chain: the limit follows the stack that is left, see
  * library.hip).  Batches above the limit run as plain launches. */
 int eigenex_basis_graph_info(eigenex_basis_t b, int* ngraphs, int64_t* nodes_total, int64_t* node_limit);
+/* One-sweep Lanczos steps (one shard, device operator, real data, batched scheme against every column, no deflation vectors, no
+ * filter, no thick restart; EIGENEX_TWO_SWEEPS=1 turns them off): how many steps since the last clear had their pending vector
+ * re-orthogonalised by the two-sweep pass because a lagged coefficient exceeded 2^-27 (close to a breakdown).  Synchronises. */
+int eigenex_basis_repairs(eigenex_basis_t b, int* repairs);
 
 /* host <-> device vectors (rows owned by this context) */
 int eigenex_vec_upload(eigenex_basis_t b, int vec_ref, const double* host);
