@@ -159,9 +159,13 @@ __host__ __device__ inline uint64_t random_sign_key(uint64_t seed, uint64_t stre
 }
 __host__ __device__ inline bool random_sign_bit(uint64_t key, uint64_t row) { return (random_sign_mix((key ^ row) + 0x9E3779B97F4A7C15ull) >> 63) != 0; }
 
-// One-sweep Lanczos step k (lag_terms.hpp has the scheme; kernels.hip: k_sweep).  The pending raw vector in w made column k
-// as u~ = w*scale, the product the operator formed and stored; the sweep recomputes it from w, so that the stored column may
-// already hold its corrected form (the end of a batch) without the sweep seeing a difference.
+// One-sweep Lanczos step k (lag_terms.hpp has the scheme; kernels.hip: k_sweep).  The pending raw vector in w makes column k
+// as u~ = w*scale, the product the operator formed; the sweep recomputes it from w and never reads the column, so that the
+// column may already hold its corrected form (the end of a batch) without the sweep seeing a difference.  The sweep (full or
+// correct_only) is column k's ONLY writer: the operator of a one-sweep step does not store u~ (library.hip: ApplyPass::store_u),
+// and between that operator and the sweep or closing pass that follows it nothing reads column k (the repair pass of step k-1
+// runs over columns 0..k-1, a stopped state never gets the column, a batch ends with the closing pass).  Column 0 of the first
+// call is stored by its operator.
 //   full:          w0 = (v - a' u~) - beta_{k-1} u_{k-1};  per row tile, j ascending over columns 0..k-1:  d_j = x_j . w0,
 //                  u -= c_j x_j,  w -= f_j x_j;  then d_k = u . w0,  w -= f_k u;  column k = u,  w stored in place of the pending
 //                  vector, partial ||w||^2.  Workgroup 0 records alpha_k = a' - da, a' (lag[0]) and f (lag + f_off).

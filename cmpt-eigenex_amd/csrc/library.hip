@@ -1803,6 +1803,10 @@ struct ApplyPass {
   // the operator kernel, which then gets no device scale
   const InlineFin* fin = nullptr;
   const InlineArnoldiBegin* begin = nullptr;  // only when inline_begin_ok
+  // false (device operators): column `ucol` is not stored -- the caller's next pass over the basis forms it again from w*scale
+  // and is its only writer (lanczos_step_one_sweep); every operator kernel tests its u_out.  If an enqueue fails in the middle
+  // of a batch, that pass never runs and the newest column is left unwritten: such a state is in error and has to be cleared
+  bool store_u = true;
 };
 int enq_apply(eigenex_basis_s* b, const ApplyPass& p, bool* fin_merged = nullptr) {
   eigenex_context_s* c = b->ctx;
@@ -1841,9 +1845,9 @@ int enq_apply(eigenex_basis_s* b, const ApplyPass& p, bool* fin_merged = nullptr
     CHK(halo_exchange(b, CtrlBlock::State, overlap));
     for (auto& s : b->sh) {
       {
-        ProfScope ps(c, EIGENEX_K_SPMV, operator_bytes(s.csr, b->es) + 32.0 * s.nd + (want_alpha ? 16.0 * s.nd : 0.0));
+        ProfScope ps(c, EIGENEX_K_SPMV, operator_bytes(s.csr, b->es) + (p.store_u ? 32.0 : 24.0) * s.nd + (want_alpha ? 16.0 * s.nd : 0.0));
         launch_operator(c->stream, s, {.x = s.w, .scale = p.fin ? nullptr : &s.ctrl->scale, .shift = b->shift, .shift_im = b->shift_im, .y = s.v,
-                                       .u_out = s.V + (int64_t)p.ucol * s.ldd, .partials = p.out == ApplyOut::None ? nullptr : stays ? s.palpha : s.partials.get(),
+                                       .u_out = p.store_u ? s.V + (int64_t)p.ucol * s.ldd : nullptr, .partials = p.out == ApplyOut::None ? nullptr : stays ? s.palpha : s.partials.get(),
                                        .ctrl = s.ctrl, .pass_flags = want_norm ? kPassSelfNorm : 0, .fin = p.fin, .begin = p.begin,
                                        .halo_done = overlap ? c->ev_halo_done : nullptr});
       }
@@ -2008,7 +2012,7 @@ int lanczos_step_one_sweep(eigenex_basis_s* b, int k, bool last_in_batch) {
   CHK(enq_update(b, {.src = EIGENEX_VEC_W, .dst = EIGENEX_VEC_W, .cols = cols, .ctrl = CtrlBlock::Repair, .norm = NormOut::Partials, .reduce_inline = merged_sums}));
   if (inl) {
     const InlineFin fin_norm{s.pnorm, s.g_vec, kFinLanczos, b->threshold, s.beta, s.ctrl, s.hbuf + b->slot_nrm()};
-    CHK(enq_apply(b, {.ucol = k + 1, .out = ApplyOut::AlphaPartials, .fin = &fin_norm}));
+    CHK(enq_apply(b, {.ucol = k + 1, .out = ApplyOut::AlphaPartials, .fin = &fin_norm, .store_u = false}));
     if (last_in_batch) {
       ProfScope ps(c, EIGENEX_K_SMALL, 0.0);
       launch_reduce_fin(st, s.palpha, s.pstride, s.g_spmv, 1, s.hbuf + b->slot_alpha(), s.ctrl, kFinishAlpha, s.alpha, 0.0);
@@ -2022,7 +2026,7 @@ int lanczos_step_one_sweep(eigenex_basis_s* b, int k, bool last_in_batch) {
       launch_reduce_fin(st, s.pnorm, s.pstride, s.g_vec, 1, s.hbuf + b->slot_nrm(), s.ctrl, kFinLanczos, s.beta, b->threshold);
     }
     bool merged = false;
-    CHK(enq_apply(b, {.ucol = k + 1, .out = ApplyOut::Alpha, .decide = kFinishAlpha}, &merged));
+    CHK(enq_apply(b, {.ucol = k + 1, .out = ApplyOut::Alpha, .decide = kFinishAlpha, .store_u = false}, &merged));
     if (!merged) launch_fin_alpha(st, s.ctrl, s.hbuf + b->slot_alpha(), s.alpha, 0, b->cap);
   }
   cur.lag_closed = false;
