@@ -101,6 +101,10 @@ SIGNATURES = {
     "eigenex_csr_info": (C.c_int, [_vp, _lp, _lp, _lp, _lp]),
     "eigenex_spin_upload": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
     "eigenex_spin_csr": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.c_int64, C.c_int64, _lp, _ip, _dp, _lp]),
+    "eigenex_spin_sector_dim": (C.c_int, [C.c_int, C.c_int, _lp]),
+    "eigenex_spin_sector_states": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_uint32)]),
+    "eigenex_spin_sector_csr": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.c_int64, C.c_int64, _lp, _ip, _dp, _lp]),
+    "eigenex_spin_sector_upload": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
     "eigenex_basis_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_create_ex": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_is_complex": (C.c_int, [_vp, C.POINTER(C.c_int)]),
@@ -288,6 +292,43 @@ def spin_csr(n_sites: int, bonds, hz=None, hx=None, row_begin: int = 0, n_rows: 
     _chk(lib().eigenex_spin_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), None, None, C.byref(nnz)))
     col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value, np.float64)
     _chk(lib().eigenex_spin_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), _i(col), _d(val), C.byref(nnz)))
+    return rowptr, col, val
+
+
+def spin_sector_dim(n_sites: int, n_up: int) -> int:
+    """eigenex_spin_sector_dim: C(n_sites, n_up), the number of states of n_sites sites (2..32) with n_up sites up"""
+    dim = C.c_int64()
+    _chk(lib().eigenex_spin_sector_dim(int(n_sites), int(n_up), C.byref(dim)))
+    return dim.value
+
+
+def spin_sector_states(n_sites: int, n_up: int, first: int = 0, count: int | None = None):
+    """eigenex_spin_sector_states: the states (uint32, ascending) of ranks first .. first + count - 1 of the sector; x_full[states]
+    = x_sector scatters a sector vector into the full space"""
+    if count is None:
+        count = spin_sector_dim(n_sites, n_up) - first
+    states = np.zeros(max(int(count), 0), np.uint32)
+    _chk(lib().eigenex_spin_sector_states(int(n_sites), int(n_up), int(first), int(count), states.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return states
+
+
+def _sector_args(args, n_up):
+    """the model arguments of _spin_model with n_up behind n_sites"""
+    return (args[0], int(n_up), *args[1:])
+
+
+def spin_sector_csr(n_sites: int, n_up: int, bonds, hz=None, hx=None, row_begin: int = 0, n_rows: int | None = None):
+    """eigenex_spin_sector_csr: rows [row_begin, row_begin + n_rows) (ranks) of the spin-1/2 Hamiltonian in the sector of n_up
+    sites up, as CSR (host code, no GPU needed), in the stored order of spin_csr.  Returns rowptr (int64), col (int32, ranks), val."""
+    keep, args = _spin_model(n_sites, bonds, hz, hx)
+    args = _sector_args(args, n_up)
+    if n_rows is None:
+        n_rows = spin_sector_dim(n_sites, n_up) - row_begin
+    rowptr = np.zeros(max(int(n_rows), 0) + 1, np.int64)
+    nnz = C.c_int64()
+    _chk(lib().eigenex_spin_sector_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), None, None, C.byref(nnz)))
+    col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value, np.float64)
+    _chk(lib().eigenex_spin_sector_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), _i(col), _d(val), C.byref(nnz)))
     return rowptr, col, val
 
 
@@ -541,6 +582,17 @@ class Csr:
         return obj
 
     @classmethod
+    def spin_half_sector(cls, ctx: Context, n_sites: int, n_up: int, bonds, hz=None, hx=None):
+        """eigenex_spin_sector_upload: the same Hamiltonian in the sector of n_up sites up (n_sites up to 32, C(n_sites, n_up)
+        rows), applied matrix-free.  The model must conserve Sz: hx is None or all zeros."""
+        keep, args = _spin_model(n_sites, bonds, hz, hx)
+        h = _vp()
+        _chk(lib().eigenex_spin_sector_upload(ctx.h, *_sector_args(args, n_up), C.byref(h)))
+        obj = cls(ctx, h)
+        obj.is_complex = False
+        return obj
+
+    @classmethod
     def laplacian3d(cls, ctx: Context, n: int):
         h = _vp()
         _chk(lib().eigenex_csr_laplacian3d(ctx.h, n, C.byref(h)))
@@ -549,7 +601,7 @@ class Csr:
     def layout(self) -> str:
         v = C.c_int()
         _chk(lib().eigenex_csr_layout(self.h, C.byref(v)))
-        return ("csr", "column_blocked", "sorted_tiles", "dense_blocks", "split_tiles", "matrix_free_spin")[v.value]
+        return ("csr", "column_blocked", "sorted_tiles", "dense_blocks", "split_tiles", "matrix_free_spin", "matrix_free_spin_sector")[v.value]
 
     def encoding(self) -> str:
         """"plain" or "row_codes" (include/eigenex_hip.h: eigenex_csr_encoding)"""

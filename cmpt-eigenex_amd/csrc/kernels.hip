@@ -1669,6 +1669,80 @@ __global__ __launch_bounds__(kBlock) void k_spin_spmv(const SpinOperatorView* __
   }
 }
 
+// ---------------------------------------------------------------------------
+// The same operator in one sector of fixed magnetisation (spin_sector.hpp: SpinSectorView), one row per lane under the
+// contract of k_spin_spmv.  Row r is the state of rank r among the states with n_up sites up: the lane unranks it from the
+// binomials C(p, k), which the workgroup keeps in LDS (n_sites predicated steps, the same for every lane; k differs between
+// lanes, so the read is a per-lane LDS address).  No per-row state array in memory: the operator is the model table and the two
+// rank tables (at most 2^16 words each: they stay in L2).  The diagonal is k_spin_spmv's.  A flip reads x[rank(s ^ mask)],
+// rank = hi_base[s' >> h] + lo_rank[s' & lo_mask]: two 4-byte gathers, then the 8-byte one.  kSpinBatch flips at a time, all
+// table loads, then all loads of x, then the products; a lane whose two spins are equal keeps s' = s, so it ranks its own state
+// and reads its own element.  Products are rounded, then added, in table order: the sums of the CSR row loop over
+// eigenex_spin_sector_csr's rows.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_spin_sector_spmv(const SpinSectorView* __restrict__ op, const uint32_t* __restrict__ lo_rank,
+                                                             const uint32_t* __restrict__ hi_base, const double* __restrict__ x_ext,
+                                                             const double* __restrict__ scale_ptr, double shift, double* __restrict__ y,
+                                                             double* __restrict__ u_out, int64_t n, int64_t ntiles,
+                                                             double* __restrict__ partials, int pass, const Ctrl* __restrict__ ctrl) {
+  constexpr int kCols = kSectorMaxSites + 1;
+  __shared__ double lds4[4];
+  __shared__ uint32_t binom[kSectorMaxSites * kCols];
+  if (ctrl->stopped) return;
+  for (int i = threadIdx.x; i < kSectorMaxSites * kCols; i += kBlock) binom[i] = op->binom[i / kCols][i % kCols];
+  __syncthreads();
+  const double scale = scale_ptr ? *scale_ptr : 1.0;
+  const int n_sites = op->model.n_sites, ndiag = op->model.ndiag, nflip = op->model.nflip, n_up = op->n_up, h = op->h;
+  const uint32_t lo_mask = op->lo_mask;
+  double dot = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + threadIdx.x;
+    if (r < n) {
+      uint32_t s = 0, left = (uint32_t)r;
+      int k = n_up;
+      for (int p = n_sites - 1; p >= 0; --p) {
+        const uint32_t c = binom[p * kCols + k];
+        const bool up = k > 0 && left >= c;
+        s |= up ? uint32_t(1) << p : 0u;
+        left -= up ? c : 0u;
+        k -= up ? 1 : 0;
+      }
+      double d = 0.0;
+      for (int t = 0; t < ndiag; ++t) {
+        const double kd = op->model.dval[t];
+        d += (__popc(s & op->model.dmask[t]) & 1) ? -kd : kd;
+      }
+      const double xr = x_ext[r] * scale;
+      double yr = add_product_nofma(0.0, d, xr);
+      for (int t0 = 0; t0 < nflip; t0 += kSpinBatch) {
+        bool on[kSpinBatch];
+        uint32_t base[kSpinBatch], low[kSpinBatch];
+        double xv[kSpinBatch];
+#pragma unroll
+        for (int t = 0; t < kSpinBatch; ++t) {
+          const uint32_t m = op->model.fmask[t0 + t];
+          on[t] = __popc(s & m) == 1;  // a bond with different spins; a padding mask (0) never
+          const uint32_t s2 = on[t] ? s ^ m : s;
+          base[t] = hi_base[s2 >> h], low[t] = lo_rank[s2 & lo_mask];
+        }
+#pragma unroll
+        for (int t = 0; t < kSpinBatch; ++t) xv[t] = x_ext[base[t] + low[t]];
+#pragma unroll
+        for (int t = 0; t < kSpinBatch; ++t)
+          if (on[t]) yr = add_product_nofma(yr, op->model.fval[t0 + t], xv[t] * scale);
+      }
+      if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
+      y[r] = yr;
+      if (u_out) u_out[r] = xr;
+      dot = (pass & kPassSelfNorm) ? fma(yr, yr, dot) : fma(xr, yr, dot);
+    }
+  }
+  if (partials) {
+    dot = block_sum(dot, lds4);
+    if (threadIdx.x == 0) partials[blockIdx.x] = dot;
+  }
+}
+
 // complex blocks: entries, input and sums are (re, im) pairs; products without contraction and added part by
 // part, exactly like k_spmv_z
 template <int NB, bool STAGED>
@@ -2597,6 +2671,13 @@ void launch_spin_spmv(hipStream_t s, const SpinOperatorView* op, const double* x
                       double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int pass) {
   hipLaunchKernelGGL(k_spin_spmv, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, y, u_out, n, (n + kBlock - 1) / kBlock,
                      partials, pass, ctrl);
+}
+
+void launch_spin_sector_spmv(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
+                             const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
+                             const Ctrl* ctrl, int pass) {
+  hipLaunchKernelGGL(k_spin_sector_spmv, dim3(grid), dim3(kBlock), 0, s, op, lo_rank, hi_base, x_ext, scale, shift, y, u_out, n,
+                     (n + kBlock - 1) / kBlock, partials, pass, ctrl);
 }
 
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,

@@ -7,6 +7,7 @@
 #include "lag_terms.hpp"
 #include "row_codes.hpp"
 #include "spin_model.hpp"
+#include "spin_sector.hpp"
 #include "split_layout.hpp"
 #include "spmv_index.hpp"
 
@@ -338,6 +339,13 @@ void launch_block_spmv_z(hipStream_t s, const BlockOperatorView& op, const doubl
 // same contract as launch_block_spmv (n = 2^n_sites rows, one row per lane, 256-row tiles)
 void launch_spin_spmv(hipStream_t s, const SpinOperatorView* op, const double* x_ext, const double* scale, double shift, double* y,
                       double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int pass = 0);
+// The same operator in one sector of fixed magnetisation (eigenex_spin_sector_upload; spin_sector.hpp has the row definition,
+// SpinSectorView and the two rank tables, all three in device memory): row r is the state of rank r, unranked by the lane;
+// columns are ranks.  The rows eigenex_spin_sector_csr writes, bit-identical to k_spmv on that CSR.
+// same contract as launch_spin_spmv (n = C(n_sites, n_up) rows)
+void launch_spin_sector_spmv(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
+                             const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
+                             const Ctrl* ctrl, int pass = 0);
 // host-operator path: u_out = x*scale
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,
                   const Ctrl* ctrl);

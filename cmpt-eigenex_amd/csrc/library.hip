@@ -324,6 +324,11 @@ struct CsrShard {
   // no halo, one pass; the table is all there is
   bool spin = false;
   DeviceBuffer<SpinOperatorView> spin_view;
+  // the same in one sector of fixed magnetisation (eigenex_spin_sector_upload; spin_sector.hpp): spin stays true, so every
+  // exclusion of the matrix-free operator holds; sector_view takes the place of spin_view, and the two rank tables come with it
+  DeviceBuffer<SpinSectorView> sector_view;
+  DeviceBuffer<uint32_t> sector_lo, sector_hi;
+  int64_t sector_table_words = 0;  // entries of both tables together
   std::vector<Segment> recv, send;
   DeviceBuffer<int32_t> send_idx;  // concatenated local row indices
   DeviceBuffer<double> sendbuf;
@@ -1579,6 +1584,7 @@ double csr_bytes(const CsrShard* m, int es) { return (4.0 + 8.0 * es) * m->nnz +
 double operator_bytes(const CsrShard* m, int es) {
   if (m->rc_rec) return (double)m->rc_bytes * row_code_rows(m->nloc) + 8.0 * m->rc_npal;
   if (m->blocked) return 8.0 * es * m->nnz + 4.0 * m->nstripcols + 4.0 * m->nloc;
+  if (m->sector_view) return (double)sizeof(SpinSectorView) + 4.0 * m->sector_table_words;
   if (m->spin) return (double)sizeof(SpinOperatorView);
   return csr_bytes(m, es);
 }
@@ -1659,6 +1665,11 @@ void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p)
       launch_block_spmv_z(st, op, p.x, p.scale, p.shift, p.shift_im, p.y, p.u_out, m->nloc, p.partials, s.pstride, grid, p.ctrl, p.pass_flags);
     else
       launch_block_spmv(st, op, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid, p.ctrl, p.pass_flags);
+    return;
+  }
+  if (m->sector_view) {
+    launch_spin_sector_spmv(st, m->sector_view, m->sector_lo, m->sector_hi, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid,
+                            p.ctrl, p.pass_flags);
     return;
   }
   if (m->spin) {
@@ -3000,11 +3011,80 @@ int eigenex_spin_upload(eigenex_context_t c, int n_sites, int n_bonds, const int
   return 0;
 }
 
+int eigenex_spin_sector_dim(int n_sites, int n_up, int64_t* dim) {
+  if (!dim) return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_dim: dim is NULL");
+  if (n_sites < kSpinMinSites || n_sites > kSectorMaxSites) return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_dim: n_sites must be 2..32");
+  if (n_up < 0 || n_up > n_sites) return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_dim: n_up must be 0..n_sites");
+  *dim = spin_sector_dim(n_sites, n_up);
+  return 0;
+}
+
+int eigenex_spin_sector_states(int n_sites, int n_up, int64_t first, int64_t count, uint32_t* states) {
+  int64_t dim = 0;
+  if (eigenex_spin_sector_dim(n_sites, n_up, &dim)) return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_states: n_sites must be 2..32 and n_up 0..n_sites");
+  if (first < 0 || count < 0 || first + count > dim) return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_states: ranks outside 0..dim");
+  if (count > 0 && !states) return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_states: states is NULL");
+  for (int64_t k = 0; k < count; ++k) states[k] = spin_sector_unrank(n_sites, n_up, first + k);
+  return 0;
+}
+
+int eigenex_spin_sector_csr(int n_sites, int n_up, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz,
+                            const double* jxy, const double* hz_or_null, const double* hx_or_null, int64_t row_begin, int64_t n_rows,
+                            int64_t* rowptr, int32_t* col, double* val, int64_t* nnz) {
+  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null};
+  if (const char* why = spin_sector_error(a, n_up)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_sector_csr: ") + why);
+  if (!rowptr || !nnz || (col == nullptr) != (val == nullptr))
+    return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_csr: rowptr and nnz are needed, col and val together or neither");
+  if (row_begin < 0 || n_rows < 0 || row_begin + n_rows > spin_sector_dim(n_sites, n_up))
+    return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_csr: rows outside 0..dim");
+  SpinSectorTables t;
+  spin_sector_build_tables(n_sites, n_up, t);
+  spin_sector_write_rows(a, t, row_begin, n_rows, rowptr, col, val, nnz);
+  return 0;
+}
+
+int eigenex_spin_sector_upload(eigenex_context_t c, int n_sites, int n_up, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                               const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null, eigenex_csr_t* out) {
+  if (!c || !out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_upload: NULL argument");
+  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null};
+  if (const char* why = spin_sector_error(a, n_up)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_sector_upload: ") + why);
+  if (c->P != 1)
+    return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_upload: a matrix-free spin operator needs a context with one shard in total; sharding it takes an "
+                                 "exchange of whole vectors for the bonds on the top bits, which is not built");
+  HIPCHK(hipSetDevice(c->device));
+  std::unique_ptr<eigenex_csr_s> m(new eigenex_csr_s());
+  m->ctx = c;
+  m->n_global = spin_sector_dim(n_sites, n_up);
+  m->es = 1;
+  m->sh.resize(1);
+  CsrShard& s = m->sh[0];
+  s.gshard = c->local[0];
+  s.spin = true;
+  partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
+  s.nloc = s.re - s.rb;
+  s.npad = pad_rows(s.nloc);
+  std::unique_ptr<SpinSectorView> v(new SpinSectorView());  // staging buffers: they live until the synchronise below
+  spin_sector_build_view(a, n_up, *v);
+  SpinSectorTables t;
+  spin_sector_build_tables(n_sites, n_up, t);
+  s.sector_table_words = (int64_t)(t.lo_rank.size() + t.hi_base.size());
+  HIPCHK(s.sector_view.alloc(1));
+  HIPCHK(s.sector_lo.alloc(t.lo_rank.size()));
+  HIPCHK(s.sector_hi.alloc(t.hi_base.size()));
+  HIPCHK(hipMemcpyAsync(s.sector_view, v.get(), sizeof(SpinSectorView), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.sector_lo, t.lo_rank.data(), 4 * t.lo_rank.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.sector_hi, t.hi_base.data(), 4 * t.hi_base.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *out = m.release();
+  return 0;
+}
+
 int eigenex_csr_layout(eigenex_csr_t m, int* layout) {
   if (!m || !layout) return fail(EIGENEX_ERR_ARG, "eigenex_csr_layout: NULL argument");
   *layout = EIGENEX_LAYOUT_CSR;
   for (auto& s : m->sh) {
     if (s.blocked) *layout = EIGENEX_LAYOUT_DENSE_BLOCKS;
+    else if (s.sector_view) *layout = EIGENEX_LAYOUT_MATRIX_FREE_SPIN_SECTOR;
     else if (s.spin) *layout = EIGENEX_LAYOUT_MATRIX_FREE_SPIN;
     else if (s.split) *layout = EIGENEX_LAYOUT_SPLIT_TILES;
     else if (s.sorted) *layout = EIGENEX_LAYOUT_SORTED_TILES;

@@ -37,9 +37,9 @@ struct SpinModelArgs {
   const double *jz, *jxy, *hz, *hx;  // hz, hx: n_sites entries or NULL
 };
 
-// nullptr if the model is valid, else what is wrong with it
-inline const char* spin_model_error(const SpinModelArgs& a) {
-  if (a.n_sites < kSpinMinSites || a.n_sites > kSpinMaxSites) return "n_sites must be 2..30";
+// nullptr if the model is valid, else what is wrong with it.  max_sites: 30 for the full space, 32 for a sector (spin_sector.hpp)
+inline const char* spin_model_error(const SpinModelArgs& a, int max_sites = kSpinMaxSites) {
+  if (a.n_sites < kSpinMinSites || a.n_sites > max_sites) return max_sites == kSpinMaxSites ? "n_sites must be 2..30" : "n_sites must be 2..32";
   if (a.n_bonds < 0 || a.n_bonds > kSpinMaxBonds) return "n_bonds must be 0..64";
   if (a.n_bonds > 0 && (!a.site_i || !a.site_j || !a.jz || !a.jxy)) return "site_i, site_j, jz or jxy is NULL";
   for (int b = 0; b < a.n_bonds; ++b) {

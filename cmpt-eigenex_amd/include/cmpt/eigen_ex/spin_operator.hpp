@@ -8,6 +8,11 @@
 //                              out every row as it goes -- the default choice, and the only one that reaches L = 28..30
 //   toCsr() + CsrOperator      the rows as stored CSR (eigenex_spin_csr: 12 bytes per entry, about L/2 + 1 entries per row)
 // Both add a row's products in the same order (include/eigenex_hip.h has it) and give bit-identical operator applications.
+//
+// A model without a transverse field conserves total Sz, and its levels are found sector by sector: the states with nUp sites
+// up, ascending, C(L, nUp) of them (L up to 32 here).  sectorRows / sectorStates / toSectorCsr describe one sector on the host,
+// device::spinHalfSectorOperator applies it matrix-free (eigenex_spin_sector_upload).  Within a sector the SU(2) multiplets of
+// the full space no longer repeat, so "the lowest k levels" can be asked of a Lanczos solver with one start vector.
 #pragma once
 
 #include <limits>
@@ -70,6 +75,38 @@ class SpinHalfModel {
     return m;
   }
 
+  // the sector of nUp sites up: its dimension C(sites, nUp), its states in ascending order (row r of the sector is state
+  // sectorStates(nUp)[r] of the full space), and rows [row_begin, row_end) of the sector matrix as CSR (columns are ranks)
+  Index sectorRows(int nUp) const {
+    std::int64_t dim = 0;
+    device::check(eigenex_spin_sector_dim(sites_, nUp, &dim), "eigenex_spin_sector_dim");
+    return static_cast<Index>(dim);
+  }
+  std::vector<std::uint32_t> sectorStates(int nUp) const {
+    std::vector<std::uint32_t> s(static_cast<std::size_t>(sectorRows(nUp)), 0u);
+    device::check(eigenex_spin_sector_states(sites_, nUp, 0, static_cast<std::int64_t>(s.size()), s.data()), "eigenex_spin_sector_states");
+    return s;
+  }
+  HostCsr<double> toSectorCsr(int nUp, Index row_begin = 0, Index row_end = -1) const {
+    if (row_end < 0) row_end = sectorRows(nUp);
+    HostCsr<double> m;
+    m.n = sectorRows(nUp);
+    std::vector<std::int64_t> rp(static_cast<std::size_t>(row_end > row_begin ? row_end - row_begin : 0) + 1, 0);
+    std::int64_t nnz = 0;
+    device::check(eigenex_spin_sector_csr(sites_, nUp, bonds(), siteI(), siteJ(), jz(), jxy(), fieldZ(), fieldX(), row_begin,
+                                          row_end - row_begin, rp.data(), nullptr, nullptr, &nnz),
+                  "eigenex_spin_sector_csr");
+    if (nnz > static_cast<std::int64_t>(std::numeric_limits<std::int32_t>::max()))
+      throw LanczosException("SpinHalfModel::toSectorCsr: more than 2^31 - 1 stored entries (use device::spinHalfSectorOperator, or fewer rows)");
+    m.col.assign(static_cast<std::size_t>(nnz), 0);
+    m.val.assign(static_cast<std::size_t>(nnz), 0.0);
+    device::check(eigenex_spin_sector_csr(sites_, nUp, bonds(), siteI(), siteJ(), jz(), jxy(), fieldZ(), fieldX(), row_begin,
+                                          row_end - row_begin, rp.data(), m.col.data(), m.val.data(), &nnz),
+                  "eigenex_spin_sector_csr");
+    m.rowptr.assign(rp.begin(), rp.end());
+    return m;
+  }
+
  private:
   SpinHalfModel& setField(std::vector<double>& h, int site, double value) {
     if (site < 0 || site >= sites_) throw LanczosException("SpinHalfModel: site index out of range");
@@ -90,6 +127,15 @@ inline std::shared_ptr<CsrOperator> spinHalfOperator(std::shared_ptr<Context> ct
   check(eigenex_spin_upload(ctx->handle(), model.sites(), model.bonds(), model.siteI(), model.siteJ(), model.jz(), model.jxy(),
                             model.fieldZ(), model.fieldX(), &h),
         "eigenex_spin_upload");
+  return CsrOperator::adopt(std::move(ctx), h);
+}
+
+// the model in the sector of nUp sites up (sites() up to 32, no transverse field), matrix-free in the same way
+inline std::shared_ptr<CsrOperator> spinHalfSectorOperator(std::shared_ptr<Context> ctx, const SpinHalfModel& model, int nUp) {
+  eigenex_csr_t h = nullptr;
+  check(eigenex_spin_sector_upload(ctx->handle(), model.sites(), nUp, model.bonds(), model.siteI(), model.siteJ(), model.jz(), model.jxy(),
+                                   model.fieldZ(), model.fieldX(), &h),
+        "eigenex_spin_sector_upload");
   return CsrOperator::adopt(std::move(ctx), h);
 }
 

@@ -279,6 +279,29 @@ int eigenex_spin_upload(eigenex_context_t ctx, int n_sites, int n_bonds, const i
 int eigenex_spin_csr(int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz,
                      const double* jxy, const double* hz_or_null, const double* hx_or_null, int64_t row_begin,
                      int64_t n_rows, int64_t* rowptr, int32_t* col, double* val, int64_t* nnz);
+/* The same Hamiltonian in one sector of fixed magnetisation: the states of n_sites sites (2..32) with exactly n_up sites up
+ * (0..n_sites), in ascending numerical order.  Row and column r is the rank of a state in that order, dim = C(n_sites, n_up)
+ * <= C(32, 16) < 2^31.  The model must conserve total Sz: hx is NULL or all zeros (else an error whose message names the
+ * transverse field); every other check is that of eigenex_spin_upload.  Row r is row s = state(r) of the full-space
+ * definition above -- the same entries, values and summation order -- with every column s' replaced by rank(s'): the sector
+ * matrix is the full-space matrix restricted to the sector, bit for bit.
+ *   eigenex_spin_sector_dim     dim
+ *   eigenex_spin_sector_states  the states of ranks first .. first + count - 1 (to scatter a sector vector into the full space)
+ *   eigenex_spin_sector_csr     rows [row_begin, row_begin + n_rows) (ranks) as CSR, arguments as eigenex_spin_csr
+ * are host code: no context, no GPU.
+ *   eigenex_spin_sector_upload  the matrix-free operator (layout EIGENEX_LAYOUT_MATRIX_FREE_SPIN_SECTOR, real states, a context
+ *                               with one shard in total): the kernel unranks r and ranks every flipped state through two
+ *                               tables of at most 2^16 32-bit words each; no row and no state is stored.  eigenex_apply is
+ *                               bit-identical to eigenex_csr_upload of eigenex_spin_sector_csr's rows.  The model is checked
+ *                               before the context is touched. */
+int eigenex_spin_sector_dim(int n_sites, int n_up, int64_t* dim);
+int eigenex_spin_sector_states(int n_sites, int n_up, int64_t first, int64_t count, uint32_t* states);
+int eigenex_spin_sector_csr(int n_sites, int n_up, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz,
+                            const double* jxy, const double* hz_or_null, const double* hx_or_null, int64_t row_begin,
+                            int64_t n_rows, int64_t* rowptr, int32_t* col, double* val, int64_t* nnz);
+int eigenex_spin_sector_upload(eigenex_context_t ctx, int n_sites, int n_up, int n_bonds, const int32_t* site_i,
+                               const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null,
+                               const double* hx_or_null, eigenex_csr_t* out);
 /* CSR that already lives in device memory of this context's GPU (e.g. tensors of a GPU framework: pass their
  * data pointers): copied device-to-device, never through the host, after a device-side check of the row pointers
  * and column indices.  Unsharded contexts only; rowptr_dev[0] = 0; columns are global = local indices. */
@@ -289,7 +312,8 @@ int eigenex_csr_column_blocks(eigenex_csr_t csr, int* passes);
 /* how the operator is stored on the device.  A layout chosen automatically never changes a result, with one exception:
  * EIGENEX_LAYOUT_SPLIT_TILES adds a row's products in another association (see column_blocks = -3) */
 enum { EIGENEX_LAYOUT_CSR = 0, EIGENEX_LAYOUT_COLUMN_BLOCKED = 1, EIGENEX_LAYOUT_SORTED_TILES = 2, EIGENEX_LAYOUT_DENSE_BLOCKS = 3,
-       EIGENEX_LAYOUT_SPLIT_TILES = 4, EIGENEX_LAYOUT_MATRIX_FREE_SPIN = 5 /* eigenex_spin_upload: nothing stored */ };
+       EIGENEX_LAYOUT_SPLIT_TILES = 4, EIGENEX_LAYOUT_MATRIX_FREE_SPIN = 5 /* eigenex_spin_upload: nothing stored */,
+       EIGENEX_LAYOUT_MATRIX_FREE_SPIN_SECTOR = 6 /* eigenex_spin_sector_upload: two rank tables, no rows */ };
 int eigenex_csr_layout(eigenex_csr_t csr, int* layout);
 /* how the entries of an EIGENEX_LAYOUT_CSR operator are encoded.  EIGENEX_ENCODING_ROW_CODES: a real operator in one pass
  * whose rows use at most 16 column offsets (col - row, halo columns in local numbering) and at most 255 bitwise-distinct
