@@ -49,6 +49,7 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _lp = C.POINTER(C.c_int64)
 _vp = C.c_void_p
+_up = C.POINTER(C.c_uint32)
 
 # name -> (restype, argtypes): every symbol include/eigenex_hip.h declares
 SIGNATURES = {
@@ -105,6 +106,9 @@ SIGNATURES = {
     "eigenex_spin_sector_states": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_uint32)]),
     "eigenex_spin_sector_csr": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.c_int64, C.c_int64, _lp, _ip, _dp, _lp]),
     "eigenex_spin_sector_upload": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
+    "eigenex_spin_measure": (C.c_int, [_vp, C.c_int, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
+    "eigenex_spin_measure_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
+    "eigenex_spin_geometry": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "eigenex_basis_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_create_ex": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_is_complex": (C.c_int, [_vp, C.POINTER(C.c_int)]),
@@ -330,6 +334,24 @@ def spin_sector_csr(n_sites: int, n_up: int, bonds, hz=None, hx=None, row_begin:
     col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value, np.float64)
     _chk(lib().eigenex_spin_sector_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), _i(col), _d(val), C.byref(nnz)))
     return rowptr, col, val
+
+
+def _mask_list(masks):
+    """a list of 32-bit site masks as (keep-alive array, count, pointer or None)"""
+    m = np.ascontiguousarray(masks, np.uint32).reshape(-1)
+    return m, int(m.size), (m.ctypes.data_as(_up) if m.size else None)
+
+
+def spin_measure_host(n_sites: int, n_up, x, diag_masks, flip_masks):
+    """eigenex_spin_measure_host: the raw sums (diag, flip, norm2) of the masks over the real vector x, in host code (no GPU).
+    n_up = None: the full space (x has 2^n_sites entries), else the sector of n_up sites up (C(n_sites, n_up) entries)."""
+    x = np.ascontiguousarray(x, np.float64)
+    dm, nd, dp = _mask_list(diag_masks)
+    fm, nf, fp = _mask_list(flip_masks)
+    diag, flip, norm2 = np.zeros(nd), np.zeros(nf), C.c_double()
+    _chk(lib().eigenex_spin_measure_host(int(n_sites), -1 if n_up is None else int(n_up), _d(x), nd, dp, nf, fp, _d(diag) if nd else None,
+                                         _d(flip) if nf else None, C.byref(norm2)))
+    return diag, flip, norm2.value
 
 
 class ShardPlan:
@@ -603,6 +625,12 @@ class Csr:
         _chk(lib().eigenex_csr_layout(self.h, C.byref(v)))
         return ("csr", "column_blocked", "sorted_tiles", "dense_blocks", "split_tiles", "matrix_free_spin", "matrix_free_spin_sector")[v.value]
 
+    def spin_geometry(self):
+        """eigenex_spin_geometry: (n_sites, n_up) of a matrix-free spin operator, n_up = None for the full space"""
+        ns, nu = C.c_int(), C.c_int()
+        _chk(lib().eigenex_spin_geometry(self.h, C.byref(ns), C.byref(nu)))
+        return ns.value, (None if nu.value < 0 else nu.value)
+
     def encoding(self) -> str:
         """"plain" or "row_codes" (include/eigenex_hip.h: eigenex_csr_encoding)"""
         v = C.c_int()
@@ -714,6 +742,15 @@ class Basis:
         d = np.zeros(1, self.dtype)
         _chk(lib().eigenex_apply(self.h, x_ref, y_ref, shift, _d(d.view(np.float64)) if want_dot else None))
         return d[0] if want_dot else None
+
+    def spin_measure(self, x_ref, diag_masks, flip_masks):
+        """eigenex_spin_measure: the raw sums (diag, flip, norm2) of the site masks over the vector x_ref, in one sweep on the
+        device; the operator of this state must be a matrix-free spin operator.  No vector and no coefficient changes."""
+        dm, nd, dp = _mask_list(diag_masks)
+        fm, nf, fp = _mask_list(flip_masks)
+        diag, flip, norm2 = np.zeros(nd), np.zeros(nf), C.c_double()
+        _chk(lib().eigenex_spin_measure(self.h, x_ref, nd, dp, nf, fp, _d(diag) if nd else None, _d(flip) if nf else None, C.byref(norm2)))
+        return diag, flip, norm2.value
 
     def set_filter(self, mu, center=0.0, halfwidth=1.0, degree=None):
         """Chebyshev filter p(A) = sum_k mu[k] T_k((A - center)/halfwidth) for the Lanczos steps and filter_apply; mu = None

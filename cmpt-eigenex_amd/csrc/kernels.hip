@@ -1743,6 +1743,118 @@ __global__ __launch_bounds__(kBlock) void k_spin_sector_spmv(const SpinSectorVie
   }
 }
 
+// ---------------------------------------------------------------------------
+// Spin correlations of one vector (spin_measure.hpp has the definition and SpinMeasureChunk): x streams past once per chunk of
+// kSpinMeasureChunk diagonal and as many flip masks and no vector is written.  One row per lane, 256-row tiles, the operator
+// kernels' persistent grid; the lane has its state as they have it (SECTOR: unranked from the binomials in LDS, else s = r).
+// The chunk is a table that every lane reads at the same index (scalar loads).  A diagonal term is the parity of the mask's down spins and one fma.  The
+// flips go kSpinBatch at a time, all table loads, then all loads of x, then the products; a lane without the entry reads its
+// own element and adds x_s * 0.  The 2 C + 1 sums (norm2, diag, flip) stay in registers across the tile loop -- every register
+// index is a constant after unrolling, a batch is skipped as a whole where the chunk has no term in it -- and leave through
+// block_sum into partials[sum * pstride + workgroup]; k_spin_measure_reduce adds those in k_reduce_fin's order.  No atomics: a
+// result depends on the grid only through the grouping of the partial sums.  ctrl->stopped is not consulted: a measurement is
+// not a Krylov step.
+// ---------------------------------------------------------------------------
+template <bool SECTOR>
+__global__ __launch_bounds__(kBlock) void k_spin_measure(const SpinMeasureChunk* __restrict__ ch, const SpinSectorView* __restrict__ op,
+                                                         const uint32_t* __restrict__ lo_rank, const uint32_t* __restrict__ hi_base,
+                                                         const double* __restrict__ x, int64_t n, int64_t ntiles,
+                                                         double* __restrict__ partials, int pstride) {
+  constexpr int C = kSpinMeasureChunk, kCols = kSectorMaxSites + 1;
+  __shared__ double lds4[4];
+  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * kCols : 1];
+  int n_sites = 0, n_up = 0, h = 0;
+  uint32_t lo_mask = 0;
+  if constexpr (SECTOR) {
+    for (int i = threadIdx.x; i < kSectorMaxSites * kCols; i += kBlock) binom[i] = op->binom[i / kCols][i % kCols];
+    __syncthreads();
+    n_sites = op->model.n_sites, n_up = op->n_up, h = op->h, lo_mask = op->lo_mask;
+  }
+  const int ndiag = ch->ndiag, nflip = ch->nflip;
+  double nrm = 0.0, dg[C], fl[C];
+#pragma unroll
+  for (int t = 0; t < C; ++t) dg[t] = 0.0, fl[t] = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + threadIdx.x;
+    if (r < n) {
+      uint32_t s = (uint32_t)r;
+      if constexpr (SECTOR) {
+        uint32_t left = s;
+        int k = n_up;
+        s = 0;
+        for (int p = n_sites - 1; p >= 0; --p) {
+          const uint32_t c = binom[p * kCols + k];
+          const bool up = k > 0 && left >= c;
+          s |= up ? uint32_t(1) << p : 0u;
+          left -= up ? c : 0u;
+          k -= up ? 1 : 0;
+        }
+      }
+      const double xs = x[r];
+      nrm = fma(xs, xs, nrm);
+#pragma unroll
+      for (int t0 = 0; t0 < C; t0 += kSpinBatch)
+        if (t0 < ndiag) {
+#pragma unroll
+          for (int t = 0; t < kSpinBatch; ++t) dg[t0 + t] = fma((__popc(~s & ch->dmask[t0 + t]) & 1) ? -xs : xs, xs, dg[t0 + t]);
+        }
+#pragma unroll
+      for (int t0 = 0; t0 < C; t0 += kSpinBatch)
+        if (t0 < nflip) {
+          bool on[kSpinBatch];
+          double xv[kSpinBatch];
+          if constexpr (SECTOR) {
+            uint32_t base[kSpinBatch], low[kSpinBatch];
+#pragma unroll
+            for (int t = 0; t < kSpinBatch; ++t) {
+              const uint32_t m = ch->fmask[t0 + t];
+              on[t] = __popc(s & m) == 1;  // a pair with different spins; a padding mask (0) never
+              const uint32_t s2 = on[t] ? s ^ m : s;
+              base[t] = hi_base[s2 >> h], low[t] = lo_rank[s2 & lo_mask];
+            }
+#pragma unroll
+            for (int t = 0; t < kSpinBatch; ++t) xv[t] = x[base[t] + low[t]];
+          } else {
+#pragma unroll
+            for (int t = 0; t < kSpinBatch; ++t) {
+              const uint32_t m = ch->fmask[t0 + t];
+              on[t] = __popc(m) == 1 || __popc(s & m) == 1;  // one site: every row; a pair: different spins; padding (0): never
+              xv[t] = x[on[t] ? s ^ m : s];
+            }
+          }
+#pragma unroll
+          for (int t = 0; t < kSpinBatch; ++t) fl[t0 + t] = fma(xs, on[t] ? xv[t] : 0.0, fl[t0 + t]);
+        }
+    }
+  }
+  const auto put = [&](int a, double mine) {  // sum a of this workgroup: 0 norm2, 1 + t diag, 1 + C + t flip
+    const double v = block_sum(mine, lds4);
+    if (threadIdx.x == 0) partials[(int64_t)a * pstride + blockIdx.x] = v;
+  };
+  put(0, nrm);
+#pragma unroll
+  for (int t = 0; t < C; ++t) put(1 + t, dg[t]);
+#pragma unroll
+  for (int t = 0; t < C; ++t) put(1 + C + t, fl[t]);
+}
+
+// Second stage of k_spin_measure, one workgroup per sum (0: norm2, 1..C: diag, C+1..2C: flip), the partials of the nblocks
+// workgroups added in k_reduce_fin's order.  A sum beyond the chunk's live terms has no destination and is dropped.
+__global__ __launch_bounds__(kBlock) void k_spin_measure_reduce(const double* __restrict__ partials, int pstride, int nblocks, int ndiag,
+                                                                int nflip, double* __restrict__ diag_out, double* __restrict__ flip_out,
+                                                                double* __restrict__ norm_out) {
+  constexpr int C = kSpinMeasureChunk;
+  __shared__ double lds4[4];
+  const int a = blockIdx.x;
+  double* dst = a == 0 ? norm_out : (a <= C ? (a - 1 < ndiag ? diag_out + (a - 1) : nullptr) : (a - 1 - C < nflip ? flip_out + (a - 1 - C) : nullptr));
+  if (!dst) return;  // the same for the whole workgroup
+  const double* p = partials + (int64_t)a * pstride;
+  double s = 0.0;
+  for (int b = threadIdx.x; b < nblocks; b += kBlock) s += p[b];
+  s = block_sum(s, lds4);
+  if (threadIdx.x == 0) *dst = s;
+}
+
 // complex blocks: entries, input and sums are (re, im) pairs; products without contraction and added part by
 // part, exactly like k_spmv_z
 template <int NB, bool STAGED>
@@ -2678,6 +2790,21 @@ void launch_spin_sector_spmv(hipStream_t s, const SpinSectorView* op, const uint
                              const Ctrl* ctrl, int pass) {
   hipLaunchKernelGGL(k_spin_sector_spmv, dim3(grid), dim3(kBlock), 0, s, op, lo_rank, hi_base, x_ext, scale, shift, y, u_out, n,
                      (n + kBlock - 1) / kBlock, partials, pass, ctrl);
+}
+
+void launch_spin_measure(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* sector, const uint32_t* lo_rank,
+                         const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid) {
+  const int64_t ntiles = (n + kBlock - 1) / kBlock;
+  if (sector)
+    hipLaunchKernelGGL(k_spin_measure<true>, dim3(grid), dim3(kBlock), 0, s, chunk, sector, lo_rank, hi_base, x, n, ntiles, partials, pstride);
+  else
+    hipLaunchKernelGGL(k_spin_measure<false>, dim3(grid), dim3(kBlock), 0, s, chunk, sector, lo_rank, hi_base, x, n, ntiles, partials, pstride);
+}
+
+void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstride, int nblocks, int ndiag, int nflip, double* diag_out,
+                                double* flip_out, double* norm_out) {
+  hipLaunchKernelGGL(k_spin_measure_reduce, dim3(2 * kSpinMeasureChunk + 1), dim3(kBlock), 0, s, partials, pstride, nblocks, ndiag, nflip,
+                     diag_out, flip_out, norm_out);
 }
 
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,

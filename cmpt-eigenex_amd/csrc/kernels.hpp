@@ -6,6 +6,7 @@
 
 #include "lag_terms.hpp"
 #include "row_codes.hpp"
+#include "spin_measure.hpp"
 #include "spin_model.hpp"
 #include "spin_sector.hpp"
 #include "split_layout.hpp"
@@ -346,6 +347,17 @@ void launch_spin_spmv(hipStream_t s, const SpinOperatorView* op, const double* x
 void launch_spin_sector_spmv(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
                              const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
                              const Ctrl* ctrl, int pass = 0);
+// Spin correlations of the vector x over the rows of a matrix-free spin operator (eigenex_spin_measure; spin_measure.hpp has the
+// definition): one chunk of terms per launch (device memory), sector = nullptr for the full space (n = 2^n_sites rows, the rank
+// tables unused), else the operator's view and tables (n = C(n_sites, n_up) rows).  x is only read; the grid's partial sums go to
+// partials[sum * pstride + workgroup], sum = 0 (norm2), 1 + t (diag), 1 + kSpinMeasureChunk + t (flip): (2 * kSpinMeasureChunk + 1)
+// * pstride doubles, pstride >= grid.  No control block: it always runs.
+void launch_spin_measure(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* sector, const uint32_t* lo_rank,
+                         const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid);
+// its second stage: the partials of nblocks workgroups added in a fixed order, the chunk's ndiag and nflip live sums stored to
+// diag_out[t] and flip_out[t], norm2 to *norm_out unless that is NULL
+void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstride, int nblocks, int ndiag, int nflip, double* diag_out,
+                                double* flip_out, double* norm_out);
 // host-operator path: u_out = x*scale
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,
                   const Ctrl* ctrl);

@@ -329,6 +329,7 @@ struct CsrShard {
   DeviceBuffer<SpinSectorView> sector_view;
   DeviceBuffer<uint32_t> sector_lo, sector_hi;
   int64_t sector_table_words = 0;  // entries of both tables together
+  int spin_sites = 0, spin_n_up = -1;  // the geometry of either form, for eigenex_spin_measure (n_up = -1: the full space)
   std::vector<Segment> recv, send;
   DeviceBuffer<int32_t> send_idx;  // concatenated local row indices
   DeviceBuffer<double> sendbuf;
@@ -2999,6 +3000,7 @@ int eigenex_spin_upload(eigenex_context_t c, int n_sites, int n_bonds, const int
   CsrShard& s = m->sh[0];
   s.gshard = c->local[0];
   s.spin = true;
+  s.spin_sites = n_sites;
   partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
   s.nloc = s.re - s.rb;
   s.npad = pad_rows(s.nloc);
@@ -3060,6 +3062,7 @@ int eigenex_spin_sector_upload(eigenex_context_t c, int n_sites, int n_up, int n
   CsrShard& s = m->sh[0];
   s.gshard = c->local[0];
   s.spin = true;
+  s.spin_sites = n_sites, s.spin_n_up = n_up;
   partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
   s.nloc = s.re - s.rb;
   s.npad = pad_rows(s.nloc);
@@ -3076,6 +3079,66 @@ int eigenex_spin_sector_upload(eigenex_context_t c, int n_sites, int n_up, int n
   HIPCHK(hipMemcpyAsync(s.sector_hi, t.hi_base.data(), 4 * t.hi_base.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   *out = m.release();
+  return 0;
+}
+
+int eigenex_spin_geometry(eigenex_csr_t m, int* n_sites, int* n_up) {
+  if (!m) return fail(EIGENEX_ERR_ARG, "eigenex_spin_geometry: NULL argument");
+  if (m->sh.empty() || !m->sh[0].spin) return fail(EIGENEX_ERR_STATE, "eigenex_spin_geometry: the operator is not a matrix-free spin operator");
+  if (n_sites) *n_sites = m->sh[0].spin_sites;
+  if (n_up) *n_up = m->sh[0].spin_n_up;
+  return 0;
+}
+
+int eigenex_spin_measure_host(int n_sites, int n_up, const double* x, int n_diag, const uint32_t* diag_masks, int n_flip,
+                              const uint32_t* flip_masks, double* diag_out, double* flip_out, double* norm2) {
+  const SpinMeasureArgs a{n_sites, n_up, n_diag, diag_masks, n_flip, flip_masks};
+  if (const char* why = spin_measure_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_measure_host: ") + why);
+  if (!x) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure_host: x is NULL");
+  if ((n_diag > 0 && !diag_out) || (n_flip > 0 && !flip_out)) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure_host: an output list is NULL but its count is not zero");
+  spin_measure_host(a, x, diag_out, flip_out, norm2);
+  return 0;
+}
+
+int eigenex_spin_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks,
+                         double* diag_out, double* flip_out, double* norm2) {
+  if (!b) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure: basis is NULL");
+  if (!b->csr || b->sh.size() != 1 || !b->sh[0].csr || !b->sh[0].csr->spin)
+    return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_measure: the operator of this state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
+                                          : "eigenex_spin_measure: the state has no device operator (a host callback knows no sites)");
+  BasisShard& s = b->sh[0];
+  const CsrShard* m = s.csr;
+  const SpinMeasureArgs a{m->spin_sites, m->spin_n_up, n_diag, diag_masks, n_flip, flip_masks};
+  if (const char* why = spin_measure_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_measure: ") + why);
+  if ((n_diag > 0 && !diag_out) || (n_flip > 0 && !flip_out)) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure: an output list is NULL but its count is not zero");
+  const double* x = vec_ptr(s, b->cap, b->nq, x_ref);
+  if (!x) return fail(EIGENEX_ERR_ARG, "bad vector reference");
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  // scratch of this call alone: the chunk table, the grid's partial sums of one chunk (reused from chunk to chunk: the launches
+  // are ordered on the stream) and the results [norm2, diag, flip].  The state's own partials may hold a pending alpha.
+  std::vector<SpinMeasureChunk> chunks;
+  spin_measure_build_chunks(a, chunks);
+  const int grid = s.g_spmv, nsums = 2 * kSpinMeasureChunk + 1;
+  DeviceBuffer<SpinMeasureChunk> d_chunks;
+  DeviceBuffer<double> d_part, d_out;
+  std::vector<double> out((size_t)(1 + n_diag + n_flip), 0.0);
+  HIPCHK(d_chunks.alloc(chunks.size()));
+  HIPCHK(d_part.alloc((size_t)nsums * grid));
+  HIPCHK(d_out.alloc(out.size()));
+  HIPCHK(hipMemcpyAsync(d_chunks, chunks.data(), sizeof(SpinMeasureChunk) * chunks.size(), hipMemcpyHostToDevice, c->stream));
+  for (size_t k = 0; k < chunks.size(); ++k) {
+    const size_t first = k * kSpinMeasureChunk;  // a list that ends before `first` has no live sum in this chunk
+    const size_t dfirst = std::min(first, (size_t)n_diag), ffirst = std::min(first, (size_t)n_flip);
+    launch_spin_measure(c->stream, d_chunks + k, m->sector_view, m->sector_lo, m->sector_hi, x, s.nloc, d_part, grid, grid);
+    launch_spin_measure_reduce(c->stream, d_part, grid, grid, chunks[k].ndiag, chunks[k].nflip, d_out + 1 + dfirst, d_out + 1 + n_diag + ffirst,
+                               k == 0 ? d_out.get() : nullptr);
+  }
+  HIPCHK(hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the staging buffers and the scratch live until here
+  if (norm2) *norm2 = out[0];
+  for (int t = 0; t < n_diag; ++t) diag_out[t] = out[(size_t)(1 + t)];
+  for (int t = 0; t < n_flip; ++t) flip_out[t] = out[(size_t)(1 + n_diag + t)];
   return 0;
 }
 

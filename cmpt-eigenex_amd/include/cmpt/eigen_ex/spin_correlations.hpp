@@ -1,0 +1,142 @@
+// Spin correlations of a state of a matrix-free spin-1/2 operator (spin_operator.hpp), measured on the device in one call.
+//
+// NOT part of the reference.  For a real vector v over the rows of device::spinHalfOperator (full space) or
+// device::spinHalfSectorOperator (nUp sites up), compute() measures every site and every pair i < j at once
+// (eigenex_spin_measure: v streams past once per 16 terms, nothing is written but the sums) and keeps
+//   sz(i)      = <Sz_i>                          sx(i)     = <Sx_i>   (zero in a sector, without any gather)
+//   szsz(i, j) = <Sz_i Sz_j>                     sxy(i, j) = <Sx_i Sx_j + Sy_i Sy_j>
+//   dot(i, j)  = <S_i . S_j> = szsz + sxy        (i = j: 1/4, 1/2 and 3/4)
+// all normalised by <v|v>.  From these follow
+//   totalSpinSquared()   = sum_ij <S_i . S_j> = S(S + 1) of an eigenstate of an SU(2)-symmetric model: which multiplet a level of
+//                          a sector belongs to
+//   structureFactorZ(q)  = (1/L) sum_ij cos(q (i - j)) <Sz_i Sz_j>, the site index taken as position
+// The vector is a host vector (e.g. a column of a solver's eigenvectors()) and is uploaded by compute().
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "lanczos.hpp"
+#include "spin_operator.hpp"
+
+namespace cmpt {
+namespace EigenEx {
+
+class SpinCorrelationSolver {
+ public:
+  using Index = EigenEx::Index;
+  using VectorType = DenseVector<double>;
+
+  static std::string headERROR() { return std::string("ERROR     "); }
+  static std::string headINFO() { return std::string("INFO      "); }
+
+  SpinCorrelationSolver& setDeviceOperator(const std::shared_ptr<device::CsrOperator>& op) {
+    op_ = op;
+    height_ = op ? static_cast<Index>(op->rows()) : 0;
+    return *this;
+  }
+  SpinCorrelationSolver& setState(const VectorType& v) {
+    state_ = v;
+    return *this;
+  }
+  Index matrixHeight() const { return height_; }
+  int sites() const { return sites_; }
+  int sitesUp() const { return nUp_; }  // -1: the full space
+  double normSquared() const { return norm2_; }
+
+  Index compute() {
+    log_.clear();
+    log_.push_back(headINFO() + "SpinCorrelationSolver::compute(...) was called");
+    info_ = Success;
+    sites_ = 0, nUp_ = -1, norm2_ = 0.0;
+    sz_.clear(), sx_.clear(), zz_.clear(), xy_.clear();
+    if (!op_ || height_ <= 0 || eigenex_spin_geometry(op_->handle(), &sites_, &nUp_) != 0) {
+      sites_ = 0;
+      return invalid_("invalid input: a matrix-free spin operator (device::spinHalfOperator, device::spinHalfSectorOperator) is required");
+    }
+    if (static_cast<Index>(state_.size()) != height_) return invalid_("invalid input: the state must have one entry per row of the operator");
+    const std::size_t L = static_cast<std::size_t>(sites_);
+    std::vector<std::uint32_t> diag, flip;
+    for (std::size_t i = 0; i < L; ++i) diag.push_back(std::uint32_t(1) << i);
+    for (std::size_t i = 0; i < L; ++i)
+      for (std::size_t j = i + 1; j < L; ++j) diag.push_back((std::uint32_t(1) << i) | (std::uint32_t(1) << j));
+    flip.assign(diag.begin() + static_cast<std::ptrdiff_t>(L), diag.end());
+    if (nUp_ < 0) flip.insert(flip.end(), diag.begin(), diag.begin() + static_cast<std::ptrdiff_t>(L));  // <Sx_i>: the full space only
+    if (!dev_.alive() || devOp_ != op_.get()) {
+      dev_.create(op_->context(), op_, height_, 1, 0, false);
+      devOp_ = op_.get();
+    }
+    dev_.upload(EIGENEX_VEC_COL(0), state_);
+    std::vector<double> d(diag.size(), 0.0), f(flip.size(), 0.0);
+    device::check(eigenex_spin_measure(dev_.handle(), EIGENEX_VEC_COL(0), static_cast<int>(diag.size()), diag.data(), static_cast<int>(flip.size()),
+                                       flip.data(), d.data(), f.data(), &norm2_),
+                  "eigenex_spin_measure");
+    if (!(norm2_ > 0.0) || !std::isfinite(norm2_)) return invalid_("invalid input: the state is zero (or not finite)");
+    const std::size_t npairs = L * (L - 1) / 2;
+    sz_.assign(L, 0.0), sx_.assign(L, 0.0);
+    zz_.assign(L * L, 0.0), xy_.assign(L * L, 0.0);
+    for (std::size_t i = 0; i < L; ++i) {
+      sz_[i] = d[i] / (2.0 * norm2_);
+      if (nUp_ < 0) sx_[i] = f[npairs + i] / (2.0 * norm2_);
+      zz_[i * L + i] = 0.25, xy_[i * L + i] = 0.5;
+    }
+    std::size_t k = 0;
+    for (std::size_t i = 0; i < L; ++i)
+      for (std::size_t j = i + 1; j < L; ++j, ++k) {
+        zz_[i * L + j] = zz_[j * L + i] = d[L + k] / (4.0 * norm2_);
+        xy_[i * L + j] = xy_[j * L + i] = f[k] / (2.0 * norm2_);
+      }
+    log_.push_back(headINFO() + "sites: " + std::to_string(sites_) + (nUp_ < 0 ? std::string(", full space") : ", sites up: " + std::to_string(nUp_)) +
+                   ", terms measured: " + std::to_string(diag.size() + flip.size()));
+    return 0;
+  }
+
+  // ---- results (after a successful compute(); a site outside 0..sites()-1 throws) ----
+  double sz(int i) const { return sz_[site_(i)]; }
+  double sx(int i) const { return sx_[site_(i)]; }
+  double szsz(int i, int j) const { return zz_[site_(i) * static_cast<std::size_t>(sites_) + site_(j)]; }
+  double sxy(int i, int j) const { return xy_[site_(i) * static_cast<std::size_t>(sites_) + site_(j)]; }
+  double dot(int i, int j) const { return szsz(i, j) + sxy(i, j); }
+  double totalSpinSquared() const {
+    double s = 0.0;
+    for (int i = 0; i < sites_ && !zz_.empty(); ++i)
+      for (int j = 0; j < sites_; ++j) s += dot(i, j);
+    return s;
+  }
+  double structureFactorZ(double q) const {
+    double s = 0.0;
+    for (int i = 0; i < sites_ && !zz_.empty(); ++i)
+      for (int j = 0; j < sites_; ++j) s += std::cos(q * static_cast<double>(i - j)) * szsz(i, j);
+    return sites_ > 0 ? s / static_cast<double>(sites_) : 0.0;
+  }
+  ComputationInfo info() const { return info_; }
+  const std::vector<std::string>& log() const { return log_; }
+
+ private:
+  Index invalid_(const std::string& what) {
+    log_.push_back(headERROR() + what);
+    info_ = InvalidInput;
+    sz_.clear(), sx_.clear(), zz_.clear(), xy_.clear();
+    return 0;
+  }
+  std::size_t site_(int i) const {
+    if (i < 0 || i >= sites_ || sz_.empty()) throw LanczosException("SpinCorrelationSolver: no result for this site (compute() first; sites are 0..sites()-1)");
+    return static_cast<std::size_t>(i);
+  }
+
+  std::shared_ptr<device::CsrOperator> op_;
+  const device::CsrOperator* devOp_ = nullptr;
+  detail::KrylovDevice dev_;
+  Index height_ = 0;
+  VectorType state_;
+  int sites_ = 0, nUp_ = -1;
+  double norm2_ = 0.0;
+  std::vector<double> sz_, sx_, zz_, xy_;
+  ComputationInfo info_ = Success;
+  std::vector<std::string> log_;
+};
+
+}  // namespace EigenEx
+}  // namespace cmpt

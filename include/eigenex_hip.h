@@ -302,6 +302,37 @@ int eigenex_spin_sector_csr(int n_sites, int n_up, int n_bonds, const int32_t* s
 int eigenex_spin_sector_upload(eigenex_context_t ctx, int n_sites, int n_up, int n_bonds, const int32_t* site_i,
                                const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null,
                                const double* hx_or_null, eigenex_csr_t* out);
+/* Spin correlations of a real vector x over the rows of a matrix-free spin operator, all terms in one sweep: x is read once
+ * per 16 terms of each list and nothing is written but the sums.  A measurement is two lists of 32-bit site masks (bit i = site
+ * i); with sigma_i(s) as above it yields the raw, unnormalised sums
+ *   norm2       = sum_s x_s^2
+ *   diag_out[t] = sum_s (prod_{i in mask} sigma_i(s)) x_s^2              a mask of 1..n_sites bits
+ *   flip_out[t] = sum_s [sigma_i(s) != sigma_j(s)] x_s x_{s ^ mask}      a two-bit mask {i, j}
+ *   flip_out[t] = sum_s x_s x_{s ^ mask}                                 a one-bit mask {i}: the full space only
+ * from which <Sz_i> = diag{i} / (2 norm2), <Sz_i Sz_j> = diag{i,j} / (4 norm2), <Sx_i> = flip{i} / (2 norm2), <Sx_i Sx_j + Sy_i
+ * Sy_j> = flip{i,j} / (2 norm2) and <S_i.S_j> = the sum of the last two; a diagonal mask of more bits is a string or parity
+ * correlator.  At most 1024 masks per list; duplicates are allowed; empty lists are valid (norm2 alone).  An output pointer whose
+ * count is zero may be NULL, norm2 may be NULL.  Errors (EIGENEX_ERR_ARG, message in eigenex_last_error): a zero mask, a site at
+ * or above n_sites, a flip mask of neither one nor two bits, a one-bit flip mask in a sector (it does not conserve total Sz),
+ * a count out of range, a NULL list with a count.
+ *   eigenex_spin_measure       x = any vector reference of a state whose operator handle came from eigenex_spin_upload or
+ *                              eigenex_spin_sector_upload: sites, sector and rank tables are the handle's.  Any other operator
+ *                              or a host callback: EIGENEX_ERR_STATE.  Runs on the context's stream and synchronises once.  No
+ *                              vector of the state, no coefficient, counter or recorded step batch is touched: a Lanczos run may
+ *                              be measured between two batches and goes on as if nothing had happened.  No atomics: a result
+ *                              depends on the launch grid (eigenex_basis_tune) only through the grouping of partial sums, not on
+ *                              the other terms of the call, and is bit-reproducible from run to run.
+ *   eigenex_spin_measure_host  the definition the kernel is held against, in host code: no context, no GPU.  n_up = -1: the
+ *                              full space (n_sites 2..30, x has 2^n_sites entries); else the sector (n_sites 2..32, x has
+ *                              C(n_sites, n_up) entries).  Rows ascending, one fma per term.
+ *   eigenex_spin_geometry      n_sites and n_up (-1: the full space) of a matrix-free spin operator handle; EIGENEX_ERR_STATE
+ *                              for any other handle.  Either output may be NULL. */
+int eigenex_spin_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint32_t* diag_masks, int n_flip,
+                         const uint32_t* flip_masks, double* diag_out, double* flip_out, double* norm2);
+int eigenex_spin_measure_host(int n_sites, int n_up /* -1: full space */, const double* x, int n_diag,
+                              const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks, double* diag_out,
+                              double* flip_out, double* norm2);
+int eigenex_spin_geometry(eigenex_csr_t csr, int* n_sites, int* n_up);
 /* CSR that already lives in device memory of this context's GPU (e.g. tensors of a GPU framework: pass their
  * data pointers): copied device-to-device, never through the host, after a device-side check of the row pointers
  * and column indices.  Unsharded contexts only; rowptr_dev[0] = 0; columns are global = local indices. */
