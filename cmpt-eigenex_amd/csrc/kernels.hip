@@ -45,13 +45,7 @@ __device__ __forceinline__ double inline_fin_sum(const InlineFin& f, double* lds
   return block_sum(s, lds4);
 }
 
-// a + b*c with the product rounded first (HIP's __dmul_rn/__dadd_rn are plain operators and get contracted):
-// the shift term is added the way the oracle's row loop adds it
-__device__ __forceinline__ double add_product_nofma(double a, double b, double c) {
-#pragma clang fp contract(off)
-  const double p = b * c;
-  return a + p;
-}
+// add_product_nofma (a + b*c, the product rounded first): spmv_index.hpp
 
 // One row of a Chebyshev step (kernels.hpp: ChebStep), every product rounded before it is added: returns t_next, *acc_out = acc
 __device__ __forceinline__ double cheb_row_nofma(double a, double t_prev, double acc, const ChebStep& ch, double* acc_out) {
@@ -1615,121 +1609,73 @@ __global__ __launch_bounds__(kBlock) void k_block_spmv(BlockOperatorView op, con
 }
 
 // ---------------------------------------------------------------------------
-// Matrix-free spin-1/2 operator (spin_model.hpp: SpinOperatorView), one row per lane: row s follows from the bits of s, so the
-// kernel streams no operator at all -- the tables are a few hundred bytes that every lane reads at the same index (scalar
-// loads).  The diagonal is ALU work.  A flip reads x[s ^ mask], which keeps the lane's low bits: a mask above bit 5 moves a
-// wave's 512 contiguous bytes to another place as a whole, one inside bits 0..5 permutes the wave's own 512 bytes, bits 6..7
-// stay in the tile.  The flips are taken kSpinBatch at a time with every load issued before the first product is added; a lane
-// whose two spins are equal has no entry there and reads its own element instead (a line the wave has fetched anyway), so the
-// loads are not branched around where half the lanes diverge.  No LDS staging.  Products are rounded, then added, in table
-// order: the sums of the CSR row loop over eigenex_spin_csr's rows.
+// Matrix-free spin-1/2 operator, one row per lane under the contract of k_block_spmv; spin_rows.hpp has the row walk (the lane's
+// state, the diagonal, the flips in batches of kSpinBatch) and these kernels call it with the accessors below.  The kernel
+// streams no operator at all: the model tables (SpinOperatorView, the head of SpinSectorView) are a few hundred bytes that every
+// lane reads at the same index (scalar loads).  No LDS staging of x.
+//   SECTOR = false (spin_model.hpp): row s is state s, only op->model is read and the table pointers are null.  A flip reads
+//     x[s ^ mask], which keeps the lane's low bits: a mask above bit 5 moves a wave's 512 contiguous bytes to another place as a
+//     whole, one inside bits 0..5 permutes the wave's own 512 bytes, bits 6..7 stay in the tile.
+//   SECTOR = true (spin_sector.hpp): row r is the state of rank r, unranked from the binomials C(p, k), which the workgroup keeps
+//     in LDS (k differs between lanes, so the read is a per-lane LDS address).  No per-row state array in memory: the operator
+//     is the model table and the two rank tables (at most 2^16 words each: they stay in L2).
+// The sums are those of the CSR row loop over eigenex_spin_csr's / eigenex_spin_sector_csr's rows.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_spin_spmv(const SpinOperatorView* __restrict__ op, const double* __restrict__ x_ext,
+struct SpinBinomials32 {  // C(p, k) in LDS
+  const uint32_t* c;
+  __device__ __forceinline__ uint32_t operator()(int i) const { return c[i]; }
+};
+struct SpinRankTables {
+  const uint32_t *lo_rank, *hi_base;
+  __device__ __forceinline__ uint32_t hi(uint32_t i) const { return hi_base[i]; }
+  __device__ __forceinline__ uint32_t lo(uint32_t i) const { return lo_rank[i]; }
+};
+struct SpinVector {
+  const double* x;
+  __device__ __forceinline__ double operator()(uint32_t i) const { return x[i]; }
+};
+
+// the workgroup's copy of the binomials; the caller synchronises
+__device__ __forceinline__ void spin_stage_binomials(const SpinSectorView* __restrict__ op, uint32_t* binom) {
+  constexpr int kCols = kSectorMaxSites + 1;
+  for (int i = threadIdx.x; i < kSectorMaxSites * kCols; i += kBlock) binom[i] = op->binom[i / kCols][i % kCols];
+}
+
+template <bool SECTOR>
+__global__ __launch_bounds__(kBlock) void k_spin_spmv(const SpinSectorView* __restrict__ op, const uint32_t* __restrict__ lo_rank,
+                                                      const uint32_t* __restrict__ hi_base, const double* __restrict__ x_ext,
                                                       const double* __restrict__ scale_ptr, double shift, double* __restrict__ y,
                                                       double* __restrict__ u_out, int64_t n, int64_t ntiles,
                                                       double* __restrict__ partials, int pass, const Ctrl* __restrict__ ctrl) {
   __shared__ double lds4[4];
+  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
   if (ctrl->stopped) return;
+  int n_up = 0, h = 0;
+  uint32_t lo_mask = 0;
+  if constexpr (SECTOR) {
+    spin_stage_binomials(op, binom);
+    __syncthreads();
+    n_up = op->n_up, h = op->h, lo_mask = op->lo_mask;
+  }
   const double scale = scale_ptr ? *scale_ptr : 1.0;
-  const int ndiag = op->ndiag, nflip = op->nflip;
+  const SpinOperatorView* model = &op->model;
+  const int n_sites = model->n_sites, ndiag = model->ndiag, nflip = model->nflip;
+  const SpinRankTables tab{lo_rank, hi_base};
   double dot = 0.0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t r = tile * kBlock + threadIdx.x;
     if (r < n) {
-      const uint32_t s = (uint32_t)r;
-      double d = 0.0;
-      for (int t = 0; t < ndiag; ++t) {
-        const double k = op->dval[t];
-        d += (__popc(s & op->dmask[t]) & 1) ? -k : k;
-      }
-      const double xr = x_ext[r] * scale;
-      double yr = add_product_nofma(0.0, d, xr);
-      for (int t0 = 0; t0 < nflip; t0 += kSpinBatch) {
-        bool on[kSpinBatch];
-        double xv[kSpinBatch];
-#pragma unroll
-        for (int t = 0; t < kSpinBatch; ++t) {
-          const uint32_t m = op->fmask[t0 + t];
-          on[t] = m != 0 && ((m & (m - 1)) == 0 || (__popc(s & m) & 1));
-          xv[t] = x_ext[on[t] ? s ^ m : s];
-        }
-#pragma unroll
-        for (int t = 0; t < kSpinBatch; ++t)
-          if (on[t]) yr = add_product_nofma(yr, op->fval[t0 + t], xv[t] * scale);
-      }
-      if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
-      y[r] = yr;
-      if (u_out) u_out[r] = xr;
-      dot = (pass & kPassSelfNorm) ? fma(yr, yr, dot) : fma(xr, yr, dot);
-    }
-  }
-  if (partials) {
-    dot = block_sum(dot, lds4);
-    if (threadIdx.x == 0) partials[blockIdx.x] = dot;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// The same operator in one sector of fixed magnetisation (spin_sector.hpp: SpinSectorView), one row per lane under the
-// contract of k_spin_spmv.  Row r is the state of rank r among the states with n_up sites up: the lane unranks it from the
-// binomials C(p, k), which the workgroup keeps in LDS (n_sites predicated steps, the same for every lane; k differs between
-// lanes, so the read is a per-lane LDS address).  No per-row state array in memory: the operator is the model table and the two
-// rank tables (at most 2^16 words each: they stay in L2).  The diagonal is k_spin_spmv's.  A flip reads x[rank(s ^ mask)],
-// rank = hi_base[s' >> h] + lo_rank[s' & lo_mask]: two 4-byte gathers, then the 8-byte one.  kSpinBatch flips at a time, all
-// table loads, then all loads of x, then the products; a lane whose two spins are equal keeps s' = s, so it ranks its own state
-// and reads its own element.  Products are rounded, then added, in table order: the sums of the CSR row loop over
-// eigenex_spin_sector_csr's rows.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_spin_sector_spmv(const SpinSectorView* __restrict__ op, const uint32_t* __restrict__ lo_rank,
-                                                             const uint32_t* __restrict__ hi_base, const double* __restrict__ x_ext,
-                                                             const double* __restrict__ scale_ptr, double shift, double* __restrict__ y,
-                                                             double* __restrict__ u_out, int64_t n, int64_t ntiles,
-                                                             double* __restrict__ partials, int pass, const Ctrl* __restrict__ ctrl) {
-  constexpr int kCols = kSectorMaxSites + 1;
-  __shared__ double lds4[4];
-  __shared__ uint32_t binom[kSectorMaxSites * kCols];
-  if (ctrl->stopped) return;
-  for (int i = threadIdx.x; i < kSectorMaxSites * kCols; i += kBlock) binom[i] = op->binom[i / kCols][i % kCols];
-  __syncthreads();
-  const double scale = scale_ptr ? *scale_ptr : 1.0;
-  const int n_sites = op->model.n_sites, ndiag = op->model.ndiag, nflip = op->model.nflip, n_up = op->n_up, h = op->h;
-  const uint32_t lo_mask = op->lo_mask;
-  double dot = 0.0;
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t r = tile * kBlock + threadIdx.x;
-    if (r < n) {
-      uint32_t s = 0, left = (uint32_t)r;
-      int k = n_up;
-      for (int p = n_sites - 1; p >= 0; --p) {
-        const uint32_t c = binom[p * kCols + k];
-        const bool up = k > 0 && left >= c;
-        s |= up ? uint32_t(1) << p : 0u;
-        left -= up ? c : 0u;
-        k -= up ? 1 : 0;
-      }
-      double d = 0.0;
-      for (int t = 0; t < ndiag; ++t) {
-        const double kd = op->model.dval[t];
-        d += (__popc(s & op->model.dmask[t]) & 1) ? -kd : kd;
-      }
+      const uint32_t s = SECTOR ? spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s : (uint32_t)r;
+      const double d = spin_row_diagonal(model->dmask, model->dval, ndiag, s);
       const double xr = x_ext[r] * scale;
       double yr = add_product_nofma(0.0, d, xr);
       for (int t0 = 0; t0 < nflip; t0 += kSpinBatch) {
         bool on[kSpinBatch];
         uint32_t base[kSpinBatch], low[kSpinBatch];
         double xv[kSpinBatch];
-#pragma unroll
-        for (int t = 0; t < kSpinBatch; ++t) {
-          const uint32_t m = op->model.fmask[t0 + t];
-          on[t] = __popc(s & m) == 1;  // a bond with different spins; a padding mask (0) never
-          const uint32_t s2 = on[t] ? s ^ m : s;
-          base[t] = hi_base[s2 >> h], low[t] = lo_rank[s2 & lo_mask];
-        }
-#pragma unroll
-        for (int t = 0; t < kSpinBatch; ++t) xv[t] = x_ext[base[t] + low[t]];
-#pragma unroll
-        for (int t = 0; t < kSpinBatch; ++t)
-          if (on[t]) yr = add_product_nofma(yr, op->model.fval[t0 + t], xv[t] * scale);
+        spin_flip_targets<SECTOR>(model->fmask + t0, s, tab, h, lo_mask, on, base, low);
+        spin_gather(SpinVector{x_ext}, base, low, xv);
+        yr = spin_add_flips(yr, model->fval + t0, on, xv, scale);
       }
       if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
       y[r] = yr;
@@ -1746,84 +1692,50 @@ __global__ __launch_bounds__(kBlock) void k_spin_sector_spmv(const SpinSectorVie
 // ---------------------------------------------------------------------------
 // Spin correlations of one vector (spin_measure.hpp has the definition and SpinMeasureChunk): x streams past once per chunk of
 // kSpinMeasureChunk diagonal and as many flip masks and no vector is written.  One row per lane, 256-row tiles, the operator
-// kernels' persistent grid; the lane has its state as they have it (SECTOR: unranked from the binomials in LDS, else s = r).
-// The chunk is a table that every lane reads at the same index (scalar loads).  A diagonal term is the parity of the mask's down spins and one fma.  The
-// flips go kSpinBatch at a time, all table loads, then all loads of x, then the products; a lane without the entry reads its
-// own element and adds x_s * 0.  The 2 C + 1 sums (norm2, diag, flip) stay in registers across the tile loop -- every register
-// index is a constant after unrolling, a batch is skipped as a whole where the chunk has no term in it -- and leave through
-// block_sum into partials[sum * pstride + workgroup]; k_spin_measure_reduce adds those in k_reduce_fin's order.  No atomics: a
-// result depends on the grid only through the grouping of the partial sums.  ctrl->stopped is not consulted: a measurement is
-// not a Krylov step.
+// kernels' persistent grid, state and batches (spin_rows.hpp); the chunk is a table that every lane reads at the same index
+// (scalar loads).  The 2 C + 1 sums (norm2, diag, flip) stay in registers across the tile loop -- every register index is a
+// constant after unrolling, a batch is skipped as a whole where the chunk has no term in it -- and leave through block_sum into
+// partials[sum * pstride + workgroup]; k_spin_measure_reduce adds those in k_reduce_fin's order.  No atomics: a result depends on
+// the grid only through the grouping of the partial sums.  ctrl->stopped is not consulted: a measurement is not a Krylov step.
 // ---------------------------------------------------------------------------
 template <bool SECTOR>
 __global__ __launch_bounds__(kBlock) void k_spin_measure(const SpinMeasureChunk* __restrict__ ch, const SpinSectorView* __restrict__ op,
                                                          const uint32_t* __restrict__ lo_rank, const uint32_t* __restrict__ hi_base,
                                                          const double* __restrict__ x, int64_t n, int64_t ntiles,
                                                          double* __restrict__ partials, int pstride) {
-  constexpr int C = kSpinMeasureChunk, kCols = kSectorMaxSites + 1;
+  constexpr int C = kSpinMeasureChunk;
   __shared__ double lds4[4];
-  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * kCols : 1];
+  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
   int n_sites = 0, n_up = 0, h = 0;
   uint32_t lo_mask = 0;
   if constexpr (SECTOR) {
-    for (int i = threadIdx.x; i < kSectorMaxSites * kCols; i += kBlock) binom[i] = op->binom[i / kCols][i % kCols];
+    spin_stage_binomials(op, binom);
     __syncthreads();
     n_sites = op->model.n_sites, n_up = op->n_up, h = op->h, lo_mask = op->lo_mask;
   }
   const int ndiag = ch->ndiag, nflip = ch->nflip;
+  const SpinRankTables tab{lo_rank, hi_base};
   double nrm = 0.0, dg[C], fl[C];
 #pragma unroll
   for (int t = 0; t < C; ++t) dg[t] = 0.0, fl[t] = 0.0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t r = tile * kBlock + threadIdx.x;
     if (r < n) {
-      uint32_t s = (uint32_t)r;
-      if constexpr (SECTOR) {
-        uint32_t left = s;
-        int k = n_up;
-        s = 0;
-        for (int p = n_sites - 1; p >= 0; --p) {
-          const uint32_t c = binom[p * kCols + k];
-          const bool up = k > 0 && left >= c;
-          s |= up ? uint32_t(1) << p : 0u;
-          left -= up ? c : 0u;
-          k -= up ? 1 : 0;
-        }
-      }
+      const uint32_t s = SECTOR ? spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s : (uint32_t)r;
       const double xs = x[r];
       nrm = fma(xs, xs, nrm);
 #pragma unroll
       for (int t0 = 0; t0 < C; t0 += kSpinBatch)
-        if (t0 < ndiag) {
-#pragma unroll
-          for (int t = 0; t < kSpinBatch; ++t) dg[t0 + t] = fma((__popc(~s & ch->dmask[t0 + t]) & 1) ? -xs : xs, xs, dg[t0 + t]);
-        }
+        if (t0 < ndiag) spin_measure_diagonals(xs, s, ch->dmask + t0, dg + t0);
 #pragma unroll
       for (int t0 = 0; t0 < C; t0 += kSpinBatch)
         if (t0 < nflip) {
           bool on[kSpinBatch];
+          uint32_t base[kSpinBatch], low[kSpinBatch];
           double xv[kSpinBatch];
-          if constexpr (SECTOR) {
-            uint32_t base[kSpinBatch], low[kSpinBatch];
-#pragma unroll
-            for (int t = 0; t < kSpinBatch; ++t) {
-              const uint32_t m = ch->fmask[t0 + t];
-              on[t] = __popc(s & m) == 1;  // a pair with different spins; a padding mask (0) never
-              const uint32_t s2 = on[t] ? s ^ m : s;
-              base[t] = hi_base[s2 >> h], low[t] = lo_rank[s2 & lo_mask];
-            }
-#pragma unroll
-            for (int t = 0; t < kSpinBatch; ++t) xv[t] = x[base[t] + low[t]];
-          } else {
-#pragma unroll
-            for (int t = 0; t < kSpinBatch; ++t) {
-              const uint32_t m = ch->fmask[t0 + t];
-              on[t] = __popc(m) == 1 || __popc(s & m) == 1;  // one site: every row; a pair: different spins; padding (0): never
-              xv[t] = x[on[t] ? s ^ m : s];
-            }
-          }
-#pragma unroll
-          for (int t = 0; t < kSpinBatch; ++t) fl[t0 + t] = fma(xs, on[t] ? xv[t] : 0.0, fl[t0 + t]);
+          spin_flip_targets<SECTOR>(ch->fmask + t0, s, tab, h, lo_mask, on, base, low);
+          spin_gather(SpinVector{x}, base, low, xv);
+          spin_measure_flips(xs, on, xv, fl + t0);
         }
     }
   }
@@ -2779,26 +2691,18 @@ void launch_block_spmv_z(hipStream_t s, const BlockOperatorView& op, const doubl
                      pstride, pass, ctrl);
 }
 
-void launch_spin_spmv(hipStream_t s, const SpinOperatorView* op, const double* x_ext, const double* scale, double shift, double* y,
-                      double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int pass) {
-  hipLaunchKernelGGL(k_spin_spmv, dim3(grid), dim3(kBlock), 0, s, op, x_ext, scale, shift, y, u_out, n, (n + kBlock - 1) / kBlock,
+void launch_spin_spmv(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
+                      const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl,
+                      int pass) {
+  const auto kernel = lo_rank ? k_spin_spmv<true> : k_spin_spmv<false>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, op, lo_rank, hi_base, x_ext, scale, shift, y, u_out, n, (n + kBlock - 1) / kBlock,
                      partials, pass, ctrl);
 }
 
-void launch_spin_sector_spmv(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
-                             const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
-                             const Ctrl* ctrl, int pass) {
-  hipLaunchKernelGGL(k_spin_sector_spmv, dim3(grid), dim3(kBlock), 0, s, op, lo_rank, hi_base, x_ext, scale, shift, y, u_out, n,
-                     (n + kBlock - 1) / kBlock, partials, pass, ctrl);
-}
-
-void launch_spin_measure(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* sector, const uint32_t* lo_rank,
+void launch_spin_measure(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
                          const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid) {
-  const int64_t ntiles = (n + kBlock - 1) / kBlock;
-  if (sector)
-    hipLaunchKernelGGL(k_spin_measure<true>, dim3(grid), dim3(kBlock), 0, s, chunk, sector, lo_rank, hi_base, x, n, ntiles, partials, pstride);
-  else
-    hipLaunchKernelGGL(k_spin_measure<false>, dim3(grid), dim3(kBlock), 0, s, chunk, sector, lo_rank, hi_base, x, n, ntiles, partials, pstride);
+  const auto kernel = lo_rank ? k_spin_measure<true> : k_spin_measure<false>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, chunk, op, lo_rank, hi_base, x, n, (n + kBlock - 1) / kBlock, partials, pstride);
 }
 
 void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstride, int nblocks, int ndiag, int nflip, double* diag_out,

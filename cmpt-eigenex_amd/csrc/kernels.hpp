@@ -8,6 +8,7 @@
 #include "row_codes.hpp"
 #include "spin_measure.hpp"
 #include "spin_model.hpp"
+#include "spin_rows.hpp"
 #include "spin_sector.hpp"
 #include "split_layout.hpp"
 #include "spmv_index.hpp"
@@ -334,25 +335,21 @@ void launch_block_spmv(hipStream_t s, const BlockOperatorView& op, const double*
 void launch_block_spmv_z(hipStream_t s, const BlockOperatorView& op, const double* x_ext, const double* scale, double shift_re,
                          double shift_im, double* y, double* u_out, int64_t n, double* partials, int pstride, int grid,
                          const Ctrl* ctrl, int pass = 0);
-// Matrix-free spin-1/2 operator (eigenex_spin_upload; spin_model.hpp has the row definition and SpinOperatorView, which lives
-// in device memory): row s is its diagonal entry followed by its flips, products rounded before they are added, in table
-// order -- the rows eigenex_spin_csr writes, so bit-identical to k_spmv on that CSR.
-// same contract as launch_block_spmv (n = 2^n_sites rows, one row per lane, 256-row tiles)
-void launch_spin_spmv(hipStream_t s, const SpinOperatorView* op, const double* x_ext, const double* scale, double shift, double* y,
-                      double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl, int pass = 0);
-// The same operator in one sector of fixed magnetisation (eigenex_spin_sector_upload; spin_sector.hpp has the row definition,
-// SpinSectorView and the two rank tables, all three in device memory): row r is the state of rank r, unranked by the lane;
-// columns are ranks.  The rows eigenex_spin_sector_csr writes, bit-identical to k_spmv on that CSR.
-// same contract as launch_spin_spmv (n = C(n_sites, n_up) rows)
-void launch_spin_sector_spmv(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
-                             const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid,
-                             const Ctrl* ctrl, int pass = 0);
+// Matrix-free spin-1/2 operator (eigenex_spin_upload, eigenex_spin_sector_upload; spin_model.hpp and spin_sector.hpp have the
+// row definitions, spin_rows.hpp the walk): row s is its diagonal entry followed by its flips, products rounded before they are
+// added, in table order -- the rows eigenex_spin_csr / eigenex_spin_sector_csr write, so bit-identical to k_spmv on that CSR.
+// op, lo_rank and hi_base live in device memory.  Full space: lo_rank = hi_base = nullptr, only op->model is read, n = 2^n_sites
+// rows, row s is state s.  A sector of fixed magnetisation: the two rank tables of the sector, n = C(n_sites, n_up) rows, row r
+// is the state of rank r, unranked by the lane; columns are ranks.
+// same contract as launch_block_spmv (one row per lane, 256-row tiles)
+void launch_spin_spmv(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
+                      const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl,
+                      int pass = 0);
 // Spin correlations of the vector x over the rows of a matrix-free spin operator (eigenex_spin_measure; spin_measure.hpp has the
-// definition): one chunk of terms per launch (device memory), sector = nullptr for the full space (n = 2^n_sites rows, the rank
-// tables unused), else the operator's view and tables (n = C(n_sites, n_up) rows).  x is only read; the grid's partial sums go to
-// partials[sum * pstride + workgroup], sum = 0 (norm2), 1 + t (diag), 1 + kSpinMeasureChunk + t (flip): (2 * kSpinMeasureChunk + 1)
-// * pstride doubles, pstride >= grid.  No control block: it always runs.
-void launch_spin_measure(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* sector, const uint32_t* lo_rank,
+// definition): one chunk of terms per launch (device memory); op, lo_rank and hi_base as for launch_spin_spmv (full space: null
+// tables, op is not read).  x is only read; the grid's partial sums go to partials[sum * pstride + workgroup], sum = 0 (norm2),
+// 1 + t (diag), 1 + kSpinMeasureChunk + t (flip): (2 * kSpinMeasureChunk + 1) * pstride doubles, pstride >= grid.  Always runs.
+void launch_spin_measure(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
                          const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid);
 // its second stage: the partials of nblocks workgroups added in a fixed order, the chunk's ndiag and nflip live sums stored to
 // diag_out[t] and flip_out[t], norm2 to *norm_out unless that is NULL

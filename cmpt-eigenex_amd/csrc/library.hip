@@ -277,6 +277,16 @@ struct Segment {  // one contiguous piece of a halo exchange with one peer
   int64_t contig_start;  // send only: >= 0 if the indices are consecutive local rows starting here
 };
 
+// A matrix-free spin-1/2 operator on its shard: the kernels' view and, in a sector of fixed magnetisation (spin_sector.hpp),
+// the two rank tables.  In the full space (spin_model.hpp) only view->model is filled and read, and there are no tables.
+struct SpinShard {
+  DeviceBuffer<SpinSectorView> view;
+  DeviceBuffer<uint32_t> lo, hi;
+  int64_t table_words = 0;     // entries of both tables together
+  int n_sites = 0, n_up = -1;  // n_up = -1: the full space
+  bool on() const { return n_sites > 0; }
+};
+
 struct CsrShard {
   int gshard = 0;
   int64_t rb = 0, re = 0, nloc = 0, npad = 0, nnz = 0, nhalo = 0;
@@ -320,16 +330,9 @@ struct CsrShard {
   DeviceBuffer<int64_t> gent, gcol;
   DeviceBuffer<int32_t> cols, grow0, rowgrp;
   int64_t nstripcols = 0;  // entries of cols
-  // matrix-free spin-1/2 operator (eigenex_spin_upload; spin_model.hpp: SpinOperatorView) instead of any stored form: nnz = 0,
-  // no halo, one pass; the table is all there is
-  bool spin = false;
-  DeviceBuffer<SpinOperatorView> spin_view;
-  // the same in one sector of fixed magnetisation (eigenex_spin_sector_upload; spin_sector.hpp): spin stays true, so every
-  // exclusion of the matrix-free operator holds; sector_view takes the place of spin_view, and the two rank tables come with it
-  DeviceBuffer<SpinSectorView> sector_view;
-  DeviceBuffer<uint32_t> sector_lo, sector_hi;
-  int64_t sector_table_words = 0;  // entries of both tables together
-  int spin_sites = 0, spin_n_up = -1;  // the geometry of either form, for eigenex_spin_measure (n_up = -1: the full space)
+  // matrix-free spin-1/2 operator (eigenex_spin_upload, eigenex_spin_sector_upload) instead of any stored form: nnz = 0, no
+  // halo, one pass
+  SpinShard spin;
   std::vector<Segment> recv, send;
   DeviceBuffer<int32_t> send_idx;  // concatenated local row indices
   DeviceBuffer<double> sendbuf;
@@ -1585,8 +1588,7 @@ double csr_bytes(const CsrShard* m, int es) { return (4.0 + 8.0 * es) * m->nnz +
 double operator_bytes(const CsrShard* m, int es) {
   if (m->rc_rec) return (double)m->rc_bytes * row_code_rows(m->nloc) + 8.0 * m->rc_npal;
   if (m->blocked) return 8.0 * es * m->nnz + 4.0 * m->nstripcols + 4.0 * m->nloc;
-  if (m->sector_view) return (double)sizeof(SpinSectorView) + 4.0 * m->sector_table_words;
-  if (m->spin) return (double)sizeof(SpinOperatorView);
+  if (m->spin.on()) return m->spin.n_up >= 0 ? (double)sizeof(SpinSectorView) + 4.0 * m->spin.table_words : (double)sizeof(SpinOperatorView);
   return csr_bytes(m, es);
 }
 // long rows (16 stored entries per row or more on average): the CSR kernels have a variant for them (kSpmvLongRows) and
@@ -1637,7 +1639,7 @@ void launch_csr_one_pass(hipStream_t st, const BasisShard& s, const OperatorPass
 void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p) {
   const CsrShard* m = s.csr;
   const int es = s.es, grid = s.g_spmv;
-  if (m->tiles_split && !m->split && !m->sorted && !m->blocked && !m->spin && m->passes == 1 && es == 1) {
+  if (m->tiles_split && !m->split && !m->sorted && !m->blocked && !m->spin.on() && m->passes == 1 && es == 1) {
     // (tile lists exist between shards only, the InlineFin / InlineArnoldiBegin hooks on one shard only: none is set here)
     const int g_int = s.g_spmv_int, g_bnd = grid - g_int;
     if (m->n_tile_int > 0 && g_int > 0) launch_csr_one_pass(st, s, p, g_int, p.partials, {m->tile_int, m->n_tile_int});
@@ -1668,13 +1670,9 @@ void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p)
       launch_block_spmv(st, op, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid, p.ctrl, p.pass_flags);
     return;
   }
-  if (m->sector_view) {
-    launch_spin_sector_spmv(st, m->sector_view, m->sector_lo, m->sector_hi, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid,
-                            p.ctrl, p.pass_flags);
-    return;
-  }
-  if (m->spin) {
-    launch_spin_spmv(st, m->spin_view, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid, p.ctrl, p.pass_flags);
+  if (m->spin.on()) {
+    launch_spin_spmv(st, m->spin.view, m->spin.lo, m->spin.hi, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid, p.ctrl,
+                     p.pass_flags);
     return;
   }
   if (m->rc_rec || (m->passes == 1 && es == 1)) {
@@ -1697,7 +1695,7 @@ void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p)
 // Does this shard's operator kernel take a Chebyshev step in its epilogue?  The kernels behind launch_csr_one_pass.
 inline bool filter_in_epilogue(const BasisShard& s) {
   const CsrShard* m = s.csr;
-  return s.es == 1 && !m->split && !m->sorted && !m->blocked && !m->spin && (m->rc_rec || m->passes == 1);
+  return s.es == 1 && !m->split && !m->sorted && !m->blocked && !m->spin.on() && (m->rc_rec || m->passes == 1);
 }
 
 // acc = p(A) x with the state's Chebyshev filter, x = w*scale (the operator input, as for an operator application): `degree`
@@ -1797,7 +1795,7 @@ bool inline_begin_ok(const eigenex_basis_s* b) {
   if (!b->csr || !decides_locally(b) || b->sh.size() != 1) return false;
   static const bool off = std::getenv("EIGENEX_NO_INLINE_FIN") != nullptr;
   const CsrShard& m = b->csr->sh[0];
-  return !off && b->es == 1 && !m.blocked && !m.sorted && !m.spin && (m.split || m.passes == 1);
+  return !off && b->es == 1 && !m.blocked && !m.sorted && !m.spin.on() && (m.split || m.passes == 1);
 }
 
 // The scalar an operator application forms besides v, and where it goes.  Alpha: u.v, all-reduced into hbuf[slot_alpha].
@@ -1950,7 +1948,7 @@ inline bool inlines_fin(const eigenex_basis_s* b) {
   static const bool off = std::getenv("EIGENEX_NO_INLINE_FIN") != nullptr;
   if (off || !decides_locally(b) || !b->csr || b->es != 1 || b->f_degree > 0) return false;  // (a filtered state applies p(A) in many launches)
   const CsrShard& m = b->csr->sh[0];
-  return !m.blocked && !m.sorted && !m.split && !m.spin && m.passes == 1 && (b->ortho_mode == EIGENEX_ORTHO_BATCHED || b->ortho_mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE);
+  return !m.blocked && !m.sorted && !m.split && !m.spin.on() && m.passes == 1 && (b->ortho_mode == EIGENEX_ORTHO_BATCHED || b->ortho_mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE);
 }
 
 // the same passes as the general step, with the hand-overs as hooks: no second-stage launch for the norm or for alpha
@@ -2983,34 +2981,50 @@ int eigenex_spin_csr(int n_sites, int n_bonds, const int32_t* site_i, const int3
   return 0;
 }
 
+// The upload behind eigenex_spin_upload (n_up = -1) and eigenex_spin_sector_upload, which have checked c, out and the model;
+// who: the entry point's name for the error text
+static int spin_upload_common(eigenex_context_t c, const SpinModelArgs& a, int n_up, const char* who, eigenex_csr_t* out) {
+  if (c->P != 1)
+    return fail(EIGENEX_ERR_ARG, std::string(who) + ": a matrix-free spin operator needs a context with one shard in total; sharding it takes an "
+                                                    "exchange of whole vectors for the bonds on the top bits, which is not built");
+  HIPCHK(hipSetDevice(c->device));
+  std::unique_ptr<eigenex_csr_s> m(new eigenex_csr_s());
+  m->ctx = c;
+  m->n_global = n_up < 0 ? int64_t(1) << a.n_sites : spin_sector_dim(a.n_sites, n_up);
+  m->es = 1;
+  m->sh.resize(1);
+  CsrShard& s = m->sh[0];
+  s.gshard = c->local[0];
+  s.spin.n_sites = a.n_sites, s.spin.n_up = n_up;
+  partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
+  s.nloc = s.re - s.rb;
+  s.npad = pad_rows(s.nloc);
+  std::unique_ptr<SpinSectorView> v(new SpinSectorView());  // staging buffers: they live until the synchronise below
+  SpinSectorTables t;
+  if (n_up < 0) {
+    spin_build_view(a, v->model);
+  } else {
+    spin_sector_build_view(a, n_up, *v);
+    spin_sector_build_tables(a.n_sites, n_up, t);
+    s.spin.table_words = (int64_t)(t.lo_rank.size() + t.hi_base.size());
+    HIPCHK(s.spin.lo.alloc(t.lo_rank.size()));
+    HIPCHK(s.spin.hi.alloc(t.hi_base.size()));
+    HIPCHK(hipMemcpyAsync(s.spin.lo, t.lo_rank.data(), 4 * t.lo_rank.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s.spin.hi, t.hi_base.data(), 4 * t.hi_base.size(), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(s.spin.view.alloc(1));
+  HIPCHK(hipMemcpyAsync(s.spin.view, v.get(), sizeof(SpinSectorView), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *out = m.release();
+  return 0;
+}
+
 int eigenex_spin_upload(eigenex_context_t c, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz,
                         const double* jxy, const double* hz_or_null, const double* hx_or_null, eigenex_csr_t* out) {
   if (!c || !out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_upload: NULL argument");
   const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null};
   if (const char* why = spin_model_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_upload: ") + why);
-  if (c->P != 1)
-    return fail(EIGENEX_ERR_ARG, "eigenex_spin_upload: a matrix-free spin operator needs a context with one shard in total; sharding it takes an "
-                                 "exchange of whole vectors for the bonds on the top bits, which is not built");
-  HIPCHK(hipSetDevice(c->device));
-  std::unique_ptr<eigenex_csr_s> m(new eigenex_csr_s());
-  m->ctx = c;
-  m->n_global = int64_t(1) << n_sites;
-  m->es = 1;
-  m->sh.resize(1);
-  CsrShard& s = m->sh[0];
-  s.gshard = c->local[0];
-  s.spin = true;
-  s.spin_sites = n_sites;
-  partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
-  s.nloc = s.re - s.rb;
-  s.npad = pad_rows(s.nloc);
-  SpinOperatorView v;
-  spin_build_view(a, v);
-  HIPCHK(s.spin_view.alloc(1));
-  HIPCHK(hipMemcpyAsync(s.spin_view, &v, sizeof(v), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));  // v is a stack-lifetime staging buffer
-  *out = m.release();
-  return 0;
+  return spin_upload_common(c, a, -1, "eigenex_spin_upload", out);
 }
 
 int eigenex_spin_sector_dim(int n_sites, int n_up, int64_t* dim) {
@@ -3050,43 +3064,14 @@ int eigenex_spin_sector_upload(eigenex_context_t c, int n_sites, int n_up, int n
   if (!c || !out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_upload: NULL argument");
   const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null};
   if (const char* why = spin_sector_error(a, n_up)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_sector_upload: ") + why);
-  if (c->P != 1)
-    return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_upload: a matrix-free spin operator needs a context with one shard in total; sharding it takes an "
-                                 "exchange of whole vectors for the bonds on the top bits, which is not built");
-  HIPCHK(hipSetDevice(c->device));
-  std::unique_ptr<eigenex_csr_s> m(new eigenex_csr_s());
-  m->ctx = c;
-  m->n_global = spin_sector_dim(n_sites, n_up);
-  m->es = 1;
-  m->sh.resize(1);
-  CsrShard& s = m->sh[0];
-  s.gshard = c->local[0];
-  s.spin = true;
-  s.spin_sites = n_sites, s.spin_n_up = n_up;
-  partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
-  s.nloc = s.re - s.rb;
-  s.npad = pad_rows(s.nloc);
-  std::unique_ptr<SpinSectorView> v(new SpinSectorView());  // staging buffers: they live until the synchronise below
-  spin_sector_build_view(a, n_up, *v);
-  SpinSectorTables t;
-  spin_sector_build_tables(n_sites, n_up, t);
-  s.sector_table_words = (int64_t)(t.lo_rank.size() + t.hi_base.size());
-  HIPCHK(s.sector_view.alloc(1));
-  HIPCHK(s.sector_lo.alloc(t.lo_rank.size()));
-  HIPCHK(s.sector_hi.alloc(t.hi_base.size()));
-  HIPCHK(hipMemcpyAsync(s.sector_view, v.get(), sizeof(SpinSectorView), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(s.sector_lo, t.lo_rank.data(), 4 * t.lo_rank.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(s.sector_hi, t.hi_base.data(), 4 * t.hi_base.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  *out = m.release();
-  return 0;
+  return spin_upload_common(c, a, n_up, "eigenex_spin_sector_upload", out);
 }
 
 int eigenex_spin_geometry(eigenex_csr_t m, int* n_sites, int* n_up) {
   if (!m) return fail(EIGENEX_ERR_ARG, "eigenex_spin_geometry: NULL argument");
-  if (m->sh.empty() || !m->sh[0].spin) return fail(EIGENEX_ERR_STATE, "eigenex_spin_geometry: the operator is not a matrix-free spin operator");
-  if (n_sites) *n_sites = m->sh[0].spin_sites;
-  if (n_up) *n_up = m->sh[0].spin_n_up;
+  if (m->sh.empty() || !m->sh[0].spin.on()) return fail(EIGENEX_ERR_STATE, "eigenex_spin_geometry: the operator is not a matrix-free spin operator");
+  if (n_sites) *n_sites = m->sh[0].spin.n_sites;
+  if (n_up) *n_up = m->sh[0].spin.n_up;
   return 0;
 }
 
@@ -3103,12 +3088,12 @@ int eigenex_spin_measure_host(int n_sites, int n_up, const double* x, int n_diag
 int eigenex_spin_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks,
                          double* diag_out, double* flip_out, double* norm2) {
   if (!b) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure: basis is NULL");
-  if (!b->csr || b->sh.size() != 1 || !b->sh[0].csr || !b->sh[0].csr->spin)
+  if (!b->csr || b->sh.size() != 1 || !b->sh[0].csr || !b->sh[0].csr->spin.on())
     return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_measure: the operator of this state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
                                           : "eigenex_spin_measure: the state has no device operator (a host callback knows no sites)");
   BasisShard& s = b->sh[0];
   const CsrShard* m = s.csr;
-  const SpinMeasureArgs a{m->spin_sites, m->spin_n_up, n_diag, diag_masks, n_flip, flip_masks};
+  const SpinMeasureArgs a{m->spin.n_sites, m->spin.n_up, n_diag, diag_masks, n_flip, flip_masks};
   if (const char* why = spin_measure_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_measure: ") + why);
   if ((n_diag > 0 && !diag_out) || (n_flip > 0 && !flip_out)) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure: an output list is NULL but its count is not zero");
   const double* x = vec_ptr(s, b->cap, b->nq, x_ref);
@@ -3130,7 +3115,7 @@ int eigenex_spin_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint32_
   for (size_t k = 0; k < chunks.size(); ++k) {
     const size_t first = k * kSpinMeasureChunk;  // a list that ends before `first` has no live sum in this chunk
     const size_t dfirst = std::min(first, (size_t)n_diag), ffirst = std::min(first, (size_t)n_flip);
-    launch_spin_measure(c->stream, d_chunks + k, m->sector_view, m->sector_lo, m->sector_hi, x, s.nloc, d_part, grid, grid);
+    launch_spin_measure(c->stream, d_chunks + k, m->spin.view, m->spin.lo, m->spin.hi, x, s.nloc, d_part, grid, grid);
     launch_spin_measure_reduce(c->stream, d_part, grid, grid, chunks[k].ndiag, chunks[k].nflip, d_out + 1 + dfirst, d_out + 1 + n_diag + ffirst,
                                k == 0 ? d_out.get() : nullptr);
   }
@@ -3147,8 +3132,7 @@ int eigenex_csr_layout(eigenex_csr_t m, int* layout) {
   *layout = EIGENEX_LAYOUT_CSR;
   for (auto& s : m->sh) {
     if (s.blocked) *layout = EIGENEX_LAYOUT_DENSE_BLOCKS;
-    else if (s.sector_view) *layout = EIGENEX_LAYOUT_MATRIX_FREE_SPIN_SECTOR;
-    else if (s.spin) *layout = EIGENEX_LAYOUT_MATRIX_FREE_SPIN;
+    else if (s.spin.on()) *layout = s.spin.n_up >= 0 ? EIGENEX_LAYOUT_MATRIX_FREE_SPIN_SECTOR : EIGENEX_LAYOUT_MATRIX_FREE_SPIN;
     else if (s.split) *layout = EIGENEX_LAYOUT_SPLIT_TILES;
     else if (s.sorted) *layout = EIGENEX_LAYOUT_SORTED_TILES;
     else if (s.passes > 1 && *layout == EIGENEX_LAYOUT_CSR) *layout = EIGENEX_LAYOUT_COLUMN_BLOCKED;
@@ -3359,7 +3343,7 @@ int eigenex_basis_is_complex(eigenex_basis_t b, int* is_complex) {
 int eigenex_basis_create_ex(eigenex_context_t c, eigenex_csr_t csr, int64_t n_global, int capacity, int n_ortho,
                             int is_complex, eigenex_basis_t* out) {
   if (!c || !out || n_global <= 0 || capacity < 1 || n_ortho < 0) return fail(EIGENEX_ERR_ARG, "eigenex_basis_create: bad argument");
-  if (csr && is_complex && !csr->sh.empty() && csr->sh[0].spin)
+  if (csr && is_complex && !csr->sh.empty() && csr->sh[0].spin.on())
     return fail(EIGENEX_ERR_ARG, "a matrix-free spin operator is real: it cannot back a complex state");
   if (csr && (csr->es == 2) != (is_complex != 0)) return fail(EIGENEX_ERR_ARG, "scalar type of the basis and of the CSR operator differ");
   if (csr && (csr->ctx != c || csr->n_global != n_global)) return fail(EIGENEX_ERR_ARG, "csr belongs to another context or has another size");

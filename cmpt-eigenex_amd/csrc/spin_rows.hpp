@@ -1,0 +1,119 @@
+// The row walk of the matrix-free spin-1/2 kernels (kernels.hip: k_spin_spmv<SECTOR>, k_spin_measure<SECTOR>), shared by the
+// device code and by the host replays tests/cpp/spin_{model,sector,measure}_sanitize.cpp, which run it under AddressSanitizer +
+// UBSan.  The kernels and the replays call THESE functions, so what a replay proves about them (every load inside its array, the
+// state equal to spin_sector_unrank, the sums equal to the CSR row loop and to spin_measure_host bit for bit) holds for the
+// kernels' rows as compiled.  No device construct in here: plain C++11.  spin_write_rows, spin_sector_unrank, spin_sector_rank
+// and spin_measure_host do not use this file: they are written from the definitions and are what this walk is checked against.
+//
+// One row per lane.  The lane has its state s: the row number itself in the full space, the state of rank r in a sector
+// (spin_unrank_row).  The diagonal is ALU work (spin_row_diagonal).  The off-diagonal terms are site masks taken kSpinBatch at a
+// time, in three phases that the callers keep apart:
+//   1. spin_flip_targets: which terms the row has (on[]) and the row each one reads (base[] + low[]).  A lane without the term keeps its
+//      own state and so its own row, a line its wave has fetched anyway: no load is branched around where half the lanes diverge.
+//      In a sector this is where the two rank tables are read, two 4-byte gathers per term.
+//   2. all kSpinBatch loads of x (spin_gather), issued before the first product is added.
+//   3. the products: spin_add_flips for the operator (rounded, then added, in table order: the CSR row loop's sum) or
+//      spin_measure_flips for a measurement (one fma per term, a lane without the term adds x_s * 0).
+// Every array has kSpinBatch entries and every loop over one a constant trip count: after unrolling and inlining a register array
+// is only ever indexed by constants.
+//
+// The mask and value tables, which every lane reads at the same index, come as pointers to a batch's first entry.  All other
+// memory is reached through accessor objects of the caller -- the kernels index raw pointers and LDS, the replays check first:
+// binom(i) is C(p, k) at i = p * (kSectorMaxSites + 1) + k; tab.hi(i) and tab.lo(i) are hi_base and lo_rank; x(i) is the vector.
+#pragma once
+#include <stdint.h>
+
+#include <cmath>
+
+#include "spin_measure.hpp"
+#include "spmv_index.hpp"
+
+#if defined(__clang__)
+#define EIGENEX_UNROLL _Pragma("unroll")
+#else
+#define EIGENEX_UNROLL
+#endif
+
+namespace eigenex {
+
+// Parity by population count, one instruction on the device.  Not spin_parity (spin_model.hpp), the folding form of the functions
+// written from the definition: the walk shares no arithmetic with what it is checked against.
+EIGENEX_HD bool spin_odd(uint32_t x) { return (__builtin_popcount(x) & 1) != 0; }
+
+// The state of rank r among the states of n_sites sites with n_up up (spin_sector.hpp: unrank), in 32-bit arithmetic: n_sites
+// predicated steps, the same for every lane; k differs between lanes.  left and k end at 0 for every r below the dimension.
+struct SpinUnranked {
+  uint32_t s, left;
+  int k;
+};
+template <class Binom>
+EIGENEX_HD SpinUnranked spin_unrank_row(const Binom& binom, int n_sites, int n_up, uint32_t r) {
+  SpinUnranked u = {0u, r, n_up};
+  for (int p = n_sites - 1; p >= 0; --p) {
+    const uint32_t c = binom(p * (kSectorMaxSites + 1) + u.k);
+    const bool up = u.k > 0 && u.left >= c;
+    u.s |= up ? uint32_t(1) << p : 0u;
+    u.left -= up ? c : 0u;
+    u.k -= up ? 1 : 0;
+  }
+  return u;
+}
+
+// The diagonal entry of row s from the (mask, constant) table of SpinOperatorView: plain additions of sign-flipped constants
+EIGENEX_HD double spin_row_diagonal(const uint32_t* dmask, const double* dval, int ndiag, uint32_t s) {
+  double d = 0.0;
+  for (int t = 0; t < ndiag; ++t) {
+    const double k = dval[t];
+    d += spin_odd(s & dmask[t]) ? -k : k;
+  }
+  return d;
+}
+
+// Phase 1 of a batch of masks (mask[0 .. kSpinBatch)) on the row of state s.  One predicate for every caller: a one-bit mask (a
+// transverse field, Sx) flips every row, a two-bit mask (a bond, a pair) the rows whose two spins differ, a zero mask (padding)
+// never.  A sector has no one-bit masks (spin_sector_error and spin_measure_error refuse them: they leave the sector), so that
+// half of the test, four scalar instructions per term, is compiled out there.  The row a term reads is base[t] + low[t]: the
+// state itself and 0 in the full space, where tab, h and lo_mask are not looked at, hi_base[..] and lo_rank[..] in a sector.  The
+// two words stay apart until the load (spin_gather), so that a load of x waits for its own table words and not for the batch's.
+// Either of the two alone left k_spin_spmv<true> 1.3 - 2 % slower (profiles/spin_rows_refactor.md).
+template <bool SECTOR, class Tables>
+EIGENEX_HD void spin_flip_targets(const uint32_t* mask, uint32_t s, const Tables& tab, int h, uint32_t lo_mask, bool* on, uint32_t* base,
+                                  uint32_t* low) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) {
+    const uint32_t m = mask[t];
+    on[t] = (!SECTOR && __builtin_popcount(m) == 1) || __builtin_popcount(s & m) == 1;
+    const uint32_t s2 = on[t] ? s ^ m : s;
+    base[t] = SECTOR ? tab.hi(s2 >> h) : s2;
+    low[t] = SECTOR ? tab.lo(s2 & lo_mask) : 0u;
+  }
+}
+
+// phase 2
+template <class Vector>
+EIGENEX_HD void spin_gather(const Vector& x, const uint32_t* base, const uint32_t* low, double* xv) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) xv[t] = x(base[t] + low[t]);
+}
+
+// phase 3 of the operator: yr + sum over the row's terms of fval[t] * (xv[t] * scale), every product rounded before it is added
+EIGENEX_HD double spin_add_flips(double yr, const double* fval, const bool* on, const double* xv, double scale) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t)
+    if (on[t]) yr = add_product_nofma(yr, fval[t], xv[t] * scale);
+  return yr;
+}
+
+// phase 3 of a measurement (spin_measure.hpp: flip[t]): one fma per term on every row
+EIGENEX_HD void spin_measure_flips(double xs, const bool* on, const double* xv, double* fl) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) fl[t] = std::fma(xs, on[t] ? xv[t] : 0.0, fl[t]);
+}
+
+// a batch of diagonal terms of a measurement (spin_measure.hpp: diag[t]): the sign is the parity of the mask's down spins
+EIGENEX_HD void spin_measure_diagonals(double xs, uint32_t s, const uint32_t* dmask, double* dg) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) dg[t] = std::fma(spin_odd(~s & dmask[t]) ? -xs : xs, xs, dg[t]);
+}
+
+}  // namespace eigenex

@@ -34,6 +34,17 @@ constexpr int kCsrTailPad = 8;       // zero entries stored behind nnz: aligned 
 EIGENEX_HD int skew(int i) { return i + (i >> 5); }
 EIGENEX_HD int skewz(int i) { return i + (i >> 4); }
 
+// a + b*c with the product rounded first (HIP's __dmul_rn/__dadd_rn are plain operators and get contracted): a row sum is
+// added the way the oracle's row loop adds it.  Here so that the kernels and the host replays of their rows (spin_rows.hpp)
+// round alike; a host compiler other than clang needs -ffp-contract=off.
+EIGENEX_HD double add_product_nofma(double a, double b, double c) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double p = b * c;
+  return a + p;
+}
+
 struct SpmvLaneLoads {
   int q0, q1;     // first entry of the lane's two groups of four
   bool in0, in1;  // group loaded?

@@ -2,10 +2,10 @@
 // csrc/spin_measure.hpp -- the argument check, the chunk table and the host evaluation -- compiled into this program, which
 // links nothing else.  For the full space (L = 3, 6, 9) and the sectors (4,2), (6,0), (6,6), (11,5), (31,2), (32,2), (32,31), with
 // every site, every pair, a four-site string, the all-sites mask and a duplicate (and every one-bit flip in the full space):
-// the outputs go into exactly-sized arrays, and k_spin_measure is replayed from its chunk table, operation for operation with
-// every load checked against its array -- the lane's state from the binomials, the batches, the gather through hi_base and
-// lo_rank, the own element where the entry is absent.  Taken over ascending rows the replay adds the same fma chain as the host
-// evaluation (a lane without the entry adds x_s * 0), so the two are compared bit for bit.
+// the outputs go into exactly-sized arrays, and the row loop of k_spin_measure runs on its chunk table -- the kernel's own
+// functions (csrc/spin_rows.hpp), every load checked against its array: the lane's state from the binomials, the batches, the
+// gather through hi_base and lo_rank, the own element where the entry is absent.  Taken over ascending rows it adds the same fma
+// chain as the host evaluation (a lane without the entry adds x_s * 0), so the two are compared bit for bit.
 // Built and run by tests/test_spin_measure_host.py; prints SPIN MEASURE OK and exits 0 when every check holds.
 #include <cmath>
 #include <cstdio>
@@ -15,24 +15,10 @@
 #include <vector>
 
 #include "spin_measure.hpp"
-
-static int fails = 0;
-#define EXPECT(c)                                                        \
-  do {                                                                   \
-    if (!(c)) {                                                          \
-      std::fprintf(stderr, "FAILED %s:%d %s\n", __FILE__, __LINE__, #c); \
-      ++fails;                                                           \
-    }                                                                    \
-  } while (0)
+#include "spin_rows_checked.hpp"
 
 using eigenex::SpinMeasureArgs;
 using eigenex::SpinMeasureChunk;
-
-static int popcount(std::uint32_t x) {
-  int c = 0;
-  for (; x; x &= x - 1) ++c;
-  return c;
-}
 
 struct Lists {
   std::vector<std::uint32_t> diag, flip;
@@ -55,9 +41,10 @@ static Lists lists_of(int L, bool sector) {
   return l;
 }
 
-// k_spin_measure (kernels.hip) over ascending rows: one chunk per pass, sums per chunk slot, every load checked
+// k_spin_measure (kernels.hip) over ascending rows, by the kernel's own functions: one chunk per pass, sums per chunk slot,
+// every load checked
 static void replay(const SpinMeasureArgs& a, const std::vector<double>& x, std::vector<double>& diag, std::vector<double>& flip, double* norm2) {
-  const int C = eigenex::kSpinMeasureChunk, B = eigenex::kSpinBatch, cols = eigenex::kSectorMaxSites + 1;
+  const int C = eigenex::kSpinMeasureChunk, B = eigenex::kSpinBatch;
   const bool sector = a.n_up != -1;
   const std::int64_t n = eigenex::spin_measure_rows(a);
   EXPECT(static_cast<std::int64_t>(x.size()) == n);
@@ -70,7 +57,9 @@ static void replay(const SpinMeasureArgs& a, const std::vector<double>& x, std::
     eigenex::spin_sector_build_view(eigenex::SpinModelArgs{a.n_sites, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, a.n_up, *v);
     eigenex::spin_sector_build_tables(a.n_sites, a.n_up, t);
   }
-  const std::uint32_t* binom = &v->binom[0][0];
+  const CheckedBinomials binom(*v);
+  const CheckedTables tab{&t};
+  const CheckedVector xs_at{&x};
   diag.assign(static_cast<std::size_t>(a.n_diag), 0.0);
   flip.assign(static_cast<std::size_t>(a.n_flip), 0.0);
   int live_d = 0, live_f = 0;
@@ -80,51 +69,37 @@ static void replay(const SpinMeasureArgs& a, const std::vector<double>& x, std::
     for (int i = ch.ndiag; i < C; ++i) EXPECT(ch.dmask[i] == 0);
     for (int i = ch.nflip; i < C; ++i) EXPECT(ch.fmask[i] == 0);
     live_d += ch.ndiag, live_f += ch.nflip;
-    double nrm = 0.0;
-    std::vector<double> dg(static_cast<std::size_t>(C), 0.0), fl(static_cast<std::size_t>(C), 0.0);
+    double nrm = 0.0, dg[eigenex::kSpinMeasureChunk] = {0.0}, fl[eigenex::kSpinMeasureChunk] = {0.0};
     for (std::int64_t r = 0; r < n; ++r) {
       std::uint32_t s = static_cast<std::uint32_t>(r);
       if (sector) {
-        std::uint32_t left = s;
-        int kk = v->n_up;
-        s = 0;
-        for (int p = v->model.n_sites - 1; p >= 0; --p) {
-          EXPECT(kk >= 0 && p * cols + kk < eigenex::kSectorMaxSites * cols);
-          const std::uint32_t c = binom[p * cols + kk];
-          const bool up = kk > 0 && left >= c;
-          s |= up ? std::uint32_t(1) << p : 0u;
-          left -= up ? c : 0u;
-          kk -= up ? 1 : 0;
-        }
-        EXPECT(left == 0 && kk == 0 && s == eigenex::spin_sector_unrank(a.n_sites, a.n_up, r));
+        const eigenex::SpinUnranked u = eigenex::spin_unrank_row(binom, v->model.n_sites, v->n_up, s);
+        EXPECT(u.left == 0 && u.k == 0 && u.s == eigenex::spin_sector_unrank(a.n_sites, a.n_up, r));
+        s = u.s;
       }
-      const double xs = x.at(static_cast<std::size_t>(r));
+      const double xs = xs_at(static_cast<std::uint32_t>(r));
       nrm = std::fma(xs, xs, nrm);
       for (int t0 = 0; t0 < C; t0 += B)
-        if (t0 < ch.ndiag)
-          for (int i = 0; i < B; ++i) dg.at(static_cast<std::size_t>(t0 + i)) = std::fma((popcount(~s & ch.dmask[t0 + i]) & 1) ? -xs : xs, xs, dg.at(static_cast<std::size_t>(t0 + i)));
+        if (t0 < ch.ndiag) eigenex::spin_measure_diagonals(xs, s, ch.dmask + t0, dg + t0);
       for (int t0 = 0; t0 < C; t0 += B)
-        if (t0 < ch.nflip)
-          for (int i = 0; i < B; ++i) {
-            const std::uint32_t m = ch.fmask[t0 + i];
-            const bool on = sector ? popcount(s & m) == 1 : (popcount(m) == 1 || popcount(s & m) == 1);
-            const std::uint32_t s2 = on ? s ^ m : s;
-            const std::size_t idx = sector ? static_cast<std::size_t>(t.hi_base.at(s2 >> v->h)) + t.lo_rank.at(s2 & v->lo_mask) : static_cast<std::size_t>(s2);
-            if (!on) EXPECT(idx == static_cast<std::size_t>(r));  // a lane without the entry reads its own element
-            if (m == 0) EXPECT(!on);                              // a padding mask never flips
-            const double xv = x.at(idx);
-            fl.at(static_cast<std::size_t>(t0 + i)) = std::fma(xs, on ? xv : 0.0, fl.at(static_cast<std::size_t>(t0 + i)));
-          }
+        if (t0 < ch.nflip) {
+          bool on[eigenex::kSpinBatch];
+          std::uint32_t base[eigenex::kSpinBatch], low[eigenex::kSpinBatch];
+          double xv[eigenex::kSpinBatch];
+          if (sector)
+            eigenex::spin_flip_targets<true>(ch.fmask + t0, s, tab, v->h, v->lo_mask, on, base, low);
+          else
+            eigenex::spin_flip_targets<false>(ch.fmask + t0, s, tab, 0, 0u, on, base, low);
+          expect_targets(ch.fmask + t0, on, base, low, r);
+          eigenex::spin_gather(xs_at, base, low, xv);
+          eigenex::spin_measure_flips(xs, on, xv, fl + t0);
+        }
     }
-    for (int i = 0; i < ch.ndiag; ++i) diag.at(k * C + static_cast<std::size_t>(i)) = dg[static_cast<std::size_t>(i)];
-    for (int i = 0; i < ch.nflip; ++i) flip.at(k * C + static_cast<std::size_t>(i)) = fl[static_cast<std::size_t>(i)];
+    for (int i = 0; i < ch.ndiag; ++i) diag.at(k * C + static_cast<std::size_t>(i)) = dg[i];
+    for (int i = 0; i < ch.nflip; ++i) flip.at(k * C + static_cast<std::size_t>(i)) = fl[i];
     if (k == 0) *norm2 = nrm;
   }
   EXPECT(live_d == a.n_diag && live_f == a.n_flip);
-}
-
-static bool same_bits(const std::vector<double>& a, const std::vector<double>& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), sizeof(double) * a.size()) == 0);
 }
 
 static void check_shape(int L, int n_up, std::mt19937& rng) {

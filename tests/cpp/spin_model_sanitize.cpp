@@ -2,8 +2,9 @@
 // csrc/spin_model.hpp -- argument checks, the CSR rows, the tables of the matrix-free kernel -- compiled into this
 // program, and SpinHalfModel of spin_operator.hpp on top of the library's eigenex_spin_csr.  For open, periodic, random
 // (zero couplings, a repeated pair), field and Ising-only models at L = 2..10: the rows go into exactly-sized arrays, the
-// count-only call agrees with the full one, a row window equals its slice, the kernel's row sum replayed from its tables
-// equals the CSR row loop bit for bit, and every load of that replay stays inside the vector.
+// count-only call agrees with the full one, a row window equals its slice, the row sum of k_spin_spmv<false> -- the kernel's own
+// functions (csrc/spin_rows.hpp) run on its tables -- equals the CSR row loop bit for bit, and every load they make stays inside
+// the vector.
 // Built and run by tests/test_spin_host.py; prints SPIN MODEL OK and exits 0 when every check holds.
 #include <cstdio>
 #include <cstring>
@@ -12,21 +13,9 @@
 
 #include "cmpt/eigen_ex/spin_operator.hpp"
 #include "spin_model.hpp"
+#include "spin_rows_checked.hpp"
 
 using namespace cmpt::EigenEx;
-
-static int fails = 0;
-#define EXPECT(c)                                                        \
-  do {                                                                   \
-    if (!(c)) {                                                          \
-      std::fprintf(stderr, "FAILED %s:%d %s\n", __FILE__, __LINE__, #c); \
-      ++fails;                                                           \
-    }                                                                    \
-  } while (0)
-
-static bool same_bits(const std::vector<double>& a, const std::vector<double>& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), sizeof(double) * a.size()) == 0);
-}
 
 struct Rows {
   std::vector<std::int64_t> rowptr;
@@ -50,23 +39,6 @@ static Rows rows_of(const SpinHalfModel& m, std::int64_t rb, std::int64_t nr) {
   eigenex::spin_write_rows(a, rb, nr, r.rowptr.data(), r.col.data(), r.val.data(), &nnz2);
   EXPECT(nnz == nnz2 && counted == r.rowptr && r.rowptr[0] == 0 && r.rowptr.back() == nnz);
   return r;
-}
-
-// the row sum of k_spin_spmv from its tables, operation for operation (kernels.hip), loads checked against n
-static double kernel_row(const eigenex::SpinOperatorView& v, const std::vector<double>& x, std::uint32_t s, double scale) {
-  double d = 0.0;
-  for (int t = 0; t < v.ndiag; ++t) d += eigenex::spin_parity(s & v.dmask[t]) ? -v.dval[t] : v.dval[t];
-  const double xr = x.at(s) * scale;
-  double yr = 0.0 + d * xr;
-  for (int t0 = 0; t0 < v.nflip; t0 += eigenex::kSpinBatch)
-    for (int t = 0; t < eigenex::kSpinBatch; ++t) {
-      EXPECT(t0 + t < eigenex::kSpinMaxTerms);
-      const std::uint32_t m = v.fmask[t0 + t];
-      const bool on = m != 0 && ((m & (m - 1)) == 0 || eigenex::spin_parity(s & m));
-      const double xv = x.at(on ? s ^ m : s);
-      if (on) yr = yr + v.fval[t0 + t] * (xv * scale);
-    }
-  return yr;
 }
 
 static void check_model(const SpinHalfModel& m, std::mt19937& rng) {
@@ -104,7 +76,7 @@ static void check_model(const SpinHalfModel& m, std::mt19937& rng) {
       EXPECT(c >= 0 && c < n);
       sum = sum + full.val[static_cast<std::size_t>(p)] * (x[static_cast<std::size_t>(c)] * scale);
     }
-    const double k = kernel_row(v, x, static_cast<std::uint32_t>(s), scale);
+    const double k = checked_operator_row<false>(v, eigenex::SpinSectorTables(), 0, 0u, x, s, static_cast<std::uint32_t>(s), scale);
     EXPECT(std::memcmp(&k, &sum, sizeof(double)) == 0);
   }
 }

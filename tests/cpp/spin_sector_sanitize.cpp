@@ -4,8 +4,8 @@
 // library.  For every (L, n_up) with L <= 12: dim, unrank and rank against enumeration.  For chains, random and field models in
 // those sectors and in the few-spin sectors of 31 and 32 sites: the rows go into exactly-sized arrays, the count-only call
 // agrees with the full one, a row window equals its slice, the rows equal the full-space rows at the sector's states with ranked
-// columns, and the row sum of k_spin_sector_spmv replayed from its tables -- every load checked against its array -- equals the
-// CSR row loop bit for bit.
+// columns, and the row sum of k_spin_spmv<true> -- the kernel's own functions (csrc/spin_rows.hpp) run on its tables, every
+// load checked against its array -- equals the CSR row loop bit for bit.
 // Built and run by tests/test_spin_sector_host.py; prints SPIN SECTOR OK and exits 0 when every check holds.
 #include <cstdio>
 #include <cstring>
@@ -14,18 +14,10 @@
 #include <vector>
 
 #include "cmpt/eigen_ex/spin_operator.hpp"
+#include "spin_rows_checked.hpp"
 #include "spin_sector.hpp"
 
 using namespace cmpt::EigenEx;
-
-static int fails = 0;
-#define EXPECT(c)                                                        \
-  do {                                                                   \
-    if (!(c)) {                                                          \
-      std::fprintf(stderr, "FAILED %s:%d %s\n", __FILE__, __LINE__, #c); \
-      ++fails;                                                           \
-    }                                                                    \
-  } while (0)
 
 struct Rows {
   std::vector<std::int64_t> rowptr;
@@ -55,41 +47,6 @@ static Rows rows_of(const SpinHalfModel& m, const eigenex::SpinSectorTables& t, 
   eigenex::spin_sector_write_rows(a, t, rb, nr, r.rowptr.data(), r.col.data(), r.val.data(), &nnz2);
   EXPECT(nnz == nnz2 && counted == r.rowptr && r.rowptr[0] == 0 && r.rowptr.back() == nnz);
   return r;
-}
-
-// the row sum of k_spin_sector_spmv from its tables, operation for operation (kernels.hip), every load checked
-static double kernel_row(const eigenex::SpinSectorView& v, const eigenex::SpinSectorTables& t, const std::vector<double>& x, std::int64_t r,
-                         double scale, std::uint32_t* state) {
-  const int cols = eigenex::kSectorMaxSites + 1;
-  const std::uint32_t* binom = &v.binom[0][0];
-  std::uint32_t s = 0, left = static_cast<std::uint32_t>(r);
-  int k = v.n_up;
-  for (int p = v.model.n_sites - 1; p >= 0; --p) {
-    EXPECT(k >= 0 && p * cols + k < eigenex::kSectorMaxSites * cols);
-    const std::uint32_t c = binom[p * cols + k];
-    const bool up = k > 0 && left >= c;
-    s |= up ? std::uint32_t(1) << p : 0u;
-    left -= up ? c : 0u;
-    k -= up ? 1 : 0;
-  }
-  EXPECT(left == 0 && k == 0);
-  *state = s;
-  double d = 0.0;
-  for (int i = 0; i < v.model.ndiag; ++i) d += eigenex::spin_parity(s & v.model.dmask[i]) ? -v.model.dval[i] : v.model.dval[i];
-  const double xr = x.at(static_cast<std::size_t>(r)) * scale;
-  double yr = 0.0 + d * xr;
-  for (int t0 = 0; t0 < v.model.nflip; t0 += eigenex::kSpinBatch)
-    for (int i = 0; i < eigenex::kSpinBatch; ++i) {
-      EXPECT(t0 + i < eigenex::kSpinMaxTerms);
-      const std::uint32_t m = v.model.fmask[t0 + i];
-      const bool on = popcount(s & m) == 1;
-      const std::uint32_t s2 = on ? s ^ m : s;
-      const std::uint32_t idx = t.hi_base.at(s2 >> v.h) + t.lo_rank.at(s2 & v.lo_mask);
-      if (!on) EXPECT(idx == static_cast<std::uint32_t>(r));  // a lane without the entry reads its own element
-      const double xv = x.at(idx);
-      if (on) yr = yr + v.model.fval[t0 + i] * (xv * scale);
-    }
-  return yr;
 }
 
 static void check_sector(const SpinHalfModel& m, int n_up, std::mt19937& rng) {
@@ -122,6 +79,7 @@ static void check_sector(const SpinHalfModel& m, int n_up, std::mt19937& rng) {
   // the kernel's tables against the CSR row loop, and the rows against the full-space rows at the same state
   std::unique_ptr<eigenex::SpinSectorView> v(new eigenex::SpinSectorView());
   eigenex::spin_sector_build_view(a, n_up, *v);
+  const CheckedBinomials binom(*v);
   EXPECT(v->model.n_sites == L && v->n_up == n_up && v->h == t.h && v->model.ndiag <= eigenex::kSpinMaxTerms && v->model.nflip <= eigenex::kSpinMaxBonds);
   for (int i = v->model.nflip; i < eigenex::kSpinMaxTerms; ++i) EXPECT(v->model.fmask[i] == 0 && v->model.fval[i] == 0.0);
   for (int i = 0; i < v->model.nflip; ++i) EXPECT(popcount(v->model.fmask[i]) == 2);
@@ -138,8 +96,10 @@ static void check_sector(const SpinHalfModel& m, int n_up, std::mt19937& rng) {
       EXPECT(c >= 0 && c < n);
       sum = sum + full.val[static_cast<std::size_t>(p)] * (x[static_cast<std::size_t>(c)] * scale);
     }
-    std::uint32_t s = 0;
-    const double k = kernel_row(*v, t, x, r, scale, &s);
+    const eigenex::SpinUnranked u = eigenex::spin_unrank_row(binom, L, n_up, static_cast<std::uint32_t>(r));  // the kernel's own unrank
+    EXPECT(u.left == 0 && u.k == 0);
+    const std::uint32_t s = u.s;
+    const double k = checked_operator_row<true>(v->model, t, v->h, v->lo_mask, x, r, s, scale);
     EXPECT(std::memcmp(&k, &sum, sizeof(double)) == 0);
     EXPECT(s == states[static_cast<std::size_t>(r)] && s == eigenex::spin_sector_unrank(L, n_up, r) && popcount(s) == n_up);
     EXPECT(eigenex::spin_sector_rank(t, s) == static_cast<std::uint32_t>(r));

@@ -4,7 +4,9 @@ spin measurement between its two batches -- shared by tests/test_gpu_spin_measur
     python -m tests.spin_measure_cases OUT.npz
 
 The library reads EIGENEX_NO_GRAPHS once per process, so the run without recorded step batches is a process of its own.
-Importable without a GPU: nothing touches the device before run()."""
+Also the shapes, term lists and the measurement whose bits tests/golden/spin_measure_bits_parent.npz records
+(scripts/record_spin_measure_bits.py writes it, test_measurement_bits_equal_the_parent_build reads it).
+Importable without a GPU: nothing touches the device before run() or measure_bits()."""
 import os
 import sys
 
@@ -16,6 +18,46 @@ if ROOT not in sys.path:
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 L, N_UP, ROWS, STEPS = 12, 6, 924, 20
+
+# (n_sites, n_up or None, one workgroup per CU): two tiles; one partial tile; 496 rows with bit 31; 512 tiles on a grid of one
+# workgroup per CU, so the tile loop goes round -- the only shape whose partial sums depend on the device's CU count
+BITS_SHAPES = [(9, None, False), (10, 5, False), (32, 2, False), (17, None, True)]
+
+
+def bits_key(n_sites, n_up):
+    return "%d_%s" % (n_sites, "full" if n_up is None else n_up)
+
+
+def bits_lists(n_sites, n_up):
+    """every site, the pairs with the top site, a low and a middle pair, the pairs with site 0, the string, the all-sites mask and
+    a duplicate: at least 17 terms on either list at every shape of BITS_SHAPES, so both span two chunks or more"""
+    import spin_measure_reference as mr
+
+    full_d, _ = mr.term_lists(n_sites, n_up)
+    top = [(1 << i) | (1 << (n_sites - 1)) for i in range(n_sites - 1)] + [0b11, (1 << (n_sites // 2 - 1)) | (1 << (n_sites // 2))]
+    low = [1 | (1 << i) for i in range(2, n_sites - 1)]
+    diag = mr.site_masks(n_sites) + top + [int(m) for m in full_d[-3:]]
+    flip = top + [top[0]] + low + (mr.site_masks(n_sites) if n_up is None else [])
+    assert len(diag) >= 17 and len(flip) >= 17
+    return np.array(diag, np.uint32), np.array(flip, np.uint32)
+
+
+def measure_bits(capi, n_sites, n_up, one_workgroup_per_cu):
+    """{"norm2", "diag", "flip"}: the raw bytes (uint8) of one eigenex_spin_measure of spin_measure_reference.vector"""
+    import spin_measure_reference as mr
+    import spin_reference as sr
+
+    bonds = sr.chain(n_sites, 1.0, 0.7, periodic=True)
+    ctx = capi.Context()
+    S = capi.Csr.spin_half(ctx, n_sites, bonds) if n_up is None else capi.Csr.spin_half_sector(ctx, n_sites, n_up, bonds)
+    b = capi.Basis(ctx, S, mr.rows(n_sites, n_up), 2)
+    if one_workgroup_per_cu:
+        b.tune(2, 1, 0)
+    b.upload(capi.VEC_COL(1), mr.vector(n_sites, n_up))
+    diag, flip, norm2 = b.spin_measure(capi.VEC_COL(1), *bits_lists(n_sites, n_up))
+    for h in (b, S, ctx):
+        h.close()
+    return {k: np.frombuffer(np.ascontiguousarray(v, np.float64).tobytes(), np.uint8) for k, v in (("norm2", norm2), ("diag", diag), ("flip", flip))}
 
 
 def run(capi, interrupt: bool):

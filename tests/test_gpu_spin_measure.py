@@ -78,6 +78,29 @@ def test_device_sums_equal_the_restatement_within_the_bound(mods, L, n_up):
         h.close()
 
 
+@pytest.mark.parametrize("L,n_up,per_cu", cases.BITS_SHAPES)
+def test_measurement_bits_equal_the_parent_build(mods, L, n_up, per_cu):
+    """norm2, diag and flip of one measurement are the bytes tests/golden/spin_measure_bits_parent.npz holds, recorded by
+    scripts/record_spin_measure_bits.py from the build before the kernels took their row walk from csrc/spin_rows.hpp: the
+    bound of the test above would not notice an fma that became a multiply and an add.  (9, full), (10,5) and (32,2) have at
+    most one tile per workgroup, so their partial sums, and with them the fixture, are the same on every device.  (17, full) runs
+    512 tiles on one workgroup per CU: which tiles a workgroup adds up depends on the CU count, so that shape holds only on a
+    device with as many CUs as the recording one, which the test asserts first."""
+    capi, _ = mods
+    with np.load(os.path.join(ROOT, "tests", "golden", "spin_measure_bits_parent.npz")) as z:
+        golden = {k: z[k] for k in z.files}
+    if per_cu:
+        import torch
+
+        cus, cus_rec = int(torch.cuda.get_device_properties(0).multi_processor_count), int(golden["cus"])
+        assert cus == cus_rec, f"this device has {cus} CUs, the fixture was recorded on {cus_rec}: the grid fixes the partial sums of this shape"
+    got = cases.measure_bits(capi, L, n_up, per_cu)
+    diag_masks, flip_masks = cases.bits_lists(L, n_up)
+    assert got["diag"].size == 8 * diag_masks.size and got["flip"].size == 8 * flip_masks.size and got["norm2"].size == 8
+    for k in ("norm2", "diag", "flip"):
+        assert got[k].tobytes() == golden[cases.bits_key(L, n_up) + "/" + k].tobytes(), (L, n_up, k)
+
+
 COUNTS = [0, 1, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 496 + 32]
 
 

@@ -133,7 +133,8 @@ def test_exports_are_declared_and_present(capi):
 def test_spin_host_code_under_sanitizers(capi, tmp_path):
     """csrc/spin_model.hpp (argument checks, the CSR rows, the kernel's tables) compiled into a stand-alone program with
     AddressSanitizer + UBSan, together with SpinHalfModel of spin_operator.hpp: for every model above at L = 2..10 the rows
-    are written into exactly-sized arrays, replayed from the kernel's tables in the kernel's order, and compared bitwise."""
+    are written into exactly-sized arrays and compared bitwise with the row sums of k_spin_spmv<false>, for which the kernel's
+    own functions (csrc/spin_rows.hpp, compiled into the program) run on the kernel's tables through bounds-checked accessors."""
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
     exe = str(tmp_path / "spin_model_sanitize")

@@ -187,8 +187,9 @@ def test_exports_are_declared_and_present(capi):
 
 def test_measure_host_code_under_sanitizers(tmp_path):
     """csrc/spin_measure.hpp (argument check, chunk table, host evaluation) compiled into a stand-alone program with
-    AddressSanitizer + UBSan: outputs into exactly-sized arrays, and the kernel's loop replayed from its chunk table with every
-    load bounds-checked, bit-identical to the host evaluation."""
+    AddressSanitizer + UBSan: outputs into exactly-sized arrays, and the row loop of k_spin_measure on its chunk table -- the
+    kernel's own functions (csrc/spin_rows.hpp, compiled into the program) with every load bounds-checked -- bit-identical to
+    the host evaluation."""
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
     exe = str(tmp_path / "spin_measure_sanitize")

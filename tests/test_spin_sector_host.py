@@ -201,8 +201,8 @@ def test_exports_are_declared_and_present(capi):
 def test_sector_host_code_under_sanitizers(capi, tmp_path):
     """csrc/spin_sector.hpp (argument checks, binomials, unrank, the rank tables, the sector rows, the kernel's view) compiled
     into a stand-alone program with AddressSanitizer + UBSan, together with the sector calls of SpinHalfModel: rank and unrank
-    round trips, rows written into exactly-sized arrays, and the kernel's row sum replayed from its tables with checked loads
-    and compared bitwise with the rows."""
+    round trips, rows written into exactly-sized arrays, and the row sum of k_spin_spmv<true> compared bitwise with the rows:
+    the kernel's own functions (csrc/spin_rows.hpp, compiled into the program) run on its tables, every load bounds-checked."""
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
     exe = str(tmp_path / "spin_sector_sanitize")
