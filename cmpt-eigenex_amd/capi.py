@@ -24,6 +24,7 @@ VEC_V = -1
 VEC_W = -2
 VEC_START = -3
 K_SPMV, K_DOTS, K_UPDATE, K_SMALL, K_COMM, K_RITZ = range(6)
+SPIN_SITE_Z, SPIN_SITE_PLUS, SPIN_SITE_MINUS = range(3)
 
 
 def VEC_COL(c: int) -> int:
@@ -109,6 +110,8 @@ SIGNATURES = {
     "eigenex_spin_measure": (C.c_int, [_vp, C.c_int, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_measure_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_geometry": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "eigenex_spin_site_apply": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _dp, _dp]),
+    "eigenex_spin_site_apply_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "eigenex_basis_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_create_ex": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_is_complex": (C.c_int, [_vp, C.POINTER(C.c_int)]),
@@ -352,6 +355,24 @@ def spin_measure_host(n_sites: int, n_up, x, diag_masks, flip_masks):
     _chk(lib().eigenex_spin_measure_host(int(n_sites), -1 if n_up is None else int(n_up), _d(x), nd, dp, nf, fp, _d(diag) if nd else None,
                                          _d(flip) if nf else None, C.byref(norm2)))
     return diag, flip, norm2.value
+
+
+def spin_site_apply_host(n_sites: int, n_up, kind: int, coef, x):
+    """eigenex_spin_site_apply_host: (y, norm2) of y = O x for the sum of site operators (kind, coef), in host code (no GPU).
+    n_up = None: the full space; else x lives on the sector of n_up sites up and y on the sector the kind leads to (Z: the same,
+    PLUS: n_up + 1, MINUS: n_up - 1)."""
+    x = np.ascontiguousarray(x, np.float64)
+    coef = np.ascontiguousarray(coef, np.float64)
+    if coef.size < int(n_sites):  # the library reads n_sites entries
+        raise EigenexError("spin_site_apply_host: coef has fewer entries than n_sites")
+    if n_up is None:
+        rows = 1 << max(int(n_sites), 0) if int(n_sites) <= 30 else 0
+    else:
+        up = int(n_up) + (1 if kind == SPIN_SITE_PLUS else -1 if kind == SPIN_SITE_MINUS else 0)
+        rows = spin_sector_dim(n_sites, up) if 2 <= int(n_sites) <= 32 and 0 <= up <= int(n_sites) else 0
+    y, norm2 = np.zeros(rows), C.c_double()
+    _chk(lib().eigenex_spin_site_apply_host(int(n_sites), -1 if n_up is None else int(n_up), int(kind), _d(coef), _d(x), _d(y), C.byref(norm2)))
+    return y, norm2.value
 
 
 class ShardPlan:
@@ -751,6 +772,17 @@ class Basis:
         diag, flip, norm2 = np.zeros(nd), np.zeros(nf), C.c_double()
         _chk(lib().eigenex_spin_measure(self.h, x_ref, nd, dp, nf, fp, _d(diag) if nd else None, _d(flip) if nf else None, C.byref(norm2)))
         return diag, flip, norm2.value
+
+    def spin_site_apply(self, x_ref, dst, y_ref, kind, coef):
+        """eigenex_spin_site_apply: vector y_ref of the state dst = (sum of site operators kind, coef) applied to vector x_ref of
+        this state, on the device; returns norm2 = |y|^2.  Both states need matrix-free spin operators of one context whose
+        geometries fit the kind; dst may be this state.  No coefficient, counter or recorded step batch changes."""
+        coef = np.ascontiguousarray(coef, np.float64).reshape(-1)
+        buf = np.zeros(max(32, coef.size))  # the library reads n_sites <= 32 entries, whatever the caller handed over
+        buf[:coef.size] = coef
+        norm2 = C.c_double()
+        _chk(lib().eigenex_spin_site_apply(self.h, x_ref, dst.h, y_ref, int(kind), _d(buf), C.byref(norm2)))
+        return norm2.value
 
     def set_filter(self, mu, center=0.0, halfwidth=1.0, degree=None):
         """Chebyshev filter p(A) = sum_k mu[k] T_k((A - center)/halfwidth) for the Lanczos steps and filter_apply; mu = None

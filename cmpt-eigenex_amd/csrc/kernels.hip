@@ -1767,6 +1767,61 @@ __global__ __launch_bounds__(kBlock) void k_spin_measure_reduce(const double* __
   if (threadIdx.x == 0) *dst = s;
 }
 
+// ---------------------------------------------------------------------------
+// A sum of site operators applied to a vector (spin_site.hpp has the definition and SpinSiteTable; spin_rows.hpp the walk): one
+// row of the DESTINATION per lane, 256-row tiles, the operator kernels' persistent grid and LDS binomials.  dst_op is the
+// destination operator's view (its binomials and n_up unrank the row; not read in the full space), src_lo and src_hi are the
+// SOURCE operator's rank tables: a flipped state has the source's number of up sites.  A lane without a term ranks the table's
+// fallback state, row 0 of the source, and its sum ignores what it loaded (spin_rows.hpp says why its own row will not do).
+// The table is read by every lane at the same index (scalar loads); x is not staged in LDS.  Z reads and writes only the lane's
+// own element, so y may be x there; for the flips the caller keeps them apart.  norm2 = sum y_r^2 leaves through block_sum
+// into partials[workgroup]; k_spin_measure_reduce adds those in k_reduce_fin's order.  No atomics.  ctrl->stopped is not
+// consulted: this is not a Krylov step.
+// ---------------------------------------------------------------------------
+template <bool SECTOR>
+__global__ __launch_bounds__(kBlock) void k_spin_site_apply(const SpinSiteTable* __restrict__ tb, const SpinSectorView* __restrict__ dst_op,
+                                                            const uint32_t* __restrict__ src_lo, const uint32_t* __restrict__ src_hi,
+                                                            const double* x, double* y, int64_t n, int64_t ntiles,
+                                                            double* __restrict__ partials) {
+  __shared__ double lds4[4];
+  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
+  int n_up = 0, h = 0;
+  uint32_t lo_mask = 0;
+  if constexpr (SECTOR) {
+    spin_stage_binomials(dst_op, binom);
+    __syncthreads();
+    n_up = dst_op->n_up, h = dst_op->h, lo_mask = dst_op->lo_mask;
+  }
+  const int kind = tb->kind, n_sites = tb->n_sites;
+  const uint32_t site_mask = tb->site_mask, fallback = tb->fallback;
+  const SpinRankTables tab{src_lo, src_hi};
+  double nrm = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + threadIdx.x;
+    if (r < n) {
+      const uint32_t s = SECTOR ? spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s : (uint32_t)r;
+      double yr = 0.0;
+      if (kind == kSpinSiteZ) {
+        yr = spin_site_weight(tb->half, n_sites, s) * x[r];
+      } else {
+        const uint32_t has = kind == kSpinSitePlus ? s : ~s & site_mask;
+        for (int i0 = 0; i0 < n_sites; i0 += kSpinBatch) {
+          bool on[kSpinBatch];
+          uint32_t base[kSpinBatch], low[kSpinBatch];
+          double xv[kSpinBatch];
+          spin_site_targets<SECTOR>(i0, s, has, fallback, tab, h, lo_mask, on, base, low);
+          spin_gather(SpinVector{x}, base, low, xv);
+          yr = spin_site_add(yr, tb->coef + i0, on, xv);
+        }
+      }
+      y[r] = yr;
+      nrm = fma(yr, yr, nrm);
+    }
+  }
+  nrm = block_sum(nrm, lds4);
+  if (threadIdx.x == 0) partials[blockIdx.x] = nrm;
+}
+
 // complex blocks: entries, input and sums are (re, im) pairs; products without contraction and added part by
 // part, exactly like k_spmv_z
 template <int NB, bool STAGED>
@@ -2709,6 +2764,12 @@ void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstri
                                 double* flip_out, double* norm_out) {
   hipLaunchKernelGGL(k_spin_measure_reduce, dim3(2 * kSpinMeasureChunk + 1), dim3(kBlock), 0, s, partials, pstride, nblocks, ndiag, nflip,
                      diag_out, flip_out, norm_out);
+}
+
+void launch_spin_site_apply(hipStream_t s, const SpinSiteTable* table, const SpinSectorView* dst_op, const uint32_t* src_lo,
+                            const uint32_t* src_hi, const double* x, double* y, int64_t n, double* partials, int grid) {
+  const auto kernel = src_lo ? k_spin_site_apply<true> : k_spin_site_apply<false>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, table, dst_op, src_lo, src_hi, x, y, n, (n + kBlock - 1) / kBlock, partials);
 }
 
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,

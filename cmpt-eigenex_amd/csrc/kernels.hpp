@@ -10,6 +10,7 @@
 #include "spin_model.hpp"
 #include "spin_rows.hpp"
 #include "spin_sector.hpp"
+#include "spin_site.hpp"
 #include "split_layout.hpp"
 #include "spmv_index.hpp"
 
@@ -355,6 +356,13 @@ void launch_spin_measure(hipStream_t s, const SpinMeasureChunk* chunk, const Spi
 // diag_out[t] and flip_out[t], norm2 to *norm_out unless that is NULL
 void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstride, int nblocks, int ndiag, int nflip, double* diag_out,
                                 double* flip_out, double* norm_out);
+// A sum of site operators applied to x, y = O x (eigenex_spin_site_apply; spin_site.hpp has the definition and the table): one
+// launch.  table, dst_op, src_lo and src_hi live in device memory.  y has n rows, those of the DESTINATION operator, whose view
+// dst_op is; src_lo and src_hi are the rank tables of the SOURCE operator, on whose rows x lives (full space: null tables, dst_op
+// is not read).  y may be x for Z only.  The grid's partial sums of y_r^2 go to partials[workgroup], `grid` doubles; their second
+// stage is launch_spin_measure_reduce(s, partials, grid, grid, 0, 0, nullptr, nullptr, norm_out).  Always runs.
+void launch_spin_site_apply(hipStream_t s, const SpinSiteTable* table, const SpinSectorView* dst_op, const uint32_t* src_lo,
+                            const uint32_t* src_hi, const double* x, double* y, int64_t n, double* partials, int grid);
 // host-operator path: u_out = x*scale
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,
                   const Ctrl* ctrl);

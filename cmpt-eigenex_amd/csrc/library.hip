@@ -3127,6 +3127,57 @@ int eigenex_spin_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint32_
   return 0;
 }
 
+int eigenex_spin_site_apply_host(int n_sites, int n_up_src, int kind, const double* coef, const double* x, double* y, double* norm2) {
+  const SpinSiteArgs a{n_sites, n_up_src, kind, coef, n_sites, spin_site_dst_up(n_up_src, kind)};
+  if (const char* why = spin_site_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_site_apply_host: ") + why);
+  if (!x || !y) return fail(EIGENEX_ERR_ARG, "eigenex_spin_site_apply_host: x or y is NULL");
+  if (x == y && kind != kSpinSiteZ) return fail(EIGENEX_ERR_ARG, "eigenex_spin_site_apply_host: y may be x for EIGENEX_SPIN_SITE_Z only (a flip reads what it would write)");
+  spin_site_apply_host(a, x, y, norm2);
+  return 0;
+}
+
+// the one shard of a state behind a matrix-free spin operator, or nullptr
+static BasisShard* spin_state_shard(eigenex_basis_t b) {
+  return b->csr && b->sh.size() == 1 && b->sh[0].csr && b->sh[0].csr->spin.on() ? &b->sh[0] : nullptr;
+}
+
+int eigenex_spin_site_apply(eigenex_basis_t src, int x_ref, eigenex_basis_t dst, int y_ref, int kind, const double* coef, double* norm2) {
+  if (!src || !dst) return fail(EIGENEX_ERR_ARG, "eigenex_spin_site_apply: a state is NULL");
+  for (eigenex_basis_t b : {src, dst})
+    if (!spin_state_shard(b))
+      return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_site_apply: the operator of a state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
+                                            : "eigenex_spin_site_apply: a state has no device operator (a host callback knows no sites)");
+  if (src->ctx != dst->ctx) return fail(EIGENEX_ERR_STATE, "eigenex_spin_site_apply: the two states live on different contexts");
+  BasisShard &ss = *spin_state_shard(src), &sd = *spin_state_shard(dst);
+  const SpinShard &ms = ss.csr->spin, &md = sd.csr->spin;
+  const SpinSiteArgs a{ms.n_sites, ms.n_up, kind, coef, md.n_sites, md.n_up};
+  if (const char* why = spin_site_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_site_apply: ") + why);
+  const double* x = vec_ptr(ss, src->cap, src->nq, x_ref);
+  double* y = vec_ptr(sd, dst->cap, dst->nq, y_ref);
+  if (!x || !y) return fail(EIGENEX_ERR_ARG, "bad vector reference");
+  if (x == y && kind != kSpinSiteZ)
+    return fail(EIGENEX_ERR_ARG, "eigenex_spin_site_apply: y may be x for EIGENEX_SPIN_SITE_Z only (the gather of a flip reads what it would write)");
+  eigenex_context_s* c = dst->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  // scratch of this call alone: the table, the grid's partial sums and norm2.  The states' own partials may hold a pending alpha.
+  SpinSiteTable table;
+  spin_site_build_table(a, table);
+  const int grid = sd.g_spmv;
+  DeviceBuffer<SpinSiteTable> d_table;
+  DeviceBuffer<double> d_part, d_out;
+  double out = 0.0;
+  HIPCHK(d_table.alloc(1));
+  HIPCHK(d_part.alloc((size_t)grid));
+  HIPCHK(d_out.alloc(1));
+  HIPCHK(hipMemcpyAsync(d_table, &table, sizeof(SpinSiteTable), hipMemcpyHostToDevice, c->stream));
+  launch_spin_site_apply(c->stream, d_table, md.view, ms.lo, ms.hi, x, y, sd.nloc, d_part, grid);
+  launch_spin_measure_reduce(c->stream, d_part, grid, grid, 0, 0, nullptr, nullptr, d_out);
+  HIPCHK(hipMemcpyAsync(&out, d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the table and the scratch live until here
+  if (norm2) *norm2 = out;
+  return 0;
+}
+
 int eigenex_csr_layout(eigenex_csr_t m, int* layout) {
   if (!m || !layout) return fail(EIGENEX_ERR_ARG, "eigenex_csr_layout: NULL argument");
   *layout = EIGENEX_LAYOUT_CSR;

@@ -10,7 +10,8 @@
 //   eigenex_arnoldi_solver_*   ArnoldiEigenSolver<double>
 //   eigenex_zarnoldi_solver_*  ArnoldiEigenSolver<std::complex<double>>
 // plus eigenex_[z]trlanczos_solver_* (ThickRestartLanczosEigenSolver), eigenex_[z]kschur_solver_* (KrylovSchurEigenSolver) and
-// eigenex_[z]flanczos_solver_* (FilteredLanczosEigenSolver); eigenex_[z]density_solver_* (SpectralDensitySolver).
+// eigenex_[z]flanczos_solver_* (FilteredLanczosEigenSolver); eigenex_[z]density_solver_* (SpectralDensitySolver);
+// eigenex_spin_dynamics_solver_* (SpinDynamicsSolver).
 // Complex data cross this boundary as interleaved (re, im) doubles.
 #include <complex>
 #include <cstring>
@@ -25,6 +26,8 @@
 #include "cmpt/eigen_ex/lanczos.hpp"
 #include "cmpt/eigen_ex/lanczos_function.hpp"
 #include "cmpt/eigen_ex/spectral_density.hpp"
+#include "cmpt/eigen_ex/spin_correlations.hpp"
+#include "cmpt/eigen_ex/spin_dynamics.hpp"
 #include "cmpt/eigen_ex/thick_restart_lanczos.hpp"
 #include "cmpt/eigen_ex/triplets_operator.hpp"
 
@@ -840,5 +843,102 @@ EIGENEX_LANCZOS_FAMILY(eigenex_lanczos_solver_, double)
 EIGENEX_LANCZOS_FAMILY(eigenex_zlanczos_solver_, std::complex<double>)
 EIGENEX_ARNOLDI_FAMILY(eigenex_arnoldi_solver_, double)
 EIGENEX_ARNOLDI_FAMILY(eigenex_zarnoldi_solver_, std::complex<double>)
+
+// ---- SpinDynamicsSolver (spin_dynamics.hpp).  The model crosses as the arrays of eigenex_spin_upload; n_up = -1: the full space.
+struct SpinDynamicsBox {
+  std::shared_ptr<device::Context> ctx;
+  SpinHalfModel model;
+  int n_up = -1;
+  DenseVector<double> state;
+  SpinDynamicsSolver es;
+};
+void* eigenex_spin_dynamics_solver_create(void) {
+  try {
+    return new SpinDynamicsBox();
+  } catch (const std::exception& e) {
+    g_serr = e.what();
+    return nullptr;
+  }
+}
+void eigenex_spin_dynamics_solver_destroy(void* p) { delete static_cast<SpinDynamicsBox*>(p); }
+int eigenex_spin_dynamics_solver_set_model(void* p, eigenex_context_t ctx, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                                           const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null, int n_up) {
+  return guard([&] {
+    auto* b = static_cast<SpinDynamicsBox*>(p);
+    b->ctx = device::Context::borrow(ctx);
+    b->model = SpinHalfModel(n_sites);
+    for (int k = 0; k < n_bonds; ++k) b->model.addBond(site_i[k], site_j[k], jz[k], jxy[k]);
+    for (int i = 0; i < n_sites; ++i) {
+      if (hz_or_null) b->model.setFieldZ(i, hz_or_null[i]);
+      if (hx_or_null) b->model.setFieldX(i, hx_or_null[i]);
+    }
+    b->n_up = n_up;
+    b->es.setModel(b->ctx, b->model, n_up);
+  });
+}
+int eigenex_spin_dynamics_solver_set_state(void* p, const double* v, int64_t n) {
+  return guard([&] {
+    auto* b = static_cast<SpinDynamicsBox*>(p);
+    b->state = make_vector<double>(v, n);
+    b->es.setState(b->state);
+  });
+}
+int eigenex_spin_dynamics_solver_set_state_energy(void* p, double E0) {
+  return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.setStateEnergy(E0); });
+}
+int eigenex_spin_dynamics_solver_set_site_operator(void* p, int kind, const double* coef, int n) {
+  return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.setSiteOperator(kind, std::vector<double>(coef, coef + (n > 0 ? n : 0))); });
+}
+int eigenex_spin_dynamics_solver_set_lanczos_steps(void* p, int64_t m) {
+  return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.setLanczosSteps((Index)m); });
+}
+int eigenex_spin_dynamics_solver_compute(void* p) { return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.compute(); }); }
+int eigenex_spin_dynamics_solver_compute_structure_factor_z(void* p, double q) {
+  return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.computeStructureFactorZ(q); });
+}
+// out[5]: poles, alpha, beta, log lines, info
+int eigenex_spin_dynamics_solver_sizes(void* p, int64_t* out) {
+  return guard([&] {
+    auto& es = static_cast<SpinDynamicsBox*>(p)->es;
+    out[0] = (int64_t)es.poles().size(), out[1] = (int64_t)es.lanczosAlpha().size(), out[2] = (int64_t)es.lanczosBeta().size();
+    out[3] = (int64_t)es.log().size(), out[4] = (int64_t)es.info();
+  });
+}
+// any pointer may be NULL; scalars[3] = (totalWeight, stateEnergy, stateNormSquared)
+int eigenex_spin_dynamics_solver_get(void* p, double* poles, double* weights, double* alpha, double* beta, double* scalars) {
+  return guard([&] {
+    auto& es = static_cast<SpinDynamicsBox*>(p)->es;
+    if (poles) std::copy(es.poles().begin(), es.poles().end(), poles);
+    if (weights) std::copy(es.weights().begin(), es.weights().end(), weights);
+    if (alpha) std::copy(es.lanczosAlpha().begin(), es.lanczosAlpha().end(), alpha);
+    if (beta) std::copy(es.lanczosBeta().begin(), es.lanczosBeta().end(), beta);
+    if (scalars) scalars[0] = es.totalWeight(), scalars[1] = es.stateEnergy(), scalars[2] = es.stateNormSquared();
+  });
+}
+int eigenex_spin_dynamics_solver_spectrum(void* p, const double* omega, int64_t n, double eta, double* out) {
+  return guard([&] {
+    for (int64_t i = 0; i < n; ++i) out[i] = static_cast<SpinDynamicsBox*>(p)->es.spectrum(omega[i], eta);
+  });
+}
+int eigenex_spin_dynamics_solver_moment(void* p, int k, double* out) {
+  return guard([&] { *out = static_cast<SpinDynamicsBox*>(p)->es.moment(k); });
+}
+// SpinCorrelationSolver::structureFactorZ(q) of the same model and state: the sum rule of computeStructureFactorZ(q)
+int eigenex_spin_dynamics_solver_static_structure_factor_z(void* p, double q, double* out) {
+  return guard([&] {
+    auto* b = static_cast<SpinDynamicsBox*>(p);
+    if (!b->ctx) throw LanczosException("static_structure_factor_z: no model");
+    SpinCorrelationSolver sc;
+    sc.setDeviceOperator(b->n_up < 0 ? device::spinHalfOperator(b->ctx, b->model) : device::spinHalfSectorOperator(b->ctx, b->model, b->n_up));
+    sc.setState(b->state);
+    sc.compute();
+    if (sc.info() != Success) throw LanczosException("static_structure_factor_z: " + (sc.log().empty() ? std::string("failed") : sc.log().back()));
+    *out = sc.structureFactorZ(q);
+  });
+}
+const char* eigenex_spin_dynamics_solver_log_line(void* p, int64_t i) {
+  auto& log = static_cast<SpinDynamicsBox*>(p)->es.log();
+  return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
+}
 
 }  // extern "C"

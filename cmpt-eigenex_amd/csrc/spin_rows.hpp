@@ -1,5 +1,6 @@
-// The row walk of the matrix-free spin-1/2 kernels (kernels.hip: k_spin_spmv<SECTOR>, k_spin_measure<SECTOR>), shared by the
-// device code and by the host replays tests/cpp/spin_{model,sector,measure}_sanitize.cpp, which run it under AddressSanitizer +
+// The row walk of the matrix-free spin-1/2 kernels (kernels.hip: k_spin_spmv<SECTOR>, k_spin_measure<SECTOR>,
+// k_spin_site_apply<SECTOR>), shared by the
+// device code and by the host replays tests/cpp/spin_{model,sector,measure,site}_sanitize.cpp, which run it under AddressSanitizer +
 // UBSan.  The kernels and the replays call THESE functions, so what a replay proves about them (every load inside its array, the
 // state equal to spin_sector_unrank, the sums equal to the CSR row loop and to spin_measure_host bit for bit) holds for the
 // kernels' rows as compiled.  No device construct in here: plain C++11.  spin_write_rows, spin_sector_unrank, spin_sector_rank
@@ -114,6 +115,48 @@ EIGENEX_HD void spin_measure_flips(double xs, const bool* on, const double* xv, 
 EIGENEX_HD void spin_measure_diagonals(double xs, uint32_t s, const uint32_t* dmask, double* dg) {
   EIGENEX_UNROLL
   for (int t = 0; t < kSpinBatch; ++t) dg[t] = std::fma(spin_odd(~s & dmask[t]) ? -xs : xs, xs, dg[t]);
+}
+
+// ---- a sum of site operators (spin_site.hpp; kernels.hip: k_spin_site_apply<SECTOR>), one row of the DESTINATION per lane ----
+// The lane unranks its state s with the destination's n_up (spin_unrank_row).  Z is ALU work on the lane's own element
+// (spin_site_weight).  PLUS and MINUS take the sites kSpinBatch at a time in the three phases above: spin_site_targets,
+// spin_gather, spin_site_add.  The row has term i where bit i of `has` is set: has = s for PLUS (site i up in the row), ~s &
+// site_mask for MINUS (down).  The flipped state s ^ 1<<i belongs to the SOURCE geometry and is ranked through the source's
+// tables.  The fall-back of spin_flip_targets is not valid here: the lane's own state has the wrong number of up sites for those
+// tables, so their sum may lie outside x.  A lane without the term ranks `fallback` instead, the lowest state of the source
+// geometry: both table reads stay inside the tables, the row is 0, which every source vector has, no load is branched around,
+// and spin_site_add does not look at what was loaded.
+
+// w(s) of Z from the halved coefficients half[i] = c[i] * 0.5: plain additions of sign-flipped constants, sites ascending
+EIGENEX_HD double spin_site_weight(const double* half, int n_sites, uint32_t s) {
+  double w = 0.0;
+  for (int i = 0; i < n_sites; ++i) {
+    const double k = half[i];
+    w += ((s >> i) & 1u) ? k : -k;
+  }
+  return w;
+}
+
+// phase 1 of the sites i0 .. i0 + kSpinBatch - 1 (i0 a multiple of kSpinBatch below n_sites, so every shift is below 32; a site at
+// or above n_sites has no bit in `has`)
+template <bool SECTOR, class Tables>
+EIGENEX_HD void spin_site_targets(int i0, uint32_t s, uint32_t has, uint32_t fallback, const Tables& src_tab, int h, uint32_t lo_mask, bool* on,
+                                  uint32_t* base, uint32_t* low) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) {
+    const uint32_t bit = uint32_t(1) << (i0 + t);
+    on[t] = (has & bit) != 0;
+    const uint32_t s2 = on[t] ? s ^ bit : fallback;
+    base[t] = SECTOR ? src_tab.hi(s2 >> h) : s2;
+    low[t] = SECTOR ? src_tab.lo(s2 & lo_mask) : 0u;
+  }
+}
+
+// phase 3: one fma per term the row has, sites ascending; a lane without the term keeps its sum
+EIGENEX_HD double spin_site_add(double yr, const double* coef, const bool* on, const double* xv) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) yr = on[t] ? std::fma(coef[t], xv[t], yr) : yr;
+  return yr;
 }
 
 }  // namespace eigenex

@@ -1,0 +1,281 @@
+// Dynamical spin correlations of a state of a spin-1/2 model by the Lanczos continued fraction (E. R. Gagliano and C. A.
+// Balseiro, Phys. Rev. Lett. 59 (1987) 2999), matrix-free and without the start vector ever visiting the host.
+//
+// NOT part of the reference.  For a real state |v> over the rows of a SpinHalfModel (full space, or the sector of nUp sites up)
+// with energy E0, and O a sum of site operators (a kind and real coefficients c_i: sum_i c_i Sz_i, sum_i c_i S+_i or
+// sum_i c_i S-_i),
+//   S_O(w) = sum_n |<n| O |v>|^2 delta(w - (E_n - E0)) / <v|v>
+// compute() uploads v once, forms |phi> = O|v> on the device (eigenex_spin_site_apply) straight into the work vector of a
+// state on the DESTINATION operator -- S-_i takes the sector nUp to nUp - 1, S+_i to nUp + 1; the class builds that operator
+// itself --, runs m Lanczos steps from it in the library's default scheme and diagonalises the tridiagonal matrix
+// (small_eigen.hpp): T = S diag(theta) S^T.  Then
+//   poles()       p_n = theta_n - E0                  weights()   w_n = <phi|phi> / <v|v> * S(0, n)^2
+//   totalWeight() = sum_n w_n = <O^dagger O>          moment(k)   = sum_n w_n p_n^k   (exact for k < 2 m: Gauss quadrature)
+//   spectrum(w, eta) = sum_n w_n (eta / pi) / ((w - p_n)^2 + eta^2), the Lorentzian-broadened continued fraction
+// If O|v> = 0 -- or no larger than the roundings of the application can make an exact zero, |O v|^2 <= (L 2^-52 sum_i |c_i|)^2
+// <v|v>, as for sum_i Sz_i on a state of a sector with Sz = 0 when the partial sums of w(s) round -- the response is
+// identically zero: Success, no poles.  Otherwise |phi> is scaled to unit length on the device before the run.  A breakdown (an invariant subspace is exhausted before m
+// steps) ends the fraction where the state reports it; the poles are then exact.  Without setStateEnergy, E0 = <v|H|v> / <v|v>
+// from one operator application.
+//
+// computeStructureFactorZ(q) is Szz(q, w) for O = Sz_q = L^{-1/2} sum_r e^{iqr} Sz_r, the site index taken as position (as
+// SpinCorrelationSolver::structureFactorZ does).  Coefficients are real here, so it runs the cos part, c_i = L^{-1/2} cos(q i), and
+// the sin part, c_i = L^{-1/2} sin(q i), and merges their poles: for a real state and a real Hamiltonian the cross terms
+// <v|A (w - H)^{-1} B|v> - <v|B (w - H)^{-1} A|v> of O = A + iB cancel, so the response is the sum of the two real runs.  A part
+// whose O|v> is zero is skipped.  totalWeight() then equals the static structureFactorZ(q).
+//
+// Out of scope: complex coefficients in a single run; products of site operators as O; a basis-free three-term recurrence for
+// very long fractions (the run keeps m + 1 columns, like every Lanczos run here); more than one GPU (the matrix-free spin
+// operators are one shard); finite temperature.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "lanczos.hpp"
+#include "small_eigen.hpp"
+#include "spin_operator.hpp"
+
+namespace cmpt {
+namespace EigenEx {
+
+class SpinDynamicsSolver {
+ public:
+  using Index = EigenEx::Index;
+  using VectorType = DenseVector<double>;
+
+  static std::string headERROR() { return std::string("ERROR     "); }
+  static std::string headINFO() { return std::string("INFO      "); }
+
+  // nUp = -1: the full space (up to 30 sites); else the sector of nUp sites up (up to 32 sites, no transverse field)
+  SpinDynamicsSolver& setModel(const std::shared_ptr<device::Context>& ctx, const SpinHalfModel& model, int nUp = -1) {
+    ctx_ = ctx, model_ = model, nUp_ = nUp, haveModel_ = true;
+    srcDev_.release(), dstDev_.release();  // the states go before their operators
+    srcOp_.reset(), dstOp_.reset();
+    return *this;
+  }
+  // a host vector over the source rows, e.g. a column of a solver's eigenvectors(); it need not be normalised
+  SpinDynamicsSolver& setState(const VectorType& v) {
+    state_ = v;
+    return *this;
+  }
+  SpinDynamicsSolver& setStateEnergy(double E0) {
+    E0set_ = E0, haveE0_ = true;
+    return *this;
+  }
+  // kind: EIGENEX_SPIN_SITE_Z, _PLUS or _MINUS; coef: one real coefficient per site
+  SpinDynamicsSolver& setSiteOperator(int kind, const std::vector<double>& coef) {
+    kind_ = kind, coef_ = coef;
+    return *this;
+  }
+  SpinDynamicsSolver& setLanczosSteps(Index m) {
+    steps_ = m;
+    return *this;
+  }
+
+  Index compute() {
+    begin_("compute");
+    if (!prepare_(kind_, coef_)) return 0;
+    run_(kind_, coef_);
+    finish_();
+    return static_cast<Index>(poles_.size());
+  }
+
+  // Szz(q, w): the cos part and the sin part of Sz_q, merged (see the top of this file); the site operator that was set is not used
+  Index computeStructureFactorZ(double q) {
+    begin_("computeStructureFactorZ");
+    if (!haveModel_ || !ctx_) return invalid_("invalid input: no model (setModel)");
+    const int L = model_.sites();
+    if (L < 1) return invalid_("invalid input: the model has no sites");
+    std::vector<double> c(static_cast<std::size_t>(L), 0.0);
+    if (!prepare_(EIGENEX_SPIN_SITE_Z, c)) return 0;
+    const double scale = 1.0 / std::sqrt(static_cast<double>(L));
+    for (int part = 0; part < 2 && info_ == Success; ++part) {
+      for (int i = 0; i < L; ++i) c[static_cast<std::size_t>(i)] = scale * (part == 0 ? std::cos(q * i) : std::sin(q * i));
+      run_(EIGENEX_SPIN_SITE_Z, c);
+    }
+    finish_();
+    return static_cast<Index>(poles_.size());
+  }
+
+  // ---- results (after compute(); empty / zero after InvalidInput or a zero response) ----
+  const std::vector<double>& poles() const { return poles_; }      // ascending
+  const std::vector<double>& weights() const { return weights_; }
+  double totalWeight() const { return total_; }
+  double stateEnergy() const { return E0_; }
+  double stateNormSquared() const { return vv_; }
+  double spectrum(double omega, double eta) const {
+    const double pi = 3.14159265358979323846;
+    double s = 0.0;
+    for (std::size_t n = 0; n < poles_.size(); ++n) s += weights_[n] * (eta / pi) / ((omega - poles_[n]) * (omega - poles_[n]) + eta * eta);
+    return s;
+  }
+  double moment(int k) const {
+    double s = 0.0;
+    for (std::size_t n = 0; n < poles_.size(); ++n) s += weights_[n] * std::pow(poles_[n], k);
+    return s;
+  }
+  // the coefficients of the last Lanczos run (of the sin part after computeStructureFactorZ, if it ran)
+  const std::vector<double>& lanczosAlpha() const { return alpha_; }
+  const std::vector<double>& lanczosBeta() const { return beta_; }
+  int sites() const { return haveModel_ ? model_.sites() : 0; }
+  int sitesUp() const { return nUp_; }
+  ComputationInfo info() const { return info_; }
+  const std::vector<std::string>& log() const { return log_; }
+
+ private:
+  void begin_(const char* who) {
+    log_.clear();
+    log_.push_back(headINFO() + "SpinDynamicsSolver::" + who + "(...) was called");
+    info_ = Success;
+    poles_.clear(), weights_.clear(), alpha_.clear(), beta_.clear();
+    total_ = 0.0, E0_ = 0.0, vv_ = 0.0;
+  }
+  Index invalid_(const std::string& what) {
+    log_.push_back(headERROR() + what);
+    info_ = InvalidInput;
+    poles_.clear(), weights_.clear();
+    total_ = 0.0;
+    return 0;
+  }
+  static int dstUp_(int nUp, int kind) { return nUp < 0 || kind == EIGENEX_SPIN_SITE_Z ? nUp : (kind == EIGENEX_SPIN_SITE_PLUS ? nUp + 1 : nUp - 1); }
+  std::shared_ptr<device::CsrOperator> makeOperator_(int nUp) const {
+    return nUp < 0 ? device::spinHalfOperator(ctx_, model_) : device::spinHalfSectorOperator(ctx_, model_, nUp);
+  }
+
+  // checks, the source operator, the state on the device, <v|v> and E0; false after invalid_()
+  bool prepare_(int kind, const std::vector<double>& coef) {
+    if (!haveModel_ || !ctx_) return invalid_("invalid input: no model (setModel)"), false;
+    const int L = model_.sites();
+    if (kind != EIGENEX_SPIN_SITE_Z && kind != EIGENEX_SPIN_SITE_PLUS && kind != EIGENEX_SPIN_SITE_MINUS)
+      return invalid_("invalid input: no site operator (setSiteOperator: EIGENEX_SPIN_SITE_Z, _PLUS or _MINUS)"), false;
+    if (static_cast<int>(coef.size()) != L) return invalid_("invalid input: the site operator needs one coefficient per site"), false;
+    for (double c : coef)
+      if (!std::isfinite(c)) return invalid_("invalid input: a coefficient of the site operator is not finite"), false;
+    if (steps_ < 1) return invalid_("invalid input: setLanczosSteps needs at least one step"), false;
+    if (nUp_ >= 0 && (dstUp_(nUp_, kind) < 0 || dstUp_(nUp_, kind) > L))
+      return invalid_("invalid input: the site operator leaves the sectors of the model (S+ of the sector with every site up, S- of the one with none)"), false;
+    try {
+      if (!srcOp_) srcOp_ = makeOperator_(nUp_);
+    } catch (const LanczosException& e) {
+      return invalid_(std::string("invalid input: the model has no such operator: ") + e.what()), false;
+    }
+    const Index n = static_cast<Index>(srcOp_->rows());
+    if (state_.size() != n) return invalid_("invalid input: the state must have one entry per row of the model's space or sector (setState)"), false;
+    if (!srcDev_.alive()) srcDev_.create(ctx_, srcOp_, n, 1, 0, false);
+    srcDev_.upload(EIGENEX_VEC_COL(0), state_);
+    device::check(eigenex_spin_measure(srcDev_.handle(), EIGENEX_VEC_COL(0), 0, nullptr, 0, nullptr, nullptr, nullptr, &vv_), "eigenex_spin_measure");
+    if (!(vv_ > 0.0) || !std::isfinite(vv_)) return invalid_("invalid input: the state is zero (or not finite)"), false;
+    if (haveE0_) {
+      E0_ = E0set_;
+    } else {
+      double vHv = 0.0;
+      device::check(eigenex_apply(srcDev_.handle(), EIGENEX_VEC_COL(0), EIGENEX_VEC_V, 0.0, &vHv), "eigenex_apply");
+      E0_ = vHv / vv_;
+    }
+    return true;
+  }
+
+  // one continued fraction: |phi> = O|v> into the work vector of the destination state, m Lanczos steps, poles and weights appended
+  void run_(int kind, const std::vector<double>& coef) {
+    const int up = dstUp_(nUp_, kind);
+    std::shared_ptr<device::CsrOperator> want = up == nUp_ ? srcOp_ : (dstOp_ && dstOp_ != srcOp_ && dstUpBuilt_ == up ? dstOp_ : makeOperator_(up));
+    if (want != dstOp_) {
+      dstDev_.release();  // the state goes before its operator
+      dstOp_ = want;
+    }
+    dstUpBuilt_ = up;
+    const Index n = static_cast<Index>(dstOp_->rows());
+    const Index m = std::min<Index>(steps_, n);
+    const int cap = static_cast<int>(m + 1);
+    if (!dstDev_.alive() || dstDevOp_ != dstOp_.get() || dstDev_.capacity() < cap) {
+      dstDev_.create(ctx_, dstOp_, n, cap, 0, false);
+      dstDevOp_ = dstOp_.get();
+    } else {
+      device::check(eigenex_basis_clear(dstDev_.handle()), "eigenex_basis_clear");
+    }
+    double norm2 = 0.0;
+    device::check(eigenex_spin_site_apply(srcDev_.handle(), EIGENEX_VEC_COL(0), dstDev_.handle(), EIGENEX_VEC_W, kind, coef.data(), &norm2),
+                  "eigenex_spin_site_apply");
+    if (!std::isfinite(norm2)) {
+      log_.push_back(headERROR() + "O|v> is not finite");
+      info_ = NumericalIssue;
+      return;
+    }
+    // |y_r| <= L eps sum_i |c_i| |x| is what the roundings of the application alone can leave of an exact zero (Z: half of it)
+    double csum = 0.0;
+    for (double c : coef) csum += std::fabs(c);
+    const double noise = static_cast<double>(model_.sites()) * std::ldexp(1.0, -52) * csum * (kind == EIGENEX_SPIN_SITE_Z ? 0.5 : 1.0);
+    if (norm2 <= noise * noise * vv_) {
+      log_.push_back(headINFO() + (norm2 == 0.0 ? "O|v> = 0" : "O|v> vanishes within the rounding of its application") +
+                     ": this part of the response is identically zero");
+      return;
+    }
+    // the run starts from a unit vector, whatever the scale of the coefficients: its breakdown threshold is an absolute number
+    // (through v_, which the run overwrites with its first operator application: the scaling kernel is not an in-place one)
+    device::check(eigenex_scale(dstDev_.handle(), EIGENEX_VEC_V, EIGENEX_VEC_W, 1.0 / std::sqrt(norm2)), "eigenex_scale");
+    device::check(eigenex_vec_copy(dstDev_.handle(), EIGENEX_VEC_W, EIGENEX_VEC_V), "eigenex_vec_copy");
+    device::check(eigenex_lanczos_enqueue(dstDev_.handle(), static_cast<int>(m)), "eigenex_lanczos_enqueue");
+    eigenex_state_t st;
+    alpha_.assign(static_cast<std::size_t>(m) + 4, 0.0), beta_.assign(static_cast<std::size_t>(m) + 4, 0.0);
+    device::check(eigenex_lanczos_state(dstDev_.handle(), &st, alpha_.data(), beta_.data()), "eigenex_lanczos_state");
+    const int k = std::min<int>(st.nalpha, static_cast<int>(m));  // a breakdown leaves fewer: the fraction ends there
+    if (k < 1) {
+      log_.push_back(headERROR() + "the start vector O|v> failed the breakdown threshold of the Lanczos run");
+      info_ = NumericalIssue;
+      alpha_.clear(), beta_.clear();
+      return;
+    }
+    alpha_.resize(static_cast<std::size_t>(k)), beta_.resize(static_cast<std::size_t>(k - 1));
+    std::vector<double> theta, S;
+    if (!small_eigen::tridiagonal(alpha_.data(), beta_.data(), k, theta, &S)) {
+      log_.push_back(headERROR() + "the tridiagonal eigenproblem did not converge");
+      info_ = NumericalIssue;
+      return;
+    }
+    for (int j = 0; j < k; ++j) {
+      const double s0 = S[static_cast<std::size_t>(j) * static_cast<std::size_t>(k)];  // row 0 of column j
+      found_.push_back(std::make_pair(theta[static_cast<std::size_t>(j)] - E0_, norm2 / vv_ * s0 * s0));
+    }
+    parts_ += norm2 / vv_;
+    log_.push_back(headINFO() + "lanczos steps: " + std::to_string(k) + (st.stopped ? " (breakdown: the fraction is complete)" : "") +
+                   ", <O^dagger O> of this part: " + std::to_string(norm2 / vv_));
+  }
+
+  void finish_() {
+    if (info_ == Success) {
+      std::stable_sort(found_.begin(), found_.end(), [](const std::pair<double, double>& a, const std::pair<double, double>& b) { return a.first < b.first; });
+      for (const auto& pw : found_) poles_.push_back(pw.first), weights_.push_back(pw.second);
+      total_ = parts_;
+    }
+    found_.clear();
+    parts_ = 0.0;
+  }
+
+  std::shared_ptr<device::Context> ctx_;
+  SpinHalfModel model_;
+  bool haveModel_ = false, haveE0_ = false;
+  int nUp_ = -1, kind_ = -1, dstUpBuilt_ = -2;
+  std::vector<double> coef_;
+  VectorType state_;
+  Index steps_ = 100;
+  double E0set_ = 0.0;
+
+  std::shared_ptr<device::CsrOperator> srcOp_, dstOp_;
+  const device::CsrOperator* dstDevOp_ = nullptr;
+  detail::KrylovDevice srcDev_, dstDev_;
+
+  std::vector<std::pair<double, double>> found_;
+  double parts_ = 0.0;
+  std::vector<double> poles_, weights_, alpha_, beta_;
+  double total_ = 0.0, E0_ = 0.0, vv_ = 0.0;
+  ComputationInfo info_ = Success;
+  std::vector<std::string> log_;
+};
+
+}  // namespace EigenEx
+}  // namespace cmpt

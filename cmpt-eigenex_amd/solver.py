@@ -84,6 +84,25 @@ def lib():
             getattr(L, p + "energy_window").argtypes = [_vp, C.c_double, C.c_double, _dp]
             getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
             getattr(L, p + "log_line").restype = C.c_char_p
+        p = "eigenex_spin_dynamics_solver_"
+        _ip32 = C.POINTER(C.c_int32)
+        getattr(L, p + "create").restype = _vp
+        getattr(L, p + "destroy").argtypes = [_vp]
+        getattr(L, p + "destroy").restype = None
+        getattr(L, p + "set_model").argtypes = [_vp, _vp, C.c_int, C.c_int, _ip32, _ip32, _dp, _dp, _dp, _dp, C.c_int]
+        getattr(L, p + "set_state").argtypes = [_vp, _dp, C.c_int64]
+        getattr(L, p + "set_state_energy").argtypes = [_vp, C.c_double]
+        getattr(L, p + "set_site_operator").argtypes = [_vp, C.c_int, _dp, C.c_int]
+        getattr(L, p + "set_lanczos_steps").argtypes = [_vp, C.c_int64]
+        getattr(L, p + "compute").argtypes = [_vp]
+        getattr(L, p + "compute_structure_factor_z").argtypes = [_vp, C.c_double]
+        getattr(L, p + "sizes").argtypes = [_vp, _lp]
+        getattr(L, p + "get").argtypes = [_vp, _dp, _dp, _dp, _dp, _dp]
+        getattr(L, p + "spectrum").argtypes = [_vp, _dp, C.c_int64, C.c_double, _dp]
+        getattr(L, p + "moment").argtypes = [_vp, C.c_int, _dp]
+        getattr(L, p + "static_structure_factor_z").argtypes = [_vp, C.c_double, _dp]
+        getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
+        getattr(L, p + "log_line").restype = C.c_char_p
         for kind in FAMILIES:
             p = f"eigenex_{kind}_solver_"
             getattr(L, p + "create").restype = _vp
@@ -610,3 +629,103 @@ class SpectralDensitySolver(_SolverBase):
         d = C.c_double()
         _chk(self._f("energy_window")(self.h, tau, count, C.byref(d)))
         return d.value
+
+
+class SpinDynamicsSolver:
+    """SpinDynamicsSolver (spin_dynamics.hpp): dynamical spin correlations of a state by the Lanczos continued fraction.  The
+    model is (n_sites, bonds, hz, hx) with bonds = [(i, j, Jz, Jxy), ...]; n_up = None: the full space."""
+
+    _names = ("npoles", "nalpha", "nbeta", "nlog", "info")
+
+    def __init__(self):
+        self._L = lib()
+        self.h = _vp(self._L.eigenex_spin_dynamics_solver_create())
+        if not self.h:
+            raise capi.EigenexError("solver create failed")
+        self._keep = []
+
+    def _f(self, name):
+        return getattr(self._L, "eigenex_spin_dynamics_solver_" + name)
+
+    def setModel(self, ctx: capi.Context, n_sites, bonds, hz=None, hx=None, n_up=None):
+        i32 = C.POINTER(C.c_int32)
+        si = np.ascontiguousarray([b[0] for b in bonds], np.int32)
+        sj = np.ascontiguousarray([b[1] for b in bonds], np.int32)
+        jz = np.ascontiguousarray([b[2] for b in bonds], np.float64)
+        jxy = np.ascontiguousarray([b[3] for b in bonds], np.float64)
+        fz = None if hz is None else np.ascontiguousarray(hz, np.float64)
+        fx = None if hx is None else np.ascontiguousarray(hx, np.float64)
+        self._keep.append(ctx)
+        _chk(self._f("set_model")(self.h, ctx.h, int(n_sites), si.size, si.ctypes.data_as(i32), sj.ctypes.data_as(i32), _d(jz), _d(jxy),
+                                  None if fz is None else _d(fz), None if fx is None else _d(fx), -1 if n_up is None else int(n_up)))
+        return self
+
+    def setState(self, v):
+        a = np.ascontiguousarray(v, np.float64)
+        _chk(self._f("set_state")(self.h, _d(a), a.size))
+        return self
+
+    def setStateEnergy(self, E0):
+        _chk(self._f("set_state_energy")(self.h, float(E0)))
+        return self
+
+    def setSiteOperator(self, kind, coef):
+        a = np.ascontiguousarray(coef, np.float64)
+        _chk(self._f("set_site_operator")(self.h, int(kind), _d(a), a.size))
+        return self
+
+    def setLanczosSteps(self, m):
+        _chk(self._f("set_lanczos_steps")(self.h, int(m)))
+        return self
+
+    def compute(self):
+        _chk(self._f("compute")(self.h))
+        return self
+
+    def computeStructureFactorZ(self, q):
+        _chk(self._f("compute_structure_factor_z")(self.h, float(q)))
+        return self
+
+    def _sizes(self):
+        out = np.zeros(len(self._names), np.int64)
+        _chk(self._f("sizes")(self.h, out.ctypes.data_as(_lp)))
+        return dict(zip(self._names, (int(x) for x in out)))
+
+    def results(self):
+        s = self._sizes()
+        poles, weights, alpha, beta, sc = np.zeros(s["npoles"]), np.zeros(s["npoles"]), np.zeros(s["nalpha"]), np.zeros(s["nbeta"]), np.zeros(3)
+        _chk(self._f("get")(self.h, _d(poles), _d(weights), _d(alpha), _d(beta), _d(sc)))
+        s.update(poles=poles, weights=weights, lanczosAlpha=alpha, lanczosBeta=beta, totalWeight=sc[0], stateEnergy=sc[1],
+                 stateNormSquared=sc[2], info_name=INFO[s["info"]])
+        return s
+
+    def spectrum(self, omega, eta):
+        w = np.ascontiguousarray(np.atleast_1d(omega), np.float64)
+        out = np.zeros(w.size)
+        _chk(self._f("spectrum")(self.h, _d(w), w.size, float(eta), _d(out)))
+        return out
+
+    def moment(self, k):
+        m = C.c_double()
+        _chk(self._f("moment")(self.h, int(k), C.byref(m)))
+        return m.value
+
+    def staticStructureFactorZ(self, q):
+        """SpinCorrelationSolver::structureFactorZ(q) of the same model and state"""
+        v = C.c_double()
+        _chk(self._f("static_structure_factor_z")(self.h, float(q), C.byref(v)))
+        return v.value
+
+    def log(self):
+        return [self._f("log_line")(self.h, i).decode() for i in range(self._sizes()["nlog"])]
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -333,6 +333,36 @@ int eigenex_spin_measure_host(int n_sites, int n_up /* -1: full space */, const 
                               const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks, double* diag_out,
                               double* flip_out, double* norm2);
 int eigenex_spin_geometry(eigenex_csr_t csr, int* n_sites, int* n_up);
+/* A sum of single-site spin operators applied to a real vector, y = O x: the start vector of a dynamical correlation function
+ * (Lanczos continued fraction) formed on the device, also where O changes the magnetisation.  NOT part of the reference.  O is a
+ * kind and n_sites real coefficients c[i]; x lives on the rows of the source geometry (n_sites, n_up_src; n_up = -1: the full
+ * space), y on the destination's.  With sigma_i(s) as above:
+ *   EIGENEX_SPIN_SITE_Z      O = sum_i c[i] Sz_i.  y_r = w(s_r) * x_r;  w(s) = 0.0, then for i ascending
+ *                            w += sigma_i(s) > 0 ? +(c[i] * 0.5) : -(c[i] * 0.5)  -- plain additions of sign-flipped constants, as
+ *                            for the operator's diagonal.  The destination geometry equals the source's.
+ *   EIGENEX_SPIN_SITE_PLUS   O = sum_i c[i] S+_i.  Destination: the sector n_up_src + 1; the full space for the full space.  Row
+ *                            t of the destination, with state s_t:  y_t = 0.0, then for i ascending with site i up in s_t
+ *                            y_t = fma(c[i], x[row_src(s_t ^ 1<<i)], y_t)
+ *   EIGENEX_SPIN_SITE_MINUS  O = sum_i c[i] S-_i: the same with "site i down in s_t".  Destination: the sector n_up_src - 1.
+ *   norm2 = sum_r y_r^2 comes with every call (host: one fma per row, rows ascending; device: per-workgroup partial sums added in a
+ *   fixed order, no atomics, bit-reproducible from run to run); it may be NULL.
+ * Errors (EIGENEX_ERR_ARG, message in eigenex_last_error): a kind out of range, a coefficient that is not finite, a destination
+ * sector outside 0..n_sites (S+ of the all-up sector, S- of the all-down one), geometries that do not belong together.
+ *   eigenex_spin_site_apply       src and dst are states on the SAME context whose operator handles came from eigenex_spin_upload
+ *                                 or eigenex_spin_sector_upload and whose geometries (eigenex_spin_geometry) fit the kind; dst may
+ *                                 be src.  x_ref is a vector of src, y_ref one of dst; y_ref = EIGENEX_VEC_W of dst is the intended
+ *                                 use: that is where a Lanczos run takes its start vector.  For Z, y may be x (in place); for PLUS
+ *                                 and MINUS y == x (dst == src in the full space) is refused: the gather reads what it writes.
+ *                                 Runs on the context's stream and synchronises once; touches no coefficient, counter or recorded
+ *                                 step batch of either state.  Any other operator, a host callback or two different contexts:
+ *                                 EIGENEX_ERR_STATE.  Everything is checked before anything is allocated.
+ *   eigenex_spin_site_apply_host  the definition the kernel is held against, in host code: no context, no GPU.  x has the source's
+ *                                 rows (2^n_sites, n_sites 2..30; or C(n_sites, n_up_src), n_sites 2..32), y the destination's. */
+enum { EIGENEX_SPIN_SITE_Z = 0, EIGENEX_SPIN_SITE_PLUS = 1, EIGENEX_SPIN_SITE_MINUS = 2 };
+int eigenex_spin_site_apply(eigenex_basis_t src, int x_ref, eigenex_basis_t dst, int y_ref, int kind,
+                            const double* coef /* n_sites */, double* norm2 /* or NULL */);
+int eigenex_spin_site_apply_host(int n_sites, int n_up_src /* -1: full space */, int kind, const double* coef,
+                                 const double* x, double* y, double* norm2);
 /* CSR that already lives in device memory of this context's GPU (e.g. tensors of a GPU framework: pass their
  * data pointers): copied device-to-device, never through the host, after a device-side check of the row pointers
  * and column indices.  Unsharded contexts only; rowptr_dev[0] = 0; columns are global = local indices. */
