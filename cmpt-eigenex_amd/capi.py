@@ -112,6 +112,9 @@ SIGNATURES = {
     "eigenex_spin_geometry": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "eigenex_spin_site_apply": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _dp, _dp]),
     "eigenex_spin_site_apply_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "eigenex_spin_rdm_layout": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int), _lp, _lp]),
+    "eigenex_spin_rdm": (C.c_int, [_vp, C.c_int, C.c_uint32, _dp, C.c_int64]),
+    "eigenex_spin_rdm_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_uint32, _dp, C.c_int64]),
     "eigenex_basis_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_create_ex": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_is_complex": (C.c_int, [_vp, C.POINTER(C.c_int)]),
@@ -355,6 +358,34 @@ def spin_measure_host(n_sites: int, n_up, x, diag_masks, flip_masks):
     _chk(lib().eigenex_spin_measure_host(int(n_sites), -1 if n_up is None else int(n_up), _d(x), nd, dp, nf, fp, _d(diag) if nd else None,
                                          _d(flip) if nf else None, C.byref(norm2)))
     return diag, flip, norm2.value
+
+
+def spin_rdm_layout(n_sites: int, n_up, mask_a: int):
+    """eigenex_spin_rdm_layout: (k_first, dims, offsets) of the reduced density matrix of the subsystem mask_a -- block n has k_first
+    + n up sites inside the subsystem (one block, k_first = 0, in the full space: n_up = None), dims[n] rows and starts at offsets[n]
+    of the packed output, whose length is offsets[-1].  Host code, no GPU."""
+    nb, kf = C.c_int(), C.c_int()
+    dims, offs = np.zeros(33, np.int64), np.zeros(34, np.int64)
+    _chk(lib().eigenex_spin_rdm_layout(int(n_sites), -1 if n_up is None else int(n_up), int(mask_a), C.byref(nb), C.byref(kf),
+                                       dims.ctypes.data_as(_lp), offs.ctypes.data_as(_lp)))
+    return kf.value, [int(d) for d in dims[: nb.value]], [int(o) for o in offs[: nb.value + 1]]
+
+
+def _rdm_blocks(k_first, dims, offsets, out):
+    """the packed column-major blocks as [(k, ndarray(d, d)), ...] (copies)"""
+    return [(k_first + n, out[offsets[n] : offsets[n + 1]].reshape(d, d).T.copy()) for n, d in enumerate(dims)]
+
+
+def spin_rdm_host(n_sites: int, n_up, x, mask_a: int):
+    """eigenex_spin_rdm_host: the raw, unnormalised reduced density matrix of the subsystem mask_a of the real vector x as a list
+    of (k, ndarray(d_k, d_k)), in host code (no GPU).  n_up = None: the full space (one block, k = 0)."""
+    x = np.ascontiguousarray(x, np.float64)
+    kf, dims, offs = spin_rdm_layout(n_sites, n_up, mask_a)
+    if x.size != (1 << int(n_sites) if n_up is None else spin_sector_dim(n_sites, n_up)):  # the library cannot see the length
+        raise EigenexError("spin_rdm_host: x must have one entry per row of the geometry")
+    out = np.zeros(offs[-1])
+    _chk(lib().eigenex_spin_rdm_host(int(n_sites), -1 if n_up is None else int(n_up), _d(x), int(mask_a), _d(out), out.size))
+    return _rdm_blocks(kf, dims, offs, out)
 
 
 def spin_site_apply_host(n_sites: int, n_up, kind: int, coef, x):
@@ -772,6 +803,22 @@ class Basis:
         diag, flip, norm2 = np.zeros(nd), np.zeros(nf), C.c_double()
         _chk(lib().eigenex_spin_measure(self.h, x_ref, nd, dp, nf, fp, _d(diag) if nd else None, _d(flip) if nf else None, C.byref(norm2)))
         return diag, flip, norm2.value
+
+    def spin_rdm(self, x_ref, mask_a):
+        """eigenex_spin_rdm: the raw, unnormalised reduced density matrix of the subsystem mask_a of the vector x_ref, formed on
+        the device, as a list of (k, ndarray(d_k, d_k)); the operator of this state must be a matrix-free spin operator.  No
+        vector and no coefficient changes."""
+        ns, nu = C.c_int(), C.c_int()
+        if self.csr is None or lib().eigenex_spin_geometry(self.csr.h, C.byref(ns), C.byref(nu)) != 0:
+            _chk(lib().eigenex_spin_rdm(self.h, x_ref, int(mask_a), None, 0))  # the library says what is wrong with the state
+        try:
+            kf, dims, offs = spin_rdm_layout(ns.value, None if nu.value < 0 else nu.value, mask_a)
+        except EigenexError:
+            _chk(lib().eigenex_spin_rdm(self.h, x_ref, int(mask_a), None, 0))  # the same refusal under the entry point's own name
+            raise
+        out = np.zeros(offs[-1])
+        _chk(lib().eigenex_spin_rdm(self.h, x_ref, int(mask_a), _d(out), out.size))
+        return _rdm_blocks(kf, dims, offs, out)
 
     def spin_site_apply(self, x_ref, dst, y_ref, kind, coef):
         """eigenex_spin_site_apply: vector y_ref of the state dst = (sum of site operators kind, coef) applied to vector x_ref of

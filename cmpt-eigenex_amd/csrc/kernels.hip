@@ -1822,6 +1822,137 @@ __global__ __launch_bounds__(kBlock) void k_spin_site_apply(const SpinSiteTable*
   if (threadIdx.x == 0) partials[blockIdx.x] = nrm;
 }
 
+// ---------------------------------------------------------------------------
+// The reduced density matrix of one vector (spin_rdm.hpp has the definition, the work table and the slicing rule;
+// spin_rdm_rows.hpp the index arithmetic): rho_A = M M^T with M[a, b] = x[rank(dep_A(a) | dep_B(b))] never stored.  One
+// workgroup per work item (block k, tile pair (ti, tj <= ti), slice of the b range).  Per chunk of CHUNK b's the workgroup
+//   1. forms the states dep_B(b) once (LDS binomials, spin_rdm_party_state with (nB, n_up - k)); the states dep_A(a) of its
+//      TILE rows (and of the other tile's rows) were formed once per item;
+//   2. gathers the TILE x CHUNK panel of x into LDS, one panel for a diagonal pair, two otherwise: 8 loads per lane, all issued
+//      before the first is stored (spin_rdm_element: a padded lane loads row 0 and stores 0).  Panels are b-major with a pitch of
+//      TILE + 2 doubles: a lane's four rows are two 16-byte LDS reads, and a gather whose b's run along the lanes is a 4-way
+//      bank conflict on its stores, not a 64-way one;
+//   3. accumulates in registers by plain fp64 fma, a 4 x 4 register tile per lane: TILE = 64 is 16 x 16 lanes that each take every
+//      b of the chunk; TILE = 16 is 4 x 4 lanes per group and kSpinRdmSmallGroups groups that take the chunk's b's round robin
+//      (b = group, group + 16, ...) and whose tiles are added in ascending group order through LDS at the end.
+// Each entry i >= j of the tile is written by one lane to this slice's partials; k_spin_rdm_reduce adds the slices.  No atomics:
+// a result depends on the grid only through the number of slices.  ctrl->stopped is not consulted: this is not a Krylov step.
+// ---------------------------------------------------------------------------
+template <bool SECTOR, int TILE>
+__global__ __launch_bounds__(kBlock) void k_spin_rdm(const SpinRdmTable* __restrict__ tb, const SpinRdmItem* __restrict__ items,
+                                                     const SpinSectorView* __restrict__ op, const uint32_t* __restrict__ lo_rank,
+                                                     const uint32_t* __restrict__ hi_base, const double* __restrict__ x,
+                                                     double* __restrict__ partials) {
+  constexpr int CHUNK = TILE == kSpinRdmBigTile ? kSpinRdmBigChunk : kSpinRdmSmallChunk;
+  constexpr int GROUPS = TILE == kSpinRdmBigTile ? 1 : kSpinRdmSmallGroups;
+  constexpr int SIDE = TILE / 4, PITCH = TILE + 2, LOADS = TILE * CHUNK / kBlock;
+  static_assert(SIDE * SIDE * GROUPS == kBlock && TILE * CHUNK % kBlock == 0 && CHUNK <= kBlock && CHUNK % GROUPS == 0, "tile shape");
+  static_assert(GROUPS == 1 || TILE * TILE == kBlock, "the group sums are added by one lane per entry");
+  constexpr int PANEL = CHUNK * PITCH;
+  __shared__ __attribute__((aligned(16))) double panel[(GROUPS == 1 ? 2 : 1) * PANEL];  // a 16-row block has one tile: no second panel
+  __shared__ double red[GROUPS > 1 ? GROUPS * TILE * TILE : 1];
+  __shared__ uint32_t sa_i[TILE], sa_j[TILE], sb[CHUNK];
+  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
+  int h = 0;
+  uint32_t lo_mask = 0;
+  if constexpr (SECTOR) {
+    spin_stage_binomials(op, binom);
+    __syncthreads();
+    h = op->h, lo_mask = op->lo_mask;
+  }
+  const SpinRdmItem it = items[blockIdx.x];
+  const SpinRdmBlock* bk = tb->block + it.block;
+  const int d = bk->d, k = bk->k, nA = tb->nA, nB = tb->nB, kb = tb->n_up - k;
+  const uint32_t mask_a = tb->mask_a, mask_b = tb->mask_b, fallback = tb->fallback;
+  const bool along_a = TILE == kSpinRdmBigTile && tb->along_a != 0, diagonal = it.ti == it.tj;
+  const int i0 = it.ti * TILE, j0 = it.tj * TILE;
+  const int tid = threadIdx.x;
+  const SpinBinomials32 bin{binom};
+  const SpinRankTables tab{lo_rank, hi_base};
+  const SpinVector xv{x};
+  if (tid < TILE) {
+    sa_i[tid] = spin_rdm_party_state<SECTOR>(bin, nA, k, mask_a, (uint32_t)(i0 + tid), i0 + tid < d);
+    sa_j[tid] = spin_rdm_party_state<SECTOR>(bin, nA, k, mask_a, (uint32_t)(j0 + tid), j0 + tid < d);
+  }
+  const int group = tid / (SIDE * SIDE), tx = tid % SIDE, ty = tid % (SIDE * SIDE) / SIDE;
+  const int other = diagonal || GROUPS > 1 ? 0 : PANEL;  // where the rows a_j of the pair lie: a diagonal pair has one panel
+  double acc[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[r][c] = 0.0;
+  for (uint32_t b0 = it.b_begin; b0 < it.b_end; b0 += CHUNK) {
+    __syncthreads();  // sa_i and sa_j are written; the last chunk's panels are read
+    if (tid < CHUNK) sb[tid] = spin_rdm_party_state<SECTOR>(bin, nB, kb, mask_b, b0 + tid, tid < it.b_end - b0);
+    __syncthreads();
+    double va[LOADS], vb[LOADS];
+#pragma unroll
+    for (int q = 0; q < LOADS; ++q) {
+      int row, bj;
+      spin_rdm_panel_slot(along_a, TILE, CHUNK, q * kBlock + tid, &row, &bj);
+      const bool live_b = (uint32_t)bj < it.b_end - b0;
+      va[q] = spin_rdm_element<SECTOR>(tab, xv, h, lo_mask, sa_i[row], sb[bj], live_b && i0 + row < d, fallback);
+      if (other != 0) vb[q] = spin_rdm_element<SECTOR>(tab, xv, h, lo_mask, sa_j[row], sb[bj], live_b && j0 + row < d, fallback);
+    }
+#pragma unroll
+    for (int q = 0; q < LOADS; ++q) {
+      int row, bj;
+      spin_rdm_panel_slot(along_a, TILE, CHUNK, q * kBlock + tid, &row, &bj);
+      panel[bj * PITCH + row] = va[q];
+      if (other != 0) panel[other + bj * PITCH + row] = vb[q];
+    }
+    __syncthreads();
+    for (int bj = group; bj < CHUNK; bj += GROUPS) {
+      double a[4], b[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) a[r] = panel[bj * PITCH + 4 * tx + r], b[r] = panel[other + bj * PITCH + 4 * ty + r];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = fma(a[r], b[c], acc[r][c]);
+    }
+  }
+  double* out = partials + bk->part_offset + (int64_t)it.slice * d * d;
+  if constexpr (GROUPS == 1) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int i = i0 + 4 * tx + r, j = j0 + 4 * ty + c;
+        if (i < d && j < d && i >= j) out[i + (int64_t)j * d] = acc[r][c];
+      }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) red[group * TILE * TILE + (4 * ty + c) * TILE + 4 * tx + r] = acc[r][c];
+    __syncthreads();
+    double sum = 0.0;
+    for (int g = 0; g < GROUPS; ++g) sum += red[g * TILE * TILE + tid];
+    const int i = i0 + tid % TILE, j = j0 + tid / TILE;
+    if (i < d && j < d && i >= j) out[i + (int64_t)j * d] = sum;
+  }
+}
+
+// Second stage of k_spin_rdm, one lane per entry of the packed output: the lane of an entry i >= j adds the block's slices in
+// ascending order with plain adds and writes (i, j) and (j, i) from the same value; the lane of an entry i < j writes nothing.
+__global__ __launch_bounds__(kBlock) void k_spin_rdm_reduce(const SpinRdmTable* __restrict__ tb, const double* __restrict__ partials,
+                                                            double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= tb->total) return;
+  int n = 0;
+  while (n + 1 < tb->n_blocks && e >= tb->block[n + 1].out_offset) ++n;
+  const SpinRdmBlock* bk = tb->block + n;
+  const int64_t d = bk->d, local = e - bk->out_offset;
+  const int64_t i = local % d, j = local / d;
+  if (i < j) return;
+  const double* p = partials + bk->part_offset + i + j * d;
+  double sum = 0.0;
+  for (int s = 0; s < bk->nslices; ++s) sum += p[(int64_t)s * d * d];
+  out[bk->out_offset + i + j * d] = sum;
+  out[bk->out_offset + j + i * d] = sum;
+}
+
 // complex blocks: entries, input and sums are (re, im) pairs; products without contraction and added part by
 // part, exactly like k_spmv_z
 template <int NB, bool STAGED>
@@ -2770,6 +2901,18 @@ void launch_spin_site_apply(hipStream_t s, const SpinSiteTable* table, const Spi
                             const uint32_t* src_hi, const double* x, double* y, int64_t n, double* partials, int grid) {
   const auto kernel = src_lo ? k_spin_site_apply<true> : k_spin_site_apply<false>;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, table, dst_op, src_lo, src_hi, x, y, n, (n + kBlock - 1) / kBlock, partials);
+}
+
+void launch_spin_rdm(hipStream_t s, bool big, const SpinRdmTable* table, const SpinRdmItem* items, int n_items, const SpinSectorView* op,
+                     const uint32_t* lo_rank, const uint32_t* hi_base, const double* x, double* partials) {
+  if (n_items <= 0) return;
+  const auto kernel = big ? (lo_rank ? k_spin_rdm<true, kSpinRdmBigTile> : k_spin_rdm<false, kSpinRdmBigTile>)
+                          : (lo_rank ? k_spin_rdm<true, kSpinRdmSmallTile> : k_spin_rdm<false, kSpinRdmSmallTile>);
+  hipLaunchKernelGGL(kernel, dim3(n_items), dim3(kBlock), 0, s, table, items, op, lo_rank, hi_base, x, partials);
+}
+
+void launch_spin_rdm_reduce(hipStream_t s, const SpinRdmTable* table, int64_t total, const double* partials, double* out) {
+  hipLaunchKernelGGL(k_spin_rdm_reduce, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, table, partials, out);
 }
 
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,

@@ -7,6 +7,7 @@
 #include "lag_terms.hpp"
 #include "row_codes.hpp"
 #include "spin_measure.hpp"
+#include "spin_rdm.hpp"
 #include "spin_model.hpp"
 #include "spin_rows.hpp"
 #include "spin_sector.hpp"
@@ -363,6 +364,15 @@ void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstri
 // stage is launch_spin_measure_reduce(s, partials, grid, grid, 0, 0, nullptr, nullptr, norm_out).  Always runs.
 void launch_spin_site_apply(hipStream_t s, const SpinSiteTable* table, const SpinSectorView* dst_op, const uint32_t* src_lo,
                             const uint32_t* src_hi, const double* x, double* y, int64_t n, double* partials, int grid);
+// The reduced density matrix of x over the rows of a matrix-free spin operator (eigenex_spin_rdm; spin_rdm.hpp has the definition
+// and the work table): one workgroup per item, n_items of them, with 64-row tiles (big) or one 16-row tile; table, items, op,
+// lo_rank and hi_base live in device memory (full space: null tables, op is not read).  x is only read; slice s of a block writes
+// the entries i >= j of its tile to partials[block.part_offset + s * d * d + i + j * d].  Always runs.
+void launch_spin_rdm(hipStream_t s, bool big, const SpinRdmTable* table, const SpinRdmItem* items, int n_items, const SpinSectorView* op,
+                     const uint32_t* lo_rank, const uint32_t* hi_base, const double* x, double* partials);
+// its second stage: every entry i >= j of every block is the sum of its slices in ascending order, written to (i, j) and (j, i)
+// of out (table->total doubles, `total` on the host)
+void launch_spin_rdm_reduce(hipStream_t s, const SpinRdmTable* table, int64_t total, const double* partials, double* out);
 // host-operator path: u_out = x*scale
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,
                   const Ctrl* ctrl);

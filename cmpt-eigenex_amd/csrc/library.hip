@@ -3178,6 +3178,69 @@ int eigenex_spin_site_apply(eigenex_basis_t src, int x_ref, eigenex_basis_t dst,
   return 0;
 }
 
+int eigenex_spin_rdm_layout(int n_sites, int n_up, uint32_t mask_a, int* n_blocks, int* k_first, int64_t* dims, int64_t* offsets) {
+  const SpinRdmArgs a{n_sites, n_up, mask_a};
+  if (const char* why = spin_rdm_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_rdm_layout: ") + why);
+  SpinRdmLayout l;
+  spin_rdm_layout(a, l);
+  if (n_blocks) *n_blocks = l.n_blocks;
+  if (k_first) *k_first = l.k_first;
+  for (int n = 0; n < l.n_blocks && dims; ++n) dims[n] = l.dims[n];
+  for (int n = 0; n <= l.n_blocks && offsets; ++n) offsets[n] = l.offsets[n];
+  return 0;
+}
+
+int eigenex_spin_rdm_host(int n_sites, int n_up, const double* x, uint32_t mask_a, double* out, int64_t out_len) {
+  const SpinRdmArgs a{n_sites, n_up, mask_a};
+  if (const char* why = spin_rdm_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_rdm_host: ") + why);
+  if (!x || !out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_host: x or out is NULL");
+  SpinRdmLayout l;
+  spin_rdm_layout(a, l);
+  if (out_len != l.offsets[l.n_blocks]) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_host: out_len is not the length eigenex_spin_rdm_layout gives");
+  spin_rdm_host(a, x, out);
+  return 0;
+}
+
+int eigenex_spin_rdm(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out, int64_t out_len) {
+  if (!b) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm: basis is NULL");
+  if (!spin_state_shard(b))
+    return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_rdm: the operator of this state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
+                                          : "eigenex_spin_rdm: the state has no device operator (a host callback knows no sites)");
+  BasisShard& s = *spin_state_shard(b);
+  const SpinShard& m = s.csr->spin;
+  const SpinRdmArgs a{m.n_sites, m.n_up, mask_a};
+  if (const char* why = spin_rdm_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_rdm: ") + why);
+  if (!out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm: out is NULL");
+  SpinRdmPlan plan;
+  spin_rdm_build_plan(a, s.g_spmv, plan);
+  const SpinRdmTable& t = plan.table;
+  if (out_len != t.total) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm: out_len is not the length eigenex_spin_rdm_layout gives");
+  const double* x = vec_ptr(s, b->cap, b->nq, x_ref);
+  if (!x) return fail(EIGENEX_ERR_ARG, "bad vector reference");
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  // scratch of this call alone: the work table (header, then the items of the two tile sizes), the slices' partial sums and the
+  // packed result.  The state's own partials may hold a pending alpha.
+  const size_t nbig = plan.big.size(), nsmall = plan.small.size();
+  std::vector<SpinRdmItem> items(plan.big);
+  items.insert(items.end(), plan.small.begin(), plan.small.end());
+  DeviceBuffer<SpinRdmTable> d_table;
+  DeviceBuffer<SpinRdmItem> d_items;
+  DeviceBuffer<double> d_part, d_out;
+  HIPCHK(d_table.alloc(1));
+  HIPCHK(d_items.alloc(items.size()));
+  HIPCHK(d_part.alloc((size_t)t.part_total));
+  HIPCHK(d_out.alloc((size_t)t.total));
+  HIPCHK(hipMemcpyAsync(d_table, &t, sizeof(SpinRdmTable), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_items, items.data(), sizeof(SpinRdmItem) * items.size(), hipMemcpyHostToDevice, c->stream));
+  launch_spin_rdm(c->stream, true, d_table, d_items, (int)nbig, m.view, m.lo, m.hi, x, d_part);
+  launch_spin_rdm(c->stream, false, d_table, d_items + nbig, (int)nsmall, m.view, m.lo, m.hi, x, d_part);
+  launch_spin_rdm_reduce(c->stream, d_table, t.total, d_part, d_out);
+  HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)t.total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the table and the scratch live until here
+  return 0;
+}
+
 int eigenex_csr_layout(eigenex_csr_t m, int* layout) {
   if (!m || !layout) return fail(EIGENEX_ERR_ARG, "eigenex_csr_layout: NULL argument");
   *layout = EIGENEX_LAYOUT_CSR;

@@ -11,7 +11,7 @@
 //   eigenex_zarnoldi_solver_*  ArnoldiEigenSolver<std::complex<double>>
 // plus eigenex_[z]trlanczos_solver_* (ThickRestartLanczosEigenSolver), eigenex_[z]kschur_solver_* (KrylovSchurEigenSolver) and
 // eigenex_[z]flanczos_solver_* (FilteredLanczosEigenSolver); eigenex_[z]density_solver_* (SpectralDensitySolver);
-// eigenex_spin_dynamics_solver_* (SpinDynamicsSolver).
+// eigenex_spin_dynamics_solver_* (SpinDynamicsSolver); eigenex_spin_entanglement_solver_* (SpinEntanglementSolver).
 // Complex data cross this boundary as interleaved (re, im) doubles.
 #include <complex>
 #include <cstring>
@@ -28,6 +28,7 @@
 #include "cmpt/eigen_ex/spectral_density.hpp"
 #include "cmpt/eigen_ex/spin_correlations.hpp"
 #include "cmpt/eigen_ex/spin_dynamics.hpp"
+#include "cmpt/eigen_ex/spin_entanglement.hpp"
 #include "cmpt/eigen_ex/thick_restart_lanczos.hpp"
 #include "cmpt/eigen_ex/triplets_operator.hpp"
 
@@ -938,6 +939,79 @@ int eigenex_spin_dynamics_solver_static_structure_factor_z(void* p, double q, do
 }
 const char* eigenex_spin_dynamics_solver_log_line(void* p, int64_t i) {
   auto& log = static_cast<SpinDynamicsBox*>(p)->es.log();
+  return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
+}
+
+// ---- SpinEntanglementSolver (spin_entanglement.hpp).  The operator crosses as a handle of eigenex_spin_upload / eigenex_spin_sector_upload.
+struct SpinEntanglementBox {
+  std::shared_ptr<device::Context> ctx;
+  std::shared_ptr<device::CsrOperator> op;
+  DenseVector<double> state;
+  SpinEntanglementSolver es;
+};
+void* eigenex_spin_entanglement_solver_create(void) {
+  try {
+    return new SpinEntanglementBox();
+  } catch (const std::exception& e) {
+    g_serr = e.what();
+    return nullptr;
+  }
+}
+void eigenex_spin_entanglement_solver_destroy(void* p) { delete static_cast<SpinEntanglementBox*>(p); }
+int eigenex_spin_entanglement_solver_set_device_operator(void* p, eigenex_context_t ctx, eigenex_csr_t csr) {
+  return guard([&] {
+    auto* b = static_cast<SpinEntanglementBox*>(p);
+    b->ctx = device::Context::borrow(ctx);
+    b->op = device::CsrOperator::borrow(b->ctx, csr);
+    b->es.setDeviceOperator(b->op);
+  });
+}
+int eigenex_spin_entanglement_solver_set_state(void* p, const double* v, int64_t n) {
+  return guard([&] {
+    auto* b = static_cast<SpinEntanglementBox*>(p);
+    b->state = make_vector<double>(v, n);
+    b->es.setState(b->state);
+  });
+}
+int eigenex_spin_entanglement_solver_set_subsystem(void* p, const int32_t* sites, int n) {
+  return guard([&] { static_cast<SpinEntanglementBox*>(p)->es.setSubsystem(std::vector<int>(sites, sites + (n > 0 ? n : 0))); });
+}
+int eigenex_spin_entanglement_solver_set_subsystem_mask(void* p, uint32_t mask) {
+  return guard([&] { static_cast<SpinEntanglementBox*>(p)->es.setSubsystemMask(mask); });
+}
+int eigenex_spin_entanglement_solver_compute(void* p) { return guard([&] { static_cast<SpinEntanglementBox*>(p)->es.compute(); }); }
+// out[4]: blocks, eigenvalues, log lines, info
+int eigenex_spin_entanglement_solver_sizes(void* p, int64_t* out) {
+  return guard([&] {
+    auto& es = static_cast<SpinEntanglementBox*>(p)->es;
+    out[0] = (int64_t)es.blocks(), out[1] = (int64_t)es.spectrum().size(), out[2] = (int64_t)es.log().size(), out[3] = (int64_t)es.info();
+  });
+}
+// block n: sites up inside the subsystem, dimension and, unless NULL, the dimension^2 column-major entries of unit-trace rho_A
+int eigenex_spin_entanglement_solver_block(void* p, int64_t n, int* sites_up, int64_t* dim, double* rho) {
+  return guard([&] {
+    auto& es = static_cast<SpinEntanglementBox*>(p)->es;
+    if (sites_up) *sites_up = es.blockSitesUp((Index)n);
+    if (dim) *dim = (int64_t)es.blockDimension((Index)n);
+    if (rho) std::copy(es.reducedDensityMatrix((Index)n).begin(), es.reducedDensityMatrix((Index)n).end(), rho);
+  });
+}
+// any pointer may be NULL; scalars[3] = (normSquared, entropy, renyi2), the last two only after a successful compute()
+int eigenex_spin_entanglement_solver_get(void* p, double* spectrum, double* scalars) {
+  return guard([&] {
+    auto& es = static_cast<SpinEntanglementBox*>(p)->es;
+    if (spectrum) std::copy(es.spectrum().begin(), es.spectrum().end(), spectrum);
+    if (scalars) scalars[0] = es.normSquared(), scalars[1] = es.entropy(), scalars[2] = es.blocks() > 0 ? es.renyi2() : 0.0;
+  });
+}
+int eigenex_spin_entanglement_solver_renyi(void* p, double alpha, double* out) {
+  return guard([&] { *out = static_cast<SpinEntanglementBox*>(p)->es.renyi(alpha); });
+}
+int eigenex_spin_entanglement_solver_schmidt_rank(void* p, double tol, int64_t* out) {
+  return guard([&] { *out = (int64_t)static_cast<SpinEntanglementBox*>(p)->es.schmidtRank(tol); });
+}
+const char* eigenex_spin_entanglement_solver_log_line(void* p, int64_t i) {
+  auto& log = static_cast<SpinEntanglementBox*>(p)->es.log();
   return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
 }
 

@@ -1,6 +1,6 @@
 // The row walk of the matrix-free spin-1/2 kernels (kernels.hip: k_spin_spmv<SECTOR>, k_spin_measure<SECTOR>,
-// k_spin_site_apply<SECTOR>), shared by the
-// device code and by the host replays tests/cpp/spin_{model,sector,measure,site}_sanitize.cpp, which run it under AddressSanitizer +
+// k_spin_site_apply<SECTOR>, and through spin_rdm_rows.hpp k_spin_rdm<SECTOR, TILE>), shared by the
+// device code and by the host replays tests/cpp/spin_{model,sector,measure,site,rdm}_sanitize.cpp, which run it under AddressSanitizer +
 // UBSan.  The kernels and the replays call THESE functions, so what a replay proves about them (every load inside its array, the
 // state equal to spin_sector_unrank, the sums equal to the CSR row loop and to spin_measure_host bit for bit) holds for the
 // kernels' rows as compiled.  No device construct in here: plain C++11.  spin_write_rows, spin_sector_unrank, spin_sector_rank
@@ -160,3 +160,6 @@ EIGENEX_HD double spin_site_add(double yr, const double* coef, const bool* on, c
 }
 
 }  // namespace eigenex
+
+// the index arithmetic of the reduced-density-matrix kernel (k_spin_rdm<SECTOR, TILE>), under the same rules
+#include "spin_rdm_rows.hpp"

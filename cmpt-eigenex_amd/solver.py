@@ -103,6 +103,23 @@ def lib():
         getattr(L, p + "static_structure_factor_z").argtypes = [_vp, C.c_double, _dp]
         getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
         getattr(L, p + "log_line").restype = C.c_char_p
+        p = "eigenex_spin_entanglement_solver_"
+        getattr(L, p + "create").argtypes = []
+        getattr(L, p + "create").restype = _vp
+        getattr(L, p + "destroy").argtypes = [_vp]
+        getattr(L, p + "destroy").restype = None
+        getattr(L, p + "set_device_operator").argtypes = [_vp, _vp, _vp]
+        getattr(L, p + "set_state").argtypes = [_vp, _dp, C.c_int64]
+        getattr(L, p + "set_subsystem").argtypes = [_vp, _ip32, C.c_int]
+        getattr(L, p + "set_subsystem_mask").argtypes = [_vp, C.c_uint32]
+        getattr(L, p + "compute").argtypes = [_vp]
+        getattr(L, p + "sizes").argtypes = [_vp, _lp]
+        getattr(L, p + "block").argtypes = [_vp, C.c_int64, C.POINTER(C.c_int), _lp, _dp]
+        getattr(L, p + "get").argtypes = [_vp, _dp, _dp]
+        getattr(L, p + "renyi").argtypes = [_vp, C.c_double, _dp]
+        getattr(L, p + "schmidt_rank").argtypes = [_vp, C.c_double, _lp]
+        getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
+        getattr(L, p + "log_line").restype = C.c_char_p
         for kind in FAMILIES:
             p = f"eigenex_{kind}_solver_"
             getattr(L, p + "create").restype = _vp
@@ -715,6 +732,91 @@ class SpinDynamicsSolver:
         v = C.c_double()
         _chk(self._f("static_structure_factor_z")(self.h, float(q), C.byref(v)))
         return v.value
+
+    def log(self):
+        return [self._f("log_line")(self.h, i).decode() for i in range(self._sizes()["nlog"])]
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SpinEntanglementSolver:
+    """SpinEntanglementSolver (spin_entanglement.hpp): the reduced density matrix of a subsystem of a state of a matrix-free
+    spin-1/2 operator (capi.Csr.spin_half, capi.Csr.spin_half_sector), formed on the device, and what follows from it: the
+    entanglement spectrum, the von Neumann and Renyi entropies and the Schmidt rank."""
+
+    _names = ("nblocks", "neigenvalues", "nlog", "info")
+
+    def __init__(self):
+        self._L = lib()
+        self.h = _vp(self._L.eigenex_spin_entanglement_solver_create())
+        if not self.h:
+            raise capi.EigenexError("solver create failed")
+        self._keep = []
+
+    def _f(self, name):
+        return getattr(self._L, "eigenex_spin_entanglement_solver_" + name)
+
+    def setDeviceOperator(self, csr: capi.Csr):
+        self._keep.append(csr)
+        _chk(self._f("set_device_operator")(self.h, csr.ctx.h, csr.h))
+        return self
+
+    def setState(self, v):
+        a = np.ascontiguousarray(v, np.float64)
+        _chk(self._f("set_state")(self.h, _d(a), a.size))
+        return self
+
+    def setSubsystem(self, sites):
+        a = np.ascontiguousarray(sites, np.int32).reshape(-1)
+        _chk(self._f("set_subsystem")(self.h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.size))
+        return self
+
+    def setSubsystemMask(self, mask):
+        _chk(self._f("set_subsystem_mask")(self.h, int(mask)))
+        return self
+
+    def compute(self):
+        _chk(self._f("compute")(self.h))
+        return self
+
+    def _sizes(self):
+        out = np.zeros(len(self._names), np.int64)
+        _chk(self._f("sizes")(self.h, out.ctypes.data_as(_lp)))
+        return dict(zip(self._names, (int(x) for x in out)))
+
+    def results(self):
+        """blocks = [(sites up inside the subsystem, unit-trace block of rho_A as ndarray(d, d)), ...], spectrum (descending),
+        normSquared, entropy, renyi2, info"""
+        s = self._sizes()
+        spectrum, sc, blocks = np.zeros(s["neigenvalues"]), np.zeros(3), []
+        _chk(self._f("get")(self.h, _d(spectrum), _d(sc)))
+        for n in range(s["nblocks"]):
+            up, dim = C.c_int(), C.c_int64()
+            _chk(self._f("block")(self.h, n, C.byref(up), C.byref(dim), None))
+            rho = np.zeros(dim.value * dim.value)
+            _chk(self._f("block")(self.h, n, None, None, _d(rho)))
+            blocks.append((up.value, rho.reshape(dim.value, dim.value).T.copy()))
+        s.update(blocks=blocks, spectrum=spectrum, normSquared=sc[0], entropy=sc[1], renyi2=sc[2], info_name=INFO[s["info"]])
+        return s
+
+    def renyi(self, alpha):
+        v = C.c_double()
+        _chk(self._f("renyi")(self.h, float(alpha), C.byref(v)))
+        return v.value
+
+    def schmidtRank(self, tol):
+        r = C.c_int64()
+        _chk(self._f("schmidt_rank")(self.h, float(tol), C.byref(r)))
+        return r.value
 
     def log(self):
         return [self._f("log_line")(self.h, i).decode() for i in range(self._sizes()["nlog"])]

@@ -363,6 +363,38 @@ int eigenex_spin_site_apply(eigenex_basis_t src, int x_ref, eigenex_basis_t dst,
                             const double* coef /* n_sites */, double* norm2 /* or NULL */);
 int eigenex_spin_site_apply_host(int n_sites, int n_up_src /* -1: full space */, int kind, const double* coef,
                                  const double* x, double* y, double* norm2);
+/* The reduced density matrix rho_A of a real vector over the rows of a matrix-free spin-1/2 operator, on the device, without
+ * downloading the vector: what the entanglement entropy, the Renyi entropies and the entanglement spectrum are taken from.  NOT
+ * part of the reference.  The subsystem A is a 32-bit site mask mask_a (bit i = site i); nA = popcount(mask_a), nB = n_sites - nA,
+ * mask_b = the other sites; dep_A(a) deposits the nA-bit word a into mask_a (bit j of a goes to the j-th lowest set bit), dep_B
+ * likewise.
+ *   full space   one block of d = 2^nA rows:  rho[a, a'] = sum_{b < 2^nB} x[dep_A(a) | dep_B(b)] * x[dep_A(a') | dep_B(b)]
+ *   sector       rho_A is block-diagonal in the number k of up sites inside A: blocks k = max(0, n_up - nB) .. min(nA, n_up);
+ *                block k has d_k = C(nA, k) rows, row i is the i-th nA-bit word with k bits set in ascending order, b runs over
+ *                the C(nB, n_up - k) words of nB bits with n_up - k bits set in ascending order, and the element is
+ *                x[rank(dep_A(a) | dep_B(b))]
+ * The blocks are packed in ascending k, each a full d_k x d_k column-major matrix with both triangles stored; (i, j) and (j, i)
+ * hold the same bits.  The sums are raw and unnormalised (the trace is sum_s x_s^2).  Errors (EIGENEX_ERR_ARG, message in
+ * eigenex_last_error): a zero mask, a site at or above n_sites, a mask that leaves no site out, a geometry that
+ * eigenex_spin_measure_host refuses, a block of more than 4096 rows (nA <= 12 in the full space, nA <= 14 in a sector), an
+ * out_len that is not the layout's length.
+ *   eigenex_spin_rdm_layout  host only, no context: the number of blocks, k of the first (0 in the full space), dims[n_blocks]
+ *                            (at most 33) and offsets[n_blocks + 1] (at most 34; the last is the length of `out`).  Any output
+ *                            may be NULL.
+ *   eigenex_spin_rdm         x = any vector reference of a state whose operator handle came from eigenex_spin_upload or
+ *                            eigenex_spin_sector_upload; any other operator or a host callback: EIGENEX_ERR_STATE.  out is host
+ *                            memory of exactly the layout's length.  Runs on the context's stream and synchronises once.  No
+ *                            vector of the state, no coefficient, counter or recorded step batch is touched.  No atomics: every
+ *                            entry is the sum of its b range cut into slices, the slices added in ascending order; the number
+ *                            of slices depends on the geometry, the mask and the launch grid (eigenex_basis_tune) alone, so two
+ *                            calls return identical bytes.
+ *   eigenex_spin_rdm_host    the definition the kernels are held against, in host code: no context, no GPU.  The b terms are
+ *                            added in ascending order, one fma per term. */
+int eigenex_spin_rdm_layout(int n_sites, int n_up /* -1: full space */, uint32_t mask_a, int* n_blocks, int* k_first,
+                            int64_t* dims /* <= 33 */, int64_t* offsets /* <= 34 */);
+int eigenex_spin_rdm(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out, int64_t out_len);
+int eigenex_spin_rdm_host(int n_sites, int n_up /* -1: full space */, const double* x, uint32_t mask_a, double* out,
+                          int64_t out_len);
 /* CSR that already lives in device memory of this context's GPU (e.g. tensors of a GPU framework: pass their
  * data pointers): copied device-to-device, never through the host, after a device-side check of the row pointers
  * and column indices.  Unsharded contexts only; rowptr_dev[0] = 0; columns are global = local indices. */
