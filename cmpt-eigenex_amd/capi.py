@@ -146,6 +146,7 @@ SIGNATURES = {
     "eigenex_basis_clone": (C.c_int, [_vp, C.POINTER(_vp)]),
     "eigenex_basis_graph_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "eigenex_basis_repairs": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "eigenex_basis_close_pending": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "eigenex_arnoldi_enqueue": (C.c_int, [_vp, C.c_int]),
     "eigenex_lanczos_restart": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double]),
     "eigenex_arnoldi_restart": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, C.c_int]),
@@ -766,6 +767,12 @@ class Basis:
         _chk(lib().eigenex_basis_repairs(self.h, C.byref(n)))
         return n.value
 
+    def close_pending(self) -> bool:
+        """the last batch of one-sweep Lanczos steps has left its newest column to be written by the next call that needs it"""
+        n = C.c_int()
+        _chk(lib().eigenex_basis_close_pending(self.h, C.byref(n)))
+        return bool(n.value)
+
     def set_alpha_fusion(self, on: bool):
         _chk(lib().eigenex_basis_set_alpha_fusion(self.h, int(bool(on))))
 
@@ -779,6 +786,14 @@ class Basis:
 
     def copy(self, dst_ref: int, src_ref: int):
         _chk(lib().eigenex_vec_copy(self.h, dst_ref, src_ref))
+
+    def clone(self):
+        """eigenex_basis_clone: a deep copy of this state on the device (same context and operator)"""
+        other = Basis.__new__(Basis)
+        other.__dict__.update(self.__dict__)
+        other.h, other._cb = _vp(), None
+        _chk(lib().eigenex_basis_clone(self.h, C.byref(other.h)))
+        return other
 
     def reserve(self, capacity: int):
         _chk(lib().eigenex_basis_reserve(self.h, capacity))

@@ -634,22 +634,31 @@ __global__ __launch_bounds__(kBlock) void k_sweep(SweepStep st, InlineFin fin, i
   if (threadIdx.x == 0) npartials[blockIdx.x] = nrm;
 }
 
-// behind the full sweep (kernels.hpp: launch_lag_terms), one workgroup: a wave per coefficient, lanes strided over the partials
-__global__ __launch_bounds__(kBlock) void k_lag_terms(int k, const double* __restrict__ dpartials, int pstride, int nblocks,
-                                                      const double* __restrict__ npartials, double* lag, int f_off, double threshold,
-                                                      Ctrl* ctrl, Ctrl* repair) {
+// behind the full sweep (kernels.hpp: launch_lag_terms), one workgroup of up to kLagWaves waves: a wave per coefficient and round,
+// lanes strided over the partials.  The chain sweep -> this -> operator is serial on the stream and each round is one latency-bound
+// load, so the rounds are what it costs: ceil((k+1)/16) instead of ceil((k+1)/4).  beta is formed by the first four waves alone,
+// with block_sum's strides and order (the number inline_fin_sum gives the operator kernel), and handed to the others through LDS.
+constexpr int kLagWaves = 16;
+__global__ __launch_bounds__(64 * kLagWaves) void k_lag_terms(int k, const double* __restrict__ dpartials, int pstride, int nblocks,
+                                                              const double* __restrict__ npartials, double* lag, int f_off, double threshold,
+                                                              Ctrl* ctrl, Ctrl* repair) {
   __shared__ double lds4[4];
-  __shared__ double wmax[4];
+  __shared__ double wmax[kLagWaves];
   if (ctrl->stopped) {
     if (threadIdx.x == 0) repair->stopped = 1;
     return;
   }
-  double s = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += kBlock) s += npartials[b];
-  const double beta = sqrt(block_sum(s, lds4));
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  if (wave < kBlock / 64) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += kBlock) s += npartials[b];
+    s = wave_sum(s);
+    if (lane == 0) lds4[wave] = s;
+  }
+  __syncthreads();
+  const double beta = sqrt((lds4[0] + lds4[1]) + (lds4[2] + lds4[3]));
   double m = 0.0;
-  for (int c = wave; c <= k; c += 4) {
+  for (int c = wave; c <= k; c += nwaves) {
     const double* p = dpartials + (int64_t)c * pstride;
     double d = 0.0;
     for (int b = lane; b < nblocks; b += 64) d += p[b];
@@ -662,13 +671,25 @@ __global__ __launch_bounds__(kBlock) void k_lag_terms(int k, const double* __res
   }
   if (lane == 0) wmax[wave] = m;
   __syncthreads();
-  const bool armed = fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3])) > kLagGuard;
+  double mx = 0.0;
+  for (int w = 0; w < nwaves; ++w) mx = fmax(mx, wmax[w]);
+  const bool armed = mx > kLagGuard;
   if (armed)
-    for (int c = threadIdx.x; c <= k; c += kBlock) lag[kLagC + c] = 0.0;  // the repair leaves nothing pending
+    for (int c = threadIdx.x; c <= k; c += blockDim.x) lag[kLagC + c] = 0.0;  // the repair leaves nothing pending
   if (threadIdx.x == 0) {
     repair->stopped = armed ? 0 : 1;
     if (armed) ctrl->repairs++;
   }
+}
+
+// The scalars of a closing pass (k_sweep<true>'s prologue, the same arithmetic on one thread): a' kept in lag[0], alpha_k = a' - da
+// into the series.  The column part of the pass waits until something reads the column (library.hip: settle_columns).
+__global__ void k_close_scalars(int k, const double* a_raw, double* alpha, const double* __restrict__ beta, double* lag, const Ctrl* __restrict__ ctrl) {
+  if (ctrl->stopped) return;
+  const double a = *a_raw;
+  const double da = lag_alpha_correction(k, beta, lag + kLagC);
+  lag[0] = a;
+  if (k > 0) alpha[k] = a - da;
 }
 
 // ---------------------------------------------------------------------------
@@ -2656,7 +2677,12 @@ void launch_sweep(hipStream_t s, const SweepStep& st, const InlineFin* fin, int6
 
 void launch_lag_terms(hipStream_t s, int k, const double* dpartials, int pstride, int nblocks, const double* npartials, double* lag,
                       int f_off, double threshold, Ctrl* ctrl, Ctrl* repair) {
-  hipLaunchKernelGGL(k_lag_terms, dim3(1), dim3(kBlock), 0, s, k, dpartials, pstride, nblocks, npartials, lag, f_off, threshold, ctrl, repair);
+  const int waves = std::min(kLagWaves, std::max(kBlock / 64, k + 1));
+  hipLaunchKernelGGL(k_lag_terms, dim3(1), dim3(64 * waves), 0, s, k, dpartials, pstride, nblocks, npartials, lag, f_off, threshold, ctrl, repair);
+}
+
+void launch_close_scalars(hipStream_t s, int k, const double* a_raw, double* alpha, const double* beta, double* lag, const Ctrl* ctrl) {
+  hipLaunchKernelGGL(k_close_scalars, dim3(1), dim3(1), 0, s, k, a_raw, alpha, beta, lag, ctrl);
 }
 
 void launch_spmv_z(hipStream_t s, const int32_t* rowptr, const int32_t* col, const double* val, const double* x_ext,

@@ -169,12 +169,13 @@ __host__ __device__ inline bool random_sign_bit(uint64_t key, uint64_t row) { re
 // column may already hold its corrected form (the end of a batch) without the sweep seeing a difference.  The sweep (full or
 // correct_only) is column k's ONLY writer: the operator of a one-sweep step does not store u~ (library.hip: ApplyPass::store_u),
 // and between that operator and the sweep or closing pass that follows it nothing reads column k (the repair pass of step k-1
-// runs over columns 0..k-1, a stopped state never gets the column, a batch ends with the closing pass).  Column 0 of the first
+// runs over columns 0..k-1, a stopped state never gets the column, a batch ends with the scalars of the closing pass and whatever
+// would read the column next runs the pass itself first: library.hip, settle_columns).  Column 0 of the first
 // call is stored by its operator.
 //   full:          w0 = (v - a' u~) - beta_{k-1} u_{k-1};  per row tile, j ascending over columns 0..k-1:  d_j = x_j . w0,
 //                  u -= c_j x_j,  w -= f_j x_j;  then d_k = u . w0,  w -= f_k u;  column k = u,  w stored in place of the pending
 //                  vector, partial ||w||^2.  Workgroup 0 records alpha_k = a' - da, a' (lag[0]) and f (lag + f_off).
-//   correct_only:  column k = u~ - sum_j c_j x_j, nothing else is read or written; workgroup 0 records a' and alpha_k.  Closes a batch.
+//   correct_only:  column k = u~ - sum_j c_j x_j, nothing else is read or written; workgroup 0 records a' and alpha_k.  The closing pass.
 // a' = the sum of the operator's partials (fin, which then appends alpha_k to the series as k_dots does), or *a_raw.
 constexpr int kLagC = 8;  // lag[kLagC + j] = c_j
 struct SweepStep {
@@ -199,6 +200,9 @@ void launch_sweep(hipStream_t s, const SweepStep& st, const InlineFin* fin, int6
 // max |c| > kLagGuard: c = 0, repair->stopped = 0 (the kernels of the repair pass run), ++ctrl->repairs; else repair->stopped = 1.
 void launch_lag_terms(hipStream_t s, int k, const double* dpartials, int pstride, int nblocks, const double* npartials, double* lag,
                       int f_off, double threshold, Ctrl* ctrl, Ctrl* repair);
+// the scalar part of the closing pass for column k, one thread: lag[0] = a' = *a_raw, alpha[k] = a' - da (k_sweep's own arithmetic,
+// the same bits); the column part is a correct_only sweep with a_raw = lag, whenever it is run
+void launch_close_scalars(hipStream_t s, int k, const double* a_raw, double* alpha, const double* beta, double* lag, const Ctrl* ctrl);
 
 int grid_for_tiles(int64_t ntiles, int blocks_per_cu);
 void set_num_cu(int n);

@@ -402,6 +402,10 @@ struct StepCursor {
   // lag_closed: the last enqueued call closed its batch, so the raw a' of the newest column is in lag[0]
   int lag_nvec = -1;
   bool lag_closed = false;
+  // close_pending >= 0: the last batch ended with the scalars of its closing pass only, and column close_pending (the newest one)
+  // has not been written yet.  settle_columns writes it before anything but the next one-sweep step, which forms the same
+  // column from the pending vector itself, touches the state.
+  int close_pending = -1;
 };
 struct StepGraphKey {
   int kind, started, h_nvec, ncalls, ortho_mode, nq, flags, g_vec, g_spmv, cap, lag;
@@ -1984,12 +1988,46 @@ inline bool sweeps_once(const eigenex_basis_s* b) {
          b->nq == 0 && b->f_degree == 0 && !b->t_restarted && b->cap + 1 <= kSweepMaxCols;
 }
 
+// EIGENEX_EAGER_CLOSE=1: every batch of one-sweep steps writes its newest column at once instead of when something reads it
+inline bool closes_eagerly() {
+  static const bool on = std::getenv("EIGENEX_EAGER_CLOSE") != nullptr;
+  return on;
+}
+
+// The column part of a closing pass that a batch of one-sweep steps has left for later: column k = u~ - sum_j c_j x_j from the
+// pending vector.  What it reads -- W, the scale, the c coefficients, a' in lag[0] (not its slot in hbuf, which other calls
+// use) -- stays as the batch left it until the next step is enqueued, because every entry point that could change or read any
+// of it calls this first (see the list at the C ABI).  The scalars it rewrites (a', alpha_k) get the bits they have.
+int settle_columns(eigenex_basis_s* b) {
+  StepCursor& cur = b->cur;
+  if (cur.close_pending < 0) return 0;
+  eigenex_context_s* c = b->ctx;
+  BasisShard& s = b->sh[0];
+  const int k = cur.close_pending;
+  SweepStep cl{k, s.V, s.ldd, s.v, s.w, &s.ctrl->scale, s.lag, s.alpha, s.beta, s.lag, kLagC + b->cap + 2, 1};
+  ProfScope ps(c, EIGENEX_K_UPDATE, 8.0 * s.nd * (k + 2));
+  LAUNCH_BEGIN();
+  launch_sweep(c->stream, cl, nullptr, s.nd, s.partials, s.pstride, s.pnorm, s.g_vec, s.ctrl);
+  LAUNCHCHK("k_sweep (closing)");
+  cur.close_pending = -1;
+  return 0;
+}
+
+// What a C ABI entry point that takes a state does first, unless it is on the list of those that leave a pending close alone
+// (in front of the C ABI below; tests/test_settle_rule.py holds every entry point of the header against that list).
+int enter_settled(eigenex_basis_s* b) {
+  if (b->cur.close_pending < 0) return 0;
+  HIPCHK(hipSetDevice(b->ctx->device));
+  return settle_columns(b);
+}
+
 // Step k in one sweep of the basis (lag_terms.hpp; kernels.hpp: SweepStep): k_sweep, k_lag_terms, the guard's repair pass (the
 // two-sweep pass on the pending vector under a control block of its own, which k_lag_terms arms; its launches return at once
 // otherwise, like the adaptive second pass of an Arnoldi step), the operator.  With inline finalisers alpha' and beta travel as
 // partial sums into their consumer kernels, without them through k_reduce_fin: the same sums in the same order.
-// The last call of a batch corrects the newest column and its alpha too (the closing pass), so that every batch leaves a complete
-// state; the next batch's first sweep recomputes both from the pending vector and the kept a', bit for bit.
+// The last call of a batch corrects the newest alpha (k_close_scalars) and keeps a', so that every batch leaves complete series;
+// the newest column is corrected by settle_columns, when something other than the next one-sweep step is about to touch the
+// state: that step's sweep recomputes both from the pending vector and the kept a', bit for bit, and never reads the column.
 int lanczos_step_one_sweep(eigenex_basis_s* b, int k, bool last_in_batch) {
   eigenex_context_s* c = b->ctx;
   hipStream_t st = c->stream;
@@ -2040,17 +2078,18 @@ int lanczos_step_one_sweep(eigenex_basis_s* b, int k, bool last_in_batch) {
     if (!merged) launch_fin_alpha(st, s.ctrl, s.hbuf + b->slot_alpha(), s.alpha, 0, b->cap);
   }
   cur.lag_closed = false;
-  if (last_in_batch) {  // close: column k+1 and alpha_{k+1} corrected, a' kept
-    SweepStep cl = sw;
-    cl.k = k + 1, cl.a_raw = s.hbuf + b->slot_alpha(), cl.correct_only = 1;
-    ProfScope ps(c, EIGENEX_K_UPDATE, 8.0 * s.nd * (k + 3));
-    LAUNCH_BEGIN();
-    launch_sweep(st, cl, nullptr, s.nd, s.partials, s.pstride, s.pnorm, s.g_vec, s.ctrl);
-    LAUNCHCHK("k_sweep (closing)");
-    cur.lag_closed = true;
-  }
+  cur.close_pending = -1;  // this step's sweep has written the column a pending close was about
   cur.h_nvec++;
   cur.lag_nvec = cur.h_nvec;
+  if (last_in_batch) {  // close: alpha_{k+1} corrected and a' kept now, column k+1 when something reads it (settle_columns)
+    {
+      ProfScope ps(c, EIGENEX_K_UPDATE, 0.0);  // the batch-end part of the closing pass: booked where the pass is, with no bytes
+      launch_close_scalars(st, k + 1, s.hbuf + b->slot_alpha(), s.alpha, s.beta, s.lag, s.ctrl);
+    }
+    cur.lag_closed = true;
+    cur.close_pending = k + 1;
+    if (closes_eagerly()) CHK(settle_columns(b));
+  }
   return 0;
 }
 
@@ -2236,7 +2275,7 @@ int enqueue_steps(eigenex_basis_s* b, int ncalls, int kind) {
   StepGraphKey key;
   std::memset(&key, 0, sizeof(key));
   key.kind = kind, key.started = b->cur.started ? 1 : 0, key.h_nvec = b->cur.h_nvec, key.ncalls = ncalls, key.ortho_mode = b->ortho_mode;
-  key.lag = (b->cur.lag_nvec == b->cur.h_nvec ? 1 : 0) | (b->cur.lag_closed ? 2 : 0) | (b->t_restarted ? 4 : 0);
+  key.lag = (b->cur.lag_nvec == b->cur.h_nvec ? 1 : 0) | (b->cur.lag_closed ? 2 : 0) | (b->t_restarted ? 4 : 0) | (b->cur.close_pending >= 0 ? 8 : 0);
   key.nq = b->nq, key.flags = b->sh[0].spmv_flags, key.g_vec = b->sh[0].g_vec, key.g_spmv = b->sh[0].g_spmv, key.cap = b->cap;
   key.interval = b->interval, key.threshold = b->threshold, key.shift = b->shift, key.shift_im = b->shift_im, key.slab = b->sh[0].V;
   for (auto& g : b->graphs)
@@ -2325,6 +2364,18 @@ void fill_state(const Ctrl& ct, eigenex_state_t* st) {
 
 // ===========================================================================
 // C ABI
+//
+// A batch of one-sweep Lanczos steps leaves its newest column unwritten (StepCursor::close_pending).  Every entry point that
+// takes a state calls enter_settled first, EXCEPT these, which neither read nor change anything the deferred pass depends on:
+//   eigenex_lanczos_enqueue          when the next call is a one-sweep step again (its sweep writes the column); settles otherwise
+//   eigenex_lanczos_state            alpha and beta are complete at every batch end
+//   eigenex_basis_repairs            a counter in the control block, read only
+//   eigenex_basis_configure[_z]      host-side settings; a change that ends the one-sweep steps is seen by the next enqueue
+//   eigenex_basis_set_alpha_fusion   host-side setting
+//   eigenex_basis_capacity, eigenex_basis_is_complex, eigenex_basis_graph_info, eigenex_basis_close_pending      getters
+//   eigenex_basis_clear              drops the pending close with the state it belonged to
+//   eigenex_basis_destroy
+// A new entry point is not on the list, so it settles.
 // ===========================================================================
 extern "C" {
 
@@ -3088,6 +3139,7 @@ int eigenex_spin_measure_host(int n_sites, int n_up, const double* x, int n_diag
 int eigenex_spin_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks,
                          double* diag_out, double* flip_out, double* norm2) {
   if (!b) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure: basis is NULL");
+  CHK(enter_settled(b));
   if (!b->csr || b->sh.size() != 1 || !b->sh[0].csr || !b->sh[0].csr->spin.on())
     return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_measure: the operator of this state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
                                           : "eigenex_spin_measure: the state has no device operator (a host callback knows no sites)");
@@ -3143,6 +3195,8 @@ static BasisShard* spin_state_shard(eigenex_basis_t b) {
 
 int eigenex_spin_site_apply(eigenex_basis_t src, int x_ref, eigenex_basis_t dst, int y_ref, int kind, const double* coef, double* norm2) {
   if (!src || !dst) return fail(EIGENEX_ERR_ARG, "eigenex_spin_site_apply: a state is NULL");
+  CHK(enter_settled(src));
+  CHK(enter_settled(dst));
   for (eigenex_basis_t b : {src, dst})
     if (!spin_state_shard(b))
       return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_site_apply: the operator of a state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
@@ -3203,6 +3257,7 @@ int eigenex_spin_rdm_host(int n_sites, int n_up, const double* x, uint32_t mask_
 
 int eigenex_spin_rdm(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out, int64_t out_len) {
   if (!b) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm: basis is NULL");
+  CHK(enter_settled(b));
   if (!spin_state_shard(b))
     return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_rdm: the operator of this state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
                                           : "eigenex_spin_rdm: the state has no device operator (a host callback knows no sites)");
@@ -3550,6 +3605,7 @@ int eigenex_basis_create_ex(eigenex_context_t c, eigenex_csr_t csr, int64_t n_gl
 // classes are implicitly copyable and own their vectors (lanczos.hpp:104-105, :233-239).  Device-to-device.
 int eigenex_basis_clone(eigenex_basis_t src, eigenex_basis_t* out) {
   if (!src || !out) return fail(EIGENEX_ERR_ARG, "eigenex_basis_clone: NULL argument");
+  CHK(enter_settled(src));
   eigenex_context_s* c = src->ctx;
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -3591,6 +3647,7 @@ int eigenex_basis_clone(eigenex_basis_t src, eigenex_basis_t* out) {
 int eigenex_basis_tune(eigenex_basis_t b, int vec_blocks_per_cu, int spmv_blocks_per_cu, int flags) {
   if (!b || vec_blocks_per_cu < 1 || vec_blocks_per_cu > kMaxBlocksPerCu || spmv_blocks_per_cu < 1 || spmv_blocks_per_cu > kMaxBlocksPerCu)
     return fail(EIGENEX_ERR_ARG, "eigenex_basis_tune: blocks per CU must be in [1, 16]");
+  CHK(enter_settled(b));
   for (auto& s : b->sh) {
     s.g_vec = grid_for_tiles((s.nd + kTileRows - 1) / kTileRows, vec_blocks_per_cu);
     s.g_spmv = operator_partials(s.csr, s.nloc, spmv_blocks_per_cu, &s.g_spmv_int);
@@ -3608,6 +3665,7 @@ int eigenex_basis_capacity(eigenex_basis_t b, int* capacity) {
 int eigenex_basis_reserve(eigenex_basis_t b, int capacity) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
   if (capacity <= b->cap) return 0;
+  CHK(enter_settled(b));  // the arrays it reads move, and f sits behind cap + 2 coefficients
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -3661,6 +3719,7 @@ int eigenex_basis_reserve(eigenex_basis_t b, int capacity) {
 int eigenex_basis_set_host_operator(eigenex_basis_t b, eigenex_matvec_fn fn, void* user) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
   if (b->csr) return fail(EIGENEX_ERR_STATE, "this basis was created for a device CSR operator");
+  CHK(enter_settled(b));
   b->fn = fn;
   b->fn_user = user;
   return 0;
@@ -3694,6 +3753,7 @@ int eigenex_basis_clear(eigenex_basis_t b) {
   StepCursor& cur = b->cur;
   cur.started = false, cur.h_nvec = 0, cur.alpha_pending = cur.alpha_pending_inline = false, cur.tail_pending = false;
   cur.lag_nvec = -1, cur.lag_closed = false;
+  cur.close_pending = -1;  // nothing is pending in an empty state
   return 0;
 }
 
@@ -3707,6 +3767,12 @@ int eigenex_basis_graph_info(eigenex_basis_t b, int* ngraphs, int64_t* nodes_tot
   return 0;
 }
 
+int eigenex_basis_close_pending(eigenex_basis_t b, int* pending) {
+  if (!b || !pending) return fail(EIGENEX_ERR_ARG, "NULL argument");
+  *pending = b->cur.close_pending >= 0 ? 1 : 0;
+  return 0;
+}
+
 int eigenex_basis_set_alpha_fusion(eigenex_basis_t b, int on) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
   b->fuse_alpha = on != 0;
@@ -3715,6 +3781,7 @@ int eigenex_basis_set_alpha_fusion(eigenex_basis_t b, int on) {
 
 static int vec_copy(eigenex_basis_t b, int ref, double* host, bool up) {
   if (!b || !host) return fail(EIGENEX_ERR_ARG, "NULL argument");
+  CHK(enter_settled(b));
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   const int64_t rb0 = b->sh[0].rb;
@@ -3735,6 +3802,7 @@ int eigenex_vec_download(eigenex_basis_t b, int ref, double* host) { return vec_
 
 int eigenex_vec_copy(eigenex_basis_t b, int dst_ref, int src_ref) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  CHK(enter_settled(b));
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   for (auto& s : b->sh) {
@@ -3768,6 +3836,7 @@ static bool cols_ok(eigenex_basis_t b, int first, int stride, int count, int nq)
 
 int eigenex_apply(eigenex_basis_t b, int x_ref, int y_ref, double shift, double* dot) {
   if (!b || (!b->csr && !b->fn)) return fail(EIGENEX_ERR_ARG, "eigenex_apply needs a basis with a device operator or a host callback");
+  CHK(enter_settled(b));
   if (y_ref == EIGENEX_VEC_W) return fail(EIGENEX_ERR_ARG, "y may not be the operator input vector");
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
@@ -3839,6 +3908,7 @@ static int ensure_cheb_buffers(eigenex_basis_s* b, bool with_fy) {
 
 int eigenex_basis_set_filter(eigenex_basis_t b, int degree, const double* mu, double center, double halfwidth) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  CHK(enter_settled(b));
   if (degree < 0 || (degree > 0 && (!mu || !(halfwidth > 0.0) || !std::isfinite(halfwidth) || !std::isfinite(center))))
     return fail(EIGENEX_ERR_ARG, "eigenex_basis_set_filter: degree >= 0, mu[degree + 1] and halfwidth > 0 are needed");
   if (degree > 0 && !b->csr) return fail(EIGENEX_ERR_STATE, "eigenex_basis_set_filter: a filter needs a device operator");
@@ -3856,6 +3926,7 @@ int eigenex_basis_set_filter(eigenex_basis_t b, int degree, const double* mu, do
 
 int eigenex_filter_apply(eigenex_basis_t b, int x_ref, int y_ref) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  CHK(enter_settled(b));
   if (b->f_degree < 1 || !b->csr) return fail(EIGENEX_ERR_STATE, "eigenex_filter_apply: no filter is set (eigenex_basis_set_filter)");
   if (y_ref == EIGENEX_VEC_W) return fail(EIGENEX_ERR_ARG, "y may not be the operator input vector");
   eigenex_context_s* c = b->ctx;
@@ -3923,6 +3994,7 @@ static int kpm_collect(eigenex_basis_s* b, int d, int runs, int n_moments, doubl
 
 int eigenex_kpm_moments(eigenex_basis_t b, int x_ref, int n_moments, double center, double halfwidth, double* mu) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  CHK(enter_settled(b));
   if (n_moments < 1 || !mu || !(halfwidth > 0.0) || !std::isfinite(halfwidth) || !std::isfinite(center))
     return fail(EIGENEX_ERR_ARG, "eigenex_kpm_moments: n_moments >= 1, mu[n_moments] and halfwidth > 0 are needed");
   if (!b->csr) return fail(EIGENEX_ERR_STATE, "eigenex_kpm_moments: the moments need a device operator");
@@ -3945,6 +4017,7 @@ int eigenex_kpm_moments(eigenex_basis_t b, int x_ref, int n_moments, double cent
 int eigenex_kpm_trace_moments(eigenex_basis_t b, int n_moments, int n_vectors, uint64_t seed, uint64_t first_stream, double center,
                               double halfwidth, double* mu_each) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  CHK(enter_settled(b));
   if (n_moments < 1 || n_vectors < 1 || !mu_each || !(halfwidth > 0.0) || !std::isfinite(halfwidth) || !std::isfinite(center))
     return fail(EIGENEX_ERR_ARG, "eigenex_kpm_trace_moments: n_moments >= 1, n_vectors >= 1, mu_each[n_vectors * n_moments] and halfwidth > 0 are needed");
   if (!b->csr) return fail(EIGENEX_ERR_STATE, "eigenex_kpm_trace_moments: the moments need a device operator");
@@ -3965,6 +4038,7 @@ int eigenex_kpm_trace_moments(eigenex_basis_t b, int n_moments, int n_vectors, u
 
 int eigenex_vec_random_signs(eigenex_basis_t b, int x_ref, uint64_t seed, uint64_t stream) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  CHK(enter_settled(b));
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   for (auto& s : b->sh)
@@ -3976,6 +4050,7 @@ int eigenex_vec_random_signs(eigenex_basis_t b, int x_ref, uint64_t seed, uint64
 
 int eigenex_dots(eigenex_basis_t b, int w_ref, int first, int stride, int count, int n_ortho_used, double* h) {
   if (!b || !h) return fail(EIGENEX_ERR_ARG, "NULL argument");
+  CHK(enter_settled(b));
   if (!cols_ok(b, first, stride, count, n_ortho_used)) return fail(EIGENEX_ERR_ARG, "bad column selection");
   if (!vec_ptr(b->sh[0], b->cap, b->nq, w_ref)) return fail(EIGENEX_ERR_ARG, "bad vector reference");
   HIPCHK(hipSetDevice(b->ctx->device));
@@ -3986,6 +4061,7 @@ int eigenex_dots(eigenex_basis_t b, int w_ref, int first, int stride, int count,
 int eigenex_update(eigenex_basis_t b, int w_ref, int first, int stride, int count, int n_ortho_used, const double* h,
                    double* nrm2) {
   if (!b) return fail(EIGENEX_ERR_ARG, "NULL argument");
+  CHK(enter_settled(b));
   if (!cols_ok(b, first, stride, count, n_ortho_used)) return fail(EIGENEX_ERR_ARG, "bad column selection");
   if (count + n_ortho_used > 0 && !h) return fail(EIGENEX_ERR_ARG, "h is NULL");
   if (!vec_ptr(b->sh[0], b->cap, b->nq, w_ref)) return fail(EIGENEX_ERR_ARG, "bad vector reference");
@@ -3999,6 +4075,7 @@ int eigenex_update(eigenex_basis_t b, int w_ref, int first, int stride, int coun
 
 int eigenex_axpy2(eigenex_basis_t b, int z_ref, int x_ref, double a, int p_ref, double bcoef, int q_ref) {
   if (!b) return fail(EIGENEX_ERR_ARG, "NULL argument");
+  CHK(enter_settled(b));
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   const double ab[2] = {a, bcoef};
@@ -4017,6 +4094,7 @@ int eigenex_axpy2(eigenex_basis_t b, int z_ref, int x_ref, double a, int p_ref, 
 
 int eigenex_scale(eigenex_basis_t b, int dst_ref, int src_ref, double sc) {
   if (!b) return fail(EIGENEX_ERR_ARG, "NULL argument");
+  CHK(enter_settled(b));
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   for (auto& s : b->sh) {
@@ -4034,6 +4112,9 @@ int eigenex_lanczos_enqueue(eigenex_basis_t b, int ncalls) {
   if (b->f_degree > 0 && (b->shift != 0.0 || b->shift_im != 0.0))
     return fail(EIGENEX_ERR_STATE, "eigenex_lanczos_enqueue: a filtered state takes no eigenvalue shift");
   HIPCHK(hipSetDevice(b->ctx->device));
+  // a pending close is left to the first sweep of this batch only if that is what comes next
+  const StepCursor& cur = b->cur;
+  if (!(ncalls > 0 && cur.started && cur.lag_nvec == cur.h_nvec && cur.h_nvec < b->cap && sweeps_once(b))) CHK(enter_settled(b));
   return enqueue_steps(b, ncalls, 0);
 }
 
@@ -4042,6 +4123,7 @@ int eigenex_lanczos_enqueue(eigenex_basis_t b, int ncalls) {
 // are formed in the free columns m+1.. of the slab (capacity >= m+1+nkeep) and copied down.
 int eigenex_lanczos_restart(eigenex_basis_t b, int nkeep, const double* S, int lds, double coupling_last) {
   if (!b || nkeep < 1 || !S) return fail(EIGENEX_ERR_ARG, "eigenex_lanczos_restart: bad argument");
+  CHK(enter_settled(b));
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   Ctrl ct;
@@ -4080,6 +4162,7 @@ int eigenex_lanczos_restart(eigenex_basis_t b, int nkeep, const double* S, int l
 
 int eigenex_arnoldi_enqueue(eigenex_basis_t b, int ncalls) {
   if (!b || ncalls < 0) return fail(EIGENEX_ERR_ARG, "bad argument");
+  CHK(enter_settled(b));
   if (b->f_degree > 0) return fail(EIGENEX_ERR_STATE, "eigenex_arnoldi_enqueue: the filter of this state is for Hermitian operators (Lanczos steps)");
   HIPCHK(hipSetDevice(b->ctx->device));
   return enqueue_steps(b, ncalls, 1);
@@ -4092,6 +4175,7 @@ int eigenex_arnoldi_enqueue(eigenex_basis_t b, int ncalls) {
 // The products are formed in the free columns m.. of the slab (capacity >= m + nkeep) and copied down.  Synchronises.
 int eigenex_arnoldi_restart(eigenex_basis_t b, int nkeep, const double* Q, int ldq, const double* B, int ldb) {
   if (!b || nkeep < 1 || !Q || !B) return fail(EIGENEX_ERR_ARG, "eigenex_arnoldi_restart: bad argument");
+  CHK(enter_settled(b));
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   Ctrl ct;
@@ -4155,6 +4239,7 @@ int eigenex_lanczos_state(eigenex_basis_t b, eigenex_state_t* st, double* alpha,
 
 int eigenex_arnoldi_state(eigenex_basis_t b, eigenex_state_t* st, double* hess, int ldh) {
   if (!b) return fail(EIGENEX_ERR_ARG, "basis is NULL");
+  CHK(enter_settled(b));
   HIPCHK(hipSetDevice(b->ctx->device));
   Ctrl ct;
   CHK(sync_ctrl(b, &ct));
@@ -4261,6 +4346,7 @@ int ritz_finish(eigenex_basis_s* b, const std::vector<double*>& bufs, const std:
 // real coefficients (lanczos.hpp:798-816).  X has the basis' scalar type: real, or interleaved complex.
 int ritz_vectors_real(eigenex_basis_t b, int nvec, int nev, const double* S, int lds, double* X, int64_t ldx, bool raw) {
   if (!b || nvec < 0 || nvec > b->cap || nev < 0 || (nev && (!S || !X)) || lds < nvec) return fail(EIGENEX_ERR_ARG, "eigenex_ritz_vectors: bad argument");
+  CHK(enter_settled(b));
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   int64_t nrows = 0;
@@ -4294,6 +4380,7 @@ int ritz_vectors_real(eigenex_basis_t b, int nvec, int nev, const double* S, int
 int ritz_vectors_cplx(eigenex_basis_t b, int nvec, int nev, const double* S_re, const double* S_im, int lds, double* X,
                       int64_t ldx, bool raw) {
   if (!b || nvec < 0 || nvec > b->cap || nev < 0 || (nev && (!S_re || !S_im || !X)) || lds < nvec) return fail(EIGENEX_ERR_ARG, "eigenex_ritz_vectors_complex: bad argument");
+  CHK(enter_settled(b));
   eigenex_context_s* c = b->ctx;
   HIPCHK(hipSetDevice(c->device));
   int64_t nrows = 0;

@@ -472,6 +472,13 @@ int eigenex_basis_graph_info(eigenex_basis_t b, int* ngraphs, int64_t* nodes_tot
  * filter, no thick restart; EIGENEX_TWO_SWEEPS=1 turns them off): how many steps since the last clear had their pending vector
  * re-orthogonalised by the two-sweep pass because a lagged coefficient exceeded 2^-27 (close to a breakdown).  Synchronises. */
 int eigenex_basis_repairs(eigenex_basis_t b, int* repairs);
+/* A batch of one-sweep Lanczos steps ends with complete alpha and beta, but writes the corrected form of its newest basis column
+ * only when something other than a further one-sweep step touches the state: every call that takes the state does that first,
+ * except eigenex_lanczos_enqueue (when a one-sweep step follows), eigenex_lanczos_state, eigenex_basis_repairs,
+ * eigenex_basis_configure[_z], eigenex_basis_set_alpha_fusion, eigenex_basis_clear, eigenex_basis_destroy and the getters.
+ * *pending = 1 while that column is still outstanding.  Results never depend on it; EIGENEX_EAGER_CLOSE=1 (read once per process)
+ * writes the column at every batch end instead.  Does not synchronise. */
+int eigenex_basis_close_pending(eigenex_basis_t b, int* pending);
 
 /* host <-> device vectors (rows owned by this context) */
 int eigenex_vec_upload(eigenex_basis_t b, int vec_ref, const double* host);
