@@ -107,8 +107,11 @@ SIGNATURES = {
     "eigenex_spin_sector_states": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_uint32)]),
     "eigenex_spin_sector_csr": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.c_int64, C.c_int64, _lp, _ip, _dp, _lp]),
     "eigenex_spin_sector_upload": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
+    "eigenex_spin_upload_z": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
+    "eigenex_spin_sector_upload_z": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
     "eigenex_spin_measure": (C.c_int, [_vp, C.c_int, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_measure_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
+    "eigenex_spin_measure_host_z": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_geometry": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "eigenex_spin_site_apply": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _dp, _dp]),
     "eigenex_spin_site_apply_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
@@ -131,6 +134,7 @@ SIGNATURES = {
     "eigenex_basis_tune": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "eigenex_ritz_vectors_complex": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int64]),
     "eigenex_krylov_combine": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int64]),
+    "eigenex_krylov_combine_to": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int]),
     "eigenex_apply": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _dp]),
     "eigenex_basis_set_filter": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double]),
     "eigenex_filter_apply": (C.c_int, [_vp, C.c_int, C.c_int]),
@@ -358,6 +362,18 @@ def spin_measure_host(n_sites: int, n_up, x, diag_masks, flip_masks):
     diag, flip, norm2 = np.zeros(nd), np.zeros(nf), C.c_double()
     _chk(lib().eigenex_spin_measure_host(int(n_sites), -1 if n_up is None else int(n_up), _d(x), nd, dp, nf, fp, _d(diag) if nd else None,
                                          _d(flip) if nf else None, C.byref(norm2)))
+    return diag, flip, norm2.value
+
+
+def spin_measure_host_z(n_sites: int, n_up, x, diag_masks, flip_masks):
+    """eigenex_spin_measure_host_z: the Hermitian raw sums (diag, flip, norm2) of the masks over the complex vector x, in host code
+    (no GPU); n_up as for spin_measure_host."""
+    x = np.ascontiguousarray(x, np.complex128)
+    dm, nd, dp = _mask_list(diag_masks)
+    fm, nf, fp = _mask_list(flip_masks)
+    diag, flip, norm2 = np.zeros(nd), np.zeros(nf), C.c_double()
+    _chk(lib().eigenex_spin_measure_host_z(int(n_sites), -1 if n_up is None else int(n_up), _d(x.view(np.float64)), nd, dp, nf, fp,
+                                           _d(diag) if nd else None, _d(flip) if nf else None, C.byref(norm2)))
     return diag, flip, norm2.value
 
 
@@ -646,25 +662,27 @@ class Csr:
         return obj
 
     @classmethod
-    def spin_half(cls, ctx: Context, n_sites: int, bonds, hz=None, hx=None):
+    def spin_half(cls, ctx: Context, n_sites: int, bonds, hz=None, hx=None, complex_states=False):
         """eigenex_spin_upload: the spin-1/2 Hamiltonian on n_sites sites, applied matrix-free (nothing is stored).
-        bonds = [(i, j, Jz, Jxy), ...]; hz, hx = n_sites fields or None."""
+        bonds = [(i, j, Jz, Jxy), ...]; hz, hx = n_sites fields or None.  complex_states: eigenex_spin_upload_z, the same
+        Hamiltonian as a handle for complex states."""
         keep, args = _spin_model(n_sites, bonds, hz, hx)
         h = _vp()
-        _chk(lib().eigenex_spin_upload(ctx.h, *args, C.byref(h)))
+        _chk((lib().eigenex_spin_upload_z if complex_states else lib().eigenex_spin_upload)(ctx.h, *args, C.byref(h)))
         obj = cls(ctx, h)
-        obj.is_complex = False
+        obj.is_complex = bool(complex_states)
         return obj
 
     @classmethod
-    def spin_half_sector(cls, ctx: Context, n_sites: int, n_up: int, bonds, hz=None, hx=None):
+    def spin_half_sector(cls, ctx: Context, n_sites: int, n_up: int, bonds, hz=None, hx=None, complex_states=False):
         """eigenex_spin_sector_upload: the same Hamiltonian in the sector of n_up sites up (n_sites up to 32, C(n_sites, n_up)
-        rows), applied matrix-free.  The model must conserve Sz: hx is None or all zeros."""
+        rows), applied matrix-free.  The model must conserve Sz: hx is None or all zeros.  complex_states:
+        eigenex_spin_sector_upload_z."""
         keep, args = _spin_model(n_sites, bonds, hz, hx)
         h = _vp()
-        _chk(lib().eigenex_spin_sector_upload(ctx.h, *_sector_args(args, n_up), C.byref(h)))
+        _chk((lib().eigenex_spin_sector_upload_z if complex_states else lib().eigenex_spin_sector_upload)(ctx.h, *_sector_args(args, n_up), C.byref(h)))
         obj = cls(ctx, h)
-        obj.is_complex = False
+        obj.is_complex = bool(complex_states)
         return obj
 
     @classmethod
@@ -972,6 +990,16 @@ class Basis:
         """X = V C as it is (eigenex_krylov_combine: no normalisation, no phase).  Real C: X has the basis dtype;
         complex C: X is complex."""
         return self._combine(nvec, C, ldc, ldx, True)
+
+    def krylov_combine_to(self, nvec: int, coef, dst_ref: int):
+        """dst = sum_m coef[m] col(m), left on the device (eigenex_krylov_combine_to); complex coef needs a complex state"""
+        c = np.asarray(coef).reshape(-1)
+        if np.iscomplexobj(c):
+            cr, ci = np.ascontiguousarray(c.real, np.float64), np.ascontiguousarray(c.imag, np.float64)
+            _chk(lib().eigenex_krylov_combine_to(self.h, int(nvec), _d(cr), _d(ci), int(dst_ref)))
+        else:
+            cr = np.ascontiguousarray(c, np.float64)
+            _chk(lib().eigenex_krylov_combine_to(self.h, int(nvec), _d(cr), None, int(dst_ref)))
 
     def close(self):
         if self.h:

@@ -1710,6 +1710,86 @@ __global__ __launch_bounds__(kBlock) void k_spin_spmv(const SpinSectorView* __re
   }
 }
 
+// The same real operator on an interleaved complex vector: y = (H + shift) (x * scale) with a complex shift.  The row walk is
+// k_spin_spmv's, taken once per row for both parts (state, diagonal, flip targets and the rank-table gathers); x is gathered as
+// 16-byte loads and each part accumulates the real kernel's sum of that part (spin_rows.hpp: spin_add_flips_z).  The shift, u_out,
+// the pass bits, ctrl->stopped and the two partial dots, conj(u) . y or |y|^2, follow k_spmv_z -- except that a norm
+// (kPassSelfNorm) leaves the second set unwritten: it is one real sum with one set of readers, and one of its callers hands
+// over a buffer of pstride doubles (library.hip: palpha).
+struct SpinVectorZ {
+  const double2* x;
+  __device__ __forceinline__ SpinZ operator()(uint32_t i) const {
+    const double2 v = x[i];
+    return SpinZ{v.x, v.y};
+  }
+};
+
+template <bool SECTOR>
+__global__ __launch_bounds__(kBlock) void k_spin_spmv_z(const SpinSectorView* __restrict__ op, const uint32_t* __restrict__ lo_rank,
+                                                        const uint32_t* __restrict__ hi_base, const double2* __restrict__ x_ext,
+                                                        const double* __restrict__ scale_ptr, double shift_re, double shift_im,
+                                                        double2* __restrict__ y, double2* __restrict__ u_out, int64_t n, int64_t ntiles,
+                                                        double* __restrict__ partials, int pstride, int pass,
+                                                        const Ctrl* __restrict__ ctrl) {
+  __shared__ double lds4[4];
+  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
+  if (ctrl->stopped) return;
+  int n_up = 0, h = 0;
+  uint32_t lo_mask = 0;
+  if constexpr (SECTOR) {
+    spin_stage_binomials(op, binom);
+    __syncthreads();
+    n_up = op->n_up, h = op->h, lo_mask = op->lo_mask;
+  }
+  const double scale = scale_ptr ? *scale_ptr : 1.0;
+  const bool has_shift = shift_re != 0.0 || shift_im != 0.0;
+  const SpinOperatorView* model = &op->model;
+  const int n_sites = model->n_sites, ndiag = model->ndiag, nflip = model->nflip;
+  const SpinRankTables tab{lo_rank, hi_base};
+  double dr = 0.0, di = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + threadIdx.x;
+    if (r < n) {
+      const uint32_t s = SECTOR ? spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s : (uint32_t)r;
+      const double d = spin_row_diagonal(model->dmask, model->dval, ndiag, s);
+      double2 xr = x_ext[r];
+      xr.x *= scale;
+      xr.y *= scale;
+      SpinZ acc{add_product_nofma(0.0, d, xr.x), add_product_nofma(0.0, d, xr.y)};
+      for (int t0 = 0; t0 < nflip; t0 += kSpinBatch) {
+        bool on[kSpinBatch];
+        uint32_t base[kSpinBatch], low[kSpinBatch];
+        SpinZ xv[kSpinBatch];
+        spin_flip_targets<SECTOR>(model->fmask + t0, s, tab, h, lo_mask, on, base, low);
+        spin_gather_z(SpinVectorZ{x_ext}, base, low, xv);
+        acc = spin_add_flips_z(acc, model->fval + t0, on, xv, scale);
+      }
+      double2 yr = make_double2(acc.re, acc.im);
+      if (has_shift) {
+        const double2 t = cmul_nofma(make_double2(shift_re, shift_im), xr);
+        yr.x = yr.x + t.x;
+        yr.y = yr.y + t.y;
+      }
+      y[r] = yr;
+      if (u_out) u_out[r] = xr;
+      if (pass & kPassSelfNorm) {
+        dr = fma(yr.x, yr.x, fma(yr.y, yr.y, dr));  // |y|^2
+      } else {
+        dr = fma(xr.x, yr.x, fma(xr.y, yr.y, dr));  // conj(u) * y
+        di = fma(xr.x, yr.y, fma(-xr.y, yr.x, di));
+      }
+    }
+  }
+  if (partials) {
+    dr = block_sum(dr, lds4);
+    di = block_sum(di, lds4);
+    if (threadIdx.x == 0) {
+      partials[blockIdx.x] = dr;
+      if (!(pass & kPassSelfNorm)) partials[pstride + blockIdx.x] = di;  // a norm is one set of partials: its readers have room for one
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Spin correlations of one vector (spin_measure.hpp has the definition and SpinMeasureChunk): x streams past once per chunk of
 // kSpinMeasureChunk diagonal and as many flip masks and no vector is written.  One row per lane, 256-row tiles, the operator
@@ -1757,6 +1837,62 @@ __global__ __launch_bounds__(kBlock) void k_spin_measure(const SpinMeasureChunk*
           spin_flip_targets<SECTOR>(ch->fmask + t0, s, tab, h, lo_mask, on, base, low);
           spin_gather(SpinVector{x}, base, low, xv);
           spin_measure_flips(xs, on, xv, fl + t0);
+        }
+    }
+  }
+  const auto put = [&](int a, double mine) {  // sum a of this workgroup: 0 norm2, 1 + t diag, 1 + C + t flip
+    const double v = block_sum(mine, lds4);
+    if (threadIdx.x == 0) partials[(int64_t)a * pstride + blockIdx.x] = v;
+  };
+  put(0, nrm);
+#pragma unroll
+  for (int t = 0; t < C; ++t) put(1 + t, dg[t]);
+#pragma unroll
+  for (int t = 0; t < C; ++t) put(1 + C + t, fl[t]);
+}
+
+// The Hermitian sums of an interleaved complex vector (spin_measure.hpp): |x_s|^2 for x_s^2 and Re(conj(x_s) x_{s ^ mask}) for
+// the product of a flip, two fmas per term (real part, then imaginary part).  Chunks, registers, partials and the second stage
+// are k_spin_measure's; x is read as 16-byte loads.
+template <bool SECTOR>
+__global__ __launch_bounds__(kBlock) void k_spin_measure_z(const SpinMeasureChunk* __restrict__ ch, const SpinSectorView* __restrict__ op,
+                                                           const uint32_t* __restrict__ lo_rank, const uint32_t* __restrict__ hi_base,
+                                                           const double2* __restrict__ x, int64_t n, int64_t ntiles,
+                                                           double* __restrict__ partials, int pstride) {
+  constexpr int C = kSpinMeasureChunk;
+  __shared__ double lds4[4];
+  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
+  int n_sites = 0, n_up = 0, h = 0;
+  uint32_t lo_mask = 0;
+  if constexpr (SECTOR) {
+    spin_stage_binomials(op, binom);
+    __syncthreads();
+    n_sites = op->model.n_sites, n_up = op->n_up, h = op->h, lo_mask = op->lo_mask;
+  }
+  const int ndiag = ch->ndiag, nflip = ch->nflip;
+  const SpinRankTables tab{lo_rank, hi_base};
+  double nrm = 0.0, dg[C], fl[C];
+#pragma unroll
+  for (int t = 0; t < C; ++t) dg[t] = 0.0, fl[t] = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + threadIdx.x;
+    if (r < n) {
+      const uint32_t s = SECTOR ? spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s : (uint32_t)r;
+      const SpinZ xs = SpinVectorZ{x}((uint32_t)r);
+      nrm = fma(xs.re, xs.re, nrm);
+      nrm = fma(xs.im, xs.im, nrm);
+#pragma unroll
+      for (int t0 = 0; t0 < C; t0 += kSpinBatch)
+        if (t0 < ndiag) spin_measure_diagonals_z(xs, s, ch->dmask + t0, dg + t0);
+#pragma unroll
+      for (int t0 = 0; t0 < C; t0 += kSpinBatch)
+        if (t0 < nflip) {
+          bool on[kSpinBatch];
+          uint32_t base[kSpinBatch], low[kSpinBatch];
+          SpinZ xv[kSpinBatch];
+          spin_flip_targets<SECTOR>(ch->fmask + t0, s, tab, h, lo_mask, on, base, low);
+          spin_gather_z(SpinVectorZ{x}, base, low, xv);
+          spin_measure_flips_z(xs, on, xv, fl + t0);
         }
     }
   }
@@ -2915,6 +3051,22 @@ void launch_spin_measure(hipStream_t s, const SpinMeasureChunk* chunk, const Spi
                          const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid) {
   const auto kernel = lo_rank ? k_spin_measure<true> : k_spin_measure<false>;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, chunk, op, lo_rank, hi_base, x, n, (n + kBlock - 1) / kBlock, partials, pstride);
+}
+
+void launch_spin_spmv_z(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
+                        const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n, double* partials,
+                        int pstride, int grid, const Ctrl* ctrl, int pass) {
+  const auto kernel = lo_rank ? k_spin_spmv_z<true> : k_spin_spmv_z<false>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, op, lo_rank, hi_base, reinterpret_cast<const double2*>(x_ext), scale, shift_re,
+                     shift_im, reinterpret_cast<double2*>(y), reinterpret_cast<double2*>(u_out), n, (n + kBlock - 1) / kBlock, partials,
+                     pstride, pass, ctrl);
+}
+
+void launch_spin_measure_z(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
+                           const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid) {
+  const auto kernel = lo_rank ? k_spin_measure_z<true> : k_spin_measure_z<false>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, chunk, op, lo_rank, hi_base, reinterpret_cast<const double2*>(x), n,
+                     (n + kBlock - 1) / kBlock, partials, pstride);
 }
 
 void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstride, int nblocks, int ndiag, int nflip, double* diag_out,

@@ -351,6 +351,14 @@ void launch_block_spmv_z(hipStream_t s, const BlockOperatorView& op, const doubl
 void launch_spin_spmv(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
                       const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl,
                       int pass = 0);
+// the same real operator on interleaved complex vectors (eigenex_spin_upload_z, eigenex_spin_sector_upload_z): each part of y is
+// launch_spin_spmv's sum of that part of x, the row walked once; complex shift, u_out and partials as launch_spmv_z
+void launch_spin_spmv_z(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
+                        const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n, double* partials,
+                        int pstride, int grid, const Ctrl* ctrl, int pass = 0);
+// launch_spin_measure for an interleaved complex x: the Hermitian sums of spin_measure.hpp, same partials and second stage
+void launch_spin_measure_z(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
+                           const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid);
 // Spin correlations of the vector x over the rows of a matrix-free spin operator (eigenex_spin_measure; spin_measure.hpp has the
 // definition): one chunk of terms per launch (device memory); op, lo_rank and hi_base as for launch_spin_spmv (full space: null
 // tables, op is not read).  x is only read; the grid's partial sums go to partials[sum * pstride + workgroup], sum = 0 (norm2),

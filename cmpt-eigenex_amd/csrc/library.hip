@@ -1675,8 +1675,12 @@ void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p)
     return;
   }
   if (m->spin.on()) {
-    launch_spin_spmv(st, m->spin.view, m->spin.lo, m->spin.hi, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid, p.ctrl,
-                     p.pass_flags);
+    if (es == 2)
+      launch_spin_spmv_z(st, m->spin.view, m->spin.lo, m->spin.hi, p.x, p.scale, p.shift, p.shift_im, p.y, p.u_out, m->nloc, p.partials,
+                         s.pstride, grid, p.ctrl, p.pass_flags);
+    else
+      launch_spin_spmv(st, m->spin.view, m->spin.lo, m->spin.hi, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid, p.ctrl,
+                       p.pass_flags);
     return;
   }
   if (m->rc_rec || (m->passes == 1 && es == 1)) {
@@ -3033,8 +3037,8 @@ int eigenex_spin_csr(int n_sites, int n_bonds, const int32_t* site_i, const int3
 }
 
 // The upload behind eigenex_spin_upload (n_up = -1) and eigenex_spin_sector_upload, which have checked c, out and the model;
-// who: the entry point's name for the error text
-static int spin_upload_common(eigenex_context_t c, const SpinModelArgs& a, int n_up, const char* who, eigenex_csr_t* out) {
+// who: the entry point's name for the error text; es: the scalar type of the states the handle backs (the tables are the same)
+static int spin_upload_common(eigenex_context_t c, const SpinModelArgs& a, int n_up, const char* who, int es, eigenex_csr_t* out) {
   if (c->P != 1)
     return fail(EIGENEX_ERR_ARG, std::string(who) + ": a matrix-free spin operator needs a context with one shard in total; sharding it takes an "
                                                     "exchange of whole vectors for the bonds on the top bits, which is not built");
@@ -3042,7 +3046,7 @@ static int spin_upload_common(eigenex_context_t c, const SpinModelArgs& a, int n
   std::unique_ptr<eigenex_csr_s> m(new eigenex_csr_s());
   m->ctx = c;
   m->n_global = n_up < 0 ? int64_t(1) << a.n_sites : spin_sector_dim(a.n_sites, n_up);
-  m->es = 1;
+  m->es = es;
   m->sh.resize(1);
   CsrShard& s = m->sh[0];
   s.gshard = c->local[0];
@@ -3070,12 +3074,22 @@ static int spin_upload_common(eigenex_context_t c, const SpinModelArgs& a, int n
   return 0;
 }
 
+static int spin_upload_full(const char* who, int es, eigenex_context_t c, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                            const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null, eigenex_csr_t* out) {
+  if (!c || !out) return fail(EIGENEX_ERR_ARG, std::string(who) + ": NULL argument");
+  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null};
+  if (const char* why = spin_model_error(a)) return fail(EIGENEX_ERR_ARG, std::string(who) + ": " + why);
+  return spin_upload_common(c, a, -1, who, es, out);
+}
+
 int eigenex_spin_upload(eigenex_context_t c, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz,
                         const double* jxy, const double* hz_or_null, const double* hx_or_null, eigenex_csr_t* out) {
-  if (!c || !out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_upload: NULL argument");
-  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null};
-  if (const char* why = spin_model_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_upload: ") + why);
-  return spin_upload_common(c, a, -1, "eigenex_spin_upload", out);
+  return spin_upload_full("eigenex_spin_upload", 1, c, n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null, out);
+}
+
+int eigenex_spin_upload_z(eigenex_context_t c, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz,
+                          const double* jxy, const double* hz_or_null, const double* hx_or_null, eigenex_csr_t* out) {
+  return spin_upload_full("eigenex_spin_upload_z", 2, c, n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null, out);
 }
 
 int eigenex_spin_sector_dim(int n_sites, int n_up, int64_t* dim) {
@@ -3110,12 +3124,23 @@ int eigenex_spin_sector_csr(int n_sites, int n_up, int n_bonds, const int32_t* s
   return 0;
 }
 
+static int spin_upload_sector(const char* who, int es, eigenex_context_t c, int n_sites, int n_up, int n_bonds, const int32_t* site_i,
+                              const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null,
+                              eigenex_csr_t* out) {
+  if (!c || !out) return fail(EIGENEX_ERR_ARG, std::string(who) + ": NULL argument");
+  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null};
+  if (const char* why = spin_sector_error(a, n_up)) return fail(EIGENEX_ERR_ARG, std::string(who) + ": " + why);
+  return spin_upload_common(c, a, n_up, who, es, out);
+}
+
 int eigenex_spin_sector_upload(eigenex_context_t c, int n_sites, int n_up, int n_bonds, const int32_t* site_i, const int32_t* site_j,
                                const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null, eigenex_csr_t* out) {
-  if (!c || !out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_sector_upload: NULL argument");
-  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null};
-  if (const char* why = spin_sector_error(a, n_up)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_sector_upload: ") + why);
-  return spin_upload_common(c, a, n_up, "eigenex_spin_sector_upload", out);
+  return spin_upload_sector("eigenex_spin_sector_upload", 1, c, n_sites, n_up, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null, out);
+}
+
+int eigenex_spin_sector_upload_z(eigenex_context_t c, int n_sites, int n_up, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                                 const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null, eigenex_csr_t* out) {
+  return spin_upload_sector("eigenex_spin_sector_upload_z", 2, c, n_sites, n_up, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null, out);
 }
 
 int eigenex_spin_geometry(eigenex_csr_t m, int* n_sites, int* n_up) {
@@ -3133,6 +3158,16 @@ int eigenex_spin_measure_host(int n_sites, int n_up, const double* x, int n_diag
   if (!x) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure_host: x is NULL");
   if ((n_diag > 0 && !diag_out) || (n_flip > 0 && !flip_out)) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure_host: an output list is NULL but its count is not zero");
   spin_measure_host(a, x, diag_out, flip_out, norm2);
+  return 0;
+}
+
+int eigenex_spin_measure_host_z(int n_sites, int n_up, const double* x, int n_diag, const uint32_t* diag_masks, int n_flip,
+                                const uint32_t* flip_masks, double* diag_out, double* flip_out, double* norm2) {
+  const SpinMeasureArgs a{n_sites, n_up, n_diag, diag_masks, n_flip, flip_masks};
+  if (const char* why = spin_measure_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_measure_host_z: ") + why);
+  if (!x) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure_host_z: x is NULL");
+  if ((n_diag > 0 && !diag_out) || (n_flip > 0 && !flip_out)) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure_host_z: an output list is NULL but its count is not zero");
+  spin_measure_host_z(a, x, diag_out, flip_out, norm2);
   return 0;
 }
 
@@ -3167,7 +3202,7 @@ int eigenex_spin_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint32_
   for (size_t k = 0; k < chunks.size(); ++k) {
     const size_t first = k * kSpinMeasureChunk;  // a list that ends before `first` has no live sum in this chunk
     const size_t dfirst = std::min(first, (size_t)n_diag), ffirst = std::min(first, (size_t)n_flip);
-    launch_spin_measure(c->stream, d_chunks + k, m->spin.view, m->spin.lo, m->spin.hi, x, s.nloc, d_part, grid, grid);
+    (b->es == 2 ? launch_spin_measure_z : launch_spin_measure)(c->stream, d_chunks + k, m->spin.view, m->spin.lo, m->spin.hi, x, s.nloc, d_part, grid, grid);
     launch_spin_measure_reduce(c->stream, d_part, grid, grid, chunks[k].ndiag, chunks[k].nflip, d_out + 1 + dfirst, d_out + 1 + n_diag + ffirst,
                                k == 0 ? d_out.get() : nullptr);
   }
@@ -3201,6 +3236,8 @@ int eigenex_spin_site_apply(eigenex_basis_t src, int x_ref, eigenex_basis_t dst,
     if (!spin_state_shard(b))
       return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_site_apply: the operator of a state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
                                             : "eigenex_spin_site_apply: a state has no device operator (a host callback knows no sites)");
+  if (src->es != 1 || dst->es != 1)
+    return fail(EIGENEX_ERR_STATE, "eigenex_spin_site_apply: real states only (a complex spin state, eigenex_spin_upload_z, has no site-operator kernel)");
   if (src->ctx != dst->ctx) return fail(EIGENEX_ERR_STATE, "eigenex_spin_site_apply: the two states live on different contexts");
   BasisShard &ss = *spin_state_shard(src), &sd = *spin_state_shard(dst);
   const SpinShard &ms = ss.csr->spin, &md = sd.csr->spin;
@@ -3261,6 +3298,8 @@ int eigenex_spin_rdm(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out,
   if (!spin_state_shard(b))
     return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_rdm: the operator of this state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
                                           : "eigenex_spin_rdm: the state has no device operator (a host callback knows no sites)");
+  if (b->es != 1)
+    return fail(EIGENEX_ERR_STATE, "eigenex_spin_rdm: real states only (a complex spin state, eigenex_spin_upload_z, has no density-matrix kernel)");
   BasisShard& s = *spin_state_shard(b);
   const SpinShard& m = s.csr->spin;
   const SpinRdmArgs a{m.n_sites, m.n_up, mask_a};
@@ -3512,7 +3551,7 @@ int eigenex_basis_is_complex(eigenex_basis_t b, int* is_complex) {
 int eigenex_basis_create_ex(eigenex_context_t c, eigenex_csr_t csr, int64_t n_global, int capacity, int n_ortho,
                             int is_complex, eigenex_basis_t* out) {
   if (!c || !out || n_global <= 0 || capacity < 1 || n_ortho < 0) return fail(EIGENEX_ERR_ARG, "eigenex_basis_create: bad argument");
-  if (csr && is_complex && !csr->sh.empty() && csr->sh[0].spin.on())
+  if (csr && is_complex && csr->es != 2 && !csr->sh.empty() && csr->sh[0].spin.on())
     return fail(EIGENEX_ERR_ARG, "a matrix-free spin operator is real: it cannot back a complex state");
   if (csr && (csr->es == 2) != (is_complex != 0)) return fail(EIGENEX_ERR_ARG, "scalar type of the basis and of the CSR operator differ");
   if (csr && (csr->ctx != c || csr->n_global != n_global)) return fail(EIGENEX_ERR_ARG, "csr belongs to another context or has another size");
@@ -4438,6 +4477,41 @@ int eigenex_ritz_vectors_complex(eigenex_basis_t b, int nvec, int nev, const dou
 int eigenex_krylov_combine(eigenex_basis_t b, int nvec, int ncols, const double* C_re, const double* C_im, int ldc, double* X,
                            int64_t ldx) {
   return C_im ? ritz_vectors_cplx(b, nvec, ncols, C_re, C_im, ldc, X, ldx, true) : ritz_vectors_real(b, nvec, ncols, C_re, ldc, X, ldx, true);
+}
+
+// The one-column case of eigenex_krylov_combine with the result left on the device: the same launches (k_ritz as ritz_raw makes it,
+// and k_ritz_combine for complex coefficients) into the same scratch, then a device copy into dst where the other copies to the
+// host.  ritz_raw itself is not called: it synchronises for its staging buffer, which here lives until the one synchronisation.
+int eigenex_krylov_combine_to(eigenex_basis_t b, int nvec, const double* C_re, const double* C_im, int dst_ref) {
+  if (!b || nvec < 1 || nvec > b->cap || !C_re) return fail(EIGENEX_ERR_ARG, "eigenex_krylov_combine_to: bad argument");
+  if (!(dst_ref == EIGENEX_VEC_W || dst_ref == EIGENEX_VEC_V || (dst_ref >= nvec && dst_ref < b->cap)))
+    return fail(EIGENEX_ERR_ARG, "eigenex_krylov_combine_to: dst must be EIGENEX_VEC_W, EIGENEX_VEC_V or a basis column at or above nvec (the columns below are read)");
+  if (C_im && b->es != 2) return fail(EIGENEX_ERR_ARG, "eigenex_krylov_combine_to: complex coefficients need a complex state (the result stays in one of its vectors)");
+  if (b->sh.size() != 1) return fail(EIGENEX_ERR_STATE, "eigenex_krylov_combine_to: a state of one shard is needed");
+  CHK(enter_settled(b));
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  BasisShard& s = b->sh[0];
+  const int E = 8;
+  DeviceBuffer<double> d_S, out;
+  HIPCHK(d_S.alloc((size_t)nvec * E));
+  if (!s.X) HIPCHK(s.X.alloc((size_t)s.ldd * E));
+  if (C_im) HIPCHK(out.alloc((size_t)s.ldv * 2));
+  const int ne = C_im ? 2 : 1;
+  std::vector<double> St((size_t)nvec * E, 0.0);  // packed [nvec][8] as in ritz_raw; lives until the synchronisation below
+  for (int j = 0; j < nvec; ++j) {
+    St[(size_t)j * E] = C_re[j];
+    if (C_im) St[(size_t)j * E + 1] = C_im[j];
+  }
+  HIPCHK(hipMemcpyAsync(d_S, St.data(), sizeof(double) * St.size(), hipMemcpyHostToDevice, c->stream));
+  {
+    ProfScope ps(c, EIGENEX_K_RITZ, 8.0 * s.nd * nvec + 8.0 * s.nd * ne);
+    launch_ritz(c->stream, s.V, s.ldd, nvec, d_S, E, ne, s.X, s.ldd, s.nd, s.partials, s.pstride, s.g_vec);  // (the norms in partials: unused)
+  }
+  if (C_im) launch_ritz_combine(c->stream, s.X, s.ldd, 1, s.nloc, s.es, out, s.ldv, s.partials, s.pstride, s.g_vec);
+  HIPCHK(hipMemcpyAsync(vec_ptr(s, b->cap, b->nq, dst_ref), C_im ? out.get() : s.X.get(), sizeof(double) * s.nd, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation of the result: the scratch lives until here
+  return 0;
 }
 
 }  // extern "C"

@@ -11,7 +11,8 @@
 //   eigenex_zarnoldi_solver_*  ArnoldiEigenSolver<std::complex<double>>
 // plus eigenex_[z]trlanczos_solver_* (ThickRestartLanczosEigenSolver), eigenex_[z]kschur_solver_* (KrylovSchurEigenSolver) and
 // eigenex_[z]flanczos_solver_* (FilteredLanczosEigenSolver); eigenex_[z]density_solver_* (SpectralDensitySolver);
-// eigenex_spin_dynamics_solver_* (SpinDynamicsSolver); eigenex_spin_entanglement_solver_* (SpinEntanglementSolver).
+// eigenex_spin_dynamics_solver_* (SpinDynamicsSolver); eigenex_spin_entanglement_solver_* (SpinEntanglementSolver);
+// eigenex_spin_evolution_solver_* (SpinTimeEvolutionSolver).
 // Complex data cross this boundary as interleaved (re, im) doubles.
 #include <complex>
 #include <cstring>
@@ -29,6 +30,7 @@
 #include "cmpt/eigen_ex/spin_correlations.hpp"
 #include "cmpt/eigen_ex/spin_dynamics.hpp"
 #include "cmpt/eigen_ex/spin_entanglement.hpp"
+#include "cmpt/eigen_ex/spin_evolution.hpp"
 #include "cmpt/eigen_ex/thick_restart_lanczos.hpp"
 #include "cmpt/eigen_ex/triplets_operator.hpp"
 
@@ -939,6 +941,112 @@ int eigenex_spin_dynamics_solver_static_structure_factor_z(void* p, double q, do
 }
 const char* eigenex_spin_dynamics_solver_log_line(void* p, int64_t i) {
   auto& log = static_cast<SpinDynamicsBox*>(p)->es.log();
+  return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
+}
+
+// ---- SpinTimeEvolutionSolver (spin_evolution.hpp).  The model crosses as for SpinDynamicsSolver; vectors are interleaved (re, im).
+struct SpinEvolutionBox {
+  std::shared_ptr<device::Context> ctx;
+  SpinTimeEvolutionSolver es;
+  std::vector<double> out;  // the last vector-valued result, until the next one
+};
+void* eigenex_spin_evolution_solver_create(void) {
+  try {
+    return new SpinEvolutionBox();
+  } catch (const std::exception& e) {
+    g_serr = e.what();
+    return nullptr;
+  }
+}
+void eigenex_spin_evolution_solver_destroy(void* p) { delete static_cast<SpinEvolutionBox*>(p); }
+int eigenex_spin_evolution_solver_set_model(void* p, eigenex_context_t ctx, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                                            const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null, int n_up) {
+  return guard([&] {
+    auto* b = static_cast<SpinEvolutionBox*>(p);
+    b->ctx = device::Context::borrow(ctx);
+    SpinHalfModel model(n_sites);
+    for (int k = 0; k < n_bonds; ++k) model.addBond(site_i[k], site_j[k], jz[k], jxy[k]);
+    for (int i = 0; i < n_sites; ++i) {
+      if (hz_or_null) model.setFieldZ(i, hz_or_null[i]);
+      if (hx_or_null) model.setFieldX(i, hx_or_null[i]);
+    }
+    b->es.setModel(b->ctx, model, n_up);
+  });
+}
+// v: n entries, interleaved (re, im) if is_complex, else real
+int eigenex_spin_evolution_solver_set_state(void* p, const double* v, int64_t n, int is_complex) {
+  return guard([&] {
+    auto& es = static_cast<SpinEvolutionBox*>(p)->es;
+    if (is_complex)
+      es.setState(make_vector<std::complex<double>>(v, n));
+    else
+      es.setState(make_vector<double>(v, n));
+  });
+}
+int eigenex_spin_evolution_solver_set_product_state(void* p, uint32_t bits) {
+  return guard([&] { static_cast<SpinEvolutionBox*>(p)->es.setProductState(bits); });
+}
+int eigenex_spin_evolution_solver_set_krylov_dimension(void* p, int64_t m) {
+  return guard([&] { static_cast<SpinEvolutionBox*>(p)->es.setKrylovDimension((Index)m); });
+}
+int eigenex_spin_evolution_solver_set_tolerance(void* p, double tol) {
+  return guard([&] { static_cast<SpinEvolutionBox*>(p)->es.setTolerance(tol); });
+}
+int eigenex_spin_evolution_solver_evolve(void* p, double dt, int64_t* substeps) {
+  return guard([&] {
+    const Index s = static_cast<SpinEvolutionBox*>(p)->es.evolve(dt);
+    if (substeps) *substeps = (int64_t)s;
+  });
+}
+// scalars[5] = (time, errorBound, totalErrorBound, initialNorm, operatorApplications); counts[4] = (log lines, info, sites, rows of out)
+int eigenex_spin_evolution_solver_status(void* p, double* scalars, int64_t* counts) {
+  return guard([&] {
+    auto* b = static_cast<SpinEvolutionBox*>(p);
+    auto& es = b->es;
+    if (scalars)
+      scalars[0] = es.time(), scalars[1] = es.errorBound(), scalars[2] = es.totalErrorBound(), scalars[3] = es.initialNorm(),
+      scalars[4] = (double)es.operatorApplications();
+    if (counts) counts[0] = (int64_t)es.log().size(), counts[1] = (int64_t)es.info(), counts[2] = es.sites(), counts[3] = (int64_t)b->out.size();
+  });
+}
+// what: 0 normSquared, 1 energy, 2 overlapWithInitial (re, im); out[2]
+int eigenex_spin_evolution_solver_scalar(void* p, int what, double* out) {
+  return guard([&] {
+    auto& es = static_cast<SpinEvolutionBox*>(p)->es;
+    out[0] = out[1] = 0.0;
+    if (what == 0) out[0] = es.normSquared();
+    else if (what == 1) out[0] = es.energy();
+    else if (what == 2) {
+      const std::complex<double> z = es.overlapWithInitial();
+      out[0] = z.real(), out[1] = z.imag();
+    } else throw LanczosException("eigenex_spin_evolution_solver_scalar: what must be 0..2");
+  });
+}
+// what: 0 magnetisation (sites), 1 correlationsZZ, 2 correlationsXY (sites^2, row-major), 3 state (2 * rows, interleaved).  Forms the
+// result and returns its length in doubles; eigenex_spin_evolution_solver_fetch copies it out.
+int eigenex_spin_evolution_solver_measure(void* p, int what, int64_t* len) {
+  return guard([&] {
+    auto* b = static_cast<SpinEvolutionBox*>(p);
+    auto& es = b->es;
+    if (what == 0) b->out = es.magnetisation();
+    else if (what == 1) b->out = es.correlationsZZ();
+    else if (what == 2) b->out = es.correlationsXY();
+    else if (what == 3) {
+      const auto v = es.state();
+      b->out.assign(reinterpret_cast<const double*>(v.data()), reinterpret_cast<const double*>(v.data()) + 2 * v.size());
+    } else throw LanczosException("eigenex_spin_evolution_solver_measure: what must be 0..3");
+    if (len) *len = (int64_t)b->out.size();
+  });
+}
+int eigenex_spin_evolution_solver_fetch(void* p, double* out) {
+  return guard([&] {
+    auto* b = static_cast<SpinEvolutionBox*>(p);
+    std::copy(b->out.begin(), b->out.end(), out);
+    std::vector<double>().swap(b->out);
+  });
+}
+const char* eigenex_spin_evolution_solver_log_line(void* p, int64_t i) {
+  auto& log = static_cast<SpinEvolutionBox*>(p)->es.log();
   return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
 }
 

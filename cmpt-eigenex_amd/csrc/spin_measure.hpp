@@ -115,4 +115,41 @@ inline void spin_measure_host(const SpinMeasureArgs& a, const double* x, double*
   if (norm2) *norm2 = nrm;
 }
 
+// The Hermitian definitions for a complex vector, x interleaved (re, im), 2 * spin_measure_rows doubles:
+//   norm2   = sum_s |x_s|^2
+//   diag[t] = sum_s (prod_{i in mask} sigma_i(s)) |x_s|^2
+//   flip[t] = sum_s [predicate as above] Re(conj(x_s) x_{s ^ mask})
+// so the normalisations above hold unchanged.  Rows ascending; every sum takes two fmas per row, the product of the real parts and
+// then the product of the imaginary parts.  With every imaginary part +0 the sums are spin_measure_host's: fma(0, 0, a) is a.
+inline void spin_measure_host_z(const SpinMeasureArgs& a, const double* x, double* diag_out, double* flip_out, double* norm2) {
+  const bool sector = a.n_up != -1;
+  const int64_t n = spin_measure_rows(a);
+  SpinSectorTables t;
+  if (sector && a.n_flip > 0) spin_sector_build_tables(a.n_sites, a.n_up, t);
+  std::vector<double> dg((size_t)a.n_diag, 0.0), fl((size_t)a.n_flip, 0.0);
+  double nrm = 0.0;
+  for (int64_t r = 0; r < n; ++r) {
+    const uint32_t s = sector ? spin_sector_unrank(a.n_sites, a.n_up, r) : (uint32_t)r;
+    const double xr = x[2 * r], xi = x[2 * r + 1];
+    nrm = std::fma(xr, xr, nrm);
+    nrm = std::fma(xi, xi, nrm);
+    for (int i = 0; i < a.n_diag; ++i) {
+      const bool neg = spin_parity(~s & a.diag_masks[i]);
+      dg[(size_t)i] = std::fma(neg ? -xr : xr, xr, dg[(size_t)i]);
+      dg[(size_t)i] = std::fma(neg ? -xi : xi, xi, dg[(size_t)i]);
+    }
+    for (int i = 0; i < a.n_flip; ++i) {
+      const uint32_t m = a.flip_masks[i];
+      if ((m & (m - 1)) != 0 && !spin_parity(s & m)) continue;  // a pair with equal spins has no entry
+      const uint32_t s2 = s ^ m;
+      const int64_t r2 = sector ? (int64_t)spin_sector_rank(t, s2) : (int64_t)s2;
+      fl[(size_t)i] = std::fma(xr, x[2 * r2], fl[(size_t)i]);
+      fl[(size_t)i] = std::fma(xi, x[2 * r2 + 1], fl[(size_t)i]);
+    }
+  }
+  for (int i = 0; i < a.n_diag && diag_out; ++i) diag_out[i] = dg[(size_t)i];
+  for (int i = 0; i < a.n_flip && flip_out; ++i) flip_out[i] = fl[(size_t)i];
+  if (norm2) *norm2 = nrm;
+}
+
 }  // namespace eigenex

@@ -1,6 +1,7 @@
 // The row walk of the matrix-free spin-1/2 kernels (kernels.hip: k_spin_spmv<SECTOR>, k_spin_measure<SECTOR>,
-// k_spin_site_apply<SECTOR>, and through spin_rdm_rows.hpp k_spin_rdm<SECTOR, TILE>), shared by the
-// device code and by the host replays tests/cpp/spin_{model,sector,measure,site,rdm}_sanitize.cpp, which run it under AddressSanitizer +
+// k_spin_site_apply<SECTOR>, their complex-state forms k_spin_spmv_z<SECTOR> and k_spin_measure_z<SECTOR>, and through
+// spin_rdm_rows.hpp k_spin_rdm<SECTOR, TILE>), shared by the
+// device code and by the host replays tests/cpp/spin_{model,sector,measure,site,rdm,complex}_sanitize.cpp, which run it under AddressSanitizer +
 // UBSan.  The kernels and the replays call THESE functions, so what a replay proves about them (every load inside its array, the
 // state equal to spin_sector_unrank, the sums equal to the CSR row loop and to spin_measure_host bit for bit) holds for the
 // kernels' rows as compiled.  No device construct in here: plain C++11.  spin_write_rows, spin_sector_unrank, spin_sector_rank
@@ -115,6 +116,52 @@ EIGENEX_HD void spin_measure_flips(double xs, const bool* on, const double* xv, 
 EIGENEX_HD void spin_measure_diagonals(double xs, uint32_t s, const uint32_t* dmask, double* dg) {
   EIGENEX_UNROLL
   for (int t = 0; t < kSpinBatch; ++t) dg[t] = std::fma(spin_odd(~s & dmask[t]) ? -xs : xs, xs, dg[t]);
+}
+
+// ---- complex vectors (kernels.hip: k_spin_spmv_z<SECTOR>, k_spin_measure_z<SECTOR>; host replay: spin_complex_sanitize.cpp) ----
+// The operator is the same real one, so the lane's state, the diagonal and phase 1 above serve both parts of a complex vector
+// unchanged and once per row.  Phases 2 and 3 take an element as (re, im): x(i) returns a SpinZ, which the kernels fill from one
+// 16-byte load.  Each part is the real walk's sum of that part: the same products, rounded and added in the same order.
+struct SpinZ {
+  double re, im;
+};
+
+// phase 2
+template <class Vector>
+EIGENEX_HD void spin_gather_z(const Vector& x, const uint32_t* base, const uint32_t* low, SpinZ* xv) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) xv[t] = x(base[t] + low[t]);
+}
+
+// phase 3 of the operator: spin_add_flips on each part
+EIGENEX_HD SpinZ spin_add_flips_z(SpinZ yr, const double* fval, const bool* on, const SpinZ* xv, double scale) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t)
+    if (on[t]) {
+      yr.re = add_product_nofma(yr.re, fval[t], xv[t].re * scale);
+      yr.im = add_product_nofma(yr.im, fval[t], xv[t].im * scale);
+    }
+  return yr;
+}
+
+// phase 3 of a measurement (spin_measure.hpp: flip[t] of a complex vector, Re(conj(x_s) x_{s ^ mask})): the real part's fma, then
+// the imaginary part's, on every row
+EIGENEX_HD void spin_measure_flips_z(SpinZ xs, const bool* on, const SpinZ* xv, double* fl) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) {
+    fl[t] = std::fma(xs.re, on[t] ? xv[t].re : 0.0, fl[t]);
+    fl[t] = std::fma(xs.im, on[t] ? xv[t].im : 0.0, fl[t]);
+  }
+}
+
+// a batch of diagonal terms of a measurement (diag[t] of a complex vector, sign |x_s|^2): real part, then imaginary part
+EIGENEX_HD void spin_measure_diagonals_z(SpinZ xs, uint32_t s, const uint32_t* dmask, double* dg) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) {
+    const bool neg = spin_odd(~s & dmask[t]);
+    dg[t] = std::fma(neg ? -xs.re : xs.re, xs.re, dg[t]);
+    dg[t] = std::fma(neg ? -xs.im : xs.im, xs.im, dg[t]);
+  }
 }
 
 // ---- a sum of site operators (spin_site.hpp; kernels.hip: k_spin_site_apply<SECTOR>), one row of the DESTINATION per lane ----

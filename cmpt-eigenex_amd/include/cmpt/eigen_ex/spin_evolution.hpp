@@ -1,0 +1,384 @@
+// Real-time evolution |psi(t)> = exp(-i H t) |psi_0> of a state of a spin-1/2 model by Krylov (Lanczos) propagation (T. J. Park
+// and J. C. Light, J. Chem. Phys. 85 (1986) 5870), matrix-free and without a vector visiting the host between time steps.
+//
+// NOT part of the reference.  The state is a complex vector over the rows of a SpinHalfModel (full space, or the sector of nUp
+// sites up) and lives in the work vector W of a complex Krylov state on device::spinHalfComplexOperator, the matrix-free operator
+// for complex states (eigenex_spin_upload_z / eigenex_spin_sector_upload_z: the same real Hamiltonian).  psi_0 is kept in the
+// last basis column of that state.  setState normalises: the device holds psi / |psi_0| and state() multiplies the norm back.
+//
+// A sub-step.  m + 1 calls of the Lanczos step from W (eigenex_lanczos_enqueue: the complex state takes the two-sweep path, full
+// re-orthogonalisation) give the basis V_m, T_m = tridiag(alpha, beta) and beta_m, the coupling to the next vector.  T_m = S theta
+// S^T on the host (small_eigen.hpp), the coefficients of the step tau are c(tau) = S exp(-i tau theta) S^T e_1, and
+// psi <- V_m c(tau) by eigenex_krylov_combine_to(..., EIGENEX_VEC_W), followed by eigenex_basis_clear.  The Lanczos start divides W
+// by its norm, so every sub-step starts from a unit vector.
+//
+// Step control.  The error e(s) = psi_Krylov(s) - psi(s) of a sub-step obeys e' = -i H e - i beta_m [exp(-i s T_m)]_{m,1} v_{m+1}
+// with e(0) = 0 and a unitary propagator, hence
+//   |e(tau)| <= B(tau) = beta_m  int_0^tau |[exp(-i s T_m)]_{m,1}| ds,      [exp(-i s T_m)]_{m,1} = sum_j S(m,j) exp(-i s theta_j) S(1,j),
+// a bound in exact arithmetic.  B is evaluated on the host by the composite Simpson rule with kQuadPanels = 512 panels (513
+// equidistant nodes on [0, tau]).  A sub-step takes the largest tau <= remaining with B(tau) <= tol * tau / |dt|: tau = remaining
+// if that passes, else a bisection of [0, remaining] of exactly 60 halvings, keeping the largest passing point; over one
+// evolve(dt) the accepted B therefore add up to at most tol.  errorBound() is that sum for the last evolve(dt),
+// totalErrorBound() the sum since setState.  A breakdown (the Lanczos run stops on an invariant subspace, or m is at least the
+// dimension, then m is the dimension and beta_m is not formed) makes the step exact: B = 0, tau = remaining.  A run stops where a
+// coupling beta_k falls to the state's breakdown threshold (the library's default, 1e-12) or below, so "exact" there means up to
+// that neglected coupling: by the bound above it adds at most threshold * tau to the error, which errorBound() does not count.
+// Coefficients that are not finite end the call with NumericalIssue.  dt may be negative.
+//
+// Measurements read W where it is: normSquared(), magnetisation(), correlationsZZ() and correlationsXY() through
+// eigenex_spin_measure (Hermitian sums of a complex vector), energy() = Re <psi|H|psi> / <psi|psi> through one operator application
+// and its dot, overlapWithInitial() = <psi_0|psi(t)> through eigenex_dots with the kept column.  state() downloads.
+//
+// Out of scope: complex couplings (Sy, Dzyaloshinskii-Moriya terms); momentum sectors; S(q, w) with complex coefficients in one
+// run; time-dependent Hamiltonians; Chebyshev propagators; reduced density matrices and site operators of complex states; more
+// than one GPU (the matrix-free spin operators are one shard).
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <complex>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "lanczos.hpp"
+#include "small_eigen.hpp"
+#include "spin_operator.hpp"
+
+namespace cmpt {
+namespace EigenEx {
+
+class SpinTimeEvolutionSolver {
+ public:
+  using Index = EigenEx::Index;
+  using Complex = std::complex<double>;
+  using VectorType = DenseVector<Complex>;
+  using RealVectorType = DenseVector<double>;
+
+  static constexpr int kQuadPanels = 512;    // composite Simpson: kQuadPanels + 1 nodes
+  static constexpr int kBisections = 60;
+  static constexpr Index kMaxSubSteps = 1000000;
+
+  static std::string headERROR() { return std::string("ERROR     "); }
+  static std::string headINFO() { return std::string("INFO      "); }
+
+  // nUp = -1: the full space (up to 30 sites); else the sector of nUp sites up (up to 32 sites, no transverse field)
+  SpinTimeEvolutionSolver& setModel(const std::shared_ptr<device::Context>& ctx, const SpinHalfModel& model, int nUp = -1) {
+    ctx_ = ctx, model_ = model, nUp_ = nUp, haveModel_ = true, haveState_ = false;
+    dev_.release();  // the state goes before its operator
+    op_.reset();
+    return *this;
+  }
+  // the Krylov dimension m of a sub-step (default 30, at least 2) and the error budget of one evolve(dt) (default 1e-10)
+  SpinTimeEvolutionSolver& setKrylovDimension(Index m) {
+    if (m < 2) {  // refused: the dimension and the state stay as they were
+      begin_("setKrylovDimension");
+      invalid_("invalid input: setKrylovDimension needs at least 2");
+      return *this;
+    }
+    if (m != m_ && dev_.alive()) {  // the state moves to a Krylov state of the new capacity
+      const VectorType psi = dev_.download<Complex>(EIGENEX_VEC_W), psi0 = dev_.download<Complex>(EIGENEX_VEC_COL(dev_.capacity() - 1));
+      m_ = m;
+      place_(psi, psi0);
+    }
+    m_ = m;
+    return *this;
+  }
+  SpinTimeEvolutionSolver& setTolerance(double tol) {
+    tol_ = tol;
+    return *this;
+  }
+  Index krylovDimension() const { return m_; }
+  double tolerance() const { return tol_; }
+
+  // a host vector over the rows of the model's space or sector; normalised on upload, the norm is kept (initialNorm())
+  SpinTimeEvolutionSolver& setState(const VectorType& v) {
+    begin_("setState");
+    if (!ready_()) return *this;
+    if (v.size() != rows_()) return invalid_("invalid input: the state must have one entry per row of the model's space or sector"), *this;
+    const double nrm = v.norm();
+    if (!(nrm > 0.0) || !std::isfinite(nrm)) return invalid_("invalid input: the state is zero (or not finite)"), *this;
+    VectorType u(v.size());
+    for (Index r = 0; r < v.size(); ++r) u[r] = v[r] / nrm;
+    norm0_ = nrm;
+    place_(u, u);
+    reset_();
+    return *this;
+  }
+  SpinTimeEvolutionSolver& setState(const RealVectorType& v) {
+    VectorType z(v.size());
+    for (Index r = 0; r < v.size(); ++r) z[r] = Complex(v[r], 0.0);
+    return setState(z);
+  }
+  // the basis state with site i up where bit i of `bits` is set, e.g. the Neel state 0b0101...; it must lie in the sector
+  SpinTimeEvolutionSolver& setProductState(std::uint32_t bits) {
+    begin_("setProductState");
+    if (!ready_()) return *this;
+    const int L = model_.sites();
+    if (L < 32 && (bits >> L) != 0u) return invalid_("invalid input: the product state names a site outside 0..sites-1"), *this;
+    if (nUp_ >= 0 && upSites_(bits) != nUp_) return invalid_("invalid input: the product state does not lie in the sector (its number of up sites differs)"), *this;
+    const Index row = nUp_ < 0 ? static_cast<Index>(bits) : rank_(bits);
+    if (row < 0) return invalid_("invalid input: the product state was not found among the sector's states"), *this;
+    VectorType u(rows_(), Complex(0.0, 0.0));
+    u[row] = Complex(1.0, 0.0);
+    norm0_ = 1.0;
+    place_(u, u);
+    reset_();
+    return *this;
+  }
+
+  // psi <- exp(-i H dt) psi; returns the number of sub-steps (0 after an error: info(), log())
+  Index evolve(double dt) {
+    begin_("evolve");
+    lastBound_ = 0.0;
+    if (!ready_()) return 0;
+    if (!haveState_) return invalid_("invalid input: no state (setState, setProductState)");
+    if (!std::isfinite(dt)) return invalid_("invalid input: dt is not finite");
+    if (!(tol_ > 0.0) || !std::isfinite(tol_)) return invalid_("invalid input: setTolerance needs a positive tolerance");
+    const double total = std::fabs(dt), sign = dt < 0.0 ? -1.0 : 1.0;
+    double remaining = total;
+    Index steps = 0;
+    while (remaining > 0.0) {
+      if (steps >= kMaxSubSteps) return failed_("more than 10^6 sub-steps: the Krylov dimension is too small for this tolerance");
+      double tau = 0.0, bound = 0.0;
+      if (!subStep_(remaining, total, sign, tau, bound)) return 0;
+      lastBound_ += bound, totalBound_ += bound;
+      time_ += sign * tau;
+      remaining = tau >= remaining ? 0.0 : remaining - tau;
+      ++steps;
+    }
+    log_.push_back(headINFO() + "sub-steps: " + std::to_string(steps) + ", error bound of this call: " + std::to_string(lastBound_));
+    return steps;
+  }
+
+  double time() const { return time_; }
+  double errorBound() const { return lastBound_; }
+  double totalErrorBound() const { return totalBound_; }
+  Index operatorApplications() const { return applications_; }
+  double initialNorm() const { return norm0_; }
+
+  // <psi|psi> of the device vector (1 up to rounding: the kept norm is not in it)
+  double normSquared() {
+    double n2 = 0.0;
+    if (!measurable_()) return 0.0;
+    device::check(eigenex_spin_measure(dev_.handle(), EIGENEX_VEC_W, 0, nullptr, 0, nullptr, nullptr, nullptr, &n2), "eigenex_spin_measure");
+    return n2;
+  }
+  // Re <psi|H|psi> / <psi|psi>: one operator application and its dot
+  double energy() {
+    if (!measurable_()) return 0.0;
+    double dot[2] = {0.0, 0.0};
+    device::check(eigenex_apply(dev_.handle(), EIGENEX_VEC_W, EIGENEX_VEC_V, 0.0, dot), "eigenex_apply");
+    ++applications_;
+    return dot[0] / normSquared();
+  }
+  // <Sz_i>, i < sites
+  std::vector<double> magnetisation() {
+    if (!measurable_()) return {};
+    const std::size_t L = static_cast<std::size_t>(model_.sites());
+    std::vector<std::uint32_t> masks;
+    for (std::size_t i = 0; i < L; ++i) masks.push_back(std::uint32_t(1) << i);
+    std::vector<double> d(L, 0.0);
+    double n2 = 0.0;
+    device::check(eigenex_spin_measure(dev_.handle(), EIGENEX_VEC_W, static_cast<int>(L), masks.data(), 0, nullptr, d.data(), nullptr, &n2), "eigenex_spin_measure");
+    for (double& x : d) x /= 2.0 * n2;
+    return d;
+  }
+  // <Sz_i Sz_j> and <Sx_i Sx_j + Sy_i Sy_j>, row-major sites x sites (i = j: 1/4 and 1/2)
+  std::vector<double> correlationsZZ() { return pairs_(true); }
+  std::vector<double> correlationsXY() { return pairs_(false); }
+  // <psi_0|psi(t)>, both of unit norm
+  Complex overlapWithInitial() {
+    if (!measurable_()) return Complex(0.0, 0.0);
+    double h[2] = {0.0, 0.0};
+    device::check(eigenex_dots(dev_.handle(), EIGENEX_VEC_W, dev_.capacity() - 1, 1, 1, 0, h), "eigenex_dots");
+    return Complex(h[0], h[1]);
+  }
+  // psi(t) on the host, the kept norm multiplied back
+  VectorType state() {
+    if (!measurable_()) return VectorType();
+    VectorType v = dev_.download<Complex>(EIGENEX_VEC_W);
+    if (norm0_ != 1.0)
+      for (Index r = 0; r < v.size(); ++r) v[r] *= norm0_;
+    return v;
+  }
+
+  int sites() const { return haveModel_ ? model_.sites() : 0; }
+  int sitesUp() const { return nUp_; }
+  ComputationInfo info() const { return info_; }
+  const std::vector<std::string>& log() const { return log_; }
+
+  // B(tau) of the header for T = S diag(theta) S^T of dimension k (S column-major): beta_m times the Simpson sum
+  static double errorIntegral(const std::vector<double>& theta, const std::vector<double>& S, int k, double betaM, double tau) {
+    std::vector<double> w(static_cast<std::size_t>(k));
+    for (int j = 0; j < k; ++j) w[static_cast<std::size_t>(j)] = S[static_cast<std::size_t>(j) * k + (k - 1)] * S[static_cast<std::size_t>(j) * k];
+    const double hstep = tau / kQuadPanels;
+    double sum = 0.0;
+    for (int q = 0; q <= kQuadPanels; ++q) {
+      const double s = hstep * q;
+      double re = 0.0, im = 0.0;
+      for (int j = 0; j < k; ++j) {
+        re += w[static_cast<std::size_t>(j)] * std::cos(s * theta[static_cast<std::size_t>(j)]);
+        im -= w[static_cast<std::size_t>(j)] * std::sin(s * theta[static_cast<std::size_t>(j)]);
+      }
+      const double weight = (q == 0 || q == kQuadPanels) ? 1.0 : ((q & 1) ? 4.0 : 2.0);
+      sum += weight * std::sqrt(re * re + im * im);
+    }
+    return betaM * sum * hstep / 3.0;
+  }
+
+ private:
+  void begin_(const char* who) {
+    log_.clear();
+    log_.push_back(headINFO() + "SpinTimeEvolutionSolver::" + who + "(...) was called");
+    info_ = Success;
+  }
+  Index invalid_(const std::string& what) {
+    log_.push_back(headERROR() + what);
+    info_ = InvalidInput;
+    return 0;
+  }
+  Index failed_(const std::string& what) {
+    log_.push_back(headERROR() + what);
+    info_ = NumericalIssue;
+    return 0;
+  }
+  void reset_() { time_ = 0.0, lastBound_ = 0.0, totalBound_ = 0.0, applications_ = 0, haveState_ = true; }
+  Index rows_() const { return static_cast<Index>(op_->rows()); }
+  bool measurable_() const { return haveState_ && dev_.alive(); }
+
+  // the model, the settings and the operator; false after invalid_()
+  bool ready_() {
+    if (!haveModel_ || !ctx_) return invalid_("invalid input: no model (setModel)"), false;
+    try {
+      if (!op_) op_ = device::spinHalfComplexOperator(ctx_, model_, nUp_);
+    } catch (const LanczosException& e) {
+      return invalid_(std::string("invalid input: the model has no such operator: ") + e.what()), false;
+    }
+    return true;
+  }
+  Index krylov_() const { return std::min<Index>(m_, rows_()); }
+  // a complex Krylov state of m + 2 columns: the run's m + 1 and psi_0 in the last
+  void place_(const VectorType& psi, const VectorType& psi0) {
+    const int cap = static_cast<int>(krylov_() + 2);
+    if (!dev_.alive() || dev_.capacity() != cap)
+      dev_.create(ctx_, op_, rows_(), cap, 0, true);
+    else
+      device::check(eigenex_basis_clear(dev_.handle()), "eigenex_basis_clear");
+    dev_.upload(EIGENEX_VEC_W, psi);
+    dev_.upload(EIGENEX_VEC_COL(cap - 1), psi0);
+  }
+  static int upSites_(std::uint32_t bits) {
+    int c = 0;
+    for (; bits; bits &= bits - 1) ++c;
+    return c;
+  }
+  // the row of a state of the sector, from the library's own ordering (eigenex_spin_sector_states: the states ascending) by
+  // bisection over the ranks; -1 if it is not among them
+  Index rank_(std::uint32_t bits) const {
+    Index lo = 0, hi = rows_() - 1;
+    while (lo <= hi) {
+      const Index mid = lo + (hi - lo) / 2;
+      std::uint32_t s = 0;
+      device::check(eigenex_spin_sector_states(model_.sites(), nUp_, mid, 1, &s), "eigenex_spin_sector_states");
+      if (s == bits) return mid;
+      if (s < bits)
+        lo = mid + 1;
+      else
+        hi = mid - 1;
+    }
+    return -1;
+  }
+
+  bool subStep_(double remaining, double total, double sign, double& tau, double& bound) {
+    const Index n = rows_(), m = krylov_();
+    const bool whole = m >= n;  // the Krylov space is the space: exact without beta_m
+    const int calls = static_cast<int>(whole ? m : m + 1);
+    device::check(eigenex_lanczos_enqueue(dev_.handle(), calls), "eigenex_lanczos_enqueue");
+    eigenex_state_t st;
+    std::vector<double> alpha(static_cast<std::size_t>(m) + 4, 0.0), beta(static_cast<std::size_t>(m) + 4, 0.0);
+    device::check(eigenex_lanczos_state(dev_.handle(), &st, alpha.data(), beta.data()), "eigenex_lanczos_state");
+    applications_ += st.nalpha;
+    const int k = std::min<int>(st.nalpha, static_cast<int>(m));
+    if (k < 1) return failed_("the state failed the breakdown threshold of the Lanczos run (it is zero or not finite)"), false;
+    for (int j = 0; j < k; ++j)
+      if (!std::isfinite(alpha[static_cast<std::size_t>(j)]) || (j + 1 < k && !std::isfinite(beta[static_cast<std::size_t>(j)])))
+        return failed_("the Lanczos coefficients are not finite"), false;
+    const bool exact = whole || st.stopped != 0 || st.nbeta < static_cast<int>(m);
+    std::vector<double> theta, S;
+    if (!small_eigen::tridiagonal(alpha.data(), beta.data(), k, theta, &S)) return failed_("the tridiagonal eigenproblem did not converge"), false;
+    const double betaM = exact ? 0.0 : beta[static_cast<std::size_t>(m) - 1];
+    if (!std::isfinite(betaM)) return failed_("the Lanczos coefficients are not finite"), false;
+    tau = remaining, bound = 0.0;
+    if (!exact) {
+      const auto passes = [&](double t, double& B) {
+        B = errorIntegral(theta, S, k, betaM, t);
+        return B <= tol_ * t / total;
+      };
+      double B = 0.0;
+      if (passes(remaining, B)) {
+        bound = B;
+      } else {
+        double lo = 0.0, hi = remaining, Blo = 0.0;
+        for (int it = 0; it < kBisections; ++it) {
+          const double mid = 0.5 * (lo + hi);
+          if (passes(mid, B))
+            lo = mid, Blo = B;
+          else
+            hi = mid;
+        }
+        if (!(lo > 0.0)) return failed_("no step passes the tolerance: the Krylov dimension is too small"), false;
+        tau = lo, bound = Blo;
+      }
+    }
+    // c = S exp(-i sign tau theta) S^T e_1
+    std::vector<double> cre(static_cast<std::size_t>(k), 0.0), cim(static_cast<std::size_t>(k), 0.0);
+    for (int j = 0; j < k; ++j) {
+      const double ph = sign * tau * theta[static_cast<std::size_t>(j)], s0 = S[static_cast<std::size_t>(j) * k];
+      const double fr = std::cos(ph) * s0, fi = -std::sin(ph) * s0;
+      for (int r = 0; r < k; ++r) {
+        cre[static_cast<std::size_t>(r)] += S[static_cast<std::size_t>(j) * k + r] * fr;
+        cim[static_cast<std::size_t>(r)] += S[static_cast<std::size_t>(j) * k + r] * fi;
+      }
+    }
+    device::check(eigenex_krylov_combine_to(dev_.handle(), k, cre.data(), cim.data(), EIGENEX_VEC_W), "eigenex_krylov_combine_to");
+    device::check(eigenex_basis_clear(dev_.handle()), "eigenex_basis_clear");
+    return true;
+  }
+
+  std::vector<double> pairs_(bool zz) {
+    if (!measurable_()) return {};
+    const std::size_t L = static_cast<std::size_t>(model_.sites());
+    std::vector<std::uint32_t> masks;
+    for (std::size_t i = 0; i < L; ++i)
+      for (std::size_t j = i + 1; j < L; ++j) masks.push_back((std::uint32_t(1) << i) | (std::uint32_t(1) << j));
+    std::vector<double> raw(masks.size(), 0.0), out(L * L, 0.0);
+    double n2 = 0.0;
+    device::check(eigenex_spin_measure(dev_.handle(), EIGENEX_VEC_W, zz ? static_cast<int>(masks.size()) : 0, zz ? masks.data() : nullptr,
+                                       zz ? 0 : static_cast<int>(masks.size()), zz ? nullptr : masks.data(), zz ? raw.data() : nullptr,
+                                       zz ? nullptr : raw.data(), &n2),
+                  "eigenex_spin_measure");
+    std::size_t k = 0;
+    for (std::size_t i = 0; i < L; ++i) {
+      out[i * L + i] = zz ? 0.25 : 0.5;
+      for (std::size_t j = i + 1; j < L; ++j, ++k) out[i * L + j] = out[j * L + i] = raw[k] / ((zz ? 4.0 : 2.0) * n2);
+    }
+    return out;
+  }
+
+  std::shared_ptr<device::Context> ctx_;
+  SpinHalfModel model_;
+  bool haveModel_ = false, haveState_ = false;
+  int nUp_ = -1;
+  Index m_ = 30;
+  double tol_ = 1e-10;
+  std::shared_ptr<device::CsrOperator> op_;
+  detail::KrylovDevice dev_;
+  double norm0_ = 1.0, time_ = 0.0, lastBound_ = 0.0, totalBound_ = 0.0;
+  Index applications_ = 0;
+  ComputationInfo info_ = Success;
+  std::vector<std::string> log_;
+};
+
+}  // namespace EigenEx
+}  // namespace cmpt

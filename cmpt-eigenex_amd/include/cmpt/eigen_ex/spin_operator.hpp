@@ -139,6 +139,21 @@ inline std::shared_ptr<CsrOperator> spinHalfSectorOperator(std::shared_ptr<Conte
   return CsrOperator::adopt(std::move(ctx), h);
 }
 
+// the same two operators for complex states (eigenex_spin_upload_z, eigenex_spin_sector_upload_z): the same real Hamiltonian and
+// tables; a state created on such a handle is complex.  nUp = -1: the full space.
+inline std::shared_ptr<CsrOperator> spinHalfComplexOperator(std::shared_ptr<Context> ctx, const SpinHalfModel& model, int nUp = -1) {
+  eigenex_csr_t h = nullptr;
+  if (nUp < 0)
+    check(eigenex_spin_upload_z(ctx->handle(), model.sites(), model.bonds(), model.siteI(), model.siteJ(), model.jz(), model.jxy(),
+                                model.fieldZ(), model.fieldX(), &h),
+          "eigenex_spin_upload_z");
+  else
+    check(eigenex_spin_sector_upload_z(ctx->handle(), model.sites(), nUp, model.bonds(), model.siteI(), model.siteJ(), model.jz(),
+                                       model.jxy(), model.fieldZ(), model.fieldX(), &h),
+          "eigenex_spin_sector_upload_z");
+  return CsrOperator::adopt(std::move(ctx), h);
+}
+
 }  // namespace device
 }  // namespace EigenEx
 }  // namespace cmpt

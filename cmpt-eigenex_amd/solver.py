@@ -103,6 +103,23 @@ def lib():
         getattr(L, p + "static_structure_factor_z").argtypes = [_vp, C.c_double, _dp]
         getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
         getattr(L, p + "log_line").restype = C.c_char_p
+        p = "eigenex_spin_evolution_solver_"
+        getattr(L, p + "create").argtypes = []
+        getattr(L, p + "create").restype = _vp
+        getattr(L, p + "destroy").argtypes = [_vp]
+        getattr(L, p + "destroy").restype = None
+        getattr(L, p + "set_model").argtypes = [_vp, _vp, C.c_int, C.c_int, _ip32, _ip32, _dp, _dp, _dp, _dp, C.c_int]
+        getattr(L, p + "set_state").argtypes = [_vp, _dp, C.c_int64, C.c_int]
+        getattr(L, p + "set_product_state").argtypes = [_vp, C.c_uint32]
+        getattr(L, p + "set_krylov_dimension").argtypes = [_vp, C.c_int64]
+        getattr(L, p + "set_tolerance").argtypes = [_vp, C.c_double]
+        getattr(L, p + "evolve").argtypes = [_vp, C.c_double, _lp]
+        getattr(L, p + "status").argtypes = [_vp, _dp, _lp]
+        getattr(L, p + "scalar").argtypes = [_vp, C.c_int, _dp]
+        getattr(L, p + "measure").argtypes = [_vp, C.c_int, _lp]
+        getattr(L, p + "fetch").argtypes = [_vp, _dp]
+        getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
+        getattr(L, p + "log_line").restype = C.c_char_p
         p = "eigenex_spin_entanglement_solver_"
         getattr(L, p + "create").argtypes = []
         getattr(L, p + "create").restype = _vp
@@ -735,6 +752,129 @@ class SpinDynamicsSolver:
 
     def log(self):
         return [self._f("log_line")(self.h, i).decode() for i in range(self._sizes()["nlog"])]
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SpinTimeEvolutionSolver:
+    """SpinTimeEvolutionSolver (spin_evolution.hpp): |psi(t)> = exp(-i H t)|psi_0> of a spin-1/2 model by Krylov propagation on
+    the device, with an a-posteriori error bound per call.  The model is given as for SpinDynamicsSolver."""
+
+    def __init__(self):
+        self._L = lib()
+        self.h = _vp(self._L.eigenex_spin_evolution_solver_create())
+        if not self.h:
+            raise capi.EigenexError("solver create failed")
+        self._keep = []
+
+    def _f(self, name):
+        return getattr(self._L, "eigenex_spin_evolution_solver_" + name)
+
+    def setModel(self, ctx: capi.Context, n_sites, bonds, hz=None, hx=None, n_up=None):
+        i32 = C.POINTER(C.c_int32)
+        si = np.ascontiguousarray([b[0] for b in bonds], np.int32)
+        sj = np.ascontiguousarray([b[1] for b in bonds], np.int32)
+        jz = np.ascontiguousarray([b[2] for b in bonds], np.float64)
+        jxy = np.ascontiguousarray([b[3] for b in bonds], np.float64)
+        fz = None if hz is None else np.ascontiguousarray(hz, np.float64)
+        fx = None if hx is None else np.ascontiguousarray(hx, np.float64)
+        self._keep.append(ctx)
+        self._sites = int(n_sites)
+        _chk(self._f("set_model")(self.h, ctx.h, int(n_sites), si.size, si.ctypes.data_as(i32), sj.ctypes.data_as(i32), _d(jz), _d(jxy),
+                                  None if fz is None else _d(fz), None if fx is None else _d(fx), -1 if n_up is None else int(n_up)))
+        return self
+
+    def setState(self, v):
+        cplx = np.iscomplexobj(v)
+        a = np.ascontiguousarray(v, np.complex128 if cplx else np.float64)
+        _chk(self._f("set_state")(self.h, _d(a.view(np.float64)), a.size, int(cplx)))
+        return self
+
+    def setProductState(self, bits):
+        _chk(self._f("set_product_state")(self.h, int(bits)))
+        return self
+
+    def setKrylovDimension(self, m):
+        _chk(self._f("set_krylov_dimension")(self.h, int(m)))
+        return self
+
+    def setTolerance(self, tol):
+        _chk(self._f("set_tolerance")(self.h, float(tol)))
+        return self
+
+    def evolve(self, dt):
+        n = C.c_int64()
+        _chk(self._f("evolve")(self.h, float(dt), C.byref(n)))
+        return n.value
+
+    def _status(self):
+        sc, cnt = np.zeros(5), np.zeros(4, np.int64)
+        _chk(self._f("status")(self.h, _d(sc), cnt.ctypes.data_as(_lp)))
+        return sc, cnt
+
+    def time(self):
+        return self._status()[0][0]
+
+    def errorBound(self):
+        return self._status()[0][1]
+
+    def totalErrorBound(self):
+        return self._status()[0][2]
+
+    def initialNorm(self):
+        return self._status()[0][3]
+
+    def operatorApplications(self):
+        return int(self._status()[0][4])
+
+    def info(self):
+        return INFO[int(self._status()[1][1])]
+
+    def _scalar(self, what):
+        out = np.zeros(2)
+        _chk(self._f("scalar")(self.h, what, _d(out)))
+        return out
+
+    def normSquared(self):
+        return float(self._scalar(0)[0])
+
+    def energy(self):
+        return float(self._scalar(1)[0])
+
+    def overlapWithInitial(self):
+        z = self._scalar(2)
+        return complex(z[0], z[1])
+
+    def _vector(self, what):
+        n = C.c_int64()
+        _chk(self._f("measure")(self.h, what, C.byref(n)))
+        out = np.zeros(n.value)
+        _chk(self._f("fetch")(self.h, _d(out)))
+        return out
+
+    def magnetisation(self):
+        return self._vector(0)
+
+    def correlationsZZ(self):
+        return self._vector(1).reshape(self._sites, self._sites)
+
+    def correlationsXY(self):
+        return self._vector(2).reshape(self._sites, self._sites)
+
+    def state(self):
+        return self._vector(3).view(np.complex128)
+
+    def log(self):
+        return [self._f("log_line")(self.h, i).decode() for i in range(int(self._status()[1][0]))]
 
     def close(self):
         if self.h:

@@ -302,6 +302,28 @@ int eigenex_spin_sector_csr(int n_sites, int n_up, int n_bonds, const int32_t* s
 int eigenex_spin_sector_upload(eigenex_context_t ctx, int n_sites, int n_up, int n_bonds, const int32_t* site_i,
                                const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null,
                                const double* hx_or_null, eigenex_csr_t* out);
+/* The same two matrix-free operators for COMPLEX states (real-time evolution exp(-iHt)|psi>): the same arguments, checks and
+ * error messages (under their own names), the same layout and tables, the same real Hamiltonian; only the scalar type of the
+ * handle is complex.  eigenex_basis_create on such a handle gives a complex state, eigenex_basis_create_ex(is_complex = 0) is
+ * refused by the scalar-type check; a handle of eigenex_spin_upload / eigenex_spin_sector_upload keeps refusing is_complex = 1.
+ * An application to x = a + ib (interleaved) is the real kernel's result on a and on b, the row walked once: each part has the
+ * real kernel's products, rounded and added in its order (with a shift only the sign of a zero may differ); a complex shift
+ * (eigenex_basis_configure_z) is a plain complex multiply added last.  The dot is conj(x) . y.  eigenex_spin_geometry,
+ * eigenex_csr_info, eigenex_csr_layout and eigenex_csr_encoding answer as for the real handles.  On a complex spin state:
+ *   eigenex_spin_measure                             the Hermitian sums, see below
+ *   eigenex_spin_rdm, eigenex_spin_site_apply        EIGENEX_ERR_STATE, "real states only", before anything is allocated
+ *   eigenex_basis_set_filter, eigenex_filter_apply,  supported: a complex state takes the streaming form of the Chebyshev step,
+ *   eigenex_kpm_moments, eigenex_kpm_trace_moments   whose real coefficients act on both parts alike and whose dots are the real
+ *                                                    parts of the Hermitian ones, which is all a Hermitian operator's moments
+ *                                                    need; the operator kernel supplies (H - center) t_k, u_out and the scale as
+ *                                                    every other complex operator kernel does.  Tested against the complex CSR
+ *                                                    upload of the same rows. */
+int eigenex_spin_upload_z(eigenex_context_t ctx, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                          const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null,
+                          eigenex_csr_t* out);
+int eigenex_spin_sector_upload_z(eigenex_context_t ctx, int n_sites, int n_up, int n_bonds, const int32_t* site_i,
+                                 const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null,
+                                 const double* hx_or_null, eigenex_csr_t* out);
 /* Spin correlations of a real vector x over the rows of a matrix-free spin operator, all terms in one sweep: x is read once
  * per 16 terms of each list and nothing is written but the sums.  A measurement is two lists of 32-bit site masks (bit i = site
  * i); with sigma_i(s) as above it yields the raw, unnormalised sums
@@ -325,13 +347,22 @@ int eigenex_spin_sector_upload(eigenex_context_t ctx, int n_sites, int n_up, int
  *   eigenex_spin_measure_host  the definition the kernel is held against, in host code: no context, no GPU.  n_up = -1: the
  *                              full space (n_sites 2..30, x has 2^n_sites entries); else the sector (n_sites 2..32, x has
  *                              C(n_sites, n_up) entries).  Rows ascending, one fma per term.
- *   eigenex_spin_geometry      n_sites and n_up (-1: the full space) of a matrix-free spin operator handle; EIGENEX_ERR_STATE
+ *   complex states             on a state of eigenex_spin_upload_z / eigenex_spin_sector_upload_z, eigenex_spin_measure computes the
+ *                              Hermitian sums norm2 = sum_s |x_s|^2, diag_out[t] = sum_s sign |x_s|^2 and flip_out[t] = sum_s
+ *                              [predicate] Re(conj(x_s) x_{s ^ mask}), so the normalisations above stay valid; same chunks, same
+ *                              fixed-order reduction without atomics.  eigenex_spin_measure_host_z is its host definition: x
+ *                              interleaved (re, im), rows ascending, per term the fma of the real parts and then the fma of the
+ *                              imaginary parts; with all imaginary parts +0 it returns eigenex_spin_measure_host's bytes.
+ *   eigenex_spin_geometry     n_sites and n_up (-1: the full space) of a matrix-free spin operator handle; EIGENEX_ERR_STATE
  *                              for any other handle.  Either output may be NULL. */
 int eigenex_spin_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint32_t* diag_masks, int n_flip,
                          const uint32_t* flip_masks, double* diag_out, double* flip_out, double* norm2);
 int eigenex_spin_measure_host(int n_sites, int n_up /* -1: full space */, const double* x, int n_diag,
                               const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks, double* diag_out,
                               double* flip_out, double* norm2);
+int eigenex_spin_measure_host_z(int n_sites, int n_up /* -1: full space */, const double* x_interleaved, int n_diag,
+                                const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks, double* diag_out,
+                                double* flip_out, double* norm2);
 int eigenex_spin_geometry(eigenex_csr_t csr, int* n_sites, int* n_up);
 /* A sum of single-site spin operators applied to a real vector, y = O x: the start vector of a dynamical correlation function
  * (Lanczos continued fraction) formed on the device, also where O changes the magnetisation.  NOT part of the reference.  O is a
@@ -603,6 +634,13 @@ int eigenex_ritz_vectors_complex(eigenex_basis_t b, int nvec, int nev, const dou
  * complex coefficients C_re + i C_im and X holds interleaved (re, im) pairs. */
 int eigenex_krylov_combine(eigenex_basis_t b, int nvec, int ncols, const double* C_re, const double* C_im, int ldc,
                            double* X, int64_t ldx);
+/* dst = sum_m C[m] * col(m), m < nvec, left on the device in a vector of the same state: the one-column case of
+ * eigenex_krylov_combine (the same kernels, the same arithmetic, the same bytes) without the transfer to the host, e.g. a time
+ * step psi <- V c.  dst_ref is EIGENEX_VEC_W, EIGENEX_VEC_V or a basis column at or above nvec; a column below nvec (it is
+ * read), any other reference, nvec outside 1..capacity or complex coefficients on a real state: EIGENEX_ERR_ARG.  C_im == NULL:
+ * real coefficients.  Any operator, real or complex state, one shard (more: EIGENEX_ERR_STATE).  A pending close of a one-sweep
+ * batch is carried out first; synchronises once. */
+int eigenex_krylov_combine_to(eigenex_basis_t b, int nvec, const double* C_re, const double* C_im_or_null, int dst_ref);
 
 #ifdef __cplusplus
 }
