@@ -118,6 +118,8 @@ SIGNATURES = {
     "eigenex_spin_rdm_layout": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int), _lp, _lp]),
     "eigenex_spin_rdm": (C.c_int, [_vp, C.c_int, C.c_uint32, _dp, C.c_int64]),
     "eigenex_spin_rdm_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_uint32, _dp, C.c_int64]),
+    "eigenex_spin_rdm_z": (C.c_int, [_vp, C.c_int, C.c_uint32, _dp, C.c_int64]),
+    "eigenex_spin_rdm_host_z": (C.c_int, [C.c_int, C.c_int, _dp, C.c_uint32, _dp, C.c_int64]),
     "eigenex_basis_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_create_ex": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "eigenex_basis_is_complex": (C.c_int, [_vp, C.POINTER(C.c_int)]),
@@ -403,6 +405,24 @@ def spin_rdm_host(n_sites: int, n_up, x, mask_a: int):
     out = np.zeros(offs[-1])
     _chk(lib().eigenex_spin_rdm_host(int(n_sites), -1 if n_up is None else int(n_up), _d(x), int(mask_a), _d(out), out.size))
     return _rdm_blocks(kf, dims, offs, out)
+
+
+def _rdm_blocks_z(k_first, dims, offsets, out):
+    """the packed column-major blocks of interleaved pairs as [(k, ndarray(d, d), complex128), ...] (copies)"""
+    z = out.view(np.complex128)
+    return [(k_first + n, z[offsets[n] : offsets[n + 1]].reshape(d, d).T.copy()) for n, d in enumerate(dims)]
+
+
+def spin_rdm_host_z(n_sites: int, n_up, x, mask_a: int):
+    """eigenex_spin_rdm_host_z: the raw, unnormalised reduced density matrix M M^H of the subsystem mask_a of the complex vector
+    x as a list of (k, ndarray(d_k, d_k), complex128), in host code (no GPU).  n_up = None: the full space (one block, k = 0)."""
+    x = np.ascontiguousarray(x, np.complex128)
+    kf, dims, offs = spin_rdm_layout(n_sites, n_up, mask_a)
+    if x.size != (1 << int(n_sites) if n_up is None else spin_sector_dim(n_sites, n_up)):  # the library cannot see the length
+        raise EigenexError("spin_rdm_host_z: x must have one entry per row of the geometry")
+    out = np.zeros(2 * offs[-1])
+    _chk(lib().eigenex_spin_rdm_host_z(int(n_sites), -1 if n_up is None else int(n_up), _d(x.view(np.float64)), int(mask_a), _d(out), out.size))
+    return _rdm_blocks_z(kf, dims, offs, out)
 
 
 def spin_site_apply_host(n_sites: int, n_up, kind: int, coef, x):
@@ -852,6 +872,22 @@ class Basis:
         out = np.zeros(offs[-1])
         _chk(lib().eigenex_spin_rdm(self.h, x_ref, int(mask_a), _d(out), out.size))
         return _rdm_blocks(kf, dims, offs, out)
+
+    def spin_rdm_z(self, x_ref, mask_a):
+        """eigenex_spin_rdm_z: the raw, unnormalised reduced density matrix M M^H of the subsystem mask_a of the complex vector
+        x_ref, formed on the device, as a list of (k, ndarray(d_k, d_k), complex128); the state must be a complex one on a
+        matrix-free spin operator for complex states.  No vector and no coefficient changes."""
+        ns, nu = C.c_int(), C.c_int()
+        if self.csr is None or lib().eigenex_spin_geometry(self.csr.h, C.byref(ns), C.byref(nu)) != 0:
+            _chk(lib().eigenex_spin_rdm_z(self.h, x_ref, int(mask_a), None, 0))  # the library says what is wrong with the state
+        try:
+            kf, dims, offs = spin_rdm_layout(ns.value, None if nu.value < 0 else nu.value, mask_a)
+        except EigenexError:
+            _chk(lib().eigenex_spin_rdm_z(self.h, x_ref, int(mask_a), None, 0))  # the same refusal under the entry point's own name
+            raise
+        out = np.zeros(2 * offs[-1])
+        _chk(lib().eigenex_spin_rdm_z(self.h, x_ref, int(mask_a), _d(out), out.size))
+        return _rdm_blocks_z(kf, dims, offs, out)
 
     def spin_site_apply(self, x_ref, dst, y_ref, kind, coef):
         """eigenex_spin_site_apply: vector y_ref of the state dst = (sum of site operators kind, coef) applied to vector x_ref of

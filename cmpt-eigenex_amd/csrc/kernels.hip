@@ -2110,6 +2110,148 @@ __global__ __launch_bounds__(kBlock) void k_spin_rdm_reduce(const SpinRdmTable* 
   out[bk->out_offset + j + i * d] = sum;
 }
 
+// The same for an interleaved complex vector (eigenex_spin_rdm_z; spin_rdm.hpp: spin_rdm_host_z is the definition):
+// rho_A = M M^H.  The plan, the items, the slices, the party states, the padding rule and the order of the sums are
+// k_spin_rdm's; what differs is the arithmetic and the shape of the panels.  A panel element is one 16-byte load of x behind one
+// walk of the rank tables (spin_rdm_element_z) and one 16-byte LDS store; the chunk is kSpinRdmBigChunkZ / kSpinRdmSmallChunkZ
+// b's (four gathers per lane and panel), the pitch TILE + 1 pairs, and a lane's four rows are t, t + SIDE, t + 2 SIDE, t + 3 SIDE
+// (spin_rdm_lane_row_z), each one 16-byte LDS read.  Per pair of rows and per b four fmas in the definition's order into a 4 x 4
+// register tile of (re, im): 32 fp64 accumulators.  The imaginary part of a diagonal entry is not stored: +0.0 is.
+template <bool SECTOR, int TILE>
+__global__ __launch_bounds__(kBlock) void k_spin_rdm_z(const SpinRdmTable* __restrict__ tb, const SpinRdmItem* __restrict__ items,
+                                                       const SpinSectorView* __restrict__ op, const uint32_t* __restrict__ lo_rank,
+                                                       const uint32_t* __restrict__ hi_base, const double2* __restrict__ x,
+                                                       double2* __restrict__ partials) {
+  constexpr int CHUNK = TILE == kSpinRdmBigTile ? kSpinRdmBigChunkZ : kSpinRdmSmallChunkZ;
+  constexpr int GROUPS = TILE == kSpinRdmBigTile ? 1 : kSpinRdmSmallGroups;
+  constexpr int SIDE = TILE / 4, LOADS = TILE * CHUNK / kBlock;
+  static_assert(SIDE * SIDE * GROUPS == kBlock && TILE * CHUNK % kBlock == 0 && CHUNK <= kBlock && CHUNK % GROUPS == 0, "tile shape");
+  static_assert(GROUPS == 1 || TILE * TILE == kBlock, "the group sums are added by one lane per entry");
+  constexpr int PANEL = CHUNK * (TILE + 1);  // spin_rdm_panel_index_z
+  __shared__ double2 panel[(GROUPS == 1 ? 2 : 1) * PANEL];
+  __shared__ double red[GROUPS > 1 ? GROUPS * TILE * TILE : 1];
+  __shared__ uint32_t sa_i[TILE], sa_j[TILE], sb[CHUNK];
+  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
+  int h = 0;
+  uint32_t lo_mask = 0;
+  if constexpr (SECTOR) {
+    spin_stage_binomials(op, binom);
+    __syncthreads();
+    h = op->h, lo_mask = op->lo_mask;
+  }
+  const SpinRdmItem it = items[blockIdx.x];
+  const SpinRdmBlock* bk = tb->block + it.block;
+  const int d = bk->d, k = bk->k, nA = tb->nA, nB = tb->nB, kb = tb->n_up - k;
+  const uint32_t mask_a = tb->mask_a, mask_b = tb->mask_b, fallback = tb->fallback;
+  const bool along_a = TILE == kSpinRdmBigTile && tb->along_a != 0, diagonal = it.ti == it.tj;
+  const int i0 = it.ti * TILE, j0 = it.tj * TILE;
+  const int tid = threadIdx.x;
+  const SpinBinomials32 bin{binom};
+  const SpinRankTables tab{lo_rank, hi_base};
+  const SpinVectorZ xv{x};
+  if (tid < TILE) {
+    sa_i[tid] = spin_rdm_party_state<SECTOR>(bin, nA, k, mask_a, (uint32_t)(i0 + tid), i0 + tid < d);
+    sa_j[tid] = spin_rdm_party_state<SECTOR>(bin, nA, k, mask_a, (uint32_t)(j0 + tid), j0 + tid < d);
+  }
+  const int group = tid / (SIDE * SIDE), tx = tid % SIDE, ty = tid % (SIDE * SIDE) / SIDE;
+  const int other = diagonal || GROUPS > 1 ? 0 : PANEL;  // where the rows a_j of the pair lie: a diagonal pair has one panel
+  double re[4][4], im[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) re[r][c] = 0.0, im[r][c] = 0.0;
+  for (uint32_t b0 = it.b_begin; b0 < it.b_end; b0 += CHUNK) {
+    __syncthreads();  // sa_i and sa_j are written; the last chunk's panels are read
+    if (tid < CHUNK) sb[tid] = spin_rdm_party_state<SECTOR>(bin, nB, kb, mask_b, b0 + tid, tid < it.b_end - b0);
+    __syncthreads();
+    SpinZ va[LOADS], vb[LOADS];
+#pragma unroll
+    for (int q = 0; q < LOADS; ++q) {
+      int row, bj;
+      spin_rdm_panel_slot(along_a, TILE, CHUNK, q * kBlock + tid, &row, &bj);
+      const bool live_b = (uint32_t)bj < it.b_end - b0;
+      va[q] = spin_rdm_element_z<SECTOR>(tab, xv, h, lo_mask, sa_i[row], sb[bj], live_b && i0 + row < d, fallback);
+      if (other != 0) vb[q] = spin_rdm_element_z<SECTOR>(tab, xv, h, lo_mask, sa_j[row], sb[bj], live_b && j0 + row < d, fallback);
+    }
+#pragma unroll
+    for (int q = 0; q < LOADS; ++q) {
+      int row, bj;
+      spin_rdm_panel_slot(along_a, TILE, CHUNK, q * kBlock + tid, &row, &bj);
+      panel[spin_rdm_panel_index_z(TILE, bj, row)] = make_double2(va[q].re, va[q].im);
+      if (other != 0) panel[other + spin_rdm_panel_index_z(TILE, bj, row)] = make_double2(vb[q].re, vb[q].im);
+    }
+    __syncthreads();
+    for (int bj = group; bj < CHUNK; bj += GROUPS) {
+      double2 a[4], b[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        a[r] = panel[spin_rdm_panel_index_z(TILE, bj, spin_rdm_lane_row_z(SIDE, tx, r))];
+        b[r] = panel[other + spin_rdm_panel_index_z(TILE, bj, spin_rdm_lane_row_z(SIDE, ty, r))];
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          re[r][c] = fma(a[r].x, b[c].x, re[r][c]);
+          re[r][c] = fma(a[r].y, b[c].y, re[r][c]);
+          im[r][c] = fma(a[r].y, b[c].x, im[r][c]);
+          im[r][c] = fma(-a[r].x, b[c].y, im[r][c]);
+        }
+    }
+  }
+  double2* out = partials + bk->part_offset + (int64_t)it.slice * d * d;
+  if constexpr (GROUPS == 1) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int i = i0 + spin_rdm_lane_row_z(SIDE, tx, r), j = j0 + spin_rdm_lane_row_z(SIDE, ty, c);
+        if (i < d && j < d && i >= j) out[i + (int64_t)j * d] = make_double2(re[r][c], i == j ? 0.0 : im[r][c]);
+      }
+  } else {
+    // the groups' tiles are added part by part through the real kernel's red[]: the real parts, then the imaginary ones
+    const auto group_sum = [&](const double(&part)[4][4]) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) red[group * TILE * TILE + spin_rdm_lane_row_z(SIDE, ty, c) * TILE + spin_rdm_lane_row_z(SIDE, tx, r)] = part[r][c];
+      __syncthreads();
+      double sum = 0.0;
+      for (int g = 0; g < GROUPS; ++g) sum += red[g * TILE * TILE + tid];
+      return sum;
+    };
+    const double sr = group_sum(re);
+    __syncthreads();  // the real parts are read
+    const double si = group_sum(im);
+    const int i = i0 + tid % TILE, j = j0 + tid / TILE;
+    if (i < d && j < d && i >= j) out[i + (int64_t)j * d] = make_double2(sr, i == j ? 0.0 : si);
+  }
+}
+
+// Second stage of k_spin_rdm_z, one lane per entry of the packed output: the lane of an entry i >= j adds the block's slices
+// in ascending order, both parts with plain adds, and writes (i, j) and, with the imaginary part negated, (j, i) from the same two
+// values; a diagonal entry is written once with the imaginary part +0.0.  The lane of an entry i < j writes nothing.
+__global__ __launch_bounds__(kBlock) void k_spin_rdm_reduce_z(const SpinRdmTable* __restrict__ tb, const double2* __restrict__ partials,
+                                                              double2* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= tb->total) return;
+  int n = 0;
+  while (n + 1 < tb->n_blocks && e >= tb->block[n + 1].out_offset) ++n;
+  const SpinRdmBlock* bk = tb->block + n;
+  const int64_t d = bk->d, local = e - bk->out_offset;
+  const int64_t i = local % d, j = local / d;
+  if (i < j) return;
+  const double2* p = partials + bk->part_offset + i + j * d;
+  double sr = 0.0, si = 0.0;
+  for (int s = 0; s < bk->nslices; ++s) sr += p[(int64_t)s * d * d].x, si += p[(int64_t)s * d * d].y;
+  if (i == j) {
+    out[bk->out_offset + i + j * d] = make_double2(sr, 0.0);
+  } else {
+    out[bk->out_offset + i + j * d] = make_double2(sr, si);
+    out[bk->out_offset + j + i * d] = make_double2(sr, -si);
+  }
+}
+
 // complex blocks: entries, input and sums are (re, im) pairs; products without contraction and added part by
 // part, exactly like k_spmv_z
 template <int NB, bool STAGED>
@@ -3091,6 +3233,20 @@ void launch_spin_rdm(hipStream_t s, bool big, const SpinRdmTable* table, const S
 
 void launch_spin_rdm_reduce(hipStream_t s, const SpinRdmTable* table, int64_t total, const double* partials, double* out) {
   hipLaunchKernelGGL(k_spin_rdm_reduce, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, table, partials, out);
+}
+
+void launch_spin_rdm_z(hipStream_t s, bool big, const SpinRdmTable* table, const SpinRdmItem* items, int n_items, const SpinSectorView* op,
+                       const uint32_t* lo_rank, const uint32_t* hi_base, const double* x, double* partials) {
+  if (n_items <= 0) return;
+  const auto kernel = big ? (lo_rank ? k_spin_rdm_z<true, kSpinRdmBigTile> : k_spin_rdm_z<false, kSpinRdmBigTile>)
+                          : (lo_rank ? k_spin_rdm_z<true, kSpinRdmSmallTile> : k_spin_rdm_z<false, kSpinRdmSmallTile>);
+  hipLaunchKernelGGL(kernel, dim3(n_items), dim3(kBlock), 0, s, table, items, op, lo_rank, hi_base, reinterpret_cast<const double2*>(x),
+                     reinterpret_cast<double2*>(partials));
+}
+
+void launch_spin_rdm_reduce_z(hipStream_t s, const SpinRdmTable* table, int64_t total, const double* partials, double* out) {
+  hipLaunchKernelGGL(k_spin_rdm_reduce_z, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, table,
+                     reinterpret_cast<const double2*>(partials), reinterpret_cast<double2*>(out));
 }
 
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,

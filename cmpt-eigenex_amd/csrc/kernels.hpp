@@ -385,6 +385,11 @@ void launch_spin_rdm(hipStream_t s, bool big, const SpinRdmTable* table, const S
 // its second stage: every entry i >= j of every block is the sum of its slices in ascending order, written to (i, j) and (j, i)
 // of out (table->total doubles, `total` on the host)
 void launch_spin_rdm_reduce(hipStream_t s, const SpinRdmTable* table, int64_t total, const double* partials, double* out);
+// The same two stages for an interleaved complex x (eigenex_spin_rdm_z): the same table and items; partials and out hold (re, im)
+// pairs at the same indices, so 2 * part_total and 2 * total doubles, 16-byte aligned like x.
+void launch_spin_rdm_z(hipStream_t s, bool big, const SpinRdmTable* table, const SpinRdmItem* items, int n_items, const SpinSectorView* op,
+                       const uint32_t* lo_rank, const uint32_t* hi_base, const double* x, double* partials);
+void launch_spin_rdm_reduce_z(hipStream_t s, const SpinRdmTable* table, int64_t total, const double* partials, double* out);
 // host-operator path: u_out = x*scale
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,
                   const Ctrl* ctrl);

@@ -3299,7 +3299,7 @@ int eigenex_spin_rdm(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out,
     return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_rdm: the operator of this state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
                                           : "eigenex_spin_rdm: the state has no device operator (a host callback knows no sites)");
   if (b->es != 1)
-    return fail(EIGENEX_ERR_STATE, "eigenex_spin_rdm: real states only (a complex spin state, eigenex_spin_upload_z, has no density-matrix kernel)");
+    return fail(EIGENEX_ERR_STATE, "eigenex_spin_rdm: real states only (a complex spin state, eigenex_spin_upload_z, has no density-matrix kernel here: eigenex_spin_rdm_z)");
   BasisShard& s = *spin_state_shard(b);
   const SpinShard& m = s.csr->spin;
   const SpinRdmArgs a{m.n_sites, m.n_up, mask_a};
@@ -3331,6 +3331,59 @@ int eigenex_spin_rdm(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out,
   launch_spin_rdm(c->stream, false, d_table, d_items + nbig, (int)nsmall, m.view, m.lo, m.hi, x, d_part);
   launch_spin_rdm_reduce(c->stream, d_table, t.total, d_part, d_out);
   HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)t.total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the table and the scratch live until here
+  return 0;
+}
+
+int eigenex_spin_rdm_host_z(int n_sites, int n_up, const double* x, uint32_t mask_a, double* out, int64_t out_len) {
+  const SpinRdmArgs a{n_sites, n_up, mask_a};
+  if (const char* why = spin_rdm_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_rdm_host_z: ") + why);
+  if (!x || !out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_host_z: x or out is NULL");
+  SpinRdmLayout l;
+  spin_rdm_layout(a, l);
+  if (out_len != 2 * l.offsets[l.n_blocks]) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_host_z: out_len is not twice the length eigenex_spin_rdm_layout gives");
+  spin_rdm_host_z(a, x, out);
+  return 0;
+}
+
+int eigenex_spin_rdm_z(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out, int64_t out_len) {
+  if (!b) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_z: basis is NULL");
+  CHK(enter_settled(b));
+  if (!spin_state_shard(b))
+    return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_rdm_z: the operator of this state is not a matrix-free spin operator for complex states (eigenex_spin_upload_z, eigenex_spin_sector_upload_z)"
+                                          : "eigenex_spin_rdm_z: the state has no device operator (a host callback knows no sites)");
+  if (b->es != 2)
+    return fail(EIGENEX_ERR_STATE, "eigenex_spin_rdm_z: complex states only (a real spin state, eigenex_spin_upload, goes through eigenex_spin_rdm)");
+  BasisShard& s = *spin_state_shard(b);
+  const SpinShard& m = s.csr->spin;
+  const SpinRdmArgs a{m.n_sites, m.n_up, mask_a};
+  if (const char* why = spin_rdm_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_rdm_z: ") + why);
+  if (!out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_z: out is NULL");
+  SpinRdmPlan plan;
+  spin_rdm_build_plan(a, s.g_spmv, plan);  // the real call's plan: the same items and slices
+  const SpinRdmTable& t = plan.table;
+  if (out_len != 2 * t.total) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_z: out_len is not twice the length eigenex_spin_rdm_layout gives");
+  const double* x = vec_ptr(s, b->cap, b->nq, x_ref);
+  if (!x) return fail(EIGENEX_ERR_ARG, "bad vector reference");
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  // scratch of this call alone, as in eigenex_spin_rdm; the partial sums and the packed result are (re, im) pairs
+  const size_t nbig = plan.big.size(), nsmall = plan.small.size();
+  std::vector<SpinRdmItem> items(plan.big);
+  items.insert(items.end(), plan.small.begin(), plan.small.end());
+  DeviceBuffer<SpinRdmTable> d_table;
+  DeviceBuffer<SpinRdmItem> d_items;
+  DeviceBuffer<double> d_part, d_out;
+  HIPCHK(d_table.alloc(1));
+  HIPCHK(d_items.alloc(items.size()));
+  HIPCHK(d_part.alloc(2 * (size_t)t.part_total));
+  HIPCHK(d_out.alloc(2 * (size_t)t.total));
+  HIPCHK(hipMemcpyAsync(d_table, &t, sizeof(SpinRdmTable), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_items, items.data(), sizeof(SpinRdmItem) * items.size(), hipMemcpyHostToDevice, c->stream));
+  launch_spin_rdm_z(c->stream, true, d_table, d_items, (int)nbig, m.view, m.lo, m.hi, x, d_part);
+  launch_spin_rdm_z(c->stream, false, d_table, d_items + nbig, (int)nsmall, m.view, m.lo, m.hi, x, d_part);
+  launch_spin_rdm_reduce_z(c->stream, d_table, t.total, d_part, d_out);
+  HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * 2 * (size_t)t.total, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the table and the scratch live until here
   return 0;
 }

@@ -1038,6 +1038,21 @@ int eigenex_spin_evolution_solver_measure(void* p, int what, int64_t* len) {
     if (len) *len = (int64_t)b->out.size();
   });
 }
+// The entanglement of a subsystem of the state (SpinTimeEvolutionSolver::entanglementEntropy, entanglementRenyi2,
+// entanglementSpectrum), given as a mask (sites = NULL) or as n_sites_listed sites.  what: 0 entropy, 1 renyi2 (one double each), 2 the
+// spectrum.  Forms the result and returns its length; eigenex_spin_evolution_solver_fetch copies it out.
+int eigenex_spin_evolution_solver_entanglement(void* p, uint32_t mask, const int32_t* sites, int n_sites_listed, int what, int64_t* len) {
+  return guard([&] {
+    auto* b = static_cast<SpinEvolutionBox*>(p);
+    auto& es = b->es;
+    const std::vector<int> list(sites, sites + (sites && n_sites_listed > 0 ? n_sites_listed : 0));
+    if (what == 0) b->out.assign(1, sites ? es.entanglementEntropy(list) : es.entanglementEntropy(mask));
+    else if (what == 1) b->out.assign(1, sites ? es.entanglementRenyi2(list) : es.entanglementRenyi2(mask));
+    else if (what == 2) b->out = sites ? es.entanglementSpectrum(list) : es.entanglementSpectrum(mask);
+    else throw LanczosException("eigenex_spin_evolution_solver_entanglement: what must be 0..2");
+    if (len) *len = (int64_t)b->out.size();
+  });
+}
 int eigenex_spin_evolution_solver_fetch(void* p, double* out) {
   return guard([&] {
     auto* b = static_cast<SpinEvolutionBox*>(p);
@@ -1055,6 +1070,7 @@ struct SpinEntanglementBox {
   std::shared_ptr<device::Context> ctx;
   std::shared_ptr<device::CsrOperator> op;
   DenseVector<double> state;
+  DenseVector<std::complex<double>> stateZ;
   SpinEntanglementSolver es;
 };
 void* eigenex_spin_entanglement_solver_create(void) {
@@ -1081,6 +1097,14 @@ int eigenex_spin_entanglement_solver_set_state(void* p, const double* v, int64_t
     b->es.setState(b->state);
   });
 }
+// a complex state: n interleaved (re, im) pairs
+int eigenex_spin_entanglement_solver_set_state_z(void* p, const double* v, int64_t n) {
+  return guard([&] {
+    auto* b = static_cast<SpinEntanglementBox*>(p);
+    b->stateZ = make_vector<std::complex<double>>(v, n);
+    b->es.setState(b->stateZ);
+  });
+}
 int eigenex_spin_entanglement_solver_set_subsystem(void* p, const int32_t* sites, int n) {
   return guard([&] { static_cast<SpinEntanglementBox*>(p)->es.setSubsystem(std::vector<int>(sites, sites + (n > 0 ? n : 0))); });
 }
@@ -1102,6 +1126,18 @@ int eigenex_spin_entanglement_solver_block(void* p, int64_t n, int* sites_up, in
     if (sites_up) *sites_up = es.blockSitesUp((Index)n);
     if (dim) *dim = (int64_t)es.blockDimension((Index)n);
     if (rho) std::copy(es.reducedDensityMatrix((Index)n).begin(), es.reducedDensityMatrix((Index)n).end(), rho);
+  });
+}
+// the same of a complex state: rho takes 2 * dimension^2 doubles, interleaved (re, im); *is_complex (may be NULL) says which of
+// the two calls has the entries (the other one throws)
+int eigenex_spin_entanglement_solver_block_z(void* p, int64_t n, int* is_complex, double* rho) {
+  return guard([&] {
+    auto& es = static_cast<SpinEntanglementBox*>(p)->es;
+    if (is_complex) *is_complex = es.stateIsComplex() ? 1 : 0;
+    if (rho) {
+      const auto& z = es.reducedDensityMatrixComplex((Index)n);
+      std::copy(reinterpret_cast<const double*>(z.data()), reinterpret_cast<const double*>(z.data()) + 2 * z.size(), rho);
+    }
   });
 }
 // any pointer may be NULL; scalars[3] = (normSquared, entropy, renyi2), the last two only after a successful compute()

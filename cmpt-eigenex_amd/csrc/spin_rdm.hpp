@@ -16,6 +16,13 @@
 // Output: the blocks packed in ascending k, each a full d_k x d_k column-major matrix, both triangles stored, out[i,j] and
 // out[j,i] the same bits.  The sums are raw and unnormalised, like spin_measure: the trace is sum x^2.  The host definition
 // adds the b terms in ascending order, one fma per term.
+//
+// A complex vector (interleaved (re, im) pairs; eigenex_spin_rdm_z, eigenex_spin_rdm_host_z; kernels.hip: k_spin_rdm_z,
+// k_spin_rdm_reduce_z): rho_k = M_k M_k^H, rho[i, j] = sum_b M[i, b] conj(M[j, b]), over the same blocks, layout, limit and
+// argument check.  Output: the blocks packed in ascending k, each a full column-major d_k x d_k matrix of interleaved (re, im)
+// pairs, 2 * offsets[n_blocks] doubles; raw sums, the trace is sum |x|^2.  Two properties are part of the definition and every
+// evaluation keeps them bit for bit: Im rho[i, i] is stored as +0.0 (not the computed chain: with fma the two products of a
+// diagonal term do not cancel exactly), and (j, i) is written from the two values of (i, j) with the imaginary part negated.
 #pragma once
 #include <stdint.h>
 
@@ -31,8 +38,23 @@ constexpr int kSpinRdmMaxBlocks = kSectorMaxSites + 1;   // k = 0 .. 32
 constexpr int kSpinRdmBigTile = 64, kSpinRdmSmallTile = 16;     // blocks above 16 rows, blocks of at most 16 rows
 constexpr int kSpinRdmBigChunk = 32, kSpinRdmSmallChunk = 128;  // b's staged in LDS at a time, per tile size
 constexpr int kSpinRdmSmallGroups = 16;                  // a 16-tile workgroup splits a chunk's b's over 16 groups of 16 threads
+// The complex kernel (k_spin_rdm_z) stages half as many b's, so that its panels of 16-byte elements take the real kernel's LDS:
+//   64-row tile: CHUNK = 16, two panels of 16 x (64 + 1) pairs = 33 280 B; with the staged states and (in a sector) the
+//     binomials 38 080 B per workgroup (real kernel: 38 656 B); four 16-byte gathers per lane and panel
+//   16-row tile: CHUNK = 64, one panel of 64 x (16 + 1) pairs = 17 408 B; the 16 groups' tiles go through red[] of the real
+//     kernel's size, 32 768 B, twice (the real parts, then the imaginary ones), not through one of twice the size, which would
+//     leave one workgroup per CU: 54 720 B per workgroup in a sector (real kernel: 56 000 B); four gathers per lane
+// (the byte counts are the compiler's, profiles/spin_entanglement_z.md).  The panels are b-major with a pitch of TILE + 1
+// pairs (16-byte units, so every element is 16-byte aligned), and a lane's four rows are t, t + TILE/4, t + 2 TILE/4,
+// t + 3 TILE/4 (spin_rdm_rows.hpp: spin_rdm_lane_row_z), not four consecutive ones: each is one 16-byte LDS read, and the 16
+// lanes of a read group then take 16 consecutive pairs, 256 bytes = one row of the 64 banks: no conflict, where the real
+// kernel's four consecutive doubles per lane are a 2-way one.  A gather whose b's run along the lanes stores with a stride of
+// TILE + 1 pairs, 16 bytes past a multiple of the 128 bytes a store covers per cycle: eight consecutive lanes fill the 32 store
+// banks once, the rate of a contiguous 16-byte store (the real kernel's TILE + 2 doubles do the same for 8-byte stores).
+constexpr int kSpinRdmBigChunkZ = 16, kSpinRdmSmallChunkZ = 64;
 // partial sums of one block beyond its first slice: at most 2^21 doubles (16 MiB), so that the partials of a call never exceed
-// the packed output's length plus kSpinRdmMaxBlocks * 16 MiB
+// the packed output's length plus kSpinRdmMaxBlocks * 16 MiB.  The complex call (eigenex_spin_rdm_z) takes the same plan, the
+// same slices, and its partials are (re, im) pairs: twice these bytes.
 constexpr int64_t kSpinRdmSliceBudget = int64_t(1) << 21;
 
 struct SpinRdmArgs {
@@ -112,6 +134,45 @@ inline void spin_rdm_host(const SpinRdmArgs& a, const double* x, double* out) {
         double acc = 0.0;
         for (size_t b = 0; b < nb; ++b) acc = std::fma(M[i * nb + b], M[j * nb + b], acc);
         o[i + j * d] = acc, o[j + i * d] = acc;
+      }
+  }
+}
+
+// The definition for a complex vector (x: interleaved pairs, out: 2 * the layout's length): for every i >= j one chain over
+// ascending b with four fmas per term, in this order; the diagonal's imaginary part is +0.0 and (j, i) the conjugate of (i, j).
+inline void spin_rdm_host_z(const SpinRdmArgs& a, const double* x, double* out) {
+  const bool sector = a.n_up != -1;
+  SpinRdmLayout l;
+  spin_rdm_layout(a, l);
+  SpinSectorTables t;
+  if (sector) spin_sector_build_tables(a.n_sites, a.n_up, t);
+  for (int n = 0; n < l.n_blocks; ++n) {
+    const int k = l.k_first + n;
+    const size_t d = (size_t)l.dims[n], nb = (size_t)l.nb[n];
+    std::vector<uint32_t> sb(nb);
+    for (size_t j = 0; j < nb; ++j) sb[j] = spin_rdm_deposit(sector ? spin_sector_unrank(l.nB, a.n_up - k, (int64_t)j) : (uint32_t)j, l.mask_b);
+    std::vector<double> Mr(d * nb), Mi(d * nb);
+    for (size_t i = 0; i < d; ++i) {
+      const uint32_t sa = spin_rdm_deposit(sector ? spin_sector_unrank(l.nA, k, (int64_t)i) : (uint32_t)i, a.mask_a);
+      for (size_t j = 0; j < nb; ++j) {
+        const size_t r = sector ? (size_t)spin_sector_rank(t, sa | sb[j]) : (size_t)(sa | sb[j]);
+        Mr[i * nb + j] = x[2 * r], Mi[i * nb + j] = x[2 * r + 1];
+      }
+    }
+    double* o = out + 2 * l.offsets[n];
+    for (size_t i = 0; i < d; ++i)
+      for (size_t j = 0; j <= i; ++j) {
+        double re = 0.0, im = 0.0;
+        for (size_t b = 0; b < nb; ++b) {
+          const double ar_i = Mr[i * nb + b], ai_i = Mi[i * nb + b], ar_j = Mr[j * nb + b], ai_j = Mi[j * nb + b];
+          re = std::fma(ar_i, ar_j, re);
+          re = std::fma(ai_i, ai_j, re);
+          im = std::fma(ai_i, ar_j, im);
+          im = std::fma(-ar_i, ai_j, im);
+        }
+        if (i == j) im = 0.0;
+        o[2 * (i + j * d)] = re, o[2 * (i + j * d) + 1] = im;
+        o[2 * (j + i * d)] = re, o[2 * (j + i * d) + 1] = i == j ? 0.0 : -im;
       }
   }
 }

@@ -51,4 +51,21 @@ EIGENEX_HD double spin_rdm_element(const Tables& tab, const Vector& x, int h, ui
   return live ? v : 0.0;
 }
 
+// The same element of an interleaved complex vector (k_spin_rdm_z): one walk of the rank tables and one load serve both parts
+// (x(i) is the pair at row i, a 16-byte load on the device; SpinZ is spin_rows.hpp's pair).
+template <bool SECTOR, class Tables, class Vector>
+EIGENEX_HD SpinZ spin_rdm_element_z(const Tables& tab, const Vector& x, int h, uint32_t lo_mask, uint32_t sa, uint32_t sb, bool live, uint32_t fallback) {
+  const uint32_t s = live ? (sa | sb) : fallback;
+  const uint32_t base = SECTOR ? tab.hi(s >> h) : s;
+  const uint32_t low = SECTOR ? tab.lo(s & lo_mask) : 0u;
+  const SpinZ v = x(base + low);
+  return live ? v : SpinZ{0.0, 0.0};
+}
+
+// k_spin_rdm_z: the r-th of the four tile rows (columns) of the lane at position t of `side` = TILE / 4 positions, and where
+// row `row` of b `bj` lies in a b-major panel of CHUNK * (TILE + 1) pairs (spin_rdm.hpp says why these and not the real
+// kernel's 4 t + r and TILE + 2)
+EIGENEX_HD int spin_rdm_lane_row_z(int side, int t, int r) { return t + side * r; }
+EIGENEX_HD int spin_rdm_panel_index_z(int tile, int bj, int row) { return bj * (tile + 1) + row; }
+
 }  // namespace eigenex

@@ -27,11 +27,15 @@
 //
 // Measurements read W where it is: normSquared(), magnetisation(), correlationsZZ() and correlationsXY() through
 // eigenex_spin_measure (Hermitian sums of a complex vector), energy() = Re <psi|H|psi> / <psi|psi> through one operator application
-// and its dot, overlapWithInitial() = <psi_0|psi(t)> through eigenex_dots with the kept column.  state() downloads.
+// and its dot, overlapWithInitial() = <psi_0|psi(t)> through eigenex_dots with the kept column.  entanglementEntropy(A),
+// entanglementSpectrum(A) and entanglementRenyi2(A) of a subsystem A (a site mask or a site list; at most 12 sites in the full
+// space, 14 in a sector) form rho_A = M M^H of W through eigenex_spin_rdm_z and take the spectrum on the host with the code of
+// SpinEntanglementSolver (spin_entanglement.hpp: detail::EntanglementBlocks); they change no vector, time, bound or counter.
+// state() downloads.
 //
 // Out of scope: complex couplings (Sy, Dzyaloshinskii-Moriya terms); momentum sectors; S(q, w) with complex coefficients in one
-// run; time-dependent Hamiltonians; Chebyshev propagators; reduced density matrices and site operators of complex states; more
-// than one GPU (the matrix-free spin operators are one shard).
+// run; time-dependent Hamiltonians; Chebyshev propagators; site operators of complex states; more than one GPU (the matrix-free
+// spin operators are one shard).
 #pragma once
 
 #include <algorithm>
@@ -43,6 +47,7 @@
 
 #include "lanczos.hpp"
 #include "small_eigen.hpp"
+#include "spin_entanglement.hpp"
 #include "spin_operator.hpp"
 
 namespace cmpt {
@@ -194,6 +199,39 @@ class SpinTimeEvolutionSolver {
     device::check(eigenex_dots(dev_.handle(), EIGENEX_VEC_W, dev_.capacity() - 1, 1, 1, 0, h), "eigenex_dots");
     return Complex(h[0], h[1]);
   }
+  // The entanglement of the subsystem `mask` (bit i = site i) with the other sites: the von Neumann entropy, the spectrum of rho_A
+  // (descending) and the Renyi-2 entropy -ln ||rho_A||_F^2 (no eigen-solve).  An invalid subsystem is logged (info(), log()) and
+  // gives 0 or an empty spectrum.  Nothing of the trajectory changes; log() and info() are those of the call.
+  double entanglementEntropy(std::uint32_t mask) {
+    detail::EntanglementBlocks e;
+    return entangle_(mask, true, e) ? e.entropy() : 0.0;
+  }
+  std::vector<double> entanglementSpectrum(std::uint32_t mask) {
+    detail::EntanglementBlocks e;
+    return entangle_(mask, true, e) ? e.spectrum : std::vector<double>();
+  }
+  double entanglementRenyi2(std::uint32_t mask) {
+    detail::EntanglementBlocks e;
+    return entangle_(mask, true, e) ? e.renyi2() : 0.0;
+  }
+  double entanglementEntropy(const std::vector<int>& sites) {
+    bool valid = true;
+    const std::uint32_t mask = siteMask_(sites, valid);
+    detail::EntanglementBlocks e;
+    return entangle_(mask, valid, e) ? e.entropy() : 0.0;
+  }
+  std::vector<double> entanglementSpectrum(const std::vector<int>& sites) {
+    bool valid = true;
+    const std::uint32_t mask = siteMask_(sites, valid);
+    detail::EntanglementBlocks e;
+    return entangle_(mask, valid, e) ? e.spectrum : std::vector<double>();
+  }
+  double entanglementRenyi2(const std::vector<int>& sites) {
+    bool valid = true;
+    const std::uint32_t mask = siteMask_(sites, valid);
+    detail::EntanglementBlocks e;
+    return entangle_(mask, valid, e) ? e.renyi2() : 0.0;
+  }
   // psi(t) on the host, the kept norm multiplied back
   VectorType state() {
     if (!measurable_()) return VectorType();
@@ -343,6 +381,36 @@ class SpinTimeEvolutionSolver {
     }
     device::check(eigenex_krylov_combine_to(dev_.handle(), k, cre.data(), cim.data(), EIGENEX_VEC_W), "eigenex_krylov_combine_to");
     device::check(eigenex_basis_clear(dev_.handle()), "eigenex_basis_clear");
+    return true;
+  }
+
+  static std::uint32_t siteMask_(const std::vector<int>& sites, bool& valid) {
+    std::uint32_t mask = 0;
+    for (int i : sites) {
+      if (i < 0 || i > 31 || ((mask >> i) & 1u)) valid = false;
+      else mask |= std::uint32_t(1) << i;
+    }
+    return mask;
+  }
+  // rho_A of W, to unit trace and diagonalised; false (and logged) for an invalid subsystem or without a state
+  bool entangle_(std::uint32_t mask, bool sitesValid, detail::EntanglementBlocks& e) {
+    begin_("entanglement");  // these calls can be refused: the log and info() are theirs, as for setState and evolve
+    if (!measurable_()) return invalid_("invalid input: no state (setState, setProductState)"), false;
+    if (!sitesValid) return invalid_("invalid input: the subsystem names a site outside 0..31 or names a site twice"), false;
+    int nBlocks = 0, kFirst = 0;
+    std::int64_t dims[33], offsets[34];
+    if (eigenex_spin_rdm_layout(model_.sites(), nUp_, mask, &nBlocks, &kFirst, dims, offsets) != 0)
+      return invalid_(std::string("invalid input: ") + eigenex_last_error()), false;
+    std::vector<double> raw(2 * static_cast<std::size_t>(offsets[nBlocks]), 0.0);
+    device::check(eigenex_spin_rdm_z(dev_.handle(), EIGENEX_VEC_W, mask, raw.data(), static_cast<std::int64_t>(raw.size())), "eigenex_spin_rdm_z");
+    switch (e.assemble(raw, true, nBlocks, kFirst, dims, offsets)) {
+      case detail::EntanglementBlocks::ZeroState:
+        return failed_("the state is zero (or not finite)"), false;
+      case detail::EntanglementBlocks::NoConvergence:
+        return failed_("the eigen-solve of a block of the reduced density matrix did not converge"), false;
+      case detail::EntanglementBlocks::Ok:
+        break;
+    }
     return true;
   }
 

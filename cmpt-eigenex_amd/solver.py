@@ -117,6 +117,7 @@ def lib():
         getattr(L, p + "status").argtypes = [_vp, _dp, _lp]
         getattr(L, p + "scalar").argtypes = [_vp, C.c_int, _dp]
         getattr(L, p + "measure").argtypes = [_vp, C.c_int, _lp]
+        getattr(L, p + "entanglement").argtypes = [_vp, C.c_uint32, _ip32, C.c_int, C.c_int, _lp]
         getattr(L, p + "fetch").argtypes = [_vp, _dp]
         getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
         getattr(L, p + "log_line").restype = C.c_char_p
@@ -132,6 +133,8 @@ def lib():
         getattr(L, p + "compute").argtypes = [_vp]
         getattr(L, p + "sizes").argtypes = [_vp, _lp]
         getattr(L, p + "block").argtypes = [_vp, C.c_int64, C.POINTER(C.c_int), _lp, _dp]
+        getattr(L, p + "set_state_z").argtypes = [_vp, _dp, C.c_int64]
+        getattr(L, p + "block_z").argtypes = [_vp, C.c_int64, C.POINTER(C.c_int), _dp]
         getattr(L, p + "get").argtypes = [_vp, _dp, _dp]
         getattr(L, p + "renyi").argtypes = [_vp, C.c_double, _dp]
         getattr(L, p + "schmidt_rank").argtypes = [_vp, C.c_double, _lp]
@@ -873,6 +876,29 @@ class SpinTimeEvolutionSolver:
     def state(self):
         return self._vector(3).view(np.complex128)
 
+    def _entanglement(self, subsystem, what):
+        """subsystem: a site mask (int) or a list of sites"""
+        n = C.c_int64()
+        if isinstance(subsystem, (int, np.integer)):
+            _chk(self._f("entanglement")(self.h, int(subsystem), None, 0, what, C.byref(n)))
+        else:
+            a = np.ascontiguousarray(subsystem, np.int32).reshape(-1)
+            keep = a if a.size else np.zeros(1, np.int32)  # an empty list is still a list: a non-NULL pointer
+            _chk(self._f("entanglement")(self.h, 0, keep.ctypes.data_as(C.POINTER(C.c_int32)), a.size, what, C.byref(n)))
+        out = np.zeros(n.value)
+        _chk(self._f("fetch")(self.h, _d(out)))
+        return out
+
+    def entanglementEntropy(self, subsystem):
+        """the von Neumann entropy of the subsystem (a site mask or a list of sites) of psi(t), formed on the device"""
+        return float(self._entanglement(subsystem, 0)[0])
+
+    def entanglementRenyi2(self, subsystem):
+        return float(self._entanglement(subsystem, 1)[0])
+
+    def entanglementSpectrum(self, subsystem):
+        return self._entanglement(subsystem, 2)
+
     def log(self):
         return [self._f("log_line")(self.h, i).decode() for i in range(int(self._status()[1][0]))]
 
@@ -911,8 +937,13 @@ class SpinEntanglementSolver:
         return self
 
     def setState(self, v):
-        a = np.ascontiguousarray(v, np.float64)
-        _chk(self._f("set_state")(self.h, _d(a), a.size))
+        """a real state, or a complex one (then the operator must be one for complex states: complex_states=True)"""
+        if np.iscomplexobj(v):
+            a = np.ascontiguousarray(v, np.complex128)
+            _chk(self._f("set_state_z")(self.h, _d(a.view(np.float64)), a.size))
+        else:
+            a = np.ascontiguousarray(v, np.float64)
+            _chk(self._f("set_state")(self.h, _d(a), a.size))
         return self
 
     def setSubsystem(self, sites):
@@ -940,10 +971,16 @@ class SpinEntanglementSolver:
         spectrum, sc, blocks = np.zeros(s["neigenvalues"]), np.zeros(3), []
         _chk(self._f("get")(self.h, _d(spectrum), _d(sc)))
         for n in range(s["nblocks"]):
-            up, dim = C.c_int(), C.c_int64()
+            up, dim, cplx = C.c_int(), C.c_int64(), C.c_int()
             _chk(self._f("block")(self.h, n, C.byref(up), C.byref(dim), None))
-            rho = np.zeros(dim.value * dim.value)
-            _chk(self._f("block")(self.h, n, None, None, _d(rho)))
+            _chk(self._f("block_z")(self.h, n, C.byref(cplx), None))
+            if cplx.value:  # a complex state: complex128 blocks
+                rho = np.zeros(2 * dim.value * dim.value)
+                _chk(self._f("block_z")(self.h, n, None, _d(rho)))
+                rho = rho.view(np.complex128)
+            else:
+                rho = np.zeros(dim.value * dim.value)
+                _chk(self._f("block")(self.h, n, None, None, _d(rho)))
             blocks.append((up.value, rho.reshape(dim.value, dim.value).T.copy()))
         s.update(blocks=blocks, spectrum=spectrum, normSquared=sc[0], entropy=sc[1], renyi2=sc[2], info_name=INFO[s["info"]])
         return s

@@ -311,7 +311,9 @@ int eigenex_spin_sector_upload(eigenex_context_t ctx, int n_sites, int n_up, int
  * (eigenex_basis_configure_z) is a plain complex multiply added last.  The dot is conj(x) . y.  eigenex_spin_geometry,
  * eigenex_csr_info, eigenex_csr_layout and eigenex_csr_encoding answer as for the real handles.  On a complex spin state:
  *   eigenex_spin_measure                             the Hermitian sums, see below
+ *   eigenex_spin_rdm_z                               the reduced density matrix M M^H, see below
  *   eigenex_spin_rdm, eigenex_spin_site_apply        EIGENEX_ERR_STATE, "real states only", before anything is allocated
+ *                                                    (eigenex_spin_rdm's message names eigenex_spin_rdm_z)
  *   eigenex_basis_set_filter, eigenex_filter_apply,  supported: a complex state takes the streaming form of the Chebyshev step,
  *   eigenex_kpm_moments, eigenex_kpm_trace_moments   whose real coefficients act on both parts alike and whose dots are the real
  *                                                    parts of the Hermitian ones, which is all a Hermitian operator's moments
@@ -426,6 +428,20 @@ int eigenex_spin_rdm_layout(int n_sites, int n_up /* -1: full space */, uint32_t
 int eigenex_spin_rdm(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out, int64_t out_len);
 int eigenex_spin_rdm_host(int n_sites, int n_up /* -1: full space */, const double* x, uint32_t mask_a, double* out,
                           int64_t out_len);
+/* The same for a COMPLEX vector x (interleaved (re, im) pairs): rho[i, j] = sum_b M[i, b] conj(M[j, b]) over the same blocks, with
+ * the same layout, limits, argument check and messages (under these names).  out: the blocks packed in ascending k, each a full
+ * column-major d_k x d_k matrix of interleaved (re, im) pairs; out_len = 2 * the layout's length.  Raw sums: the trace is
+ * sum |x|^2.  The imaginary part of a diagonal entry is +0.0 and (j, i) holds the bits of (i, j) with the imaginary part negated.
+ *   eigenex_spin_rdm_z       x = any vector reference of a COMPLEX state whose operator handle came from eigenex_spin_upload_z or
+ *                            eigenex_spin_sector_upload_z.  EIGENEX_ERR_STATE: a real state (that is eigenex_spin_rdm), any other
+ *                            operator, a host callback.  Everything else as eigenex_spin_rdm: the same plan and slices (the
+ *                            scratch is twice the real call's), no atomics, nothing of the state touched, identical bytes from
+ *                            two calls.
+ *   eigenex_spin_rdm_host_z  the definition in host code: per entry i >= j one chain over ascending b of four fmas per term,
+ *                            re += ar_i ar_j, re += ai_i ai_j, im += ai_i ar_j, im -= ar_i ai_j. */
+int eigenex_spin_rdm_z(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out, int64_t out_len);
+int eigenex_spin_rdm_host_z(int n_sites, int n_up /* -1: full space */, const double* x /* interleaved */, uint32_t mask_a,
+                            double* out, int64_t out_len);
 /* CSR that already lives in device memory of this context's GPU (e.g. tensors of a GPU framework: pass their
  * data pointers): copied device-to-device, never through the host, after a device-side check of the row pointers
  * and column indices.  Unsharded contexts only; rowptr_dev[0] = 0; columns are global = local indices. */
