@@ -355,28 +355,27 @@ def _mask_list(masks):
     return m, int(m.size), (m.ctypes.data_as(_up) if m.size else None)
 
 
-def spin_measure_host(n_sites: int, n_up, x, diag_masks, flip_masks):
-    """eigenex_spin_measure_host: the raw sums (diag, flip, norm2) of the masks over the real vector x, in host code (no GPU).
-    n_up = None: the full space (x has 2^n_sites entries), else the sector of n_up sites up (C(n_sites, n_up) entries)."""
-    x = np.ascontiguousarray(x, np.float64)
+def _spin_measure_host(entry, dtype, n_sites, n_up, x, diag_masks, flip_masks):
+    """spin_measure_host and spin_measure_host_z: x as dtype, handed over as doubles"""
+    x = np.ascontiguousarray(x, dtype)
     dm, nd, dp = _mask_list(diag_masks)
     fm, nf, fp = _mask_list(flip_masks)
     diag, flip, norm2 = np.zeros(nd), np.zeros(nf), C.c_double()
-    _chk(lib().eigenex_spin_measure_host(int(n_sites), -1 if n_up is None else int(n_up), _d(x), nd, dp, nf, fp, _d(diag) if nd else None,
-                                         _d(flip) if nf else None, C.byref(norm2)))
+    _chk(entry(int(n_sites), -1 if n_up is None else int(n_up), _d(x.view(np.float64)), nd, dp, nf, fp, _d(diag) if nd else None,
+               _d(flip) if nf else None, C.byref(norm2)))
     return diag, flip, norm2.value
+
+
+def spin_measure_host(n_sites: int, n_up, x, diag_masks, flip_masks):
+    """eigenex_spin_measure_host: the raw sums (diag, flip, norm2) of the masks over the real vector x, in host code (no GPU).
+    n_up = None: the full space (x has 2^n_sites entries), else the sector of n_up sites up (C(n_sites, n_up) entries)."""
+    return _spin_measure_host(lib().eigenex_spin_measure_host, np.float64, n_sites, n_up, x, diag_masks, flip_masks)
 
 
 def spin_measure_host_z(n_sites: int, n_up, x, diag_masks, flip_masks):
     """eigenex_spin_measure_host_z: the Hermitian raw sums (diag, flip, norm2) of the masks over the complex vector x, in host code
     (no GPU); n_up as for spin_measure_host."""
-    x = np.ascontiguousarray(x, np.complex128)
-    dm, nd, dp = _mask_list(diag_masks)
-    fm, nf, fp = _mask_list(flip_masks)
-    diag, flip, norm2 = np.zeros(nd), np.zeros(nf), C.c_double()
-    _chk(lib().eigenex_spin_measure_host_z(int(n_sites), -1 if n_up is None else int(n_up), _d(x.view(np.float64)), nd, dp, nf, fp,
-                                           _d(diag) if nd else None, _d(flip) if nf else None, C.byref(norm2)))
-    return diag, flip, norm2.value
+    return _spin_measure_host(lib().eigenex_spin_measure_host_z, np.complex128, n_sites, n_up, x, diag_masks, flip_masks)
 
 
 def spin_rdm_layout(n_sites: int, n_up, mask_a: int):
@@ -390,39 +389,33 @@ def spin_rdm_layout(n_sites: int, n_up, mask_a: int):
     return kf.value, [int(d) for d in dims[: nb.value]], [int(o) for o in offs[: nb.value + 1]]
 
 
-def _rdm_blocks(k_first, dims, offsets, out):
-    """the packed column-major blocks as [(k, ndarray(d, d)), ...] (copies)"""
-    return [(k_first + n, out[offsets[n] : offsets[n + 1]].reshape(d, d).T.copy()) for n, d in enumerate(dims)]
+def _rdm_blocks(k_first, dims, offsets, out, dtype):
+    """the packed column-major blocks (doubles; of a complex dtype interleaved pairs) as [(k, ndarray(d, d), dtype), ...] (copies)"""
+    z = out.view(dtype)
+    return [(k_first + n, z[offsets[n] : offsets[n + 1]].reshape(d, d).T.copy()) for n, d in enumerate(dims)]
+
+
+def _spin_rdm_host(name, dtype, n_sites, n_up, x, mask_a):
+    """spin_rdm_host and spin_rdm_host_z: x as dtype, x and the result handed over as doubles"""
+    x = np.ascontiguousarray(x, dtype)
+    kf, dims, offs = spin_rdm_layout(n_sites, n_up, mask_a)
+    if x.size != (1 << int(n_sites) if n_up is None else spin_sector_dim(n_sites, n_up)):  # the library cannot see the length
+        raise EigenexError(name + ": x must have one entry per row of the geometry")
+    out = np.zeros(offs[-1], dtype).view(np.float64)
+    _chk(getattr(lib(), "eigenex_" + name)(int(n_sites), -1 if n_up is None else int(n_up), _d(x.view(np.float64)), int(mask_a), _d(out), out.size))
+    return _rdm_blocks(kf, dims, offs, out, dtype)
 
 
 def spin_rdm_host(n_sites: int, n_up, x, mask_a: int):
     """eigenex_spin_rdm_host: the raw, unnormalised reduced density matrix of the subsystem mask_a of the real vector x as a list
     of (k, ndarray(d_k, d_k)), in host code (no GPU).  n_up = None: the full space (one block, k = 0)."""
-    x = np.ascontiguousarray(x, np.float64)
-    kf, dims, offs = spin_rdm_layout(n_sites, n_up, mask_a)
-    if x.size != (1 << int(n_sites) if n_up is None else spin_sector_dim(n_sites, n_up)):  # the library cannot see the length
-        raise EigenexError("spin_rdm_host: x must have one entry per row of the geometry")
-    out = np.zeros(offs[-1])
-    _chk(lib().eigenex_spin_rdm_host(int(n_sites), -1 if n_up is None else int(n_up), _d(x), int(mask_a), _d(out), out.size))
-    return _rdm_blocks(kf, dims, offs, out)
-
-
-def _rdm_blocks_z(k_first, dims, offsets, out):
-    """the packed column-major blocks of interleaved pairs as [(k, ndarray(d, d), complex128), ...] (copies)"""
-    z = out.view(np.complex128)
-    return [(k_first + n, z[offsets[n] : offsets[n + 1]].reshape(d, d).T.copy()) for n, d in enumerate(dims)]
+    return _spin_rdm_host("spin_rdm_host", np.float64, n_sites, n_up, x, mask_a)
 
 
 def spin_rdm_host_z(n_sites: int, n_up, x, mask_a: int):
     """eigenex_spin_rdm_host_z: the raw, unnormalised reduced density matrix M M^H of the subsystem mask_a of the complex vector
     x as a list of (k, ndarray(d_k, d_k), complex128), in host code (no GPU).  n_up = None: the full space (one block, k = 0)."""
-    x = np.ascontiguousarray(x, np.complex128)
-    kf, dims, offs = spin_rdm_layout(n_sites, n_up, mask_a)
-    if x.size != (1 << int(n_sites) if n_up is None else spin_sector_dim(n_sites, n_up)):  # the library cannot see the length
-        raise EigenexError("spin_rdm_host_z: x must have one entry per row of the geometry")
-    out = np.zeros(2 * offs[-1])
-    _chk(lib().eigenex_spin_rdm_host_z(int(n_sites), -1 if n_up is None else int(n_up), _d(x.view(np.float64)), int(mask_a), _d(out), out.size))
-    return _rdm_blocks_z(kf, dims, offs, out)
+    return _spin_rdm_host("spin_rdm_host_z", np.complex128, n_sites, n_up, x, mask_a)
 
 
 def spin_site_apply_host(n_sites: int, n_up, kind: int, coef, x):
@@ -857,37 +850,31 @@ class Basis:
         _chk(lib().eigenex_spin_measure(self.h, x_ref, nd, dp, nf, fp, _d(diag) if nd else None, _d(flip) if nf else None, C.byref(norm2)))
         return diag, flip, norm2.value
 
+    def _spin_rdm(self, entry, dtype, x_ref, mask_a):
+        """spin_rdm and spin_rdm_z: the result is handed over as doubles and returned as blocks of dtype"""
+        ns, nu = C.c_int(), C.c_int()
+        if self.csr is None or lib().eigenex_spin_geometry(self.csr.h, C.byref(ns), C.byref(nu)) != 0:
+            _chk(entry(self.h, x_ref, int(mask_a), None, 0))  # the library says what is wrong with the state
+        try:
+            kf, dims, offs = spin_rdm_layout(ns.value, None if nu.value < 0 else nu.value, mask_a)
+        except EigenexError:
+            _chk(entry(self.h, x_ref, int(mask_a), None, 0))  # the same refusal under the entry point's own name
+            raise
+        out = np.zeros(offs[-1], dtype).view(np.float64)
+        _chk(entry(self.h, x_ref, int(mask_a), _d(out), out.size))
+        return _rdm_blocks(kf, dims, offs, out, dtype)
+
     def spin_rdm(self, x_ref, mask_a):
         """eigenex_spin_rdm: the raw, unnormalised reduced density matrix of the subsystem mask_a of the vector x_ref, formed on
         the device, as a list of (k, ndarray(d_k, d_k)); the operator of this state must be a matrix-free spin operator.  No
         vector and no coefficient changes."""
-        ns, nu = C.c_int(), C.c_int()
-        if self.csr is None or lib().eigenex_spin_geometry(self.csr.h, C.byref(ns), C.byref(nu)) != 0:
-            _chk(lib().eigenex_spin_rdm(self.h, x_ref, int(mask_a), None, 0))  # the library says what is wrong with the state
-        try:
-            kf, dims, offs = spin_rdm_layout(ns.value, None if nu.value < 0 else nu.value, mask_a)
-        except EigenexError:
-            _chk(lib().eigenex_spin_rdm(self.h, x_ref, int(mask_a), None, 0))  # the same refusal under the entry point's own name
-            raise
-        out = np.zeros(offs[-1])
-        _chk(lib().eigenex_spin_rdm(self.h, x_ref, int(mask_a), _d(out), out.size))
-        return _rdm_blocks(kf, dims, offs, out)
+        return self._spin_rdm(lib().eigenex_spin_rdm, np.float64, x_ref, mask_a)
 
     def spin_rdm_z(self, x_ref, mask_a):
         """eigenex_spin_rdm_z: the raw, unnormalised reduced density matrix M M^H of the subsystem mask_a of the complex vector
         x_ref, formed on the device, as a list of (k, ndarray(d_k, d_k), complex128); the state must be a complex one on a
         matrix-free spin operator for complex states.  No vector and no coefficient changes."""
-        ns, nu = C.c_int(), C.c_int()
-        if self.csr is None or lib().eigenex_spin_geometry(self.csr.h, C.byref(ns), C.byref(nu)) != 0:
-            _chk(lib().eigenex_spin_rdm_z(self.h, x_ref, int(mask_a), None, 0))  # the library says what is wrong with the state
-        try:
-            kf, dims, offs = spin_rdm_layout(ns.value, None if nu.value < 0 else nu.value, mask_a)
-        except EigenexError:
-            _chk(lib().eigenex_spin_rdm_z(self.h, x_ref, int(mask_a), None, 0))  # the same refusal under the entry point's own name
-            raise
-        out = np.zeros(2 * offs[-1])
-        _chk(lib().eigenex_spin_rdm_z(self.h, x_ref, int(mask_a), _d(out), out.size))
-        return _rdm_blocks_z(kf, dims, offs, out)
+        return self._spin_rdm(lib().eigenex_spin_rdm_z, np.complex128, x_ref, mask_a)
 
     def spin_site_apply(self, x_ref, dst, y_ref, kind, coef):
         """eigenex_spin_site_apply: vector y_ref of the state dst = (sum of site operators kind, coef) applied to vector x_ref of

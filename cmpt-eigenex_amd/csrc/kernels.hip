@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace eigenex {
 
@@ -1651,71 +1652,13 @@ struct SpinRankTables {
   __device__ __forceinline__ uint32_t hi(uint32_t i) const { return hi_base[i]; }
   __device__ __forceinline__ uint32_t lo(uint32_t i) const { return lo_rank[i]; }
 };
+// Every kernel of a vector's elements is written once for E = double and E = SpinZ (spin_rows.hpp), an interleaved complex
+// vector.  SpinElement<E> has what the device adds: the type an element is loaded and stored as (one 8-byte or one 16-byte
+// access) and the accessor of the walk.
 struct SpinVector {
   const double* x;
   __device__ __forceinline__ double operator()(uint32_t i) const { return x[i]; }
 };
-
-// the workgroup's copy of the binomials; the caller synchronises
-__device__ __forceinline__ void spin_stage_binomials(const SpinSectorView* __restrict__ op, uint32_t* binom) {
-  constexpr int kCols = kSectorMaxSites + 1;
-  for (int i = threadIdx.x; i < kSectorMaxSites * kCols; i += kBlock) binom[i] = op->binom[i / kCols][i % kCols];
-}
-
-template <bool SECTOR>
-__global__ __launch_bounds__(kBlock) void k_spin_spmv(const SpinSectorView* __restrict__ op, const uint32_t* __restrict__ lo_rank,
-                                                      const uint32_t* __restrict__ hi_base, const double* __restrict__ x_ext,
-                                                      const double* __restrict__ scale_ptr, double shift, double* __restrict__ y,
-                                                      double* __restrict__ u_out, int64_t n, int64_t ntiles,
-                                                      double* __restrict__ partials, int pass, const Ctrl* __restrict__ ctrl) {
-  __shared__ double lds4[4];
-  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
-  if (ctrl->stopped) return;
-  int n_up = 0, h = 0;
-  uint32_t lo_mask = 0;
-  if constexpr (SECTOR) {
-    spin_stage_binomials(op, binom);
-    __syncthreads();
-    n_up = op->n_up, h = op->h, lo_mask = op->lo_mask;
-  }
-  const double scale = scale_ptr ? *scale_ptr : 1.0;
-  const SpinOperatorView* model = &op->model;
-  const int n_sites = model->n_sites, ndiag = model->ndiag, nflip = model->nflip;
-  const SpinRankTables tab{lo_rank, hi_base};
-  double dot = 0.0;
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t r = tile * kBlock + threadIdx.x;
-    if (r < n) {
-      const uint32_t s = SECTOR ? spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s : (uint32_t)r;
-      const double d = spin_row_diagonal(model->dmask, model->dval, ndiag, s);
-      const double xr = x_ext[r] * scale;
-      double yr = add_product_nofma(0.0, d, xr);
-      for (int t0 = 0; t0 < nflip; t0 += kSpinBatch) {
-        bool on[kSpinBatch];
-        uint32_t base[kSpinBatch], low[kSpinBatch];
-        double xv[kSpinBatch];
-        spin_flip_targets<SECTOR>(model->fmask + t0, s, tab, h, lo_mask, on, base, low);
-        spin_gather(SpinVector{x_ext}, base, low, xv);
-        yr = spin_add_flips(yr, model->fval + t0, on, xv, scale);
-      }
-      if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
-      y[r] = yr;
-      if (u_out) u_out[r] = xr;
-      dot = (pass & kPassSelfNorm) ? fma(yr, yr, dot) : fma(xr, yr, dot);
-    }
-  }
-  if (partials) {
-    dot = block_sum(dot, lds4);
-    if (threadIdx.x == 0) partials[blockIdx.x] = dot;
-  }
-}
-
-// The same real operator on an interleaved complex vector: y = (H + shift) (x * scale) with a complex shift.  The row walk is
-// k_spin_spmv's, taken once per row for both parts (state, diagonal, flip targets and the rank-table gathers); x is gathered as
-// 16-byte loads and each part accumulates the real kernel's sum of that part (spin_rows.hpp: spin_add_flips_z).  The shift, u_out,
-// the pass bits, ctrl->stopped and the two partial dots, conj(u) . y or |y|^2, follow k_spmv_z -- except that a norm
-// (kPassSelfNorm) leaves the second set unwritten: it is one real sum with one set of readers, and one of its callers hands
-// over a buffer of pstride doubles (library.hip: palpha).
 struct SpinVectorZ {
   const double2* x;
   __device__ __forceinline__ SpinZ operator()(uint32_t i) const {
@@ -1723,14 +1666,50 @@ struct SpinVectorZ {
     return SpinZ{v.x, v.y};
   }
 };
+template <class E>
+struct SpinElement {
+  using Stored = double;
+  using Vector = SpinVector;
+};
+template <>
+struct SpinElement<SpinZ> {
+  using Stored = double2;
+  using Vector = SpinVectorZ;
+};
+__device__ __forceinline__ double spin_loaded(double v) { return v; }
+__device__ __forceinline__ SpinZ spin_loaded(double2 v) { return SpinZ{v.x, v.y}; }
+__device__ __forceinline__ double spin_stored(double v) { return v; }
+__device__ __forceinline__ double2 spin_stored(SpinZ v) { return make_double2(v.re, v.im); }
 
-template <bool SECTOR>
-__global__ __launch_bounds__(kBlock) void k_spin_spmv_z(const SpinSectorView* __restrict__ op, const uint32_t* __restrict__ lo_rank,
-                                                        const uint32_t* __restrict__ hi_base, const double2* __restrict__ x_ext,
-                                                        const double* __restrict__ scale_ptr, double shift_re, double shift_im,
-                                                        double2* __restrict__ y, double2* __restrict__ u_out, int64_t n, int64_t ntiles,
-                                                        double* __restrict__ partials, int pstride, int pass,
-                                                        const Ctrl* __restrict__ ctrl) {
+// the workgroup's copy of the binomials; the caller synchronises
+__device__ __forceinline__ void spin_stage_binomials(const SpinSectorView* __restrict__ op, uint32_t* binom) {
+  constexpr int kCols = kSectorMaxSites + 1;
+  for (int i = threadIdx.x; i < kSectorMaxSites * kCols; i += kBlock) binom[i] = op->binom[i / kCols][i % kCols];
+}
+
+// y = (H + shift) (x * scale).  On an interleaved complex vector it is the same real operator: the row walk is taken once per row
+// for both parts (state, diagonal, flip targets and the rank-table gathers), x is gathered as 16-byte loads and each part
+// accumulates the real sum of that part (spin_rows.hpp: spin_add_flips).  The shift is then complex, and the two partial dots,
+// conj(u) . y or |y|^2, follow k_spmv_z, with the second set at partials[pstride + workgroup] -- except that a norm
+// (kPassSelfNorm) leaves the second set unwritten: it is one real sum with one set of readers, and one of its callers hands
+// over a buffer of pstride doubles (library.hip: palpha).  The two arguments that only a complex vector has, shift_im and
+// pstride, are expansions of the pack ComplexOnly: <int> for E = SpinZ, empty for double, whose kernel so keeps its single
+// shift and its one set of partials.  (As scalar arguments and not as members of E or of a struct: the loads of a struct argument
+// are not merged with the other arguments' loads.)  u_out, the pass bits and ctrl->stopped are the same for both.
+template <class>
+using SpinShiftIm = double;
+
+template <bool SECTOR, class E, class... ComplexOnly>
+__global__ __launch_bounds__(kBlock) void k_spin_spmv(const SpinSectorView* __restrict__ op, const uint32_t* __restrict__ lo_rank,
+                                                      const uint32_t* __restrict__ hi_base,
+                                                      const typename SpinElement<E>::Stored* __restrict__ x_ext,
+                                                      const double* __restrict__ scale_ptr, double shift, SpinShiftIm<ComplexOnly>... shift_im,
+                                                      typename SpinElement<E>::Stored* __restrict__ y,
+                                                      typename SpinElement<E>::Stored* __restrict__ u_out, int64_t n, int64_t ntiles,
+                                                      double* __restrict__ partials, ComplexOnly... pstride, int pass,
+                                                      const Ctrl* __restrict__ ctrl) {
+  static_assert(sizeof...(ComplexOnly) == (std::is_same<E, SpinZ>::value ? 1 : 0), "shift_im and pstride for complex vectors only");
+  constexpr bool COMPLEX = std::is_same<E, SpinZ>::value;
   __shared__ double lds4[4];
   __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
   if (ctrl->stopped) return;
@@ -1742,50 +1721,58 @@ __global__ __launch_bounds__(kBlock) void k_spin_spmv_z(const SpinSectorView* __
     n_up = op->n_up, h = op->h, lo_mask = op->lo_mask;
   }
   const double scale = scale_ptr ? *scale_ptr : 1.0;
-  const bool has_shift = shift_re != 0.0 || shift_im != 0.0;
+  bool has_shift = false;  // a complex shift is tested once, here
+  if constexpr (COMPLEX) has_shift = shift != 0.0 || (shift_im + ...) != 0.0;
   const SpinOperatorView* model = &op->model;
   const int n_sites = model->n_sites, ndiag = model->ndiag, nflip = model->nflip;
   const SpinRankTables tab{lo_rank, hi_base};
-  double dr = 0.0, di = 0.0;
+  double dot = 0.0, dot_im = 0.0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t r = tile * kBlock + threadIdx.x;
     if (r < n) {
       const uint32_t s = SECTOR ? spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s : (uint32_t)r;
       const double d = spin_row_diagonal(model->dmask, model->dval, ndiag, s);
-      double2 xr = x_ext[r];
-      xr.x *= scale;
-      xr.y *= scale;
-      SpinZ acc{add_product_nofma(0.0, d, xr.x), add_product_nofma(0.0, d, xr.y)};
+      const E xr = spin_scaled(spin_loaded(x_ext[r]), scale);  // the row's own element by its 64-bit index, not through the accessor
+      E yr = spin_add_product(E{}, d, xr);
       for (int t0 = 0; t0 < nflip; t0 += kSpinBatch) {
         bool on[kSpinBatch];
         uint32_t base[kSpinBatch], low[kSpinBatch];
-        SpinZ xv[kSpinBatch];
+        E xv[kSpinBatch];
         spin_flip_targets<SECTOR>(model->fmask + t0, s, tab, h, lo_mask, on, base, low);
-        spin_gather_z(SpinVectorZ{x_ext}, base, low, xv);
-        acc = spin_add_flips_z(acc, model->fval + t0, on, xv, scale);
+        spin_gather(typename SpinElement<E>::Vector{x_ext}, base, low, xv);
+        yr = spin_add_flips(yr, model->fval + t0, on, xv, scale);
       }
-      double2 yr = make_double2(acc.re, acc.im);
-      if (has_shift) {
-        const double2 t = cmul_nofma(make_double2(shift_re, shift_im), xr);
-        yr.x = yr.x + t.x;
-        yr.y = yr.y + t.y;
-      }
-      y[r] = yr;
-      if (u_out) u_out[r] = xr;
-      if (pass & kPassSelfNorm) {
-        dr = fma(yr.x, yr.x, fma(yr.y, yr.y, dr));  // |y|^2
+      if constexpr (COMPLEX) {
+        if (has_shift) {
+          const double2 t = cmul_nofma(make_double2(shift, (shift_im + ...)), spin_stored(xr));
+          yr.re = yr.re + t.x;
+          yr.im = yr.im + t.y;
+        }
       } else {
-        dr = fma(xr.x, yr.x, fma(xr.y, yr.y, dr));  // conj(u) * y
-        di = fma(xr.x, yr.y, fma(-xr.y, yr.x, di));
+        if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
+      }
+      y[r] = spin_stored(yr);
+      if (u_out) u_out[r] = spin_stored(xr);
+      if constexpr (COMPLEX) {
+        if (pass & kPassSelfNorm) {
+          dot = fma(yr.re, yr.re, fma(yr.im, yr.im, dot));  // |y|^2
+        } else {
+          dot = fma(xr.re, yr.re, fma(xr.im, yr.im, dot));  // conj(u) * y
+          dot_im = fma(xr.re, yr.im, fma(-xr.im, yr.re, dot_im));
+        }
+      } else {
+        dot = (pass & kPassSelfNorm) ? fma(yr, yr, dot) : fma(xr, yr, dot);
       }
     }
   }
   if (partials) {
-    dr = block_sum(dr, lds4);
-    di = block_sum(di, lds4);
+    dot = block_sum(dot, lds4);
+    if constexpr (COMPLEX) dot_im = block_sum(dot_im, lds4);
     if (threadIdx.x == 0) {
-      partials[blockIdx.x] = dr;
-      if (!(pass & kPassSelfNorm)) partials[pstride + blockIdx.x] = di;  // a norm is one set of partials: its readers have room for one
+      partials[blockIdx.x] = dot;
+      // a norm is one set of partials: its readers have room for one
+      if constexpr (COMPLEX)
+        if (!(pass & kPassSelfNorm)) partials[(pstride + ...) + blockIdx.x] = dot_im;
     }
   }
 }
@@ -1798,11 +1785,14 @@ __global__ __launch_bounds__(kBlock) void k_spin_spmv_z(const SpinSectorView* __
 // constant after unrolling, a batch is skipped as a whole where the chunk has no term in it -- and leave through block_sum into
 // partials[sum * pstride + workgroup]; k_spin_measure_reduce adds those in k_reduce_fin's order.  No atomics: a result depends on
 // the grid only through the grouping of the partial sums.  ctrl->stopped is not consulted: a measurement is not a Krylov step.
+// Of an interleaved complex vector (E = SpinZ) the sums are the Hermitian ones of spin_measure.hpp: |x_s|^2 for x_s^2 and
+// Re(conj(x_s) x_{s ^ mask}) for the product of a flip, two fmas per term (real part, then imaginary part); chunks, registers,
+// partials and the second stage are the same, and x is read as 16-byte loads.
 // ---------------------------------------------------------------------------
-template <bool SECTOR>
+template <bool SECTOR, class E>
 __global__ __launch_bounds__(kBlock) void k_spin_measure(const SpinMeasureChunk* __restrict__ ch, const SpinSectorView* __restrict__ op,
                                                          const uint32_t* __restrict__ lo_rank, const uint32_t* __restrict__ hi_base,
-                                                         const double* __restrict__ x, int64_t n, int64_t ntiles,
+                                                         const typename SpinElement<E>::Stored* __restrict__ x, int64_t n, int64_t ntiles,
                                                          double* __restrict__ partials, int pstride) {
   constexpr int C = kSpinMeasureChunk;
   __shared__ double lds4[4];
@@ -1823,8 +1813,12 @@ __global__ __launch_bounds__(kBlock) void k_spin_measure(const SpinMeasureChunk*
     const int64_t r = tile * kBlock + threadIdx.x;
     if (r < n) {
       const uint32_t s = SECTOR ? spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s : (uint32_t)r;
-      const double xs = x[r];
-      nrm = fma(xs, xs, nrm);
+      E xs;  // the row's own element: a real one by its 64-bit index, a complex one through the 32-bit accessor, as measured
+      if constexpr (std::is_same<E, SpinZ>::value)
+        xs = SpinVectorZ{x}((uint32_t)r);
+      else
+        xs = x[r];
+      nrm = spin_norm_add(nrm, xs);
 #pragma unroll
       for (int t0 = 0; t0 < C; t0 += kSpinBatch)
         if (t0 < ndiag) spin_measure_diagonals(xs, s, ch->dmask + t0, dg + t0);
@@ -1833,66 +1827,10 @@ __global__ __launch_bounds__(kBlock) void k_spin_measure(const SpinMeasureChunk*
         if (t0 < nflip) {
           bool on[kSpinBatch];
           uint32_t base[kSpinBatch], low[kSpinBatch];
-          double xv[kSpinBatch];
+          E xv[kSpinBatch];
           spin_flip_targets<SECTOR>(ch->fmask + t0, s, tab, h, lo_mask, on, base, low);
-          spin_gather(SpinVector{x}, base, low, xv);
+          spin_gather(typename SpinElement<E>::Vector{x}, base, low, xv);
           spin_measure_flips(xs, on, xv, fl + t0);
-        }
-    }
-  }
-  const auto put = [&](int a, double mine) {  // sum a of this workgroup: 0 norm2, 1 + t diag, 1 + C + t flip
-    const double v = block_sum(mine, lds4);
-    if (threadIdx.x == 0) partials[(int64_t)a * pstride + blockIdx.x] = v;
-  };
-  put(0, nrm);
-#pragma unroll
-  for (int t = 0; t < C; ++t) put(1 + t, dg[t]);
-#pragma unroll
-  for (int t = 0; t < C; ++t) put(1 + C + t, fl[t]);
-}
-
-// The Hermitian sums of an interleaved complex vector (spin_measure.hpp): |x_s|^2 for x_s^2 and Re(conj(x_s) x_{s ^ mask}) for
-// the product of a flip, two fmas per term (real part, then imaginary part).  Chunks, registers, partials and the second stage
-// are k_spin_measure's; x is read as 16-byte loads.
-template <bool SECTOR>
-__global__ __launch_bounds__(kBlock) void k_spin_measure_z(const SpinMeasureChunk* __restrict__ ch, const SpinSectorView* __restrict__ op,
-                                                           const uint32_t* __restrict__ lo_rank, const uint32_t* __restrict__ hi_base,
-                                                           const double2* __restrict__ x, int64_t n, int64_t ntiles,
-                                                           double* __restrict__ partials, int pstride) {
-  constexpr int C = kSpinMeasureChunk;
-  __shared__ double lds4[4];
-  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
-  int n_sites = 0, n_up = 0, h = 0;
-  uint32_t lo_mask = 0;
-  if constexpr (SECTOR) {
-    spin_stage_binomials(op, binom);
-    __syncthreads();
-    n_sites = op->model.n_sites, n_up = op->n_up, h = op->h, lo_mask = op->lo_mask;
-  }
-  const int ndiag = ch->ndiag, nflip = ch->nflip;
-  const SpinRankTables tab{lo_rank, hi_base};
-  double nrm = 0.0, dg[C], fl[C];
-#pragma unroll
-  for (int t = 0; t < C; ++t) dg[t] = 0.0, fl[t] = 0.0;
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t r = tile * kBlock + threadIdx.x;
-    if (r < n) {
-      const uint32_t s = SECTOR ? spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s : (uint32_t)r;
-      const SpinZ xs = SpinVectorZ{x}((uint32_t)r);
-      nrm = fma(xs.re, xs.re, nrm);
-      nrm = fma(xs.im, xs.im, nrm);
-#pragma unroll
-      for (int t0 = 0; t0 < C; t0 += kSpinBatch)
-        if (t0 < ndiag) spin_measure_diagonals_z(xs, s, ch->dmask + t0, dg + t0);
-#pragma unroll
-      for (int t0 = 0; t0 < C; t0 += kSpinBatch)
-        if (t0 < nflip) {
-          bool on[kSpinBatch];
-          uint32_t base[kSpinBatch], low[kSpinBatch];
-          SpinZ xv[kSpinBatch];
-          spin_flip_targets<SECTOR>(ch->fmask + t0, s, tab, h, lo_mask, on, base, low);
-          spin_gather_z(SpinVectorZ{x}, base, low, xv);
-          spin_measure_flips_z(xs, on, xv, fl + t0);
         }
     }
   }
@@ -1981,32 +1919,46 @@ __global__ __launch_bounds__(kBlock) void k_spin_site_apply(const SpinSiteTable*
 
 // ---------------------------------------------------------------------------
 // The reduced density matrix of one vector (spin_rdm.hpp has the definition, the work table and the slicing rule;
-// spin_rdm_rows.hpp the index arithmetic): rho_A = M M^T with M[a, b] = x[rank(dep_A(a) | dep_B(b))] never stored.  One
-// workgroup per work item (block k, tile pair (ti, tj <= ti), slice of the b range).  Per chunk of CHUNK b's the workgroup
+// spin_rdm_rows.hpp the index arithmetic and the panel shape per element, SpinRdmGeometry): rho_A = M M^H with
+// M[a, b] = x[rank(dep_A(a) | dep_B(b))] never stored.  One workgroup per work item (block k, tile pair (ti, tj <= ti), slice
+// of the b range).  Per chunk of CHUNK b's the workgroup
 //   1. forms the states dep_B(b) once (LDS binomials, spin_rdm_party_state with (nB, n_up - k)); the states dep_A(a) of its
 //      TILE rows (and of the other tile's rows) were formed once per item;
-//   2. gathers the TILE x CHUNK panel of x into LDS, one panel for a diagonal pair, two otherwise: 8 loads per lane, all issued
-//      before the first is stored (spin_rdm_element: a padded lane loads row 0 and stores 0).  Panels are b-major with a pitch of
-//      TILE + 2 doubles: a lane's four rows are two 16-byte LDS reads, and a gather whose b's run along the lanes is a 4-way
-//      bank conflict on its stores, not a 64-way one;
+//   2. gathers the TILE x CHUNK panel of x into LDS, one panel for a diagonal pair, two otherwise: LOADS loads per lane and
+//      panel, all issued before the first is stored (spin_rdm_element: a padded lane loads row 0 and stores 0).  Panels are
+//      b-major;
 //   3. accumulates in registers by plain fp64 fma, a 4 x 4 register tile per lane: TILE = 64 is 16 x 16 lanes that each take every
 //      b of the chunk; TILE = 16 is 4 x 4 lanes per group and kSpinRdmSmallGroups groups that take the chunk's b's round robin
 //      (b = group, group + 16, ...) and whose tiles are added in ascending group order through LDS at the end.
 // Each entry i >= j of the tile is written by one lane to this slice's partials; k_spin_rdm_reduce adds the slices.  No atomics:
 // a result depends on the grid only through the number of slices.  ctrl->stopped is not consulted: this is not a Krylov step.
+// The plan, the items, the slices, the party states, the padding rule and the order of the sums are the same for both elements;
+// what differs is the arithmetic and the shape of the panels.
+//   E = double (eigenex_spin_rdm): CHUNK = kSpinRdmBigChunk / kSpinRdmSmallChunk, 8 loads per lane and panel.  The pitch is
+//     TILE + 2 doubles and a lane's four rows are 4 t .. 4 t + 3: two 16-byte LDS reads, and a gather whose b's run along the
+//     lanes is a 4-way bank conflict on its stores, not a 64-way one.
+//   E = SpinZ (eigenex_spin_rdm_z; spin_rdm_host_z is the definition): a panel element is one 16-byte load of x behind one walk
+//     of the rank tables and one 16-byte LDS store; the chunk is kSpinRdmBigChunkZ / kSpinRdmSmallChunkZ b's (four gathers per
+//     lane and panel), the pitch TILE + 1 pairs, and a lane's four rows are t, t + SIDE, t + 2 SIDE, t + 3 SIDE, each one
+//     16-byte LDS read (spin_rdm.hpp has the LDS budgets and the bank argument).  Per pair of rows and per b four fmas in the
+//     definition's order (spin_rdm_fma) into a 4 x 4 register tile of (re, im): 32 fp64 accumulators.  The 16 groups' tiles go
+//     through red[] twice, the real parts, then the imaginary ones.  The imaginary part of a diagonal entry is not stored:
+//     +0.0 is (spin_rdm_entry).
 // ---------------------------------------------------------------------------
-template <bool SECTOR, int TILE>
+template <bool SECTOR, int TILE, class E>
 __global__ __launch_bounds__(kBlock) void k_spin_rdm(const SpinRdmTable* __restrict__ tb, const SpinRdmItem* __restrict__ items,
                                                      const SpinSectorView* __restrict__ op, const uint32_t* __restrict__ lo_rank,
-                                                     const uint32_t* __restrict__ hi_base, const double* __restrict__ x,
-                                                     double* __restrict__ partials) {
-  constexpr int CHUNK = TILE == kSpinRdmBigTile ? kSpinRdmBigChunk : kSpinRdmSmallChunk;
+                                                     const uint32_t* __restrict__ hi_base,
+                                                     const typename SpinElement<E>::Stored* __restrict__ x,
+                                                     typename SpinElement<E>::Stored* __restrict__ partials) {
+  using G = SpinRdmGeometry<E, TILE>;
+  using Stored = typename SpinElement<E>::Stored;
+  constexpr int CHUNK = G::CHUNK, PANEL = G::PANEL, SIDE = G::SIDE;
   constexpr int GROUPS = TILE == kSpinRdmBigTile ? 1 : kSpinRdmSmallGroups;
-  constexpr int SIDE = TILE / 4, PITCH = TILE + 2, LOADS = TILE * CHUNK / kBlock;
+  constexpr int LOADS = TILE * CHUNK / kBlock;
   static_assert(SIDE * SIDE * GROUPS == kBlock && TILE * CHUNK % kBlock == 0 && CHUNK <= kBlock && CHUNK % GROUPS == 0, "tile shape");
   static_assert(GROUPS == 1 || TILE * TILE == kBlock, "the group sums are added by one lane per entry");
-  constexpr int PANEL = CHUNK * PITCH;
-  __shared__ __attribute__((aligned(16))) double panel[(GROUPS == 1 ? 2 : 1) * PANEL];  // a 16-row block has one tile: no second panel
+  __shared__ __attribute__((aligned(16))) Stored panel[(GROUPS == 1 ? 2 : 1) * PANEL];  // a 16-row block has one tile: no second panel
   __shared__ double red[GROUPS > 1 ? GROUPS * TILE * TILE : 1];
   __shared__ uint32_t sa_i[TILE], sa_j[TILE], sb[CHUNK];
   __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
@@ -2026,23 +1978,23 @@ __global__ __launch_bounds__(kBlock) void k_spin_rdm(const SpinRdmTable* __restr
   const int tid = threadIdx.x;
   const SpinBinomials32 bin{binom};
   const SpinRankTables tab{lo_rank, hi_base};
-  const SpinVector xv{x};
+  const typename SpinElement<E>::Vector xv{x};
   if (tid < TILE) {
     sa_i[tid] = spin_rdm_party_state<SECTOR>(bin, nA, k, mask_a, (uint32_t)(i0 + tid), i0 + tid < d);
     sa_j[tid] = spin_rdm_party_state<SECTOR>(bin, nA, k, mask_a, (uint32_t)(j0 + tid), j0 + tid < d);
   }
   const int group = tid / (SIDE * SIDE), tx = tid % SIDE, ty = tid % (SIDE * SIDE) / SIDE;
   const int other = diagonal || GROUPS > 1 ? 0 : PANEL;  // where the rows a_j of the pair lie: a diagonal pair has one panel
-  double acc[4][4];
+  double re[4][4], im[4][4];  // the accumulators part by part (spin_rdm_fma); a real vector leaves im alone
 #pragma unroll
   for (int r = 0; r < 4; ++r)
 #pragma unroll
-    for (int c = 0; c < 4; ++c) acc[r][c] = 0.0;
+    for (int c = 0; c < 4; ++c) re[r][c] = 0.0, im[r][c] = 0.0;
   for (uint32_t b0 = it.b_begin; b0 < it.b_end; b0 += CHUNK) {
     __syncthreads();  // sa_i and sa_j are written; the last chunk's panels are read
     if (tid < CHUNK) sb[tid] = spin_rdm_party_state<SECTOR>(bin, nB, kb, mask_b, b0 + tid, tid < it.b_end - b0);
     __syncthreads();
-    double va[LOADS], vb[LOADS];
+    E va[LOADS], vb[LOADS];
 #pragma unroll
     for (int q = 0; q < LOADS; ++q) {
       int row, bj;
@@ -2055,46 +2007,72 @@ __global__ __launch_bounds__(kBlock) void k_spin_rdm(const SpinRdmTable* __restr
     for (int q = 0; q < LOADS; ++q) {
       int row, bj;
       spin_rdm_panel_slot(along_a, TILE, CHUNK, q * kBlock + tid, &row, &bj);
-      panel[bj * PITCH + row] = va[q];
-      if (other != 0) panel[other + bj * PITCH + row] = vb[q];
+      panel[G::panel_column(bj) + row] = spin_stored(va[q]);
+      if (other != 0) panel[other + G::panel_column(bj) + row] = spin_stored(vb[q]);
     }
     __syncthreads();
     for (int bj = group; bj < CHUNK; bj += GROUPS) {
-      double a[4], b[4];
+      E a[4], b[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) a[r] = panel[bj * PITCH + 4 * tx + r], b[r] = panel[other + bj * PITCH + 4 * ty + r];
+      for (int r = 0; r < 4; ++r) {
+        a[r] = spin_loaded(panel[G::panel_column(bj) + G::lane_row(tx, r)]);
+        b[r] = spin_loaded(panel[other + G::panel_column(bj) + G::lane_row(ty, r)]);
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) acc[r][c] = fma(a[r], b[c], acc[r][c]);
+        for (int c = 0; c < 4; ++c) spin_rdm_fma(a[r], b[c], re[r][c], im[r][c]);
     }
   }
-  double* out = partials + bk->part_offset + (int64_t)it.slice * d * d;
+  Stored* out = partials + bk->part_offset + (int64_t)it.slice * d * d;
   if constexpr (GROUPS == 1) {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const int i = i0 + 4 * tx + r, j = j0 + 4 * ty + c;
-        if (i < d && j < d && i >= j) out[i + (int64_t)j * d] = acc[r][c];
+        const int i = i0 + G::lane_row(tx, r), j = j0 + G::lane_row(ty, c);
+        if (i < d && j < d && i >= j) out[i + (int64_t)j * d] = spin_stored(spin_rdm_entry<E>(re[r][c], im[r][c], i == j));
       }
   } else {
+    // The groups' tiles are added through red[], one double per entry and group; of a complex vector part by part, the real
+    // parts, then the imaginary ones.  The one pass of a real vector is written out and does not go through group_sum: the
+    // compiler pairs the stores of the two forms differently.
+    double sr = 0.0, si = 0.0;
+    if constexpr (std::is_same<E, SpinZ>::value) {
+      const auto group_sum = [&](const double(&part)[4][4]) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
+        for (int r = 0; r < 4; ++r)
 #pragma unroll
-      for (int c = 0; c < 4; ++c) red[group * TILE * TILE + (4 * ty + c) * TILE + 4 * tx + r] = acc[r][c];
-    __syncthreads();
-    double sum = 0.0;
-    for (int g = 0; g < GROUPS; ++g) sum += red[g * TILE * TILE + tid];
+          for (int c = 0; c < 4; ++c) red[group * TILE * TILE + G::lane_row(ty, c) * TILE + G::lane_row(tx, r)] = part[r][c];
+        __syncthreads();
+        double sum = 0.0;
+        for (int g = 0; g < GROUPS; ++g) sum += red[g * TILE * TILE + tid];
+        return sum;
+      };
+      sr = group_sum(re);
+      __syncthreads();  // the real parts are read
+      si = group_sum(im);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) red[group * TILE * TILE + G::lane_row(ty, c) * TILE + G::lane_row(tx, r)] = re[r][c];
+      __syncthreads();
+      for (int g = 0; g < GROUPS; ++g) sr += red[g * TILE * TILE + tid];
+    }
     const int i = i0 + tid % TILE, j = j0 + tid / TILE;
-    if (i < d && j < d && i >= j) out[i + (int64_t)j * d] = sum;
+    if (i < d && j < d && i >= j) out[i + (int64_t)j * d] = spin_stored(spin_rdm_entry<E>(sr, si, i == j));
   }
 }
 
 // Second stage of k_spin_rdm, one lane per entry of the packed output: the lane of an entry i >= j adds the block's slices in
-// ascending order with plain adds and writes (i, j) and (j, i) from the same value; the lane of an entry i < j writes nothing.
-__global__ __launch_bounds__(kBlock) void k_spin_rdm_reduce(const SpinRdmTable* __restrict__ tb, const double* __restrict__ partials,
-                                                            double* __restrict__ out) {
+// ascending order with plain adds, part by part, and writes (i, j) and (j, i) from the same value: a real entry twice, a complex
+// one with the imaginary part negated in (j, i), and on the diagonal once with the imaginary part +0.0.  The lane of an entry
+// i < j writes nothing.
+template <class E>
+__global__ __launch_bounds__(kBlock) void k_spin_rdm_reduce(const SpinRdmTable* __restrict__ tb,
+                                                            const typename SpinElement<E>::Stored* __restrict__ partials,
+                                                            typename SpinElement<E>::Stored* __restrict__ out) {
   const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (e >= tb->total) return;
   int n = 0;
@@ -2103,152 +2081,19 @@ __global__ __launch_bounds__(kBlock) void k_spin_rdm_reduce(const SpinRdmTable* 
   const int64_t d = bk->d, local = e - bk->out_offset;
   const int64_t i = local % d, j = local / d;
   if (i < j) return;
-  const double* p = partials + bk->part_offset + i + j * d;
-  double sum = 0.0;
-  for (int s = 0; s < bk->nslices; ++s) sum += p[(int64_t)s * d * d];
-  out[bk->out_offset + i + j * d] = sum;
-  out[bk->out_offset + j + i * d] = sum;
-}
-
-// The same for an interleaved complex vector (eigenex_spin_rdm_z; spin_rdm.hpp: spin_rdm_host_z is the definition):
-// rho_A = M M^H.  The plan, the items, the slices, the party states, the padding rule and the order of the sums are
-// k_spin_rdm's; what differs is the arithmetic and the shape of the panels.  A panel element is one 16-byte load of x behind one
-// walk of the rank tables (spin_rdm_element_z) and one 16-byte LDS store; the chunk is kSpinRdmBigChunkZ / kSpinRdmSmallChunkZ
-// b's (four gathers per lane and panel), the pitch TILE + 1 pairs, and a lane's four rows are t, t + SIDE, t + 2 SIDE, t + 3 SIDE
-// (spin_rdm_lane_row_z), each one 16-byte LDS read.  Per pair of rows and per b four fmas in the definition's order into a 4 x 4
-// register tile of (re, im): 32 fp64 accumulators.  The imaginary part of a diagonal entry is not stored: +0.0 is.
-template <bool SECTOR, int TILE>
-__global__ __launch_bounds__(kBlock) void k_spin_rdm_z(const SpinRdmTable* __restrict__ tb, const SpinRdmItem* __restrict__ items,
-                                                       const SpinSectorView* __restrict__ op, const uint32_t* __restrict__ lo_rank,
-                                                       const uint32_t* __restrict__ hi_base, const double2* __restrict__ x,
-                                                       double2* __restrict__ partials) {
-  constexpr int CHUNK = TILE == kSpinRdmBigTile ? kSpinRdmBigChunkZ : kSpinRdmSmallChunkZ;
-  constexpr int GROUPS = TILE == kSpinRdmBigTile ? 1 : kSpinRdmSmallGroups;
-  constexpr int SIDE = TILE / 4, LOADS = TILE * CHUNK / kBlock;
-  static_assert(SIDE * SIDE * GROUPS == kBlock && TILE * CHUNK % kBlock == 0 && CHUNK <= kBlock && CHUNK % GROUPS == 0, "tile shape");
-  static_assert(GROUPS == 1 || TILE * TILE == kBlock, "the group sums are added by one lane per entry");
-  constexpr int PANEL = CHUNK * (TILE + 1);  // spin_rdm_panel_index_z
-  __shared__ double2 panel[(GROUPS == 1 ? 2 : 1) * PANEL];
-  __shared__ double red[GROUPS > 1 ? GROUPS * TILE * TILE : 1];
-  __shared__ uint32_t sa_i[TILE], sa_j[TILE], sb[CHUNK];
-  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
-  int h = 0;
-  uint32_t lo_mask = 0;
-  if constexpr (SECTOR) {
-    spin_stage_binomials(op, binom);
-    __syncthreads();
-    h = op->h, lo_mask = op->lo_mask;
-  }
-  const SpinRdmItem it = items[blockIdx.x];
-  const SpinRdmBlock* bk = tb->block + it.block;
-  const int d = bk->d, k = bk->k, nA = tb->nA, nB = tb->nB, kb = tb->n_up - k;
-  const uint32_t mask_a = tb->mask_a, mask_b = tb->mask_b, fallback = tb->fallback;
-  const bool along_a = TILE == kSpinRdmBigTile && tb->along_a != 0, diagonal = it.ti == it.tj;
-  const int i0 = it.ti * TILE, j0 = it.tj * TILE;
-  const int tid = threadIdx.x;
-  const SpinBinomials32 bin{binom};
-  const SpinRankTables tab{lo_rank, hi_base};
-  const SpinVectorZ xv{x};
-  if (tid < TILE) {
-    sa_i[tid] = spin_rdm_party_state<SECTOR>(bin, nA, k, mask_a, (uint32_t)(i0 + tid), i0 + tid < d);
-    sa_j[tid] = spin_rdm_party_state<SECTOR>(bin, nA, k, mask_a, (uint32_t)(j0 + tid), j0 + tid < d);
-  }
-  const int group = tid / (SIDE * SIDE), tx = tid % SIDE, ty = tid % (SIDE * SIDE) / SIDE;
-  const int other = diagonal || GROUPS > 1 ? 0 : PANEL;  // where the rows a_j of the pair lie: a diagonal pair has one panel
-  double re[4][4], im[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) re[r][c] = 0.0, im[r][c] = 0.0;
-  for (uint32_t b0 = it.b_begin; b0 < it.b_end; b0 += CHUNK) {
-    __syncthreads();  // sa_i and sa_j are written; the last chunk's panels are read
-    if (tid < CHUNK) sb[tid] = spin_rdm_party_state<SECTOR>(bin, nB, kb, mask_b, b0 + tid, tid < it.b_end - b0);
-    __syncthreads();
-    SpinZ va[LOADS], vb[LOADS];
-#pragma unroll
-    for (int q = 0; q < LOADS; ++q) {
-      int row, bj;
-      spin_rdm_panel_slot(along_a, TILE, CHUNK, q * kBlock + tid, &row, &bj);
-      const bool live_b = (uint32_t)bj < it.b_end - b0;
-      va[q] = spin_rdm_element_z<SECTOR>(tab, xv, h, lo_mask, sa_i[row], sb[bj], live_b && i0 + row < d, fallback);
-      if (other != 0) vb[q] = spin_rdm_element_z<SECTOR>(tab, xv, h, lo_mask, sa_j[row], sb[bj], live_b && j0 + row < d, fallback);
+  const typename SpinElement<E>::Stored* p = partials + bk->part_offset + i + j * d;
+  E sum = E{};
+  for (int s = 0; s < bk->nslices; ++s) sum = spin_sum(sum, spin_loaded(p[(int64_t)s * d * d]));
+  if constexpr (std::is_same<E, SpinZ>::value) {
+    if (i == j) {
+      out[bk->out_offset + i + j * d] = make_double2(sum.re, 0.0);
+    } else {
+      out[bk->out_offset + i + j * d] = make_double2(sum.re, sum.im);
+      out[bk->out_offset + j + i * d] = make_double2(sum.re, -sum.im);
     }
-#pragma unroll
-    for (int q = 0; q < LOADS; ++q) {
-      int row, bj;
-      spin_rdm_panel_slot(along_a, TILE, CHUNK, q * kBlock + tid, &row, &bj);
-      panel[spin_rdm_panel_index_z(TILE, bj, row)] = make_double2(va[q].re, va[q].im);
-      if (other != 0) panel[other + spin_rdm_panel_index_z(TILE, bj, row)] = make_double2(vb[q].re, vb[q].im);
-    }
-    __syncthreads();
-    for (int bj = group; bj < CHUNK; bj += GROUPS) {
-      double2 a[4], b[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        a[r] = panel[spin_rdm_panel_index_z(TILE, bj, spin_rdm_lane_row_z(SIDE, tx, r))];
-        b[r] = panel[other + spin_rdm_panel_index_z(TILE, bj, spin_rdm_lane_row_z(SIDE, ty, r))];
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          re[r][c] = fma(a[r].x, b[c].x, re[r][c]);
-          re[r][c] = fma(a[r].y, b[c].y, re[r][c]);
-          im[r][c] = fma(a[r].y, b[c].x, im[r][c]);
-          im[r][c] = fma(-a[r].x, b[c].y, im[r][c]);
-        }
-    }
-  }
-  double2* out = partials + bk->part_offset + (int64_t)it.slice * d * d;
-  if constexpr (GROUPS == 1) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int i = i0 + spin_rdm_lane_row_z(SIDE, tx, r), j = j0 + spin_rdm_lane_row_z(SIDE, ty, c);
-        if (i < d && j < d && i >= j) out[i + (int64_t)j * d] = make_double2(re[r][c], i == j ? 0.0 : im[r][c]);
-      }
   } else {
-    // the groups' tiles are added part by part through the real kernel's red[]: the real parts, then the imaginary ones
-    const auto group_sum = [&](const double(&part)[4][4]) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) red[group * TILE * TILE + spin_rdm_lane_row_z(SIDE, ty, c) * TILE + spin_rdm_lane_row_z(SIDE, tx, r)] = part[r][c];
-      __syncthreads();
-      double sum = 0.0;
-      for (int g = 0; g < GROUPS; ++g) sum += red[g * TILE * TILE + tid];
-      return sum;
-    };
-    const double sr = group_sum(re);
-    __syncthreads();  // the real parts are read
-    const double si = group_sum(im);
-    const int i = i0 + tid % TILE, j = j0 + tid / TILE;
-    if (i < d && j < d && i >= j) out[i + (int64_t)j * d] = make_double2(sr, i == j ? 0.0 : si);
-  }
-}
-
-// Second stage of k_spin_rdm_z, one lane per entry of the packed output: the lane of an entry i >= j adds the block's slices
-// in ascending order, both parts with plain adds, and writes (i, j) and, with the imaginary part negated, (j, i) from the same two
-// values; a diagonal entry is written once with the imaginary part +0.0.  The lane of an entry i < j writes nothing.
-__global__ __launch_bounds__(kBlock) void k_spin_rdm_reduce_z(const SpinRdmTable* __restrict__ tb, const double2* __restrict__ partials,
-                                                              double2* __restrict__ out) {
-  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (e >= tb->total) return;
-  int n = 0;
-  while (n + 1 < tb->n_blocks && e >= tb->block[n + 1].out_offset) ++n;
-  const SpinRdmBlock* bk = tb->block + n;
-  const int64_t d = bk->d, local = e - bk->out_offset;
-  const int64_t i = local % d, j = local / d;
-  if (i < j) return;
-  const double2* p = partials + bk->part_offset + i + j * d;
-  double sr = 0.0, si = 0.0;
-  for (int s = 0; s < bk->nslices; ++s) sr += p[(int64_t)s * d * d].x, si += p[(int64_t)s * d * d].y;
-  if (i == j) {
-    out[bk->out_offset + i + j * d] = make_double2(sr, 0.0);
-  } else {
-    out[bk->out_offset + i + j * d] = make_double2(sr, si);
-    out[bk->out_offset + j + i * d] = make_double2(sr, -si);
+    out[bk->out_offset + i + j * d] = sum;
+    out[bk->out_offset + j + i * d] = sum;
   }
 }
 
@@ -3184,31 +3029,41 @@ void launch_block_spmv_z(hipStream_t s, const BlockOperatorView& op, const doubl
 void launch_spin_spmv(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
                       const double* scale, double shift, double* y, double* u_out, int64_t n, double* partials, int grid, const Ctrl* ctrl,
                       int pass) {
-  const auto kernel = lo_rank ? k_spin_spmv<true> : k_spin_spmv<false>;
+  const auto kernel = lo_rank ? k_spin_spmv<true, double> : k_spin_spmv<false, double>;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, op, lo_rank, hi_base, x_ext, scale, shift, y, u_out, n, (n + kBlock - 1) / kBlock,
                      partials, pass, ctrl);
-}
-
-void launch_spin_measure(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
-                         const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid) {
-  const auto kernel = lo_rank ? k_spin_measure<true> : k_spin_measure<false>;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, chunk, op, lo_rank, hi_base, x, n, (n + kBlock - 1) / kBlock, partials, pstride);
 }
 
 void launch_spin_spmv_z(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
                         const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n, double* partials,
                         int pstride, int grid, const Ctrl* ctrl, int pass) {
-  const auto kernel = lo_rank ? k_spin_spmv_z<true> : k_spin_spmv_z<false>;
+  const auto kernel = lo_rank ? k_spin_spmv<true, SpinZ, int> : k_spin_spmv<false, SpinZ, int>;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, op, lo_rank, hi_base, reinterpret_cast<const double2*>(x_ext), scale, shift_re,
-                     shift_im, reinterpret_cast<double2*>(y), reinterpret_cast<double2*>(u_out), n, (n + kBlock - 1) / kBlock, partials,
-                     pstride, pass, ctrl);
+                     shift_im, reinterpret_cast<double2*>(y), reinterpret_cast<double2*>(u_out), n, (n + kBlock - 1) / kBlock,
+                     partials, pstride, pass, ctrl);
 }
 
-void launch_spin_measure_z(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
-                           const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid) {
-  const auto kernel = lo_rank ? k_spin_measure_z<true> : k_spin_measure_z<false>;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, chunk, op, lo_rank, hi_base, reinterpret_cast<const double2*>(x), n,
-                     (n + kBlock - 1) / kBlock, partials, pstride);
+// The launchers below take es, the doubles per element of the vector (1: real, 2: interleaved complex), and the vector, the
+// partials and the result as pointers to double whatever the element.
+template <class E>
+static const typename SpinElement<E>::Stored* spin_elements(const double* p) {
+  return reinterpret_cast<const typename SpinElement<E>::Stored*>(p);
+}
+template <class E>
+static typename SpinElement<E>::Stored* spin_elements(double* p) {
+  return reinterpret_cast<typename SpinElement<E>::Stored*>(p);
+}
+
+template <class E>
+static void spin_measure_launch(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
+                                const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid) {
+  const auto kernel = lo_rank ? k_spin_measure<true, E> : k_spin_measure<false, E>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, chunk, op, lo_rank, hi_base, spin_elements<E>(x), n, (n + kBlock - 1) / kBlock,
+                     partials, pstride);
+}
+void launch_spin_measure(hipStream_t s, int es, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
+                         const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid) {
+  (es == 2 ? spin_measure_launch<SpinZ> : spin_measure_launch<double>)(s, chunk, op, lo_rank, hi_base, x, n, partials, pstride, grid);
 }
 
 void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstride, int nblocks, int ndiag, int nflip, double* diag_out,
@@ -3223,30 +3078,27 @@ void launch_spin_site_apply(hipStream_t s, const SpinSiteTable* table, const Spi
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, table, dst_op, src_lo, src_hi, x, y, n, (n + kBlock - 1) / kBlock, partials);
 }
 
-void launch_spin_rdm(hipStream_t s, bool big, const SpinRdmTable* table, const SpinRdmItem* items, int n_items, const SpinSectorView* op,
-                     const uint32_t* lo_rank, const uint32_t* hi_base, const double* x, double* partials) {
+template <class E>
+static void spin_rdm_launch(hipStream_t s, bool big, const SpinRdmTable* table, const SpinRdmItem* items, int n_items,
+                            const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x, double* partials) {
+  const auto kernel = big ? (lo_rank ? k_spin_rdm<true, kSpinRdmBigTile, E> : k_spin_rdm<false, kSpinRdmBigTile, E>)
+                          : (lo_rank ? k_spin_rdm<true, kSpinRdmSmallTile, E> : k_spin_rdm<false, kSpinRdmSmallTile, E>);
+  hipLaunchKernelGGL(kernel, dim3(n_items), dim3(kBlock), 0, s, table, items, op, lo_rank, hi_base, spin_elements<E>(x),
+                     spin_elements<E>(partials));
+}
+void launch_spin_rdm(hipStream_t s, int es, bool big, const SpinRdmTable* table, const SpinRdmItem* items, int n_items,
+                     const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x, double* partials) {
   if (n_items <= 0) return;
-  const auto kernel = big ? (lo_rank ? k_spin_rdm<true, kSpinRdmBigTile> : k_spin_rdm<false, kSpinRdmBigTile>)
-                          : (lo_rank ? k_spin_rdm<true, kSpinRdmSmallTile> : k_spin_rdm<false, kSpinRdmSmallTile>);
-  hipLaunchKernelGGL(kernel, dim3(n_items), dim3(kBlock), 0, s, table, items, op, lo_rank, hi_base, x, partials);
+  (es == 2 ? spin_rdm_launch<SpinZ> : spin_rdm_launch<double>)(s, big, table, items, n_items, op, lo_rank, hi_base, x, partials);
 }
 
-void launch_spin_rdm_reduce(hipStream_t s, const SpinRdmTable* table, int64_t total, const double* partials, double* out) {
-  hipLaunchKernelGGL(k_spin_rdm_reduce, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, table, partials, out);
+template <class E>
+static void spin_rdm_reduce_launch(hipStream_t s, const SpinRdmTable* table, int64_t total, const double* partials, double* out) {
+  hipLaunchKernelGGL(k_spin_rdm_reduce<E>, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, table,
+                     spin_elements<E>(partials), spin_elements<E>(out));
 }
-
-void launch_spin_rdm_z(hipStream_t s, bool big, const SpinRdmTable* table, const SpinRdmItem* items, int n_items, const SpinSectorView* op,
-                       const uint32_t* lo_rank, const uint32_t* hi_base, const double* x, double* partials) {
-  if (n_items <= 0) return;
-  const auto kernel = big ? (lo_rank ? k_spin_rdm_z<true, kSpinRdmBigTile> : k_spin_rdm_z<false, kSpinRdmBigTile>)
-                          : (lo_rank ? k_spin_rdm_z<true, kSpinRdmSmallTile> : k_spin_rdm_z<false, kSpinRdmSmallTile>);
-  hipLaunchKernelGGL(kernel, dim3(n_items), dim3(kBlock), 0, s, table, items, op, lo_rank, hi_base, reinterpret_cast<const double2*>(x),
-                     reinterpret_cast<double2*>(partials));
-}
-
-void launch_spin_rdm_reduce_z(hipStream_t s, const SpinRdmTable* table, int64_t total, const double* partials, double* out) {
-  hipLaunchKernelGGL(k_spin_rdm_reduce_z, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, table,
-                     reinterpret_cast<const double2*>(partials), reinterpret_cast<double2*>(out));
+void launch_spin_rdm_reduce(hipStream_t s, int es, const SpinRdmTable* table, int64_t total, const double* partials, double* out) {
+  (es == 2 ? spin_rdm_reduce_launch<SpinZ> : spin_rdm_reduce_launch<double>)(s, table, total, partials, out);
 }
 
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,

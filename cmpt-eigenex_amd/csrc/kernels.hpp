@@ -356,14 +356,13 @@ void launch_spin_spmv(hipStream_t s, const SpinSectorView* op, const uint32_t* l
 void launch_spin_spmv_z(hipStream_t s, const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x_ext,
                         const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n, double* partials,
                         int pstride, int grid, const Ctrl* ctrl, int pass = 0);
-// launch_spin_measure for an interleaved complex x: the Hermitian sums of spin_measure.hpp, same partials and second stage
-void launch_spin_measure_z(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
-                           const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid);
 // Spin correlations of the vector x over the rows of a matrix-free spin operator (eigenex_spin_measure; spin_measure.hpp has the
 // definition): one chunk of terms per launch (device memory); op, lo_rank and hi_base as for launch_spin_spmv (full space: null
 // tables, op is not read).  x is only read; the grid's partial sums go to partials[sum * pstride + workgroup], sum = 0 (norm2),
 // 1 + t (diag), 1 + kSpinMeasureChunk + t (flip): (2 * kSpinMeasureChunk + 1) * pstride doubles, pstride >= grid.  Always runs.
-void launch_spin_measure(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
+// es is the doubles per element of x, here and below: 1 a real vector, 2 an interleaved complex one (16-byte aligned), of which
+// the sums are the Hermitian ones of spin_measure.hpp, with the same partials and second stage.
+void launch_spin_measure(hipStream_t s, int es, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
                          const uint32_t* hi_base, const double* x, int64_t n, double* partials, int pstride, int grid);
 // its second stage: the partials of nblocks workgroups added in a fixed order, the chunk's ndiag and nflip live sums stored to
 // diag_out[t] and flip_out[t], norm2 to *norm_out unless that is NULL
@@ -380,16 +379,13 @@ void launch_spin_site_apply(hipStream_t s, const SpinSiteTable* table, const Spi
 // and the work table): one workgroup per item, n_items of them, with 64-row tiles (big) or one 16-row tile; table, items, op,
 // lo_rank and hi_base live in device memory (full space: null tables, op is not read).  x is only read; slice s of a block writes
 // the entries i >= j of its tile to partials[block.part_offset + s * d * d + i + j * d].  Always runs.
-void launch_spin_rdm(hipStream_t s, bool big, const SpinRdmTable* table, const SpinRdmItem* items, int n_items, const SpinSectorView* op,
-                     const uint32_t* lo_rank, const uint32_t* hi_base, const double* x, double* partials);
+void launch_spin_rdm(hipStream_t s, int es, bool big, const SpinRdmTable* table, const SpinRdmItem* items, int n_items,
+                     const SpinSectorView* op, const uint32_t* lo_rank, const uint32_t* hi_base, const double* x, double* partials);
 // its second stage: every entry i >= j of every block is the sum of its slices in ascending order, written to (i, j) and (j, i)
 // of out (table->total doubles, `total` on the host)
-void launch_spin_rdm_reduce(hipStream_t s, const SpinRdmTable* table, int64_t total, const double* partials, double* out);
-// The same two stages for an interleaved complex x (eigenex_spin_rdm_z): the same table and items; partials and out hold (re, im)
-// pairs at the same indices, so 2 * part_total and 2 * total doubles, 16-byte aligned like x.
-void launch_spin_rdm_z(hipStream_t s, bool big, const SpinRdmTable* table, const SpinRdmItem* items, int n_items, const SpinSectorView* op,
-                       const uint32_t* lo_rank, const uint32_t* hi_base, const double* x, double* partials);
-void launch_spin_rdm_reduce_z(hipStream_t s, const SpinRdmTable* table, int64_t total, const double* partials, double* out);
+void launch_spin_rdm_reduce(hipStream_t s, int es, const SpinRdmTable* table, int64_t total, const double* partials, double* out);
+// For an interleaved complex x (es = 2; eigenex_spin_rdm_z) the two stages take the same table and items; partials and out hold
+// (re, im) pairs at the same indices, so 2 * part_total and 2 * total doubles, 16-byte aligned like x.
 // host-operator path: u_out = x*scale
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,
                   const Ctrl* ctrl);

@@ -3151,24 +3151,28 @@ int eigenex_spin_geometry(eigenex_csr_t m, int* n_sites, int* n_up) {
   return 0;
 }
 
+// the argument checks of the two host evaluations, then `host`: spin_measure_host or spin_measure_host_z, the definitions
+static int spin_measure_host_call(const std::string& who, decltype(&spin_measure_host) host, int n_sites, int n_up, const double* x, int n_diag,
+                                  const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks, double* diag_out, double* flip_out,
+                                  double* norm2) {
+  const SpinMeasureArgs a{n_sites, n_up, n_diag, diag_masks, n_flip, flip_masks};
+  if (const char* why = spin_measure_error(a)) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  if (!x) return fail(EIGENEX_ERR_ARG, who + ": x is NULL");
+  if ((n_diag > 0 && !diag_out) || (n_flip > 0 && !flip_out)) return fail(EIGENEX_ERR_ARG, who + ": an output list is NULL but its count is not zero");
+  host(a, x, diag_out, flip_out, norm2);
+  return 0;
+}
+
 int eigenex_spin_measure_host(int n_sites, int n_up, const double* x, int n_diag, const uint32_t* diag_masks, int n_flip,
                               const uint32_t* flip_masks, double* diag_out, double* flip_out, double* norm2) {
-  const SpinMeasureArgs a{n_sites, n_up, n_diag, diag_masks, n_flip, flip_masks};
-  if (const char* why = spin_measure_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_measure_host: ") + why);
-  if (!x) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure_host: x is NULL");
-  if ((n_diag > 0 && !diag_out) || (n_flip > 0 && !flip_out)) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure_host: an output list is NULL but its count is not zero");
-  spin_measure_host(a, x, diag_out, flip_out, norm2);
-  return 0;
+  return spin_measure_host_call("eigenex_spin_measure_host", spin_measure_host, n_sites, n_up, x, n_diag, diag_masks, n_flip, flip_masks, diag_out,
+                                flip_out, norm2);
 }
 
 int eigenex_spin_measure_host_z(int n_sites, int n_up, const double* x, int n_diag, const uint32_t* diag_masks, int n_flip,
                                 const uint32_t* flip_masks, double* diag_out, double* flip_out, double* norm2) {
-  const SpinMeasureArgs a{n_sites, n_up, n_diag, diag_masks, n_flip, flip_masks};
-  if (const char* why = spin_measure_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_measure_host_z: ") + why);
-  if (!x) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure_host_z: x is NULL");
-  if ((n_diag > 0 && !diag_out) || (n_flip > 0 && !flip_out)) return fail(EIGENEX_ERR_ARG, "eigenex_spin_measure_host_z: an output list is NULL but its count is not zero");
-  spin_measure_host_z(a, x, diag_out, flip_out, norm2);
-  return 0;
+  return spin_measure_host_call("eigenex_spin_measure_host_z", spin_measure_host_z, n_sites, n_up, x, n_diag, diag_masks, n_flip, flip_masks,
+                                diag_out, flip_out, norm2);
 }
 
 int eigenex_spin_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks,
@@ -3202,7 +3206,7 @@ int eigenex_spin_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint32_
   for (size_t k = 0; k < chunks.size(); ++k) {
     const size_t first = k * kSpinMeasureChunk;  // a list that ends before `first` has no live sum in this chunk
     const size_t dfirst = std::min(first, (size_t)n_diag), ffirst = std::min(first, (size_t)n_flip);
-    (b->es == 2 ? launch_spin_measure_z : launch_spin_measure)(c->stream, d_chunks + k, m->spin.view, m->spin.lo, m->spin.hi, x, s.nloc, d_part, grid, grid);
+    launch_spin_measure(c->stream, b->es, d_chunks + k, m->spin.view, m->spin.lo, m->spin.hi, x, s.nloc, d_part, grid, grid);
     launch_spin_measure_reduce(c->stream, d_part, grid, grid, chunks[k].ndiag, chunks[k].nflip, d_out + 1 + dfirst, d_out + 1 + n_diag + ffirst,
                                k == 0 ? d_out.get() : nullptr);
   }
@@ -3281,34 +3285,50 @@ int eigenex_spin_rdm_layout(int n_sites, int n_up, uint32_t mask_a, int* n_block
   return 0;
 }
 
-int eigenex_spin_rdm_host(int n_sites, int n_up, const double* x, uint32_t mask_a, double* out, int64_t out_len) {
+// "the length" of a real result, "twice the length" of a complex one (es doubles per entry)
+static std::string spin_rdm_bad_length(const std::string& who, int es) {
+  return who + (es == 2 ? ": out_len is not twice the length eigenex_spin_rdm_layout gives" : ": out_len is not the length eigenex_spin_rdm_layout gives");
+}
+
+// the argument checks of the two host evaluations, then `host`: spin_rdm_host or spin_rdm_host_z, the definitions
+static int spin_rdm_host_call(const std::string& who, int es, decltype(&spin_rdm_host) host, int n_sites, int n_up, const double* x,
+                              uint32_t mask_a, double* out, int64_t out_len) {
   const SpinRdmArgs a{n_sites, n_up, mask_a};
-  if (const char* why = spin_rdm_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_rdm_host: ") + why);
-  if (!x || !out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_host: x or out is NULL");
+  if (const char* why = spin_rdm_error(a)) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  if (!x || !out) return fail(EIGENEX_ERR_ARG, who + ": x or out is NULL");
   SpinRdmLayout l;
   spin_rdm_layout(a, l);
-  if (out_len != l.offsets[l.n_blocks]) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_host: out_len is not the length eigenex_spin_rdm_layout gives");
-  spin_rdm_host(a, x, out);
+  if (out_len != es * l.offsets[l.n_blocks]) return fail(EIGENEX_ERR_ARG, spin_rdm_bad_length(who, es));
+  host(a, x, out);
   return 0;
 }
 
-int eigenex_spin_rdm(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out, int64_t out_len) {
-  if (!b) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm: basis is NULL");
+int eigenex_spin_rdm_host(int n_sites, int n_up, const double* x, uint32_t mask_a, double* out, int64_t out_len) {
+  return spin_rdm_host_call("eigenex_spin_rdm_host", 1, spin_rdm_host, n_sites, n_up, x, mask_a, out, out_len);
+}
+
+int eigenex_spin_rdm_host_z(int n_sites, int n_up, const double* x, uint32_t mask_a, double* out, int64_t out_len) {
+  return spin_rdm_host_call("eigenex_spin_rdm_host_z", 2, spin_rdm_host_z, n_sites, n_up, x, mask_a, out, out_len);
+}
+
+// eigenex_spin_rdm (es = 1) and eigenex_spin_rdm_z (es = 2): the state must have es doubles per element.  The plan, the items
+// and the slices are the same for both; a complex state's partial sums and packed result are (re, im) pairs, es times the doubles.
+static int spin_rdm_call(const std::string& who, int es, const char* not_spin, const char* wrong_kind, eigenex_basis_t b, int x_ref,
+                         uint32_t mask_a, double* out, int64_t out_len) {
+  if (!b) return fail(EIGENEX_ERR_ARG, who + ": basis is NULL");
   CHK(enter_settled(b));
   if (!spin_state_shard(b))
-    return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_rdm: the operator of this state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
-                                          : "eigenex_spin_rdm: the state has no device operator (a host callback knows no sites)");
-  if (b->es != 1)
-    return fail(EIGENEX_ERR_STATE, "eigenex_spin_rdm: real states only (a complex spin state, eigenex_spin_upload_z, has no density-matrix kernel here: eigenex_spin_rdm_z)");
+    return fail(EIGENEX_ERR_STATE, who + (b->csr ? not_spin : ": the state has no device operator (a host callback knows no sites)"));
+  if (b->es != es) return fail(EIGENEX_ERR_STATE, who + wrong_kind);
   BasisShard& s = *spin_state_shard(b);
   const SpinShard& m = s.csr->spin;
   const SpinRdmArgs a{m.n_sites, m.n_up, mask_a};
-  if (const char* why = spin_rdm_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_rdm: ") + why);
-  if (!out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm: out is NULL");
+  if (const char* why = spin_rdm_error(a)) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  if (!out) return fail(EIGENEX_ERR_ARG, who + ": out is NULL");
   SpinRdmPlan plan;
   spin_rdm_build_plan(a, s.g_spmv, plan);
   const SpinRdmTable& t = plan.table;
-  if (out_len != t.total) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm: out_len is not the length eigenex_spin_rdm_layout gives");
+  if (out_len != es * t.total) return fail(EIGENEX_ERR_ARG, spin_rdm_bad_length(who, es));
   const double* x = vec_ptr(s, b->cap, b->nq, x_ref);
   if (!x) return fail(EIGENEX_ERR_ARG, "bad vector reference");
   eigenex_context_s* c = b->ctx;
@@ -3323,69 +3343,28 @@ int eigenex_spin_rdm(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out,
   DeviceBuffer<double> d_part, d_out;
   HIPCHK(d_table.alloc(1));
   HIPCHK(d_items.alloc(items.size()));
-  HIPCHK(d_part.alloc((size_t)t.part_total));
-  HIPCHK(d_out.alloc((size_t)t.total));
+  HIPCHK(d_part.alloc(es * (size_t)t.part_total));
+  HIPCHK(d_out.alloc(es * (size_t)t.total));
   HIPCHK(hipMemcpyAsync(d_table, &t, sizeof(SpinRdmTable), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_items, items.data(), sizeof(SpinRdmItem) * items.size(), hipMemcpyHostToDevice, c->stream));
-  launch_spin_rdm(c->stream, true, d_table, d_items, (int)nbig, m.view, m.lo, m.hi, x, d_part);
-  launch_spin_rdm(c->stream, false, d_table, d_items + nbig, (int)nsmall, m.view, m.lo, m.hi, x, d_part);
-  launch_spin_rdm_reduce(c->stream, d_table, t.total, d_part, d_out);
-  HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)t.total, hipMemcpyDeviceToHost, c->stream));
+  launch_spin_rdm(c->stream, es, true, d_table, d_items, (int)nbig, m.view, m.lo, m.hi, x, d_part);
+  launch_spin_rdm(c->stream, es, false, d_table, d_items + nbig, (int)nsmall, m.view, m.lo, m.hi, x, d_part);
+  launch_spin_rdm_reduce(c->stream, es, d_table, t.total, d_part, d_out);
+  HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * es * (size_t)t.total, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the table and the scratch live until here
   return 0;
 }
 
-int eigenex_spin_rdm_host_z(int n_sites, int n_up, const double* x, uint32_t mask_a, double* out, int64_t out_len) {
-  const SpinRdmArgs a{n_sites, n_up, mask_a};
-  if (const char* why = spin_rdm_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_rdm_host_z: ") + why);
-  if (!x || !out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_host_z: x or out is NULL");
-  SpinRdmLayout l;
-  spin_rdm_layout(a, l);
-  if (out_len != 2 * l.offsets[l.n_blocks]) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_host_z: out_len is not twice the length eigenex_spin_rdm_layout gives");
-  spin_rdm_host_z(a, x, out);
-  return 0;
+int eigenex_spin_rdm(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out, int64_t out_len) {
+  return spin_rdm_call("eigenex_spin_rdm", 1, ": the operator of this state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)",
+                       ": real states only (a complex spin state, eigenex_spin_upload_z, has no density-matrix kernel here: eigenex_spin_rdm_z)", b,
+                       x_ref, mask_a, out, out_len);
 }
 
 int eigenex_spin_rdm_z(eigenex_basis_t b, int x_ref, uint32_t mask_a, double* out, int64_t out_len) {
-  if (!b) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_z: basis is NULL");
-  CHK(enter_settled(b));
-  if (!spin_state_shard(b))
-    return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_rdm_z: the operator of this state is not a matrix-free spin operator for complex states (eigenex_spin_upload_z, eigenex_spin_sector_upload_z)"
-                                          : "eigenex_spin_rdm_z: the state has no device operator (a host callback knows no sites)");
-  if (b->es != 2)
-    return fail(EIGENEX_ERR_STATE, "eigenex_spin_rdm_z: complex states only (a real spin state, eigenex_spin_upload, goes through eigenex_spin_rdm)");
-  BasisShard& s = *spin_state_shard(b);
-  const SpinShard& m = s.csr->spin;
-  const SpinRdmArgs a{m.n_sites, m.n_up, mask_a};
-  if (const char* why = spin_rdm_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_rdm_z: ") + why);
-  if (!out) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_z: out is NULL");
-  SpinRdmPlan plan;
-  spin_rdm_build_plan(a, s.g_spmv, plan);  // the real call's plan: the same items and slices
-  const SpinRdmTable& t = plan.table;
-  if (out_len != 2 * t.total) return fail(EIGENEX_ERR_ARG, "eigenex_spin_rdm_z: out_len is not twice the length eigenex_spin_rdm_layout gives");
-  const double* x = vec_ptr(s, b->cap, b->nq, x_ref);
-  if (!x) return fail(EIGENEX_ERR_ARG, "bad vector reference");
-  eigenex_context_s* c = b->ctx;
-  HIPCHK(hipSetDevice(c->device));
-  // scratch of this call alone, as in eigenex_spin_rdm; the partial sums and the packed result are (re, im) pairs
-  const size_t nbig = plan.big.size(), nsmall = plan.small.size();
-  std::vector<SpinRdmItem> items(plan.big);
-  items.insert(items.end(), plan.small.begin(), plan.small.end());
-  DeviceBuffer<SpinRdmTable> d_table;
-  DeviceBuffer<SpinRdmItem> d_items;
-  DeviceBuffer<double> d_part, d_out;
-  HIPCHK(d_table.alloc(1));
-  HIPCHK(d_items.alloc(items.size()));
-  HIPCHK(d_part.alloc(2 * (size_t)t.part_total));
-  HIPCHK(d_out.alloc(2 * (size_t)t.total));
-  HIPCHK(hipMemcpyAsync(d_table, &t, sizeof(SpinRdmTable), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(d_items, items.data(), sizeof(SpinRdmItem) * items.size(), hipMemcpyHostToDevice, c->stream));
-  launch_spin_rdm_z(c->stream, true, d_table, d_items, (int)nbig, m.view, m.lo, m.hi, x, d_part);
-  launch_spin_rdm_z(c->stream, false, d_table, d_items + nbig, (int)nsmall, m.view, m.lo, m.hi, x, d_part);
-  launch_spin_rdm_reduce_z(c->stream, d_table, t.total, d_part, d_out);
-  HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * 2 * (size_t)t.total, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the table and the scratch live until here
-  return 0;
+  return spin_rdm_call("eigenex_spin_rdm_z", 2,
+                       ": the operator of this state is not a matrix-free spin operator for complex states (eigenex_spin_upload_z, eigenex_spin_sector_upload_z)",
+                       ": complex states only (a real spin state, eigenex_spin_upload, goes through eigenex_spin_rdm)", b, x_ref, mask_a, out, out_len);
 }
 
 int eigenex_csr_layout(eigenex_csr_t m, int* layout) {

@@ -1,7 +1,8 @@
 // The reduced density matrix of a real vector over the rows of a spin-1/2 operator (host side, no HIP): the definition, the
-// argument check, the layout of the result, the work table of the kernels (kernels.hip: k_spin_rdm, k_spin_rdm_reduce) and the
+// argument check, the layout of the result, the work table of the kernels (kernels.hip: k_spin_rdm<SECTOR, TILE, E>,
+// k_spin_rdm_reduce<E>, each written once for real and complex vectors) and the
 // host evaluation.  Shared by the library (eigenex_spin_rdm, eigenex_spin_rdm_layout, eigenex_spin_rdm_host) and by the host
-// program tests/cpp/spin_rdm_sanitize.cpp, which runs this file under AddressSanitizer + UBSan.
+// programs tests/cpp/spin_rdm_sanitize.cpp and spin_rdm_z_sanitize.cpp, which run this file under AddressSanitizer + UBSan.
 //
 // The state is a real vector x over the rows of spin_model.hpp (n_up = -1: the full space, row s is state s) or of
 // spin_sector.hpp (row r is the state of rank r among the states with n_up sites up).  The subsystem A is a 32-bit site mask
@@ -17,8 +18,8 @@
 // out[j,i] the same bits.  The sums are raw and unnormalised, like spin_measure: the trace is sum x^2.  The host definition
 // adds the b terms in ascending order, one fma per term.
 //
-// A complex vector (interleaved (re, im) pairs; eigenex_spin_rdm_z, eigenex_spin_rdm_host_z; kernels.hip: k_spin_rdm_z,
-// k_spin_rdm_reduce_z): rho_k = M_k M_k^H, rho[i, j] = sum_b M[i, b] conj(M[j, b]), over the same blocks, layout, limit and
+// A complex vector (interleaved (re, im) pairs; eigenex_spin_rdm_z, eigenex_spin_rdm_host_z; the kernels with E = SpinZ):
+// rho_k = M_k M_k^H, rho[i, j] = sum_b M[i, b] conj(M[j, b]), over the same blocks, layout, limit and
 // argument check.  Output: the blocks packed in ascending k, each a full column-major d_k x d_k matrix of interleaved (re, im)
 // pairs, 2 * offsets[n_blocks] doubles; raw sums, the trace is sum |x|^2.  Two properties are part of the definition and every
 // evaluation keeps them bit for bit: Im rho[i, i] is stored as +0.0 (not the computed chain: with fma the two products of a
@@ -38,7 +39,7 @@ constexpr int kSpinRdmMaxBlocks = kSectorMaxSites + 1;   // k = 0 .. 32
 constexpr int kSpinRdmBigTile = 64, kSpinRdmSmallTile = 16;     // blocks above 16 rows, blocks of at most 16 rows
 constexpr int kSpinRdmBigChunk = 32, kSpinRdmSmallChunk = 128;  // b's staged in LDS at a time, per tile size
 constexpr int kSpinRdmSmallGroups = 16;                  // a 16-tile workgroup splits a chunk's b's over 16 groups of 16 threads
-// The complex kernel (k_spin_rdm_z) stages half as many b's, so that its panels of 16-byte elements take the real kernel's LDS:
+// The complex kernel (k_spin_rdm<SECTOR, TILE, SpinZ>) stages half as many b's, so that its panels of 16-byte elements take the real kernel's LDS:
 //   64-row tile: CHUNK = 16, two panels of 16 x (64 + 1) pairs = 33 280 B; with the staged states and (in a sector) the
 //     binomials 38 080 B per workgroup (real kernel: 38 656 B); four 16-byte gathers per lane and panel
 //   16-row tile: CHUNK = 64, one panel of 64 x (16 + 1) pairs = 17 408 B; the 16 groups' tiles go through red[] of the real
@@ -46,7 +47,7 @@ constexpr int kSpinRdmSmallGroups = 16;                  // a 16-tile workgroup 
 //     leave one workgroup per CU: 54 720 B per workgroup in a sector (real kernel: 56 000 B); four gathers per lane
 // (the byte counts are the compiler's, profiles/spin_entanglement_z.md).  The panels are b-major with a pitch of TILE + 1
 // pairs (16-byte units, so every element is 16-byte aligned), and a lane's four rows are t, t + TILE/4, t + 2 TILE/4,
-// t + 3 TILE/4 (spin_rdm_rows.hpp: spin_rdm_lane_row_z), not four consecutive ones: each is one 16-byte LDS read, and the 16
+// t + 3 TILE/4 (spin_rdm_rows.hpp: SpinRdmGeometry<SpinZ, TILE>::lane_row), not four consecutive ones: each is one 16-byte LDS read, and the 16
 // lanes of a read group then take 16 consecutive pairs, 256 bytes = one row of the 64 banks: no conflict, where the real
 // kernel's four consecutive doubles per lane are a 2-way one.  A gather whose b's run along the lanes stores with a stride of
 // TILE + 1 pairs, 16 bytes past a multiple of the 128 bytes a store covers per cycle: eight consecutive lanes fill the 32 store

@@ -1,7 +1,7 @@
-// The row walk of the matrix-free spin-1/2 kernels (kernels.hip: k_spin_spmv<SECTOR>, k_spin_measure<SECTOR>,
-// k_spin_site_apply<SECTOR>, their complex-state forms k_spin_spmv_z<SECTOR> and k_spin_measure_z<SECTOR>, and through
-// spin_rdm_rows.hpp k_spin_rdm<SECTOR, TILE>), shared by the
-// device code and by the host replays tests/cpp/spin_{model,sector,measure,site,rdm,complex}_sanitize.cpp, which run it under AddressSanitizer +
+// The row walk of the matrix-free spin-1/2 kernels (kernels.hip: k_spin_spmv<SECTOR, E> and k_spin_measure<SECTOR, E>, each
+// written once for real (E = double) and complex (E = SpinZ) vectors, k_spin_site_apply<SECTOR>, and through spin_rdm_rows.hpp
+// k_spin_rdm<SECTOR, TILE, E>), shared by the device code and by the host replays
+// tests/cpp/spin_{model,sector,measure,site,rdm,rdm_z,complex}_sanitize.cpp, which run it under AddressSanitizer +
 // UBSan.  The kernels and the replays call THESE functions, so what a replay proves about them (every load inside its array, the
 // state equal to spin_sector_unrank, the sums equal to the CSR row loop and to spin_measure_host bit for bit) holds for the
 // kernels' rows as compiled.  No device construct in here: plain C++11.  spin_write_rows, spin_sector_unrank, spin_sector_rank
@@ -91,9 +91,28 @@ EIGENEX_HD void spin_flip_targets(const uint32_t* mask, uint32_t s, const Tables
   }
 }
 
+// An element of the vector is a double or, of an interleaved complex vector, a pair (re, im): x(i) of the caller's accessor
+// returns one, which the kernels fill from one 8-byte or one 16-byte load.  The operator is real, so the lane's state, the
+// diagonal and phase 1 above serve both parts of a complex element unchanged and once per row; phases 2 and 3 and the helpers
+// below are written once per element.  Each part of a complex sum is the real walk's sum of that part: the same products, rounded
+// and added in the same order.  E{} is the zero element of either.
+struct SpinZ {
+  double re, im;
+};
+
+// x * c and y + a * x with a real c and a, part by part, every product rounded before it is added
+EIGENEX_HD double spin_scaled(double x, double c) { return x * c; }
+EIGENEX_HD SpinZ spin_scaled(SpinZ x, double c) { return SpinZ{x.re * c, x.im * c}; }
+EIGENEX_HD double spin_add_product(double y, double a, double x) { return add_product_nofma(y, a, x); }
+EIGENEX_HD SpinZ spin_add_product(SpinZ y, double a, SpinZ x) { return SpinZ{add_product_nofma(y.re, a, x.re), add_product_nofma(y.im, a, x.im)}; }
+
+// nrm + |x|^2: one fma, of a complex element the real part's, then the imaginary part's
+EIGENEX_HD double spin_norm_add(double nrm, double x) { return std::fma(x, x, nrm); }
+EIGENEX_HD double spin_norm_add(double nrm, SpinZ x) { return std::fma(x.im, x.im, std::fma(x.re, x.re, nrm)); }
+
 // phase 2
-template <class Vector>
-EIGENEX_HD void spin_gather(const Vector& x, const uint32_t* base, const uint32_t* low, double* xv) {
+template <class Vector, class E>
+EIGENEX_HD void spin_gather(const Vector& x, const uint32_t* base, const uint32_t* low, E* xv) {
   EIGENEX_UNROLL
   for (int t = 0; t < kSpinBatch; ++t) xv[t] = x(base[t] + low[t]);
 }
@@ -105,36 +124,8 @@ EIGENEX_HD double spin_add_flips(double yr, const double* fval, const bool* on, 
     if (on[t]) yr = add_product_nofma(yr, fval[t], xv[t] * scale);
   return yr;
 }
-
-// phase 3 of a measurement (spin_measure.hpp: flip[t]): one fma per term on every row
-EIGENEX_HD void spin_measure_flips(double xs, const bool* on, const double* xv, double* fl) {
-  EIGENEX_UNROLL
-  for (int t = 0; t < kSpinBatch; ++t) fl[t] = std::fma(xs, on[t] ? xv[t] : 0.0, fl[t]);
-}
-
-// a batch of diagonal terms of a measurement (spin_measure.hpp: diag[t]): the sign is the parity of the mask's down spins
-EIGENEX_HD void spin_measure_diagonals(double xs, uint32_t s, const uint32_t* dmask, double* dg) {
-  EIGENEX_UNROLL
-  for (int t = 0; t < kSpinBatch; ++t) dg[t] = std::fma(spin_odd(~s & dmask[t]) ? -xs : xs, xs, dg[t]);
-}
-
-// ---- complex vectors (kernels.hip: k_spin_spmv_z<SECTOR>, k_spin_measure_z<SECTOR>; host replay: spin_complex_sanitize.cpp) ----
-// The operator is the same real one, so the lane's state, the diagonal and phase 1 above serve both parts of a complex vector
-// unchanged and once per row.  Phases 2 and 3 take an element as (re, im): x(i) returns a SpinZ, which the kernels fill from one
-// 16-byte load.  Each part is the real walk's sum of that part: the same products, rounded and added in the same order.
-struct SpinZ {
-  double re, im;
-};
-
-// phase 2
-template <class Vector>
-EIGENEX_HD void spin_gather_z(const Vector& x, const uint32_t* base, const uint32_t* low, SpinZ* xv) {
-  EIGENEX_UNROLL
-  for (int t = 0; t < kSpinBatch; ++t) xv[t] = x(base[t] + low[t]);
-}
-
-// phase 3 of the operator: spin_add_flips on each part
-EIGENEX_HD SpinZ spin_add_flips_z(SpinZ yr, const double* fval, const bool* on, const SpinZ* xv, double scale) {
+// ... of a complex vector: the same on each part
+EIGENEX_HD SpinZ spin_add_flips(SpinZ yr, const double* fval, const bool* on, const SpinZ* xv, double scale) {
   EIGENEX_UNROLL
   for (int t = 0; t < kSpinBatch; ++t)
     if (on[t]) {
@@ -144,9 +135,13 @@ EIGENEX_HD SpinZ spin_add_flips_z(SpinZ yr, const double* fval, const bool* on, 
   return yr;
 }
 
-// phase 3 of a measurement (spin_measure.hpp: flip[t] of a complex vector, Re(conj(x_s) x_{s ^ mask})): the real part's fma, then
-// the imaginary part's, on every row
-EIGENEX_HD void spin_measure_flips_z(SpinZ xs, const bool* on, const SpinZ* xv, double* fl) {
+// phase 3 of a measurement (spin_measure.hpp: flip[t]): one fma per term on every row
+EIGENEX_HD void spin_measure_flips(double xs, const bool* on, const double* xv, double* fl) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) fl[t] = std::fma(xs, on[t] ? xv[t] : 0.0, fl[t]);
+}
+// ... of a complex vector (flip[t] = Re(conj(x_s) x_{s ^ mask})): the real part's fma, then the imaginary part's
+EIGENEX_HD void spin_measure_flips(SpinZ xs, const bool* on, const SpinZ* xv, double* fl) {
   EIGENEX_UNROLL
   for (int t = 0; t < kSpinBatch; ++t) {
     fl[t] = std::fma(xs.re, on[t] ? xv[t].re : 0.0, fl[t]);
@@ -154,8 +149,13 @@ EIGENEX_HD void spin_measure_flips_z(SpinZ xs, const bool* on, const SpinZ* xv, 
   }
 }
 
-// a batch of diagonal terms of a measurement (diag[t] of a complex vector, sign |x_s|^2): real part, then imaginary part
-EIGENEX_HD void spin_measure_diagonals_z(SpinZ xs, uint32_t s, const uint32_t* dmask, double* dg) {
+// a batch of diagonal terms of a measurement (spin_measure.hpp: diag[t]): the sign is the parity of the mask's down spins
+EIGENEX_HD void spin_measure_diagonals(double xs, uint32_t s, const uint32_t* dmask, double* dg) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) dg[t] = std::fma(spin_odd(~s & dmask[t]) ? -xs : xs, xs, dg[t]);
+}
+// ... of a complex vector (diag[t], sign |x_s|^2): real part, then imaginary part
+EIGENEX_HD void spin_measure_diagonals(SpinZ xs, uint32_t s, const uint32_t* dmask, double* dg) {
   EIGENEX_UNROLL
   for (int t = 0; t < kSpinBatch; ++t) {
     const bool neg = spin_odd(~s & dmask[t]);
@@ -208,5 +208,5 @@ EIGENEX_HD double spin_site_add(double yr, const double* coef, const bool* on, c
 
 }  // namespace eigenex
 
-// the index arithmetic of the reduced-density-matrix kernel (k_spin_rdm<SECTOR, TILE>), under the same rules
+// the index arithmetic of the reduced-density-matrix kernel (k_spin_rdm<SECTOR, TILE, E>), under the same rules
 #include "spin_rdm_rows.hpp"

@@ -143,11 +143,13 @@ def step(args):
 
 
 def short(name):
-    """'void eigenex::(anonymous namespace)::k_spin_rdm_z<true, 64>(...)' -> 'k_spin_rdm_z'"""
+    """'void eigenex::(anonymous namespace)::k_spin_rdm<true, 64, eigenex::SpinZ>(...)' -> 'k_spin_rdm<SpinZ>': the kernel and the
+    element of the vector, SpinZ or double"""
     name = name.strip()
     name = name[5:] if name.startswith("void ") else name
     name = name.replace("eigenex::(anonymous namespace)::", "").replace("eigenex::", "")
-    return re.split(r"[<(]", name)[0].strip()
+    head = name.split("(")[0]
+    return re.split(r"[<(]", name)[0].strip() + ("<SpinZ>" if "SpinZ" in head else "<double>")
 
 
 def kernel_stats(args):
@@ -161,25 +163,25 @@ def kernel_stats(args):
         if k.startswith("k_spin_rdm"):
             total[k] = total.get(k, 0.0) + float(r["TotalDurationNs"])
             calls[k] = calls.get(k, 0) + int(r["Calls"])
-    n_calls = calls.get("k_spin_rdm_reduce_z", 0)
-    assert n_calls > 0 and calls.get("k_spin_rdm_reduce", 0) == n_calls, calls
+    n_calls = calls.get("k_spin_rdm_reduce<SpinZ>", 0)
+    assert n_calls > 0 and calls.get("k_spin_rdm_reduce<double>", 0) == n_calls, calls
     rec = dict(kind="kernels", L=L, n_up=n_up, cut=args.cut, calls_each=n_calls,
-               tiles_z_ms=total.get("k_spin_rdm_z", 0.0) / n_calls * 1e-6, reduce_z_ms=total["k_spin_rdm_reduce_z"] / n_calls * 1e-6,
-               tiles_ms=total.get("k_spin_rdm", 0.0) / n_calls * 1e-6, reduce_ms=total["k_spin_rdm_reduce"] / n_calls * 1e-6)
+               tiles_z_ms=total.get("k_spin_rdm<SpinZ>", 0.0) / n_calls * 1e-6, reduce_z_ms=total["k_spin_rdm_reduce<SpinZ>"] / n_calls * 1e-6,
+               tiles_ms=total.get("k_spin_rdm<double>", 0.0) / n_calls * 1e-6, reduce_ms=total["k_spin_rdm_reduce<double>"] / n_calls * 1e-6)
     print(json.dumps(rec), flush=True)
     with open(args.out, "a") as f:
         f.write(json.dumps(rec) + "\n")
 
 
 def resources(path):
-    """[(kernel, SECTOR, TILE, VGPRs, scratch bytes, spilled VGPRs, LDS bytes, waves/SIMD)] of k_spin_rdm and k_spin_rdm_z from the
-    compiler's remarks"""
+    """[(kernel, SECTOR, TILE, VGPRs, scratch bytes, spilled VGPRs, LDS bytes, waves/SIMD)] of k_spin_rdm<SECTOR, TILE, E> for
+    E = double and SpinZ from the compiler's remarks"""
     rows, cur = [], None
     for line in open(path):
         m = re.search(r"Function Name: (\S+)", line)
         if m:
-            t = re.match(r"_ZN7eigenex12_GLOBAL__N_1\d+(k_spin_rdm(?:_z)?)ILb([01])ELi(\d+)EEE", m.group(1))
-            cur = dict(kernel=t.group(1), sector=int(t.group(2)), tile=int(t.group(3))) if t else None
+            t = re.match(r"_ZN7eigenex12_GLOBAL__N_1\d+(k_spin_rdm)ILb([01])ELi(\d+)E(d|NS_5SpinZE)EE", m.group(1))
+            cur = dict(kernel=t.group(1) + ("<double>" if t.group(4) == "d" else "<SpinZ>"), sector=int(t.group(2)), tile=int(t.group(3))) if t else None
             if cur is not None:
                 rows.append(cur)
             continue
@@ -215,7 +217,7 @@ def write_profile(args):
               "run.  Call times: host clock around calls that end in a synchronise (the download of the packed result is part of the call), one warm-up",
               "call of each, then the two in turn, with the profiler off; median (min – max) in ms.  Expectation from the code alone: about 2× the real",
               "kernel where the gather dominates (16 instead of 8 bytes per element), up to 4× on the half cut (four fmas instead of one).", "",
-              "| `(L, n_up)` | cut | blocks, largest | `k_spin_rdm_z` + reduce | `k_spin_rdm` + reduce | kernel ratio | `rdm_z` call | `rdm` call | call ratio | download + numpy | largest difference |",
+              "| `(L, n_up)` | cut | blocks, largest | `k_spin_rdm<SpinZ>` + reduce | `k_spin_rdm<double>` + reduce | kernel ratio | `rdm_z` call | `rdm` call | call ratio | download + numpy | largest difference |",
               "|---|---|---|---|---|---|---|---|---|---|---|"]
     missing_calls, missing_kern, notes = [], [], []
     for key in want:
@@ -246,7 +248,7 @@ def write_profile(args):
     name = lambda keys: ", ".join(f"({L},{k}) {cut}" for (L, k, cut) in keys)  # noqa: E731
     gaps = (f"call times of {name(missing_calls)}; " if missing_calls else "") + (f"kernel times of {name(missing_kern)}; " if missing_kern else "")
     lines += [""] + notes + ["", f"Not measured: {gaps}`(30,15)` and `(32,16)`; a full-space operator; "
-                                  "any hardware counter of `k_spin_rdm_z` (LDS bank conflicts among them: the panel layout is derived from the bank rule, not counted); the spread between processes and machines."]
+                                  "any hardware counter of `k_spin_rdm<SpinZ>` (LDS bank conflicts among them: the panel layout is derived from the bank rule, not counted); the spread between processes and machines."]
     with open(args.write_profile, "w") as f:
         f.write("\n".join(lines) + "\n")
     print("\n".join(lines))

@@ -9,7 +9,7 @@ a synchronise, one warm-up call of each kind first, then the kinds in turn, `--r
 calls of its kind (every call synchronises, so a window is `--batch` times launch + kernel + synchronise) and is reported per
 call.  These are CALL times; the kernels' own times come from a kernel trace of `--kernels-only`, which runs 20 calls of each
 kind and times nothing:
-  apply_z     one application of the complex-state operator (k_spin_spmv_z): eigenex_apply from W into V on a complex state
+  apply_z     one application of the complex-state operator (k_spin_spmv<..., SpinZ>): eigenex_apply from W into V on a complex state
   apply_real  one application of the real operator (k_spin_spmv) on a real state of the same sector; two of them are what
               evolving the real and the imaginary part as separate planes would cost per operator application
   measure_z   a one-chunk eigenex_spin_measure (16 site masks, 16 pair masks) of the complex vector, measure_real of the real one

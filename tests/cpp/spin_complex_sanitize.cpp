@@ -1,13 +1,14 @@
 // The row walk of the complex-state spin kernels under AddressSanitizer + UBSan (device code cannot be sanitised on the GPU pool):
-// csrc/spin_rows.hpp's additions for complex vectors (spin_gather_z, spin_add_flips_z, spin_measure_flips_z,
-// spin_measure_diagonals_z) and csrc/spin_measure.hpp's spin_measure_host_z, compiled into this program, which links nothing else.
+// csrc/spin_rows.hpp's functions on complex elements (SpinZ: spin_gather, spin_add_flips, spin_measure_flips,
+// spin_measure_diagonals and the element helpers) and csrc/spin_measure.hpp's spin_measure_host_z, compiled into this program,
+// which links nothing else.
 // For the sectors (4,2), (11,5), (32,2), (31,2) and the full space of L = 2 and 9 sites, on models with bonds across the split of
 // the rank tables and on the top sites, longitudinal fields and (full space) a transverse field:
-//   - the row sum of k_spin_spmv_z<SECTOR> -- the kernel's own functions on its tables, every load checked against its array, an
+//   - the row sum of k_spin_spmv<SECTOR, SpinZ> -- the kernel's own functions on its tables, every load checked against its array, an
 //     element read as the (re, im) pair at 2 i and 2 i + 1 of an exactly-sized interleaved vector -- equals, part by part and bit
-//     for bit, the real walk (checked_operator_row, the row sum of k_spin_spmv) on the vector of real parts and on the vector of
+//     for bit, the real walk (checked_operator_row, the row sum of k_spin_spmv<SECTOR, double>) on the vector of real parts and on the vector of
 //     imaginary parts;
-//   - the row loop of k_spin_measure_z over ascending rows equals spin_measure_host_z bit for bit, and with every imaginary part
+//   - the row loop of k_spin_measure<SECTOR, SpinZ> over ascending rows equals spin_measure_host_z bit for bit, and with every imaginary part
 //     +0 both equal spin_measure_host.
 // Built and run by tests/test_spin_complex_host.py; prints SPIN COMPLEX OK and exits 0 when every check holds.
 #include <cmath>
@@ -60,30 +61,6 @@ static Model model_of(int L, bool sector, std::mt19937& rng) {
   return m;
 }
 
-// The row sum of k_spin_spmv_z<SECTOR> (kernels.hip) on row r, whose state is s, before the shift: the kernel's own functions,
-// every load checked
-template <bool SECTOR>
-static SpinZ checked_operator_row_z(const eigenex::SpinOperatorView& m, const eigenex::SpinSectorTables& t, int h, std::uint32_t lo_mask,
-                                    const std::vector<double>& xz, std::int64_t r, std::uint32_t s, double scale) {
-  const CheckedTables tab{&t};
-  const CheckedVectorZ xs{&xz};
-  const double d = eigenex::spin_row_diagonal(m.dmask, m.dval, m.ndiag, s);
-  SpinZ xr = xs(static_cast<std::uint32_t>(r));
-  xr.re *= scale, xr.im *= scale;
-  SpinZ acc = {eigenex::add_product_nofma(0.0, d, xr.re), eigenex::add_product_nofma(0.0, d, xr.im)};
-  for (int t0 = 0; t0 < m.nflip; t0 += eigenex::kSpinBatch) {
-    EXPECT(t0 + eigenex::kSpinBatch <= eigenex::kSpinMaxTerms);
-    bool on[eigenex::kSpinBatch];
-    std::uint32_t base[eigenex::kSpinBatch], low[eigenex::kSpinBatch];
-    SpinZ xv[eigenex::kSpinBatch];
-    eigenex::spin_flip_targets<SECTOR>(m.fmask + t0, s, tab, h, lo_mask, on, base, low);
-    expect_targets(m.fmask + t0, on, base, low, r);
-    eigenex::spin_gather_z(xs, base, low, xv);
-    acc = eigenex::spin_add_flips_z(acc, m.fval + t0, on, xv, scale);
-  }
-  return acc;
-}
-
 static void check_operator(int L, int n_up, std::mt19937& rng) {
   const bool sector = n_up != -1;
   const Model mod = model_of(L, sector, rng);
@@ -116,11 +93,11 @@ static void check_operator(int L, int n_up, std::mt19937& rng) {
       SpinZ z;
       double wr, wi;
       if (sector) {
-        z = checked_operator_row_z<true>(v->model, t, v->h, v->lo_mask, xz, r, s, scale);
+        z = checked_operator_row_of<true, SpinZ>(v->model, t, v->h, v->lo_mask, CheckedVectorZ{&xz}, r, s, scale);
         wr = checked_operator_row<true>(v->model, t, v->h, v->lo_mask, re, r, s, scale);
         wi = checked_operator_row<true>(v->model, t, v->h, v->lo_mask, im, r, s, scale);
       } else {
-        z = checked_operator_row_z<false>(v->model, t, 0, 0u, xz, r, s, scale);
+        z = checked_operator_row_of<false, SpinZ>(v->model, t, 0, 0u, CheckedVectorZ{&xz}, r, s, scale);
         wr = checked_operator_row<false>(v->model, t, 0, 0u, re, r, s, scale);
         wi = checked_operator_row<false>(v->model, t, 0, 0u, im, r, s, scale);
       }
@@ -128,7 +105,7 @@ static void check_operator(int L, int n_up, std::mt19937& rng) {
     }
 }
 
-// k_spin_measure_z (kernels.hip) over ascending rows, by the kernel's own functions: one chunk per pass, every load checked
+// k_spin_measure<SECTOR, SpinZ> (kernels.hip) over ascending rows, by the kernel's own functions: one chunk per pass, every load checked
 static void replay_z(const SpinMeasureArgs& a, const std::vector<double>& xz, std::vector<double>& diag, std::vector<double>& flip, double* norm2) {
   const int C = eigenex::kSpinMeasureChunk, B = eigenex::kSpinBatch;
   const bool sector = a.n_up != -1;
@@ -154,10 +131,9 @@ static void replay_z(const SpinMeasureArgs& a, const std::vector<double>& xz, st
       std::uint32_t s = static_cast<std::uint32_t>(r);
       if (sector) s = eigenex::spin_unrank_row(binom, v->model.n_sites, v->n_up, s).s;
       const SpinZ xs = xs_at(static_cast<std::uint32_t>(r));
-      nrm = std::fma(xs.re, xs.re, nrm);
-      nrm = std::fma(xs.im, xs.im, nrm);
+      nrm = eigenex::spin_norm_add(nrm, xs);
       for (int t0 = 0; t0 < C; t0 += B)
-        if (t0 < ch.ndiag) eigenex::spin_measure_diagonals_z(xs, s, ch.dmask + t0, dg + t0);
+        if (t0 < ch.ndiag) eigenex::spin_measure_diagonals(xs, s, ch.dmask + t0, dg + t0);
       for (int t0 = 0; t0 < C; t0 += B)
         if (t0 < ch.nflip) {
           bool on[eigenex::kSpinBatch];
@@ -168,8 +144,8 @@ static void replay_z(const SpinMeasureArgs& a, const std::vector<double>& xz, st
           else
             eigenex::spin_flip_targets<false>(ch.fmask + t0, s, tab, 0, 0u, on, base, low);
           expect_targets(ch.fmask + t0, on, base, low, r);
-          eigenex::spin_gather_z(xs_at, base, low, xv);
-          eigenex::spin_measure_flips_z(xs, on, xv, fl + t0);
+          eigenex::spin_gather(xs_at, base, low, xv);
+          eigenex::spin_measure_flips(xs, on, xv, fl + t0);
         }
     }
     for (int i = 0; i < ch.ndiag; ++i) diag.at(k * C + static_cast<std::size_t>(i)) = dg[i];

@@ -2,7 +2,7 @@
 // csrc/spin_measure.hpp -- the argument check, the chunk table and the host evaluation -- compiled into this program, which
 // links nothing else.  For the full space (L = 3, 6, 9) and the sectors (4,2), (6,0), (6,6), (11,5), (31,2), (32,2), (32,31), with
 // every site, every pair, a four-site string, the all-sites mask and a duplicate (and every one-bit flip in the full space):
-// the outputs go into exactly-sized arrays, and the row loop of k_spin_measure runs on its chunk table -- the kernel's own
+// the outputs go into exactly-sized arrays, and the row loop of k_spin_measure<SECTOR, double> runs on its chunk table -- the kernel's own
 // functions (csrc/spin_rows.hpp), every load checked against its array: the lane's state from the binomials, the batches, the
 // gather through hi_base and lo_rank, the own element where the entry is absent.  Taken over ascending rows it adds the same fma
 // chain as the host evaluation (a lane without the entry adds x_s * 0), so the two are compared bit for bit.
@@ -78,7 +78,7 @@ static void replay(const SpinMeasureArgs& a, const std::vector<double>& x, std::
         s = u.s;
       }
       const double xs = xs_at(static_cast<std::uint32_t>(r));
-      nrm = std::fma(xs, xs, nrm);
+      nrm = eigenex::spin_norm_add(nrm, xs);
       for (int t0 = 0; t0 < C; t0 += B)
         if (t0 < ch.ndiag) eigenex::spin_measure_diagonals(xs, s, ch.dmask + t0, dg + t0);
       for (int t0 = 0; t0 < C; t0 += B)

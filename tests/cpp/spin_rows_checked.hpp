@@ -51,25 +51,32 @@ static inline void expect_targets(const std::uint32_t* mask, const bool* on, con
   }
 }
 
-// The row sum of k_spin_spmv<SECTOR> (kernels.hip) on row r, whose state is s, from the kernel's tables by the kernel's own
-// functions, every load checked.  The full space passes empty tables, h = 0 and lo_mask = 0.
-template <bool SECTOR>
-static double checked_operator_row(const eigenex::SpinOperatorView& m, const eigenex::SpinSectorTables& t, int h, std::uint32_t lo_mask,
-                                   const std::vector<double>& x, std::int64_t r, std::uint32_t s, double scale) {
+// The row sum of k_spin_spmv<SECTOR, E> (kernels.hip) on row r, whose state is s, before the shift, from the kernel's tables by
+// the kernel's own functions, every load checked; xs(i) is element i of the vector, a double or a SpinZ.  The full space passes
+// empty tables, h = 0 and lo_mask = 0.
+template <bool SECTOR, class E, class Vector>
+static E checked_operator_row_of(const eigenex::SpinOperatorView& m, const eigenex::SpinSectorTables& t, int h, std::uint32_t lo_mask, const Vector& xs,
+                                 std::int64_t r, std::uint32_t s, double scale) {
   const CheckedTables tab{&t};
-  const CheckedVector xs{&x};
   const double d = eigenex::spin_row_diagonal(m.dmask, m.dval, m.ndiag, s);
-  const double xr = xs(static_cast<std::uint32_t>(r)) * scale;
-  double yr = eigenex::add_product_nofma(0.0, d, xr);
+  const E xr = eigenex::spin_scaled(xs(static_cast<std::uint32_t>(r)), scale);
+  E yr = eigenex::spin_add_product(E{}, d, xr);
   for (int t0 = 0; t0 < m.nflip; t0 += eigenex::kSpinBatch) {
     EXPECT(t0 + eigenex::kSpinBatch <= eigenex::kSpinMaxTerms);
     bool on[eigenex::kSpinBatch];
     std::uint32_t base[eigenex::kSpinBatch], low[eigenex::kSpinBatch];
-    double xv[eigenex::kSpinBatch];
+    E xv[eigenex::kSpinBatch];
     eigenex::spin_flip_targets<SECTOR>(m.fmask + t0, s, tab, h, lo_mask, on, base, low);
     expect_targets(m.fmask + t0, on, base, low, r);
     eigenex::spin_gather(xs, base, low, xv);
     yr = eigenex::spin_add_flips(yr, m.fval + t0, on, xv, scale);
   }
   return yr;
+}
+
+// ... of a real vector
+template <bool SECTOR>
+static double checked_operator_row(const eigenex::SpinOperatorView& m, const eigenex::SpinSectorTables& t, int h, std::uint32_t lo_mask,
+                                   const std::vector<double>& x, std::int64_t r, std::uint32_t s, double scale) {
+  return checked_operator_row_of<SECTOR, double>(m, t, h, lo_mask, CheckedVector{&x}, r, s, scale);
 }

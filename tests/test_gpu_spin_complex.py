@@ -1,5 +1,5 @@
 """The matrix-free spin-1/2 operators for complex states (eigenex_spin_upload_z, eigenex_spin_sector_upload_z; kernels.hip:
-k_spin_spmv_z, k_spin_measure_z) on the device.
+k_spin_spmv<..., SpinZ>, k_spin_measure<..., SpinZ>) on the device.
 
 An application to x = a + ib is held against two references: the existing real kernel applied to a and to b (np.array_equal:
 each part is the real kernel's sum, only the sign of a zero may differ and only with a shift), and the complex plain-CSR upload

@@ -1,5 +1,5 @@
-"""The reduced density matrix of a complex state on the device (eigenex_spin_rdm_z, kernels.hip: k_spin_rdm_z<SECTOR, TILE> and
-k_spin_rdm_reduce_z) against the long double restatement of tests/spin_rdm_z_reference.py, within 2 n_b eps times the sums of
+"""The reduced density matrix of a complex state on the device (eigenex_spin_rdm_z, kernels.hip: k_spin_rdm<SECTOR, TILE, SpinZ> and
+k_spin_rdm_reduce<SpinZ>) against the long double restatement of tests/spin_rdm_z_reference.py, within 2 n_b eps times the sums of
 magnitudes -- the rounding of a 2 n_b-term sum in any grouping, so it holds for every launch grid, slice count and tile size.  The
 shapes are those of tests/test_gpu_spin_rdm.py, for its reasons: the complex kernel takes the same plan.  On every shape: the
 bound, the diagonal's imaginary part +0.0, (j, i) the conjugate of (i, j) bit for bit, two calls bitwise equal, the vector

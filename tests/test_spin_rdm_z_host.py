@@ -2,7 +2,7 @@
 tests/spin_rdm_z_reference.py within the rounding bound of a 2 n_b-term sum, on every shape of tests/test_gpu_spin_rdm.py; the
 two properties of the definition (the diagonal's imaginary part is +0.0, (j, i) is the conjugate of (i, j) bit for bit); the real
 case against eigenex_spin_rdm_host; a global phase; the refusals; small_eigen::hermitian through a stand-alone C++ program; and
-the host code together with a replay of k_spin_rdm_z's work table, panels and padding under AddressSanitizer + UBSan in a
+the host code together with a replay of k_spin_rdm<..., SpinZ>'s work table, panels and padding under AddressSanitizer + UBSan in a
 stand-alone program.  No GPU."""
 import ctypes as C
 import json
@@ -155,7 +155,7 @@ def test_small_eigen_hermitian(tmp_path):
 
 def test_rdm_z_host_code_under_sanitizers(tmp_path):
     """csrc/spin_rdm.hpp (spin_rdm_host_z and the work table) compiled into a stand-alone program with AddressSanitizer + UBSan:
-    outputs into exactly-sized arrays, and the work items of k_spin_rdm_z and k_spin_rdm_reduce_z replayed over the shapes of the
+    outputs into exactly-sized arrays, and the work items of k_spin_rdm<..., SpinZ> and k_spin_rdm_reduce<SpinZ> replayed over the shapes of the
     GPU tests on three launch grids -- the kernel's own index functions (csrc/spin_rdm_rows.hpp, compiled into the program) with
     every access bounds-checked -- equal to the host evaluation within twice the bound."""
     if shutil.which("g++") is None:
