@@ -115,6 +115,8 @@ SIGNATURES = {
     "eigenex_spin_geometry": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "eigenex_spin_site_apply": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _dp, _dp]),
     "eigenex_spin_site_apply_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "eigenex_spin_site_apply_z": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "eigenex_spin_site_apply_host_z": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "eigenex_spin_rdm_layout": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int), _lp, _lp]),
     "eigenex_spin_rdm": (C.c_int, [_vp, C.c_int, C.c_uint32, _dp, C.c_int64]),
     "eigenex_spin_rdm_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_uint32, _dp, C.c_int64]),
@@ -433,6 +435,27 @@ def spin_site_apply_host(n_sites: int, n_up, kind: int, coef, x):
         rows = spin_sector_dim(n_sites, up) if 2 <= int(n_sites) <= 32 and 0 <= up <= int(n_sites) else 0
     y, norm2 = np.zeros(rows), C.c_double()
     _chk(lib().eigenex_spin_site_apply_host(int(n_sites), -1 if n_up is None else int(n_up), int(kind), _d(coef), _d(x), _d(y), C.byref(norm2)))
+    return y, norm2.value
+
+
+def spin_site_apply_host_z(n_sites: int, n_up, kind: int, coef, x, imaginary="auto"):
+    """eigenex_spin_site_apply_host_z: (y, norm2) of y = O x for a complex vector x and real or complex coefficients, in host code
+    (no GPU); geometry as for spin_site_apply_host.  imaginary: "auto" hands the imaginary parts over when coef is a complex
+    array and NULL otherwise, True always hands them over (zeros for a real coef), False never."""
+    x = np.ascontiguousarray(x, np.complex128)
+    coef = np.asarray(coef)
+    if coef.size < int(n_sites):  # the library reads n_sites entries
+        raise EigenexError("spin_site_apply_host_z: coef has fewer entries than n_sites")
+    with_im = np.iscomplexobj(coef) if imaginary == "auto" else bool(imaginary)
+    cr, ci = np.ascontiguousarray(coef.real, np.float64), np.ascontiguousarray(coef.imag, np.float64)
+    if n_up is None:
+        rows = 1 << max(int(n_sites), 0) if int(n_sites) <= 30 else 0
+    else:
+        up = int(n_up) + (1 if kind == SPIN_SITE_PLUS else -1 if kind == SPIN_SITE_MINUS else 0)
+        rows = spin_sector_dim(n_sites, up) if 2 <= int(n_sites) <= 32 and 0 <= up <= int(n_sites) else 0
+    y, norm2 = np.zeros(rows, np.complex128), C.c_double()
+    _chk(lib().eigenex_spin_site_apply_host_z(int(n_sites), -1 if n_up is None else int(n_up), int(kind), _d(cr), _d(ci) if with_im else None,
+                                              _d(x.view(np.float64)), _d(y.view(np.float64)), C.byref(norm2)))
     return y, norm2.value
 
 
@@ -885,6 +908,18 @@ class Basis:
         buf[:coef.size] = coef
         norm2 = C.c_double()
         _chk(lib().eigenex_spin_site_apply(self.h, x_ref, dst.h, y_ref, int(kind), _d(buf), C.byref(norm2)))
+        return norm2.value
+
+    def spin_site_apply_z(self, x_ref, dst, y_ref, kind, coef, imaginary="auto"):
+        """eigenex_spin_site_apply_z: spin_site_apply for two complex spin states, with real or complex coefficients; returns
+        norm2 = |y|^2.  imaginary: "auto" hands the imaginary parts over when coef is a complex array and NULL otherwise, True
+        always hands them over (zeros for a real coef), False never."""
+        coef = np.asarray(coef).reshape(-1)
+        with_im = np.iscomplexobj(coef) if imaginary == "auto" else bool(imaginary)
+        cr, ci = np.zeros(max(32, coef.size)), np.zeros(max(32, coef.size))  # the library reads n_sites <= 32 entries
+        cr[:coef.size], ci[:coef.size] = coef.real, coef.imag
+        norm2 = C.c_double()
+        _chk(lib().eigenex_spin_site_apply_z(self.h, x_ref, dst.h, y_ref, int(kind), _d(cr), _d(ci) if with_im else None, C.byref(norm2)))
         return norm2.value
 
     def set_filter(self, mu, center=0.0, halfwidth=1.0, degree=None):

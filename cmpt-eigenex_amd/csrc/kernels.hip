@@ -1872,12 +1872,15 @@ __global__ __launch_bounds__(kBlock) void k_spin_measure_reduce(const double* __
 // own element, so y may be x there; for the flips the caller keeps them apart.  norm2 = sum y_r^2 leaves through block_sum
 // into partials[workgroup]; k_spin_measure_reduce adds those in k_reduce_fin's order.  No atomics.  ctrl->stopped is not
 // consulted: this is not a Krylov step.
+// Of an interleaved complex vector (E = SpinZ) the coefficients are complex and the table's real_coef says whether any has an
+// imaginary part; without one, each part of y is the real kernel's y of that part of x.  x is gathered as 16-byte loads, y is one
+// 16-byte store, norm2 = sum |y_r|^2; the state, the targets and the rank-table gathers are taken once per row for both parts.
 // ---------------------------------------------------------------------------
-template <bool SECTOR>
+template <bool SECTOR, class E>
 __global__ __launch_bounds__(kBlock) void k_spin_site_apply(const SpinSiteTable* __restrict__ tb, const SpinSectorView* __restrict__ dst_op,
                                                             const uint32_t* __restrict__ src_lo, const uint32_t* __restrict__ src_hi,
-                                                            const double* x, double* y, int64_t n, int64_t ntiles,
-                                                            double* __restrict__ partials) {
+                                                            const typename SpinElement<E>::Stored* x, typename SpinElement<E>::Stored* y,
+                                                            int64_t n, int64_t ntiles, double* __restrict__ partials) {
   __shared__ double lds4[4];
   __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
   int n_up = 0, h = 0;
@@ -1889,28 +1892,31 @@ __global__ __launch_bounds__(kBlock) void k_spin_site_apply(const SpinSiteTable*
   }
   const int kind = tb->kind, n_sites = tb->n_sites;
   const uint32_t site_mask = tb->site_mask, fallback = tb->fallback;
+  bool real_coef = true;  // read once, here: the branches on it are uniform; a real vector has no imaginary coefficients
+  if constexpr (std::is_same<E, SpinZ>::value) real_coef = tb->real_coef != 0;
   const SpinRankTables tab{src_lo, src_hi};
   double nrm = 0.0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t r = tile * kBlock + threadIdx.x;
     if (r < n) {
       const uint32_t s = SECTOR ? spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s : (uint32_t)r;
-      double yr = 0.0;
+      E yr = E{};
       if (kind == kSpinSiteZ) {
-        yr = spin_site_weight(tb->half, n_sites, s) * x[r];
+        const E w = spin_site_weights(SpinSiteCoefficients{tb->half, tb->half_im, real_coef}, n_sites, s, E{});
+        yr = spin_site_product(w, real_coef, spin_loaded(x[r]));
       } else {
         const uint32_t has = kind == kSpinSitePlus ? s : ~s & site_mask;
         for (int i0 = 0; i0 < n_sites; i0 += kSpinBatch) {
           bool on[kSpinBatch];
           uint32_t base[kSpinBatch], low[kSpinBatch];
-          double xv[kSpinBatch];
+          E xv[kSpinBatch];
           spin_site_targets<SECTOR>(i0, s, has, fallback, tab, h, lo_mask, on, base, low);
-          spin_gather(SpinVector{x}, base, low, xv);
-          yr = spin_site_add(yr, tb->coef + i0, on, xv);
+          spin_gather(typename SpinElement<E>::Vector{x}, base, low, xv);
+          yr = spin_site_add(yr, SpinSiteCoefficients{tb->coef + i0, tb->coef_im + i0, real_coef}, on, xv);
         }
       }
-      y[r] = yr;
-      nrm = fma(yr, yr, nrm);
+      y[r] = spin_stored(yr);
+      nrm = spin_norm_add(nrm, yr);
     }
   }
   nrm = block_sum(nrm, lds4);
@@ -3072,10 +3078,16 @@ void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstri
                      diag_out, flip_out, norm_out);
 }
 
-void launch_spin_site_apply(hipStream_t s, const SpinSiteTable* table, const SpinSectorView* dst_op, const uint32_t* src_lo,
+template <class E>
+static void spin_site_apply_launch(hipStream_t s, const SpinSiteTable* table, const SpinSectorView* dst_op, const uint32_t* src_lo,
+                                   const uint32_t* src_hi, const double* x, double* y, int64_t n, double* partials, int grid) {
+  const auto kernel = src_lo ? k_spin_site_apply<true, E> : k_spin_site_apply<false, E>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, table, dst_op, src_lo, src_hi, spin_elements<E>(x), spin_elements<E>(y), n,
+                     (n + kBlock - 1) / kBlock, partials);
+}
+void launch_spin_site_apply(hipStream_t s, int es, const SpinSiteTable* table, const SpinSectorView* dst_op, const uint32_t* src_lo,
                             const uint32_t* src_hi, const double* x, double* y, int64_t n, double* partials, int grid) {
-  const auto kernel = src_lo ? k_spin_site_apply<true> : k_spin_site_apply<false>;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, table, dst_op, src_lo, src_hi, x, y, n, (n + kBlock - 1) / kBlock, partials);
+  (es == 2 ? spin_site_apply_launch<SpinZ> : spin_site_apply_launch<double>)(s, table, dst_op, src_lo, src_hi, x, y, n, partials, grid);
 }
 
 template <class E>

@@ -372,8 +372,9 @@ void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstri
 // launch.  table, dst_op, src_lo and src_hi live in device memory.  y has n rows, those of the DESTINATION operator, whose view
 // dst_op is; src_lo and src_hi are the rank tables of the SOURCE operator, on whose rows x lives (full space: null tables, dst_op
 // is not read).  y may be x for Z only.  The grid's partial sums of y_r^2 go to partials[workgroup], `grid` doubles; their second
-// stage is launch_spin_measure_reduce(s, partials, grid, grid, 0, 0, nullptr, nullptr, norm_out).  Always runs.
-void launch_spin_site_apply(hipStream_t s, const SpinSiteTable* table, const SpinSectorView* dst_op, const uint32_t* src_lo,
+// stage is launch_spin_measure_reduce(s, partials, grid, grid, 0, 0, nullptr, nullptr, norm_out).  Always runs.  es = 2: x and y
+// are interleaved complex vectors, the table's complex coefficients apply and the sums are those of |y_r|^2.
+void launch_spin_site_apply(hipStream_t s, int es, const SpinSiteTable* table, const SpinSectorView* dst_op, const uint32_t* src_lo,
                             const uint32_t* src_hi, const double* x, double* y, int64_t n, double* partials, int grid);
 // The reduced density matrix of x over the rows of a matrix-free spin operator (eigenex_spin_rdm; spin_rdm.hpp has the definition
 // and the work table): one workgroup per item, n_items of them, with 64-row tiles (big) or one 16-row tile; table, items, op,

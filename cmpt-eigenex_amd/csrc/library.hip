@@ -3232,26 +3232,38 @@ static BasisShard* spin_state_shard(eigenex_basis_t b) {
   return b->csr && b->sh.size() == 1 && b->sh[0].csr && b->sh[0].csr->spin.on() ? &b->sh[0] : nullptr;
 }
 
-int eigenex_spin_site_apply(eigenex_basis_t src, int x_ref, eigenex_basis_t dst, int y_ref, int kind, const double* coef, double* norm2) {
-  if (!src || !dst) return fail(EIGENEX_ERR_ARG, "eigenex_spin_site_apply: a state is NULL");
+int eigenex_spin_site_apply_host_z(int n_sites, int n_up_src, int kind, const double* coef_re, const double* coef_im, const double* x, double* y,
+                                   double* norm2) {
+  const SpinSiteArgs a{n_sites, n_up_src, kind, coef_re, n_sites, spin_site_dst_up(n_up_src, kind), coef_im};
+  if (const char* why = spin_site_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_site_apply_host_z: ") + why);
+  if (!x || !y) return fail(EIGENEX_ERR_ARG, "eigenex_spin_site_apply_host_z: x or y is NULL");
+  if (x == y && kind != kSpinSiteZ) return fail(EIGENEX_ERR_ARG, "eigenex_spin_site_apply_host_z: y may be x for EIGENEX_SPIN_SITE_Z only (a flip reads what it would write)");
+  spin_site_apply_host_z(a, x, y, norm2);
+  return 0;
+}
+
+// eigenex_spin_site_apply (es = 1, coef_im NULL) and eigenex_spin_site_apply_z (es = 2) under the name `who`; `wrong_scalar` is what
+// a state of the other scalar type is told
+static int spin_site_apply_call(const std::string& who, int es, const char* wrong_scalar, eigenex_basis_t src, int x_ref, eigenex_basis_t dst, int y_ref,
+                                int kind, const double* coef, const double* coef_im, double* norm2) {
+  if (!src || !dst) return fail(EIGENEX_ERR_ARG, who + ": a state is NULL");
   CHK(enter_settled(src));
   CHK(enter_settled(dst));
   for (eigenex_basis_t b : {src, dst})
     if (!spin_state_shard(b))
-      return fail(EIGENEX_ERR_STATE, b->csr ? "eigenex_spin_site_apply: the operator of a state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
-                                            : "eigenex_spin_site_apply: a state has no device operator (a host callback knows no sites)");
-  if (src->es != 1 || dst->es != 1)
-    return fail(EIGENEX_ERR_STATE, "eigenex_spin_site_apply: real states only (a complex spin state, eigenex_spin_upload_z, has no site-operator kernel)");
-  if (src->ctx != dst->ctx) return fail(EIGENEX_ERR_STATE, "eigenex_spin_site_apply: the two states live on different contexts");
+      return fail(EIGENEX_ERR_STATE, who + (b->csr ? ": the operator of a state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
+                                                   : ": a state has no device operator (a host callback knows no sites)"));
+  if (src->es != es || dst->es != es) return fail(EIGENEX_ERR_STATE, who + wrong_scalar);
+  if (src->ctx != dst->ctx) return fail(EIGENEX_ERR_STATE, who + ": the two states live on different contexts");
   BasisShard &ss = *spin_state_shard(src), &sd = *spin_state_shard(dst);
   const SpinShard &ms = ss.csr->spin, &md = sd.csr->spin;
-  const SpinSiteArgs a{ms.n_sites, ms.n_up, kind, coef, md.n_sites, md.n_up};
-  if (const char* why = spin_site_error(a)) return fail(EIGENEX_ERR_ARG, std::string("eigenex_spin_site_apply: ") + why);
+  const SpinSiteArgs a{ms.n_sites, ms.n_up, kind, coef, md.n_sites, md.n_up, coef_im};
+  if (const char* why = spin_site_error(a)) return fail(EIGENEX_ERR_ARG, who + ": " + why);
   const double* x = vec_ptr(ss, src->cap, src->nq, x_ref);
   double* y = vec_ptr(sd, dst->cap, dst->nq, y_ref);
   if (!x || !y) return fail(EIGENEX_ERR_ARG, "bad vector reference");
   if (x == y && kind != kSpinSiteZ)
-    return fail(EIGENEX_ERR_ARG, "eigenex_spin_site_apply: y may be x for EIGENEX_SPIN_SITE_Z only (the gather of a flip reads what it would write)");
+    return fail(EIGENEX_ERR_ARG, who + ": y may be x for EIGENEX_SPIN_SITE_Z only (the gather of a flip reads what it would write)");
   eigenex_context_s* c = dst->ctx;
   HIPCHK(hipSetDevice(c->device));
   // scratch of this call alone: the table, the grid's partial sums and norm2.  The states' own partials may hold a pending alpha.
@@ -3265,12 +3277,24 @@ int eigenex_spin_site_apply(eigenex_basis_t src, int x_ref, eigenex_basis_t dst,
   HIPCHK(d_part.alloc((size_t)grid));
   HIPCHK(d_out.alloc(1));
   HIPCHK(hipMemcpyAsync(d_table, &table, sizeof(SpinSiteTable), hipMemcpyHostToDevice, c->stream));
-  launch_spin_site_apply(c->stream, d_table, md.view, ms.lo, ms.hi, x, y, sd.nloc, d_part, grid);
+  launch_spin_site_apply(c->stream, es, d_table, md.view, ms.lo, ms.hi, x, y, sd.nloc, d_part, grid);
   launch_spin_measure_reduce(c->stream, d_part, grid, grid, 0, 0, nullptr, nullptr, d_out);
   HIPCHK(hipMemcpyAsync(&out, d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the table and the scratch live until here
   if (norm2) *norm2 = out;
   return 0;
+}
+
+int eigenex_spin_site_apply(eigenex_basis_t src, int x_ref, eigenex_basis_t dst, int y_ref, int kind, const double* coef, double* norm2) {
+  return spin_site_apply_call("eigenex_spin_site_apply", 1, ": real states only (a complex spin state, eigenex_spin_upload_z, takes eigenex_spin_site_apply_z)", src,
+                              x_ref, dst, y_ref, kind, coef, nullptr, norm2);
+}
+
+int eigenex_spin_site_apply_z(eigenex_basis_t src, int x_ref, eigenex_basis_t dst, int y_ref, int kind, const double* coef_re, const double* coef_im,
+                              double* norm2) {
+  return spin_site_apply_call("eigenex_spin_site_apply_z", 2,
+                              ": complex states only, both of them (eigenex_spin_upload_z, eigenex_spin_sector_upload_z); real states take eigenex_spin_site_apply",
+                              src, x_ref, dst, y_ref, kind, coef_re, coef_im, norm2);
 }
 
 int eigenex_spin_rdm_layout(int n_sites, int n_up, uint32_t mask_a, int* n_blocks, int* k_first, int64_t* dims, int64_t* offsets) {

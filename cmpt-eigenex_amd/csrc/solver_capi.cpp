@@ -12,7 +12,7 @@
 // plus eigenex_[z]trlanczos_solver_* (ThickRestartLanczosEigenSolver), eigenex_[z]kschur_solver_* (KrylovSchurEigenSolver) and
 // eigenex_[z]flanczos_solver_* (FilteredLanczosEigenSolver); eigenex_[z]density_solver_* (SpectralDensitySolver);
 // eigenex_spin_dynamics_solver_* (SpinDynamicsSolver); eigenex_spin_entanglement_solver_* (SpinEntanglementSolver);
-// eigenex_spin_evolution_solver_* (SpinTimeEvolutionSolver).
+// eigenex_spin_evolution_solver_* (SpinTimeEvolutionSolver); eigenex_spin_time_correlation_solver_* (SpinTimeCorrelationSolver).
 // Complex data cross this boundary as interleaved (re, im) doubles.
 #include <complex>
 #include <cstring>
@@ -31,6 +31,7 @@
 #include "cmpt/eigen_ex/spin_dynamics.hpp"
 #include "cmpt/eigen_ex/spin_entanglement.hpp"
 #include "cmpt/eigen_ex/spin_evolution.hpp"
+#include "cmpt/eigen_ex/spin_time_correlation.hpp"
 #include "cmpt/eigen_ex/thick_restart_lanczos.hpp"
 #include "cmpt/eigen_ex/triplets_operator.hpp"
 
@@ -892,12 +893,26 @@ int eigenex_spin_dynamics_solver_set_state_energy(void* p, double E0) {
 int eigenex_spin_dynamics_solver_set_site_operator(void* p, int kind, const double* coef, int n) {
   return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.setSiteOperator(kind, std::vector<double>(coef, coef + (n > 0 ? n : 0))); });
 }
+// a complex state (n entries, interleaved) and complex coefficients (two arrays): the run becomes a complex one
+int eigenex_spin_dynamics_solver_set_state_z(void* p, const double* v, int64_t n) {
+  return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.setState(make_vector<std::complex<double>>(v, n)); });
+}
+int eigenex_spin_dynamics_solver_set_site_operator_z(void* p, int kind, const double* coef_re, const double* coef_im, int n) {
+  return guard([&] {
+    std::vector<std::complex<double>> c((size_t)(n > 0 ? n : 0));
+    for (size_t i = 0; i < c.size(); ++i) c[i] = std::complex<double>(coef_re[i], coef_im ? coef_im[i] : 0.0);
+    static_cast<SpinDynamicsBox*>(p)->es.setSiteOperator(kind, c);
+  });
+}
 int eigenex_spin_dynamics_solver_set_lanczos_steps(void* p, int64_t m) {
   return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.setLanczosSteps((Index)m); });
 }
 int eigenex_spin_dynamics_solver_compute(void* p) { return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.compute(); }); }
 int eigenex_spin_dynamics_solver_compute_structure_factor_z(void* p, double q) {
   return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.computeStructureFactorZ(q); });
+}
+int eigenex_spin_dynamics_solver_compute_structure_factor_z_single_run(void* p, double q) {
+  return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.computeStructureFactorZSingleRun(q); });
 }
 // out[5]: poles, alpha, beta, log lines, info
 int eigenex_spin_dynamics_solver_sizes(void* p, int64_t* out) {
@@ -1062,6 +1077,122 @@ int eigenex_spin_evolution_solver_fetch(void* p, double* out) {
 }
 const char* eigenex_spin_evolution_solver_log_line(void* p, int64_t i) {
   auto& log = static_cast<SpinEvolutionBox*>(p)->es.log();
+  return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
+}
+
+// ---- SpinTimeCorrelationSolver (spin_time_correlation.hpp).  The model crosses as for SpinDynamicsSolver; vectors and complex
+// coefficients are interleaved (re, im).
+struct SpinTimeCorrelationBox {
+  std::shared_ptr<device::Context> ctx;
+  SpinTimeCorrelationSolver es;
+  std::vector<std::complex<double>> out;  // the last values()
+};
+static std::vector<std::complex<double>> complex_coefficients(const double* c, int n) {
+  std::vector<std::complex<double>> out((size_t)(n > 0 ? n : 0));
+  for (size_t i = 0; i < out.size(); ++i) out[i] = std::complex<double>(c[2 * i], c[2 * i + 1]);
+  return out;
+}
+void* eigenex_spin_time_correlation_solver_create(void) {
+  try {
+    return new SpinTimeCorrelationBox();
+  } catch (const std::exception& e) {
+    g_serr = e.what();
+    return nullptr;
+  }
+}
+void eigenex_spin_time_correlation_solver_destroy(void* p) { delete static_cast<SpinTimeCorrelationBox*>(p); }
+int eigenex_spin_time_correlation_solver_set_model(void* p, eigenex_context_t ctx, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                                                   const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null, int n_up) {
+  return guard([&] {
+    auto* b = static_cast<SpinTimeCorrelationBox*>(p);
+    b->ctx = device::Context::borrow(ctx);
+    SpinHalfModel model(n_sites);
+    for (int k = 0; k < n_bonds; ++k) model.addBond(site_i[k], site_j[k], jz[k], jxy[k]);
+    for (int i = 0; i < n_sites; ++i) {
+      if (hz_or_null) model.setFieldZ(i, hz_or_null[i]);
+      if (hx_or_null) model.setFieldX(i, hx_or_null[i]);
+    }
+    b->es.setModel(b->ctx, model, n_up);
+  });
+}
+// v: n entries, interleaved (re, im) if is_complex, else real
+int eigenex_spin_time_correlation_solver_set_state(void* p, const double* v, int64_t n, int is_complex) {
+  return guard([&] {
+    auto& es = static_cast<SpinTimeCorrelationBox*>(p)->es;
+    if (is_complex)
+      es.setState(make_vector<std::complex<double>>(v, n));
+    else
+      es.setState(make_vector<double>(v, n));
+  });
+}
+int eigenex_spin_time_correlation_solver_set_product_state(void* p, uint32_t bits) {
+  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setProductState(bits); });
+}
+int eigenex_spin_time_correlation_solver_set_eigenstate(void* p, double E0) {
+  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setEigenstate(E0); });
+}
+// coef: n complex coefficients, interleaved
+int eigenex_spin_time_correlation_solver_set_source_operator(void* p, int kind, const double* coef, int n) {
+  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setSourceOperator(kind, complex_coefficients(coef, n)); });
+}
+int eigenex_spin_time_correlation_solver_add_measured_operator(void* p, const double* coef, int n) {
+  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.addMeasuredOperator(complex_coefficients(coef, n)); });
+}
+int eigenex_spin_time_correlation_solver_clear_measured_operators(void* p) {
+  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.clearMeasuredOperators(); });
+}
+int eigenex_spin_time_correlation_solver_set_measured_sites(void* p) {
+  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setMeasuredSites(); });
+}
+int eigenex_spin_time_correlation_solver_set_momentum_z(void* p, double q) {
+  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setMomentumZ(q); });
+}
+int eigenex_spin_time_correlation_solver_set_krylov_dimension(void* p, int64_t m) {
+  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setKrylovDimension((Index)m); });
+}
+int eigenex_spin_time_correlation_solver_set_tolerance(void* p, double tol) {
+  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setTolerance(tol); });
+}
+int eigenex_spin_time_correlation_solver_evolve(void* p, double dt, int64_t* substeps) {
+  return guard([&] {
+    const Index s = static_cast<SpinTimeCorrelationBox*>(p)->es.evolve(dt);
+    if (substeps) *substeps = (int64_t)s;
+  });
+}
+// forms values() and returns their number; eigenex_spin_time_correlation_solver_fetch copies them out, interleaved
+int eigenex_spin_time_correlation_solver_values(void* p, int64_t* count) {
+  return guard([&] {
+    auto* b = static_cast<SpinTimeCorrelationBox*>(p);
+    b->out = b->es.values();
+    if (count) *count = (int64_t)b->out.size();
+  });
+}
+int eigenex_spin_time_correlation_solver_fetch(void* p, double* out) {
+  return guard([&] {
+    auto* b = static_cast<SpinTimeCorrelationBox*>(p);
+    for (size_t i = 0; i < b->out.size(); ++i) out[2 * i] = b->out[i].real(), out[2 * i + 1] = b->out[i].imag();
+  });
+}
+// scalars[6] = (time, sourceNormSquared, errorBound, stateErrorBound, sourceErrorBound, operatorApplications);
+// counts[3] = (log lines, info, measured operators)
+int eigenex_spin_time_correlation_solver_status(void* p, double* scalars, int64_t* counts) {
+  return guard([&] {
+    auto& es = static_cast<SpinTimeCorrelationBox*>(p)->es;
+    if (scalars)
+      scalars[0] = es.time(), scalars[1] = es.sourceNormSquared(), scalars[2] = es.errorBound(), scalars[3] = es.stateErrorBound(),
+      scalars[4] = es.sourceErrorBound(), scalars[5] = (double)es.operatorApplications();
+    if (counts) counts[0] = (int64_t)es.log().size(), counts[1] = (int64_t)es.info(), counts[2] = (int64_t)es.measuredOperators();
+  });
+}
+// errorBound(n) and operatorNormBound(n) of measured operator n; out[2]
+int eigenex_spin_time_correlation_solver_operator_bounds(void* p, int64_t n, double* out) {
+  return guard([&] {
+    auto& es = static_cast<SpinTimeCorrelationBox*>(p)->es;
+    out[0] = es.errorBound((size_t)n), out[1] = es.operatorNormBound((size_t)n);
+  });
+}
+const char* eigenex_spin_time_correlation_solver_log_line(void* p, int64_t i) {
+  auto& log = static_cast<SpinTimeCorrelationBox*>(p)->es.log();
   return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
 }
 

@@ -1,7 +1,7 @@
 // The row walk of the matrix-free spin-1/2 kernels (kernels.hip: k_spin_spmv<SECTOR, E> and k_spin_measure<SECTOR, E>, each
-// written once for real (E = double) and complex (E = SpinZ) vectors, k_spin_site_apply<SECTOR>, and through spin_rdm_rows.hpp
+// written once for real (E = double) and complex (E = SpinZ) vectors, as k_spin_site_apply<SECTOR, E> is, and through spin_rdm_rows.hpp
 // k_spin_rdm<SECTOR, TILE, E>), shared by the device code and by the host replays
-// tests/cpp/spin_{model,sector,measure,site,rdm,rdm_z,complex}_sanitize.cpp, which run it under AddressSanitizer +
+// tests/cpp/spin_{model,sector,measure,site,site_z,rdm,rdm_z,complex}_sanitize.cpp, which run it under AddressSanitizer +
 // UBSan.  The kernels and the replays call THESE functions, so what a replay proves about them (every load inside its array, the
 // state equal to spin_sector_unrank, the sums equal to the CSR row loop and to spin_measure_host bit for bit) holds for the
 // kernels' rows as compiled.  No device construct in here: plain C++11.  spin_write_rows, spin_sector_unrank, spin_sector_rank
@@ -164,7 +164,7 @@ EIGENEX_HD void spin_measure_diagonals(SpinZ xs, uint32_t s, const uint32_t* dma
   }
 }
 
-// ---- a sum of site operators (spin_site.hpp; kernels.hip: k_spin_site_apply<SECTOR>), one row of the DESTINATION per lane ----
+// ---- a sum of site operators (spin_site.hpp; kernels.hip: k_spin_site_apply<SECTOR, E>), one row of the DESTINATION per lane ----
 // The lane unranks its state s with the destination's n_up (spin_unrank_row).  Z is ALU work on the lane's own element
 // (spin_site_weight).  PLUS and MINUS take the sites kSpinBatch at a time in the three phases above: spin_site_targets,
 // spin_gather, spin_site_add.  The row has term i where bit i of `has` is set: has = s for PLUS (site i up in the row), ~s &
@@ -173,6 +173,14 @@ EIGENEX_HD void spin_measure_diagonals(SpinZ xs, uint32_t s, const uint32_t* dma
 // tables, so their sum may lie outside x.  A lane without the term ranks `fallback` instead, the lowest state of the source
 // geometry: both table reads stay inside the tables, the row is 0, which every source vector has, no load is branched around,
 // and spin_site_add does not look at what was loaded.
+// The kernel is written once for both elements.  A complex vector has complex coefficients (cr, ci); real_coef, the same for every
+// lane, says that every ci is zero, and then neither ci nor the products with it are looked at: each part of the result is the real
+// walk's on that part of x, bit for bit (spin_site.hpp states the operations and their order).  SpinSiteCoefficients is what
+// the table holds of either form for the sites from a batch's first on; the real overloads read `re` alone.
+struct SpinSiteCoefficients {
+  const double *re, *im;
+  bool real_coef;
+};
 
 // w(s) of Z from the halved coefficients half[i] = c[i] * 0.5: plain additions of sign-flipped constants, sites ascending
 EIGENEX_HD double spin_site_weight(const double* half, int n_sites, uint32_t s) {
@@ -204,6 +212,38 @@ EIGENEX_HD double spin_site_add(double yr, const double* coef, const bool* on, c
   EIGENEX_UNROLL
   for (int t = 0; t < kSpinBatch; ++t) yr = on[t] ? std::fma(coef[t], xv[t], yr) : yr;
   return yr;
+}
+// ... of a complex vector with complex coefficients: per term re += cr x.re, re -= ci x.im, im += cr x.im, im += ci x.re, one fma
+// each; the second and the fourth not with real_coef
+EIGENEX_HD SpinZ spin_site_add(SpinZ yr, const SpinSiteCoefficients& c, const bool* on, const SpinZ* xv) {
+  if (c.real_coef) {
+    EIGENEX_UNROLL
+    for (int t = 0; t < kSpinBatch; ++t) {
+      yr.re = on[t] ? std::fma(c.re[t], xv[t].re, yr.re) : yr.re;
+      yr.im = on[t] ? std::fma(c.re[t], xv[t].im, yr.im) : yr.im;
+    }
+  } else {
+    EIGENEX_UNROLL
+    for (int t = 0; t < kSpinBatch; ++t) {
+      yr.re = on[t] ? std::fma(-c.im[t], xv[t].im, std::fma(c.re[t], xv[t].re, yr.re)) : yr.re;
+      yr.im = on[t] ? std::fma(c.im[t], xv[t].re, std::fma(c.re[t], xv[t].im, yr.im)) : yr.im;
+    }
+  }
+  return yr;
+}
+EIGENEX_HD double spin_site_add(double yr, const SpinSiteCoefficients& c, const bool* on, const double* xv) { return spin_site_add(yr, c.re, on, xv); }
+
+// Z: the row's weight, of a complex vector the pair (wr, wi) of the two halves of the halved coefficients (wi = 0.0 and not summed
+// with real_coef), then its product with the row's own element, which the caller loads after the weight is formed.  The last
+// argument of spin_site_weights only selects the element.
+EIGENEX_HD double spin_site_weights(const SpinSiteCoefficients& half, int n_sites, uint32_t s, double) { return spin_site_weight(half.re, n_sites, s); }
+EIGENEX_HD SpinZ spin_site_weights(const SpinSiteCoefficients& half, int n_sites, uint32_t s, SpinZ) {
+  return SpinZ{spin_site_weight(half.re, n_sites, s), half.real_coef ? 0.0 : spin_site_weight(half.im, n_sites, s)};
+}
+EIGENEX_HD double spin_site_product(double w, bool, double x) { return w * x; }
+EIGENEX_HD SpinZ spin_site_product(SpinZ w, bool real_coef, SpinZ x) {
+  if (real_coef) return SpinZ{w.re * x.re, w.re * x.im};
+  return SpinZ{std::fma(-w.im, x.im, w.re * x.re), std::fma(w.im, x.re, w.re * x.im)};
 }
 
 }  // namespace eigenex

@@ -24,13 +24,23 @@
 // <v|A (w - H)^{-1} B|v> - <v|B (w - H)^{-1} A|v> of O = A + iB cancel, so the response is the sum of the two real runs.  A part
 // whose O|v> is zero is skipped.  totalWeight() then equals the static structureFactorZ(q).
 //
-// Out of scope: complex coefficients in a single run; products of site operators as O; a basis-free three-term recurrence for
+// A complex run.  setSiteOperator with complex coefficients, or setState with a complex vector, switches compute() to the operators
+// for complex states (device::spinHalfComplexOperator: the same real Hamiltonian) and to eigenex_spin_site_apply_z: |phi> = O|v>
+// with complex c_i is formed on the device and ONE fraction is run from it; the Lanczos coefficients of a Hermitian operator are
+// real, so everything after the run is as above.  computeStructureFactorZSingleRun(q) is Szz(q, w) with c_r = L^{-1/2} e^{iqr} in
+// one such run -- half the operator applications of computeStructureFactorZ(q), whose poles and weights it does not reproduce one
+// by one (one fraction of m steps stands for two), while moments, sum rule and broadened spectrum agree.  The real
+// setSiteOperator, computeStructureFactorZ and what they return are untouched by this; computeStructureFactorZ(q) after setState
+// with a complex vector is InvalidInput (its two real runs stand for a real state only) and names the single run.
+//
+// Out of scope: products of site operators as O; a basis-free three-term recurrence for
 // very long fractions (the run keeps m + 1 columns, like every Lanczos run here); more than one GPU (the matrix-free spin
 // operators are one shard); finite temperature.
 #pragma once
 
 #include <algorithm>
 #include <cmath>
+#include <complex>
 #include <cstdint>
 #include <string>
 #include <utility>
@@ -47,6 +57,8 @@ class SpinDynamicsSolver {
  public:
   using Index = EigenEx::Index;
   using VectorType = DenseVector<double>;
+  using Complex = std::complex<double>;
+  using ComplexVectorType = DenseVector<Complex>;
 
   static std::string headERROR() { return std::string("ERROR     "); }
   static std::string headINFO() { return std::string("INFO      "); }
@@ -60,7 +72,12 @@ class SpinDynamicsSolver {
   }
   // a host vector over the source rows, e.g. a column of a solver's eigenvectors(); it need not be normalised
   SpinDynamicsSolver& setState(const VectorType& v) {
-    state_ = v;
+    state_ = v, stateComplex_ = false;
+    return *this;
+  }
+  // a complex state: the run is a complex one (see the top of this file)
+  SpinDynamicsSolver& setState(const ComplexVectorType& v) {
+    stateZ_ = v, stateComplex_ = true;
     return *this;
   }
   SpinDynamicsSolver& setStateEnergy(double E0) {
@@ -69,7 +86,15 @@ class SpinDynamicsSolver {
   }
   // kind: EIGENEX_SPIN_SITE_Z, _PLUS or _MINUS; coef: one real coefficient per site
   SpinDynamicsSolver& setSiteOperator(int kind, const std::vector<double>& coef) {
-    kind_ = kind, coef_ = coef;
+    kind_ = kind, coef_ = coef, coefComplex_ = false;
+    coefIm_.clear();
+    return *this;
+  }
+  // one complex coefficient per site: the run is a complex one
+  SpinDynamicsSolver& setSiteOperator(int kind, const std::vector<Complex>& coef) {
+    kind_ = kind, coefComplex_ = true;
+    coef_.assign(coef.size(), 0.0), coefIm_.assign(coef.size(), 0.0);
+    for (std::size_t i = 0; i < coef.size(); ++i) coef_[i] = coef[i].real(), coefIm_[i] = coef[i].imag();
     return *this;
   }
   SpinDynamicsSolver& setLanczosSteps(Index m) {
@@ -79,8 +104,10 @@ class SpinDynamicsSolver {
 
   Index compute() {
     begin_("compute");
-    if (!prepare_(kind_, coef_)) return 0;
-    run_(kind_, coef_);
+    const bool z = stateComplex_ || coefComplex_;
+    const std::vector<double>* im = coefComplex_ ? &coefIm_ : nullptr;
+    if (!prepare_(kind_, coef_, im, z)) return 0;
+    run_(kind_, coef_, im, z);
     finish_();
     return static_cast<Index>(poles_.size());
   }
@@ -92,12 +119,28 @@ class SpinDynamicsSolver {
     const int L = model_.sites();
     if (L < 1) return invalid_("invalid input: the model has no sites");
     std::vector<double> c(static_cast<std::size_t>(L), 0.0);
-    if (!prepare_(EIGENEX_SPIN_SITE_Z, c)) return 0;
+    if (!prepare_(EIGENEX_SPIN_SITE_Z, c, nullptr, false)) return 0;
     const double scale = 1.0 / std::sqrt(static_cast<double>(L));
     for (int part = 0; part < 2 && info_ == Success; ++part) {
       for (int i = 0; i < L; ++i) c[static_cast<std::size_t>(i)] = scale * (part == 0 ? std::cos(q * i) : std::sin(q * i));
-      run_(EIGENEX_SPIN_SITE_Z, c);
+      run_(EIGENEX_SPIN_SITE_Z, c, nullptr, false);
     }
+    finish_();
+    return static_cast<Index>(poles_.size());
+  }
+
+  // Szz(q, w) from ONE complex run with c_r = L^{-1/2} e^{iqr} (see the top of this file); a real state is taken as a complex one.
+  // The site operator that was set is not used.
+  Index computeStructureFactorZSingleRun(double q) {
+    begin_("computeStructureFactorZSingleRun");
+    if (!haveModel_ || !ctx_) return invalid_("invalid input: no model (setModel)");
+    const int L = model_.sites();
+    if (L < 1) return invalid_("invalid input: the model has no sites");
+    std::vector<double> cr(static_cast<std::size_t>(L), 0.0), ci(static_cast<std::size_t>(L), 0.0);
+    const double scale = 1.0 / std::sqrt(static_cast<double>(L));
+    for (int i = 0; i < L; ++i) cr[static_cast<std::size_t>(i)] = scale * std::cos(q * i), ci[static_cast<std::size_t>(i)] = scale * std::sin(q * i);
+    if (!prepare_(EIGENEX_SPIN_SITE_Z, cr, &ci, true)) return 0;
+    run_(EIGENEX_SPIN_SITE_Z, cr, &ci, true);
     finish_();
     return static_cast<Index>(poles_.size());
   }
@@ -144,11 +187,13 @@ class SpinDynamicsSolver {
   }
   static int dstUp_(int nUp, int kind) { return nUp < 0 || kind == EIGENEX_SPIN_SITE_Z ? nUp : (kind == EIGENEX_SPIN_SITE_PLUS ? nUp + 1 : nUp - 1); }
   std::shared_ptr<device::CsrOperator> makeOperator_(int nUp) const {
+    if (complexRun_) return device::spinHalfComplexOperator(ctx_, model_, nUp);
     return nUp < 0 ? device::spinHalfOperator(ctx_, model_) : device::spinHalfSectorOperator(ctx_, model_, nUp);
   }
 
   // checks, the source operator, the state on the device, <v|v> and E0; false after invalid_()
-  bool prepare_(int kind, const std::vector<double>& coef) {
+  // coefIm: the imaginary parts of complex coefficients or null; z: a complex run (complex operators, states and site kernel)
+  bool prepare_(int kind, const std::vector<double>& coef, const std::vector<double>* coefIm, bool z) {
     if (!haveModel_ || !ctx_) return invalid_("invalid input: no model (setModel)"), false;
     const int L = model_.sites();
     if (kind != EIGENEX_SPIN_SITE_Z && kind != EIGENEX_SPIN_SITE_PLUS && kind != EIGENEX_SPIN_SITE_MINUS)
@@ -156,32 +201,53 @@ class SpinDynamicsSolver {
     if (static_cast<int>(coef.size()) != L) return invalid_("invalid input: the site operator needs one coefficient per site"), false;
     for (double c : coef)
       if (!std::isfinite(c)) return invalid_("invalid input: a coefficient of the site operator is not finite"), false;
+    if (coefIm) {
+      if (coefIm->size() != coef.size()) return invalid_("invalid input: the site operator needs one coefficient per site"), false;
+      for (double c : *coefIm)
+        if (!std::isfinite(c)) return invalid_("invalid input: a coefficient of the site operator is not finite"), false;
+    }
     if (steps_ < 1) return invalid_("invalid input: setLanczosSteps needs at least one step"), false;
+    if (!z && stateComplex_)  // only computeStructureFactorZ asks for a real run whatever was set: its cos + sin sum holds for real states
+      return invalid_("invalid input: computeStructureFactorZ needs a real state; a complex one takes computeStructureFactorZSingleRun"), false;
     if (nUp_ >= 0 && (dstUp_(nUp_, kind) < 0 || dstUp_(nUp_, kind) > L))
       return invalid_("invalid input: the site operator leaves the sectors of the model (S+ of the sector with every site up, S- of the one with none)"), false;
+    if (z != complexRun_) {  // the other scalar type: its own operators and states
+      srcDev_.release(), dstDev_.release();
+      srcOp_.reset(), dstOp_.reset();
+      complexRun_ = z;
+    }
     try {
       if (!srcOp_) srcOp_ = makeOperator_(nUp_);
     } catch (const LanczosException& e) {
       return invalid_(std::string("invalid input: the model has no such operator: ") + e.what()), false;
     }
     const Index n = static_cast<Index>(srcOp_->rows());
-    if (state_.size() != n) return invalid_("invalid input: the state must have one entry per row of the model's space or sector (setState)"), false;
-    if (!srcDev_.alive()) srcDev_.create(ctx_, srcOp_, n, 1, 0, false);
-    srcDev_.upload(EIGENEX_VEC_COL(0), state_);
+    if ((stateComplex_ ? stateZ_.size() : state_.size()) != n)
+      return invalid_("invalid input: the state must have one entry per row of the model's space or sector (setState)"), false;
+    if (!srcDev_.alive()) srcDev_.create(ctx_, srcOp_, n, 1, 0, z);
+    if (!z) {
+      srcDev_.upload(EIGENEX_VEC_COL(0), state_);
+    } else if (stateComplex_) {
+      srcDev_.upload(EIGENEX_VEC_COL(0), stateZ_);
+    } else {
+      ComplexVectorType promoted(n);
+      for (Index r = 0; r < n; ++r) promoted[r] = Complex(state_[r], 0.0);
+      srcDev_.upload(EIGENEX_VEC_COL(0), promoted);
+    }
     device::check(eigenex_spin_measure(srcDev_.handle(), EIGENEX_VEC_COL(0), 0, nullptr, 0, nullptr, nullptr, nullptr, &vv_), "eigenex_spin_measure");
     if (!(vv_ > 0.0) || !std::isfinite(vv_)) return invalid_("invalid input: the state is zero (or not finite)"), false;
     if (haveE0_) {
       E0_ = E0set_;
     } else {
-      double vHv = 0.0;
-      device::check(eigenex_apply(srcDev_.handle(), EIGENEX_VEC_COL(0), EIGENEX_VEC_V, 0.0, &vHv), "eigenex_apply");
-      E0_ = vHv / vv_;
+      double vHv[2] = {0.0, 0.0};  // a complex state's dot has two parts; <v|H|v> is the real one
+      device::check(eigenex_apply(srcDev_.handle(), EIGENEX_VEC_COL(0), EIGENEX_VEC_V, 0.0, vHv), "eigenex_apply");
+      E0_ = vHv[0] / vv_;
     }
     return true;
   }
 
   // one continued fraction: |phi> = O|v> into the work vector of the destination state, m Lanczos steps, poles and weights appended
-  void run_(int kind, const std::vector<double>& coef) {
+  void run_(int kind, const std::vector<double>& coef, const std::vector<double>* coefIm, bool z) {
     const int up = dstUp_(nUp_, kind);
     std::shared_ptr<device::CsrOperator> want = up == nUp_ ? srcOp_ : (dstOp_ && dstOp_ != srcOp_ && dstUpBuilt_ == up ? dstOp_ : makeOperator_(up));
     if (want != dstOp_) {
@@ -193,14 +259,19 @@ class SpinDynamicsSolver {
     const Index m = std::min<Index>(steps_, n);
     const int cap = static_cast<int>(m + 1);
     if (!dstDev_.alive() || dstDevOp_ != dstOp_.get() || dstDev_.capacity() < cap) {
-      dstDev_.create(ctx_, dstOp_, n, cap, 0, false);
+      dstDev_.create(ctx_, dstOp_, n, cap, 0, z);
       dstDevOp_ = dstOp_.get();
     } else {
       device::check(eigenex_basis_clear(dstDev_.handle()), "eigenex_basis_clear");
     }
     double norm2 = 0.0;
-    device::check(eigenex_spin_site_apply(srcDev_.handle(), EIGENEX_VEC_COL(0), dstDev_.handle(), EIGENEX_VEC_W, kind, coef.data(), &norm2),
-                  "eigenex_spin_site_apply");
+    if (z)
+      device::check(eigenex_spin_site_apply_z(srcDev_.handle(), EIGENEX_VEC_COL(0), dstDev_.handle(), EIGENEX_VEC_W, kind, coef.data(),
+                                              coefIm ? coefIm->data() : nullptr, &norm2),
+                    "eigenex_spin_site_apply_z");
+    else
+      device::check(eigenex_spin_site_apply(srcDev_.handle(), EIGENEX_VEC_COL(0), dstDev_.handle(), EIGENEX_VEC_W, kind, coef.data(), &norm2),
+                    "eigenex_spin_site_apply");
     if (!std::isfinite(norm2)) {
       log_.push_back(headERROR() + "O|v> is not finite");
       info_ = NumericalIssue;
@@ -209,6 +280,8 @@ class SpinDynamicsSolver {
     // |y_r| <= L eps sum_i |c_i| |x| is what the roundings of the application alone can leave of an exact zero (Z: half of it)
     double csum = 0.0;
     for (double c : coef) csum += std::fabs(c);
+    if (coefIm)
+      for (double c : *coefIm) csum += std::fabs(c);  // a complex coefficient: |Re| + |Im| bounds what each part of a row sums
     const double noise = static_cast<double>(model_.sites()) * std::ldexp(1.0, -52) * csum * (kind == EIGENEX_SPIN_SITE_Z ? 0.5 : 1.0);
     if (norm2 <= noise * noise * vv_) {
       log_.push_back(headINFO() + (norm2 == 0.0 ? "O|v> = 0" : "O|v> vanishes within the rounding of its application") +
@@ -260,8 +333,10 @@ class SpinDynamicsSolver {
   SpinHalfModel model_;
   bool haveModel_ = false, haveE0_ = false;
   int nUp_ = -1, kind_ = -1, dstUpBuilt_ = -2;
-  std::vector<double> coef_;
+  std::vector<double> coef_, coefIm_;
   VectorType state_;
+  ComplexVectorType stateZ_;
+  bool stateComplex_ = false, coefComplex_ = false, complexRun_ = false;
   Index steps_ = 100;
   double E0set_ = 0.0;
 

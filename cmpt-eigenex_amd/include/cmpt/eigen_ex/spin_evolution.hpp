@@ -33,9 +33,11 @@
 // SpinEntanglementSolver (spin_entanglement.hpp: detail::EntanglementBlocks); they change no vector, time, bound or counter.
 // state() downloads.
 //
-// Out of scope: complex couplings (Sy, Dzyaloshinskii-Moriya terms); momentum sectors; S(q, w) with complex coefficients in one
-// run; time-dependent Hamiltonians; Chebyshev propagators; site operators of complex states; more than one GPU (the matrix-free
-// spin operators are one shard).
+// The sub-step and its bound are detail::krylovSubStep and detail::krylovErrorIntegral below, which SpinTimeCorrelationSolver
+// (spin_time_correlation.hpp: unequal-time correlations <A(t) B(0)>, through site operators of complex states) shares.
+//
+// Out of scope: complex couplings (Sy, Dzyaloshinskii-Moriya terms); momentum sectors; time-dependent Hamiltonians; Chebyshev
+// propagators; more than one GPU (the matrix-free spin operators are one shard).
 #pragma once
 
 #include <algorithm>
@@ -53,6 +55,102 @@
 namespace cmpt {
 namespace EigenEx {
 
+namespace detail {
+
+constexpr int kKrylovQuadPanels = 512;  // composite Simpson: kKrylovQuadPanels + 1 nodes
+constexpr int kKrylovBisections = 60;
+
+// B(tau) of the header for T = S diag(theta) S^T of dimension k (S column-major): beta_m times the Simpson sum
+inline double krylovErrorIntegral(const std::vector<double>& theta, const std::vector<double>& S, int k, double betaM, double tau) {
+  std::vector<double> w(static_cast<std::size_t>(k));
+  for (int j = 0; j < k; ++j) w[static_cast<std::size_t>(j)] = S[static_cast<std::size_t>(j) * k + (k - 1)] * S[static_cast<std::size_t>(j) * k];
+  const double hstep = tau / kKrylovQuadPanels;
+  double sum = 0.0;
+  for (int q = 0; q <= kKrylovQuadPanels; ++q) {
+    const double s = hstep * q;
+    double re = 0.0, im = 0.0;
+    for (int j = 0; j < k; ++j) {
+      re += w[static_cast<std::size_t>(j)] * std::cos(s * theta[static_cast<std::size_t>(j)]);
+      im -= w[static_cast<std::size_t>(j)] * std::sin(s * theta[static_cast<std::size_t>(j)]);
+    }
+    const double weight = (q == 0 || q == kKrylovQuadPanels) ? 1.0 : ((q & 1) ? 4.0 : 2.0);
+    sum += weight * std::sqrt(re * re + im * im);
+  }
+  return betaM * sum * hstep / 3.0;
+}
+
+// One sub-step of the header on the work vector W of the complex Krylov state `basis` of n rows, whose capacity is at least m + 2
+// columns (m: the Krylov dimension, at most n): W <- exp(-i sign tau H) W for the largest tau <= remaining whose bound passes
+// tol * tau / total; the state is cleared afterwards.  failure: null, or what went wrong (a NumericalIssue of the caller);
+// applications counts the operator applications of the Lanczos run whether the step failed or not.
+struct KrylovSubStep {
+  double tau = 0.0, bound = 0.0;
+  Index applications = 0;
+  const char* failure = nullptr;
+};
+inline KrylovSubStep krylovSubStep(eigenex_basis_t basis, Index n, Index m, double tol, double remaining, double total, double sign) {
+  KrylovSubStep out;
+  const auto failed = [&out](const char* what) {
+    out.failure = what;
+    return out;
+  };
+  const bool whole = m >= n;  // the Krylov space is the space: exact without beta_m
+  const int calls = static_cast<int>(whole ? m : m + 1);
+  device::check(eigenex_lanczos_enqueue(basis, calls), "eigenex_lanczos_enqueue");
+  eigenex_state_t st;
+  std::vector<double> alpha(static_cast<std::size_t>(m) + 4, 0.0), beta(static_cast<std::size_t>(m) + 4, 0.0);
+  device::check(eigenex_lanczos_state(basis, &st, alpha.data(), beta.data()), "eigenex_lanczos_state");
+  out.applications = st.nalpha;
+  const int k = std::min<int>(st.nalpha, static_cast<int>(m));
+  if (k < 1) return failed("the state failed the breakdown threshold of the Lanczos run (it is zero or not finite)");
+  for (int j = 0; j < k; ++j)
+    if (!std::isfinite(alpha[static_cast<std::size_t>(j)]) || (j + 1 < k && !std::isfinite(beta[static_cast<std::size_t>(j)])))
+      return failed("the Lanczos coefficients are not finite");
+  const bool exact = whole || st.stopped != 0 || st.nbeta < static_cast<int>(m);
+  std::vector<double> theta, S;
+  if (!small_eigen::tridiagonal(alpha.data(), beta.data(), k, theta, &S)) return failed("the tridiagonal eigenproblem did not converge");
+  const double betaM = exact ? 0.0 : beta[static_cast<std::size_t>(m) - 1];
+  if (!std::isfinite(betaM)) return failed("the Lanczos coefficients are not finite");
+  double tau = remaining, bound = 0.0;
+  if (!exact) {
+    const auto passes = [&](double t, double& B) {
+      B = krylovErrorIntegral(theta, S, k, betaM, t);
+      return B <= tol * t / total;
+    };
+    double B = 0.0;
+    if (passes(remaining, B)) {
+      bound = B;
+    } else {
+      double lo = 0.0, hi = remaining, Blo = 0.0;
+      for (int it = 0; it < kKrylovBisections; ++it) {
+        const double mid = 0.5 * (lo + hi);
+        if (passes(mid, B))
+          lo = mid, Blo = B;
+        else
+          hi = mid;
+      }
+      if (!(lo > 0.0)) return failed("no step passes the tolerance: the Krylov dimension is too small");
+      tau = lo, bound = Blo;
+    }
+  }
+  // c = S exp(-i sign tau theta) S^T e_1
+  std::vector<double> cre(static_cast<std::size_t>(k), 0.0), cim(static_cast<std::size_t>(k), 0.0);
+  for (int j = 0; j < k; ++j) {
+    const double ph = sign * tau * theta[static_cast<std::size_t>(j)], s0 = S[static_cast<std::size_t>(j) * k];
+    const double fr = std::cos(ph) * s0, fi = -std::sin(ph) * s0;
+    for (int r = 0; r < k; ++r) {
+      cre[static_cast<std::size_t>(r)] += S[static_cast<std::size_t>(j) * k + r] * fr;
+      cim[static_cast<std::size_t>(r)] += S[static_cast<std::size_t>(j) * k + r] * fi;
+    }
+  }
+  device::check(eigenex_krylov_combine_to(basis, k, cre.data(), cim.data(), EIGENEX_VEC_W), "eigenex_krylov_combine_to");
+  device::check(eigenex_basis_clear(basis), "eigenex_basis_clear");
+  out.tau = tau, out.bound = bound;
+  return out;
+}
+
+}  // namespace detail
+
 class SpinTimeEvolutionSolver {
  public:
   using Index = EigenEx::Index;
@@ -60,8 +158,8 @@ class SpinTimeEvolutionSolver {
   using VectorType = DenseVector<Complex>;
   using RealVectorType = DenseVector<double>;
 
-  static constexpr int kQuadPanels = 512;    // composite Simpson: kQuadPanels + 1 nodes
-  static constexpr int kBisections = 60;
+  static constexpr int kQuadPanels = detail::kKrylovQuadPanels;  // composite Simpson: kQuadPanels + 1 nodes
+  static constexpr int kBisections = detail::kKrylovBisections;
   static constexpr Index kMaxSubSteps = 1000000;
 
   static std::string headERROR() { return std::string("ERROR     "); }
@@ -248,21 +346,7 @@ class SpinTimeEvolutionSolver {
 
   // B(tau) of the header for T = S diag(theta) S^T of dimension k (S column-major): beta_m times the Simpson sum
   static double errorIntegral(const std::vector<double>& theta, const std::vector<double>& S, int k, double betaM, double tau) {
-    std::vector<double> w(static_cast<std::size_t>(k));
-    for (int j = 0; j < k; ++j) w[static_cast<std::size_t>(j)] = S[static_cast<std::size_t>(j) * k + (k - 1)] * S[static_cast<std::size_t>(j) * k];
-    const double hstep = tau / kQuadPanels;
-    double sum = 0.0;
-    for (int q = 0; q <= kQuadPanels; ++q) {
-      const double s = hstep * q;
-      double re = 0.0, im = 0.0;
-      for (int j = 0; j < k; ++j) {
-        re += w[static_cast<std::size_t>(j)] * std::cos(s * theta[static_cast<std::size_t>(j)]);
-        im -= w[static_cast<std::size_t>(j)] * std::sin(s * theta[static_cast<std::size_t>(j)]);
-      }
-      const double weight = (q == 0 || q == kQuadPanels) ? 1.0 : ((q & 1) ? 4.0 : 2.0);
-      sum += weight * std::sqrt(re * re + im * im);
-    }
-    return betaM * sum * hstep / 3.0;
+    return detail::krylovErrorIntegral(theta, S, k, betaM, tau);
   }
 
  private:
@@ -329,58 +413,10 @@ class SpinTimeEvolutionSolver {
   }
 
   bool subStep_(double remaining, double total, double sign, double& tau, double& bound) {
-    const Index n = rows_(), m = krylov_();
-    const bool whole = m >= n;  // the Krylov space is the space: exact without beta_m
-    const int calls = static_cast<int>(whole ? m : m + 1);
-    device::check(eigenex_lanczos_enqueue(dev_.handle(), calls), "eigenex_lanczos_enqueue");
-    eigenex_state_t st;
-    std::vector<double> alpha(static_cast<std::size_t>(m) + 4, 0.0), beta(static_cast<std::size_t>(m) + 4, 0.0);
-    device::check(eigenex_lanczos_state(dev_.handle(), &st, alpha.data(), beta.data()), "eigenex_lanczos_state");
-    applications_ += st.nalpha;
-    const int k = std::min<int>(st.nalpha, static_cast<int>(m));
-    if (k < 1) return failed_("the state failed the breakdown threshold of the Lanczos run (it is zero or not finite)"), false;
-    for (int j = 0; j < k; ++j)
-      if (!std::isfinite(alpha[static_cast<std::size_t>(j)]) || (j + 1 < k && !std::isfinite(beta[static_cast<std::size_t>(j)])))
-        return failed_("the Lanczos coefficients are not finite"), false;
-    const bool exact = whole || st.stopped != 0 || st.nbeta < static_cast<int>(m);
-    std::vector<double> theta, S;
-    if (!small_eigen::tridiagonal(alpha.data(), beta.data(), k, theta, &S)) return failed_("the tridiagonal eigenproblem did not converge"), false;
-    const double betaM = exact ? 0.0 : beta[static_cast<std::size_t>(m) - 1];
-    if (!std::isfinite(betaM)) return failed_("the Lanczos coefficients are not finite"), false;
-    tau = remaining, bound = 0.0;
-    if (!exact) {
-      const auto passes = [&](double t, double& B) {
-        B = errorIntegral(theta, S, k, betaM, t);
-        return B <= tol_ * t / total;
-      };
-      double B = 0.0;
-      if (passes(remaining, B)) {
-        bound = B;
-      } else {
-        double lo = 0.0, hi = remaining, Blo = 0.0;
-        for (int it = 0; it < kBisections; ++it) {
-          const double mid = 0.5 * (lo + hi);
-          if (passes(mid, B))
-            lo = mid, Blo = B;
-          else
-            hi = mid;
-        }
-        if (!(lo > 0.0)) return failed_("no step passes the tolerance: the Krylov dimension is too small"), false;
-        tau = lo, bound = Blo;
-      }
-    }
-    // c = S exp(-i sign tau theta) S^T e_1
-    std::vector<double> cre(static_cast<std::size_t>(k), 0.0), cim(static_cast<std::size_t>(k), 0.0);
-    for (int j = 0; j < k; ++j) {
-      const double ph = sign * tau * theta[static_cast<std::size_t>(j)], s0 = S[static_cast<std::size_t>(j) * k];
-      const double fr = std::cos(ph) * s0, fi = -std::sin(ph) * s0;
-      for (int r = 0; r < k; ++r) {
-        cre[static_cast<std::size_t>(r)] += S[static_cast<std::size_t>(j) * k + r] * fr;
-        cim[static_cast<std::size_t>(r)] += S[static_cast<std::size_t>(j) * k + r] * fi;
-      }
-    }
-    device::check(eigenex_krylov_combine_to(dev_.handle(), k, cre.data(), cim.data(), EIGENEX_VEC_W), "eigenex_krylov_combine_to");
-    device::check(eigenex_basis_clear(dev_.handle()), "eigenex_basis_clear");
+    const detail::KrylovSubStep step = detail::krylovSubStep(dev_.handle(), rows_(), krylov_(), tol_, remaining, total, sign);
+    applications_ += step.applications;
+    if (step.failure) return failed_(step.failure), false;
+    tau = step.tau, bound = step.bound;
     return true;
   }
 

@@ -96,6 +96,9 @@ def lib():
         getattr(L, p + "set_lanczos_steps").argtypes = [_vp, C.c_int64]
         getattr(L, p + "compute").argtypes = [_vp]
         getattr(L, p + "compute_structure_factor_z").argtypes = [_vp, C.c_double]
+        getattr(L, p + "compute_structure_factor_z_single_run").argtypes = [_vp, C.c_double]
+        getattr(L, p + "set_state_z").argtypes = [_vp, _dp, C.c_int64]
+        getattr(L, p + "set_site_operator_z").argtypes = [_vp, C.c_int, _dp, _dp, C.c_int]
         getattr(L, p + "sizes").argtypes = [_vp, _lp]
         getattr(L, p + "get").argtypes = [_vp, _dp, _dp, _dp, _dp, _dp]
         getattr(L, p + "spectrum").argtypes = [_vp, _dp, C.c_int64, C.c_double, _dp]
@@ -119,6 +122,29 @@ def lib():
         getattr(L, p + "measure").argtypes = [_vp, C.c_int, _lp]
         getattr(L, p + "entanglement").argtypes = [_vp, C.c_uint32, _ip32, C.c_int, C.c_int, _lp]
         getattr(L, p + "fetch").argtypes = [_vp, _dp]
+        getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
+        getattr(L, p + "log_line").restype = C.c_char_p
+        p = "eigenex_spin_time_correlation_solver_"
+        getattr(L, p + "create").argtypes = []
+        getattr(L, p + "create").restype = _vp
+        getattr(L, p + "destroy").argtypes = [_vp]
+        getattr(L, p + "destroy").restype = None
+        getattr(L, p + "set_model").argtypes = [_vp, _vp, C.c_int, C.c_int, _ip32, _ip32, _dp, _dp, _dp, _dp, C.c_int]
+        getattr(L, p + "set_state").argtypes = [_vp, _dp, C.c_int64, C.c_int]
+        getattr(L, p + "set_product_state").argtypes = [_vp, C.c_uint32]
+        getattr(L, p + "set_eigenstate").argtypes = [_vp, C.c_double]
+        getattr(L, p + "set_source_operator").argtypes = [_vp, C.c_int, _dp, C.c_int]
+        getattr(L, p + "add_measured_operator").argtypes = [_vp, _dp, C.c_int]
+        getattr(L, p + "clear_measured_operators").argtypes = [_vp]
+        getattr(L, p + "set_measured_sites").argtypes = [_vp]
+        getattr(L, p + "set_momentum_z").argtypes = [_vp, C.c_double]
+        getattr(L, p + "set_krylov_dimension").argtypes = [_vp, C.c_int64]
+        getattr(L, p + "set_tolerance").argtypes = [_vp, C.c_double]
+        getattr(L, p + "evolve").argtypes = [_vp, C.c_double, _lp]
+        getattr(L, p + "values").argtypes = [_vp, _lp]
+        getattr(L, p + "fetch").argtypes = [_vp, _dp]
+        getattr(L, p + "status").argtypes = [_vp, _dp, _lp]
+        getattr(L, p + "operator_bounds").argtypes = [_vp, C.c_int64, _dp]
         getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
         getattr(L, p + "log_line").restype = C.c_char_p
         p = "eigenex_spin_entanglement_solver_"
@@ -698,6 +724,11 @@ class SpinDynamicsSolver:
         return self
 
     def setState(self, v):
+        """a real state, or a complex one (then the run is a complex one)"""
+        if np.iscomplexobj(v):
+            a = np.ascontiguousarray(v, np.complex128)
+            _chk(self._f("set_state_z")(self.h, _d(a.view(np.float64)), a.size))
+            return self
         a = np.ascontiguousarray(v, np.float64)
         _chk(self._f("set_state")(self.h, _d(a), a.size))
         return self
@@ -707,6 +738,12 @@ class SpinDynamicsSolver:
         return self
 
     def setSiteOperator(self, kind, coef):
+        """real coefficients, or complex ones (then the run is a complex one)"""
+        if np.iscomplexobj(coef):
+            c = np.asarray(coef).reshape(-1)
+            cr, ci = np.ascontiguousarray(c.real, np.float64), np.ascontiguousarray(c.imag, np.float64)
+            _chk(self._f("set_site_operator_z")(self.h, int(kind), _d(cr), _d(ci), cr.size))
+            return self
         a = np.ascontiguousarray(coef, np.float64)
         _chk(self._f("set_site_operator")(self.h, int(kind), _d(a), a.size))
         return self
@@ -721,6 +758,11 @@ class SpinDynamicsSolver:
 
     def computeStructureFactorZ(self, q):
         _chk(self._f("compute_structure_factor_z")(self.h, float(q)))
+        return self
+
+    def computeStructureFactorZSingleRun(self, q):
+        """Szz(q, w) from one complex run with c_r = L^{-1/2} e^{iqr}"""
+        _chk(self._f("compute_structure_factor_z_single_run")(self.h, float(q)))
         return self
 
     def _sizes(self):
@@ -898,6 +940,145 @@ class SpinTimeEvolutionSolver:
 
     def entanglementSpectrum(self, subsystem):
         return self._entanglement(subsystem, 2)
+
+    def log(self):
+        return [self._f("log_line")(self.h, i).decode() for i in range(int(self._status()[1][0]))]
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SpinTimeCorrelationSolver:
+    """SpinTimeCorrelationSolver (spin_time_correlation.hpp): C_n(t) = <A_n psi(t) | exp(-iHt) B psi_0> of a spin-1/2 model by
+    Krylov propagation of two vectors on the device.  The model is given as for SpinDynamicsSolver; coefficients are real or
+    complex, one per site."""
+
+    def __init__(self):
+        self._L = lib()
+        self.h = _vp(self._L.eigenex_spin_time_correlation_solver_create())
+        if not self.h:
+            raise capi.EigenexError("solver create failed")
+        self._keep = []
+
+    def _f(self, name):
+        return getattr(self._L, "eigenex_spin_time_correlation_solver_" + name)
+
+    def setModel(self, ctx: capi.Context, n_sites, bonds, hz=None, hx=None, n_up=None):
+        i32 = C.POINTER(C.c_int32)
+        si = np.ascontiguousarray([b[0] for b in bonds], np.int32)
+        sj = np.ascontiguousarray([b[1] for b in bonds], np.int32)
+        jz = np.ascontiguousarray([b[2] for b in bonds], np.float64)
+        jxy = np.ascontiguousarray([b[3] for b in bonds], np.float64)
+        fz = None if hz is None else np.ascontiguousarray(hz, np.float64)
+        fx = None if hx is None else np.ascontiguousarray(hx, np.float64)
+        self._keep.append(ctx)
+        _chk(self._f("set_model")(self.h, ctx.h, int(n_sites), si.size, si.ctypes.data_as(i32), sj.ctypes.data_as(i32), _d(jz), _d(jxy),
+                                  None if fz is None else _d(fz), None if fx is None else _d(fx), -1 if n_up is None else int(n_up)))
+        return self
+
+    def setState(self, v):
+        cplx = np.iscomplexobj(v)
+        a = np.ascontiguousarray(v, np.complex128 if cplx else np.float64)
+        _chk(self._f("set_state")(self.h, _d(a.view(np.float64)), a.size, int(cplx)))
+        return self
+
+    def setProductState(self, bits):
+        _chk(self._f("set_product_state")(self.h, int(bits)))
+        return self
+
+    def setEigenstate(self, E0):
+        _chk(self._f("set_eigenstate")(self.h, float(E0)))
+        return self
+
+    @staticmethod
+    def _coef(coef):
+        return np.ascontiguousarray(np.asarray(coef).reshape(-1), np.complex128)
+
+    def setSourceOperator(self, kind, coef):
+        c = self._coef(coef)
+        _chk(self._f("set_source_operator")(self.h, int(kind), _d(c.view(np.float64)), c.size))
+        return self
+
+    def addMeasuredOperator(self, coef):
+        c = self._coef(coef)
+        _chk(self._f("add_measured_operator")(self.h, _d(c.view(np.float64)), c.size))
+        return self
+
+    def clearMeasuredOperators(self):
+        _chk(self._f("clear_measured_operators")(self.h))
+        return self
+
+    def setMeasuredSites(self):
+        _chk(self._f("set_measured_sites")(self.h))
+        return self
+
+    def setMomentumZ(self, q):
+        _chk(self._f("set_momentum_z")(self.h, float(q)))
+        return self
+
+    def setKrylovDimension(self, m):
+        _chk(self._f("set_krylov_dimension")(self.h, int(m)))
+        return self
+
+    def setTolerance(self, tol):
+        _chk(self._f("set_tolerance")(self.h, float(tol)))
+        return self
+
+    def evolve(self, dt):
+        n = C.c_int64()
+        _chk(self._f("evolve")(self.h, float(dt), C.byref(n)))
+        return n.value
+
+    def values(self):
+        n = C.c_int64()
+        _chk(self._f("values")(self.h, C.byref(n)))
+        out = np.zeros(n.value, np.complex128)
+        _chk(self._f("fetch")(self.h, _d(out.view(np.float64))))
+        return out
+
+    def _status(self):
+        sc, cnt = np.zeros(6), np.zeros(3, np.int64)
+        _chk(self._f("status")(self.h, _d(sc), cnt.ctypes.data_as(_lp)))
+        return sc, cnt
+
+    def time(self):
+        return self._status()[0][0]
+
+    def sourceNormSquared(self):
+        return self._status()[0][1]
+
+    def errorBound(self, n=None):
+        """the bound on |delta C_n| of measured operator n, or the largest over all of them"""
+        if n is None:
+            return self._status()[0][2]
+        out = np.zeros(2)
+        _chk(self._f("operator_bounds")(self.h, int(n), _d(out)))
+        return out[0]
+
+    def operatorNormBound(self, n):
+        out = np.zeros(2)
+        _chk(self._f("operator_bounds")(self.h, int(n), _d(out)))
+        return out[1]
+
+    def stateErrorBound(self):
+        return self._status()[0][3]
+
+    def sourceErrorBound(self):
+        return self._status()[0][4]
+
+    def operatorApplications(self):
+        return int(self._status()[0][5])
+
+    def info(self):
+        return INFO[int(self._status()[1][1])]
 
     def log(self):
         return [self._f("log_line")(self.h, i).decode() for i in range(int(self._status()[1][0]))]

@@ -312,8 +312,9 @@ int eigenex_spin_sector_upload(eigenex_context_t ctx, int n_sites, int n_up, int
  * eigenex_csr_info, eigenex_csr_layout and eigenex_csr_encoding answer as for the real handles.  On a complex spin state:
  *   eigenex_spin_measure                             the Hermitian sums, see below
  *   eigenex_spin_rdm_z                               the reduced density matrix M M^H, see below
+ *   eigenex_spin_site_apply_z                        a sum of site operators with complex coefficients, see below
  *   eigenex_spin_rdm, eigenex_spin_site_apply        EIGENEX_ERR_STATE, "real states only", before anything is allocated
- *                                                    (eigenex_spin_rdm's message names eigenex_spin_rdm_z)
+ *                                                    (the messages name eigenex_spin_rdm_z and eigenex_spin_site_apply_z)
  *   eigenex_basis_set_filter, eigenex_filter_apply,  supported: a complex state takes the streaming form of the Chebyshev step,
  *   eigenex_kpm_moments, eigenex_kpm_trace_moments   whose real coefficients act on both parts alike and whose dots are the real
  *                                                    parts of the Hermitian ones, which is all a Hermitian operator's moments
@@ -396,6 +397,28 @@ int eigenex_spin_site_apply(eigenex_basis_t src, int x_ref, eigenex_basis_t dst,
                             const double* coef /* n_sites */, double* norm2 /* or NULL */);
 int eigenex_spin_site_apply_host(int n_sites, int n_up_src /* -1: full space */, int kind, const double* coef,
                                  const double* x, double* y, double* norm2);
+/* The same of a COMPLEX vector (interleaved (re, im)) with complex coefficients c[i] = (coef_re[i], coef_im[i]): O psi(t) of an
+ * evolved state and the operators sum_r exp(iqr) S_r, formed on the device.  NOT part of the reference.  coef_im may be NULL;
+ * real_coef = coef_im is NULL or every one of its n_sites entries is zero.  Kinds, geometries and rows are those above.  With
+ * wr = w(s) of coef_re and wi = w(s) of coef_im as defined for EIGENEX_SPIN_SITE_Z above:
+ *   Z            real_coef:  y.re = wr * x.re                   y.im = wr * x.im
+ *                otherwise:  y.re = fma(-wi, x.im, wr * x.re)   y.im = fma(wi, x.re, wr * x.im)
+ *   PLUS, MINUS  y = (0.0, 0.0), then for i ascending over the terms the row has, x being the element the term reads:
+ *                y.re = fma(cr, x.re, y.re);  y.re = fma(-ci, x.im, y.re)   (the second not with real_coef)
+ *                y.im = fma(cr, x.im, y.im);  y.im = fma(ci, x.re, y.im)    (the second not with real_coef)
+ *   norm2 = sum_r |y_r|^2: per row the fma of the real part, then that of the imaginary part (device: fixed-order partial sums).
+ * With real_coef each part of y is eigenex_spin_site_apply's result on that part of x, bit for bit.
+ *   eigenex_spin_site_apply_z       both states are complex spin states (eigenex_spin_upload_z, eigenex_spin_sector_upload_z); a
+ *                                   real state, or one real and one complex, is EIGENEX_ERR_STATE with a message that names
+ *                                   eigenex_spin_site_apply.  Geometries, aliasing (y may be x for Z only), scratch, the one
+ *                                   synchronisation and what is left untouched are those of eigenex_spin_site_apply; a coefficient
+ *                                   of either part that is not finite is refused.
+ *   eigenex_spin_site_apply_host_z  the definition the kernel is held against, in host code: x and y have 2 doubles per row. */
+int eigenex_spin_site_apply_z(eigenex_basis_t src, int x_ref, eigenex_basis_t dst, int y_ref, int kind,
+                              const double* coef_re /* n_sites */, const double* coef_im /* n_sites, or NULL */,
+                              double* norm2 /* or NULL */);
+int eigenex_spin_site_apply_host_z(int n_sites, int n_up_src /* -1: full space */, int kind, const double* coef_re,
+                                   const double* coef_im /* or NULL */, const double* x, double* y, double* norm2);
 /* The reduced density matrix rho_A of a real vector over the rows of a matrix-free spin-1/2 operator, on the device, without
  * downloading the vector: what the entanglement entropy, the Renyi entropies and the entanglement spectrum are taken from.  NOT
  * part of the reference.  The subsystem A is a 32-bit site mask mask_a (bit i = site i); nA = popcount(mask_a), nB = n_sites - nA,
