@@ -109,6 +109,14 @@ SIGNATURES = {
     "eigenex_spin_sector_upload": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
     "eigenex_spin_upload_z": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
     "eigenex_spin_sector_upload_z": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
+    "eigenex_spin_momentum_dim": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _lp]),
+    "eigenex_spin_momentum_states": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
+    "eigenex_spin_momentum_csr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, C.c_int64, C.c_int64, _lp, _ip, _dp, _lp]),
+    "eigenex_spin_momentum_upload": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, C.POINTER(_vp)]),
+    "eigenex_spin_momentum_upload_z": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, C.POINTER(_vp)]),
+    "eigenex_spin_momentum_geometry": (C.c_int, [_vp] + [C.POINTER(C.c_int)] * 4),
+    "eigenex_spin_momentum_expand": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _dp]),
+    "eigenex_spin_momentum_expand_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "eigenex_spin_measure": (C.c_int, [_vp, C.c_int, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_measure_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_measure_host_z": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
@@ -349,6 +357,60 @@ def spin_sector_csr(n_sites: int, n_up: int, bonds, hz=None, hx=None, row_begin:
     col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value, np.float64)
     _chk(lib().eigenex_spin_sector_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), _i(col), _d(val), C.byref(nnz)))
     return rowptr, col, val
+
+
+def _momentum_args(args, n_up, cell, momentum):
+    """the model arguments of _spin_model(hx=None) as the momentum entry points take them: (n_sites, n_up, cell, momentum,
+    n_bonds, site_i, site_j, jz, jxy, hz) -- there is no hx argument"""
+    return (args[0], int(n_up), int(cell), int(momentum), *args[1:-1])
+
+
+def spin_momentum_dim(n_sites: int, n_up: int, momentum: int, cell: int = 1) -> int:
+    """eigenex_spin_momentum_dim: the number of rows of the momentum sector (n_sites, n_up, cell, momentum)"""
+    dim = C.c_int64()
+    _chk(lib().eigenex_spin_momentum_dim(int(n_sites), int(n_up), int(cell), int(momentum), C.byref(dim)))
+    return dim.value
+
+
+def spin_momentum_states(n_sites: int, n_up: int, momentum: int, cell: int = 1, first: int = 0, count: int | None = None):
+    """eigenex_spin_momentum_states: (representatives (uint32, ascending), their periods (uint8)) of rows first .. first + count - 1"""
+    if count is None:
+        count = spin_momentum_dim(n_sites, n_up, momentum, cell) - first
+    states, periods = np.zeros(max(int(count), 0), np.uint32), np.zeros(max(int(count), 0), np.uint8)
+    _chk(lib().eigenex_spin_momentum_states(int(n_sites), int(n_up), int(cell), int(momentum), int(first), int(count),
+                                            states.ctypes.data_as(C.POINTER(C.c_uint32)), periods.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return states, periods
+
+
+def spin_momentum_csr(n_sites: int, n_up: int, momentum: int, bonds, hz=None, cell: int = 1, row_begin: int = 0, n_rows: int | None = None):
+    """eigenex_spin_momentum_csr: rows [row_begin, row_begin + n_rows) of the spin-1/2 Hamiltonian in a momentum sector as CSR
+    (host code, no GPU needed), in the stored order the matrix-free kernel adds them in.  Returns rowptr (int64), col (int32),
+    val (complex128; all imaginary parts are exactly 0 at a real momentum)."""
+    keep, args = _spin_model(n_sites, bonds, hz, None)
+    args = _momentum_args(args, n_up, cell, momentum)
+    nnz = C.c_int64()
+    if n_rows is None:
+        one = np.zeros(1, np.int64)
+        _chk(lib().eigenex_spin_momentum_csr(*args, 0, 0, one.ctypes.data_as(_lp), None, None, C.byref(nnz)))  # the model's own refusal first
+        n_rows = spin_momentum_dim(n_sites, n_up, momentum, cell) - row_begin
+    rowptr = np.zeros(max(int(n_rows), 0) + 1, np.int64)
+    _chk(lib().eigenex_spin_momentum_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), None, None, C.byref(nnz)))
+    col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value, np.complex128)
+    _chk(lib().eigenex_spin_momentum_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), _i(col), _d(val.view(np.float64)), C.byref(nnz)))
+    return rowptr, col, val
+
+
+def spin_momentum_expand_host(n_sites: int, n_up: int, momentum: int, x, cell: int = 1):
+    """eigenex_spin_momentum_expand_host: the Sz-sector vector of the momentum vector x (float64: a real momentum only; complex128
+    else), the definition the device call is held against"""
+    is_complex = np.iscomplexobj(x)
+    x = np.ascontiguousarray(x, np.complex128 if is_complex else np.float64).reshape(-1)
+    if x.size != spin_momentum_dim(n_sites, n_up, momentum, cell):  # the library cannot see the length
+        raise ValueError("x needs one entry per row of the momentum sector")
+    y = np.zeros(spin_sector_dim(n_sites, n_up), x.dtype)
+    _chk(lib().eigenex_spin_momentum_expand_host(int(n_sites), int(n_up), int(cell), int(momentum), int(is_complex), _d(x.view(np.float64)),
+                                                 _d(y.view(np.float64))))
+    return y
 
 
 def _mask_list(masks):
@@ -722,6 +784,20 @@ class Csr:
         return obj
 
     @classmethod
+    def spin_half_momentum(cls, ctx: Context, n_sites: int, n_up: int, momentum: int, bonds, hz=None, cell: int = 1, complex_states=False):
+        """eigenex_spin_momentum_upload: the same Hamiltonian in the momentum sector `momentum` (0 .. n_sites/cell - 1) of the
+        sector of n_up sites up, applied matrix-free.  The model must be invariant under the translation by `cell` sites.  Real
+        states take a real momentum only (0 or half the number of translations); complex_states:
+        eigenex_spin_momentum_upload_z, any momentum.  Every argument is checked before ctx is looked at."""
+        keep, args = _spin_model(n_sites, bonds, hz, None)
+        h = _vp()
+        entry = lib().eigenex_spin_momentum_upload_z if complex_states else lib().eigenex_spin_momentum_upload
+        _chk(entry(ctx.h if ctx is not None else None, *_momentum_args(args, n_up, cell, momentum), C.byref(h)))
+        obj = cls(ctx, h)
+        obj.is_complex = bool(complex_states)
+        return obj
+
+    @classmethod
     def laplacian3d(cls, ctx: Context, n: int):
         h = _vp()
         _chk(lib().eigenex_csr_laplacian3d(ctx.h, n, C.byref(h)))
@@ -730,7 +806,14 @@ class Csr:
     def layout(self) -> str:
         v = C.c_int()
         _chk(lib().eigenex_csr_layout(self.h, C.byref(v)))
-        return ("csr", "column_blocked", "sorted_tiles", "dense_blocks", "split_tiles", "matrix_free_spin", "matrix_free_spin_sector")[v.value]
+        return ("csr", "column_blocked", "sorted_tiles", "dense_blocks", "split_tiles", "matrix_free_spin", "matrix_free_spin_sector",
+                "matrix_free_spin_momentum")[v.value]
+
+    def spin_momentum_geometry(self):
+        """eigenex_spin_momentum_geometry: (n_sites, n_up, cell, momentum) of a momentum-sector operator"""
+        out = [C.c_int() for _ in range(4)]
+        _chk(lib().eigenex_spin_momentum_geometry(self.h, *[C.byref(v) for v in out]))
+        return tuple(v.value for v in out)
 
     def spin_geometry(self):
         """eigenex_spin_geometry: (n_sites, n_up) of a matrix-free spin operator, n_up = None for the full space"""
@@ -908,6 +991,14 @@ class Basis:
         buf[:coef.size] = coef
         norm2 = C.c_double()
         _chk(lib().eigenex_spin_site_apply(self.h, x_ref, dst.h, y_ref, int(kind), _d(buf), C.byref(norm2)))
+        return norm2.value
+
+    def spin_momentum_expand(self, x_ref, dst, y_ref):
+        """eigenex_spin_momentum_expand: vector y_ref of the state dst, on a sector operator of the same (n_sites, n_up), scalar
+        type and context, = the momentum vector x_ref of this state written out in the Sz sector; returns norm2 = |y|^2.  No
+        coefficient, counter or recorded step batch changes."""
+        norm2 = C.c_double()
+        _chk(lib().eigenex_spin_momentum_expand(self.h, x_ref, dst.h, y_ref, C.byref(norm2)))
         return norm2.value
 
     def spin_site_apply_z(self, x_ref, dst, y_ref, kind, coef, imaginary="auto"):

@@ -1924,6 +1924,152 @@ __global__ __launch_bounds__(kBlock) void k_spin_site_apply(const SpinSiteTable*
 }
 
 // ---------------------------------------------------------------------------
+// Matrix-free spin-1/2 operator in a momentum sector (spin_momentum.hpp has the definition, spin_rows.hpp the walk): one row
+// per lane, 256-row tiles, the persistent grid and the pass, shift, u_out, partials and ctrl->stopped conventions of
+// k_spin_spmv<SECTOR, E>.  The lane's state is its representative reps[r], one coalesced load; its period comes from the same
+// orbit walk as the flips'.  The model tables are read by every lane at the same index (scalar loads); ratio, phase and inv_sqrt
+// are indexed per lane and live in LDS (9.5 KB).  reps and bucket are searched per term, `steps` dependent 4-byte gathers
+// inside one bucket, which is a contiguous run of reps.  x is gathered as 8-byte or 16-byte loads, kSpinBatch at a time, all
+// issued before the first product is added.  The sums are those of the CSR row loop over eigenex_spin_momentum_csr's rows:
+// k_spmv's for E = double on val.re at a real momentum, k_spmv_z's for E = SpinZ.
+// ---------------------------------------------------------------------------
+static_assert(kSpinRatioPitch == kMomentumRatioPitch, "spin_rows.hpp indexes ratio with spin_momentum.hpp's pitch");
+struct SpinMomentumLookup {
+  const uint32_t *reps_, *bucket_;
+  __device__ __forceinline__ uint32_t reps(uint32_t i) const { return reps_[i]; }
+  __device__ __forceinline__ uint32_t bucket(uint32_t i) const { return bucket_[i]; }
+};
+struct SpinMomentumLds {  // the workgroup's copy of SpinMomentumTables
+  const double* t;
+  static constexpr int kRatio = 0, kInvSqrt = kMomentumRatioPitch * kMomentumRatioPitch, kPhaseRe = kInvSqrt + kMomentumRatioPitch,
+                       kPhaseIm = kPhaseRe + kMomentumMaxPeriod, kSize = kPhaseIm + kMomentumMaxPeriod;
+  __device__ __forceinline__ double ratio(int i) const { return t[kRatio + i]; }
+  __device__ __forceinline__ double inv_sqrt(int i) const { return t[kInvSqrt + i]; }
+  __device__ __forceinline__ double phase_re(int i) const { return t[kPhaseRe + i]; }
+  __device__ __forceinline__ double phase_im(int i) const { return t[kPhaseIm + i]; }
+};
+static_assert(sizeof(SpinMomentumTables) == sizeof(double) * SpinMomentumLds::kSize, "the LDS copy is the struct, member by member");
+// the caller synchronises
+__device__ __forceinline__ void spin_stage_momentum_tables(const SpinMomentumView* __restrict__ op, double* tab) {
+  const double* src = reinterpret_cast<const double*>(&op->tab);
+  for (int i = threadIdx.x; i < SpinMomentumLds::kSize; i += kBlock) tab[i] = src[i];
+}
+
+template <class E, class... ComplexOnly>
+__global__ __launch_bounds__(kBlock) void k_spin_momentum_spmv(const SpinMomentumView* __restrict__ op, const uint32_t* __restrict__ reps,
+                                                               const uint32_t* __restrict__ bucket,
+                                                               const typename SpinElement<E>::Stored* __restrict__ x_ext,
+                                                               const double* __restrict__ scale_ptr, double shift,
+                                                               SpinShiftIm<ComplexOnly>... shift_im, typename SpinElement<E>::Stored* __restrict__ y,
+                                                               typename SpinElement<E>::Stored* __restrict__ u_out, int64_t n, int64_t ntiles,
+                                                               double* __restrict__ partials, ComplexOnly... pstride, int pass,
+                                                               const Ctrl* __restrict__ ctrl) {
+  static_assert(sizeof...(ComplexOnly) == (std::is_same<E, SpinZ>::value ? 1 : 0), "shift_im and pstride for complex vectors only");
+  constexpr bool COMPLEX = std::is_same<E, SpinZ>::value;
+  __shared__ double lds4[4];
+  __shared__ double tables[SpinMomentumLds::kSize];
+  if (ctrl->stopped) return;
+  spin_stage_momentum_tables(op, tables);
+  __syncthreads();
+  const double scale = scale_ptr ? *scale_ptr : 1.0;
+  bool has_shift = false;  // a complex shift is tested once, here
+  if constexpr (COMPLEX) has_shift = shift != 0.0 || (shift_im + ...) != 0.0;
+  const SpinOperatorView* model = &op->model;
+  const int n_sites = model->n_sites, ndiag = model->ndiag, nflip = model->nflip;
+  const int cell = op->cell, n_trans = op->n_trans, h = op->h, steps = op->steps;
+  const uint32_t compatible = op->compatible;
+  const SpinMomentumLookup lk{reps, bucket};
+  const SpinMomentumLds tb{tables};
+  double dot = 0.0, dot_im = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + threadIdx.x;
+    if (r < n) {
+      const uint32_t s = reps[r];
+      const int period = spin_orbit(s, n_sites, cell, n_trans).period;
+      const double d = spin_row_diagonal(model->dmask, model->dval, ndiag, s);
+      const E xraw = spin_loaded(x_ext[r]);
+      const E xr = spin_scaled(xraw, scale);
+      E yr = spin_momentum_add(E{}, SpinZ{d, 0.0}, xraw, scale);
+      for (int t0 = 0; t0 < nflip; t0 += kSpinBatch) {
+        bool on[kSpinBatch];
+        uint32_t column[kSpinBatch];
+        int ri[kSpinBatch], li[kSpinBatch];
+        E xv[kSpinBatch];
+        spin_momentum_targets(model->fmask + t0, s, period, n_sites, cell, n_trans, compatible, h, steps, lk, on, column, ri, li);
+        spin_momentum_gather(typename SpinElement<E>::Vector{x_ext}, column, xv);
+        yr = spin_momentum_add_flips(yr, model->fval + t0, tb, on, ri, li, xv, scale);
+      }
+      if constexpr (COMPLEX) {
+        if (has_shift) {
+          const double2 t = cmul_nofma(make_double2(shift, (shift_im + ...)), spin_stored(xr));
+          yr.re = yr.re + t.x;
+          yr.im = yr.im + t.y;
+        }
+      } else {
+        if (shift != 0.0) yr = add_product_nofma(yr, shift, xr);  // lanczos.hpp:390-392
+      }
+      y[r] = spin_stored(yr);
+      if (u_out) u_out[r] = spin_stored(xr);
+      if constexpr (COMPLEX) {
+        if (pass & kPassSelfNorm) {
+          dot = fma(yr.re, yr.re, fma(yr.im, yr.im, dot));  // |y|^2
+        } else {
+          dot = fma(xr.re, yr.re, fma(xr.im, yr.im, dot));  // conj(u) * y
+          dot_im = fma(xr.re, yr.im, fma(-xr.im, yr.re, dot_im));
+        }
+      } else {
+        dot = (pass & kPassSelfNorm) ? fma(yr, yr, dot) : fma(xr, yr, dot);
+      }
+    }
+  }
+  if (partials) {
+    dot = block_sum(dot, lds4);
+    if constexpr (COMPLEX) dot_im = block_sum(dot_im, lds4);
+    if (threadIdx.x == 0) {
+      partials[blockIdx.x] = dot;
+      // a norm is one set of partials: its readers have room for one
+      if constexpr (COMPLEX)
+        if (!(pass & kPassSelfNorm)) partials[(pstride + ...) + blockIdx.x] = dot_im;
+    }
+  }
+}
+
+// expand (spin_momentum.hpp): y = the Sz-sector vector of the momentum vector x.  One row of the DESTINATION per lane, unranked
+// with the destination's binomials (dst_op; LDS); the orbit, the lookup, one gather and one product are spin_momentum_expand_row.
+// A lane whose representative does not carry the momentum looks up the sector's first row and writes 0.  norm2 = sum |y_r|^2
+// leaves through block_sum into partials[workgroup]; k_spin_measure_reduce adds those in k_reduce_fin's order.  No atomics.
+// ctrl->stopped is not consulted: this is not a Krylov step.
+template <class E>
+__global__ __launch_bounds__(kBlock) void k_spin_momentum_expand(const SpinMomentumView* __restrict__ op, const SpinSectorView* __restrict__ dst_op,
+                                                                 const uint32_t* __restrict__ reps, const uint32_t* __restrict__ bucket,
+                                                                 const typename SpinElement<E>::Stored* __restrict__ x,
+                                                                 typename SpinElement<E>::Stored* __restrict__ y, int64_t n, int64_t ntiles,
+                                                                 double* __restrict__ partials) {
+  __shared__ double lds4[4];
+  __shared__ double tables[SpinMomentumLds::kSize];
+  __shared__ uint32_t binom[kSectorMaxSites * (kSectorMaxSites + 1)];
+  spin_stage_binomials(dst_op, binom);
+  spin_stage_momentum_tables(op, tables);
+  __syncthreads();
+  const int n_sites = op->model.n_sites, n_up = op->n_up, cell = op->cell, n_trans = op->n_trans, h = op->h, steps = op->steps;
+  const uint32_t compatible = op->compatible, fallback = op->first_rep;
+  const SpinMomentumLookup lk{reps, bucket};
+  const SpinMomentumLds tb{tables};
+  double nrm = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + threadIdx.x;
+    if (r < n) {
+      const uint32_t s = spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s;
+      const E yr = spin_momentum_expand_row(s, n_sites, cell, n_trans, compatible, fallback, h, steps, lk, tb, typename SpinElement<E>::Vector{x}, E{});
+      y[r] = spin_stored(yr);
+      nrm = spin_norm_add(nrm, yr);
+    }
+  }
+  nrm = block_sum(nrm, lds4);
+  if (threadIdx.x == 0) partials[blockIdx.x] = nrm;
+}
+
+// ---------------------------------------------------------------------------
 // The reduced density matrix of one vector (spin_rdm.hpp has the definition, the work table and the slicing rule;
 // spin_rdm_rows.hpp the index arithmetic and the panel shape per element, SpinRdmGeometry): rho_A = M M^H with
 // M[a, b] = x[rank(dep_A(a) | dep_B(b))] never stored.  One workgroup per work item (block k, tile pair (ti, tj <= ti), slice
@@ -3088,6 +3234,29 @@ static void spin_site_apply_launch(hipStream_t s, const SpinSiteTable* table, co
 void launch_spin_site_apply(hipStream_t s, int es, const SpinSiteTable* table, const SpinSectorView* dst_op, const uint32_t* src_lo,
                             const uint32_t* src_hi, const double* x, double* y, int64_t n, double* partials, int grid) {
   (es == 2 ? spin_site_apply_launch<SpinZ> : spin_site_apply_launch<double>)(s, table, dst_op, src_lo, src_hi, x, y, n, partials, grid);
+}
+
+void launch_spin_momentum_spmv(hipStream_t s, int es, const SpinMomentumView* op, const uint32_t* reps, const uint32_t* bucket,
+                               const double* x_ext, const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n,
+                               double* partials, int pstride, int grid, const Ctrl* ctrl, int pass) {
+  const int64_t ntiles = (n + kBlock - 1) / kBlock;
+  if (es == 2)
+    hipLaunchKernelGGL((k_spin_momentum_spmv<SpinZ, int>), dim3(grid), dim3(kBlock), 0, s, op, reps, bucket, spin_elements<SpinZ>(x_ext), scale,
+                       shift_re, shift_im, spin_elements<SpinZ>(y), spin_elements<SpinZ>(u_out), n, ntiles, partials, pstride, pass, ctrl);
+  else
+    hipLaunchKernelGGL((k_spin_momentum_spmv<double>), dim3(grid), dim3(kBlock), 0, s, op, reps, bucket, x_ext, scale, shift_re, y, u_out, n,
+                       ntiles, partials, pass, ctrl);
+}
+
+template <class E>
+static void spin_momentum_expand_launch(hipStream_t s, const SpinMomentumView* op, const SpinSectorView* dst_op, const uint32_t* reps,
+                                        const uint32_t* bucket, const double* x, double* y, int64_t n, double* partials, int grid) {
+  hipLaunchKernelGGL(k_spin_momentum_expand<E>, dim3(grid), dim3(kBlock), 0, s, op, dst_op, reps, bucket, spin_elements<E>(x), spin_elements<E>(y),
+                     n, (n + kBlock - 1) / kBlock, partials);
+}
+void launch_spin_momentum_expand(hipStream_t s, int es, const SpinMomentumView* op, const SpinSectorView* dst_op, const uint32_t* reps,
+                                 const uint32_t* bucket, const double* x, double* y, int64_t n, double* partials, int grid) {
+  (es == 2 ? spin_momentum_expand_launch<SpinZ> : spin_momentum_expand_launch<double>)(s, op, dst_op, reps, bucket, x, y, n, partials, grid);
 }
 
 template <class E>

@@ -9,6 +9,7 @@
 #include "spin_measure.hpp"
 #include "spin_rdm.hpp"
 #include "spin_model.hpp"
+#include "spin_momentum.hpp"
 #include "spin_rows.hpp"
 #include "spin_sector.hpp"
 #include "spin_site.hpp"
@@ -387,6 +388,19 @@ void launch_spin_rdm(hipStream_t s, int es, bool big, const SpinRdmTable* table,
 void launch_spin_rdm_reduce(hipStream_t s, int es, const SpinRdmTable* table, int64_t total, const double* partials, double* out);
 // For an interleaved complex x (es = 2; eigenex_spin_rdm_z) the two stages take the same table and items; partials and out hold
 // (re, im) pairs at the same indices, so 2 * part_total and 2 * total doubles, 16-byte aligned like x.
+// Matrix-free spin-1/2 operator in a momentum sector (eigenex_spin_momentum_upload; spin_momentum.hpp has the definition,
+// spin_rows.hpp the walk): row r is the representative reps[r], its diagonal entry followed by the bond flips whose orbit carries
+// the momentum, in table order -- the rows eigenex_spin_momentum_csr writes, so bit-identical to k_spmv (es = 1, a real momentum,
+// val.re) or k_spmv_z (es = 2) on that CSR.  op, reps (n entries) and bucket live in device memory.  The contract of
+// launch_spin_spmv / launch_spin_spmv_z; pstride is read for es = 2 only.
+void launch_spin_momentum_spmv(hipStream_t s, int es, const SpinMomentumView* op, const uint32_t* reps, const uint32_t* bucket,
+                               const double* x_ext, const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n,
+                               double* partials, int pstride, int grid, const Ctrl* ctrl, int pass = 0);
+// expand (eigenex_spin_momentum_expand): y, the n = C(n_sites, n_up) rows of the sector operator whose view dst_op is, from the
+// momentum vector x on the rows of op.  The grid's partial sums of |y_r|^2 go to partials[workgroup]; second stage as for
+// launch_spin_site_apply.  Always runs.
+void launch_spin_momentum_expand(hipStream_t s, int es, const SpinMomentumView* op, const SpinSectorView* dst_op, const uint32_t* reps,
+                                 const uint32_t* bucket, const double* x, double* y, int64_t n, double* partials, int grid);
 // host-operator path: u_out = x*scale
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,
                   const Ctrl* ctrl);

@@ -287,6 +287,17 @@ struct SpinShard {
   bool on() const { return n_sites > 0; }
 };
 
+// A matrix-free spin-1/2 operator in a momentum sector on its shard (spin_momentum.hpp): the kernels' view, the ascending list of
+// representatives (one per row) and the bucket table of the search.  Not a SpinShard: a row is an orbit, not a state, so the
+// calls that read states off the rows (eigenex_spin_geometry, _measure, _rdm, _site_apply) must keep refusing the handle.
+struct SpinMomentumShard {
+  DeviceBuffer<SpinMomentumView> view;
+  DeviceBuffer<uint32_t> reps, bucket;
+  int64_t table_words = 0;  // entries of reps and bucket together
+  int n_sites = 0, n_up = 0, cell = 0, momentum = 0;
+  bool on() const { return n_sites > 0; }
+};
+
 struct CsrShard {
   int gshard = 0;
   int64_t rb = 0, re = 0, nloc = 0, npad = 0, nnz = 0, nhalo = 0;
@@ -333,6 +344,8 @@ struct CsrShard {
   // matrix-free spin-1/2 operator (eigenex_spin_upload, eigenex_spin_sector_upload) instead of any stored form: nnz = 0, no
   // halo, one pass
   SpinShard spin;
+  // ... in a momentum sector (eigenex_spin_momentum_upload): the same, and spin.on() stays false
+  SpinMomentumShard momentum;
   std::vector<Segment> recv, send;
   DeviceBuffer<int32_t> send_idx;  // concatenated local row indices
   DeviceBuffer<double> sendbuf;
@@ -1593,6 +1606,7 @@ double operator_bytes(const CsrShard* m, int es) {
   if (m->rc_rec) return (double)m->rc_bytes * row_code_rows(m->nloc) + 8.0 * m->rc_npal;
   if (m->blocked) return 8.0 * es * m->nnz + 4.0 * m->nstripcols + 4.0 * m->nloc;
   if (m->spin.on()) return m->spin.n_up >= 0 ? (double)sizeof(SpinSectorView) + 4.0 * m->spin.table_words : (double)sizeof(SpinOperatorView);
+  if (m->momentum.on()) return (double)sizeof(SpinMomentumView) + 4.0 * m->momentum.table_words;
   return csr_bytes(m, es);
 }
 // long rows (16 stored entries per row or more on average): the CSR kernels have a variant for them (kSpmvLongRows) and
@@ -1643,7 +1657,7 @@ void launch_csr_one_pass(hipStream_t st, const BasisShard& s, const OperatorPass
 void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p) {
   const CsrShard* m = s.csr;
   const int es = s.es, grid = s.g_spmv;
-  if (m->tiles_split && !m->split && !m->sorted && !m->blocked && !m->spin.on() && m->passes == 1 && es == 1) {
+  if (m->tiles_split && !m->split && !m->sorted && !m->blocked && !m->spin.on() && !m->momentum.on() && m->passes == 1 && es == 1) {
     // (tile lists exist between shards only, the InlineFin / InlineArnoldiBegin hooks on one shard only: none is set here)
     const int g_int = s.g_spmv_int, g_bnd = grid - g_int;
     if (m->n_tile_int > 0 && g_int > 0) launch_csr_one_pass(st, s, p, g_int, p.partials, {m->tile_int, m->n_tile_int});
@@ -1683,6 +1697,11 @@ void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p)
                        p.pass_flags);
     return;
   }
+  if (m->momentum.on()) {
+    launch_spin_momentum_spmv(st, es, m->momentum.view, m->momentum.reps, m->momentum.bucket, p.x, p.scale, p.shift, p.shift_im, p.y, p.u_out,
+                              m->nloc, p.partials, s.pstride, grid, p.ctrl, p.pass_flags);
+    return;
+  }
   if (m->rc_rec || (m->passes == 1 && es == 1)) {
     launch_csr_one_pass(st, s, p, grid, p.partials);
     return;
@@ -1703,7 +1722,7 @@ void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p)
 // Does this shard's operator kernel take a Chebyshev step in its epilogue?  The kernels behind launch_csr_one_pass.
 inline bool filter_in_epilogue(const BasisShard& s) {
   const CsrShard* m = s.csr;
-  return s.es == 1 && !m->split && !m->sorted && !m->blocked && !m->spin.on() && (m->rc_rec || m->passes == 1);
+  return s.es == 1 && !m->split && !m->sorted && !m->blocked && !m->spin.on() && !m->momentum.on() && (m->rc_rec || m->passes == 1);
 }
 
 // acc = p(A) x with the state's Chebyshev filter, x = w*scale (the operator input, as for an operator application): `degree`
@@ -1803,7 +1822,7 @@ bool inline_begin_ok(const eigenex_basis_s* b) {
   if (!b->csr || !decides_locally(b) || b->sh.size() != 1) return false;
   static const bool off = std::getenv("EIGENEX_NO_INLINE_FIN") != nullptr;
   const CsrShard& m = b->csr->sh[0];
-  return !off && b->es == 1 && !m.blocked && !m.sorted && !m.spin.on() && (m.split || m.passes == 1);
+  return !off && b->es == 1 && !m.blocked && !m.sorted && !m.spin.on() && !m.momentum.on() && (m.split || m.passes == 1);
 }
 
 // The scalar an operator application forms besides v, and where it goes.  Alpha: u.v, all-reduced into hbuf[slot_alpha].
@@ -1956,7 +1975,7 @@ inline bool inlines_fin(const eigenex_basis_s* b) {
   static const bool off = std::getenv("EIGENEX_NO_INLINE_FIN") != nullptr;
   if (off || !decides_locally(b) || !b->csr || b->es != 1 || b->f_degree > 0) return false;  // (a filtered state applies p(A) in many launches)
   const CsrShard& m = b->csr->sh[0];
-  return !m.blocked && !m.sorted && !m.split && !m.spin.on() && m.passes == 1 && (b->ortho_mode == EIGENEX_ORTHO_BATCHED || b->ortho_mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE);
+  return !m.blocked && !m.sorted && !m.split && !m.spin.on() && !m.momentum.on() && m.passes == 1 && (b->ortho_mode == EIGENEX_ORTHO_BATCHED || b->ortho_mode == EIGENEX_ORTHO_BATCHED_ADAPTIVE);
 }
 
 // the same passes as the general step, with the hand-overs as hooks: no second-stage launch for the norm or for alpha
@@ -3151,6 +3170,173 @@ int eigenex_spin_geometry(eigenex_csr_t m, int* n_sites, int* n_up) {
   return 0;
 }
 
+// ---- momentum sectors (spin_momentum.hpp) ----
+static BasisShard* spin_state_shard(eigenex_basis_t b);
+// the checks every entry point shares, before anything is built: the geometry, then (with a model) Sz and translation invariance
+static int spin_momentum_check(const std::string& who, int n_sites, int n_up, int cell, int momentum, const SpinModelArgs* a) {
+  const std::string geo = spin_momentum_geometry_error(n_sites, n_up, cell, momentum);
+  if (!geo.empty()) return fail(EIGENEX_ERR_ARG, who + ": " + geo);
+  if (a) {
+    const std::string why = spin_momentum_model_error(*a, n_up, cell);
+    if (!why.empty()) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  }
+  return 0;
+}
+static int spin_momentum_empty(const std::string& who) {
+  return fail(EIGENEX_ERR_ARG, who + ": the sector is empty: no orbit of this magnetisation has a period that carries this momentum");
+}
+
+int eigenex_spin_momentum_dim(int n_sites, int n_up, int cell, int momentum, int64_t* dim) {
+  if (!dim) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_dim: dim is NULL");
+  CHK(spin_momentum_check("eigenex_spin_momentum_dim", n_sites, n_up, cell, momentum, nullptr));
+  const int64_t n = spin_momentum_build_basis(n_sites, n_up, cell, momentum, nullptr);
+  if (n == 0) return spin_momentum_empty("eigenex_spin_momentum_dim");
+  *dim = n;
+  return 0;
+}
+
+int eigenex_spin_momentum_states(int n_sites, int n_up, int cell, int momentum, int64_t first, int64_t count, uint32_t* states,
+                                 uint8_t* periods_or_null) {
+  CHK(spin_momentum_check("eigenex_spin_momentum_states", n_sites, n_up, cell, momentum, nullptr));
+  SpinMomentumBasis b;
+  if (spin_momentum_build_basis(n_sites, n_up, cell, momentum, &b) == 0) return spin_momentum_empty("eigenex_spin_momentum_states");
+  if (first < 0 || count < 0 || first + count > (int64_t)b.reps.size()) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_states: rows outside 0..dim");
+  if (count > 0 && !states) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_states: states is NULL");
+  for (int64_t k = 0; k < count; ++k) {
+    states[k] = b.reps[(size_t)(first + k)];
+    if (periods_or_null) periods_or_null[k] = b.period[(size_t)(first + k)];
+  }
+  return 0;
+}
+
+int eigenex_spin_momentum_csr(int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                              const double* jz, const double* jxy, const double* hz_or_null, int64_t row_begin, int64_t n_rows, int64_t* rowptr,
+                              int32_t* col, double* val, int64_t* nnz) {
+  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, nullptr};
+  CHK(spin_momentum_check("eigenex_spin_momentum_csr", n_sites, n_up, cell, momentum, &a));
+  if (!rowptr || !nnz || (col == nullptr) != (val == nullptr))
+    return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_csr: rowptr and nnz are needed, col and val together or neither");
+  SpinMomentumBasis b;
+  if (spin_momentum_build_basis(n_sites, n_up, cell, momentum, &b) == 0) return spin_momentum_empty("eigenex_spin_momentum_csr");
+  if (row_begin < 0 || n_rows < 0 || row_begin + n_rows > (int64_t)b.reps.size()) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_csr: rows outside 0..dim");
+  std::unique_ptr<SpinMomentumTables> t(new SpinMomentumTables());
+  spin_momentum_build_tables(b.n_trans, momentum, *t);
+  spin_momentum_write_rows(a, b, *t, row_begin, n_rows, rowptr, col, val, nnz);
+  return 0;
+}
+
+static int spin_momentum_upload(const std::string& who, int es, eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds,
+                                const int32_t* site_i, const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null,
+                                eigenex_csr_t* out) {
+  // every argument check before the context is touched
+  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, nullptr};
+  CHK(spin_momentum_check(who, n_sites, n_up, cell, momentum, &a));
+  if (es == 1 && !spin_momentum_is_real(n_sites / cell, momentum))
+    return fail(EIGENEX_ERR_ARG, who + ": real states take a real momentum only (0 or half the number of translations); this one has complex matrix "
+                                       "elements and needs complex states (eigenex_spin_momentum_upload_z)");
+  if (!c || !out) return fail(EIGENEX_ERR_ARG, who + ": NULL argument");
+  if (c->P != 1)
+    return fail(EIGENEX_ERR_ARG, who + ": a matrix-free spin operator needs a context with one shard in total; sharding it takes an "
+                                       "exchange of whole vectors for the bonds on the top bits, which is not built");
+  SpinMomentumBasis b;
+  if (spin_momentum_build_basis(n_sites, n_up, cell, momentum, &b) == 0) return spin_momentum_empty(who);
+  HIPCHK(hipSetDevice(c->device));
+  std::unique_ptr<eigenex_csr_s> m(new eigenex_csr_s());
+  m->ctx = c;
+  m->n_global = (int64_t)b.reps.size();
+  m->es = es;
+  m->sh.resize(1);
+  CsrShard& s = m->sh[0];
+  s.gshard = c->local[0];
+  s.momentum.n_sites = n_sites, s.momentum.n_up = n_up, s.momentum.cell = cell, s.momentum.momentum = momentum;
+  partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
+  s.nloc = s.re - s.rb;
+  s.npad = pad_rows(s.nloc);
+  std::unique_ptr<SpinMomentumView> v(new SpinMomentumView());  // staging buffers: they live until the synchronise below
+  spin_momentum_build_view(a, b, *v);
+  s.momentum.table_words = (int64_t)(b.reps.size() + b.bucket.size());
+  HIPCHK(s.momentum.reps.alloc(b.reps.size()));
+  HIPCHK(s.momentum.bucket.alloc(b.bucket.size()));
+  HIPCHK(s.momentum.view.alloc(1));
+  HIPCHK(hipMemcpyAsync(s.momentum.reps, b.reps.data(), 4 * b.reps.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.momentum.bucket, b.bucket.data(), 4 * b.bucket.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.momentum.view, v.get(), sizeof(SpinMomentumView), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *out = m.release();
+  return 0;
+}
+
+int eigenex_spin_momentum_upload(eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
+                                 const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, eigenex_csr_t* out) {
+  return spin_momentum_upload("eigenex_spin_momentum_upload", 1, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy, hz_or_null, out);
+}
+
+int eigenex_spin_momentum_upload_z(eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
+                                   const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, eigenex_csr_t* out) {
+  return spin_momentum_upload("eigenex_spin_momentum_upload_z", 2, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy, hz_or_null, out);
+}
+
+int eigenex_spin_momentum_geometry(eigenex_csr_t m, int* n_sites, int* n_up, int* cell, int* momentum) {
+  if (!m) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_geometry: NULL argument");
+  if (m->sh.empty() || !m->sh[0].momentum.on())
+    return fail(EIGENEX_ERR_STATE, "eigenex_spin_momentum_geometry: the operator is not a matrix-free spin operator in a momentum sector");
+  const SpinMomentumShard& k = m->sh[0].momentum;
+  if (n_sites) *n_sites = k.n_sites;
+  if (n_up) *n_up = k.n_up;
+  if (cell) *cell = k.cell;
+  if (momentum) *momentum = k.momentum;
+  return 0;
+}
+
+int eigenex_spin_momentum_expand_host(int n_sites, int n_up, int cell, int momentum, int is_complex, const double* x, double* y) {
+  CHK(spin_momentum_check("eigenex_spin_momentum_expand_host", n_sites, n_up, cell, momentum, nullptr));
+  if (!is_complex && !spin_momentum_is_real(n_sites / cell, momentum))
+    return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_expand_host: a real vector takes a real momentum only (0 or half the number of translations)");
+  if (!x || !y) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_expand_host: x or y is NULL");
+  SpinMomentumBasis b;
+  if (spin_momentum_build_basis(n_sites, n_up, cell, momentum, &b) == 0) return spin_momentum_empty("eigenex_spin_momentum_expand_host");
+  std::unique_ptr<SpinMomentumTables> t(new SpinMomentumTables());
+  spin_momentum_build_tables(b.n_trans, momentum, *t);
+  spin_momentum_expand_host(b, *t, is_complex != 0, x, y);
+  return 0;
+}
+
+int eigenex_spin_momentum_expand(eigenex_basis_t src, int x_ref, eigenex_basis_t dst, int y_ref, double* norm2) {
+  const std::string who = "eigenex_spin_momentum_expand";
+  if (!src || !dst) return fail(EIGENEX_ERR_ARG, who + ": a state is NULL");
+  CHK(enter_settled(src));
+  CHK(enter_settled(dst));
+  if (!src->csr || src->sh.size() != 1 || !src->sh[0].csr || !src->sh[0].csr->momentum.on())
+    return fail(EIGENEX_ERR_STATE, who + ": the operator of the source state is not a momentum-sector operator (eigenex_spin_momentum_upload)");
+  BasisShard* sdp = spin_state_shard(dst);
+  if (!sdp || sdp->csr->spin.n_up < 0)
+    return fail(EIGENEX_ERR_STATE, who + ": the operator of the destination state is not a sector operator (eigenex_spin_sector_upload)");
+  BasisShard &ss = src->sh[0], &sd = *sdp;
+  const SpinMomentumShard& mk = ss.csr->momentum;
+  const SpinShard& md = sd.csr->spin;
+  if (mk.n_sites != md.n_sites || mk.n_up != md.n_up)
+    return fail(EIGENEX_ERR_STATE, who + ": the momentum sector and the destination sector differ in n_sites or n_up");
+  if (src->es != dst->es) return fail(EIGENEX_ERR_STATE, who + ": the two states differ in scalar type (one real, one complex)");
+  if (src->ctx != dst->ctx) return fail(EIGENEX_ERR_STATE, who + ": the two states live on different contexts");
+  const double* x = vec_ptr(ss, src->cap, src->nq, x_ref);
+  double* y = vec_ptr(sd, dst->cap, dst->nq, y_ref);
+  if (!x || !y) return fail(EIGENEX_ERR_ARG, "bad vector reference");
+  eigenex_context_s* c = dst->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  // scratch of this call alone: the grid's partial sums and norm2.  The states' own partials may hold a pending alpha.
+  const int grid = sd.g_spmv;
+  DeviceBuffer<double> d_part, d_out;
+  double out = 0.0;
+  HIPCHK(d_part.alloc((size_t)grid));
+  HIPCHK(d_out.alloc(1));
+  launch_spin_momentum_expand(c->stream, dst->es, mk.view, md.view, mk.reps, mk.bucket, x, y, sd.nloc, d_part, grid);
+  launch_spin_measure_reduce(c->stream, d_part, grid, grid, 0, 0, nullptr, nullptr, d_out);
+  HIPCHK(hipMemcpyAsync(&out, d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the scratch lives until here
+  if (norm2) *norm2 = out;
+  return 0;
+}
+
 // the argument checks of the two host evaluations, then `host`: spin_measure_host or spin_measure_host_z, the definitions
 static int spin_measure_host_call(const std::string& who, decltype(&spin_measure_host) host, int n_sites, int n_up, const double* x, int n_diag,
                                   const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks, double* diag_out, double* flip_out,
@@ -3397,6 +3583,7 @@ int eigenex_csr_layout(eigenex_csr_t m, int* layout) {
   for (auto& s : m->sh) {
     if (s.blocked) *layout = EIGENEX_LAYOUT_DENSE_BLOCKS;
     else if (s.spin.on()) *layout = s.spin.n_up >= 0 ? EIGENEX_LAYOUT_MATRIX_FREE_SPIN_SECTOR : EIGENEX_LAYOUT_MATRIX_FREE_SPIN;
+    else if (s.momentum.on()) *layout = EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM;
     else if (s.split) *layout = EIGENEX_LAYOUT_SPLIT_TILES;
     else if (s.sorted) *layout = EIGENEX_LAYOUT_SORTED_TILES;
     else if (s.passes > 1 && *layout == EIGENEX_LAYOUT_CSR) *layout = EIGENEX_LAYOUT_COLUMN_BLOCKED;

@@ -1,7 +1,8 @@
 // The row walk of the matrix-free spin-1/2 kernels (kernels.hip: k_spin_spmv<SECTOR, E> and k_spin_measure<SECTOR, E>, each
 // written once for real (E = double) and complex (E = SpinZ) vectors, as k_spin_site_apply<SECTOR, E> is, and through spin_rdm_rows.hpp
-// k_spin_rdm<SECTOR, TILE, E>), shared by the device code and by the host replays
-// tests/cpp/spin_{model,sector,measure,site,site_z,rdm,rdm_z,complex}_sanitize.cpp, which run it under AddressSanitizer +
+// k_spin_rdm<SECTOR, TILE, E>; at the end of this file the walk of k_spin_momentum_spmv<E> and k_spin_momentum_expand<E>), shared by
+// the device code and by the host replays
+// tests/cpp/spin_{model,sector,measure,site,site_z,rdm,rdm_z,complex,momentum}_sanitize.cpp, which run it under AddressSanitizer +
 // UBSan.  The kernels and the replays call THESE functions, so what a replay proves about them (every load inside its array, the
 // state equal to spin_sector_unrank, the sums equal to the CSR row loop and to spin_measure_host bit for bit) holds for the
 // kernels' rows as compiled.  No device construct in here: plain C++11.  spin_write_rows, spin_sector_unrank, spin_sector_rank
@@ -244,6 +245,137 @@ EIGENEX_HD double spin_site_product(double w, bool, double x) { return w * x; }
 EIGENEX_HD SpinZ spin_site_product(SpinZ w, bool real_coef, SpinZ x) {
   if (real_coef) return SpinZ{w.re * x.re, w.re * x.im};
   return SpinZ{std::fma(-w.im, x.im, w.re * x.re), std::fma(w.im, x.re, w.re * x.im)};
+}
+
+// ---- a momentum sector (spin_momentum.hpp; kernels.hip: k_spin_momentum_spmv<E> and k_spin_momentum_expand<E>) ----
+// One row per lane; the lane's state is its representative reps[r], a coalesced load of the caller.  A bond flip s' = a ^ mask
+// leaves the list of representatives, so phase 1 (spin_momentum_targets) runs the orbit of s' -- all n_trans rotations on every
+// lane, no early exit: the trip count is the same for the whole wave -- and looks the representative up (spin_momentum_index).
+// The search is a lower bound with the trip count `steps` of the upload, branch-free, in the bucket of the state's high bits.
+// Every state it is given is a row of the sector, so the bucket is not empty and every probe lies inside it.  A lane without
+// the term (the spins of the bond are equal, or the period of s' does not carry the momentum) searches for its own row's state
+// under the rule of spin_flip_targets: no load is branched around.  The coefficient of a term is fval * ratio[ri] * phase[li],
+// each product rounded (spin_momentum_value); ri = R_a * kMomentumRatioPitch + R_s' and li = (N - j*) mod N are valid table
+// indices on every lane.  Phase 3 is the product form of the plain CSR kernels, so that an application equals the CSR upload of
+// spin_momentum_write_rows' rows bit for bit: real  yr = add_product_nofma(yr, value.re, xv * scale);  complex  p =
+// spin_cmul_nofma(value, x * scale), yr.re += p.re, yr.im += p.im, the diagonal (d, 0) included: k_spmv_z's stored-order sum.
+// lk.reps(i) and lk.bucket(i) are the two arrays; tb.ratio(i), tb.phase_re(i), tb.phase_im(i), tb.inv_sqrt(i) the tables.
+constexpr int kSpinRatioPitch = kSectorMaxSites + 1;  // spin_momentum.hpp: kMomentumRatioPitch
+
+EIGENEX_HD uint32_t spin_rotate(uint32_t s, int n_sites, int cell, uint32_t site_mask) {
+  return ((s << cell) | (s >> (n_sites - cell))) & site_mask;  // both shifts are 1..31: cell <= n_sites / 2
+}
+
+// the representative of the orbit of s, the smallest j >= 0 with T^j s = rep and the period: n_trans rotations, always
+struct SpinOrbit {
+  uint32_t rep;
+  int j, period;
+};
+EIGENEX_HD SpinOrbit spin_orbit(uint32_t s, int n_sites, int cell, int n_trans) {
+  const uint32_t site_mask = 0xffffffffu >> (32 - n_sites);
+  SpinOrbit o = {s, 0, n_trans};
+  uint32_t t = s;
+  bool closed = false;
+  for (int r = 1; r <= n_trans; ++r) {
+    t = spin_rotate(t, n_sites, cell, site_mask);
+    const bool smaller = t < o.rep;  // strictly: the first of equal rotations stays
+    o.rep = smaller ? t : o.rep;
+    o.j = smaller ? r : o.j;
+    const bool first_return = !closed && t == s;
+    o.period = first_return ? r : o.period;
+    closed = closed || first_return;
+  }
+  return o;
+}
+
+// idx(b) of a representative b of the sector: the lower bound of b in its bucket, `steps` probes
+template <class Lookup>
+EIGENEX_HD uint32_t spin_momentum_index(const Lookup& lk, uint32_t b, int h, int steps) {
+  uint32_t base = lk.bucket(b >> h);
+  uint32_t n = lk.bucket((b >> h) + 1) - base;  // >= 1: b is in there
+  for (int i = 0; i < steps; ++i) {
+    const uint32_t half = n >> 1;
+    const uint32_t v = lk.reps(base + (half ? half - 1 : 0));
+    base += (half && v < b) ? half : 0u;
+    n -= half;
+  }
+  return base;
+}
+
+// phase 1 of a batch of bond masks on the row of representative s with period `period`
+template <class Lookup>
+EIGENEX_HD void spin_momentum_targets(const uint32_t* mask, uint32_t s, int period, int n_sites, int cell, int n_trans, uint32_t compatible, int h,
+                                      int steps, const Lookup& lk, bool* on, uint32_t* column, int* ri, int* li) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) {
+    const uint32_t m = mask[t];
+    const bool flips = __builtin_popcount(s & m) == 1;  // two-bit masks only; a zero mask (padding) never
+    const SpinOrbit o = spin_orbit(flips ? s ^ m : s, n_sites, cell, n_trans);
+    on[t] = flips && ((compatible >> (o.period - 1)) & 1u) != 0;
+    column[t] = spin_momentum_index(lk, on[t] ? o.rep : s, h, steps);
+    ri[t] = period * kSpinRatioPitch + o.period;
+    li[t] = o.j == 0 ? 0 : n_trans - o.j;
+  }
+}
+
+// phase 2
+template <class Vector, class E>
+EIGENEX_HD void spin_momentum_gather(const Vector& x, const uint32_t* column, E* xv) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) xv[t] = x(column[t]);
+}
+
+// a * b of two complex numbers as a plain C multiply without contraction (kernels.hip: cmul_nofma)
+EIGENEX_HD SpinZ spin_cmul_nofma(SpinZ a, SpinZ b) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double rr = a.re * b.re, ii = a.im * b.im, ri = a.re * b.im, ir = a.im * b.re;
+  return SpinZ{rr - ii, ri + ir};
+}
+
+// the stored value of a term: c = fval * ratio, then (c * phase.re, c * phase.im)
+EIGENEX_HD SpinZ spin_momentum_value(double fval, double ratio, double phase_re, double phase_im) {
+  const double c = fval * ratio;
+  return SpinZ{c * phase_re, c * phase_im};
+}
+
+// one stored entry of a row added to its sum
+EIGENEX_HD double spin_momentum_add(double yr, SpinZ value, double x, double scale) { return add_product_nofma(yr, value.re, x * scale); }
+EIGENEX_HD SpinZ spin_momentum_add(SpinZ yr, SpinZ value, SpinZ x, double scale) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const SpinZ p = spin_cmul_nofma(value, spin_scaled(x, scale));
+  return SpinZ{yr.re + p.re, yr.im + p.im};
+}
+
+// phase 3, in table order
+template <class Tables, class E>
+EIGENEX_HD E spin_momentum_add_flips(E yr, const double* fval, const Tables& tb, const bool* on, const int* ri, const int* li, const E* xv,
+                                     double scale) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t)
+    if (on[t]) yr = spin_momentum_add(yr, spin_momentum_value(fval[t], tb.ratio(ri[t]), tb.phase_re(li[t]), tb.phase_im(li[t])), xv[t], scale);
+  return yr;
+}
+
+// expand (spin_momentum.hpp), one row of the DESTINATION (the Sz sector) per lane: the orbit of the lane's state s, the lookup of
+// its representative -- `fallback`, the sector's first row, where the representative does not carry the momentum -- one gather and
+// one product.  x * phase is the plain complex multiply (of a real vector x * phase.re), then each part times inv_sqrt[R].
+EIGENEX_HD double spin_momentum_expanded(double x, double phase_re, double, double w) { return (x * phase_re) * w; }
+EIGENEX_HD SpinZ spin_momentum_expanded(SpinZ x, double phase_re, double phase_im, double w) {
+  const SpinZ p = spin_cmul_nofma(x, SpinZ{phase_re, phase_im});
+  return SpinZ{p.re * w, p.im * w};
+}
+template <class Lookup, class Tables, class Vector, class E>
+EIGENEX_HD E spin_momentum_expand_row(uint32_t s, int n_sites, int cell, int n_trans, uint32_t compatible, uint32_t fallback, int h, int steps,
+                                      const Lookup& lk, const Tables& tb, const Vector& x, E zero) {
+  const SpinOrbit o = spin_orbit(s, n_sites, cell, n_trans);
+  const bool on = ((compatible >> (o.period - 1)) & 1u) != 0;
+  const E xv = x(spin_momentum_index(lk, on ? o.rep : fallback, h, steps));
+  const int l = o.j == 0 ? 0 : n_trans - o.j;
+  return on ? spin_momentum_expanded(xv, tb.phase_re(l), tb.phase_im(l), tb.inv_sqrt(o.period)) : zero;
 }
 
 }  // namespace eigenex

@@ -13,8 +13,15 @@
 // up, ascending, C(L, nUp) of them (L up to 32 here).  sectorRows / sectorStates / toSectorCsr describe one sector on the host,
 // device::spinHalfSectorOperator applies it matrix-free (eigenex_spin_sector_upload).  Within a sector the SU(2) multiplets of
 // the full space no longer repeat, so "the lowest k levels" can be asked of a Lanczos solver with one start vector.
+//
+// A model that is also invariant under the translation by `cell` sites splits further, into the L / cell momentum sectors of each
+// Sz sector: the orbits of the translation, one row each, about L / cell times fewer rows.  translationInvariant /
+// momentumDimension / momentumStates / toMomentumCsr describe one on the host, device::spinHalfMomentumOperator applies it
+// matrix-free (eigenex_spin_momentum_upload).  Momentum 0 and half the number of translations are real symmetric and take real
+// states; every other momentum is complex Hermitian and needs complex states.
 #pragma once
 
+#include <complex>
 #include <limits>
 
 #include "device.hpp"
@@ -107,6 +114,54 @@ class SpinHalfModel {
     return m;
   }
 
+  // Is the model invariant under the translation by `cell` sites and free of a transverse field, i.e. does it have momentum
+  // sectors of that cell?  (eigenex_last_error says which bond or site breaks the symmetry.)
+  bool translationInvariant(int cell = 1) const {
+    for (double h : hx_)
+      if (h != 0.0) return false;
+    std::int64_t rp[1] = {0}, nnz = 0;
+    return eigenex_spin_momentum_csr(sites_, 0, cell, 0, bonds(), siteI(), siteJ(), jz(), jxy(), fieldZ(), 0, 0, rp, nullptr, nullptr, &nnz) == 0;
+  }
+  // the momentum sector m (0 .. sites / cell - 1) of the sector of nUp sites up: its dimension, its representatives in ascending
+  // order with their periods, and rows [row_begin, row_end) as CSR (values complex; all real at m = 0 and 2 m = sites / cell)
+  Index momentumDimension(int nUp, int cell, int m) const {
+    std::int64_t dim = 0;
+    device::check(eigenex_spin_momentum_dim(sites_, nUp, cell, m, &dim), "eigenex_spin_momentum_dim");
+    return static_cast<Index>(dim);
+  }
+  std::vector<std::uint32_t> momentumStates(int nUp, int cell, int m, std::vector<std::uint8_t>* periods = nullptr) const {
+    std::vector<std::uint32_t> s(static_cast<std::size_t>(momentumDimension(nUp, cell, m)), 0u);
+    if (periods) periods->assign(s.size(), 0);
+    device::check(eigenex_spin_momentum_states(sites_, nUp, cell, m, 0, static_cast<std::int64_t>(s.size()), s.data(), periods ? periods->data() : nullptr),
+                  "eigenex_spin_momentum_states");
+    return s;
+  }
+  HostCsr<std::complex<double>> toMomentumCsr(int nUp, int cell, int m, Index row_begin = 0, Index row_end = -1) const {
+    requireNoTransverseField("SpinHalfModel::toMomentumCsr");
+    HostCsr<std::complex<double>> out;
+    out.n = momentumDimension(nUp, cell, m);
+    if (row_end < 0) row_end = out.n;
+    std::vector<std::int64_t> rp(static_cast<std::size_t>(row_end > row_begin ? row_end - row_begin : 0) + 1, 0);
+    std::int64_t nnz = 0;
+    device::check(eigenex_spin_momentum_csr(sites_, nUp, cell, m, bonds(), siteI(), siteJ(), jz(), jxy(), fieldZ(), row_begin, row_end - row_begin,
+                                            rp.data(), nullptr, nullptr, &nnz),
+                  "eigenex_spin_momentum_csr");
+    if (nnz > static_cast<std::int64_t>(std::numeric_limits<std::int32_t>::max()))
+      throw LanczosException("SpinHalfModel::toMomentumCsr: more than 2^31 - 1 stored entries (use device::spinHalfMomentumOperator, or fewer rows)");
+    out.col.assign(static_cast<std::size_t>(nnz), 0);
+    out.val.assign(static_cast<std::size_t>(nnz), std::complex<double>(0.0, 0.0));
+    device::check(eigenex_spin_momentum_csr(sites_, nUp, cell, m, bonds(), siteI(), siteJ(), jz(), jxy(), fieldZ(), row_begin, row_end - row_begin,
+                                            rp.data(), out.col.data(), reinterpret_cast<double*>(out.val.data()), &nnz),
+                  "eigenex_spin_momentum_csr");
+    out.rowptr.assign(rp.begin(), rp.end());
+    return out;
+  }
+  // the momentum entry points take no transverse field: one that is set and not zero is an error here, not silently dropped
+  void requireNoTransverseField(const char* who) const {
+    for (double h : hx_)
+      if (h != 0.0) throw LanczosException(std::string(who) + ": a transverse field (hx != 0) does not conserve Sz: the model has no momentum sector");
+  }
+
  private:
   SpinHalfModel& setField(std::vector<double>& h, int site, double value) {
     if (site < 0 || site >= sites_) throw LanczosException("SpinHalfModel: site index out of range");
@@ -151,6 +206,25 @@ inline std::shared_ptr<CsrOperator> spinHalfComplexOperator(std::shared_ptr<Cont
     check(eigenex_spin_sector_upload_z(ctx->handle(), model.sites(), nUp, model.bonds(), model.siteI(), model.siteJ(), model.jz(),
                                        model.jxy(), model.fieldZ(), model.fieldX(), &h),
           "eigenex_spin_sector_upload_z");
+  return CsrOperator::adopt(std::move(ctx), h);
+}
+
+// the model in the momentum sector m of the sector of nUp sites up, under the translation by `cell` sites, matrix-free
+// (eigenex_spin_momentum_upload; complexStates: eigenex_spin_momentum_upload_z).  Real states take m = 0 and 2 m = sites / cell
+// only: any other momentum throws unless complexStates is set.  LanczosEigenSolver<double> and
+// LanczosEigenSolver<std::complex<double>> take the handle through setDeviceOperator as they take the others.
+inline std::shared_ptr<CsrOperator> spinHalfMomentumOperator(std::shared_ptr<Context> ctx, const SpinHalfModel& model, int nUp, int m, int cell = 1,
+                                                             bool complexStates = false) {
+  model.requireNoTransverseField("device::spinHalfMomentumOperator");
+  eigenex_csr_t h = nullptr;
+  if (complexStates)
+    check(eigenex_spin_momentum_upload_z(ctx->handle(), model.sites(), nUp, cell, m, model.bonds(), model.siteI(), model.siteJ(), model.jz(),
+                                         model.jxy(), model.fieldZ(), &h),
+          "eigenex_spin_momentum_upload_z");
+  else
+    check(eigenex_spin_momentum_upload(ctx->handle(), model.sites(), nUp, cell, m, model.bonds(), model.siteI(), model.siteJ(), model.jz(),
+                                       model.jxy(), model.fieldZ(), &h),
+          "eigenex_spin_momentum_upload");
   return CsrOperator::adopt(std::move(ctx), h);
 }
 

@@ -327,6 +327,70 @@ int eigenex_spin_upload_z(eigenex_context_t ctx, int n_sites, int n_bonds, const
 int eigenex_spin_sector_upload_z(eigenex_context_t ctx, int n_sites, int n_up, int n_bonds, const int32_t* site_i,
                                  const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null,
                                  const double* hx_or_null, eigenex_csr_t* out);
+/* The same Hamiltonian in one MOMENTUM sector of a sector of fixed magnetisation.  NOT part of the reference.  The model must
+ * conserve total Sz (no hx argument: a transverse field has no Sz sector) and be invariant under the translation T by `cell`
+ * sites, site i -> (i + cell) mod n_sites: cell divides n_sites, 1 <= cell <= n_sites / 2, N = n_sites / cell translations.  The
+ * multiset of (unordered bond, jz, jxy), couplings compared bit for bit, must map onto itself under T and hz[i] must equal
+ * hz[(i + cell) mod n_sites]; otherwise EIGENEX_ERR_ARG with a message that names the first bond or site that breaks the
+ * symmetry.  momentum = m in 0..N-1 stands for k = 2 pi m / N.
+ *   rows      A state s has period R_s, the smallest R >= 1 with T^R s = s.  The rows are the numerically smallest states
+ *             ("representatives") a of the orbits of the Sz sector with (m R_a) mod N == 0, ascending; dim < 2^31.  A sector
+ *             without such a state (n_up = 0 at m = 1) is refused with EIGENEX_ERR_ARG and a message that says so.
+ *   basis     |a(k)> = (sqrt(R_a) / N) sum_{r<N} e^{-ikr} T^r |a>
+ *   row a     in stored (= summation) order: the diagonal d(a) of eigenex_spin_upload's definition, always stored, at column
+ *             idx(a); then for b ascending over the bonds with jxy[b] != 0 and different spins on the bond, with s' = a ^ mask_b,
+ *             j* the smallest j >= 0 with T^j s' = rep(s') and l = (N - j*) mod N: nothing if (m R_s') mod N != 0, else the
+ *             value c * phase[l] at column idx(rep(s')), c = (jxy[b] * 0.5) * sqrt((double)R_a / (double)R_s') with each product
+ *             rounded, phase[l] = e^{-2 pi i ((m l) mod N) / N} -- exactly 1, -i, -1, i where 4 ((m l) mod N) is a multiple of N
+ *             -- value.re = c * phase.re, value.im = c * phase.im.  Terms are never merged: two terms of a row that reach the
+ *             same column stay two entries.
+ *   real      m == 0 or 2 m == N: every value.im is exactly 0 and the operator is real symmetric.  Real momenta may be used
+ *             with real states, every other momentum needs complex states.
+ *   expand    maps a momentum vector x to the vector y of the Sz sector (the rows of eigenex_spin_sector_upload): for a sector
+ *             state s with b = rep(s) = T^{j*} s, y[rank(s)] = x[idx(b)] * phase[(N - j*) mod N] * (1 / sqrt((double)R_b)) if b
+ *             is a row of the sector, else 0; the first product is a plain complex multiply (of a real vector x * phase.re), the
+ *             second scales each part.  It preserves the norm, and H_sector expand(x) = expand(H_k x).
+ *   eigenex_spin_momentum_dim     dim
+ *   eigenex_spin_momentum_states  the representatives of rows first .. first + count - 1 and, unless NULL, their periods
+ *   eigenex_spin_momentum_csr     rows [row_begin, row_begin + n_rows) as CSR, arguments as eigenex_spin_sector_csr but val holds
+ *                                 interleaved (re, im) pairs: 2 * nnz doubles
+ *   eigenex_spin_momentum_expand_host  expand in host code: x and y hold 1 (is_complex = 0; real momenta only) or 2 doubles per row
+ * are host code: no context, no GPU.
+ *   eigenex_spin_momentum_upload    the matrix-free operator for real states, real momenta only (layout
+ *                                   EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM, a context with one shard in total).  The device holds
+ *                                   the ascending list of representatives, 4 bytes per row, and a table of 2^(n_sites / 2) + 1
+ *                                   words that brackets the search for a column; a row's own state is one coalesced load, the
+ *                                   orbit of every flipped state is walked in registers.  eigenex_apply is bit-identical to
+ *                                   eigenex_csr_upload of the real parts of eigenex_spin_momentum_csr's rows.  eigenex_csr_info
+ *                                   reports nnz_local = 0.
+ *   eigenex_spin_momentum_upload_z  the same for complex states, any momentum: bit-identical to eigenex_csr_upload_z of
+ *                                   eigenex_spin_momentum_csr's rows.  Lanczos, the Chebyshev filter and the KPM moments run on
+ *                                   either handle as on every other operator.
+ *   eigenex_spin_momentum_geometry  n_sites, n_up, cell and momentum of such a handle; EIGENEX_ERR_STATE for any other handle.
+ *                                   Every output may be NULL.
+ *   eigenex_spin_momentum_expand    expand on the device: x a vector of a state on a momentum handle, y a vector of a state on a
+ *                                   handle of eigenex_spin_sector_upload(_z) of the same (n_sites, n_up), the same scalar type
+ *                                   and the same context; anything else is EIGENEX_ERR_STATE before anything is allocated.  One
+ *                                   launch, bit-identical to eigenex_spin_momentum_expand_host; norm2 = sum |y_r|^2 (may be NULL)
+ *                                   is reduced in a fixed order without atomics.  Synchronises once.
+ * All argument checks -- geometry, model, and a complex momentum given to eigenex_spin_momentum_upload -- happen before the context
+ * is touched.  A row of a momentum handle is an orbit, not a state: eigenex_spin_geometry, eigenex_spin_measure, eigenex_spin_rdm(_z)
+ * and eigenex_spin_site_apply(_z) refuse it as they refuse every handle that is not theirs; expand first. */
+int eigenex_spin_momentum_dim(int n_sites, int n_up, int cell, int momentum, int64_t* dim);
+int eigenex_spin_momentum_states(int n_sites, int n_up, int cell, int momentum, int64_t first, int64_t count, uint32_t* states,
+                                 uint8_t* periods_or_null);
+int eigenex_spin_momentum_csr(int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
+                              const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null,
+                              int64_t row_begin, int64_t n_rows, int64_t* rowptr, int32_t* col, double* val_interleaved, int64_t* nnz);
+int eigenex_spin_momentum_upload(eigenex_context_t ctx, int n_sites, int n_up, int cell, int momentum, int n_bonds,
+                                 const int32_t* site_i, const int32_t* site_j, const double* jz, const double* jxy,
+                                 const double* hz_or_null, eigenex_csr_t* out);
+int eigenex_spin_momentum_upload_z(eigenex_context_t ctx, int n_sites, int n_up, int cell, int momentum, int n_bonds,
+                                   const int32_t* site_i, const int32_t* site_j, const double* jz, const double* jxy,
+                                   const double* hz_or_null, eigenex_csr_t* out);
+int eigenex_spin_momentum_geometry(eigenex_csr_t csr, int* n_sites, int* n_up, int* cell, int* momentum);
+int eigenex_spin_momentum_expand(eigenex_basis_t src_basis, int x_ref, eigenex_basis_t dst_basis, int y_ref, double* norm2);
+int eigenex_spin_momentum_expand_host(int n_sites, int n_up, int cell, int momentum, int is_complex, const double* x, double* y);
 /* Spin correlations of a real vector x over the rows of a matrix-free spin operator, all terms in one sweep: x is read once
  * per 16 terms of each list and nothing is written but the sums.  A measurement is two lists of 32-bit site masks (bit i = site
  * i); with sigma_i(s) as above it yields the raw, unnormalised sums
@@ -476,7 +540,8 @@ int eigenex_csr_column_blocks(eigenex_csr_t csr, int* passes);
  * EIGENEX_LAYOUT_SPLIT_TILES adds a row's products in another association (see column_blocks = -3) */
 enum { EIGENEX_LAYOUT_CSR = 0, EIGENEX_LAYOUT_COLUMN_BLOCKED = 1, EIGENEX_LAYOUT_SORTED_TILES = 2, EIGENEX_LAYOUT_DENSE_BLOCKS = 3,
        EIGENEX_LAYOUT_SPLIT_TILES = 4, EIGENEX_LAYOUT_MATRIX_FREE_SPIN = 5 /* eigenex_spin_upload: nothing stored */,
-       EIGENEX_LAYOUT_MATRIX_FREE_SPIN_SECTOR = 6 /* eigenex_spin_sector_upload: two rank tables, no rows */ };
+       EIGENEX_LAYOUT_MATRIX_FREE_SPIN_SECTOR = 6 /* eigenex_spin_sector_upload: two rank tables, no rows */,
+       EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM = 7 /* eigenex_spin_momentum_upload: one representative per row and a bucket table */ };
 int eigenex_csr_layout(eigenex_csr_t csr, int* layout);
 /* how the entries of an EIGENEX_LAYOUT_CSR operator are encoded.  EIGENEX_ENCODING_ROW_CODES: a real operator in one pass
  * whose rows use at most 16 column offsets (col - row, halo columns in local numbering) and at most 255 bitwise-distinct
