@@ -117,6 +117,13 @@ SIGNATURES = {
     "eigenex_spin_momentum_geometry": (C.c_int, [_vp] + [C.POINTER(C.c_int)] * 4),
     "eigenex_spin_momentum_expand": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _dp]),
     "eigenex_spin_momentum_expand_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]),
+    "eigenex_spin_momentum64_dim": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _lp]),
+    "eigenex_spin_momentum64_states": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)]),
+    "eigenex_spin_momentum64_csr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, C.c_int64, C.c_int64, _lp, _ip, _dp, _lp]),
+    "eigenex_spin_momentum64_upload": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, C.POINTER(_vp)]),
+    "eigenex_spin_momentum64_upload_z": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, C.POINTER(_vp)]),
+    "eigenex_spin_momentum_measure": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint64), _dp, _dp]),
+    "eigenex_spin_momentum_measure_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_uint64), _dp, _dp]),
     "eigenex_spin_measure": (C.c_int, [_vp, C.c_int, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_measure_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_measure_host_z": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
@@ -411,6 +418,61 @@ def spin_momentum_expand_host(n_sites: int, n_up: int, momentum: int, x, cell: i
     _chk(lib().eigenex_spin_momentum_expand_host(int(n_sites), int(n_up), int(cell), int(momentum), int(is_complex), _d(x.view(np.float64)),
                                                  _d(y.view(np.float64))))
     return y
+
+
+def spin_momentum64_dim(n_sites: int, n_up: int, momentum: int, cell: int = 1) -> int:
+    """eigenex_spin_momentum64_dim: the number of rows of the momentum sector (n_sites up to 48, n_up, cell, momentum)"""
+    dim = C.c_int64()
+    _chk(lib().eigenex_spin_momentum64_dim(int(n_sites), int(n_up), int(cell), int(momentum), C.byref(dim)))
+    return dim.value
+
+
+def spin_momentum64_states(n_sites: int, n_up: int, momentum: int, cell: int = 1, first: int = 0, count: int | None = None):
+    """eigenex_spin_momentum64_states: (representatives (uint64, ascending), their periods (uint8)) of rows first .. first + count - 1"""
+    if count is None:
+        count = spin_momentum64_dim(n_sites, n_up, momentum, cell) - first
+    states, periods = np.zeros(max(int(count), 0), np.uint64), np.zeros(max(int(count), 0), np.uint8)
+    _chk(lib().eigenex_spin_momentum64_states(int(n_sites), int(n_up), int(cell), int(momentum), int(first), int(count),
+                                              states.ctypes.data_as(C.POINTER(C.c_uint64)), periods.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return states, periods
+
+
+def spin_momentum64_csr(n_sites: int, n_up: int, momentum: int, bonds, hz=None, cell: int = 1, row_begin: int = 0, n_rows: int | None = None):
+    """eigenex_spin_momentum64_csr: spin_momentum_csr for rings of up to 48 sites and 128 bonds (64-bit states).  Returns rowptr
+    (int64), col (int32), val (complex128; all imaginary parts are exactly 0 at a real momentum)."""
+    keep, args = _spin_model(n_sites, bonds, hz, None)
+    args = _momentum_args(args, n_up, cell, momentum)
+    nnz = C.c_int64()
+    if n_rows is None:
+        one = np.zeros(1, np.int64)
+        _chk(lib().eigenex_spin_momentum64_csr(*args, 0, 0, one.ctypes.data_as(_lp), None, None, C.byref(nnz)))  # the model's own refusal first
+        n_rows = spin_momentum64_dim(n_sites, n_up, momentum, cell) - row_begin
+    rowptr = np.zeros(max(int(n_rows), 0) + 1, np.int64)
+    _chk(lib().eigenex_spin_momentum64_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), None, None, C.byref(nnz)))
+    col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value, np.complex128)
+    _chk(lib().eigenex_spin_momentum64_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), _i(col), _d(val.view(np.float64)), C.byref(nnz)))
+    return rowptr, col, val
+
+
+def _mask_list64(masks):
+    """a list of 64-bit site masks as (keep-alive array, count, pointer or None)"""
+    m = np.ascontiguousarray(masks, np.uint64).reshape(-1)
+    return m, int(m.size), (m.ctypes.data_as(C.POINTER(C.c_uint64)) if m.size else None)
+
+
+def spin_momentum_measure_host(n_sites: int, n_up: int, momentum: int, x, masks, cell: int = 1):
+    """eigenex_spin_momentum_measure_host: (diag, norm2), the raw sums of the diagonal correlations of the momentum vector x (float64
+    or complex128, one entry per row of the sector; n_sites up to 48) over 64-bit site masks: <D_t> = diag[t] / (N norm2) with
+    N = n_sites / cell.  The definition the device call is held against."""
+    is_complex = np.iscomplexobj(x)
+    x = np.ascontiguousarray(x, np.complex128 if is_complex else np.float64).reshape(-1)
+    keep, n, ptr = _mask_list64(masks)
+    if x.size != spin_momentum64_dim(n_sites, n_up, momentum, cell):  # the library cannot see the length
+        raise ValueError("x needs one entry per row of the momentum sector")
+    diag, norm2 = np.zeros(n, np.float64), C.c_double()
+    _chk(lib().eigenex_spin_momentum_measure_host(int(n_sites), int(n_up), int(cell), int(momentum), int(is_complex), _d(x.view(np.float64)), n, ptr,
+                                                  _d(diag) if n else None, C.byref(norm2)))
+    return diag, norm2.value
 
 
 def _mask_list(masks):
@@ -798,6 +860,18 @@ class Csr:
         return obj
 
     @classmethod
+    def spin_half_momentum64(cls, ctx: Context, n_sites: int, n_up: int, momentum: int, bonds, hz=None, cell: int = 1, complex_states=False):
+        """eigenex_spin_momentum64_upload: spin_half_momentum for rings of up to 48 sites and 128 bonds, with 64-bit states
+        (complex_states: eigenex_spin_momentum64_upload_z).  Every argument is checked before ctx is looked at."""
+        keep, args = _spin_model(n_sites, bonds, hz, None)
+        h = _vp()
+        entry = lib().eigenex_spin_momentum64_upload_z if complex_states else lib().eigenex_spin_momentum64_upload
+        _chk(entry(ctx.h if ctx is not None else None, *_momentum_args(args, n_up, cell, momentum), C.byref(h)))
+        obj = cls(ctx, h)
+        obj.is_complex = bool(complex_states)
+        return obj
+
+    @classmethod
     def laplacian3d(cls, ctx: Context, n: int):
         h = _vp()
         _chk(lib().eigenex_csr_laplacian3d(ctx.h, n, C.byref(h)))
@@ -807,7 +881,7 @@ class Csr:
         v = C.c_int()
         _chk(lib().eigenex_csr_layout(self.h, C.byref(v)))
         return ("csr", "column_blocked", "sorted_tiles", "dense_blocks", "split_tiles", "matrix_free_spin", "matrix_free_spin_sector",
-                "matrix_free_spin_momentum")[v.value]
+                "matrix_free_spin_momentum", "matrix_free_spin_momentum64")[v.value]
 
     def spin_momentum_geometry(self):
         """eigenex_spin_momentum_geometry: (n_sites, n_up, cell, momentum) of a momentum-sector operator"""
@@ -1000,6 +1074,15 @@ class Basis:
         norm2 = C.c_double()
         _chk(lib().eigenex_spin_momentum_expand(self.h, x_ref, dst.h, y_ref, C.byref(norm2)))
         return norm2.value
+
+    def spin_momentum_measure(self, x_ref, masks):
+        """eigenex_spin_momentum_measure: (diag, norm2), the raw sums of the diagonal correlations of vector x_ref of this state,
+        on a momentum-sector operator of either word size, over 64-bit site masks; <D_t> = diag[t] / (N norm2).  No coefficient,
+        counter or recorded step batch changes."""
+        keep, n, ptr = _mask_list64(masks)
+        diag, norm2 = np.zeros(n, np.float64), C.c_double()
+        _chk(lib().eigenex_spin_momentum_measure(self.h, x_ref, n, ptr, _d(diag) if n else None, C.byref(norm2)))
+        return diag, norm2.value
 
     def spin_site_apply_z(self, x_ref, dst, y_ref, kind, coef, imaginary="auto"):
         """eigenex_spin_site_apply_z: spin_site_apply for two complex spin states, with real or complex coefficients; returns

@@ -1933,31 +1933,56 @@ __global__ __launch_bounds__(kBlock) void k_spin_site_apply(const SpinSiteTable*
 // issued before the first product is added.  The sums are those of the CSR row loop over eigenex_spin_momentum_csr's rows:
 // k_spmv's for E = double on val.re at a real momentum, k_spmv_z's for E = SpinZ.
 // ---------------------------------------------------------------------------
+// The state word is a parameter: Word = uint32_t for the sectors of spin_momentum.hpp, uint64_t for those of spin_momentum64.hpp
+// (up to 48 sites; reps is then 8 bytes per row, still one coalesced load, and the LDS tables are 19.9 KB).  SpinMomentumWord has
+// the view and the table sizes of either; the kernel text is the same.
 static_assert(kSpinRatioPitch == kMomentumRatioPitch, "spin_rows.hpp indexes ratio with spin_momentum.hpp's pitch");
-struct SpinMomentumLookup {
-  const uint32_t *reps_, *bucket_;
-  __device__ __forceinline__ uint32_t reps(uint32_t i) const { return reps_[i]; }
+static_assert(kSpinRatioPitch64 == kMomentum64RatioPitch, "spin_rows.hpp indexes ratio with spin_momentum64.hpp's pitch");
+template <class Word>
+struct SpinMomentumWord {
+  using View = SpinMomentumView;
+  using Tables = SpinMomentumTables;
+  static constexpr int kPitch = kMomentumRatioPitch, kMaxPeriod = kMomentumMaxPeriod;
+};
+template <>
+struct SpinMomentumWord<uint64_t> {
+  using View = SpinMomentum64View;
+  using Tables = SpinMomentum64Tables;
+  static constexpr int kPitch = kMomentum64RatioPitch, kMaxPeriod = kMomentum64MaxPeriod;
+};
+template <class Word>
+struct SpinMomentumLookupOf {
+  const Word* reps_;
+  const uint32_t* bucket_;
+  __device__ __forceinline__ Word reps(uint32_t i) const { return reps_[i]; }
   __device__ __forceinline__ uint32_t bucket(uint32_t i) const { return bucket_[i]; }
 };
-struct SpinMomentumLds {  // the workgroup's copy of SpinMomentumTables
+using SpinMomentumLookup = SpinMomentumLookupOf<uint32_t>;
+template <class Word>
+struct SpinMomentumLdsOf {  // the workgroup's copy of SpinMomentumTables or SpinMomentum64Tables
   const double* t;
-  static constexpr int kRatio = 0, kInvSqrt = kMomentumRatioPitch * kMomentumRatioPitch, kPhaseRe = kInvSqrt + kMomentumRatioPitch,
-                       kPhaseIm = kPhaseRe + kMomentumMaxPeriod, kSize = kPhaseIm + kMomentumMaxPeriod;
+  static constexpr int kPitch = SpinMomentumWord<Word>::kPitch, kMaxPeriod = SpinMomentumWord<Word>::kMaxPeriod;
+  static constexpr int kRatio = 0, kInvSqrt = kPitch * kPitch, kPhaseRe = kInvSqrt + kPitch, kPhaseIm = kPhaseRe + kMaxPeriod,
+                       kSize = kPhaseIm + kMaxPeriod;
   __device__ __forceinline__ double ratio(int i) const { return t[kRatio + i]; }
   __device__ __forceinline__ double inv_sqrt(int i) const { return t[kInvSqrt + i]; }
   __device__ __forceinline__ double phase_re(int i) const { return t[kPhaseRe + i]; }
   __device__ __forceinline__ double phase_im(int i) const { return t[kPhaseIm + i]; }
 };
+using SpinMomentumLds = SpinMomentumLdsOf<uint32_t>;
 static_assert(sizeof(SpinMomentumTables) == sizeof(double) * SpinMomentumLds::kSize, "the LDS copy is the struct, member by member");
+static_assert(sizeof(SpinMomentum64Tables) == sizeof(double) * SpinMomentumLdsOf<uint64_t>::kSize, "the LDS copy is the struct, member by member");
 // the caller synchronises
-__device__ __forceinline__ void spin_stage_momentum_tables(const SpinMomentumView* __restrict__ op, double* tab) {
+template <class View>
+__device__ __forceinline__ void spin_stage_momentum_tables(const View* __restrict__ op, double* tab) {
   const double* src = reinterpret_cast<const double*>(&op->tab);
-  for (int i = threadIdx.x; i < SpinMomentumLds::kSize; i += kBlock) tab[i] = src[i];
+  constexpr int kSize = (int)(sizeof(op->tab) / sizeof(double));
+  for (int i = threadIdx.x; i < kSize; i += kBlock) tab[i] = src[i];
 }
 
-template <class E, class... ComplexOnly>
-__global__ __launch_bounds__(kBlock) void k_spin_momentum_spmv(const SpinMomentumView* __restrict__ op, const uint32_t* __restrict__ reps,
-                                                               const uint32_t* __restrict__ bucket,
+template <class E, class Word, class... ComplexOnly>
+__global__ __launch_bounds__(kBlock) void k_spin_momentum_spmv(const typename SpinMomentumWord<Word>::View* __restrict__ op,
+                                                               const Word* __restrict__ reps, const uint32_t* __restrict__ bucket,
                                                                const typename SpinElement<E>::Stored* __restrict__ x_ext,
                                                                const double* __restrict__ scale_ptr, double shift,
                                                                SpinShiftIm<ComplexOnly>... shift_im, typename SpinElement<E>::Stored* __restrict__ y,
@@ -1967,24 +1992,24 @@ __global__ __launch_bounds__(kBlock) void k_spin_momentum_spmv(const SpinMomentu
   static_assert(sizeof...(ComplexOnly) == (std::is_same<E, SpinZ>::value ? 1 : 0), "shift_im and pstride for complex vectors only");
   constexpr bool COMPLEX = std::is_same<E, SpinZ>::value;
   __shared__ double lds4[4];
-  __shared__ double tables[SpinMomentumLds::kSize];
+  __shared__ double tables[SpinMomentumLdsOf<Word>::kSize];
   if (ctrl->stopped) return;
   spin_stage_momentum_tables(op, tables);
   __syncthreads();
   const double scale = scale_ptr ? *scale_ptr : 1.0;
   bool has_shift = false;  // a complex shift is tested once, here
   if constexpr (COMPLEX) has_shift = shift != 0.0 || (shift_im + ...) != 0.0;
-  const SpinOperatorView* model = &op->model;
+  const auto* model = &op->model;
   const int n_sites = model->n_sites, ndiag = model->ndiag, nflip = model->nflip;
   const int cell = op->cell, n_trans = op->n_trans, h = op->h, steps = op->steps;
-  const uint32_t compatible = op->compatible;
-  const SpinMomentumLookup lk{reps, bucket};
-  const SpinMomentumLds tb{tables};
+  const Word compatible = op->compatible;
+  const SpinMomentumLookupOf<Word> lk{reps, bucket};
+  const SpinMomentumLdsOf<Word> tb{tables};
   double dot = 0.0, dot_im = 0.0;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t r = tile * kBlock + threadIdx.x;
     if (r < n) {
-      const uint32_t s = reps[r];
+      const Word s = reps[r];
       const int period = spin_orbit(s, n_sites, cell, n_trans).period;
       const double d = spin_row_diagonal(model->dmask, model->dval, ndiag, s);
       const E xraw = spin_loaded(x_ext[r]);
@@ -2032,6 +2057,44 @@ __global__ __launch_bounds__(kBlock) void k_spin_momentum_spmv(const SpinMomentu
         if (!(pass & kPassSelfNorm)) partials[(pstride + ...) + blockIdx.x] = dot_im;
     }
   }
+}
+
+// Diagonal correlations of one vector in the momentum basis (spin_momentum64.hpp has the definition and the chunk): x and reps
+// stream past once per chunk of kSpinMeasureChunk masks and no vector is written.  One row per lane, 256-row tiles, the
+// persistent grid; the lane's state is reps[r], one coalesced load, and every lane rotates it n_trans times, the chunk's masks
+// applied to each rotation (spin_rows.hpp: spin_momentum_measure_diagonals).  The C + 1 sums stay in registers across the tile
+// loop and leave through block_sum into partials[sum * pstride + workgroup]; k_spin_measure_reduce adds those in k_reduce_fin's
+// order (its flip sums are not written and not read).  No atomics.  ctrl->stopped is not consulted.
+template <class E, class Word>
+__global__ __launch_bounds__(kBlock) void k_spin_momentum_measure(const SpinMomentumMeasureChunk* __restrict__ ch, const Word* __restrict__ reps,
+                                                                  const typename SpinElement<E>::Stored* __restrict__ x, int n_sites, int cell,
+                                                                  int n_trans, int64_t n, int64_t ntiles, double* __restrict__ partials,
+                                                                  int pstride) {
+  constexpr int C = kSpinMeasureChunk;
+  __shared__ double lds4[4];
+  const int ndiag = ch->ndiag;
+  double nrm = 0.0, dg[C];
+#pragma unroll
+  for (int t = 0; t < C; ++t) dg[t] = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + threadIdx.x;
+    if (r < n) {
+      const Word s = reps[r];
+      const E xs = spin_loaded(x[r]);
+      nrm = spin_norm_add(nrm, xs);
+      const double w = spin_momentum_weight(xs);
+#pragma unroll
+      for (int t0 = 0; t0 < C; t0 += kSpinBatch)
+        if (t0 < ndiag) spin_momentum_measure_diagonals(w, s, ch->dmask + t0, n_sites, cell, n_trans, dg + t0);
+    }
+  }
+  const auto put = [&](int a, double mine) {  // sum a of this workgroup: 0 norm2, 1 + t diag
+    const double v = block_sum(mine, lds4);
+    if (threadIdx.x == 0) partials[(int64_t)a * pstride + blockIdx.x] = v;
+  };
+  put(0, nrm);
+#pragma unroll
+  for (int t = 0; t < C; ++t) put(1 + t, dg[t]);
 }
 
 // expand (spin_momentum.hpp): y = the Sz-sector vector of the momentum vector x.  One row of the DESTINATION per lane, unranked
@@ -3236,16 +3299,43 @@ void launch_spin_site_apply(hipStream_t s, int es, const SpinSiteTable* table, c
   (es == 2 ? spin_site_apply_launch<SpinZ> : spin_site_apply_launch<double>)(s, table, dst_op, src_lo, src_hi, x, y, n, partials, grid);
 }
 
+template <class Word>
+static void spin_momentum_spmv_launch(hipStream_t s, int es, const typename SpinMomentumWord<Word>::View* op, const Word* reps, const uint32_t* bucket,
+                                      const double* x_ext, const double* scale, double shift_re, double shift_im, double* y, double* u_out,
+                                      int64_t n, double* partials, int pstride, int grid, const Ctrl* ctrl, int pass) {
+  const int64_t ntiles = (n + kBlock - 1) / kBlock;
+  if (es == 2)
+    hipLaunchKernelGGL((k_spin_momentum_spmv<SpinZ, Word, int>), dim3(grid), dim3(kBlock), 0, s, op, reps, bucket, spin_elements<SpinZ>(x_ext),
+                       scale, shift_re, shift_im, spin_elements<SpinZ>(y), spin_elements<SpinZ>(u_out), n, ntiles, partials, pstride, pass, ctrl);
+  else
+    hipLaunchKernelGGL((k_spin_momentum_spmv<double, Word>), dim3(grid), dim3(kBlock), 0, s, op, reps, bucket, x_ext, scale, shift_re, y, u_out, n,
+                       ntiles, partials, pass, ctrl);
+}
 void launch_spin_momentum_spmv(hipStream_t s, int es, const SpinMomentumView* op, const uint32_t* reps, const uint32_t* bucket,
                                const double* x_ext, const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n,
                                double* partials, int pstride, int grid, const Ctrl* ctrl, int pass) {
-  const int64_t ntiles = (n + kBlock - 1) / kBlock;
-  if (es == 2)
-    hipLaunchKernelGGL((k_spin_momentum_spmv<SpinZ, int>), dim3(grid), dim3(kBlock), 0, s, op, reps, bucket, spin_elements<SpinZ>(x_ext), scale,
-                       shift_re, shift_im, spin_elements<SpinZ>(y), spin_elements<SpinZ>(u_out), n, ntiles, partials, pstride, pass, ctrl);
+  spin_momentum_spmv_launch<uint32_t>(s, es, op, reps, bucket, x_ext, scale, shift_re, shift_im, y, u_out, n, partials, pstride, grid, ctrl, pass);
+}
+void launch_spin_momentum64_spmv(hipStream_t s, int es, const SpinMomentum64View* op, const uint64_t* reps, const uint32_t* bucket,
+                                 const double* x_ext, const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n,
+                                 double* partials, int pstride, int grid, const Ctrl* ctrl, int pass) {
+  spin_momentum_spmv_launch<uint64_t>(s, es, op, reps, bucket, x_ext, scale, shift_re, shift_im, y, u_out, n, partials, pstride, grid, ctrl, pass);
+}
+
+template <class E, class Word>
+static void spin_momentum_measure_launch(hipStream_t s, const SpinMomentumMeasureChunk* chunk, const Word* reps, const double* x, int n_sites,
+                                         int cell, int n_trans, int64_t n, double* partials, int pstride, int grid) {
+  hipLaunchKernelGGL((k_spin_momentum_measure<E, Word>), dim3(grid), dim3(kBlock), 0, s, chunk, reps, spin_elements<E>(x), n_sites, cell, n_trans, n,
+                     (n + kBlock - 1) / kBlock, partials, pstride);
+}
+void launch_spin_momentum_measure(hipStream_t s, int es, const SpinMomentumMeasureChunk* chunk, const uint32_t* reps32, const uint64_t* reps64,
+                                  const double* x, int n_sites, int cell, int n_trans, int64_t n, double* partials, int pstride, int grid) {
+  if (reps64)
+    (es == 2 ? spin_momentum_measure_launch<SpinZ, uint64_t> : spin_momentum_measure_launch<double, uint64_t>)(s, chunk, reps64, x, n_sites, cell,
+                                                                                                            n_trans, n, partials, pstride, grid);
   else
-    hipLaunchKernelGGL((k_spin_momentum_spmv<double>), dim3(grid), dim3(kBlock), 0, s, op, reps, bucket, x_ext, scale, shift_re, y, u_out, n,
-                       ntiles, partials, pass, ctrl);
+    (es == 2 ? spin_momentum_measure_launch<SpinZ, uint32_t> : spin_momentum_measure_launch<double, uint32_t>)(s, chunk, reps32, x, n_sites, cell,
+                                                                                                            n_trans, n, partials, pstride, grid);
 }
 
 template <class E>

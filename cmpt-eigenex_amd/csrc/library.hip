@@ -290,11 +290,16 @@ struct SpinShard {
 // A matrix-free spin-1/2 operator in a momentum sector on its shard (spin_momentum.hpp): the kernels' view, the ascending list of
 // representatives (one per row) and the bucket table of the search.  Not a SpinShard: a row is an orbit, not a state, so the
 // calls that read states off the rows (eigenex_spin_geometry, _measure, _rdm, _site_apply) must keep refusing the handle.
+// With 64-bit states (eigenex_spin_momentum64_upload; spin_momentum64.hpp) it is the same shard with the wide members in place of
+// view and reps: on() holds for both, so every predicate that tells the momentum shard from the stored forms covers both.
 struct SpinMomentumShard {
   DeviceBuffer<SpinMomentumView> view;
   DeviceBuffer<uint32_t> reps, bucket;
-  int64_t table_words = 0;  // entries of reps and bucket together
+  DeviceBuffer<SpinMomentum64View> view64;  // wide only
+  DeviceBuffer<uint64_t> reps64;            // wide only, 8 bytes per row
+  int64_t table_words = 0;  // 4-byte words of reps and bucket together
   int n_sites = 0, n_up = 0, cell = 0, momentum = 0;
+  bool wide = false;
   bool on() const { return n_sites > 0; }
 };
 
@@ -1606,7 +1611,7 @@ double operator_bytes(const CsrShard* m, int es) {
   if (m->rc_rec) return (double)m->rc_bytes * row_code_rows(m->nloc) + 8.0 * m->rc_npal;
   if (m->blocked) return 8.0 * es * m->nnz + 4.0 * m->nstripcols + 4.0 * m->nloc;
   if (m->spin.on()) return m->spin.n_up >= 0 ? (double)sizeof(SpinSectorView) + 4.0 * m->spin.table_words : (double)sizeof(SpinOperatorView);
-  if (m->momentum.on()) return (double)sizeof(SpinMomentumView) + 4.0 * m->momentum.table_words;
+  if (m->momentum.on()) return (double)(m->momentum.wide ? sizeof(SpinMomentum64View) : sizeof(SpinMomentumView)) + 4.0 * m->momentum.table_words;
   return csr_bytes(m, es);
 }
 // long rows (16 stored entries per row or more on average): the CSR kernels have a variant for them (kSpmvLongRows) and
@@ -1695,6 +1700,11 @@ void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p)
     else
       launch_spin_spmv(st, m->spin.view, m->spin.lo, m->spin.hi, p.x, p.scale, p.shift, p.y, p.u_out, m->nloc, p.partials, grid, p.ctrl,
                        p.pass_flags);
+    return;
+  }
+  if (m->momentum.on() && m->momentum.wide) {
+    launch_spin_momentum64_spmv(st, es, m->momentum.view64, m->momentum.reps64, m->momentum.bucket, p.x, p.scale, p.shift, p.shift_im, p.y, p.u_out,
+                                m->nloc, p.partials, s.pstride, grid, p.ctrl, p.pass_flags);
     return;
   }
   if (m->momentum.on()) {
@@ -3308,6 +3318,9 @@ int eigenex_spin_momentum_expand(eigenex_basis_t src, int x_ref, eigenex_basis_t
   CHK(enter_settled(dst));
   if (!src->csr || src->sh.size() != 1 || !src->sh[0].csr || !src->sh[0].csr->momentum.on())
     return fail(EIGENEX_ERR_STATE, who + ": the operator of the source state is not a momentum-sector operator (eigenex_spin_momentum_upload)");
+  if (src->sh[0].csr->momentum.wide)
+    return fail(EIGENEX_ERR_STATE, who + ": the source is a momentum sector of 64-bit states (eigenex_spin_momentum64_upload): no Sz-sector operator "
+                                         "exists beyond 32 sites to expand into; for n_sites <= 32 use eigenex_spin_momentum_upload");
   BasisShard* sdp = spin_state_shard(dst);
   if (!sdp || sdp->csr->spin.n_up < 0)
     return fail(EIGENEX_ERR_STATE, who + ": the operator of the destination state is not a sector operator (eigenex_spin_sector_upload)");
@@ -3334,6 +3347,168 @@ int eigenex_spin_momentum_expand(eigenex_basis_t src, int x_ref, eigenex_basis_t
   HIPCHK(hipMemcpyAsync(&out, d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the scratch lives until here
   if (norm2) *norm2 = out;
+  return 0;
+}
+
+// ---- momentum sectors of up to 48 sites (spin_momentum64.hpp) ----
+static int spin_momentum64_check(const std::string& who, int n_sites, int n_up, int cell, int momentum, const SpinModelArgs* a) {
+  const std::string geo = spin_momentum64_geometry_error(n_sites, n_up, cell, momentum);
+  if (!geo.empty()) return fail(EIGENEX_ERR_ARG, who + ": " + geo);
+  if (a) {
+    const std::string why = spin_momentum64_model_error(*a, cell);
+    if (!why.empty()) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  }
+  return 0;
+}
+// builds the rows; 0 if there are between 1 and 2^31 - 1 of them
+static int spin_momentum64_rows(const std::string& who, int n_sites, int n_up, int cell, int momentum, SpinMomentum64Basis* b, int64_t* dim,
+                                bool with_lookup = false) {
+  const int64_t n = spin_momentum64_build_basis(n_sites, n_up, cell, momentum, b, with_lookup);
+  if (n == 0) return spin_momentum_empty(who);
+  if (n > kMomentum64MaxDim) return fail(EIGENEX_ERR_ARG, who + ": the sector has 2^31 rows or more: dim must be below 2^31");
+  if (dim) *dim = n;
+  return 0;
+}
+
+int eigenex_spin_momentum64_dim(int n_sites, int n_up, int cell, int momentum, int64_t* dim) {
+  if (!dim) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum64_dim: dim is NULL");
+  CHK(spin_momentum64_check("eigenex_spin_momentum64_dim", n_sites, n_up, cell, momentum, nullptr));
+  return spin_momentum64_rows("eigenex_spin_momentum64_dim", n_sites, n_up, cell, momentum, nullptr, dim);
+}
+
+int eigenex_spin_momentum64_states(int n_sites, int n_up, int cell, int momentum, int64_t first, int64_t count, uint64_t* states,
+                                   uint8_t* periods_or_null) {
+  CHK(spin_momentum64_check("eigenex_spin_momentum64_states", n_sites, n_up, cell, momentum, nullptr));
+  SpinMomentum64Basis b;
+  CHK(spin_momentum64_rows("eigenex_spin_momentum64_states", n_sites, n_up, cell, momentum, &b, nullptr));
+  if (first < 0 || count < 0 || first + count > (int64_t)b.reps.size()) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum64_states: rows outside 0..dim");
+  if (count > 0 && !states) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum64_states: states is NULL");
+  for (int64_t k = 0; k < count; ++k) {
+    states[k] = b.reps[(size_t)(first + k)];
+    if (periods_or_null) periods_or_null[k] = b.period[(size_t)(first + k)];
+  }
+  return 0;
+}
+
+int eigenex_spin_momentum64_csr(int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                                const double* jz, const double* jxy, const double* hz_or_null, int64_t row_begin, int64_t n_rows, int64_t* rowptr,
+                                int32_t* col, double* val, int64_t* nnz) {
+  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, nullptr};
+  CHK(spin_momentum64_check("eigenex_spin_momentum64_csr", n_sites, n_up, cell, momentum, &a));
+  if (!rowptr || !nnz || (col == nullptr) != (val == nullptr))
+    return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum64_csr: rowptr and nnz are needed, col and val together or neither");
+  SpinMomentum64Basis b;
+  CHK(spin_momentum64_rows("eigenex_spin_momentum64_csr", n_sites, n_up, cell, momentum, &b, nullptr));
+  if (row_begin < 0 || n_rows < 0 || row_begin + n_rows > (int64_t)b.reps.size()) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum64_csr: rows outside 0..dim");
+  std::unique_ptr<SpinMomentum64Tables> t(new SpinMomentum64Tables());
+  spin_momentum64_build_tables(b.n_trans, momentum, *t);
+  spin_momentum64_write_rows(a, b, *t, row_begin, n_rows, rowptr, col, val, nnz);
+  return 0;
+}
+
+static int spin_momentum64_upload(const std::string& who, int es, eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds,
+                                  const int32_t* site_i, const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null,
+                                  eigenex_csr_t* out) {
+  // every argument check before the context is touched
+  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, nullptr};
+  CHK(spin_momentum64_check(who, n_sites, n_up, cell, momentum, &a));
+  if (es == 1 && !spin_momentum_is_real(n_sites / cell, momentum))
+    return fail(EIGENEX_ERR_ARG, who + ": real states take a real momentum only (0 or half the number of translations); this one has complex matrix "
+                                       "elements and needs complex states (eigenex_spin_momentum64_upload_z)");
+  if (!c || !out) return fail(EIGENEX_ERR_ARG, who + ": NULL argument");
+  if (c->P != 1)
+    return fail(EIGENEX_ERR_ARG, who + ": a matrix-free spin operator needs a context with one shard in total; sharding it takes an "
+                                       "exchange of whole vectors for the bonds on the top bits, which is not built");
+  SpinMomentum64Basis b;
+  CHK(spin_momentum64_rows(who, n_sites, n_up, cell, momentum, &b, nullptr, true));
+  HIPCHK(hipSetDevice(c->device));
+  std::unique_ptr<eigenex_csr_s> m(new eigenex_csr_s());
+  m->ctx = c;
+  m->n_global = (int64_t)b.reps.size();
+  m->es = es;
+  m->sh.resize(1);
+  CsrShard& s = m->sh[0];
+  s.gshard = c->local[0];
+  s.momentum.n_sites = n_sites, s.momentum.n_up = n_up, s.momentum.cell = cell, s.momentum.momentum = momentum, s.momentum.wide = true;
+  partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
+  s.nloc = s.re - s.rb;
+  s.npad = pad_rows(s.nloc);
+  std::unique_ptr<SpinMomentum64View> v(new SpinMomentum64View());  // staging buffers: they live until the synchronise below
+  spin_momentum64_build_view(a, b, *v);
+  s.momentum.table_words = (int64_t)(2 * b.reps.size() + b.bucket.size());
+  HIPCHK(s.momentum.reps64.alloc(b.reps.size()));
+  HIPCHK(s.momentum.bucket.alloc(b.bucket.size()));
+  HIPCHK(s.momentum.view64.alloc(1));
+  HIPCHK(hipMemcpyAsync(s.momentum.reps64, b.reps.data(), 8 * b.reps.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.momentum.bucket, b.bucket.data(), 4 * b.bucket.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.momentum.view64, v.get(), sizeof(SpinMomentum64View), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *out = m.release();
+  return 0;
+}
+
+int eigenex_spin_momentum64_upload(eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
+                                   const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, eigenex_csr_t* out) {
+  return spin_momentum64_upload("eigenex_spin_momentum64_upload", 1, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy, hz_or_null, out);
+}
+
+int eigenex_spin_momentum64_upload_z(eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
+                                     const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, eigenex_csr_t* out) {
+  return spin_momentum64_upload("eigenex_spin_momentum64_upload_z", 2, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy, hz_or_null, out);
+}
+
+// ---- diagonal correlations in the momentum basis (spin_momentum64.hpp) ----
+int eigenex_spin_momentum_measure_host(int n_sites, int n_up, int cell, int momentum, int is_complex, const double* x, int n_diag,
+                                       const uint64_t* masks, double* diag_out, double* norm2) {
+  const std::string who = "eigenex_spin_momentum_measure_host";
+  CHK(spin_momentum64_check(who, n_sites, n_up, cell, momentum, nullptr));
+  const SpinMomentumMeasureArgs a{n_sites, n_diag, masks};
+  if (const char* why = spin_momentum_measure_error(a)) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  if (!x) return fail(EIGENEX_ERR_ARG, who + ": x is NULL");
+  if (n_diag > 0 && !diag_out) return fail(EIGENEX_ERR_ARG, who + ": an output list is NULL but its count is not zero");
+  SpinMomentum64Basis b;
+  CHK(spin_momentum64_rows(who, n_sites, n_up, cell, momentum, &b, nullptr));
+  spin_momentum_measure_host(b, a, is_complex != 0, x, diag_out, norm2);
+  return 0;
+}
+
+int eigenex_spin_momentum_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint64_t* masks, double* diag_out, double* norm2) {
+  const std::string who = "eigenex_spin_momentum_measure";
+  if (!b) return fail(EIGENEX_ERR_ARG, who + ": basis is NULL");
+  CHK(enter_settled(b));
+  if (!b->csr || b->sh.size() != 1 || !b->sh[0].csr || !b->sh[0].csr->momentum.on())
+    return fail(EIGENEX_ERR_STATE, who + ": the operator of this state is not a momentum-sector operator (eigenex_spin_momentum_upload, "
+                                         "eigenex_spin_momentum64_upload)");
+  BasisShard& s = b->sh[0];
+  const SpinMomentumShard& mk = s.csr->momentum;
+  const SpinMomentumMeasureArgs a{mk.n_sites, n_diag, masks};
+  if (const char* why = spin_momentum_measure_error(a)) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  if (n_diag > 0 && !diag_out) return fail(EIGENEX_ERR_ARG, who + ": an output list is NULL but its count is not zero");
+  const double* x = vec_ptr(s, b->cap, b->nq, x_ref);
+  if (!x) return fail(EIGENEX_ERR_ARG, "bad vector reference");
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  // scratch of this call alone, as in eigenex_spin_measure: the chunk table, one chunk's partial sums and the results [norm2, diag]
+  std::vector<SpinMomentumMeasureChunk> chunks;
+  spin_momentum_measure_build_chunks(a, chunks);
+  const int grid = s.g_spmv, nsums = kSpinMeasureChunk + 1;
+  DeviceBuffer<SpinMomentumMeasureChunk> d_chunks;
+  DeviceBuffer<double> d_part, d_out;
+  std::vector<double> out((size_t)(1 + n_diag), 0.0);
+  HIPCHK(d_chunks.alloc(chunks.size()));
+  HIPCHK(d_part.alloc((size_t)nsums * grid));
+  HIPCHK(d_out.alloc(out.size()));
+  HIPCHK(hipMemcpyAsync(d_chunks, chunks.data(), sizeof(SpinMomentumMeasureChunk) * chunks.size(), hipMemcpyHostToDevice, c->stream));
+  for (size_t k = 0; k < chunks.size(); ++k) {
+    const size_t dfirst = std::min(k * kSpinMeasureChunk, (size_t)n_diag);
+    launch_spin_momentum_measure(c->stream, b->es, d_chunks + k, mk.wide ? nullptr : mk.reps.get(), mk.wide ? mk.reps64.get() : nullptr, x, mk.n_sites,
+                                 mk.cell, mk.n_sites / mk.cell, s.nloc, d_part, grid, grid);
+    launch_spin_measure_reduce(c->stream, d_part, grid, grid, chunks[k].ndiag, 0, d_out + 1 + dfirst, nullptr, k == 0 ? d_out.get() : nullptr);
+  }
+  HIPCHK(hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the staging buffers and the scratch live until here
+  if (norm2) *norm2 = out[0];
+  for (int t = 0; t < n_diag; ++t) diag_out[t] = out[(size_t)(1 + t)];
   return 0;
 }
 
@@ -3583,7 +3758,7 @@ int eigenex_csr_layout(eigenex_csr_t m, int* layout) {
   for (auto& s : m->sh) {
     if (s.blocked) *layout = EIGENEX_LAYOUT_DENSE_BLOCKS;
     else if (s.spin.on()) *layout = s.spin.n_up >= 0 ? EIGENEX_LAYOUT_MATRIX_FREE_SPIN_SECTOR : EIGENEX_LAYOUT_MATRIX_FREE_SPIN;
-    else if (s.momentum.on()) *layout = EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM;
+    else if (s.momentum.on()) *layout = s.momentum.wide ? EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM64 : EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM;
     else if (s.split) *layout = EIGENEX_LAYOUT_SPLIT_TILES;
     else if (s.sorted) *layout = EIGENEX_LAYOUT_SORTED_TILES;
     else if (s.passes > 1 && *layout == EIGENEX_LAYOUT_CSR) *layout = EIGENEX_LAYOUT_COLUMN_BLOCKED;

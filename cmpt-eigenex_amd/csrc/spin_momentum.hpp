@@ -90,8 +90,13 @@ inline std::string spin_momentum_geometry_error(int n_sites, int n_up, int cell,
 }
 
 // "" if the model conserves Sz and is invariant under the translation by `cell` sites (a valid geometry is assumed)
+inline std::string spin_momentum_invariance_error(const SpinModelArgs& a, int cell);
 inline std::string spin_momentum_model_error(const SpinModelArgs& a, int n_up, int cell) {
   if (const char* why = spin_sector_error(a, n_up)) return why;
+  return spin_momentum_invariance_error(a, cell);
+}
+// the invariance half of the check, of a model whose sites and bonds are valid: shared with spin_momentum64.hpp
+inline std::string spin_momentum_invariance_error(const SpinModelArgs& a, int cell) {
   struct Bond {
     int lo, hi;
     uint64_t jz, jxy;

@@ -2,7 +2,7 @@
 // written once for real (E = double) and complex (E = SpinZ) vectors, as k_spin_site_apply<SECTOR, E> is, and through spin_rdm_rows.hpp
 // k_spin_rdm<SECTOR, TILE, E>; at the end of this file the walk of k_spin_momentum_spmv<E> and k_spin_momentum_expand<E>), shared by
 // the device code and by the host replays
-// tests/cpp/spin_{model,sector,measure,site,site_z,rdm,rdm_z,complex,momentum}_sanitize.cpp, which run it under AddressSanitizer +
+// tests/cpp/spin_{model,sector,measure,site,site_z,rdm,rdm_z,complex,momentum,momentum64}_sanitize.cpp, which run it under AddressSanitizer +
 // UBSan.  The kernels and the replays call THESE functions, so what a replay proves about them (every load inside its array, the
 // state equal to spin_sector_unrank, the sums equal to the CSR row loop and to spin_measure_host bit for bit) holds for the
 // kernels' rows as compiled.  No device construct in here: plain C++11.  spin_write_rows, spin_sector_unrank, spin_sector_rank
@@ -42,6 +42,7 @@ namespace eigenex {
 // Parity by population count, one instruction on the device.  Not spin_parity (spin_model.hpp), the folding form of the functions
 // written from the definition: the walk shares no arithmetic with what it is checked against.
 EIGENEX_HD bool spin_odd(uint32_t x) { return (__builtin_popcount(x) & 1) != 0; }
+EIGENEX_HD bool spin_odd(uint64_t x) { return (__builtin_popcountll(x) & 1) != 0; }  // the 64-bit states of spin_momentum64.hpp
 
 // The state of rank r among the states of n_sites sites with n_up up (spin_sector.hpp: unrank), in 32-bit arithmetic: n_sites
 // predicated steps, the same for every lane; k differs between lanes.  left and k end at 0 for every r below the dimension.
@@ -64,6 +65,15 @@ EIGENEX_HD SpinUnranked spin_unrank_row(const Binom& binom, int n_sites, int n_u
 
 // The diagonal entry of row s from the (mask, constant) table of SpinOperatorView: plain additions of sign-flipped constants
 EIGENEX_HD double spin_row_diagonal(const uint32_t* dmask, const double* dval, int ndiag, uint32_t s) {
+  double d = 0.0;
+  for (int t = 0; t < ndiag; ++t) {
+    const double k = dval[t];
+    d += spin_odd(s & dmask[t]) ? -k : k;
+  }
+  return d;
+}
+// ... of a 64-bit state from the 64-bit masks of SpinOperatorView64 (spin_momentum64.hpp): the same additions
+EIGENEX_HD double spin_row_diagonal(const uint64_t* dmask, const double* dval, int ndiag, uint64_t s) {
   double d = 0.0;
   for (int t = 0; t < ndiag; ++t) {
     const double k = dval[t];
@@ -260,21 +270,42 @@ EIGENEX_HD SpinZ spin_site_product(SpinZ w, bool real_coef, SpinZ x) {
 // spin_momentum_write_rows' rows bit for bit: real  yr = add_product_nofma(yr, value.re, xv * scale);  complex  p =
 // spin_cmul_nofma(value, x * scale), yr.re += p.re, yr.im += p.im, the diagonal (d, 0) included: k_spmv_z's stored-order sum.
 // lk.reps(i) and lk.bucket(i) are the two arrays; tb.ratio(i), tb.phase_re(i), tb.phase_im(i), tb.inv_sqrt(i) the tables.
+// The walk is written once for both state words: Word = uint32_t (spin_momentum.hpp, up to 32 sites) and Word = uint64_t
+// (spin_momentum64.hpp, up to 48 sites; k_spin_momentum_spmv<E, uint64_t>).  SpinWord<Word> has what differs besides the width:
+// the pitch of the ratio table and the population count.  The uint32_t instantiations are the functions this file had before
+// the word became a parameter, expression for expression.
 constexpr int kSpinRatioPitch = kSectorMaxSites + 1;  // spin_momentum.hpp: kMomentumRatioPitch
+constexpr int kSpinRatioPitch64 = 48 + 1;             // spin_momentum64.hpp: kMomentum64RatioPitch
+template <class Word>
+struct SpinWord;
+template <>
+struct SpinWord<uint32_t> {
+  static constexpr int kBits = 32, kRatioPitch = kSpinRatioPitch;
+  static EIGENEX_HD int popcount(uint32_t x) { return __builtin_popcount(x); }
+};
+template <>
+struct SpinWord<uint64_t> {
+  static constexpr int kBits = 64, kRatioPitch = kSpinRatioPitch64;
+  static EIGENEX_HD int popcount(uint64_t x) { return __builtin_popcountll(x); }
+};
 
-EIGENEX_HD uint32_t spin_rotate(uint32_t s, int n_sites, int cell, uint32_t site_mask) {
-  return ((s << cell) | (s >> (n_sites - cell))) & site_mask;  // both shifts are 1..31: cell <= n_sites / 2
+template <class Word>
+EIGENEX_HD Word spin_rotate(Word s, int n_sites, int cell, Word site_mask) {
+  return ((s << cell) | (s >> (n_sites - cell))) & site_mask;  // both shifts are 1..31 (1..47 of a 64-bit word): cell <= n_sites / 2
 }
 
 // the representative of the orbit of s, the smallest j >= 0 with T^j s = rep and the period: n_trans rotations, always
-struct SpinOrbit {
-  uint32_t rep;
+template <class Word>
+struct SpinOrbitOf {
+  Word rep;
   int j, period;
 };
-EIGENEX_HD SpinOrbit spin_orbit(uint32_t s, int n_sites, int cell, int n_trans) {
-  const uint32_t site_mask = 0xffffffffu >> (32 - n_sites);
-  SpinOrbit o = {s, 0, n_trans};
-  uint32_t t = s;
+typedef SpinOrbitOf<uint32_t> SpinOrbit;
+template <class Word>
+EIGENEX_HD SpinOrbitOf<Word> spin_orbit(Word s, int n_sites, int cell, int n_trans) {
+  const Word site_mask = Word(~Word(0)) >> (SpinWord<Word>::kBits - n_sites);
+  SpinOrbitOf<Word> o = {s, 0, n_trans};
+  Word t = s;
   bool closed = false;
   for (int r = 1; r <= n_trans; ++r) {
     t = spin_rotate(t, n_sites, cell, site_mask);
@@ -289,13 +320,13 @@ EIGENEX_HD SpinOrbit spin_orbit(uint32_t s, int n_sites, int cell, int n_trans) 
 }
 
 // idx(b) of a representative b of the sector: the lower bound of b in its bucket, `steps` probes
-template <class Lookup>
-EIGENEX_HD uint32_t spin_momentum_index(const Lookup& lk, uint32_t b, int h, int steps) {
-  uint32_t base = lk.bucket(b >> h);
-  uint32_t n = lk.bucket((b >> h) + 1) - base;  // >= 1: b is in there
+template <class Lookup, class Word>
+EIGENEX_HD uint32_t spin_momentum_index(const Lookup& lk, Word b, int h, int steps) {
+  uint32_t base = lk.bucket((uint32_t)(b >> h));  // at most 24 bits are left of a 64-bit state
+  uint32_t n = lk.bucket((uint32_t)(b >> h) + 1) - base;  // >= 1: b is in there
   for (int i = 0; i < steps; ++i) {
     const uint32_t half = n >> 1;
-    const uint32_t v = lk.reps(base + (half ? half - 1 : 0));
+    const Word v = lk.reps(base + (half ? half - 1 : 0));
     base += (half && v < b) ? half : 0u;
     n -= half;
   }
@@ -303,17 +334,17 @@ EIGENEX_HD uint32_t spin_momentum_index(const Lookup& lk, uint32_t b, int h, int
 }
 
 // phase 1 of a batch of bond masks on the row of representative s with period `period`
-template <class Lookup>
-EIGENEX_HD void spin_momentum_targets(const uint32_t* mask, uint32_t s, int period, int n_sites, int cell, int n_trans, uint32_t compatible, int h,
-                                      int steps, const Lookup& lk, bool* on, uint32_t* column, int* ri, int* li) {
+template <class Lookup, class Word>
+EIGENEX_HD void spin_momentum_targets(const Word* mask, Word s, int period, int n_sites, int cell, int n_trans, Word compatible, int h, int steps,
+                                      const Lookup& lk, bool* on, uint32_t* column, int* ri, int* li) {
   EIGENEX_UNROLL
   for (int t = 0; t < kSpinBatch; ++t) {
-    const uint32_t m = mask[t];
-    const bool flips = __builtin_popcount(s & m) == 1;  // two-bit masks only; a zero mask (padding) never
-    const SpinOrbit o = spin_orbit(flips ? s ^ m : s, n_sites, cell, n_trans);
+    const Word m = mask[t];
+    const bool flips = SpinWord<Word>::popcount(s & m) == 1;  // two-bit masks only; a zero mask (padding) never
+    const SpinOrbitOf<Word> o = spin_orbit(flips ? s ^ m : s, n_sites, cell, n_trans);
     on[t] = flips && ((compatible >> (o.period - 1)) & 1u) != 0;
     column[t] = spin_momentum_index(lk, on[t] ? o.rep : s, h, steps);
-    ri[t] = period * kSpinRatioPitch + o.period;
+    ri[t] = period * SpinWord<Word>::kRatioPitch + o.period;
     li[t] = o.j == 0 ? 0 : n_trans - o.j;
   }
 }
@@ -376,6 +407,27 @@ EIGENEX_HD E spin_momentum_expand_row(uint32_t s, int n_sites, int cell, int n_t
   const E xv = x(spin_momentum_index(lk, on ? o.rep : fallback, h, steps));
   const int l = o.j == 0 ? 0 : n_trans - o.j;
   return on ? spin_momentum_expanded(xv, tb.phase_re(l), tb.phase_im(l), tb.inv_sqrt(o.period)) : zero;
+}
+
+// Diagonal correlations in the momentum basis (spin_momentum64.hpp; kernels.hip: k_spin_momentum_measure<E, Word>), one row
+// per lane: w = |x_a|^2 of the row's own element, then for a batch of masks the integer c_t(a) = sum over all n_trans rotations
+// T^r a of the product of sigma over the mask -- the full trip count on every lane -- and one fma per term.
+EIGENEX_HD double spin_momentum_weight(double x) { return x * x; }
+EIGENEX_HD double spin_momentum_weight(SpinZ x) { return std::fma(x.im, x.im, x.re * x.re); }
+template <class Word>
+EIGENEX_HD void spin_momentum_measure_diagonals(double w, Word s, const uint64_t* dmask, int n_sites, int cell, int n_trans, double* dg) {
+  const Word site_mask = Word(~Word(0)) >> (SpinWord<Word>::kBits - n_sites);
+  int c[kSpinBatch];
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) c[t] = 0;
+  Word state = s;
+  for (int r = 0; r < n_trans; ++r) {
+    EIGENEX_UNROLL
+    for (int t = 0; t < kSpinBatch; ++t) c[t] += spin_odd(Word(~state & (Word)dmask[t])) ? -1 : 1;
+    state = spin_rotate(state, n_sites, cell, site_mask);
+  }
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) dg[t] = std::fma((double)c[t], w, dg[t]);
 }
 
 }  // namespace eigenex

@@ -156,6 +156,41 @@ class SpinHalfModel {
     out.rowptr.assign(rp.begin(), rp.end());
     return out;
   }
+  // The same sector on rings of up to 48 sites and 128 bonds, with 64-bit states (eigenex_spin_momentum64_*): what momentumDimension,
+  // momentumStates and toMomentumCsr return for sites <= 32, and the only form beyond.  The enumeration is threaded; (36, 18) walks
+  // 9.1e9 states.
+  Index momentum64Dimension(int nUp, int cell, int m) const {
+    std::int64_t dim = 0;
+    device::check(eigenex_spin_momentum64_dim(sites_, nUp, cell, m, &dim), "eigenex_spin_momentum64_dim");
+    return static_cast<Index>(dim);
+  }
+  std::vector<std::uint64_t> momentum64States(int nUp, int cell, int m, std::vector<std::uint8_t>* periods = nullptr) const {
+    std::vector<std::uint64_t> s(static_cast<std::size_t>(momentum64Dimension(nUp, cell, m)), 0u);
+    if (periods) periods->assign(s.size(), 0);
+    device::check(eigenex_spin_momentum64_states(sites_, nUp, cell, m, 0, static_cast<std::int64_t>(s.size()), s.data(), periods ? periods->data() : nullptr),
+                  "eigenex_spin_momentum64_states");
+    return s;
+  }
+  HostCsr<std::complex<double>> toMomentum64Csr(int nUp, int cell, int m, Index row_begin = 0, Index row_end = -1) const {
+    requireNoTransverseField("SpinHalfModel::toMomentum64Csr");
+    HostCsr<std::complex<double>> out;
+    out.n = momentum64Dimension(nUp, cell, m);
+    if (row_end < 0) row_end = out.n;
+    std::vector<std::int64_t> rp(static_cast<std::size_t>(row_end > row_begin ? row_end - row_begin : 0) + 1, 0);
+    std::int64_t nnz = 0;
+    device::check(eigenex_spin_momentum64_csr(sites_, nUp, cell, m, bonds(), siteI(), siteJ(), jz(), jxy(), fieldZ(), row_begin, row_end - row_begin,
+                                              rp.data(), nullptr, nullptr, &nnz),
+                  "eigenex_spin_momentum64_csr");
+    if (nnz > static_cast<std::int64_t>(std::numeric_limits<std::int32_t>::max()))
+      throw LanczosException("SpinHalfModel::toMomentum64Csr: more than 2^31 - 1 stored entries (use device::spinHalfMomentum64Operator, or fewer rows)");
+    out.col.assign(static_cast<std::size_t>(nnz), 0);
+    out.val.assign(static_cast<std::size_t>(nnz), std::complex<double>(0.0, 0.0));
+    device::check(eigenex_spin_momentum64_csr(sites_, nUp, cell, m, bonds(), siteI(), siteJ(), jz(), jxy(), fieldZ(), row_begin, row_end - row_begin,
+                                              rp.data(), out.col.data(), reinterpret_cast<double*>(out.val.data()), &nnz),
+                  "eigenex_spin_momentum64_csr");
+    out.rowptr.assign(rp.begin(), rp.end());
+    return out;
+  }
   // the momentum entry points take no transverse field: one that is set and not zero is an error here, not silently dropped
   void requireNoTransverseField(const char* who) const {
     for (double h : hx_)
@@ -225,6 +260,23 @@ inline std::shared_ptr<CsrOperator> spinHalfMomentumOperator(std::shared_ptr<Con
     check(eigenex_spin_momentum_upload(ctx->handle(), model.sites(), nUp, cell, m, model.bonds(), model.siteI(), model.siteJ(), model.jz(),
                                        model.jxy(), model.fieldZ(), &h),
           "eigenex_spin_momentum_upload");
+  return CsrOperator::adopt(std::move(ctx), h);
+}
+
+// ... on a ring of up to 48 sites, with 64-bit states (eigenex_spin_momentum64_upload(_z)).  SpinMomentumCorrelationSolver
+// (spin_correlations.hpp) measures a state of either handle; no Sz-sector operator exists beyond 32 sites to expand into.
+inline std::shared_ptr<CsrOperator> spinHalfMomentum64Operator(std::shared_ptr<Context> ctx, const SpinHalfModel& model, int nUp, int m, int cell = 1,
+                                                               bool complexStates = false) {
+  model.requireNoTransverseField("device::spinHalfMomentum64Operator");
+  eigenex_csr_t h = nullptr;
+  if (complexStates)
+    check(eigenex_spin_momentum64_upload_z(ctx->handle(), model.sites(), nUp, cell, m, model.bonds(), model.siteI(), model.siteJ(), model.jz(),
+                                           model.jxy(), model.fieldZ(), &h),
+          "eigenex_spin_momentum64_upload_z");
+  else
+    check(eigenex_spin_momentum64_upload(ctx->handle(), model.sites(), nUp, cell, m, model.bonds(), model.siteI(), model.siteJ(), model.jz(),
+                                         model.jxy(), model.fieldZ(), &h),
+          "eigenex_spin_momentum64_upload");
   return CsrOperator::adopt(std::move(ctx), h);
 }
 

@@ -391,6 +391,60 @@ int eigenex_spin_momentum_upload_z(eigenex_context_t ctx, int n_sites, int n_up,
 int eigenex_spin_momentum_geometry(eigenex_csr_t csr, int* n_sites, int* n_up, int* cell, int* momentum);
 int eigenex_spin_momentum_expand(eigenex_basis_t src_basis, int x_ref, eigenex_basis_t dst_basis, int y_ref, double* norm2);
 int eigenex_spin_momentum_expand_host(int n_sites, int n_up, int cell, int momentum, int is_complex, const double* x, double* y);
+/* Momentum sectors of rings of up to 48 sites: the sector above with 64-bit state words.  NOT part of the reference.  Rows,
+ * basis, row contents, summation order, the values, the "real momentum" rule and the invariance check are those of
+ * eigenex_spin_momentum_upload, word for word; only the limits differ:
+ *   n_sites 2..48; n_bonds 0..128 (a J1-J2 ring of 36 sites has 72); n_up, cell and momentum as above; dim < 2^31 still: a
+ *   sector with more rows is refused with EIGENEX_ERR_ARG.  A state is a uint64_t with site i at bit i.
+ * For n_sites <= 32 and n_bonds <= 64 the three host functions return what their 32-bit namesakes return, byte for byte.
+ *   eigenex_spin_momentum64_dim, _states (uint64_t states), _csr   host code: no context, no GPU.  The enumeration cuts the Sz
+ *                                   sector by the top 16 bits of the state into chunks that up to 16 threads take in turn, skips a
+ *                                   chunk whose prefix alone shows a smaller rotation, and joins the chunks in ascending order:
+ *                                   the list is the plain ascending walk's.
+ *   eigenex_spin_momentum64_upload(_z)  the matrix-free operator (layout EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM64, a context with
+ *                                   one shard in total).  The device holds the representatives at 8 bytes per row and the bucket
+ *                                   table, 2^(n_sites - (n_sites + 1) / 2) + 1 words, at most 2^24 + 1.  eigenex_apply is
+ *                                   bit-identical to eigenex_csr_upload(_z) of eigenex_spin_momentum64_csr's rows.  All argument
+ *                                   checks happen before the context is touched.  Lanczos, the Chebyshev filter and the KPM
+ *                                   moments run on the handle as on every other operator.
+ * eigenex_spin_momentum_geometry answers for these handles too.  eigenex_spin_momentum_expand refuses them with EIGENEX_ERR_STATE
+ * before anything is allocated -- no Sz-sector operator exists beyond 32 sites; for n_sites <= 32 use eigenex_spin_momentum_upload
+ * -- and eigenex_spin_geometry, eigenex_spin_measure, eigenex_spin_rdm(_z) and eigenex_spin_site_apply(_z) refuse them as they
+ * refuse every handle that is not theirs. */
+int eigenex_spin_momentum64_dim(int n_sites, int n_up, int cell, int momentum, int64_t* dim);
+int eigenex_spin_momentum64_states(int n_sites, int n_up, int cell, int momentum, int64_t first, int64_t count, uint64_t* states,
+                                   uint8_t* periods_or_null);
+int eigenex_spin_momentum64_csr(int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
+                                const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null,
+                                int64_t row_begin, int64_t n_rows, int64_t* rowptr, int32_t* col, double* val_interleaved, int64_t* nnz);
+int eigenex_spin_momentum64_upload(eigenex_context_t ctx, int n_sites, int n_up, int cell, int momentum, int n_bonds,
+                                   const int32_t* site_i, const int32_t* site_j, const double* jz, const double* jxy,
+                                   const double* hz_or_null, eigenex_csr_t* out);
+int eigenex_spin_momentum64_upload_z(eigenex_context_t ctx, int n_sites, int n_up, int cell, int momentum, int n_bonds,
+                                     const int32_t* site_i, const int32_t* site_j, const double* jz, const double* jxy,
+                                     const double* hz_or_null, eigenex_csr_t* out);
+/* Diagonal correlations of a vector x of a momentum sector, without expanding it.  NOT part of the reference.  For a product D of
+ * sigma^z over a site mask and a momentum eigenstate x, <D> = sum_a |x_a|^2 (1/N) sum_{r<N} D(T^r a) over the representatives a:
+ * D is diagonal and distinct orbits are disjoint, so no cross term appears.  (For a vector that is no momentum eigenstate the sums
+ * below are still what is computed; they are then the expectation in the translation average of |x><x|.)  Raw sums, rows ascending:
+ *   norm2       = sum_a |x_a|^2              one fma per row of a real x, two of a complex one (real part, then imaginary part)
+ *   diag_out[t] = sum_a c_t(a) w_a           one fma per row, fma((double)c_t(a), w_a, diag_out[t]);
+ *                                            w_a = x_a * x_a, of a complex element fma(im, im, re * re)
+ *   c_t(a)      = sum_{r<N} prod_{i in mask_t} sigma_i(T^r a), an integer in [-N, N]; sigma_i(s) = +1 if bit i of s is set, else -1
+ * so that <D_t> = diag_out[t] / (N norm2): <Sz_i Sz_j> = diag{i,j} / (4 N norm2), and for a singlet of an SU(2)-symmetric model
+ * <S_i . S_j> = 3 <Sz_i Sz_j>.  masks: 0..1024 64-bit site masks (bit i = site i), none zero, none with a site >= n_sites
+ * (EIGENEX_ERR_ARG); n_diag = 0 returns norm2 alone.
+ *   eigenex_spin_momentum_measure_host  the definition in host code; x holds 1 (is_complex = 0) or 2 doubles per row of the
+ *                                   sector (n_sites up to 48).
+ *   eigenex_spin_momentum_measure   on the device, for a vector of a real or complex state on a handle of
+ *                                   eigenex_spin_momentum_upload(_z) or eigenex_spin_momentum64_upload(_z); any other handle is
+ *                                   EIGENEX_ERR_STATE.  16 masks per sweep: x and the representatives stream once per sweep, no
+ *                                   vector is written, partial sums are reduced in a fixed order without atomics, so results are
+ *                                   bit-reproducible and a term does not depend on the other masks of the call.  No vector,
+ *                                   coefficient or recorded step batch of the state is touched.  Synchronises once. */
+int eigenex_spin_momentum_measure(eigenex_basis_t basis, int x_ref, int n_diag, const uint64_t* masks, double* diag_out, double* norm2);
+int eigenex_spin_momentum_measure_host(int n_sites, int n_up, int cell, int momentum, int is_complex, const double* x, int n_diag,
+                                       const uint64_t* masks, double* diag_out, double* norm2);
 /* Spin correlations of a real vector x over the rows of a matrix-free spin operator, all terms in one sweep: x is read once
  * per 16 terms of each list and nothing is written but the sums.  A measurement is two lists of 32-bit site masks (bit i = site
  * i); with sigma_i(s) as above it yields the raw, unnormalised sums
@@ -541,7 +595,8 @@ int eigenex_csr_column_blocks(eigenex_csr_t csr, int* passes);
 enum { EIGENEX_LAYOUT_CSR = 0, EIGENEX_LAYOUT_COLUMN_BLOCKED = 1, EIGENEX_LAYOUT_SORTED_TILES = 2, EIGENEX_LAYOUT_DENSE_BLOCKS = 3,
        EIGENEX_LAYOUT_SPLIT_TILES = 4, EIGENEX_LAYOUT_MATRIX_FREE_SPIN = 5 /* eigenex_spin_upload: nothing stored */,
        EIGENEX_LAYOUT_MATRIX_FREE_SPIN_SECTOR = 6 /* eigenex_spin_sector_upload: two rank tables, no rows */,
-       EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM = 7 /* eigenex_spin_momentum_upload: one representative per row and a bucket table */ };
+       EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM = 7 /* eigenex_spin_momentum_upload: one representative per row and a bucket table */,
+       EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM64 = 8 /* eigenex_spin_momentum64_upload: the same with 64-bit states, up to 48 sites */ };
 int eigenex_csr_layout(eigenex_csr_t csr, int* layout);
 /* how the entries of an EIGENEX_LAYOUT_CSR operator are encoded.  EIGENEX_ENCODING_ROW_CODES: a real operator in one pass
  * whose rows use at most 16 column offsets (col - row, halo columns in local numbering) and at most 255 bitwise-distinct

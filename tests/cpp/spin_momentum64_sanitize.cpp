@@ -1,0 +1,306 @@
+// csrc/spin_momentum64.hpp and the 64-bit momentum walk of csrc/spin_rows.hpp under AddressSanitizer + UBSan, stand-alone (no
+// library, no GPU):
+//   g++ -std=c++11 -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -pthread -I cmpt-eigenex_amd/csrc spin_momentum64_sanitize.cpp
+// For every shape: the threaded, pruned enumeration against the plain ascending walk, the buckets and the search's trip count;
+// then the row walk of k_spin_momentum_spmv<E, uint64_t> -- the kernel's own functions on the real tables, every load
+// bounds-checked -- whose sum per row must equal, bit for bit, the sum over the entries spin_momentum64_write_rows wrote for that
+// row, added the way k_spmv / k_spmv_z add them; and the walk of k_spin_momentum_measure<E, Word> against
+// spin_momentum_measure_host, bit for bit, with both words where the ring has at most 32 sites.  33, 36 and 48 sites are among the
+// shapes, so that UBSan sees every shift of the 64-bit rotation.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "spin_momentum64.hpp"
+#include "spin_rows_checked.hpp"
+
+using namespace eigenex;
+
+struct CheckedLookup64 {
+  const SpinMomentum64Basis* b;
+  std::uint64_t reps(std::uint32_t i) const { return b->reps.at(i); }
+  std::uint32_t bucket(std::uint32_t i) const { return b->bucket.at(i); }
+};
+struct CheckedMomentum64Tables {
+  const SpinMomentum64Tables* t;
+  double ratio(int i) const {
+    EXPECT(i >= 0 && i < kMomentum64RatioPitch * kMomentum64RatioPitch);
+    return t->ratio[i];
+  }
+  double phase_re(int i) const {
+    EXPECT(i >= 0 && i < kMomentum64MaxPeriod);
+    return t->phase_re[i];
+  }
+  double phase_im(int i) const {
+    EXPECT(i >= 0 && i < kMomentum64MaxPeriod);
+    return t->phase_im[i];
+  }
+};
+struct CheckedVectorZ {
+  const std::vector<double>* x;  // interleaved
+  SpinZ operator()(std::uint32_t i) const { return SpinZ{x->at(2 * (std::size_t)i), x->at(2 * (std::size_t)i + 1)}; }
+};
+
+static double element_of(const CheckedVector& x, std::uint32_t i) { return x(i); }
+static SpinZ element_of(const CheckedVectorZ& x, std::uint32_t i) { return x(i); }
+static bool same(double a, double b) { return std::memcmp(&a, &b, 8) == 0; }
+static bool same(SpinZ a, SpinZ b) { return same(a.re, b.re) && same(a.im, b.im); }
+
+// a deterministic vector with both signs and some spread of magnitudes
+static std::vector<double> test_vector(std::size_t n, std::uint64_t seed) {
+  std::vector<double> x(n);
+  std::uint64_t s = seed * 0x9E3779B97F4A7C15ull + 1;
+  for (std::size_t i = 0; i < n; ++i) {
+    s = s * 6364136223846793005ull + 1442695040888963407ull;
+    x[i] = ((double)(std::int64_t)(s >> 11) / (double)(1ull << 52) - 1.0) * (1.0 + (double)(i % 7));
+  }
+  return x;
+}
+
+// the row walk of k_spin_momentum_spmv<E, uint64_t> on row r, before the shift
+template <class E, class Vector>
+static E walk_row(const SpinMomentum64View& v, const SpinMomentum64Basis& b, const Vector& xs, std::int64_t r, double scale) {
+  const CheckedLookup64 lk{&b};
+  const CheckedMomentum64Tables tb{&v.tab};
+  const SpinOperatorView64& m = v.model;
+  const std::uint64_t s = lk.reps((std::uint32_t)r);
+  const int period = spin_orbit(s, m.n_sites, v.cell, v.n_trans).period;
+  EXPECT(period == b.period.at((std::size_t)r));
+  const double d = spin_row_diagonal(m.dmask, m.dval, m.ndiag, s);
+  E yr = spin_momentum_add(E{}, SpinZ{d, 0.0}, element_of(xs, (std::uint32_t)r), scale);
+  for (int t0 = 0; t0 < m.nflip; t0 += kSpinBatch) {
+    EXPECT(t0 + kSpinBatch <= kMomentum64MaxTerms);
+    bool on[kSpinBatch];
+    std::uint32_t column[kSpinBatch];
+    int ri[kSpinBatch], li[kSpinBatch];
+    E xv[kSpinBatch];
+    spin_momentum_targets(m.fmask + t0, s, period, m.n_sites, v.cell, v.n_trans, v.compatible, v.h, v.steps, lk, on, column, ri, li);
+    for (int t = 0; t < kSpinBatch; ++t) {
+      if (!on[t]) EXPECT(column[t] == (std::uint32_t)r);  // a lane without the term reads its own element
+      if (m.fmask[t0 + t] == 0) EXPECT(!on[t]);
+      EXPECT(li[t] >= 0 && li[t] < v.n_trans);
+    }
+    spin_momentum_gather(xs, column, xv);
+    yr = spin_momentum_add_flips(yr, m.fval + t0, tb, on, ri, li, xv, scale);
+  }
+  return yr;
+}
+
+// the sum over the stored entries of one row as k_spmv (val.re) and k_spmv_z add them
+static double csr_row(const std::int32_t* col, const double* val, std::int64_t p0, std::int64_t p1, const CheckedVector& x, double scale) {
+  double sum = 0.0;
+  for (std::int64_t p = p0; p < p1; ++p) sum = add_product_nofma(sum, val[2 * p], x((std::uint32_t)col[p]) * scale);
+  return sum;
+}
+static SpinZ csr_row(const std::int32_t* col, const double* val, std::int64_t p0, std::int64_t p1, const CheckedVectorZ& x, double scale) {
+  SpinZ sum = {0.0, 0.0};
+  for (std::int64_t p = p0; p < p1; ++p) {
+    const SpinZ xv = x((std::uint32_t)col[p]);
+    const double xr = xv.re * scale, xi = xv.im * scale;
+    const double a = val[2 * p] * xr, bb = val[2 * p + 1] * xi, c = val[2 * p] * xi, d = val[2 * p + 1] * xr;
+    const double pr = a - bb, pi = c + d;
+    sum.re = sum.re + pr;
+    sum.im = sum.im + pi;
+  }
+  return sum;
+}
+
+struct Model {
+  int n_sites;
+  std::vector<std::int32_t> si, sj;
+  std::vector<double> jz, jxy, hz;
+  SpinModelArgs args() const {
+    return SpinModelArgs{n_sites, (int)si.size(), si.data(), sj.data(), jz.data(), jxy.data(), hz.empty() ? nullptr : hz.data(), nullptr};
+  }
+};
+// a ring invariant under the translation by `cell` sites: nearest neighbours and, with `far`, bonds of that reach, couplings and hz by place in the cell
+static Model ring(int L, int cell, int far) {
+  Model m;
+  m.n_sites = L;
+  for (int i = 0; i < L; ++i) {
+    const int p = i % cell;
+    m.si.push_back(i), m.sj.push_back((i + 1) % L), m.jz.push_back(0.7 + 0.25 * p), m.jxy.push_back(1.1 + 0.125 * p);
+    if (far > 1) m.si.push_back((i + far) % L), m.sj.push_back(i), m.jz.push_back(0.3 - 0.05 * p), m.jxy.push_back(p == 1 ? 0.0 : 0.2 + 0.0625 * p);
+  }
+  if (cell > 1)
+    for (int i = 0; i < L; ++i) m.hz.push_back(0.1 * (1 + i % cell));
+  return m;
+}
+
+template <class E, class Vector>
+static void check_rows(const SpinModelArgs& a, const SpinMomentum64View& v, const SpinMomentum64Basis& b, const std::vector<double>& x, double scale) {
+  const std::int64_t dim = (std::int64_t)b.reps.size();
+  const std::int64_t begin = dim > 3 ? 1 : 0, n_rows = dim - begin;  // a range from the middle
+  std::vector<std::int64_t> rowptr((std::size_t)n_rows + 1);
+  std::int64_t nnz = 0, again = 0;
+  spin_momentum64_write_rows(a, b, v.tab, begin, n_rows, rowptr.data(), nullptr, nullptr, &nnz);
+  std::vector<std::int32_t> col((std::size_t)nnz);
+  std::vector<double> val((std::size_t)(2 * nnz));  // exactly sized: a write behind the count is a heap overflow
+  spin_momentum64_write_rows(a, b, v.tab, begin, n_rows, rowptr.data(), col.data(), val.data(), &again);
+  EXPECT(again == nnz && rowptr.back() == nnz);
+  const Vector xs{&x};
+  for (std::int64_t k = 0; k < n_rows; ++k) {
+    for (std::int64_t p = rowptr[(std::size_t)k]; p < rowptr[(std::size_t)k + 1]; ++p) EXPECT(col[(std::size_t)p] >= 0 && col[(std::size_t)p] < dim);
+    EXPECT(col[(std::size_t)rowptr[(std::size_t)k]] == begin + k);  // the diagonal first
+    const E walked = walk_row<E>(v, b, xs, begin + k, scale);
+    const E stored = csr_row(col.data(), val.data(), rowptr[(std::size_t)k], rowptr[(std::size_t)k + 1], xs, scale);
+    EXPECT(same(walked, stored));
+  }
+  if (spin_momentum_is_real(b.n_trans, b.momentum))
+    for (std::int64_t p = 0; p < nnz; ++p) EXPECT(same(val[(std::size_t)(2 * p + 1)], 0.0));
+}
+
+// the sums of k_spin_momentum_measure<E, Word> over all rows in ascending order, chunk by chunk, against the host definition
+template <class Word, class States>
+static void check_measure(const SpinMomentum64Basis& b, const States& states, const std::vector<double>& x, bool is_complex) {
+  const int L = b.n_sites;
+  std::vector<std::uint64_t> masks;
+  for (int i = 0; i < L; i += 5) masks.push_back(std::uint64_t(1) << i);
+  for (int r = 1; r < L; r += 2) masks.push_back(std::uint64_t(1) | (std::uint64_t(1) << r));
+  masks.push_back((std::uint64_t(1) << (L - 1)) | 3u);
+  masks.push_back(spin_momentum64_site_mask(L));
+  const SpinMomentumMeasureArgs a{L, (int)masks.size(), masks.data()};
+  EXPECT(spin_momentum_measure_error(a) == nullptr);
+  std::vector<double> want(masks.size());  // exactly sized
+  double want_norm = 0.0;
+  spin_momentum_measure_host(b, a, is_complex, x.data(), want.data(), &want_norm);
+  std::vector<SpinMomentumMeasureChunk> chunks;
+  spin_momentum_measure_build_chunks(a, chunks);
+  EXPECT(chunks.size() == (masks.size() + kSpinMeasureChunk - 1) / kSpinMeasureChunk);
+  for (std::size_t k = 0; k < chunks.size(); ++k) {
+    double nrm = 0.0, dg[kSpinMeasureChunk] = {0.0};
+    for (std::size_t r = 0; r < b.reps.size(); ++r) {
+      const Word s = states.at(r);
+      double w;
+      if (is_complex) {
+        const SpinZ xs = SpinZ{x.at(2 * r), x.at(2 * r + 1)};
+        nrm = spin_norm_add(nrm, xs), w = spin_momentum_weight(xs);
+      } else {
+        nrm = spin_norm_add(nrm, x.at(r)), w = spin_momentum_weight(x.at(r));
+      }
+      for (int t0 = 0; t0 < kSpinMeasureChunk; t0 += kSpinBatch)
+        if (t0 < chunks[k].ndiag) spin_momentum_measure_diagonals(w, s, chunks[k].dmask + t0, L, b.cell, b.n_trans, dg + t0);
+    }
+    EXPECT(same(nrm, want_norm));
+    for (int t = 0; t < chunks[k].ndiag; ++t) EXPECT(same(dg[t], want.at(k * kSpinMeasureChunk + (std::size_t)t)));
+  }
+}
+
+// the plain ascending walk of the Sz sector, from the definition
+static void plain_rows(int L, int n_up, int cell, int m, std::vector<std::uint64_t>& reps, std::vector<std::uint8_t>& period) {
+  const int N = L / cell;
+  const std::uint64_t end = std::uint64_t(1) << L;
+  for (std::uint64_t s = n_up == 0 ? 0 : (std::uint64_t(1) << n_up) - 1; s < end;) {
+    const SpinMomentum64Orbit o = spin_momentum64_orbit_host(s, L, cell);
+    if (o.rep == s && (m * o.period) % N == 0) reps.push_back(s), period.push_back((std::uint8_t)o.period);
+    if (n_up == 0) break;
+    const std::uint64_t c = s & (~s + 1), r = s + c;
+    s = (((r ^ s) >> 2) / c) | r;
+  }
+}
+
+static void check_shape(int L, int n_up, int cell, int far) {
+  const int N = L / cell;
+  const Model model = ring(L, cell, far);
+  const SpinModelArgs a = model.args();
+  EXPECT(spin_momentum64_model_error(a, cell).empty());
+  std::int64_t total = 0;
+  for (int m = 0; m < N; ++m) {
+    EXPECT(spin_momentum64_geometry_error(L, n_up, cell, m).empty());
+    if (N > 13 && !(m <= 1 || m == N / 2 || m == N - 1)) {  // the dimensions of all, the walks of four
+      total += spin_momentum64_build_basis(L, n_up, cell, m, nullptr);
+      continue;
+    }
+    SpinMomentum64Basis b;
+    const std::int64_t dim = spin_momentum64_build_basis(L, n_up, cell, m, &b);
+    EXPECT(dim == (std::int64_t)b.reps.size() && dim == spin_momentum64_build_basis(L, n_up, cell, m, nullptr));
+    total += dim;
+    std::vector<std::uint64_t> plain;
+    std::vector<std::uint8_t> plain_period;
+    plain_rows(L, n_up, cell, m, plain, plain_period);
+    EXPECT(plain == b.reps && plain_period == b.period);  // the chunks and the pruning change nothing
+    if (dim == 0) continue;
+    EXPECT(b.bucket.size() == (std::size_t(1) << (L - b.h)) + 1 && b.bucket.front() == 0 && b.bucket.back() == dim);
+    std::size_t largest = 0;
+    for (std::size_t i = 0; i + 1 < b.bucket.size(); ++i) largest = std::max(largest, (std::size_t)(b.bucket[i + 1] - b.bucket[i]));
+    EXPECT((std::size_t(1) << b.steps) >= largest + 1 && (b.steps == 0 || (std::size_t(1) << (b.steps - 1)) < largest + 1));
+    const CheckedLookup64 lk{&b};
+    for (std::int64_t r = 0; r < dim; ++r) {
+      EXPECT(spin_momentum_index(lk, b.reps[(std::size_t)r], b.h, b.steps) == (std::uint32_t)r);
+      const SpinMomentum64Orbit o = spin_momentum64_orbit_host(b.reps[(std::size_t)r], L, cell);
+      const SpinOrbitOf<std::uint64_t> w = spin_orbit(b.reps[(std::size_t)r], L, cell, N);
+      EXPECT(w.rep == o.rep && w.j == o.j && w.period == o.period && N % o.period == 0);
+    }
+    std::unique_ptr<SpinMomentum64View> v(new SpinMomentum64View());
+    spin_momentum64_build_view(a, b, *v);
+    EXPECT(v->first_rep == b.reps[0] && v->model.ndiag <= kMomentum64MaxTerms && v->model.nflip <= kMomentum64MaxTerms);
+    const std::vector<double> xz = test_vector((std::size_t)(2 * dim), 17 + (std::uint64_t)m);
+    check_rows<SpinZ, CheckedVectorZ>(a, *v, b, xz, 1.0);
+    check_rows<SpinZ, CheckedVectorZ>(a, *v, b, xz, -0.37);
+    check_measure<std::uint64_t>(b, b.reps, xz, true);
+    const std::vector<double> x = test_vector((std::size_t)dim, 5 + (std::uint64_t)m);
+    check_measure<std::uint64_t>(b, b.reps, x, false);
+    if (spin_momentum_is_real(N, m)) {
+      check_rows<double, CheckedVector>(a, *v, b, x, 1.0);
+      check_rows<double, CheckedVector>(a, *v, b, x, 1.7);
+    }
+    if (L <= 32) {  // the 32-bit sector: the same rows, and the measurement walk on 32-bit words
+      SpinMomentumBasis b32;
+      EXPECT(spin_momentum_build_basis(L, n_up, cell, m, &b32) == dim && b32.period == b.period && b32.bucket == b.bucket && b32.steps == b.steps);
+      for (std::int64_t r = 0; r < dim; ++r) EXPECT((std::uint64_t)b32.reps[(std::size_t)r] == b.reps[(std::size_t)r]);
+      check_measure<std::uint32_t>(b, b32.reps, xz, true);
+      check_measure<std::uint32_t>(b, b32.reps, x, false);
+    }
+  }
+  std::int64_t binom = 1;  // C(L, n_up)
+  for (int i = 1; i <= n_up; ++i) binom = binom * (L - n_up + i) / i;
+  EXPECT(total == binom);  // the momentum sectors tile the Sz sector
+}
+
+int main() {
+  // every state's orbit by the kernel's walk against the definition's, on a ring where every period occurs, in the high bits too
+  for (std::uint64_t s = 0; s < (1u << 12); ++s)
+    for (int cell = 1; cell <= 6; ++cell) {
+      if (12 % cell) continue;
+      const SpinMomentum64Orbit o = spin_momentum64_orbit_host(s, 12, cell);
+      const SpinOrbitOf<std::uint64_t> w = spin_orbit(s, 12, cell, 12 / cell);
+      EXPECT(w.rep == o.rep && w.j == o.j && w.period == o.period);
+      const std::uint64_t wide = s | (s << 12) | (s << 24) | (s << 36);  // 48 sites, the same period
+      const SpinMomentum64Orbit ow = spin_momentum64_orbit_host(wide, 48, cell);
+      const SpinOrbitOf<std::uint64_t> ww = spin_orbit(wide, 48, cell, 48 / cell);
+      EXPECT(ww.rep == ow.rep && ww.j == ow.j && ww.period == ow.period && ow.period == o.period);
+    }
+  EXPECT(spin_momentum64_translate((std::uint64_t(1) << 47) | 1u, 48, 1) == 3u && spin_momentum64_translate(0xffffff000000ull, 48, 24) == 0xffffffull);
+  EXPECT(spin_momentum64_translate((std::uint64_t(1) << 32) | 1u, 33, 1) == 3u);
+  const int shapes[][4] = {{2, 1, 1, 0},   {8, 4, 1, 0},   {12, 6, 2, 5},  {16, 8, 1, 0},  {24, 3, 1, 0},  {32, 3, 2, 15}, {33, 2, 1, 0},  {33, 3, 3, 4},
+                           {34, 2, 1, 0},  {36, 3, 1, 2},  {36, 4, 2, 17}, {36, 2, 18, 0}, {40, 2, 4, 19}, {48, 3, 1, 0},  {48, 2, 24, 0}, {48, 47, 1, 0},
+                           {48, 0, 1, 0},  {48, 48, 2, 0}};
+  for (const auto& s : shapes) check_shape(s[0], s[1], s[2], s[3]);
+  // refusals
+  {
+    EXPECT(!spin_momentum64_geometry_error(49, 4, 1, 0).empty() && spin_momentum64_geometry_error(48, 4, 1, 47).empty() &&
+           !spin_momentum64_geometry_error(48, 4, 1, 48).empty() && !spin_momentum64_geometry_error(48, 4, 5, 0).empty() &&
+           !spin_momentum64_geometry_error(48, 49, 1, 0).empty() && !spin_momentum64_geometry_error(48, 4, 48, 0).empty());
+    Model open = ring(36, 1, 0);
+    open.si.pop_back(), open.sj.pop_back(), open.jz.pop_back(), open.jxy.pop_back();
+    EXPECT(spin_momentum64_model_error(open.args(), 1).find("bond") != std::string::npos);
+    Model many = ring(43, 1, 2);
+    for (int i = 0; i < 43; ++i) many.si.push_back(i), many.sj.push_back((i + 3) % 43), many.jz.push_back(0.1), many.jxy.push_back(0.1);
+    EXPECT(many.si.size() == 129 && spin_momentum64_model_error(many.args(), 1) == "n_bonds must be 0..128");
+    many.si.pop_back(), many.sj.pop_back(), many.jz.pop_back(), many.jxy.pop_back();
+    EXPECT(spin_momentum64_model_error(many.args(), 1).find("not invariant") != std::string::npos);  // 128 bonds are counted, then checked
+    const std::uint64_t bad[2] = {1u, std::uint64_t(1) << 36}, zero[2] = {1u, 0u};
+    EXPECT(spin_momentum_measure_error(SpinMomentumMeasureArgs{36, 2, bad}) != nullptr && spin_momentum_measure_error(SpinMomentumMeasureArgs{36, 2, zero}) != nullptr &&
+           spin_momentum_measure_error(SpinMomentumMeasureArgs{37, 2, bad}) == nullptr && spin_momentum_measure_error(SpinMomentumMeasureArgs{36, 0, nullptr}) == nullptr);
+    EXPECT(spin_momentum64_build_basis(36, 0, 1, 1, nullptr) == 0 && spin_momentum64_build_basis(40, 4, 1, 0, nullptr) == 2290 &&
+           spin_momentum64_build_basis(36, 5, 1, 0, nullptr) == 10472);
+  }
+  if (fails) {
+    std::fprintf(stderr, "%d check(s) failed\n", fails);
+    return 1;
+  }
+  std::printf("SPIN MOMENTUM64 OK\n");
+  return 0;
+}

@@ -1,0 +1,298 @@
+"""Momentum sectors of up to 48 sites on the host: eigenex_spin_momentum64_dim / _states / _csr against the 32-bit functions byte
+for byte where both exist and against tests/spin_momentum64_reference.py beyond 32 sites, eigenex_spin_momentum_measure_host against
+the reference and against expand + eigenex_spin_measure_host, the refusals with their messages, and the host code and the 64-bit
+row walk (csrc/spin_momentum64.hpp, csrc/spin_rows.hpp) under AddressSanitizer + UBSan in a stand-alone program.  No GPU."""
+import os
+import re
+import shutil
+import subprocess
+import sys
+from math import comb, cos, pi
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import spin_momentum64_reference as ref  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EPS = np.finfo(np.float64).eps
+
+
+@pytest.fixture(scope="module")
+def capi():
+    import __graft_entry__ as g
+
+    g.build()
+    from cmpt_eigenex_amd import capi as c
+
+    return c
+
+
+def _model(L, cell):
+    return (ref.xxz_ring(L, 1.0, 0.7), None) if cell == 1 else ref.cell_model(L, cell)
+
+
+def _momenta(L, cell):
+    N = L // cell
+    return range(N) if L <= 12 else sorted({0, 1, N // 2})
+
+
+# ---- 1. the reference against itself (passes without the feature) ----
+def test_reference_counts_are_the_necklace_formula():
+    assert ref.necklace_count(40, 4) == 2290 and ref.necklace_count(36, 5) == 10472
+    assert ref.necklace_count(36, 18) == 252088496 and ref.necklace_count(38, 19) == 930138522 and ref.necklace_count(40, 10) == 21191904
+    assert len(ref.representatives(34, 2, 1, 0)) == 17 and len(ref.representatives(36, 3, 1, 0)) == 199 == ref.necklace_count(36, 3)
+    assert ref.translate(1 << 35 | 1, 36, 1) == 3 and ref.orbit(0b110 << 30, 36, 1) == (3, 5, 36)
+
+
+# ---- 2. up to 32 sites: the 32-bit functions' bytes ----
+@pytest.mark.parametrize("L,n_up,cell", [(8, 4, 1), (12, 6, 2), (16, 8, 1), (32, 3, 1)])
+def test_up_to_32_sites_the_outputs_are_the_32_bit_functions(capi, L, n_up, cell):
+    bonds, hz = _model(L, cell)
+    for m in _momenta(L, cell):
+        try:
+            want = capi.spin_momentum_dim(L, n_up, m, cell)
+        except capi.EigenexError:
+            with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum64_dim: the sector is empty"):
+                capi.spin_momentum64_dim(L, n_up, m, cell)
+            continue
+        assert capi.spin_momentum64_dim(L, n_up, m, cell) == want
+        s32, p32 = capi.spin_momentum_states(L, n_up, m, cell)
+        s64, p64 = capi.spin_momentum64_states(L, n_up, m, cell)
+        assert s64.dtype == np.uint64 and p64.dtype == np.uint8
+        assert s64.tobytes() == s32.astype(np.uint64).tobytes() and p64.tobytes() == p32.tobytes()
+        a, b = want // 3, want - want // 4  # a window of rows
+        sw, pw = capi.spin_momentum64_states(L, n_up, m, cell, a, b - a)
+        assert sw.tobytes() == s64[a:b].tobytes() and pw.tobytes() == p64[a:b].tobytes()
+        for got, exp in zip(capi.spin_momentum64_csr(L, n_up, m, bonds, hz, cell), capi.spin_momentum_csr(L, n_up, m, bonds, hz, cell)):
+            assert got.dtype == exp.dtype and got.tobytes() == exp.tobytes()
+        for got, exp in zip(capi.spin_momentum64_csr(L, n_up, m, bonds, hz, cell, row_begin=a, n_rows=b - a),
+                            capi.spin_momentum_csr(L, n_up, m, bonds, hz, cell, row_begin=a, n_rows=b - a)):
+            assert got.tobytes() == exp.tobytes()
+
+
+# ---- 3. beyond 32 sites: the reference ----
+BEYOND = [(34, 2, 1), (36, 3, 1), (48, 3, 1), (36, 4, 2)]
+
+
+@pytest.fixture(scope="module")
+def rows():
+    """the reference's rows of a sector, computed once"""
+    cache = {}
+
+    def get(L, n_up, cell, m):
+        if (L, n_up, cell, m) not in cache:
+            cache[(L, n_up, cell, m)] = ref.representatives(L, n_up, cell, m)
+        return cache[(L, n_up, cell, m)]
+
+    return get
+
+
+@pytest.mark.parametrize("L,n_up,cell", BEYOND)
+def test_dim_states_and_periods_equal_the_reference(capi, rows, L, n_up, cell):
+    for m in _momenta(L, cell):
+        want = rows(L, n_up, cell, m)
+        assert capi.spin_momentum64_dim(L, n_up, m, cell) == len(want)
+        states, periods = capi.spin_momentum64_states(L, n_up, m, cell)
+        assert states.tolist() == [s for s, _ in want] and periods.tolist() == [p for _, p in want]
+    if cell == 1:
+        assert len(rows(L, n_up, cell, 0)) == {(34, 2): 17, (36, 3): 199, (48, 3): 361}[(L, n_up)]
+
+
+def test_necklace_counts_of_larger_sectors(capi):
+    assert capi.spin_momentum64_dim(40, 4, 0) == 2290 == ref.necklace_count(40, 4)
+    assert capi.spin_momentum64_dim(36, 5, 0) == 10472 == ref.necklace_count(36, 5)
+
+
+@pytest.mark.parametrize("L,n_up,cell", [(34, 2, 1), (36, 3, 1), (48, 3, 1), (36, 4, 2), (40, 2, 4), (48, 2, 24)])
+def test_block_dimensions_add_up_to_the_sector(capi, L, n_up, cell):
+    total = 0
+    for m in range(L // cell):
+        try:
+            total += capi.spin_momentum64_dim(L, n_up, m, cell)
+        except capi.EigenexError as e:
+            assert "the sector is empty" in str(e)
+    assert total == comb(L, n_up)
+
+
+def _models_beyond(L, cell):
+    """a ring; at 36 sites a J1-J2 ring with 72 bonds; each with and without a cell-periodic hz"""
+    if cell > 1:
+        bonds, hz = ref.cell_model(L, cell)
+        return [("cell", bonds, hz), ("cell, no field", bonds, None)]
+    uniform = [0.3] * L
+    out = [("ring", ref.xxz_ring(L, 1.0, 0.7), None), ("ring, hz", ref.xxz_ring(L, 1.0, 0.7), uniform)]
+    if L == 36:
+        j1j2 = ref.xxz_ring(L, 1.0, 0.9, reach=(1, 2))
+        assert len(j1j2) == 72
+        out += [("J1-J2", j1j2, None), ("J1-J2, hz", j1j2, uniform)]
+    return out
+
+
+@pytest.mark.parametrize("L,n_up,cell", BEYOND)
+def test_rows_equal_the_reference_block_and_are_hermitian(capi, rows, L, n_up, cell):
+    for name, bonds, hz in _models_beyond(L, cell):
+        for m in _momenta(L, cell):
+            reps = rows(L, n_up, cell, m)
+            n = len(reps)
+            rowptr, col, val = capi.spin_momentum64_csr(L, n_up, m, bonds, hz, cell)
+            assert rowptr.dtype == np.int64 and col.dtype == np.int32 and val.dtype == np.complex128 and rowptr[-1] == col.size == val.size
+            assert rowptr.size == n + 1 and np.array_equal(col[rowptr[:-1]], np.arange(n))  # the diagonal first
+            assert col.min() >= 0 and col.max() < n
+            got = {}
+            row_of = np.repeat(np.arange(n), np.diff(rowptr))
+            for r, c, v in zip(row_of.tolist(), col.tolist(), val.tolist()):
+                got[(r, c)] = got.get((r, c), 0.0) + v
+            want, bound = ref.block_entries(L, n_up, cell, m, bonds, hz, reps)
+            assert set(got) == set(want)
+            worst = 0.0
+            for key, w in want.items():
+                # _entry_bounds of tests/test_spin_momentum_host.py per stored term, and eps |sum| per addition of the row's terms
+                worst = max(worst, abs(got[key] - w) - (bound.get(key, 0.0) + EPS * abs(w) * len(bonds)))
+                # Hermitian: the transposed entry is the conjugate within the same bound on either side
+                assert abs(got[key] - np.conj(got[(key[1], key[0])])) <= 2 * (bound.get(key, 0.0) + EPS * abs(w) * len(bonds))
+            print(f"({L},{n_up},{cell}) {name} m={m}: {n} rows, worst excess over the bound {worst:.3e}")
+            assert worst <= 0.0
+            if m == 0 or 2 * m == L // cell:
+                assert not val.imag.any() and not np.signbit(val.imag).any()
+            a, b = n // 3, n - n // 4  # a range of rows from the middle
+            rp, cl, vl = capi.spin_momentum64_csr(L, n_up, m, bonds, hz, cell, row_begin=a, n_rows=b - a)
+            assert np.array_equal(rp, rowptr[a : b + 1] - rowptr[a]) and np.array_equal(cl, col[rowptr[a] : rowptr[b]])
+            assert vl.tobytes() == val[rowptr[a] : rowptr[b]].tobytes()
+
+
+@pytest.mark.parametrize("L", [36, 40, 48])
+def test_one_magnon_dispersion(capi, L):
+    """n_up = 1 on the Heisenberg ring: every block is 1 x 1 and its entries sum to J L / 4 - J (1 - cos 2 pi m / L).  Tolerance
+    (L + 2) eps |J| L / 4: that many additions of terms bounded by the diagonal."""
+    J = 1.3
+    bonds = ref.xxz_ring(L, J, J)
+    for m in range(L):
+        assert capi.spin_momentum64_dim(L, 1, m) == 1
+        rowptr, col, val = capi.spin_momentum64_csr(L, 1, m, bonds)
+        assert rowptr.tolist() == [0, 3] and col.tolist() == [0, 0, 0]
+        total = val.sum()
+        want = J * L / 4 - J * (1 - cos(2 * pi * m / L))
+        assert abs(total - want) <= (L + 2) * EPS * abs(J) * L / 4
+
+
+# ---- 4. diagonal correlations ----
+def _masks(L):
+    sites = [0, 1, L // 2, L - 1, 33]
+    masks = [1 << i for i in sites] + [1 | 1 << 1, 1 | 1 << 32, 1 | 1 << (L - 1), 1 << 5 | 1 << 33, 1 << 2 | 1 << 17 | 1 << 33, (1 << L) - 1]
+    return masks + [1 | 1 << r for r in range(2, 20)]  # 29 masks: two chunks of the device's 16
+
+
+@pytest.mark.parametrize("L,n_up", [(36, 3), (34, 2)])
+def test_measure_host_equals_the_reference(capi, rows, L, n_up):
+    """|library - reference| <= dim eps N norm2: each of the dim terms c w of a sum is at most N |x|^2 and carries the roundings of w
+    and of the fma, at most eps of the term together with the reference's own (fsum rounds once)."""
+    masks = _masks(L)
+    rs = np.random.RandomState(L)
+    for m in (0, 1, L // 2):
+        reps = rows(L, n_up, 1, m)
+        n = len(reps)
+        xs = [rs.standard_normal(n) + 1j * rs.standard_normal(n)]
+        if m != 1:
+            xs.append(rs.standard_normal(n))
+        for x in xs:
+            diag, norm2 = capi.spin_momentum_measure_host(L, n_up, m, x, masks)
+            want, wnorm = ref.measure(reps, L, 1, masks, x)
+            bound = n * EPS * L * wnorm
+            print(f"({L},{n_up}) m={m} {x.dtype}: largest error {np.abs(diag - want).max():.3e}, bound {bound:.3e}")
+            assert abs(norm2 - wnorm) <= n * EPS * wnorm and np.abs(diag - want).max() <= bound
+            assert masks[10] == (1 << L) - 1  # the mask of all sites: the same sign on every state
+            assert abs(diag[10] - ((-1) ** (L - n_up)) * L * wnorm) <= bound
+            alone, n2 = capi.spin_momentum_measure_host(L, n_up, m, x, masks[9:10])
+            assert alone.tobytes() == diag[9:10].tobytes() and n2 == norm2
+            none, n2 = capi.spin_momentum_measure_host(L, n_up, m, x, [])
+            assert none.size == 0 and n2 == norm2
+
+
+def test_measure_host_agrees_with_expand_then_spin_measure(capi):
+    """On (12, 6), one basis vector per row: diag / N of the momentum call against the sector's diag of the expanded vector (both
+    norms are 1), within the bound above."""
+    L, n_up = 12, 6
+    masks = [1 << i for i in range(L)] + [1 | 1 << r for r in range(1, L)] + [0b111, 1 << 3 | 1 << 7 | 1 << 11]
+    for m in (0, 1, 3, 6):
+        n = capi.spin_momentum64_dim(L, n_up, m)
+        for a in range(n):
+            x = np.zeros(n, np.float64 if m in (0, 6) else np.complex128)
+            x[a] = 1.0
+            diag, norm2 = capi.spin_momentum_measure_host(L, n_up, m, x, masks)
+            y = capi.spin_momentum_expand_host(L, n_up, m, x)
+            host = capi.spin_measure_host_z if np.iscomplexobj(y) else capi.spin_measure_host
+            sdiag, _, snorm = host(L, n_up, y, masks, [])
+            assert norm2 == 1.0 and abs(snorm - 1.0) <= (8 + y.size) * EPS
+            assert np.abs(diag - L * sdiag).max() <= n * EPS * L * norm2
+
+
+# ---- 5. refusals ----
+def test_refusals_and_their_messages(capi):
+    with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum64_dim: n_sites must be 2..48"):
+        capi.spin_momentum64_dim(49, 3, 0)
+    with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum64_states: n_sites must be 2..48"):
+        capi.spin_momentum64_states(49, 3, 0, count=1)
+    many = ref.xxz_ring(43, 1.0, 0.7, reach=(1, 2, 3))
+    assert len(many) == 129
+    with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum64_csr: n_bonds must be 0..128"):
+        capi.spin_momentum64_csr(43, 2, 0, many)
+    assert capi.spin_momentum64_csr(40, 2, 0, ref.xxz_ring(40, 1.0, 0.7, reach=(1, 2, 3)))[0].size == 21  # 120 bonds are taken
+    ring = ref.xxz_ring(36, 1.0, 0.7)
+    with pytest.raises(capi.EigenexError, match=r"eigenex_spin_momentum64_csr: .*not invariant.*bond 34 \(sites 34, 35\)"):
+        capi.spin_momentum64_csr(36, 3, 0, ring[:-1])
+    with pytest.raises(capi.EigenexError, match="momentum must be 0..n_sites/cell - 1"):
+        capi.spin_momentum64_dim(36, 3, 36)
+    with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum64_dim: the sector is empty"):
+        capi.spin_momentum64_dim(36, 0, 1)
+    # the uploads check everything before they look at the context: the same refusals without a GPU, with a NULL context
+    with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum64_upload: real states take a real momentum only"):
+        capi.Csr.spin_half_momentum64(None, 36, 3, 1, ring)
+    with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum64_upload_z: n_sites must be 2..48"):
+        capi.Csr.spin_half_momentum64(None, 49, 3, 1, ref.xxz_ring(49), complex_states=True)
+    with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum64_upload: n_bonds must be 0..128"):
+        capi.Csr.spin_half_momentum64(None, 43, 2, 0, many)
+    with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum64_upload_z: NULL argument"):
+        capi.Csr.spin_half_momentum64(None, 36, 3, 1, ring, complex_states=True)
+    with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum64_upload: NULL argument"):
+        capi.Csr.spin_half_momentum64(None, 36, 3, 18, ring)
+    x = np.ones(capi.spin_momentum64_dim(36, 3, 0))
+    with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum_measure_host: a mask names a site outside 0..n_sites-1"):
+        capi.spin_momentum_measure_host(36, 3, 0, x, [1, 1 << 36])
+    with pytest.raises(capi.EigenexError, match="eigenex_spin_momentum_measure_host: a mask is zero"):
+        capi.spin_momentum_measure_host(36, 3, 0, x, [1, 0])
+    with pytest.raises(capi.EigenexError, match="n_diag must be 0..1024"):
+        capi.spin_momentum_measure_host(36, 3, 0, x, [1] * 1025)
+    # the 32-bit entry points keep their limits
+    with pytest.raises(capi.EigenexError, match="n_sites must be 2..32"):
+        capi.spin_momentum_dim(33, 3, 0)
+
+
+# ---- 6. the sanitizer program ----
+def test_momentum64_host_code_under_sanitizers(tmp_path):
+    """csrc/spin_momentum64.hpp (checks, threaded enumeration, buckets, tables, rows, measure) and the 64-bit momentum walk of
+    csrc/spin_rows.hpp -- the functions k_spin_momentum_spmv<E, uint64_t> and k_spin_momentum_measure<E, Word> call -- compiled into
+    a stand-alone program with AddressSanitizer + UBSan: every load bounds-checked, each row's sum compared bitwise with the sum
+    over the stored entries; 33, 36 and 48 sites among the shapes."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "spin_momentum64_sanitize")
+    subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-ffp-contract=off", "-pthread", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cmpt-eigenex_amd", "include"),
+                           "-I", os.path.join(ROOT, "cmpt-eigenex_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "spin_momentum64_sanitize.cpp"),
+                           "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert out.returncode == 0, (out.stdout.decode()[-1500:], out.stderr.decode()[-2000:])
+    assert b"SPIN MOMENTUM64 OK" in out.stdout
+
+
+# ---- 7. the header ----
+def test_exports_are_declared_and_present(capi):
+    text = open(os.path.join(ROOT, "include", "eigenex_hip.h")).read()
+    for name in ("eigenex_spin_momentum64_dim", "eigenex_spin_momentum64_states", "eigenex_spin_momentum64_csr", "eigenex_spin_momentum64_upload",
+                 "eigenex_spin_momentum64_upload_z", "eigenex_spin_momentum_measure", "eigenex_spin_momentum_measure_host"):
+        assert re.search(r"\bint %s\s*\(" % name, text)
+        assert hasattr(capi.lib(), name) and name in capi.SIGNATURES
+    assert "EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM64 = 8" in text
+    assert "EIGENEX_LAYOUT_MATRIX_FREE_SPIN_MOMENTUM = 7" in text
