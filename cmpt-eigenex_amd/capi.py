@@ -372,39 +372,61 @@ def _momentum_args(args, n_up, cell, momentum):
     return (args[0], int(n_up), int(cell), int(momentum), *args[1:-1])
 
 
+# the host entry points of a momentum sector exist once per state word: (symbol suffix, dtype of a state)
+_WORD32, _WORD64 = ("", np.uint32), ("64", np.uint64)
+
+
+def _momentum_entry(word, name):
+    return getattr(lib(), "eigenex_spin_momentum%s_%s" % (word[0], name))
+
+
+def _momentum_dim(word, n_sites, n_up, momentum, cell):
+    dim = C.c_int64()
+    _chk(_momentum_entry(word, "dim")(int(n_sites), int(n_up), int(cell), int(momentum), C.byref(dim)))
+    return dim.value
+
+
+def _momentum_states(word, n_sites, n_up, momentum, cell, first, count):
+    if count is None:
+        count = _momentum_dim(word, n_sites, n_up, momentum, cell) - first
+    states, periods = np.zeros(max(int(count), 0), word[1]), np.zeros(max(int(count), 0), np.uint8)
+    _chk(_momentum_entry(word, "states")(int(n_sites), int(n_up), int(cell), int(momentum), int(first), int(count),
+                                         states.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(word[1]))),
+                                         periods.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return states, periods
+
+
+def _momentum_csr(word, n_sites, n_up, momentum, bonds, hz, cell, row_begin, n_rows):
+    keep, args = _spin_model(n_sites, bonds, hz, None)
+    args = _momentum_args(args, n_up, cell, momentum)
+    csr = _momentum_entry(word, "csr")
+    nnz = C.c_int64()
+    if n_rows is None:
+        one = np.zeros(1, np.int64)
+        _chk(csr(*args, 0, 0, one.ctypes.data_as(_lp), None, None, C.byref(nnz)))  # the model's own refusal first
+        n_rows = _momentum_dim(word, n_sites, n_up, momentum, cell) - row_begin
+    rowptr = np.zeros(max(int(n_rows), 0) + 1, np.int64)
+    _chk(csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), None, None, C.byref(nnz)))
+    col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value, np.complex128)
+    _chk(csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), _i(col), _d(val.view(np.float64)), C.byref(nnz)))
+    return rowptr, col, val
+
+
 def spin_momentum_dim(n_sites: int, n_up: int, momentum: int, cell: int = 1) -> int:
     """eigenex_spin_momentum_dim: the number of rows of the momentum sector (n_sites, n_up, cell, momentum)"""
-    dim = C.c_int64()
-    _chk(lib().eigenex_spin_momentum_dim(int(n_sites), int(n_up), int(cell), int(momentum), C.byref(dim)))
-    return dim.value
+    return _momentum_dim(_WORD32, n_sites, n_up, momentum, cell)
 
 
 def spin_momentum_states(n_sites: int, n_up: int, momentum: int, cell: int = 1, first: int = 0, count: int | None = None):
     """eigenex_spin_momentum_states: (representatives (uint32, ascending), their periods (uint8)) of rows first .. first + count - 1"""
-    if count is None:
-        count = spin_momentum_dim(n_sites, n_up, momentum, cell) - first
-    states, periods = np.zeros(max(int(count), 0), np.uint32), np.zeros(max(int(count), 0), np.uint8)
-    _chk(lib().eigenex_spin_momentum_states(int(n_sites), int(n_up), int(cell), int(momentum), int(first), int(count),
-                                            states.ctypes.data_as(C.POINTER(C.c_uint32)), periods.ctypes.data_as(C.POINTER(C.c_uint8))))
-    return states, periods
+    return _momentum_states(_WORD32, n_sites, n_up, momentum, cell, first, count)
 
 
 def spin_momentum_csr(n_sites: int, n_up: int, momentum: int, bonds, hz=None, cell: int = 1, row_begin: int = 0, n_rows: int | None = None):
     """eigenex_spin_momentum_csr: rows [row_begin, row_begin + n_rows) of the spin-1/2 Hamiltonian in a momentum sector as CSR
     (host code, no GPU needed), in the stored order the matrix-free kernel adds them in.  Returns rowptr (int64), col (int32),
     val (complex128; all imaginary parts are exactly 0 at a real momentum)."""
-    keep, args = _spin_model(n_sites, bonds, hz, None)
-    args = _momentum_args(args, n_up, cell, momentum)
-    nnz = C.c_int64()
-    if n_rows is None:
-        one = np.zeros(1, np.int64)
-        _chk(lib().eigenex_spin_momentum_csr(*args, 0, 0, one.ctypes.data_as(_lp), None, None, C.byref(nnz)))  # the model's own refusal first
-        n_rows = spin_momentum_dim(n_sites, n_up, momentum, cell) - row_begin
-    rowptr = np.zeros(max(int(n_rows), 0) + 1, np.int64)
-    _chk(lib().eigenex_spin_momentum_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), None, None, C.byref(nnz)))
-    col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value, np.complex128)
-    _chk(lib().eigenex_spin_momentum_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), _i(col), _d(val.view(np.float64)), C.byref(nnz)))
-    return rowptr, col, val
+    return _momentum_csr(_WORD32, n_sites, n_up, momentum, bonds, hz, cell, row_begin, n_rows)
 
 
 def spin_momentum_expand_host(n_sites: int, n_up: int, momentum: int, x, cell: int = 1):
@@ -422,36 +444,18 @@ def spin_momentum_expand_host(n_sites: int, n_up: int, momentum: int, x, cell: i
 
 def spin_momentum64_dim(n_sites: int, n_up: int, momentum: int, cell: int = 1) -> int:
     """eigenex_spin_momentum64_dim: the number of rows of the momentum sector (n_sites up to 48, n_up, cell, momentum)"""
-    dim = C.c_int64()
-    _chk(lib().eigenex_spin_momentum64_dim(int(n_sites), int(n_up), int(cell), int(momentum), C.byref(dim)))
-    return dim.value
+    return _momentum_dim(_WORD64, n_sites, n_up, momentum, cell)
 
 
 def spin_momentum64_states(n_sites: int, n_up: int, momentum: int, cell: int = 1, first: int = 0, count: int | None = None):
     """eigenex_spin_momentum64_states: (representatives (uint64, ascending), their periods (uint8)) of rows first .. first + count - 1"""
-    if count is None:
-        count = spin_momentum64_dim(n_sites, n_up, momentum, cell) - first
-    states, periods = np.zeros(max(int(count), 0), np.uint64), np.zeros(max(int(count), 0), np.uint8)
-    _chk(lib().eigenex_spin_momentum64_states(int(n_sites), int(n_up), int(cell), int(momentum), int(first), int(count),
-                                              states.ctypes.data_as(C.POINTER(C.c_uint64)), periods.ctypes.data_as(C.POINTER(C.c_uint8))))
-    return states, periods
+    return _momentum_states(_WORD64, n_sites, n_up, momentum, cell, first, count)
 
 
 def spin_momentum64_csr(n_sites: int, n_up: int, momentum: int, bonds, hz=None, cell: int = 1, row_begin: int = 0, n_rows: int | None = None):
     """eigenex_spin_momentum64_csr: spin_momentum_csr for rings of up to 48 sites and 128 bonds (64-bit states).  Returns rowptr
     (int64), col (int32), val (complex128; all imaginary parts are exactly 0 at a real momentum)."""
-    keep, args = _spin_model(n_sites, bonds, hz, None)
-    args = _momentum_args(args, n_up, cell, momentum)
-    nnz = C.c_int64()
-    if n_rows is None:
-        one = np.zeros(1, np.int64)
-        _chk(lib().eigenex_spin_momentum64_csr(*args, 0, 0, one.ctypes.data_as(_lp), None, None, C.byref(nnz)))  # the model's own refusal first
-        n_rows = spin_momentum64_dim(n_sites, n_up, momentum, cell) - row_begin
-    rowptr = np.zeros(max(int(n_rows), 0) + 1, np.int64)
-    _chk(lib().eigenex_spin_momentum64_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), None, None, C.byref(nnz)))
-    col, val = np.zeros(nnz.value, np.int32), np.zeros(nnz.value, np.complex128)
-    _chk(lib().eigenex_spin_momentum64_csr(*args, row_begin, n_rows, rowptr.ctypes.data_as(_lp), _i(col), _d(val.view(np.float64)), C.byref(nnz)))
-    return rowptr, col, val
+    return _momentum_csr(_WORD64, n_sites, n_up, momentum, bonds, hz, cell, row_begin, n_rows)
 
 
 def _mask_list64(masks):

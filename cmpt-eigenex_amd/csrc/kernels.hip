@@ -1933,23 +1933,9 @@ __global__ __launch_bounds__(kBlock) void k_spin_site_apply(const SpinSiteTable*
 // issued before the first product is added.  The sums are those of the CSR row loop over eigenex_spin_momentum_csr's rows:
 // k_spmv's for E = double on val.re at a real momentum, k_spmv_z's for E = SpinZ.
 // ---------------------------------------------------------------------------
-// The state word is a parameter: Word = uint32_t for the sectors of spin_momentum.hpp, uint64_t for those of spin_momentum64.hpp
-// (up to 48 sites; reps is then 8 bytes per row, still one coalesced load, and the LDS tables are 19.9 KB).  SpinMomentumWord has
-// the view and the table sizes of either; the kernel text is the same.
-static_assert(kSpinRatioPitch == kMomentumRatioPitch, "spin_rows.hpp indexes ratio with spin_momentum.hpp's pitch");
-static_assert(kSpinRatioPitch64 == kMomentum64RatioPitch, "spin_rows.hpp indexes ratio with spin_momentum64.hpp's pitch");
-template <class Word>
-struct SpinMomentumWord {
-  using View = SpinMomentumView;
-  using Tables = SpinMomentumTables;
-  static constexpr int kPitch = kMomentumRatioPitch, kMaxPeriod = kMomentumMaxPeriod;
-};
-template <>
-struct SpinMomentumWord<uint64_t> {
-  using View = SpinMomentum64View;
-  using Tables = SpinMomentum64Tables;
-  static constexpr int kPitch = kMomentum64RatioPitch, kMaxPeriod = kMomentum64MaxPeriod;
-};
+// The state word is a parameter: Word = uint32_t for sectors of up to 32 sites, uint64_t for those of up to 48 (reps is then
+// 8 bytes per row, still one coalesced load, and the LDS tables are 19.9 KB).  SpinWord<Word> (spin_rows.hpp) has the table sizes
+// of either and SpinMomentumViewOf<Word> is its view; the kernel text is the same.
 template <class Word>
 struct SpinMomentumLookupOf {
   const Word* reps_;
@@ -1959,9 +1945,9 @@ struct SpinMomentumLookupOf {
 };
 using SpinMomentumLookup = SpinMomentumLookupOf<uint32_t>;
 template <class Word>
-struct SpinMomentumLdsOf {  // the workgroup's copy of SpinMomentumTables or SpinMomentum64Tables
+struct SpinMomentumLdsOf {  // the workgroup's copy of SpinMomentumTablesOf<Word>
   const double* t;
-  static constexpr int kPitch = SpinMomentumWord<Word>::kPitch, kMaxPeriod = SpinMomentumWord<Word>::kMaxPeriod;
+  static constexpr int kPitch = SpinWord<Word>::kRatioPitch, kMaxPeriod = SpinWord<Word>::kMaxPeriod;
   static constexpr int kRatio = 0, kInvSqrt = kPitch * kPitch, kPhaseRe = kInvSqrt + kPitch, kPhaseIm = kPhaseRe + kMaxPeriod,
                        kSize = kPhaseIm + kMaxPeriod;
   __device__ __forceinline__ double ratio(int i) const { return t[kRatio + i]; }
@@ -1981,7 +1967,7 @@ __device__ __forceinline__ void spin_stage_momentum_tables(const View* __restric
 }
 
 template <class E, class Word, class... ComplexOnly>
-__global__ __launch_bounds__(kBlock) void k_spin_momentum_spmv(const typename SpinMomentumWord<Word>::View* __restrict__ op,
+__global__ __launch_bounds__(kBlock) void k_spin_momentum_spmv(const SpinMomentumViewOf<Word>* __restrict__ op,
                                                                const Word* __restrict__ reps, const uint32_t* __restrict__ bucket,
                                                                const typename SpinElement<E>::Stored* __restrict__ x_ext,
                                                                const double* __restrict__ scale_ptr, double shift,
@@ -2059,7 +2045,7 @@ __global__ __launch_bounds__(kBlock) void k_spin_momentum_spmv(const typename Sp
   }
 }
 
-// Diagonal correlations of one vector in the momentum basis (spin_momentum64.hpp has the definition and the chunk): x and reps
+// Diagonal correlations of one vector in the momentum basis (spin_momentum.hpp has the definition and the chunk): x and reps
 // stream past once per chunk of kSpinMeasureChunk masks and no vector is written.  One row per lane, 256-row tiles, the
 // persistent grid; the lane's state is reps[r], one coalesced load, and every lane rotates it n_trans times, the chunk's masks
 // applied to each rotation (spin_rows.hpp: spin_momentum_measure_diagonals).  The C + 1 sums stay in registers across the tile
@@ -3300,7 +3286,7 @@ void launch_spin_site_apply(hipStream_t s, int es, const SpinSiteTable* table, c
 }
 
 template <class Word>
-static void spin_momentum_spmv_launch(hipStream_t s, int es, const typename SpinMomentumWord<Word>::View* op, const Word* reps, const uint32_t* bucket,
+static void spin_momentum_spmv_launch(hipStream_t s, int es, const SpinMomentumViewOf<Word>* op, const Word* reps, const uint32_t* bucket,
                                       const double* x_ext, const double* scale, double shift_re, double shift_im, double* y, double* u_out,
                                       int64_t n, double* partials, int pstride, int grid, const Ctrl* ctrl, int pass) {
   const int64_t ntiles = (n + kBlock - 1) / kBlock;
@@ -3316,9 +3302,9 @@ void launch_spin_momentum_spmv(hipStream_t s, int es, const SpinMomentumView* op
                                double* partials, int pstride, int grid, const Ctrl* ctrl, int pass) {
   spin_momentum_spmv_launch<uint32_t>(s, es, op, reps, bucket, x_ext, scale, shift_re, shift_im, y, u_out, n, partials, pstride, grid, ctrl, pass);
 }
-void launch_spin_momentum64_spmv(hipStream_t s, int es, const SpinMomentum64View* op, const uint64_t* reps, const uint32_t* bucket,
-                                 const double* x_ext, const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n,
-                                 double* partials, int pstride, int grid, const Ctrl* ctrl, int pass) {
+void launch_spin_momentum_spmv(hipStream_t s, int es, const SpinMomentum64View* op, const uint64_t* reps, const uint32_t* bucket,
+                               const double* x_ext, const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n,
+                               double* partials, int pstride, int grid, const Ctrl* ctrl, int pass) {
   spin_momentum_spmv_launch<uint64_t>(s, es, op, reps, bucket, x_ext, scale, shift_re, shift_im, y, u_out, n, partials, pstride, grid, ctrl, pass);
 }
 
@@ -3328,14 +3314,15 @@ static void spin_momentum_measure_launch(hipStream_t s, const SpinMomentumMeasur
   hipLaunchKernelGGL((k_spin_momentum_measure<E, Word>), dim3(grid), dim3(kBlock), 0, s, chunk, reps, spin_elements<E>(x), n_sites, cell, n_trans, n,
                      (n + kBlock - 1) / kBlock, partials, pstride);
 }
-void launch_spin_momentum_measure(hipStream_t s, int es, const SpinMomentumMeasureChunk* chunk, const uint32_t* reps32, const uint64_t* reps64,
-                                  const double* x, int n_sites, int cell, int n_trans, int64_t n, double* partials, int pstride, int grid) {
-  if (reps64)
-    (es == 2 ? spin_momentum_measure_launch<SpinZ, uint64_t> : spin_momentum_measure_launch<double, uint64_t>)(s, chunk, reps64, x, n_sites, cell,
-                                                                                                            n_trans, n, partials, pstride, grid);
-  else
-    (es == 2 ? spin_momentum_measure_launch<SpinZ, uint32_t> : spin_momentum_measure_launch<double, uint32_t>)(s, chunk, reps32, x, n_sites, cell,
-                                                                                                            n_trans, n, partials, pstride, grid);
+void launch_spin_momentum_measure(hipStream_t s, int es, const SpinMomentumMeasureChunk* chunk, const uint32_t* reps, const double* x, int n_sites,
+                                  int cell, int n_trans, int64_t n, double* partials, int pstride, int grid) {
+  (es == 2 ? spin_momentum_measure_launch<SpinZ, uint32_t> : spin_momentum_measure_launch<double, uint32_t>)(s, chunk, reps, x, n_sites, cell, n_trans,
+                                                                                                          n, partials, pstride, grid);
+}
+void launch_spin_momentum_measure(hipStream_t s, int es, const SpinMomentumMeasureChunk* chunk, const uint64_t* reps, const double* x, int n_sites,
+                                  int cell, int n_trans, int64_t n, double* partials, int pstride, int grid) {
+  (es == 2 ? spin_momentum_measure_launch<SpinZ, uint64_t> : spin_momentum_measure_launch<double, uint64_t>)(s, chunk, reps, x, n_sites, cell, n_trans,
+                                                                                                          n, partials, pstride, grid);
 }
 
 template <class E>

@@ -10,7 +10,6 @@
 #include "spin_rdm.hpp"
 #include "spin_model.hpp"
 #include "spin_momentum.hpp"
-#include "spin_momentum64.hpp"
 #include "spin_rows.hpp"
 #include "spin_sector.hpp"
 #include "spin_site.hpp"
@@ -397,17 +396,19 @@ void launch_spin_rdm_reduce(hipStream_t s, int es, const SpinRdmTable* table, in
 void launch_spin_momentum_spmv(hipStream_t s, int es, const SpinMomentumView* op, const uint32_t* reps, const uint32_t* bucket,
                                const double* x_ext, const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n,
                                double* partials, int pstride, int grid, const Ctrl* ctrl, int pass = 0);
-// ... with 64-bit states (eigenex_spin_momentum64_upload; spin_momentum64.hpp): the same kernel text on uint64_t words, 8 bytes per
-// row of reps, bit-identical to the CSR upload of eigenex_spin_momentum64_csr's rows.  The same contract.
-void launch_spin_momentum64_spmv(hipStream_t s, int es, const SpinMomentum64View* op, const uint64_t* reps, const uint32_t* bucket,
-                                 const double* x_ext, const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n,
-                                 double* partials, int pstride, int grid, const Ctrl* ctrl, int pass = 0);
-// Diagonal correlations in the momentum basis (eigenex_spin_momentum_measure; spin_momentum64.hpp has the definition): one chunk
-// of masks over the n rows of x, whose states are reps64 where that is not NULL and reps32 else.  The grid's partial sums go to
+// ... with 64-bit states (eigenex_spin_momentum64_upload): the same kernel text on uint64_t words, 8 bytes per row of reps,
+// bit-identical to the CSR upload of eigenex_spin_momentum64_csr's rows.  The same contract.
+void launch_spin_momentum_spmv(hipStream_t s, int es, const SpinMomentum64View* op, const uint64_t* reps, const uint32_t* bucket,
+                               const double* x_ext, const double* scale, double shift_re, double shift_im, double* y, double* u_out, int64_t n,
+                               double* partials, int pstride, int grid, const Ctrl* ctrl, int pass = 0);
+// Diagonal correlations in the momentum basis (eigenex_spin_momentum_measure; spin_momentum.hpp has the definition): one chunk
+// of masks over the n rows of x, whose states are reps, of either word.  The grid's partial sums go to
 // partials[sum * pstride + workgroup], sum 0 norm2 and 1 + t the chunk's mask t; second stage launch_spin_measure_reduce with
 // nflip = 0.  Always runs; writes no vector.
-void launch_spin_momentum_measure(hipStream_t s, int es, const SpinMomentumMeasureChunk* chunk, const uint32_t* reps32, const uint64_t* reps64,
-                                  const double* x, int n_sites, int cell, int n_trans, int64_t n, double* partials, int pstride, int grid);
+void launch_spin_momentum_measure(hipStream_t s, int es, const SpinMomentumMeasureChunk* chunk, const uint32_t* reps, const double* x, int n_sites,
+                                  int cell, int n_trans, int64_t n, double* partials, int pstride, int grid);
+void launch_spin_momentum_measure(hipStream_t s, int es, const SpinMomentumMeasureChunk* chunk, const uint64_t* reps, const double* x, int n_sites,
+                                  int cell, int n_trans, int64_t n, double* partials, int pstride, int grid);
 // expand (eigenex_spin_momentum_expand): y, the n = C(n_sites, n_up) rows of the sector operator whose view dst_op is, from the
 // momentum vector x on the rows of op.  The grid's partial sums of |y_r|^2 go to partials[workgroup]; second stage as for
 // launch_spin_site_apply.  Always runs.

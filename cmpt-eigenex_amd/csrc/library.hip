@@ -290,17 +290,31 @@ struct SpinShard {
 // A matrix-free spin-1/2 operator in a momentum sector on its shard (spin_momentum.hpp): the kernels' view, the ascending list of
 // representatives (one per row) and the bucket table of the search.  Not a SpinShard: a row is an orbit, not a state, so the
 // calls that read states off the rows (eigenex_spin_geometry, _measure, _rdm, _site_apply) must keep refusing the handle.
-// With 64-bit states (eigenex_spin_momentum64_upload; spin_momentum64.hpp) it is the same shard with the wide members in place of
-// view and reps: on() holds for both, so every predicate that tells the momentum shard from the stored forms covers both.
+// The view and the list depend on the state word (eigenex_spin_momentum_upload: uint32_t; eigenex_spin_momentum64_upload: uint64_t,
+// `wide`); the shard holds that part once per word, fills one and hands it to visit()'s caller.  on() holds for both, so every
+// predicate that tells the momentum shard from the stored forms covers both.
+template <class Word>
+struct SpinMomentumPart {
+  DeviceBuffer<SpinMomentumViewOf<Word>> view;
+  DeviceBuffer<Word> reps;  // sizeof(Word) bytes per row
+};
 struct SpinMomentumShard {
-  DeviceBuffer<SpinMomentumView> view;
-  DeviceBuffer<uint32_t> reps, bucket;
-  DeviceBuffer<SpinMomentum64View> view64;  // wide only
-  DeviceBuffer<uint64_t> reps64;            // wide only, 8 bytes per row
+  SpinMomentumPart<uint32_t> part32;
+  SpinMomentumPart<uint64_t> part64;  // wide only
+  DeviceBuffer<uint32_t> bucket;
   int64_t table_words = 0;  // 4-byte words of reps and bucket together
   int n_sites = 0, n_up = 0, cell = 0, momentum = 0;
   bool wide = false;
   bool on() const { return n_sites > 0; }
+  SpinMomentumPart<uint32_t>& part(uint32_t) { return part32; }
+  SpinMomentumPart<uint64_t>& part(uint64_t) { return part64; }
+  template <class F>
+  void visit(F f) const {  // f(the part in use)
+    if (wide)
+      f(part64);
+    else
+      f(part32);
+  }
 };
 
 struct CsrShard {
@@ -1702,14 +1716,11 @@ void launch_operator(hipStream_t st, const BasisShard& s, const OperatorPass& p)
                        p.pass_flags);
     return;
   }
-  if (m->momentum.on() && m->momentum.wide) {
-    launch_spin_momentum64_spmv(st, es, m->momentum.view64, m->momentum.reps64, m->momentum.bucket, p.x, p.scale, p.shift, p.shift_im, p.y, p.u_out,
-                                m->nloc, p.partials, s.pstride, grid, p.ctrl, p.pass_flags);
-    return;
-  }
   if (m->momentum.on()) {
-    launch_spin_momentum_spmv(st, es, m->momentum.view, m->momentum.reps, m->momentum.bucket, p.x, p.scale, p.shift, p.shift_im, p.y, p.u_out,
-                              m->nloc, p.partials, s.pstride, grid, p.ctrl, p.pass_flags);
+    m->momentum.visit([&](const auto& k) {
+      launch_spin_momentum_spmv(st, es, k.view, k.reps, m->momentum.bucket, p.x, p.scale, p.shift, p.shift_im, p.y, p.u_out, m->nloc, p.partials,
+                                s.pstride, grid, p.ctrl, p.pass_flags);
+    });
     return;
   }
   if (m->rc_rec || (m->passes == 1 && es == 1)) {
@@ -3180,38 +3191,46 @@ int eigenex_spin_geometry(eigenex_csr_t m, int* n_sites, int* n_up) {
   return 0;
 }
 
-// ---- momentum sectors (spin_momentum.hpp) ----
+// ---- momentum sectors (spin_momentum.hpp), written once for both state words; `who` is the entry point's name in messages ----
 static BasisShard* spin_state_shard(eigenex_basis_t b);
+}  // extern "C"
 // the checks every entry point shares, before anything is built: the geometry, then (with a model) Sz and translation invariance
+template <class Word>
 static int spin_momentum_check(const std::string& who, int n_sites, int n_up, int cell, int momentum, const SpinModelArgs* a) {
-  const std::string geo = spin_momentum_geometry_error(n_sites, n_up, cell, momentum);
+  const std::string geo = spin_momentum_geometry_error<Word>(n_sites, n_up, cell, momentum);
   if (!geo.empty()) return fail(EIGENEX_ERR_ARG, who + ": " + geo);
   if (a) {
-    const std::string why = spin_momentum_model_error(*a, n_up, cell);
+    const std::string why = spin_momentum_model_error<Word>(*a, n_up, cell);
     if (!why.empty()) return fail(EIGENEX_ERR_ARG, who + ": " + why);
   }
   return 0;
 }
-static int spin_momentum_empty(const std::string& who) {
-  return fail(EIGENEX_ERR_ARG, who + ": the sector is empty: no orbit of this magnetisation has a period that carries this momentum");
-}
-
-int eigenex_spin_momentum_dim(int n_sites, int n_up, int cell, int momentum, int64_t* dim) {
-  if (!dim) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_dim: dim is NULL");
-  CHK(spin_momentum_check("eigenex_spin_momentum_dim", n_sites, n_up, cell, momentum, nullptr));
-  const int64_t n = spin_momentum_build_basis(n_sites, n_up, cell, momentum, nullptr);
-  if (n == 0) return spin_momentum_empty("eigenex_spin_momentum_dim");
-  *dim = n;
+// builds the rows (into b, unless it is NULL); 0 if there are between 1 and 2^31 - 1 of them
+template <class Word>
+static int spin_momentum_rows(const std::string& who, int n_sites, int n_up, int cell, int momentum, SpinMomentumBasisOf<Word>* b, int64_t* dim,
+                              bool with_lookup = false) {
+  const int64_t n = spin_momentum_build_basis<Word>(n_sites, n_up, cell, momentum, b, with_lookup);
+  if (n == 0) return fail(EIGENEX_ERR_ARG, who + ": the sector is empty: no orbit of this magnetisation has a period that carries this momentum");
+  if (n > kMomentumMaxDim) return fail(EIGENEX_ERR_ARG, who + ": the sector has 2^31 rows or more: dim must be below 2^31");
+  if (dim) *dim = n;
   return 0;
 }
 
-int eigenex_spin_momentum_states(int n_sites, int n_up, int cell, int momentum, int64_t first, int64_t count, uint32_t* states,
-                                 uint8_t* periods_or_null) {
-  CHK(spin_momentum_check("eigenex_spin_momentum_states", n_sites, n_up, cell, momentum, nullptr));
-  SpinMomentumBasis b;
-  if (spin_momentum_build_basis(n_sites, n_up, cell, momentum, &b) == 0) return spin_momentum_empty("eigenex_spin_momentum_states");
-  if (first < 0 || count < 0 || first + count > (int64_t)b.reps.size()) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_states: rows outside 0..dim");
-  if (count > 0 && !states) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_states: states is NULL");
+template <class Word>
+static int spin_momentum_dim(const std::string& who, int n_sites, int n_up, int cell, int momentum, int64_t* dim) {
+  if (!dim) return fail(EIGENEX_ERR_ARG, who + ": dim is NULL");
+  CHK(spin_momentum_check<Word>(who, n_sites, n_up, cell, momentum, nullptr));
+  return spin_momentum_rows<Word>(who, n_sites, n_up, cell, momentum, nullptr, dim);
+}
+
+template <class Word>
+static int spin_momentum_states(const std::string& who, int n_sites, int n_up, int cell, int momentum, int64_t first, int64_t count, Word* states,
+                                uint8_t* periods_or_null) {
+  CHK(spin_momentum_check<Word>(who, n_sites, n_up, cell, momentum, nullptr));
+  SpinMomentumBasisOf<Word> b;
+  CHK(spin_momentum_rows(who, n_sites, n_up, cell, momentum, &b, nullptr));
+  if (first < 0 || count < 0 || first + count > (int64_t)b.reps.size()) return fail(EIGENEX_ERR_ARG, who + ": rows outside 0..dim");
+  if (count > 0 && !states) return fail(EIGENEX_ERR_ARG, who + ": states is NULL");
   for (int64_t k = 0; k < count; ++k) {
     states[k] = b.reps[(size_t)(first + k)];
     if (periods_or_null) periods_or_null[k] = b.period[(size_t)(first + k)];
@@ -3219,37 +3238,40 @@ int eigenex_spin_momentum_states(int n_sites, int n_up, int cell, int momentum, 
   return 0;
 }
 
-int eigenex_spin_momentum_csr(int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i, const int32_t* site_j,
-                              const double* jz, const double* jxy, const double* hz_or_null, int64_t row_begin, int64_t n_rows, int64_t* rowptr,
-                              int32_t* col, double* val, int64_t* nnz) {
+template <class Word>
+static int spin_momentum_csr(const std::string& who, int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
+                             const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, int64_t row_begin, int64_t n_rows,
+                             int64_t* rowptr, int32_t* col, double* val, int64_t* nnz) {
   const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, nullptr};
-  CHK(spin_momentum_check("eigenex_spin_momentum_csr", n_sites, n_up, cell, momentum, &a));
+  CHK(spin_momentum_check<Word>(who, n_sites, n_up, cell, momentum, &a));
   if (!rowptr || !nnz || (col == nullptr) != (val == nullptr))
-    return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_csr: rowptr and nnz are needed, col and val together or neither");
-  SpinMomentumBasis b;
-  if (spin_momentum_build_basis(n_sites, n_up, cell, momentum, &b) == 0) return spin_momentum_empty("eigenex_spin_momentum_csr");
-  if (row_begin < 0 || n_rows < 0 || row_begin + n_rows > (int64_t)b.reps.size()) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_csr: rows outside 0..dim");
-  std::unique_ptr<SpinMomentumTables> t(new SpinMomentumTables());
+    return fail(EIGENEX_ERR_ARG, who + ": rowptr and nnz are needed, col and val together or neither");
+  SpinMomentumBasisOf<Word> b;
+  CHK(spin_momentum_rows(who, n_sites, n_up, cell, momentum, &b, nullptr));
+  if (row_begin < 0 || n_rows < 0 || row_begin + n_rows > (int64_t)b.reps.size()) return fail(EIGENEX_ERR_ARG, who + ": rows outside 0..dim");
+  std::unique_ptr<SpinMomentumTablesOf<Word>> t(new SpinMomentumTablesOf<Word>());
   spin_momentum_build_tables(b.n_trans, momentum, *t);
   spin_momentum_write_rows(a, b, *t, row_begin, n_rows, rowptr, col, val, nnz);
   return 0;
 }
 
+// who: the entry point for real states (es 1) or that name with _z (es 2)
+template <class Word>
 static int spin_momentum_upload(const std::string& who, int es, eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds,
                                 const int32_t* site_i, const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null,
                                 eigenex_csr_t* out) {
   // every argument check before the context is touched
   const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, nullptr};
-  CHK(spin_momentum_check(who, n_sites, n_up, cell, momentum, &a));
+  CHK(spin_momentum_check<Word>(who, n_sites, n_up, cell, momentum, &a));
   if (es == 1 && !spin_momentum_is_real(n_sites / cell, momentum))
     return fail(EIGENEX_ERR_ARG, who + ": real states take a real momentum only (0 or half the number of translations); this one has complex matrix "
-                                       "elements and needs complex states (eigenex_spin_momentum_upload_z)");
+                                       "elements and needs complex states (" + who + "_z)");
   if (!c || !out) return fail(EIGENEX_ERR_ARG, who + ": NULL argument");
   if (c->P != 1)
     return fail(EIGENEX_ERR_ARG, who + ": a matrix-free spin operator needs a context with one shard in total; sharding it takes an "
                                        "exchange of whole vectors for the bonds on the top bits, which is not built");
-  SpinMomentumBasis b;
-  if (spin_momentum_build_basis(n_sites, n_up, cell, momentum, &b) == 0) return spin_momentum_empty(who);
+  SpinMomentumBasisOf<Word> b;
+  CHK(spin_momentum_rows(who, n_sites, n_up, cell, momentum, &b, nullptr, true));
   HIPCHK(hipSetDevice(c->device));
   std::unique_ptr<eigenex_csr_s> m(new eigenex_csr_s());
   m->ctx = c;
@@ -3259,31 +3281,74 @@ static int spin_momentum_upload(const std::string& who, int es, eigenex_context_
   CsrShard& s = m->sh[0];
   s.gshard = c->local[0];
   s.momentum.n_sites = n_sites, s.momentum.n_up = n_up, s.momentum.cell = cell, s.momentum.momentum = momentum;
+  s.momentum.wide = sizeof(Word) == 8;
   partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
   s.nloc = s.re - s.rb;
   s.npad = pad_rows(s.nloc);
-  std::unique_ptr<SpinMomentumView> v(new SpinMomentumView());  // staging buffers: they live until the synchronise below
+  std::unique_ptr<SpinMomentumViewOf<Word>> v(new SpinMomentumViewOf<Word>());  // staging buffers: they live until the synchronise below
   spin_momentum_build_view(a, b, *v);
-  s.momentum.table_words = (int64_t)(b.reps.size() + b.bucket.size());
-  HIPCHK(s.momentum.reps.alloc(b.reps.size()));
+  s.momentum.table_words = (int64_t)(sizeof(Word) / 4 * b.reps.size() + b.bucket.size());
+  SpinMomentumPart<Word>& part = s.momentum.part(Word());
+  HIPCHK(part.reps.alloc(b.reps.size()));
   HIPCHK(s.momentum.bucket.alloc(b.bucket.size()));
-  HIPCHK(s.momentum.view.alloc(1));
-  HIPCHK(hipMemcpyAsync(s.momentum.reps, b.reps.data(), 4 * b.reps.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(part.view.alloc(1));
+  HIPCHK(hipMemcpyAsync(part.reps, b.reps.data(), sizeof(Word) * b.reps.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(s.momentum.bucket, b.bucket.data(), 4 * b.bucket.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(s.momentum.view, v.get(), sizeof(SpinMomentumView), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(part.view, v.get(), sizeof(SpinMomentumViewOf<Word>), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   *out = m.release();
   return 0;
 }
+extern "C" {
+
+int eigenex_spin_momentum_dim(int n_sites, int n_up, int cell, int momentum, int64_t* dim) {
+  return spin_momentum_dim<uint32_t>("eigenex_spin_momentum_dim", n_sites, n_up, cell, momentum, dim);
+}
+int eigenex_spin_momentum64_dim(int n_sites, int n_up, int cell, int momentum, int64_t* dim) {
+  return spin_momentum_dim<uint64_t>("eigenex_spin_momentum64_dim", n_sites, n_up, cell, momentum, dim);
+}
+
+int eigenex_spin_momentum_states(int n_sites, int n_up, int cell, int momentum, int64_t first, int64_t count, uint32_t* states,
+                                 uint8_t* periods_or_null) {
+  return spin_momentum_states("eigenex_spin_momentum_states", n_sites, n_up, cell, momentum, first, count, states, periods_or_null);
+}
+int eigenex_spin_momentum64_states(int n_sites, int n_up, int cell, int momentum, int64_t first, int64_t count, uint64_t* states,
+                                   uint8_t* periods_or_null) {
+  return spin_momentum_states("eigenex_spin_momentum64_states", n_sites, n_up, cell, momentum, first, count, states, periods_or_null);
+}
+
+int eigenex_spin_momentum_csr(int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                              const double* jz, const double* jxy, const double* hz_or_null, int64_t row_begin, int64_t n_rows, int64_t* rowptr,
+                              int32_t* col, double* val, int64_t* nnz) {
+  return spin_momentum_csr<uint32_t>("eigenex_spin_momentum_csr", n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy, hz_or_null,
+                                     row_begin, n_rows, rowptr, col, val, nnz);
+}
+int eigenex_spin_momentum64_csr(int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                                const double* jz, const double* jxy, const double* hz_or_null, int64_t row_begin, int64_t n_rows, int64_t* rowptr,
+                                int32_t* col, double* val, int64_t* nnz) {
+  return spin_momentum_csr<uint64_t>("eigenex_spin_momentum64_csr", n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy, hz_or_null,
+                                     row_begin, n_rows, rowptr, col, val, nnz);
+}
 
 int eigenex_spin_momentum_upload(eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
                                  const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, eigenex_csr_t* out) {
-  return spin_momentum_upload("eigenex_spin_momentum_upload", 1, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy, hz_or_null, out);
+  return spin_momentum_upload<uint32_t>("eigenex_spin_momentum_upload", 1, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy,
+                                        hz_or_null, out);
 }
-
 int eigenex_spin_momentum_upload_z(eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
                                    const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, eigenex_csr_t* out) {
-  return spin_momentum_upload("eigenex_spin_momentum_upload_z", 2, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy, hz_or_null, out);
+  return spin_momentum_upload<uint32_t>("eigenex_spin_momentum_upload_z", 2, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy,
+                                        hz_or_null, out);
+}
+int eigenex_spin_momentum64_upload(eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
+                                   const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, eigenex_csr_t* out) {
+  return spin_momentum_upload<uint64_t>("eigenex_spin_momentum64_upload", 1, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy,
+                                        hz_or_null, out);
+}
+int eigenex_spin_momentum64_upload_z(eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
+                                     const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, eigenex_csr_t* out) {
+  return spin_momentum_upload<uint64_t>("eigenex_spin_momentum64_upload_z", 2, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy,
+                                        hz_or_null, out);
 }
 
 int eigenex_spin_momentum_geometry(eigenex_csr_t m, int* n_sites, int* n_up, int* cell, int* momentum) {
@@ -3299,12 +3364,13 @@ int eigenex_spin_momentum_geometry(eigenex_csr_t m, int* n_sites, int* n_up, int
 }
 
 int eigenex_spin_momentum_expand_host(int n_sites, int n_up, int cell, int momentum, int is_complex, const double* x, double* y) {
-  CHK(spin_momentum_check("eigenex_spin_momentum_expand_host", n_sites, n_up, cell, momentum, nullptr));
+  const std::string who = "eigenex_spin_momentum_expand_host";
+  CHK(spin_momentum_check<uint32_t>(who, n_sites, n_up, cell, momentum, nullptr));
   if (!is_complex && !spin_momentum_is_real(n_sites / cell, momentum))
-    return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_expand_host: a real vector takes a real momentum only (0 or half the number of translations)");
-  if (!x || !y) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum_expand_host: x or y is NULL");
+    return fail(EIGENEX_ERR_ARG, who + ": a real vector takes a real momentum only (0 or half the number of translations)");
+  if (!x || !y) return fail(EIGENEX_ERR_ARG, who + ": x or y is NULL");
   SpinMomentumBasis b;
-  if (spin_momentum_build_basis(n_sites, n_up, cell, momentum, &b) == 0) return spin_momentum_empty("eigenex_spin_momentum_expand_host");
+  CHK(spin_momentum_rows(who, n_sites, n_up, cell, momentum, &b, nullptr));
   std::unique_ptr<SpinMomentumTables> t(new SpinMomentumTables());
   spin_momentum_build_tables(b.n_trans, momentum, *t);
   spin_momentum_expand_host(b, *t, is_complex != 0, x, y);
@@ -3342,7 +3408,7 @@ int eigenex_spin_momentum_expand(eigenex_basis_t src, int x_ref, eigenex_basis_t
   double out = 0.0;
   HIPCHK(d_part.alloc((size_t)grid));
   HIPCHK(d_out.alloc(1));
-  launch_spin_momentum_expand(c->stream, dst->es, mk.view, md.view, mk.reps, mk.bucket, x, y, sd.nloc, d_part, grid);
+  launch_spin_momentum_expand(c->stream, dst->es, mk.part32.view, md.view, mk.part32.reps, mk.bucket, x, y, sd.nloc, d_part, grid);
   launch_spin_measure_reduce(c->stream, d_part, grid, grid, 0, 0, nullptr, nullptr, d_out);
   HIPCHK(hipMemcpyAsync(&out, d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the scratch lives until here
@@ -3350,124 +3416,17 @@ int eigenex_spin_momentum_expand(eigenex_basis_t src, int x_ref, eigenex_basis_t
   return 0;
 }
 
-// ---- momentum sectors of up to 48 sites (spin_momentum64.hpp) ----
-static int spin_momentum64_check(const std::string& who, int n_sites, int n_up, int cell, int momentum, const SpinModelArgs* a) {
-  const std::string geo = spin_momentum64_geometry_error(n_sites, n_up, cell, momentum);
-  if (!geo.empty()) return fail(EIGENEX_ERR_ARG, who + ": " + geo);
-  if (a) {
-    const std::string why = spin_momentum64_model_error(*a, cell);
-    if (!why.empty()) return fail(EIGENEX_ERR_ARG, who + ": " + why);
-  }
-  return 0;
-}
-// builds the rows; 0 if there are between 1 and 2^31 - 1 of them
-static int spin_momentum64_rows(const std::string& who, int n_sites, int n_up, int cell, int momentum, SpinMomentum64Basis* b, int64_t* dim,
-                                bool with_lookup = false) {
-  const int64_t n = spin_momentum64_build_basis(n_sites, n_up, cell, momentum, b, with_lookup);
-  if (n == 0) return spin_momentum_empty(who);
-  if (n > kMomentum64MaxDim) return fail(EIGENEX_ERR_ARG, who + ": the sector has 2^31 rows or more: dim must be below 2^31");
-  if (dim) *dim = n;
-  return 0;
-}
-
-int eigenex_spin_momentum64_dim(int n_sites, int n_up, int cell, int momentum, int64_t* dim) {
-  if (!dim) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum64_dim: dim is NULL");
-  CHK(spin_momentum64_check("eigenex_spin_momentum64_dim", n_sites, n_up, cell, momentum, nullptr));
-  return spin_momentum64_rows("eigenex_spin_momentum64_dim", n_sites, n_up, cell, momentum, nullptr, dim);
-}
-
-int eigenex_spin_momentum64_states(int n_sites, int n_up, int cell, int momentum, int64_t first, int64_t count, uint64_t* states,
-                                   uint8_t* periods_or_null) {
-  CHK(spin_momentum64_check("eigenex_spin_momentum64_states", n_sites, n_up, cell, momentum, nullptr));
-  SpinMomentum64Basis b;
-  CHK(spin_momentum64_rows("eigenex_spin_momentum64_states", n_sites, n_up, cell, momentum, &b, nullptr));
-  if (first < 0 || count < 0 || first + count > (int64_t)b.reps.size()) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum64_states: rows outside 0..dim");
-  if (count > 0 && !states) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum64_states: states is NULL");
-  for (int64_t k = 0; k < count; ++k) {
-    states[k] = b.reps[(size_t)(first + k)];
-    if (periods_or_null) periods_or_null[k] = b.period[(size_t)(first + k)];
-  }
-  return 0;
-}
-
-int eigenex_spin_momentum64_csr(int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i, const int32_t* site_j,
-                                const double* jz, const double* jxy, const double* hz_or_null, int64_t row_begin, int64_t n_rows, int64_t* rowptr,
-                                int32_t* col, double* val, int64_t* nnz) {
-  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, nullptr};
-  CHK(spin_momentum64_check("eigenex_spin_momentum64_csr", n_sites, n_up, cell, momentum, &a));
-  if (!rowptr || !nnz || (col == nullptr) != (val == nullptr))
-    return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum64_csr: rowptr and nnz are needed, col and val together or neither");
-  SpinMomentum64Basis b;
-  CHK(spin_momentum64_rows("eigenex_spin_momentum64_csr", n_sites, n_up, cell, momentum, &b, nullptr));
-  if (row_begin < 0 || n_rows < 0 || row_begin + n_rows > (int64_t)b.reps.size()) return fail(EIGENEX_ERR_ARG, "eigenex_spin_momentum64_csr: rows outside 0..dim");
-  std::unique_ptr<SpinMomentum64Tables> t(new SpinMomentum64Tables());
-  spin_momentum64_build_tables(b.n_trans, momentum, *t);
-  spin_momentum64_write_rows(a, b, *t, row_begin, n_rows, rowptr, col, val, nnz);
-  return 0;
-}
-
-static int spin_momentum64_upload(const std::string& who, int es, eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds,
-                                  const int32_t* site_i, const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null,
-                                  eigenex_csr_t* out) {
-  // every argument check before the context is touched
-  const SpinModelArgs a{n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, nullptr};
-  CHK(spin_momentum64_check(who, n_sites, n_up, cell, momentum, &a));
-  if (es == 1 && !spin_momentum_is_real(n_sites / cell, momentum))
-    return fail(EIGENEX_ERR_ARG, who + ": real states take a real momentum only (0 or half the number of translations); this one has complex matrix "
-                                       "elements and needs complex states (eigenex_spin_momentum64_upload_z)");
-  if (!c || !out) return fail(EIGENEX_ERR_ARG, who + ": NULL argument");
-  if (c->P != 1)
-    return fail(EIGENEX_ERR_ARG, who + ": a matrix-free spin operator needs a context with one shard in total; sharding it takes an "
-                                       "exchange of whole vectors for the bonds on the top bits, which is not built");
-  SpinMomentum64Basis b;
-  CHK(spin_momentum64_rows(who, n_sites, n_up, cell, momentum, &b, nullptr, true));
-  HIPCHK(hipSetDevice(c->device));
-  std::unique_ptr<eigenex_csr_s> m(new eigenex_csr_s());
-  m->ctx = c;
-  m->n_global = (int64_t)b.reps.size();
-  m->es = es;
-  m->sh.resize(1);
-  CsrShard& s = m->sh[0];
-  s.gshard = c->local[0];
-  s.momentum.n_sites = n_sites, s.momentum.n_up = n_up, s.momentum.cell = cell, s.momentum.momentum = momentum, s.momentum.wide = true;
-  partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
-  s.nloc = s.re - s.rb;
-  s.npad = pad_rows(s.nloc);
-  std::unique_ptr<SpinMomentum64View> v(new SpinMomentum64View());  // staging buffers: they live until the synchronise below
-  spin_momentum64_build_view(a, b, *v);
-  s.momentum.table_words = (int64_t)(2 * b.reps.size() + b.bucket.size());
-  HIPCHK(s.momentum.reps64.alloc(b.reps.size()));
-  HIPCHK(s.momentum.bucket.alloc(b.bucket.size()));
-  HIPCHK(s.momentum.view64.alloc(1));
-  HIPCHK(hipMemcpyAsync(s.momentum.reps64, b.reps.data(), 8 * b.reps.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(s.momentum.bucket, b.bucket.data(), 4 * b.bucket.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(s.momentum.view64, v.get(), sizeof(SpinMomentum64View), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  *out = m.release();
-  return 0;
-}
-
-int eigenex_spin_momentum64_upload(eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
-                                   const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, eigenex_csr_t* out) {
-  return spin_momentum64_upload("eigenex_spin_momentum64_upload", 1, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy, hz_or_null, out);
-}
-
-int eigenex_spin_momentum64_upload_z(eigenex_context_t c, int n_sites, int n_up, int cell, int momentum, int n_bonds, const int32_t* site_i,
-                                     const int32_t* site_j, const double* jz, const double* jxy, const double* hz_or_null, eigenex_csr_t* out) {
-  return spin_momentum64_upload("eigenex_spin_momentum64_upload_z", 2, c, n_sites, n_up, cell, momentum, n_bonds, site_i, site_j, jz, jxy, hz_or_null, out);
-}
-
-// ---- diagonal correlations in the momentum basis (spin_momentum64.hpp) ----
+// ---- diagonal correlations in the momentum basis (spin_momentum.hpp); the host form builds a 64-bit basis for every ring ----
 int eigenex_spin_momentum_measure_host(int n_sites, int n_up, int cell, int momentum, int is_complex, const double* x, int n_diag,
                                        const uint64_t* masks, double* diag_out, double* norm2) {
   const std::string who = "eigenex_spin_momentum_measure_host";
-  CHK(spin_momentum64_check(who, n_sites, n_up, cell, momentum, nullptr));
+  CHK(spin_momentum_check<uint64_t>(who, n_sites, n_up, cell, momentum, nullptr));
   const SpinMomentumMeasureArgs a{n_sites, n_diag, masks};
   if (const char* why = spin_momentum_measure_error(a)) return fail(EIGENEX_ERR_ARG, who + ": " + why);
   if (!x) return fail(EIGENEX_ERR_ARG, who + ": x is NULL");
   if (n_diag > 0 && !diag_out) return fail(EIGENEX_ERR_ARG, who + ": an output list is NULL but its count is not zero");
   SpinMomentum64Basis b;
-  CHK(spin_momentum64_rows(who, n_sites, n_up, cell, momentum, &b, nullptr));
+  CHK(spin_momentum_rows(who, n_sites, n_up, cell, momentum, &b, nullptr));
   spin_momentum_measure_host(b, a, is_complex != 0, x, diag_out, norm2);
   return 0;
 }
@@ -3501,8 +3460,10 @@ int eigenex_spin_momentum_measure(eigenex_basis_t b, int x_ref, int n_diag, cons
   HIPCHK(hipMemcpyAsync(d_chunks, chunks.data(), sizeof(SpinMomentumMeasureChunk) * chunks.size(), hipMemcpyHostToDevice, c->stream));
   for (size_t k = 0; k < chunks.size(); ++k) {
     const size_t dfirst = std::min(k * kSpinMeasureChunk, (size_t)n_diag);
-    launch_spin_momentum_measure(c->stream, b->es, d_chunks + k, mk.wide ? nullptr : mk.reps.get(), mk.wide ? mk.reps64.get() : nullptr, x, mk.n_sites,
-                                 mk.cell, mk.n_sites / mk.cell, s.nloc, d_part, grid, grid);
+    mk.visit([&](const auto& part) {
+      launch_spin_momentum_measure(c->stream, b->es, d_chunks + k, part.reps.get(), x, mk.n_sites, mk.cell, mk.n_sites / mk.cell, s.nloc, d_part, grid,
+                                   grid);
+    });
     launch_spin_measure_reduce(c->stream, d_part, grid, grid, chunks[k].ndiag, 0, d_out + 1 + dfirst, nullptr, k == 0 ? d_out.get() : nullptr);
   }
   HIPCHK(hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, c->stream));

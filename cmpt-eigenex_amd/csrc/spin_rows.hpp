@@ -2,7 +2,7 @@
 // written once for real (E = double) and complex (E = SpinZ) vectors, as k_spin_site_apply<SECTOR, E> is, and through spin_rdm_rows.hpp
 // k_spin_rdm<SECTOR, TILE, E>; at the end of this file the walk of k_spin_momentum_spmv<E> and k_spin_momentum_expand<E>), shared by
 // the device code and by the host replays
-// tests/cpp/spin_{model,sector,measure,site,site_z,rdm,rdm_z,complex,momentum,momentum64}_sanitize.cpp, which run it under AddressSanitizer +
+// tests/cpp/spin_{model,sector,measure,site,site_z,rdm,rdm_z,complex,momentum}_sanitize.cpp, which run it under AddressSanitizer +
 // UBSan.  The kernels and the replays call THESE functions, so what a replay proves about them (every load inside its array, the
 // state equal to spin_sector_unrank, the sums equal to the CSR row loop and to spin_measure_host bit for bit) holds for the
 // kernels' rows as compiled.  No device construct in here: plain C++11.  spin_write_rows, spin_sector_unrank, spin_sector_rank
@@ -42,7 +42,7 @@ namespace eigenex {
 // Parity by population count, one instruction on the device.  Not spin_parity (spin_model.hpp), the folding form of the functions
 // written from the definition: the walk shares no arithmetic with what it is checked against.
 EIGENEX_HD bool spin_odd(uint32_t x) { return (__builtin_popcount(x) & 1) != 0; }
-EIGENEX_HD bool spin_odd(uint64_t x) { return (__builtin_popcountll(x) & 1) != 0; }  // the 64-bit states of spin_momentum64.hpp
+EIGENEX_HD bool spin_odd(uint64_t x) { return (__builtin_popcountll(x) & 1) != 0; }  // the 64-bit states of spin_momentum.hpp
 
 // The state of rank r among the states of n_sites sites with n_up up (spin_sector.hpp: unrank), in 32-bit arithmetic: n_sites
 // predicated steps, the same for every lane; k differs between lanes.  left and k end at 0 for every r below the dimension.
@@ -72,7 +72,7 @@ EIGENEX_HD double spin_row_diagonal(const uint32_t* dmask, const double* dval, i
   }
   return d;
 }
-// ... of a 64-bit state from the 64-bit masks of SpinOperatorView64 (spin_momentum64.hpp): the same additions
+// ... of a 64-bit state from the 64-bit masks of SpinOperatorView64 (below): the same additions
 EIGENEX_HD double spin_row_diagonal(const uint64_t* dmask, const double* dval, int ndiag, uint64_t s) {
   double d = 0.0;
   for (int t = 0; t < ndiag; ++t) {
@@ -265,28 +265,39 @@ EIGENEX_HD SpinZ spin_site_product(SpinZ w, bool real_coef, SpinZ x) {
 // Every state it is given is a row of the sector, so the bucket is not empty and every probe lies inside it.  A lane without
 // the term (the spins of the bond are equal, or the period of s' does not carry the momentum) searches for its own row's state
 // under the rule of spin_flip_targets: no load is branched around.  The coefficient of a term is fval * ratio[ri] * phase[li],
-// each product rounded (spin_momentum_value); ri = R_a * kMomentumRatioPitch + R_s' and li = (N - j*) mod N are valid table
+// each product rounded (spin_momentum_value); ri = R_a * SpinWord<Word>::kRatioPitch + R_s' and li = (N - j*) mod N are valid table
 // indices on every lane.  Phase 3 is the product form of the plain CSR kernels, so that an application equals the CSR upload of
 // spin_momentum_write_rows' rows bit for bit: real  yr = add_product_nofma(yr, value.re, xv * scale);  complex  p =
 // spin_cmul_nofma(value, x * scale), yr.re += p.re, yr.im += p.im, the diagonal (d, 0) included: k_spmv_z's stored-order sum.
 // lk.reps(i) and lk.bucket(i) are the two arrays; tb.ratio(i), tb.phase_re(i), tb.phase_im(i), tb.inv_sqrt(i) the tables.
-// The walk is written once for both state words: Word = uint32_t (spin_momentum.hpp, up to 32 sites) and Word = uint64_t
-// (spin_momentum64.hpp, up to 48 sites; k_spin_momentum_spmv<E, uint64_t>).  SpinWord<Word> has what differs besides the width:
-// the pitch of the ratio table and the population count.  The uint32_t instantiations are the functions this file had before
-// the word became a parameter, expression for expression.
-constexpr int kSpinRatioPitch = kSectorMaxSites + 1;  // spin_momentum.hpp: kMomentumRatioPitch
-constexpr int kSpinRatioPitch64 = 48 + 1;             // spin_momentum64.hpp: kMomentum64RatioPitch
+// The walk is written once for both state words, as the host side of spin_momentum.hpp is: Word = uint32_t (up to 32 sites) and
+// Word = uint64_t (up to 48 sites; k_spin_momentum_spmv<E, uint64_t>).  SpinWord<Word> is the one description of what depends on
+// the width: the bits, the population count, the limits of the ring and of the model, the longest period (a bit of `compatible`
+// and an entry of the phase tables each), the pitch of the ratio table and the model's view, whose term tables hold kMaxTerms
+// entries, a multiple of kSpinBatch.  The uint32_t instantiations are the functions this file had before the word became a
+// parameter, expression for expression.
+struct SpinOperatorView64;
 template <class Word>
 struct SpinWord;
 template <>
 struct SpinWord<uint32_t> {
-  static constexpr int kBits = 32, kRatioPitch = kSpinRatioPitch;
+  typedef SpinOperatorView Model;
+  static constexpr int kBits = 32, kMaxSites = kSectorMaxSites, kMaxBonds = kSpinMaxBonds, kMaxTerms = kSpinMaxTerms;
+  static constexpr int kMaxPeriod = kMaxSites, kRatioPitch = kMaxPeriod + 1;
   static EIGENEX_HD int popcount(uint32_t x) { return __builtin_popcount(x); }
 };
 template <>
 struct SpinWord<uint64_t> {
-  static constexpr int kBits = 64, kRatioPitch = kSpinRatioPitch64;
+  typedef SpinOperatorView64 Model;
+  static constexpr int kBits = 64, kMaxSites = 48, kMaxBonds = 128, kMaxTerms = (kMaxBonds + kMaxSites + kSpinBatch - 1) / kSpinBatch * kSpinBatch;
+  static constexpr int kMaxPeriod = kMaxSites, kRatioPitch = kMaxPeriod + 1;
   static EIGENEX_HD int popcount(uint64_t x) { return __builtin_popcountll(x); }
+};
+// SpinOperatorView (spin_model.hpp) with 64-bit masks; no transverse field, so every flip mask has two bits
+struct SpinOperatorView64 {
+  int n_sites, ndiag, nflip, pad;
+  uint64_t dmask[SpinWord<uint64_t>::kMaxTerms], fmask[SpinWord<uint64_t>::kMaxTerms];
+  double dval[SpinWord<uint64_t>::kMaxTerms], fval[SpinWord<uint64_t>::kMaxTerms];
 };
 
 template <class Word>
@@ -409,7 +420,7 @@ EIGENEX_HD E spin_momentum_expand_row(uint32_t s, int n_sites, int cell, int n_t
   return on ? spin_momentum_expanded(xv, tb.phase_re(l), tb.phase_im(l), tb.inv_sqrt(o.period)) : zero;
 }
 
-// Diagonal correlations in the momentum basis (spin_momentum64.hpp; kernels.hip: k_spin_momentum_measure<E, Word>), one row
+// Diagonal correlations in the momentum basis (spin_momentum.hpp; kernels.hip: k_spin_momentum_measure<E, Word>), one row
 // per lane: w = |x_a|^2 of the row's own element, then for a batch of masks the integer c_t(a) = sum over all n_trans rotations
 // T^r a of the product of sigma over the mask -- the full trip count on every lane -- and one fma per term.
 EIGENEX_HD double spin_momentum_weight(double x) { return x * x; }

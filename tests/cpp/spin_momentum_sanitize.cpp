@@ -1,10 +1,14 @@
-// csrc/spin_momentum.hpp and the momentum part of csrc/spin_rows.hpp under AddressSanitizer + UBSan, stand-alone (no library, no GPU):
-//   g++ -std=c++11 -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -I cmpt-eigenex_amd/csrc spin_momentum_sanitize.cpp
-// For every shape: the basis, its buckets and the search's trip count; then the row walk of k_spin_momentum_spmv<E> -- the
-// kernel's own functions on the real tables, every load bounds-checked -- whose sum per row must equal, bit for bit, the sum over
-// the entries spin_momentum_write_rows wrote for that row (written into exactly-sized arrays), added the way k_spmv / k_spmv_z
-// add them; and the walk of k_spin_momentum_expand<E> against spin_momentum_expand_host, bit for bit.  32 sites are among the
-// shapes, so that UBSan sees every shift of the rotation.
+// csrc/spin_momentum.hpp and the momentum part of csrc/spin_rows.hpp under AddressSanitizer + UBSan, stand-alone (no library, no
+// GPU), for the state word given as the argument, 32 or 64:
+//   g++ -std=c++11 -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -pthread -I cmpt-eigenex_amd/csrc spin_momentum_sanitize.cpp
+// For every shape: the threaded, pruned enumeration against the plain ascending walk, the buckets and the search's trip count;
+// then the row walk of k_spin_momentum_spmv<E, Word> -- the kernel's own functions on the real tables, every load bounds-checked --
+// whose sum per row must equal, bit for bit, the sum over the entries spin_momentum_write_rows wrote for that row (written into
+// exactly-sized arrays), added the way k_spmv / k_spmv_z add them; the walk of k_spin_momentum_measure<E, Word> against
+// spin_momentum_measure_host, bit for bit, in the 64-bit run with both words where the ring has at most 32 sites; and in the
+// 32-bit run the walk of k_spin_momentum_expand<E> against spin_momentum_expand_host, bit for bit.  32 sites are among the shapes
+// of the 32-bit run and 33, 36 and 48 among those of the 64-bit run, so that UBSan sees every shift of either rotation; 19, 20
+// and 22 sites are on both sides of the size from which the enumeration is cut into chunks.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -16,27 +20,29 @@
 
 using namespace eigenex;
 
+template <class Word>
 struct CheckedLookup {
-  const SpinMomentumBasis* b;
-  std::uint32_t reps(std::uint32_t i) const { return b->reps.at(i); }
+  const SpinMomentumBasisOf<Word>* b;
+  Word reps(std::uint32_t i) const { return b->reps.at(i); }
   std::uint32_t bucket(std::uint32_t i) const { return b->bucket.at(i); }
 };
+template <class Word>
 struct CheckedMomentumTables {
-  const SpinMomentumTables* t;
+  const SpinMomentumTablesOf<Word>* t;
   double ratio(int i) const {
-    EXPECT(i >= 0 && i < kMomentumRatioPitch * kMomentumRatioPitch);
+    EXPECT(i >= 0 && i < SpinWord<Word>::kRatioPitch * SpinWord<Word>::kRatioPitch);
     return t->ratio[i];
   }
   double inv_sqrt(int i) const {
-    EXPECT(i >= 1 && i < kMomentumRatioPitch);
+    EXPECT(i >= 1 && i < SpinWord<Word>::kRatioPitch);
     return t->inv_sqrt[i];
   }
   double phase_re(int i) const {
-    EXPECT(i >= 0 && i < kMomentumMaxPeriod);
+    EXPECT(i >= 0 && i < SpinWord<Word>::kMaxPeriod);
     return t->phase_re[i];
   }
   double phase_im(int i) const {
-    EXPECT(i >= 0 && i < kMomentumMaxPeriod);
+    EXPECT(i >= 0 && i < SpinWord<Word>::kMaxPeriod);
     return t->phase_im[i];
   }
 };
@@ -61,19 +67,19 @@ static std::vector<double> test_vector(std::size_t n, std::uint64_t seed) {
   return x;
 }
 
-// the row walk of k_spin_momentum_spmv<E> on row r, before the shift
-template <class E, class Vector>
-static E walk_row(const SpinMomentumView& v, const SpinMomentumBasis& b, const Vector& xs, std::int64_t r, double scale) {
-  const CheckedLookup lk{&b};
-  const CheckedMomentumTables tb{&v.tab};
-  const SpinOperatorView& m = v.model;
-  const std::uint32_t s = lk.reps((std::uint32_t)r);
+// the row walk of k_spin_momentum_spmv<E, Word> on row r, before the shift
+template <class E, class Word, class Vector>
+static E walk_row(const SpinMomentumViewOf<Word>& v, const SpinMomentumBasisOf<Word>& b, const Vector& xs, std::int64_t r, double scale) {
+  const CheckedLookup<Word> lk{&b};
+  const CheckedMomentumTables<Word> tb{&v.tab};
+  const typename SpinWord<Word>::Model& m = v.model;
+  const Word s = lk.reps((std::uint32_t)r);
   const int period = spin_orbit(s, m.n_sites, v.cell, v.n_trans).period;
   EXPECT(period == b.period.at((std::size_t)r));
   const double d = spin_row_diagonal(m.dmask, m.dval, m.ndiag, s);
   E yr = spin_momentum_add(E{}, SpinZ{d, 0.0}, element_of(xs, (std::uint32_t)r), scale);
   for (int t0 = 0; t0 < m.nflip; t0 += kSpinBatch) {
-    EXPECT(t0 + kSpinBatch <= kSpinMaxTerms);
+    EXPECT(t0 + kSpinBatch <= SpinWord<Word>::kMaxTerms);
     bool on[kSpinBatch];
     std::uint32_t column[kSpinBatch];
     int ri[kSpinBatch], li[kSpinBatch];
@@ -117,13 +123,14 @@ struct Model {
     return SpinModelArgs{n_sites, (int)si.size(), si.data(), sj.data(), jz.data(), jxy.data(), hz.empty() ? nullptr : hz.data(), nullptr};
   }
 };
-// a ring invariant under the translation by `cell` sites: nearest neighbours and, with `far`, bonds of that reach, couplings and hz by place in the cell
-static Model ring(int L, int cell, int far) {
+// a ring invariant under the translation by `cell` sites: nearest neighbours and, with `far`, bonds of that reach, couplings and
+// hz by place in the cell.  On two sites the ring is one bond, or with `twice` that bond both ways round.
+static Model ring(int L, int cell, int far, bool twice = false) {
   Model m;
   m.n_sites = L;
   for (int i = 0; i < L; ++i) {
     const int p = i % cell;
-    if (!(L == 2 && i == 1)) m.si.push_back(i), m.sj.push_back((i + 1) % L), m.jz.push_back(0.7 + 0.25 * p), m.jxy.push_back(1.1 + 0.125 * p);
+    if (twice || !(L == 2 && i == 1)) m.si.push_back(i), m.sj.push_back((i + 1) % L), m.jz.push_back(0.7 + 0.25 * p), m.jxy.push_back(1.1 + 0.125 * p);
     if (far > 1) m.si.push_back((i + far) % L), m.sj.push_back(i), m.jz.push_back(0.3 - 0.05 * p), m.jxy.push_back(p == 1 ? 0.0 : 0.2 + 0.0625 * p);
   }
   if (cell > 1)
@@ -131,8 +138,9 @@ static Model ring(int L, int cell, int far) {
   return m;
 }
 
-template <class E, class Vector>
-static void check_rows(const SpinModelArgs& a, const SpinMomentumView& v, const SpinMomentumBasis& b, const std::vector<double>& x, double scale) {
+template <class E, class Vector, class Word>
+static void check_rows(const SpinModelArgs& a, const SpinMomentumViewOf<Word>& v, const SpinMomentumBasisOf<Word>& b, const std::vector<double>& x,
+                       double scale) {
   const std::int64_t dim = (std::int64_t)b.reps.size();
   const std::int64_t begin = dim > 3 ? 1 : 0, n_rows = dim - begin;  // a range from the middle
   std::vector<std::int64_t> rowptr((std::size_t)n_rows + 1);
@@ -154,6 +162,7 @@ static void check_rows(const SpinModelArgs& a, const SpinMomentumView& v, const 
     for (std::int64_t p = 0; p < nnz; ++p) EXPECT(same(val[(std::size_t)(2 * p + 1)], 0.0));
 }
 
+// the walk of k_spin_momentum_expand<E> (32-bit states only: there is no Sz-sector operator beyond 32 sites)
 template <class E, class Vector>
 static void check_expand(const SpinMomentumView& v, const SpinMomentumBasis& b, const std::vector<double>& x, bool is_complex) {
   const int L = b.n_sites, es = is_complex ? 2 : 1;
@@ -164,8 +173,8 @@ static void check_expand(const SpinMomentumView& v, const SpinMomentumBasis& b, 
   Model none = ring(L, 1, 0);
   spin_sector_build_view(none.args(), b.n_up, *sv);
   const CheckedBinomials bin(*sv);
-  const CheckedLookup lk{&b};
-  const CheckedMomentumTables tb{&v.tab};
+  const CheckedLookup<std::uint32_t> lk{&b};
+  const CheckedMomentumTables<std::uint32_t> tb{&v.tab};
   const Vector xs{&x};
   double n2x = 0.0, n2y = 0.0;
   for (double e : x) n2x += e * e;
@@ -181,90 +190,215 @@ static void check_expand(const SpinMomentumView& v, const SpinMomentumBasis& b, 
   EXPECT(std::fabs(n2y - n2x) <= 1e-12 * n2x);  // expand preserves the norm
 }
 
+// the sums of k_spin_momentum_measure<E, Word> over the rows `states` in ascending order, chunk by chunk, against the host
+// definition on the basis b (of either word: the same rows)
+template <class Word, class HostWord>
+static void check_measure(const SpinMomentumBasisOf<HostWord>& b, const std::vector<Word>& states, const std::vector<double>& x, bool is_complex) {
+  const int L = b.n_sites;
+  std::vector<std::uint64_t> masks;
+  for (int i = 0; i < L; i += 5) masks.push_back(std::uint64_t(1) << i);
+  for (int r = 1; r < L; r += 2) masks.push_back(std::uint64_t(1) | (std::uint64_t(1) << r));
+  masks.push_back((std::uint64_t(1) << (L - 1)) | 3u);
+  masks.push_back(spin_momentum_site_mask<std::uint64_t>(L));
+  const SpinMomentumMeasureArgs a{L, (int)masks.size(), masks.data()};
+  EXPECT(spin_momentum_measure_error(a) == nullptr);
+  std::vector<double> want(masks.size());  // exactly sized
+  double want_norm = 0.0;
+  spin_momentum_measure_host(b, a, is_complex, x.data(), want.data(), &want_norm);
+  std::vector<SpinMomentumMeasureChunk> chunks;
+  spin_momentum_measure_build_chunks(a, chunks);
+  EXPECT(chunks.size() == (masks.size() + kSpinMeasureChunk - 1) / kSpinMeasureChunk);
+  for (std::size_t k = 0; k < chunks.size(); ++k) {
+    double nrm = 0.0, dg[kSpinMeasureChunk] = {0.0};
+    for (std::size_t r = 0; r < b.reps.size(); ++r) {
+      const Word s = states.at(r);
+      double w;
+      if (is_complex) {
+        const SpinZ xs = SpinZ{x.at(2 * r), x.at(2 * r + 1)};
+        nrm = spin_norm_add(nrm, xs), w = spin_momentum_weight(xs);
+      } else {
+        nrm = spin_norm_add(nrm, x.at(r)), w = spin_momentum_weight(x.at(r));
+      }
+      for (int t0 = 0; t0 < kSpinMeasureChunk; t0 += kSpinBatch)
+        if (t0 < chunks[k].ndiag) spin_momentum_measure_diagonals(w, s, chunks[k].dmask + t0, L, b.cell, b.n_trans, dg + t0);
+    }
+    EXPECT(same(nrm, want_norm));
+    for (int t = 0; t < chunks[k].ndiag; ++t) EXPECT(same(dg[t], want.at(k * kSpinMeasureChunk + (std::size_t)t)));
+  }
+}
+
+// the plain ascending walk of the Sz sector, from the definition
+template <class Word>
+static void plain_rows(int L, int n_up, int cell, int m, std::vector<Word>& reps, std::vector<std::uint8_t>& period) {
+  const int N = L / cell;
+  const std::uint64_t end = std::uint64_t(1) << L;
+  for (std::uint64_t s = n_up == 0 ? 0 : (std::uint64_t(1) << n_up) - 1; s < end;) {
+    const SpinMomentumOrbitOf<Word> o = spin_momentum_orbit_host((Word)s, L, cell);
+    if (o.rep == (Word)s && (m * o.period) % N == 0) reps.push_back((Word)s), period.push_back((std::uint8_t)o.period);
+    if (n_up == 0) break;
+    const std::uint64_t c = s & (~s + 1), r = s + c;
+    s = (((r ^ s) >> 2) / c) | r;
+  }
+}
+
+// what only one word can check: expand with 32-bit states; with 64-bit ones that the 32-bit basis has the same rows and lookup
+// where it exists, and the measurement walk on its 32-bit words
+static void check_word(const SpinMomentumView& v, const SpinMomentumBasis& b, const std::vector<double>& x, const std::vector<double>& xz) {
+  check_expand<SpinZ, CheckedVectorZ>(v, b, xz, true);
+  if (spin_momentum_is_real(b.n_trans, b.momentum)) check_expand<double, CheckedVector>(v, b, x, false);
+}
+static void check_word(const SpinMomentum64View&, const SpinMomentum64Basis& b, const std::vector<double>& x, const std::vector<double>& xz) {
+  if (b.n_sites > 32) return;
+  SpinMomentumBasis b32;
+  EXPECT(spin_momentum_build_basis(b.n_sites, b.n_up, b.cell, b.momentum, &b32) == (std::int64_t)b.reps.size());
+  EXPECT(b32.period == b.period && b32.bucket == b.bucket && b32.steps == b.steps && b32.reps.size() == b.reps.size());
+  for (std::size_t r = 0; r < b32.reps.size(); ++r) EXPECT((std::uint64_t)b32.reps[r] == b.reps.at(r));
+  check_measure(b, b32.reps, xz, true);
+  check_measure(b, b32.reps, x, false);
+}
+
+template <class Word>
 static void check_shape(int L, int n_up, int cell, int far) {
   const int N = L / cell;
-  const Model model = ring(L, cell, far);
+  const Model model = ring(L, cell, far, sizeof(Word) == 8);
   const SpinModelArgs a = model.args();
-  EXPECT(spin_momentum_model_error(a, n_up, cell).empty());
+  EXPECT(spin_momentum_model_error<Word>(a, n_up, cell).empty());
   std::int64_t total = 0;
   for (int m = 0; m < N; ++m) {
-    EXPECT(spin_momentum_geometry_error(L, n_up, cell, m).empty());
+    EXPECT(spin_momentum_geometry_error<Word>(L, n_up, cell, m).empty());
     if (N > 13 && !(m <= 1 || m == N / 2 || m == N - 1)) {  // the dimensions of all, the walks of four
-      total += spin_momentum_build_basis(L, n_up, cell, m, nullptr);
+      total += spin_momentum_build_basis<Word>(L, n_up, cell, m, nullptr);
       continue;
     }
-    SpinMomentumBasis b;
+    SpinMomentumBasisOf<Word> b;
     const std::int64_t dim = spin_momentum_build_basis(L, n_up, cell, m, &b);
-    EXPECT(dim == (std::int64_t)b.reps.size() && dim == spin_momentum_build_basis(L, n_up, cell, m, nullptr));
+    EXPECT(dim == (std::int64_t)b.reps.size() && dim == spin_momentum_build_basis<Word>(L, n_up, cell, m, nullptr));
     total += dim;
+    std::vector<Word> plain;
+    std::vector<std::uint8_t> plain_period;
+    plain_rows(L, n_up, cell, m, plain, plain_period);
+    EXPECT(plain == b.reps && plain_period == b.period);  // the chunks and the pruning change nothing
+    SpinMomentumBasisOf<Word> bare;  // without the lookup: the same rows, no table
+    EXPECT(spin_momentum_build_basis(L, n_up, cell, m, &bare, false) == dim && bare.reps == b.reps && bare.period == b.period && bare.bucket.empty() &&
+           bare.steps == 0);
     if (dim == 0) continue;
     EXPECT(b.bucket.size() == (std::size_t(1) << (L - b.h)) + 1 && b.bucket.front() == 0 && b.bucket.back() == dim);
     std::size_t largest = 0;
     for (std::size_t i = 0; i + 1 < b.bucket.size(); ++i) largest = std::max(largest, (std::size_t)(b.bucket[i + 1] - b.bucket[i]));
     EXPECT((std::size_t(1) << b.steps) >= largest + 1 && (b.steps == 0 || (std::size_t(1) << (b.steps - 1)) < largest + 1));
-    const CheckedLookup lk{&b};
+    const CheckedLookup<Word> lk{&b};
     for (std::int64_t r = 0; r < dim; ++r) {
       if (r > 0) EXPECT(b.reps[(std::size_t)r - 1] < b.reps[(std::size_t)r]);
       EXPECT(spin_momentum_index(lk, b.reps[(std::size_t)r], b.h, b.steps) == (std::uint32_t)r);
-      const SpinMomentumOrbit o = spin_momentum_orbit_host(b.reps[(std::size_t)r], L, cell);
-      const SpinOrbit w = spin_orbit(b.reps[(std::size_t)r], L, cell, N);
+      const SpinMomentumOrbitOf<Word> o = spin_momentum_orbit_host(b.reps[(std::size_t)r], L, cell);
+      const SpinOrbitOf<Word> w = spin_orbit(b.reps[(std::size_t)r], L, cell, N);
       EXPECT(o.rep == b.reps[(std::size_t)r] && o.j == 0 && o.period == b.period[(std::size_t)r] && N % o.period == 0);
       EXPECT(w.rep == o.rep && w.j == o.j && w.period == o.period);
     }
-    std::unique_ptr<SpinMomentumView> v(new SpinMomentumView());
+    std::unique_ptr<SpinMomentumViewOf<Word>> v(new SpinMomentumViewOf<Word>());
     spin_momentum_build_view(a, b, *v);
-    EXPECT(v->first_rep == b.reps[0]);
+    EXPECT(v->first_rep == b.reps[0] && v->model.ndiag <= SpinWord<Word>::kMaxTerms && v->model.nflip <= SpinWord<Word>::kMaxTerms);
     const std::vector<double> xz = test_vector((std::size_t)(2 * dim), 17 + (std::uint64_t)m);
+    const std::vector<double> x = test_vector((std::size_t)dim, 5 + (std::uint64_t)m);
     check_rows<SpinZ, CheckedVectorZ>(a, *v, b, xz, 1.0);
     check_rows<SpinZ, CheckedVectorZ>(a, *v, b, xz, -0.37);
-    check_expand<SpinZ, CheckedVectorZ>(*v, b, xz, true);
+    check_measure(b, b.reps, xz, true);
+    check_measure(b, b.reps, x, false);
     if (spin_momentum_is_real(N, m)) {
-      const std::vector<double> x = test_vector((std::size_t)dim, 5 + (std::uint64_t)m);
       check_rows<double, CheckedVector>(a, *v, b, x, 1.0);
       check_rows<double, CheckedVector>(a, *v, b, x, 1.7);
-      check_expand<double, CheckedVector>(*v, b, x, false);
     }
+    check_word(*v, b, x, xz);
   }
-  EXPECT(total == spin_sector_dim(L, n_up));  // the momentum sectors tile the Sz sector
+  std::int64_t binom = 1;  // C(L, n_up)
+  for (int i = 1; i <= n_up; ++i) binom = binom * (L - n_up + i) / i;
+  EXPECT(total == binom);  // the momentum sectors tile the Sz sector
 }
 
-int main() {
-  // every state's orbit by the kernel's walk against the definition's, on a ring where every period occurs
+// every state's orbit by the kernel's walk against the definition's, on a ring of 12 sites, where every period occurs, and on
+// `copies` of it side by side: the same period, in the high bits too
+template <class Word>
+static void check_orbits(int copies) {
   for (std::uint32_t s = 0; s < (1u << 12); ++s)
     for (int cell = 1; cell <= 6; ++cell) {
       if (12 % cell) continue;
-      const SpinMomentumOrbit o = spin_momentum_orbit_host(s, 12, cell);
-      const SpinOrbit w = spin_orbit(s, 12, cell, 12 / cell);
-      EXPECT(w.rep == o.rep && w.j == o.j && w.period == o.period);
+      const int period = spin_momentum_orbit_host(s, 12, cell).period;
+      Word state = 0;
+      for (int c = 0; c < copies; ++c) state |= (Word)s << (12 * c);
+      const SpinMomentumOrbitOf<Word> o = spin_momentum_orbit_host(state, 12 * copies, cell);
+      const SpinOrbitOf<Word> w = spin_orbit(state, 12 * copies, cell, 12 * copies / cell);
+      EXPECT(w.rep == o.rep && w.j == o.j && w.period == o.period && o.period == period);
     }
+}
+
+static void run(std::uint32_t) {
+  check_orbits<std::uint32_t>(1);
   EXPECT(spin_momentum_translate(0x80000001u, 32, 1) == 0x00000003u && spin_momentum_translate(0xffff0000u, 32, 16) == 0x0000ffffu);
-  const int shapes[][4] = {{2, 1, 1, 0},  {4, 2, 1, 0},  {6, 0, 1, 0},  {6, 6, 1, 0},  {6, 3, 3, 2},  {8, 4, 1, 0},  {8, 4, 2, 3},   {8, 3, 2, 3},
-                           {9, 4, 1, 0},  {12, 6, 1, 2}, {12, 6, 2, 5}, {12, 4, 3, 5}, {13, 6, 1, 0}, {16, 8, 1, 0}, {31, 2, 1, 0},  {32, 2, 1, 0},
-                           {32, 3, 1, 0}, {32, 31, 1, 0}, {32, 2, 16, 0}, {32, 3, 2, 15}};
-  for (const auto& s : shapes) check_shape(s[0], s[1], s[2], s[3]);
+  const int shapes[][4] = {{2, 1, 1, 0},  {4, 2, 1, 0},   {6, 0, 1, 0},   {6, 6, 1, 0},   {6, 3, 3, 2},  {8, 4, 1, 0},  {8, 4, 2, 3},  {8, 3, 2, 3},
+                           {9, 4, 1, 0},  {12, 6, 1, 2},  {12, 6, 2, 5},  {12, 4, 3, 5},  {13, 6, 1, 0}, {16, 8, 1, 0}, {31, 2, 1, 0}, {32, 2, 1, 0},
+                           {32, 3, 1, 0}, {32, 31, 1, 0}, {32, 2, 16, 0}, {32, 3, 2, 15}, {19, 5, 1, 0}, {20, 5, 1, 0}, {22, 4, 2, 0}};
+  for (const auto& s : shapes) check_shape<std::uint32_t>(s[0], s[1], s[2], s[3]);
   // refusals
-  {
-    const Model open = [] {
-      Model m = ring(8, 1, 0);
-      m.si.pop_back(), m.sj.pop_back(), m.jz.pop_back(), m.jxy.pop_back();
-      return m;
-    }();
-    EXPECT(spin_momentum_model_error(open.args(), 4, 1).find("bond") != std::string::npos);
-    Model altered = ring(8, 1, 0);
-    altered.jxy[3] = 1.25;
-    EXPECT(spin_momentum_model_error(altered.args(), 4, 1).find("bond 2") != std::string::npos);  // whose image, bond 3, differs
-    Model field = ring(8, 2, 0);
-    field.hz[5] = 0.5;
-    EXPECT(spin_momentum_model_error(field.args(), 4, 2).find("hz at site 3") != std::string::npos);
-    EXPECT(!spin_momentum_geometry_error(8, 4, 3, 0).empty() && !spin_momentum_geometry_error(8, 4, 8, 0).empty() &&
-           !spin_momentum_geometry_error(8, 4, 1, 8).empty() && !spin_momentum_geometry_error(8, 4, 1, -1).empty() &&
-           !spin_momentum_geometry_error(33, 4, 1, 0).empty() && !spin_momentum_geometry_error(8, 9, 1, 0).empty());
-    EXPECT(spin_momentum_build_basis(6, 0, 1, 1, nullptr) == 0 && spin_momentum_build_basis(31, 2, 1, 7, nullptr) == 15);
+  const Model open = [] {
+    Model m = ring(8, 1, 0);
+    m.si.pop_back(), m.sj.pop_back(), m.jz.pop_back(), m.jxy.pop_back();
+    return m;
+  }();
+  EXPECT(spin_momentum_model_error<std::uint32_t>(open.args(), 4, 1).find("bond") != std::string::npos);
+  Model altered = ring(8, 1, 0);
+  altered.jxy[3] = 1.25;
+  EXPECT(spin_momentum_model_error<std::uint32_t>(altered.args(), 4, 1).find("bond 2") != std::string::npos);  // whose image, bond 3, differs
+  Model field = ring(8, 2, 0);
+  field.hz[5] = 0.5;
+  EXPECT(spin_momentum_model_error<std::uint32_t>(field.args(), 4, 2).find("hz at site 3") != std::string::npos);
+  EXPECT(!spin_momentum_geometry_error<std::uint32_t>(8, 4, 3, 0).empty() && !spin_momentum_geometry_error<std::uint32_t>(8, 4, 8, 0).empty() &&
+         !spin_momentum_geometry_error<std::uint32_t>(8, 4, 1, 8).empty() && !spin_momentum_geometry_error<std::uint32_t>(8, 4, 1, -1).empty() &&
+         spin_momentum_geometry_error<std::uint32_t>(33, 4, 1, 0) == "n_sites must be 2..32" && !spin_momentum_geometry_error<std::uint32_t>(8, 9, 1, 0).empty());
+  EXPECT(spin_momentum_build_basis<std::uint32_t>(6, 0, 1, 1, nullptr) == 0 && spin_momentum_build_basis<std::uint32_t>(31, 2, 1, 7, nullptr) == 15);
+}
+
+static void run(std::uint64_t) {
+  check_orbits<std::uint64_t>(1);
+  check_orbits<std::uint64_t>(4);
+  EXPECT(spin_momentum_translate((std::uint64_t(1) << 47) | 1u, 48, 1) == 3u && spin_momentum_translate(std::uint64_t(0xffffff000000ull), 48, 24) == 0xffffffull);
+  EXPECT(spin_momentum_translate((std::uint64_t(1) << 32) | 1u, 33, 1) == 3u);
+  const int shapes[][4] = {{2, 1, 1, 0},  {8, 4, 1, 0},  {12, 6, 2, 5},  {16, 8, 1, 0},  {24, 3, 1, 0},  {32, 3, 2, 15}, {33, 2, 1, 0},  {33, 3, 3, 4},
+                           {34, 2, 1, 0}, {36, 3, 1, 2}, {36, 4, 2, 17}, {36, 2, 18, 0}, {40, 2, 4, 19}, {48, 3, 1, 0},  {48, 2, 24, 0}, {48, 47, 1, 0},
+                           {48, 0, 1, 0}, {48, 48, 2, 0}};
+  for (const auto& s : shapes) check_shape<std::uint64_t>(s[0], s[1], s[2], s[3]);
+  // refusals
+  EXPECT(spin_momentum_geometry_error<std::uint64_t>(49, 4, 1, 0) == "n_sites must be 2..48" && spin_momentum_geometry_error<std::uint64_t>(48, 4, 1, 47).empty() &&
+         !spin_momentum_geometry_error<std::uint64_t>(48, 4, 1, 48).empty() && !spin_momentum_geometry_error<std::uint64_t>(48, 4, 5, 0).empty() &&
+         !spin_momentum_geometry_error<std::uint64_t>(48, 49, 1, 0).empty() && !spin_momentum_geometry_error<std::uint64_t>(48, 4, 48, 0).empty());
+  Model open = ring(36, 1, 0);
+  open.si.pop_back(), open.sj.pop_back(), open.jz.pop_back(), open.jxy.pop_back();
+  EXPECT(spin_momentum_model_error<std::uint64_t>(open.args(), 18, 1).find("bond") != std::string::npos);
+  Model many = ring(43, 1, 2);
+  for (int i = 0; i < 43; ++i) many.si.push_back(i), many.sj.push_back((i + 3) % 43), many.jz.push_back(0.1), many.jxy.push_back(0.1);
+  EXPECT(many.si.size() == 129 && spin_momentum_model_error<std::uint64_t>(many.args(), 21, 1) == "n_bonds must be 0..128");
+  many.si.pop_back(), many.sj.pop_back(), many.jz.pop_back(), many.jxy.pop_back();
+  EXPECT(spin_momentum_model_error<std::uint64_t>(many.args(), 21, 1).find("not invariant") != std::string::npos);  // 128 bonds are counted, then checked
+  const std::uint64_t bad[2] = {1u, std::uint64_t(1) << 36}, zero[2] = {1u, 0u};
+  EXPECT(spin_momentum_measure_error(SpinMomentumMeasureArgs{36, 2, bad}) != nullptr && spin_momentum_measure_error(SpinMomentumMeasureArgs{36, 2, zero}) != nullptr &&
+         spin_momentum_measure_error(SpinMomentumMeasureArgs{37, 2, bad}) == nullptr && spin_momentum_measure_error(SpinMomentumMeasureArgs{36, 0, nullptr}) == nullptr);
+  EXPECT(spin_momentum_build_basis<std::uint64_t>(36, 0, 1, 1, nullptr) == 0 && spin_momentum_build_basis<std::uint64_t>(40, 4, 1, 0, nullptr) == 2290 &&
+         spin_momentum_build_basis<std::uint64_t>(36, 5, 1, 0, nullptr) == 10472);
+}
+
+int main(int argc, char** argv) {
+  const bool wide = argc == 2 && std::strcmp(argv[1], "64") == 0;
+  if (!wide && !(argc == 2 && std::strcmp(argv[1], "32") == 0)) {
+    std::fprintf(stderr, "usage: spin_momentum_sanitize 32|64\n");
+    return 2;
   }
+  if (wide)
+    run(std::uint64_t());
+  else
+    run(std::uint32_t());
   if (fails) {
     std::fprintf(stderr, "%d check(s) failed\n", fails);
     return 1;
   }
-  std::printf("SPIN MOMENTUM OK\n");
+  std::puts(wide ? "SPIN MOMENTUM64 OK" : "SPIN MOMENTUM OK");
   return 0;
 }

@@ -1,7 +1,7 @@
 """Momentum sectors of up to 48 sites on the host: eigenex_spin_momentum64_dim / _states / _csr against the 32-bit functions byte
 for byte where both exist and against tests/spin_momentum64_reference.py beyond 32 sites, eigenex_spin_momentum_measure_host against
 the reference and against expand + eigenex_spin_measure_host, the refusals with their messages, and the host code and the 64-bit
-row walk (csrc/spin_momentum64.hpp, csrc/spin_rows.hpp) under AddressSanitizer + UBSan in a stand-alone program.  No GPU."""
+row walk (csrc/spin_momentum.hpp, csrc/spin_rows.hpp) under AddressSanitizer + UBSan in a stand-alone program.  No GPU."""
 import os
 import re
 import shutil
@@ -271,7 +271,7 @@ def test_refusals_and_their_messages(capi):
 
 # ---- 6. the sanitizer program ----
 def test_momentum64_host_code_under_sanitizers(tmp_path):
-    """csrc/spin_momentum64.hpp (checks, threaded enumeration, buckets, tables, rows, measure) and the 64-bit momentum walk of
+    """csrc/spin_momentum.hpp on 64-bit states (checks, threaded enumeration, buckets, tables, rows, measure) and the 64-bit momentum walk of
     csrc/spin_rows.hpp -- the functions k_spin_momentum_spmv<E, uint64_t> and k_spin_momentum_measure<E, Word> call -- compiled into
     a stand-alone program with AddressSanitizer + UBSan: every load bounds-checked, each row's sum compared bitwise with the sum
     over the stored entries; 33, 36 and 48 sites among the shapes."""
@@ -280,9 +280,9 @@ def test_momentum64_host_code_under_sanitizers(tmp_path):
     exe = str(tmp_path / "spin_momentum64_sanitize")
     subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-ffp-contract=off", "-pthread", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cmpt-eigenex_amd", "include"),
-                           "-I", os.path.join(ROOT, "cmpt-eigenex_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "spin_momentum64_sanitize.cpp"),
+                           "-I", os.path.join(ROOT, "cmpt-eigenex_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "spin_momentum_sanitize.cpp"),
                            "-o", exe])
-    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    out = subprocess.run([exe, "64"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert out.returncode == 0, (out.stdout.decode()[-1500:], out.stderr.decode()[-2000:])
     assert b"SPIN MOMENTUM64 OK" in out.stdout
 

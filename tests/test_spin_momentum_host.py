@@ -15,6 +15,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import spin_momentum_reference as ref  # noqa: E402
+import spin_momentum64_reference as ref64  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = np.finfo(np.float64).eps
@@ -83,6 +84,22 @@ def test_dimensions_of_larger_sectors(capi):
         capi.spin_momentum_dim(6, 0, 1)
     states, periods = capi.spin_momentum_states(32, 31, 5)
     assert states.tolist() == [0x7FFFFFFF] and periods.tolist() == [32]  # bit 31 rotates into bit 0
+
+
+@pytest.mark.parametrize("L,n_up,cell", [(20, 5, 1), (22, 4, 2)])
+def test_chunked_enumeration_equals_the_pure_python_reference(capi, L, n_up, cell):
+    """From 20 sites the rows come from 2^16 pruned prefixes on several threads: the list and the periods must be those of
+    tests/spin_momentum64_reference.py, which walks the necklaces in pure Python and shares nothing with the C code."""
+    N = L // cell
+    for m in (0, 1, N // 2):
+        want = ref64.representatives(L, n_up, cell, m)
+        if not want:
+            with pytest.raises(capi.EigenexError, match="empty"):
+                capi.spin_momentum_dim(L, n_up, m, cell)
+            continue
+        assert capi.spin_momentum_dim(L, n_up, m, cell) == len(want)
+        states, periods = capi.spin_momentum_states(L, n_up, m, cell)
+        assert states.dtype == np.uint32 and states.tolist() == [s for s, _ in want] and periods.tolist() == [p for _, p in want]
 
 
 # ---- 3. the rows ----
@@ -228,18 +245,19 @@ def test_refusals_and_their_messages(capi):
 
 # ---- 6. the sanitizer program ----
 def test_momentum_host_code_under_sanitizers(tmp_path):
-    """csrc/spin_momentum.hpp (checks, enumeration, buckets, tables, rows, expand) and the momentum walk of csrc/spin_rows.hpp --
-    the functions k_spin_momentum_spmv<E> and k_spin_momentum_expand<E> call -- compiled into a stand-alone program with
-    AddressSanitizer + UBSan: every load bounds-checked, each row's sum compared bitwise with the sum over the stored entries, the
-    expand walk bitwise with spin_momentum_expand_host; 32 sites among the shapes."""
+    """csrc/spin_momentum.hpp on 32-bit states (checks, threaded enumeration, buckets, tables, rows, expand, measure) and the
+    momentum walk of csrc/spin_rows.hpp -- the functions k_spin_momentum_spmv<E>, k_spin_momentum_measure<E, uint32_t> and
+    k_spin_momentum_expand<E> call -- compiled into a stand-alone program with AddressSanitizer + UBSan: every load bounds-checked,
+    the enumeration compared with the plain walk, each row's sum bitwise with the sum over the stored entries, the expand walk
+    bitwise with spin_momentum_expand_host; 19, 20, 22 and 32 sites among the shapes."""
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
     exe = str(tmp_path / "spin_momentum_sanitize")
     subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-ffp-contract=off", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cmpt-eigenex_amd", "include"),
+                           "-ffp-contract=off", "-pthread", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "cmpt-eigenex_amd", "include"),
                            "-I", os.path.join(ROOT, "cmpt-eigenex_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "spin_momentum_sanitize.cpp"),
                            "-o", exe])
-    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    out = subprocess.run([exe, "32"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert out.returncode == 0, (out.stdout.decode()[-1500:], out.stderr.decode()[-2000:])
     assert b"SPIN MOMENTUM OK" in out.stdout
 
