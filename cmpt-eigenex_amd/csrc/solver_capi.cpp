@@ -848,38 +848,123 @@ EIGENEX_LANCZOS_FAMILY(eigenex_zlanczos_solver_, std::complex<double>)
 EIGENEX_ARNOLDI_FAMILY(eigenex_arnoldi_solver_, double)
 EIGENEX_ARNOLDI_FAMILY(eigenex_zarnoldi_solver_, std::complex<double>)
 
-// ---- SpinDynamicsSolver (spin_dynamics.hpp).  The model crosses as the arrays of eigenex_spin_upload; n_up = -1: the full space.
-struct SpinDynamicsBox {
+// ---- The spin front-ends (spin_dynamics.hpp, spin_evolution.hpp, spin_time_correlation.hpp, spin_entanglement.hpp).  What their
+// entry points share is written once here, over the box type; the families below name it per prefix.
+}  // extern "C"
+
+namespace {
+
+// a solver that takes a model: the context it borrowed, the model and sector it was given (n_up = -1: the full space)
+template <class Solver>
+struct SpinBox {
   std::shared_ptr<device::Context> ctx;
   SpinHalfModel model;
   int n_up = -1;
-  DenseVector<double> state;
-  SpinDynamicsSolver es;
+  Solver es;
 };
-void* eigenex_spin_dynamics_solver_create(void) {
+struct SpinDynamicsBox : SpinBox<SpinDynamicsSolver> {
+  DenseVector<double> state;  // for static_structure_factor_z
+};
+struct SpinEvolutionBox : SpinBox<SpinTimeEvolutionSolver> {
+  std::vector<double> out;  // the last vector-valued result, until the next one
+};
+struct SpinTimeCorrelationBox : SpinBox<SpinTimeCorrelationSolver> {
+  std::vector<std::complex<double>> out;  // the last values()
+};
+struct SpinEntanglementBox : Box<SpinEntanglementSolver> {
+  DenseVector<double> state;
+  DenseVector<std::complex<double>> stateZ;
+};
+
+// the model from the arrays of eigenex_spin_upload
+SpinHalfModel spin_model_from_arrays(int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz, const double* jxy,
+                                     const double* hz_or_null, const double* hx_or_null) {
+  SpinHalfModel model(n_sites);
+  for (int k = 0; k < n_bonds; ++k) model.addBond(site_i[k], site_j[k], jz[k], jxy[k]);
+  for (int i = 0; i < n_sites; ++i) {
+    if (hz_or_null) model.setFieldZ(i, hz_or_null[i]);
+    if (hx_or_null) model.setFieldX(i, hx_or_null[i]);
+  }
+  return model;
+}
+std::vector<std::complex<double>> complex_coefficients(const double* c, int n) {
+  std::vector<std::complex<double>> out((size_t)(n > 0 ? n : 0));
+  for (size_t i = 0; i < out.size(); ++i) out[i] = std::complex<double>(c[2 * i], c[2 * i + 1]);
+  return out;
+}
+
+template <class B>
+void* sp_create() {
   try {
-    return new SpinDynamicsBox();
+    return new B();
   } catch (const std::exception& e) {
     g_serr = e.what();
     return nullptr;
   }
 }
-void eigenex_spin_dynamics_solver_destroy(void* p) { delete static_cast<SpinDynamicsBox*>(p); }
-int eigenex_spin_dynamics_solver_set_model(void* p, eigenex_context_t ctx, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j,
-                                           const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null, int n_up) {
+template <class B>
+const char* sp_log_line(void* p, int64_t i) {
+  auto& log = static_cast<B*>(p)->es.log();
+  return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
+}
+template <class B>
+int sp_set_model(void* p, eigenex_context_t ctx, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz,
+                 const double* jxy, const double* hz_or_null, const double* hx_or_null, int n_up) {
   return guard([&] {
-    auto* b = static_cast<SpinDynamicsBox*>(p);
+    auto* b = static_cast<B*>(p);
     b->ctx = device::Context::borrow(ctx);
-    b->model = SpinHalfModel(n_sites);
-    for (int k = 0; k < n_bonds; ++k) b->model.addBond(site_i[k], site_j[k], jz[k], jxy[k]);
-    for (int i = 0; i < n_sites; ++i) {
-      if (hz_or_null) b->model.setFieldZ(i, hz_or_null[i]);
-      if (hx_or_null) b->model.setFieldX(i, hx_or_null[i]);
-    }
+    b->model = spin_model_from_arrays(n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null);
     b->n_up = n_up;
     b->es.setModel(b->ctx, b->model, n_up);
   });
 }
+// v: n entries, interleaved (re, im) if is_complex, else real
+template <class B>
+int sp_set_state(void* p, const double* v, int64_t n, int is_complex) {
+  return guard([&] {
+    auto& es = static_cast<B*>(p)->es;
+    if (is_complex)
+      es.setState(make_vector<std::complex<double>>(v, n));
+    else
+      es.setState(make_vector<double>(v, n));
+  });
+}
+template <class B>
+int sp_evolve(void* p, double dt, int64_t* substeps) {
+  return guard([&] {
+    const Index s = static_cast<B*>(p)->es.evolve(dt);
+    if (substeps) *substeps = (int64_t)s;
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+#define EIGENEX_SPIN_COMMON(PFX, BOX)                       \
+  void* PFX##create(void) { return sp_create<BOX>(); }      \
+  void PFX##destroy(void* p) { delete static_cast<BOX*>(p); } \
+  const char* PFX##log_line(void* p, int64_t i) { return sp_log_line<BOX>(p, i); }
+
+// ... of a solver that takes a model, which crosses as the arrays of eigenex_spin_upload; n_up = -1: the full space
+#define EIGENEX_SPIN_MODEL_COMMON(PFX, BOX)                                                                                              \
+  EIGENEX_SPIN_COMMON(PFX, BOX)                                                                                                          \
+  int PFX##set_model(void* p, eigenex_context_t ctx, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j, const double* jz, \
+                     const double* jxy, const double* hz_or_null, const double* hx_or_null, int n_up) {                                 \
+    return sp_set_model<BOX>(p, ctx, n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, hx_or_null, n_up);                           \
+  }
+
+// ... of a solver that evolves a state; vectors are interleaved (re, im) if is_complex, else real
+#define EIGENEX_SPIN_EVOLVING_FAMILY(PFX, BOX)                                                                                           \
+  EIGENEX_SPIN_MODEL_COMMON(PFX, BOX)                                                                                                    \
+  int PFX##set_state(void* p, const double* v, int64_t n, int is_complex) { return sp_set_state<BOX>(p, v, n, is_complex); }            \
+  int PFX##set_product_state(void* p, uint32_t bits) { return guard([&] { static_cast<BOX*>(p)->es.setProductState(bits); }); }         \
+  int PFX##set_krylov_dimension(void* p, int64_t m) { return guard([&] { static_cast<BOX*>(p)->es.setKrylovDimension((Index)m); }); }   \
+  int PFX##set_tolerance(void* p, double tol) { return guard([&] { static_cast<BOX*>(p)->es.setTolerance(tol); }); }                    \
+  int PFX##evolve(void* p, double dt, int64_t* substeps) { return sp_evolve<BOX>(p, dt, substeps); }
+
+// ---- SpinDynamicsSolver
+EIGENEX_SPIN_MODEL_COMMON(eigenex_spin_dynamics_solver_, SpinDynamicsBox)
 int eigenex_spin_dynamics_solver_set_state(void* p, const double* v, int64_t n) {
   return guard([&] {
     auto* b = static_cast<SpinDynamicsBox*>(p);
@@ -887,15 +972,13 @@ int eigenex_spin_dynamics_solver_set_state(void* p, const double* v, int64_t n) 
     b->es.setState(b->state);
   });
 }
+// a complex state (n entries, interleaved) and complex coefficients (two arrays): the run becomes a complex one
+int eigenex_spin_dynamics_solver_set_state_z(void* p, const double* v, int64_t n) { return sp_set_state<SpinDynamicsBox>(p, v, n, 1); }
 int eigenex_spin_dynamics_solver_set_state_energy(void* p, double E0) {
   return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.setStateEnergy(E0); });
 }
 int eigenex_spin_dynamics_solver_set_site_operator(void* p, int kind, const double* coef, int n) {
   return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.setSiteOperator(kind, std::vector<double>(coef, coef + (n > 0 ? n : 0))); });
-}
-// a complex state (n entries, interleaved) and complex coefficients (two arrays): the run becomes a complex one
-int eigenex_spin_dynamics_solver_set_state_z(void* p, const double* v, int64_t n) {
-  return guard([&] { static_cast<SpinDynamicsBox*>(p)->es.setState(make_vector<std::complex<double>>(v, n)); });
 }
 int eigenex_spin_dynamics_solver_set_site_operator_z(void* p, int kind, const double* coef_re, const double* coef_im, int n) {
   return guard([&] {
@@ -954,65 +1037,9 @@ int eigenex_spin_dynamics_solver_static_structure_factor_z(void* p, double q, do
     *out = sc.structureFactorZ(q);
   });
 }
-const char* eigenex_spin_dynamics_solver_log_line(void* p, int64_t i) {
-  auto& log = static_cast<SpinDynamicsBox*>(p)->es.log();
-  return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
-}
 
-// ---- SpinTimeEvolutionSolver (spin_evolution.hpp).  The model crosses as for SpinDynamicsSolver; vectors are interleaved (re, im).
-struct SpinEvolutionBox {
-  std::shared_ptr<device::Context> ctx;
-  SpinTimeEvolutionSolver es;
-  std::vector<double> out;  // the last vector-valued result, until the next one
-};
-void* eigenex_spin_evolution_solver_create(void) {
-  try {
-    return new SpinEvolutionBox();
-  } catch (const std::exception& e) {
-    g_serr = e.what();
-    return nullptr;
-  }
-}
-void eigenex_spin_evolution_solver_destroy(void* p) { delete static_cast<SpinEvolutionBox*>(p); }
-int eigenex_spin_evolution_solver_set_model(void* p, eigenex_context_t ctx, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j,
-                                            const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null, int n_up) {
-  return guard([&] {
-    auto* b = static_cast<SpinEvolutionBox*>(p);
-    b->ctx = device::Context::borrow(ctx);
-    SpinHalfModel model(n_sites);
-    for (int k = 0; k < n_bonds; ++k) model.addBond(site_i[k], site_j[k], jz[k], jxy[k]);
-    for (int i = 0; i < n_sites; ++i) {
-      if (hz_or_null) model.setFieldZ(i, hz_or_null[i]);
-      if (hx_or_null) model.setFieldX(i, hx_or_null[i]);
-    }
-    b->es.setModel(b->ctx, model, n_up);
-  });
-}
-// v: n entries, interleaved (re, im) if is_complex, else real
-int eigenex_spin_evolution_solver_set_state(void* p, const double* v, int64_t n, int is_complex) {
-  return guard([&] {
-    auto& es = static_cast<SpinEvolutionBox*>(p)->es;
-    if (is_complex)
-      es.setState(make_vector<std::complex<double>>(v, n));
-    else
-      es.setState(make_vector<double>(v, n));
-  });
-}
-int eigenex_spin_evolution_solver_set_product_state(void* p, uint32_t bits) {
-  return guard([&] { static_cast<SpinEvolutionBox*>(p)->es.setProductState(bits); });
-}
-int eigenex_spin_evolution_solver_set_krylov_dimension(void* p, int64_t m) {
-  return guard([&] { static_cast<SpinEvolutionBox*>(p)->es.setKrylovDimension((Index)m); });
-}
-int eigenex_spin_evolution_solver_set_tolerance(void* p, double tol) {
-  return guard([&] { static_cast<SpinEvolutionBox*>(p)->es.setTolerance(tol); });
-}
-int eigenex_spin_evolution_solver_evolve(void* p, double dt, int64_t* substeps) {
-  return guard([&] {
-    const Index s = static_cast<SpinEvolutionBox*>(p)->es.evolve(dt);
-    if (substeps) *substeps = (int64_t)s;
-  });
-}
+// ---- SpinTimeEvolutionSolver
+EIGENEX_SPIN_EVOLVING_FAMILY(eigenex_spin_evolution_solver_, SpinEvolutionBox)
 // scalars[5] = (time, errorBound, totalErrorBound, initialNorm, operatorApplications); counts[4] = (log lines, info, sites, rows of out)
 int eigenex_spin_evolution_solver_status(void* p, double* scalars, int64_t* counts) {
   return guard([&] {
@@ -1075,59 +1102,9 @@ int eigenex_spin_evolution_solver_fetch(void* p, double* out) {
     std::vector<double>().swap(b->out);
   });
 }
-const char* eigenex_spin_evolution_solver_log_line(void* p, int64_t i) {
-  auto& log = static_cast<SpinEvolutionBox*>(p)->es.log();
-  return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
-}
 
-// ---- SpinTimeCorrelationSolver (spin_time_correlation.hpp).  The model crosses as for SpinDynamicsSolver; vectors and complex
-// coefficients are interleaved (re, im).
-struct SpinTimeCorrelationBox {
-  std::shared_ptr<device::Context> ctx;
-  SpinTimeCorrelationSolver es;
-  std::vector<std::complex<double>> out;  // the last values()
-};
-static std::vector<std::complex<double>> complex_coefficients(const double* c, int n) {
-  std::vector<std::complex<double>> out((size_t)(n > 0 ? n : 0));
-  for (size_t i = 0; i < out.size(); ++i) out[i] = std::complex<double>(c[2 * i], c[2 * i + 1]);
-  return out;
-}
-void* eigenex_spin_time_correlation_solver_create(void) {
-  try {
-    return new SpinTimeCorrelationBox();
-  } catch (const std::exception& e) {
-    g_serr = e.what();
-    return nullptr;
-  }
-}
-void eigenex_spin_time_correlation_solver_destroy(void* p) { delete static_cast<SpinTimeCorrelationBox*>(p); }
-int eigenex_spin_time_correlation_solver_set_model(void* p, eigenex_context_t ctx, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j,
-                                                   const double* jz, const double* jxy, const double* hz_or_null, const double* hx_or_null, int n_up) {
-  return guard([&] {
-    auto* b = static_cast<SpinTimeCorrelationBox*>(p);
-    b->ctx = device::Context::borrow(ctx);
-    SpinHalfModel model(n_sites);
-    for (int k = 0; k < n_bonds; ++k) model.addBond(site_i[k], site_j[k], jz[k], jxy[k]);
-    for (int i = 0; i < n_sites; ++i) {
-      if (hz_or_null) model.setFieldZ(i, hz_or_null[i]);
-      if (hx_or_null) model.setFieldX(i, hx_or_null[i]);
-    }
-    b->es.setModel(b->ctx, model, n_up);
-  });
-}
-// v: n entries, interleaved (re, im) if is_complex, else real
-int eigenex_spin_time_correlation_solver_set_state(void* p, const double* v, int64_t n, int is_complex) {
-  return guard([&] {
-    auto& es = static_cast<SpinTimeCorrelationBox*>(p)->es;
-    if (is_complex)
-      es.setState(make_vector<std::complex<double>>(v, n));
-    else
-      es.setState(make_vector<double>(v, n));
-  });
-}
-int eigenex_spin_time_correlation_solver_set_product_state(void* p, uint32_t bits) {
-  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setProductState(bits); });
-}
+// ---- SpinTimeCorrelationSolver.  Complex coefficients are interleaved (re, im).
+EIGENEX_SPIN_EVOLVING_FAMILY(eigenex_spin_time_correlation_solver_, SpinTimeCorrelationBox)
 int eigenex_spin_time_correlation_solver_set_eigenstate(void* p, double E0) {
   return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setEigenstate(E0); });
 }
@@ -1146,18 +1123,6 @@ int eigenex_spin_time_correlation_solver_set_measured_sites(void* p) {
 }
 int eigenex_spin_time_correlation_solver_set_momentum_z(void* p, double q) {
   return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setMomentumZ(q); });
-}
-int eigenex_spin_time_correlation_solver_set_krylov_dimension(void* p, int64_t m) {
-  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setKrylovDimension((Index)m); });
-}
-int eigenex_spin_time_correlation_solver_set_tolerance(void* p, double tol) {
-  return guard([&] { static_cast<SpinTimeCorrelationBox*>(p)->es.setTolerance(tol); });
-}
-int eigenex_spin_time_correlation_solver_evolve(void* p, double dt, int64_t* substeps) {
-  return guard([&] {
-    const Index s = static_cast<SpinTimeCorrelationBox*>(p)->es.evolve(dt);
-    if (substeps) *substeps = (int64_t)s;
-  });
 }
 // forms values() and returns their number; eigenex_spin_time_correlation_solver_fetch copies them out, interleaved
 int eigenex_spin_time_correlation_solver_values(void* p, int64_t* count) {
@@ -1191,28 +1156,9 @@ int eigenex_spin_time_correlation_solver_operator_bounds(void* p, int64_t n, dou
     out[0] = es.errorBound((size_t)n), out[1] = es.operatorNormBound((size_t)n);
   });
 }
-const char* eigenex_spin_time_correlation_solver_log_line(void* p, int64_t i) {
-  auto& log = static_cast<SpinTimeCorrelationBox*>(p)->es.log();
-  return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
-}
 
-// ---- SpinEntanglementSolver (spin_entanglement.hpp).  The operator crosses as a handle of eigenex_spin_upload / eigenex_spin_sector_upload.
-struct SpinEntanglementBox {
-  std::shared_ptr<device::Context> ctx;
-  std::shared_ptr<device::CsrOperator> op;
-  DenseVector<double> state;
-  DenseVector<std::complex<double>> stateZ;
-  SpinEntanglementSolver es;
-};
-void* eigenex_spin_entanglement_solver_create(void) {
-  try {
-    return new SpinEntanglementBox();
-  } catch (const std::exception& e) {
-    g_serr = e.what();
-    return nullptr;
-  }
-}
-void eigenex_spin_entanglement_solver_destroy(void* p) { delete static_cast<SpinEntanglementBox*>(p); }
+// ---- SpinEntanglementSolver.  The operator crosses as a handle of eigenex_spin_upload / eigenex_spin_sector_upload.
+EIGENEX_SPIN_COMMON(eigenex_spin_entanglement_solver_, SpinEntanglementBox)
 int eigenex_spin_entanglement_solver_set_device_operator(void* p, eigenex_context_t ctx, eigenex_csr_t csr) {
   return guard([&] {
     auto* b = static_cast<SpinEntanglementBox*>(p);
@@ -1284,10 +1230,6 @@ int eigenex_spin_entanglement_solver_renyi(void* p, double alpha, double* out) {
 }
 int eigenex_spin_entanglement_solver_schmidt_rank(void* p, double tol, int64_t* out) {
   return guard([&] { *out = (int64_t)static_cast<SpinEntanglementBox*>(p)->es.schmidtRank(tol); });
-}
-const char* eigenex_spin_entanglement_solver_log_line(void* p, int64_t i) {
-  auto& log = static_cast<SpinEntanglementBox*>(p)->es.log();
-  return i >= 0 && i < (int64_t)log.size() ? log[(size_t)i].c_str() : "";
 }
 
 }  // extern "C"

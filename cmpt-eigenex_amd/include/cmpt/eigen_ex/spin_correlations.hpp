@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "lanczos.hpp"
+#include "spin_frontend.hpp"
 #include "spin_operator.hpp"
 
 namespace cmpt {
@@ -30,8 +31,8 @@ class SpinCorrelationSolver {
   using Index = EigenEx::Index;
   using VectorType = DenseVector<double>;
 
-  static std::string headERROR() { return std::string("ERROR     "); }
-  static std::string headINFO() { return std::string("INFO      "); }
+  static std::string headERROR() { return detail::CallLog::headERROR(); }
+  static std::string headINFO() { return detail::CallLog::headINFO(); }
 
   SpinCorrelationSolver& setDeviceOperator(const std::shared_ptr<device::CsrOperator>& op) {
     op_ = op;
@@ -48,9 +49,7 @@ class SpinCorrelationSolver {
   double normSquared() const { return norm2_; }
 
   Index compute() {
-    log_.clear();
-    log_.push_back(headINFO() + "SpinCorrelationSolver::compute(...) was called");
-    info_ = Success;
+    log_.begin("SpinCorrelationSolver", "compute");
     sites_ = 0, nUp_ = -1, norm2_ = 0.0;
     sz_.clear(), sx_.clear(), zz_.clear(), xy_.clear();
     if (!op_ || height_ <= 0 || eigenex_spin_geometry(op_->handle(), &sites_, &nUp_) != 0) {
@@ -60,9 +59,8 @@ class SpinCorrelationSolver {
     if (static_cast<Index>(state_.size()) != height_) return invalid_("invalid input: the state must have one entry per row of the operator");
     const std::size_t L = static_cast<std::size_t>(sites_);
     std::vector<std::uint32_t> diag, flip;
-    for (std::size_t i = 0; i < L; ++i) diag.push_back(std::uint32_t(1) << i);
-    for (std::size_t i = 0; i < L; ++i)
-      for (std::size_t j = i + 1; j < L; ++j) diag.push_back((std::uint32_t(1) << i) | (std::uint32_t(1) << j));
+    detail::appendSiteMasks(L, diag);
+    detail::appendPairMasks(L, diag);
     flip.assign(diag.begin() + static_cast<std::ptrdiff_t>(L), diag.end());
     if (nUp_ < 0) flip.insert(flip.end(), diag.begin(), diag.begin() + static_cast<std::ptrdiff_t>(L));  // <Sx_i>: the full space only
     if (!dev_.alive() || devOp_ != op_.get()) {
@@ -77,19 +75,13 @@ class SpinCorrelationSolver {
     if (!(norm2_ > 0.0) || !std::isfinite(norm2_)) return invalid_("invalid input: the state is zero (or not finite)");
     const std::size_t npairs = L * (L - 1) / 2;
     sz_.assign(L, 0.0), sx_.assign(L, 0.0);
-    zz_.assign(L * L, 0.0), xy_.assign(L * L, 0.0);
     for (std::size_t i = 0; i < L; ++i) {
       sz_[i] = d[i] / (2.0 * norm2_);
       if (nUp_ < 0) sx_[i] = f[npairs + i] / (2.0 * norm2_);
-      zz_[i * L + i] = 0.25, xy_[i * L + i] = 0.5;
     }
-    std::size_t k = 0;
-    for (std::size_t i = 0; i < L; ++i)
-      for (std::size_t j = i + 1; j < L; ++j, ++k) {
-        zz_[i * L + j] = zz_[j * L + i] = d[L + k] / (4.0 * norm2_);
-        xy_[i * L + j] = xy_[j * L + i] = f[k] / (2.0 * norm2_);
-      }
-    log_.push_back(headINFO() + "sites: " + std::to_string(sites_) + (nUp_ < 0 ? std::string(", full space") : ", sites up: " + std::to_string(nUp_)) +
+    zz_ = detail::pairMatrix(d.data() + L, L, 4.0 * norm2_, 0.25);
+    xy_ = detail::pairMatrix(f.data(), L, 2.0 * norm2_, 0.5);
+    log_.note("sites: " + std::to_string(sites_) + (nUp_ < 0 ? std::string(", full space") : ", sites up: " + std::to_string(nUp_)) +
                    ", terms measured: " + std::to_string(diag.size() + flip.size()));
     return 0;
   }
@@ -112,15 +104,13 @@ class SpinCorrelationSolver {
       for (int j = 0; j < sites_; ++j) s += std::cos(q * static_cast<double>(i - j)) * szsz(i, j);
     return sites_ > 0 ? s / static_cast<double>(sites_) : 0.0;
   }
-  ComputationInfo info() const { return info_; }
-  const std::vector<std::string>& log() const { return log_; }
+  ComputationInfo info() const { return log_.info(); }
+  const std::vector<std::string>& log() const { return log_.log(); }
 
  private:
   Index invalid_(const std::string& what) {
-    log_.push_back(headERROR() + what);
-    info_ = InvalidInput;
     sz_.clear(), sx_.clear(), zz_.clear(), xy_.clear();
-    return 0;
+    return log_.invalid(what);
   }
   std::size_t site_(int i) const {
     if (i < 0 || i >= sites_ || sz_.empty()) throw LanczosException("SpinCorrelationSolver: no result for this site (compute() first; sites are 0..sites()-1)");
@@ -135,8 +125,7 @@ class SpinCorrelationSolver {
   int sites_ = 0, nUp_ = -1;
   double norm2_ = 0.0;
   std::vector<double> sz_, sx_, zz_, xy_;
-  ComputationInfo info_ = Success;
-  std::vector<std::string> log_;
+  detail::CallLog log_;
 };
 
 // Diagonal correlations of a state of a momentum-sector operator (device::spinHalfMomentumOperator or
@@ -152,8 +141,8 @@ class SpinMomentumCorrelationSolver {
  public:
   using Index = EigenEx::Index;
 
-  static std::string headERROR() { return std::string("ERROR     "); }
-  static std::string headINFO() { return std::string("INFO      "); }
+  static std::string headERROR() { return detail::CallLog::headERROR(); }
+  static std::string headINFO() { return detail::CallLog::headINFO(); }
 
   SpinMomentumCorrelationSolver& setDeviceOperator(const std::shared_ptr<device::CsrOperator>& op) {
     op_ = op;
@@ -176,16 +165,13 @@ class SpinMomentumCorrelationSolver {
   double normSquared() const { return norm2_; }
 
   Index compute() {
-    log_.clear();
-    log_.push_back(headINFO() + "SpinMomentumCorrelationSolver::compute(...) was called");
-    info_ = Success;
+    log_.begin("SpinMomentumCorrelationSolver", "compute");
     sz_.clear(), zz_.clear();
     if (!prepare_()) return 0;
     const std::size_t L = static_cast<std::size_t>(sites_);
     std::vector<std::uint64_t> masks;
-    for (std::size_t i = 0; i < L; ++i) masks.push_back(std::uint64_t(1) << i);
-    for (std::size_t i = 0; i < L; ++i)
-      for (std::size_t j = i + 1; j < L; ++j) masks.push_back((std::uint64_t(1) << i) | (std::uint64_t(1) << j));
+    detail::appendSiteMasks(L, masks);
+    detail::appendPairMasks(L, masks);
     std::vector<double> d(masks.size(), 0.0);
     // at most 1024 masks per call: 48 sites have 1176
     for (std::size_t first = 0; first < masks.size(); first += 1024) {
@@ -195,12 +181,10 @@ class SpinMomentumCorrelationSolver {
     }
     if (!(norm2_ > 0.0) || !std::isfinite(norm2_)) return invalid_("invalid input: the state is zero (or not finite)");
     const double n = static_cast<double>(sites_ / cell_) * norm2_;
-    sz_.assign(L, 0.0), zz_.assign(L * L, 0.0);
-    for (std::size_t i = 0; i < L; ++i) sz_[i] = d[i] / (2.0 * n), zz_[i * L + i] = 0.25;
-    std::size_t k = 0;
-    for (std::size_t i = 0; i < L; ++i)
-      for (std::size_t j = i + 1; j < L; ++j, ++k) zz_[i * L + j] = zz_[j * L + i] = d[L + k] / (4.0 * n);
-    log_.push_back(headINFO() + "sites: " + std::to_string(sites_) + ", sites up: " + std::to_string(nUp_) + ", momentum: " + std::to_string(momentum_) +
+    sz_.assign(L, 0.0);
+    for (std::size_t i = 0; i < L; ++i) sz_[i] = d[i] / (2.0 * n);
+    zz_ = detail::pairMatrix(d.data() + L, L, 4.0 * n, 0.25);
+    log_.note("sites: " + std::to_string(sites_) + ", sites up: " + std::to_string(nUp_) + ", momentum: " + std::to_string(momentum_) +
                    ", terms measured: " + std::to_string(masks.size()));
     return 0;
   }
@@ -222,14 +206,14 @@ class SpinMomentumCorrelationSolver {
   }
   // <prod_{i in mask} sigma^z_i> of the state, one further measurement (bit i of mask = site i); throws on an invalid mask or state
   double stringCorrelator(std::uint64_t mask) {
-    info_ = Success;
-    if (!prepare_()) throw LanczosException("SpinMomentumCorrelationSolver::stringCorrelator: " + log_.back());
+    log_.succeed();
+    if (!prepare_()) throw LanczosException("SpinMomentumCorrelationSolver::stringCorrelator: " + log_.log().back());
     double d = 0.0;
     device::check(eigenex_spin_momentum_measure(dev_.handle(), EIGENEX_VEC_COL(0), 1, &mask, &d, &norm2_), "eigenex_spin_momentum_measure");
     return d / (static_cast<double>(sites_ / cell_) * norm2_);
   }
-  ComputationInfo info() const { return info_; }
-  const std::vector<std::string>& log() const { return log_; }
+  ComputationInfo info() const { return log_.info(); }
+  const std::vector<std::string>& log() const { return log_.log(); }
 
  private:
   // the geometry of the handle and the state on the device; false (and info() = InvalidInput) if either is unusable
@@ -259,10 +243,8 @@ class SpinMomentumCorrelationSolver {
     return true;
   }
   Index invalid_(const std::string& what) {
-    log_.push_back(headERROR() + what);
-    info_ = InvalidInput;
     sz_.clear(), zz_.clear();
-    return 0;
+    return log_.invalid(what);
   }
 
   std::shared_ptr<device::CsrOperator> op_;
@@ -275,8 +257,7 @@ class SpinMomentumCorrelationSolver {
   int sites_ = 0, nUp_ = 0, cell_ = 1, momentum_ = 0;
   double norm2_ = 0.0;
   std::vector<double> sz_, zz_;
-  ComputationInfo info_ = Success;
-  std::vector<std::string> log_;
+  detail::CallLog log_;
 };
 
 }  // namespace EigenEx

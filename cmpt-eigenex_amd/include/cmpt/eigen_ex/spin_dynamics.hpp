@@ -48,6 +48,7 @@
 
 #include "lanczos.hpp"
 #include "small_eigen.hpp"
+#include "spin_frontend.hpp"
 #include "spin_operator.hpp"
 
 namespace cmpt {
@@ -60,14 +61,14 @@ class SpinDynamicsSolver {
   using Complex = std::complex<double>;
   using ComplexVectorType = DenseVector<Complex>;
 
-  static std::string headERROR() { return std::string("ERROR     "); }
-  static std::string headINFO() { return std::string("INFO      "); }
+  static std::string headERROR() { return detail::CallLog::headERROR(); }
+  static std::string headINFO() { return detail::CallLog::headINFO(); }
 
   // nUp = -1: the full space (up to 30 sites); else the sector of nUp sites up (up to 32 sites, no transverse field)
   SpinDynamicsSolver& setModel(const std::shared_ptr<device::Context>& ctx, const SpinHalfModel& model, int nUp = -1) {
     ctx_ = ctx, model_ = model, nUp_ = nUp, haveModel_ = true;
     srcDev_.release(), dstDev_.release();  // the states go before their operators
-    srcOp_.reset(), dstOp_.reset();
+    ops_.reset();
     return *this;
   }
   // a host vector over the source rows, e.g. a column of a solver's eigenvectors(); it need not be normalised
@@ -121,7 +122,7 @@ class SpinDynamicsSolver {
     std::vector<double> c(static_cast<std::size_t>(L), 0.0);
     if (!prepare_(EIGENEX_SPIN_SITE_Z, c, nullptr, false)) return 0;
     const double scale = 1.0 / std::sqrt(static_cast<double>(L));
-    for (int part = 0; part < 2 && info_ == Success; ++part) {
+    for (int part = 0; part < 2 && info() == Success; ++part) {
       for (int i = 0; i < L; ++i) c[static_cast<std::size_t>(i)] = scale * (part == 0 ? std::cos(q * i) : std::sin(q * i));
       run_(EIGENEX_SPIN_SITE_Z, c, nullptr, false);
     }
@@ -167,25 +168,21 @@ class SpinDynamicsSolver {
   const std::vector<double>& lanczosBeta() const { return beta_; }
   int sites() const { return haveModel_ ? model_.sites() : 0; }
   int sitesUp() const { return nUp_; }
-  ComputationInfo info() const { return info_; }
-  const std::vector<std::string>& log() const { return log_; }
+  ComputationInfo info() const { return log_.info(); }
+  const std::vector<std::string>& log() const { return log_.log(); }
 
  private:
   void begin_(const char* who) {
-    log_.clear();
-    log_.push_back(headINFO() + "SpinDynamicsSolver::" + who + "(...) was called");
-    info_ = Success;
+    log_.begin("SpinDynamicsSolver", who);
     poles_.clear(), weights_.clear(), alpha_.clear(), beta_.clear();
     total_ = 0.0, E0_ = 0.0, vv_ = 0.0;
   }
   Index invalid_(const std::string& what) {
-    log_.push_back(headERROR() + what);
-    info_ = InvalidInput;
     poles_.clear(), weights_.clear();
     total_ = 0.0;
-    return 0;
+    return log_.invalid(what);
   }
-  static int dstUp_(int nUp, int kind) { return nUp < 0 || kind == EIGENEX_SPIN_SITE_Z ? nUp : (kind == EIGENEX_SPIN_SITE_PLUS ? nUp + 1 : nUp - 1); }
+  Index failed_(const std::string& what) { return log_.failed(what); }
   std::shared_ptr<device::CsrOperator> makeOperator_(int nUp) const {
     if (complexRun_) return device::spinHalfComplexOperator(ctx_, model_, nUp);
     return nUp < 0 ? device::spinHalfOperator(ctx_, model_) : device::spinHalfSectorOperator(ctx_, model_, nUp);
@@ -198,33 +195,27 @@ class SpinDynamicsSolver {
     const int L = model_.sites();
     if (kind != EIGENEX_SPIN_SITE_Z && kind != EIGENEX_SPIN_SITE_PLUS && kind != EIGENEX_SPIN_SITE_MINUS)
       return invalid_("invalid input: no site operator (setSiteOperator: EIGENEX_SPIN_SITE_Z, _PLUS or _MINUS)"), false;
-    if (static_cast<int>(coef.size()) != L) return invalid_("invalid input: the site operator needs one coefficient per site"), false;
-    for (double c : coef)
-      if (!std::isfinite(c)) return invalid_("invalid input: a coefficient of the site operator is not finite"), false;
-    if (coefIm) {
-      if (coefIm->size() != coef.size()) return invalid_("invalid input: the site operator needs one coefficient per site"), false;
-      for (double c : *coefIm)
-        if (!std::isfinite(c)) return invalid_("invalid input: a coefficient of the site operator is not finite"), false;
-    }
+    const std::string why = detail::checkCoefficients(coef, coefIm, L, "the site operator");
+    if (!why.empty()) return invalid_(why), false;
     if (steps_ < 1) return invalid_("invalid input: setLanczosSteps needs at least one step"), false;
     if (!z && stateComplex_)  // only computeStructureFactorZ asks for a real run whatever was set: its cos + sin sum holds for real states
       return invalid_("invalid input: computeStructureFactorZ needs a real state; a complex one takes computeStructureFactorZSingleRun"), false;
-    if (nUp_ >= 0 && (dstUp_(nUp_, kind) < 0 || dstUp_(nUp_, kind) > L))
+    if (nUp_ >= 0 && (detail::dstUp(nUp_, kind) < 0 || detail::dstUp(nUp_, kind) > L))
       return invalid_("invalid input: the site operator leaves the sectors of the model (S+ of the sector with every site up, S- of the one with none)"), false;
     if (z != complexRun_) {  // the other scalar type: its own operators and states
       srcDev_.release(), dstDev_.release();
-      srcOp_.reset(), dstOp_.reset();
+      ops_.reset();
       complexRun_ = z;
     }
     try {
-      if (!srcOp_) srcOp_ = makeOperator_(nUp_);
+      if (!ops_.src) ops_.src = makeOperator_(nUp_);
     } catch (const LanczosException& e) {
       return invalid_(std::string("invalid input: the model has no such operator: ") + e.what()), false;
     }
-    const Index n = static_cast<Index>(srcOp_->rows());
+    const Index n = static_cast<Index>(ops_.src->rows());
     if ((stateComplex_ ? stateZ_.size() : state_.size()) != n)
       return invalid_("invalid input: the state must have one entry per row of the model's space or sector (setState)"), false;
-    if (!srcDev_.alive()) srcDev_.create(ctx_, srcOp_, n, 1, 0, z);
+    if (!srcDev_.alive()) srcDev_.create(ctx_, ops_.src, n, 1, 0, z);
     if (!z) {
       srcDev_.upload(EIGENEX_VEC_COL(0), state_);
     } else if (stateComplex_) {
@@ -248,79 +239,47 @@ class SpinDynamicsSolver {
 
   // one continued fraction: |phi> = O|v> into the work vector of the destination state, m Lanczos steps, poles and weights appended
   void run_(int kind, const std::vector<double>& coef, const std::vector<double>* coefIm, bool z) {
-    const int up = dstUp_(nUp_, kind);
-    std::shared_ptr<device::CsrOperator> want = up == nUp_ ? srcOp_ : (dstOp_ && dstOp_ != srcOp_ && dstUpBuilt_ == up ? dstOp_ : makeOperator_(up));
-    if (want != dstOp_) {
-      dstDev_.release();  // the state goes before its operator
-      dstOp_ = want;
-    }
-    dstUpBuilt_ = up;
-    const Index n = static_cast<Index>(dstOp_->rows());
+    ops_.destination(nUp_, detail::dstUp(nUp_, kind), [this](int nUp) { return makeOperator_(nUp); }, [this] { dstDev_.release(); });
+    const Index n = static_cast<Index>(ops_.dst->rows());
     const Index m = std::min<Index>(steps_, n);
     const int cap = static_cast<int>(m + 1);
-    if (!dstDev_.alive() || dstDevOp_ != dstOp_.get() || dstDev_.capacity() < cap) {
-      dstDev_.create(ctx_, dstOp_, n, cap, 0, z);
-      dstDevOp_ = dstOp_.get();
+    if (!dstDev_.alive() || dstDevOp_ != ops_.dst.get() || dstDev_.capacity() < cap) {
+      dstDev_.create(ctx_, ops_.dst, n, cap, 0, z);
+      dstDevOp_ = ops_.dst.get();
     } else {
       device::check(eigenex_basis_clear(dstDev_.handle()), "eigenex_basis_clear");
     }
-    double norm2 = 0.0;
-    if (z)
-      device::check(eigenex_spin_site_apply_z(srcDev_.handle(), EIGENEX_VEC_COL(0), dstDev_.handle(), EIGENEX_VEC_W, kind, coef.data(),
-                                              coefIm ? coefIm->data() : nullptr, &norm2),
-                    "eigenex_spin_site_apply_z");
-    else
-      device::check(eigenex_spin_site_apply(srcDev_.handle(), EIGENEX_VEC_COL(0), dstDev_.handle(), EIGENEX_VEC_W, kind, coef.data(), &norm2),
-                    "eigenex_spin_site_apply");
-    if (!std::isfinite(norm2)) {
-      log_.push_back(headERROR() + "O|v> is not finite");
-      info_ = NumericalIssue;
-      return;
-    }
-    // |y_r| <= L eps sum_i |c_i| |x| is what the roundings of the application alone can leave of an exact zero (Z: half of it)
-    double csum = 0.0;
-    for (double c : coef) csum += std::fabs(c);
-    if (coefIm)
-      for (double c : *coefIm) csum += std::fabs(c);  // a complex coefficient: |Re| + |Im| bounds what each part of a row sums
-    const double noise = static_cast<double>(model_.sites()) * std::ldexp(1.0, -52) * csum * (kind == EIGENEX_SPIN_SITE_Z ? 0.5 : 1.0);
-    if (norm2 <= noise * noise * vv_) {
-      log_.push_back(headINFO() + (norm2 == 0.0 ? "O|v> = 0" : "O|v> vanishes within the rounding of its application") +
-                     ": this part of the response is identically zero");
-      return;
-    }
-    // the run starts from a unit vector, whatever the scale of the coefficients: its breakdown threshold is an absolute number
-    // (through v_, which the run overwrites with its first operator application: the scaling kernel is not an in-place one)
-    device::check(eigenex_scale(dstDev_.handle(), EIGENEX_VEC_V, EIGENEX_VEC_W, 1.0 / std::sqrt(norm2)), "eigenex_scale");
-    device::check(eigenex_vec_copy(dstDev_.handle(), EIGENEX_VEC_W, EIGENEX_VEC_V), "eigenex_vec_copy");
+    // the run starts from the unit vector O|v> / |O v| (V, which the scaling passed through, is overwritten by the run's first
+    // operator application)
+    const detail::SiteApplication phi =
+        detail::applySiteOperatorToUnit(srcDev_.handle(), EIGENEX_VEC_COL(0), dstDev_.handle(), z, kind, model_.sites(), coef, coefIm, vv_);
+    if (phi.outcome == detail::SiteApplication::NotFinite) return void(failed_("O|v> is not finite"));
+    if (phi.zero()) return log_.note(phi.zeroNote("O|v>", "this part of the response"));
+    const double norm2 = phi.norm2;
     device::check(eigenex_lanczos_enqueue(dstDev_.handle(), static_cast<int>(m)), "eigenex_lanczos_enqueue");
     eigenex_state_t st;
     alpha_.assign(static_cast<std::size_t>(m) + 4, 0.0), beta_.assign(static_cast<std::size_t>(m) + 4, 0.0);
     device::check(eigenex_lanczos_state(dstDev_.handle(), &st, alpha_.data(), beta_.data()), "eigenex_lanczos_state");
     const int k = std::min<int>(st.nalpha, static_cast<int>(m));  // a breakdown leaves fewer: the fraction ends there
     if (k < 1) {
-      log_.push_back(headERROR() + "the start vector O|v> failed the breakdown threshold of the Lanczos run");
-      info_ = NumericalIssue;
+      failed_("the start vector O|v> failed the breakdown threshold of the Lanczos run");
       alpha_.clear(), beta_.clear();
       return;
     }
     alpha_.resize(static_cast<std::size_t>(k)), beta_.resize(static_cast<std::size_t>(k - 1));
     std::vector<double> theta, S;
-    if (!small_eigen::tridiagonal(alpha_.data(), beta_.data(), k, theta, &S)) {
-      log_.push_back(headERROR() + "the tridiagonal eigenproblem did not converge");
-      info_ = NumericalIssue;
-      return;
-    }
+    if (!small_eigen::tridiagonal(alpha_.data(), beta_.data(), k, theta, &S)) return void(failed_("the tridiagonal eigenproblem did not converge"));
     for (int j = 0; j < k; ++j) {
       const double s0 = S[static_cast<std::size_t>(j) * static_cast<std::size_t>(k)];  // row 0 of column j
       found_.push_back(std::make_pair(theta[static_cast<std::size_t>(j)] - E0_, norm2 / vv_ * s0 * s0));
     }
     parts_ += norm2 / vv_;
-    log_.push_back(headINFO() + "lanczos steps: " + std::to_string(k) + (st.stopped ? " (breakdown: the fraction is complete)" : "") +
-                   ", <O^dagger O> of this part: " + std::to_string(norm2 / vv_));
+    log_.note("lanczos steps: " + std::to_string(k) + (st.stopped ? " (breakdown: the fraction is complete)" : "") +
+              ", <O^dagger O> of this part: " + std::to_string(norm2 / vv_));
   }
 
   void finish_() {
-    if (info_ == Success) {
+    if (info() == Success) {
       std::stable_sort(found_.begin(), found_.end(), [](const std::pair<double, double>& a, const std::pair<double, double>& b) { return a.first < b.first; });
       for (const auto& pw : found_) poles_.push_back(pw.first), weights_.push_back(pw.second);
       total_ = parts_;
@@ -332,7 +291,7 @@ class SpinDynamicsSolver {
   std::shared_ptr<device::Context> ctx_;
   SpinHalfModel model_;
   bool haveModel_ = false, haveE0_ = false;
-  int nUp_ = -1, kind_ = -1, dstUpBuilt_ = -2;
+  int nUp_ = -1, kind_ = -1;
   std::vector<double> coef_, coefIm_;
   VectorType state_;
   ComplexVectorType stateZ_;
@@ -340,7 +299,7 @@ class SpinDynamicsSolver {
   Index steps_ = 100;
   double E0set_ = 0.0;
 
-  std::shared_ptr<device::CsrOperator> srcOp_, dstOp_;
+  detail::SectorPair ops_;
   const device::CsrOperator* dstDevOp_ = nullptr;
   detail::KrylovDevice srcDev_, dstDev_;
 
@@ -348,8 +307,7 @@ class SpinDynamicsSolver {
   double parts_ = 0.0;
   std::vector<double> poles_, weights_, alpha_, beta_;
   double total_ = 0.0, E0_ = 0.0, vv_ = 0.0;
-  ComputationInfo info_ = Success;
-  std::vector<std::string> log_;
+  detail::CallLog log_;
 };
 
 }  // namespace EigenEx

@@ -30,6 +30,7 @@
 
 #include "lanczos.hpp"
 #include "small_eigen.hpp"
+#include "spin_frontend.hpp"
 #include "spin_operator.hpp"
 
 namespace cmpt {
@@ -122,8 +123,8 @@ class SpinEntanglementSolver {
   using Complex = std::complex<double>;
   using ComplexVectorType = DenseVector<Complex>;
 
-  static std::string headERROR() { return std::string("ERROR     "); }
-  static std::string headINFO() { return std::string("INFO      "); }
+  static std::string headERROR() { return detail::CallLog::headERROR(); }
+  static std::string headINFO() { return detail::CallLog::headINFO(); }
 
   SpinEntanglementSolver& setDeviceOperator(const std::shared_ptr<device::CsrOperator>& op) {
     op_ = op;
@@ -142,11 +143,8 @@ class SpinEntanglementSolver {
   bool stateIsComplex() const { return complex_; }
   // the sites of the subsystem; a site outside 0..31 or named twice makes compute() report invalid input
   SpinEntanglementSolver& setSubsystem(const std::vector<int>& sites) {
-    mask_ = 0, sitesValid_ = true;
-    for (int i : sites) {
-      if (i < 0 || i > 31 || ((mask_ >> i) & 1u)) sitesValid_ = false;
-      else mask_ |= std::uint32_t(1) << i;
-    }
+    sitesValid_ = true;
+    mask_ = detail::siteMask(sites, sitesValid_);
     return *this;
   }
   SpinEntanglementSolver& setSubsystemMask(std::uint32_t mask) {
@@ -160,9 +158,7 @@ class SpinEntanglementSolver {
   double normSquared() const { return r_.norm2; }
 
   Index compute() {
-    log_.clear();
-    log_.push_back(headINFO() + "SpinEntanglementSolver::compute(...) was called");
-    info_ = Success;
+    log_.begin("SpinEntanglementSolver", "compute");
     clear_();
     if (!op_ || height_ <= 0 || eigenex_spin_geometry(op_->handle(), &sites_, &nUp_) != 0) {
       sites_ = 0;
@@ -199,14 +195,12 @@ class SpinEntanglementSolver {
       case detail::EntanglementBlocks::ZeroState:
         return invalid_("invalid input: the state is zero (or not finite)");
       case detail::EntanglementBlocks::NoConvergence:
-        log_.push_back(headERROR() + "the eigen-solve of a block of the reduced density matrix did not converge");
-        info_ = NoConvergence;
-        return 0;
+        return log_.failed("the eigen-solve of a block of the reduced density matrix did not converge", NoConvergence);
       case detail::EntanglementBlocks::Ok:
         break;
     }
-    log_.push_back(headINFO() + "sites: " + std::to_string(sites_) + (nUp_ < 0 ? std::string(", full space") : ", sites up: " + std::to_string(nUp_)) +
-                   ", subsystem sites: " + std::to_string(__builtin_popcount(mask_)) + ", blocks: " + std::to_string(nBlocks) +
+    log_.note("sites: " + std::to_string(sites_) + (nUp_ < 0 ? std::string(", full space") : ", sites up: " + std::to_string(nUp_)) +
+                   ", subsystem sites: " + std::to_string(detail::popcount(mask_)) + ", blocks: " + std::to_string(nBlocks) +
                    ", eigenvalues: " + std::to_string(r_.spectrum.size()));
     return 0;
   }
@@ -243,16 +237,14 @@ class SpinEntanglementSolver {
     for (double lam : r_.spectrum) r += lam > tol ? 1 : 0;
     return r;
   }
-  ComputationInfo info() const { return info_; }
-  const std::vector<std::string>& log() const { return log_; }
+  ComputationInfo info() const { return log_.info(); }
+  const std::vector<std::string>& log() const { return log_.log(); }
 
  private:
   void clear_() { r_.clear(); }
   Index invalid_(const std::string& what) {
-    log_.push_back(headERROR() + what);
-    info_ = InvalidInput;
     clear_();
-    return 0;
+    return log_.invalid(what);
   }
   std::size_t block_(Index n) const {
     if (n < 0 || n >= static_cast<Index>(r_.blocks())) throw LanczosException("SpinEntanglementSolver: no such block (compute() first; blocks are 0..blocks()-1)");
@@ -270,8 +262,7 @@ class SpinEntanglementSolver {
   bool sitesValid_ = true;
   int sites_ = 0, nUp_ = -1;
   detail::EntanglementBlocks r_;
-  ComputationInfo info_ = Success;
-  std::vector<std::string> log_;
+  detail::CallLog log_;
 };
 
 }  // namespace EigenEx

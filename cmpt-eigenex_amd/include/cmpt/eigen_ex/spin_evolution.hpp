@@ -33,8 +33,9 @@
 // SpinEntanglementSolver (spin_entanglement.hpp: detail::EntanglementBlocks); they change no vector, time, bound or counter.
 // state() downloads.
 //
-// The sub-step and its bound are detail::krylovSubStep and detail::krylovErrorIntegral below, which SpinTimeCorrelationSolver
-// (spin_time_correlation.hpp: unequal-time correlations <A(t) B(0)>, through site operators of complex states) shares.
+// The sub-step, its bound and the loop over sub-steps are detail::krylovSubStep, detail::krylovErrorIntegral and
+// detail::advanceInSubSteps below, which SpinTimeCorrelationSolver (spin_time_correlation.hpp: unequal-time correlations
+// <A(t) B(0)>, through site operators of complex states) shares.
 //
 // Out of scope: complex couplings (Sy, Dzyaloshinskii-Moriya terms); momentum sectors; time-dependent Hamiltonians; Chebyshev
 // propagators; more than one GPU (the matrix-free spin operators are one shard).
@@ -50,6 +51,7 @@
 #include "lanczos.hpp"
 #include "small_eigen.hpp"
 #include "spin_entanglement.hpp"
+#include "spin_frontend.hpp"
 #include "spin_operator.hpp"
 
 namespace cmpt {
@@ -59,6 +61,7 @@ namespace detail {
 
 constexpr int kKrylovQuadPanels = 512;  // composite Simpson: kKrylovQuadPanels + 1 nodes
 constexpr int kKrylovBisections = 60;
+constexpr Index kKrylovMaxSubSteps = 1000000;
 
 // B(tau) of the header for T = S diag(theta) S^T of dimension k (S column-major): beta_m times the Simpson sum
 inline double krylovErrorIntegral(const std::vector<double>& theta, const std::vector<double>& S, int k, double betaM, double tau) {
@@ -149,6 +152,24 @@ inline KrylovSubStep krylovSubStep(eigenex_basis_t basis, Index n, Index m, doub
   return out;
 }
 
+// W <- exp(-i H dt) W in sub-steps of Krylov dimension m until |dt| is used up.  accepted(step, sign) sees every sub-step that
+// was taken (the time it covers is sign * step.tau); applications grows by those of every Lanczos run, steps by the sub-steps
+// taken.  Null, or what went wrong (a NumericalIssue of the caller), then after the sub-steps completed so far.
+template <class Accepted>
+inline const char* advanceInSubSteps(eigenex_basis_t basis, Index n, Index m, double tol, double dt, Index& applications, Index& steps, Accepted accepted) {
+  const double total = std::fabs(dt), sign = dt < 0.0 ? -1.0 : 1.0;
+  double remaining = total;
+  for (Index mine = 0; remaining > 0.0; ++mine, ++steps) {
+    if (mine >= kKrylovMaxSubSteps) return "more than 10^6 sub-steps: the Krylov dimension is too small for this tolerance";
+    const KrylovSubStep step = krylovSubStep(basis, n, m, tol, remaining, total, sign);
+    applications += step.applications;
+    if (step.failure) return step.failure;
+    accepted(step, sign);
+    remaining = step.tau >= remaining ? 0.0 : remaining - step.tau;
+  }
+  return nullptr;
+}
+
 }  // namespace detail
 
 class SpinTimeEvolutionSolver {
@@ -160,10 +181,10 @@ class SpinTimeEvolutionSolver {
 
   static constexpr int kQuadPanels = detail::kKrylovQuadPanels;  // composite Simpson: kQuadPanels + 1 nodes
   static constexpr int kBisections = detail::kKrylovBisections;
-  static constexpr Index kMaxSubSteps = 1000000;
+  static constexpr Index kMaxSubSteps = detail::kKrylovMaxSubSteps;
 
-  static std::string headERROR() { return std::string("ERROR     "); }
-  static std::string headINFO() { return std::string("INFO      "); }
+  static std::string headERROR() { return detail::CallLog::headERROR(); }
+  static std::string headINFO() { return detail::CallLog::headINFO(); }
 
   // nUp = -1: the full space (up to 30 sites); else the sector of nUp sites up (up to 32 sites, no transverse field)
   SpinTimeEvolutionSolver& setModel(const std::shared_ptr<device::Context>& ctx, const SpinHalfModel& model, int nUp = -1) {
@@ -198,11 +219,10 @@ class SpinTimeEvolutionSolver {
   SpinTimeEvolutionSolver& setState(const VectorType& v) {
     begin_("setState");
     if (!ready_()) return *this;
-    if (v.size() != rows_()) return invalid_("invalid input: the state must have one entry per row of the model's space or sector"), *this;
-    const double nrm = v.norm();
-    if (!(nrm > 0.0) || !std::isfinite(nrm)) return invalid_("invalid input: the state is zero (or not finite)"), *this;
-    VectorType u(v.size());
-    for (Index r = 0; r < v.size(); ++r) u[r] = v[r] / nrm;
+    std::string why;
+    double nrm = 0.0;
+    const VectorType u = detail::normalised(v, rows_(), nrm, why);
+    if (!why.empty()) return invalid_(why), *this;
     norm0_ = nrm;
     place_(u, u);
     reset_();
@@ -217,11 +237,9 @@ class SpinTimeEvolutionSolver {
   SpinTimeEvolutionSolver& setProductState(std::uint32_t bits) {
     begin_("setProductState");
     if (!ready_()) return *this;
-    const int L = model_.sites();
-    if (L < 32 && (bits >> L) != 0u) return invalid_("invalid input: the product state names a site outside 0..sites-1"), *this;
-    if (nUp_ >= 0 && upSites_(bits) != nUp_) return invalid_("invalid input: the product state does not lie in the sector (its number of up sites differs)"), *this;
-    const Index row = nUp_ < 0 ? static_cast<Index>(bits) : rank_(bits);
-    if (row < 0) return invalid_("invalid input: the product state was not found among the sector's states"), *this;
+    std::string why;
+    const Index row = detail::productStateRow(model_.sites(), nUp_, rows_(), bits, why);
+    if (row < 0) return invalid_(why), *this;
     VectorType u(rows_(), Complex(0.0, 0.0));
     u[row] = Complex(1.0, 0.0);
     norm0_ = 1.0;
@@ -238,19 +256,14 @@ class SpinTimeEvolutionSolver {
     if (!haveState_) return invalid_("invalid input: no state (setState, setProductState)");
     if (!std::isfinite(dt)) return invalid_("invalid input: dt is not finite");
     if (!(tol_ > 0.0) || !std::isfinite(tol_)) return invalid_("invalid input: setTolerance needs a positive tolerance");
-    const double total = std::fabs(dt), sign = dt < 0.0 ? -1.0 : 1.0;
-    double remaining = total;
     Index steps = 0;
-    while (remaining > 0.0) {
-      if (steps >= kMaxSubSteps) return failed_("more than 10^6 sub-steps: the Krylov dimension is too small for this tolerance");
-      double tau = 0.0, bound = 0.0;
-      if (!subStep_(remaining, total, sign, tau, bound)) return 0;
-      lastBound_ += bound, totalBound_ += bound;
-      time_ += sign * tau;
-      remaining = tau >= remaining ? 0.0 : remaining - tau;
-      ++steps;
-    }
-    log_.push_back(headINFO() + "sub-steps: " + std::to_string(steps) + ", error bound of this call: " + std::to_string(lastBound_));
+    // a failed call leaves the time advanced by the sub-steps that were completed
+    const char* failure = detail::advanceInSubSteps(dev_.handle(), rows_(), krylov_(), tol_, dt, applications_, steps, [this](const detail::KrylovSubStep& step, double sign) {
+      lastBound_ += step.bound, totalBound_ += step.bound;
+      time_ += sign * step.tau;
+    });
+    if (failure) return failed_(failure);
+    log_.note("sub-steps: " + std::to_string(steps) + ", error bound of this call: " + std::to_string(lastBound_));
     return steps;
   }
 
@@ -280,7 +293,7 @@ class SpinTimeEvolutionSolver {
     if (!measurable_()) return {};
     const std::size_t L = static_cast<std::size_t>(model_.sites());
     std::vector<std::uint32_t> masks;
-    for (std::size_t i = 0; i < L; ++i) masks.push_back(std::uint32_t(1) << i);
+    detail::appendSiteMasks(L, masks);
     std::vector<double> d(L, 0.0);
     double n2 = 0.0;
     device::check(eigenex_spin_measure(dev_.handle(), EIGENEX_VEC_W, static_cast<int>(L), masks.data(), 0, nullptr, d.data(), nullptr, &n2), "eigenex_spin_measure");
@@ -314,19 +327,19 @@ class SpinTimeEvolutionSolver {
   }
   double entanglementEntropy(const std::vector<int>& sites) {
     bool valid = true;
-    const std::uint32_t mask = siteMask_(sites, valid);
+    const std::uint32_t mask = detail::siteMask(sites, valid);
     detail::EntanglementBlocks e;
     return entangle_(mask, valid, e) ? e.entropy() : 0.0;
   }
   std::vector<double> entanglementSpectrum(const std::vector<int>& sites) {
     bool valid = true;
-    const std::uint32_t mask = siteMask_(sites, valid);
+    const std::uint32_t mask = detail::siteMask(sites, valid);
     detail::EntanglementBlocks e;
     return entangle_(mask, valid, e) ? e.spectrum : std::vector<double>();
   }
   double entanglementRenyi2(const std::vector<int>& sites) {
     bool valid = true;
-    const std::uint32_t mask = siteMask_(sites, valid);
+    const std::uint32_t mask = detail::siteMask(sites, valid);
     detail::EntanglementBlocks e;
     return entangle_(mask, valid, e) ? e.renyi2() : 0.0;
   }
@@ -341,8 +354,8 @@ class SpinTimeEvolutionSolver {
 
   int sites() const { return haveModel_ ? model_.sites() : 0; }
   int sitesUp() const { return nUp_; }
-  ComputationInfo info() const { return info_; }
-  const std::vector<std::string>& log() const { return log_; }
+  ComputationInfo info() const { return log_.info(); }
+  const std::vector<std::string>& log() const { return log_.log(); }
 
   // B(tau) of the header for T = S diag(theta) S^T of dimension k (S column-major): beta_m times the Simpson sum
   static double errorIntegral(const std::vector<double>& theta, const std::vector<double>& S, int k, double betaM, double tau) {
@@ -350,21 +363,9 @@ class SpinTimeEvolutionSolver {
   }
 
  private:
-  void begin_(const char* who) {
-    log_.clear();
-    log_.push_back(headINFO() + "SpinTimeEvolutionSolver::" + who + "(...) was called");
-    info_ = Success;
-  }
-  Index invalid_(const std::string& what) {
-    log_.push_back(headERROR() + what);
-    info_ = InvalidInput;
-    return 0;
-  }
-  Index failed_(const std::string& what) {
-    log_.push_back(headERROR() + what);
-    info_ = NumericalIssue;
-    return 0;
-  }
+  void begin_(const char* who) { log_.begin("SpinTimeEvolutionSolver", who); }
+  Index invalid_(const std::string& what) { return log_.invalid(what); }
+  Index failed_(const std::string& what) { return log_.failed(what); }
   void reset_() { time_ = 0.0, lastBound_ = 0.0, totalBound_ = 0.0, applications_ = 0, haveState_ = true; }
   Index rows_() const { return static_cast<Index>(op_->rows()); }
   bool measurable_() const { return haveState_ && dev_.alive(); }
@@ -389,44 +390,6 @@ class SpinTimeEvolutionSolver {
       device::check(eigenex_basis_clear(dev_.handle()), "eigenex_basis_clear");
     dev_.upload(EIGENEX_VEC_W, psi);
     dev_.upload(EIGENEX_VEC_COL(cap - 1), psi0);
-  }
-  static int upSites_(std::uint32_t bits) {
-    int c = 0;
-    for (; bits; bits &= bits - 1) ++c;
-    return c;
-  }
-  // the row of a state of the sector, from the library's own ordering (eigenex_spin_sector_states: the states ascending) by
-  // bisection over the ranks; -1 if it is not among them
-  Index rank_(std::uint32_t bits) const {
-    Index lo = 0, hi = rows_() - 1;
-    while (lo <= hi) {
-      const Index mid = lo + (hi - lo) / 2;
-      std::uint32_t s = 0;
-      device::check(eigenex_spin_sector_states(model_.sites(), nUp_, mid, 1, &s), "eigenex_spin_sector_states");
-      if (s == bits) return mid;
-      if (s < bits)
-        lo = mid + 1;
-      else
-        hi = mid - 1;
-    }
-    return -1;
-  }
-
-  bool subStep_(double remaining, double total, double sign, double& tau, double& bound) {
-    const detail::KrylovSubStep step = detail::krylovSubStep(dev_.handle(), rows_(), krylov_(), tol_, remaining, total, sign);
-    applications_ += step.applications;
-    if (step.failure) return failed_(step.failure), false;
-    tau = step.tau, bound = step.bound;
-    return true;
-  }
-
-  static std::uint32_t siteMask_(const std::vector<int>& sites, bool& valid) {
-    std::uint32_t mask = 0;
-    for (int i : sites) {
-      if (i < 0 || i > 31 || ((mask >> i) & 1u)) valid = false;
-      else mask |= std::uint32_t(1) << i;
-    }
-    return mask;
   }
   // rho_A of W, to unit trace and diagonalised; false (and logged) for an invalid subsystem or without a state
   bool entangle_(std::uint32_t mask, bool sitesValid, detail::EntanglementBlocks& e) {
@@ -454,20 +417,14 @@ class SpinTimeEvolutionSolver {
     if (!measurable_()) return {};
     const std::size_t L = static_cast<std::size_t>(model_.sites());
     std::vector<std::uint32_t> masks;
-    for (std::size_t i = 0; i < L; ++i)
-      for (std::size_t j = i + 1; j < L; ++j) masks.push_back((std::uint32_t(1) << i) | (std::uint32_t(1) << j));
-    std::vector<double> raw(masks.size(), 0.0), out(L * L, 0.0);
+    detail::appendPairMasks(L, masks);
+    std::vector<double> raw(masks.size(), 0.0);
     double n2 = 0.0;
     device::check(eigenex_spin_measure(dev_.handle(), EIGENEX_VEC_W, zz ? static_cast<int>(masks.size()) : 0, zz ? masks.data() : nullptr,
                                        zz ? 0 : static_cast<int>(masks.size()), zz ? nullptr : masks.data(), zz ? raw.data() : nullptr,
                                        zz ? nullptr : raw.data(), &n2),
                   "eigenex_spin_measure");
-    std::size_t k = 0;
-    for (std::size_t i = 0; i < L; ++i) {
-      out[i * L + i] = zz ? 0.25 : 0.5;
-      for (std::size_t j = i + 1; j < L; ++j, ++k) out[i * L + j] = out[j * L + i] = raw[k] / ((zz ? 4.0 : 2.0) * n2);
-    }
-    return out;
+    return detail::pairMatrix(raw.data(), L, (zz ? 4.0 : 2.0) * n2, zz ? 0.25 : 0.5);
   }
 
   std::shared_ptr<device::Context> ctx_;
@@ -480,8 +437,7 @@ class SpinTimeEvolutionSolver {
   detail::KrylovDevice dev_;
   double norm0_ = 1.0, time_ = 0.0, lastBound_ = 0.0, totalBound_ = 0.0;
   Index applications_ = 0;
-  ComputationInfo info_ = Success;
-  std::vector<std::string> log_;
+  detail::CallLog log_;
 };
 
 }  // namespace EigenEx

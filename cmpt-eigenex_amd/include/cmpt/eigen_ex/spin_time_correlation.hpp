@@ -57,16 +57,16 @@ class SpinTimeCorrelationSolver {
   using Coefficients = std::vector<Complex>;
 
   static constexpr int kKeptOperators = 4;
-  static constexpr Index kMaxSubSteps = 1000000;
+  static constexpr Index kMaxSubSteps = detail::kKrylovMaxSubSteps;
 
-  static std::string headERROR() { return std::string("ERROR     "); }
-  static std::string headINFO() { return std::string("INFO      "); }
+  static std::string headERROR() { return detail::CallLog::headERROR(); }
+  static std::string headINFO() { return detail::CallLog::headINFO(); }
 
   // nUp = -1: the full space (up to 30 sites); else the sector of nUp sites up (up to 32 sites, no transverse field)
   SpinTimeCorrelationSolver& setModel(const std::shared_ptr<device::Context>& ctx, const SpinHalfModel& model, int nUp = -1) {
     ctx_ = ctx, model_ = model, nUp_ = nUp, haveModel_ = true, haveState_ = false;
     release_();
-    srcOp_.reset(), dstOp_.reset();
+    ops_.reset();
     return *this;
   }
   SpinTimeCorrelationSolver& setKrylovDimension(Index m) {
@@ -144,7 +144,7 @@ class SpinTimeCorrelationSolver {
     if (!std::isfinite(dt)) return invalid_("invalid input: dt is not finite");
     if (!(tol_ > 0.0) || !std::isfinite(tol_)) return invalid_("invalid input: setTolerance needs a positive tolerance");
     Index steps = 0;
-    if (zero_) log_.push_back(zeroNote_);
+    if (zero_) log_.note(zeroNote_);
     if (!zero_) {
       // a failed call may leave the two vectors at different times: nothing is read from them until the run is set up again
       if ((!eigen_ && !advance_(psiDev_, psiRows_(), dt, epsPsi_, steps)) || !advance_(phiDev_, phiRows_(), dt, epsPhi_, steps)) {
@@ -153,7 +153,7 @@ class SpinTimeCorrelationSolver {
       }
     }
     time_ += dt;
-    log_.push_back(headINFO() + "sub-steps: " + std::to_string(steps) + ", accumulated bounds: " + std::to_string(epsPsi_) + " (state), " +
+    log_.note("sub-steps: " + std::to_string(steps) + ", accumulated bounds: " + std::to_string(epsPsi_) + " (state), " +
                    std::to_string(epsPhi_) + " (source)");
     return steps;
   }
@@ -167,7 +167,7 @@ class SpinTimeCorrelationSolver {
     for (std::size_t n = 0; n < K; ++n)
       if (!checkCoefficients_(measured_[n], "a measured operator")) return out;
     out.assign(K, Complex(0.0, 0.0));
-    if (zero_) return log_.push_back(zeroNote_), out;
+    if (zero_) return log_.note(zeroNote_), out;
     const double amplitude = std::sqrt(bnorm2_);
     const Complex phase = eigen_ ? Complex(std::cos(E0_ * time_), std::sin(E0_ * time_)) : Complex(1.0, 0.0);  // conj of e^{-i E0 t}
     for (std::size_t n = 0; n < K; ++n) {
@@ -202,61 +202,28 @@ class SpinTimeCorrelationSolver {
   std::size_t measuredOperators() const { return measured_.size(); }
   int sites() const { return haveModel_ ? model_.sites() : 0; }
   int sitesUp() const { return nUp_; }
-  ComputationInfo info() const { return info_; }
-  const std::vector<std::string>& log() const { return log_; }
+  ComputationInfo info() const { return log_.info(); }
+  const std::vector<std::string>& log() const { return log_.log(); }
 
  private:
-  void begin_(const char* who) {
-    log_.clear();
-    log_.push_back(headINFO() + "SpinTimeCorrelationSolver::" + who + "(...) was called");
-    info_ = Success;
-  }
-  Index invalid_(const std::string& what) {
-    log_.push_back(headERROR() + what);
-    info_ = InvalidInput;
-    return 0;
-  }
-  Index failed_(const std::string& what) {
-    log_.push_back(headERROR() + what);
-    info_ = NumericalIssue;
-    return 0;
-  }
+  void begin_(const char* who) { log_.begin("SpinTimeCorrelationSolver", who); }
+  Index invalid_(const std::string& what) { return log_.invalid(what); }
+  Index failed_(const std::string& what) { return log_.failed(what); }
   void release_() {
     psiDev_.release(), phiDev_.release();  // the states go before their operators
     prepared_ = false, kept_ = false;
   }
-  static int dstUp_(int nUp, int kind) { return nUp < 0 || kind == EIGENEX_SPIN_SITE_Z ? nUp : (kind == EIGENEX_SPIN_SITE_PLUS ? nUp + 1 : nUp - 1); }
-  Index psiRows_() const { return static_cast<Index>(srcOp_->rows()); }
-  Index phiRows_() const { return static_cast<Index>(dstOp_->rows()); }
+  Index psiRows_() const { return static_cast<Index>(ops_.src->rows()); }
+  Index phiRows_() const { return static_cast<Index>(ops_.dst->rows()); }
   static void split_(const Coefficients& c, std::vector<double>& re, std::vector<double>& im) {
     re.assign(c.size(), 0.0), im.assign(c.size(), 0.0);
     for (std::size_t i = 0; i < c.size(); ++i) re[i] = c[i].real(), im[i] = c[i].imag();
   }
   bool checkCoefficients_(const Coefficients& c, const char* whose) {
-    if (static_cast<int>(c.size()) != model_.sites()) return invalid_(std::string("invalid input: ") + whose + " needs one coefficient per site"), false;
-    for (const Complex& a : c)
-      if (!std::isfinite(a.real()) || !std::isfinite(a.imag())) return invalid_(std::string("invalid input: a coefficient of ") + whose + " is not finite"), false;
-    return true;
-  }
-  static int upSites_(std::uint32_t bits) {
-    int c = 0;
-    for (; bits; bits &= bits - 1) ++c;
-    return c;
-  }
-  // the row of a state of the sector by bisection over the library's own ordering (the states ascending); -1 if it is not there
-  Index rank_(std::uint32_t bits) const {
-    Index lo = 0, hi = psiRows_() - 1;
-    while (lo <= hi) {
-      const Index mid = lo + (hi - lo) / 2;
-      std::uint32_t s = 0;
-      device::check(eigenex_spin_sector_states(model_.sites(), nUp_, mid, 1, &s), "eigenex_spin_sector_states");
-      if (s == bits) return mid;
-      if (s < bits)
-        lo = mid + 1;
-      else
-        hi = mid - 1;
-    }
-    return -1;
+    std::vector<double> re, im;
+    split_(c, re, im);
+    const std::string why = detail::checkCoefficients(re, &im, model_.sites(), whose);
+    return why.empty() || (invalid_(why), false);
   }
 
   // A_n psi (the work vector of psi's state) into column `column` of phi's state
@@ -269,19 +236,10 @@ class SpinTimeCorrelationSolver {
 
   // exp(-i H dt) on the work vector of `dev` in sub-steps; adds their bounds to eps and their number to steps
   bool advance_(detail::KrylovDevice& dev, Index rows, double dt, double& eps, Index& steps) {
-    const double total = std::fabs(dt), sign = dt < 0.0 ? -1.0 : 1.0;
-    const Index m = std::min<Index>(m_, rows);
-    double remaining = total;
     Index mine = 0;
-    while (remaining > 0.0) {
-      if (mine >= kMaxSubSteps) return failed_("more than 10^6 sub-steps: the Krylov dimension is too small for this tolerance"), false;
-      const detail::KrylovSubStep step = detail::krylovSubStep(dev.handle(), rows, m, tol_, remaining, total, sign);
-      applications_ += step.applications;
-      if (step.failure) return failed_(step.failure), false;
-      eps += step.bound;
-      remaining = step.tau >= remaining ? 0.0 : remaining - step.tau;
-      ++mine;
-    }
+    const char* failure = detail::advanceInSubSteps(dev.handle(), rows, std::min<Index>(m_, rows), tol_, dt, applications_, mine,
+                                                    [&eps](const detail::KrylovSubStep& step, double) { eps += step.bound; });
+    if (failure) return failed_(failure), false;
     steps += mine;
     return true;
   }
@@ -305,38 +263,30 @@ class SpinTimeCorrelationSolver {
       if (!checkCoefficients_(a, "a measured operator")) return false;
     if (m_ < 2) return invalid_("invalid input: setKrylovDimension needs at least 2"), false;
     if (eigen_ && !std::isfinite(E0_)) return invalid_("invalid input: the energy of setEigenstate is not finite"), false;
-    const int up = dstUp_(nUp_, kind_);
+    const int up = detail::dstUp(nUp_, kind_);
     if (nUp_ >= 0 && (up < 0 || up > L))
       return invalid_("invalid input: the operators leave the sectors of the model (S+ of the sector with every site up, S- of the one with none)"), false;
     try {
-      if (!srcOp_) srcOp_ = device::spinHalfComplexOperator(ctx_, model_, nUp_);
-      if (up == nUp_) {
-        if (dstOp_ != srcOp_) phiDev_.release();
-        dstOp_ = srcOp_;
-      } else if (!dstOp_ || dstOp_ == srcOp_ || dstUpBuilt_ != up) {
-        phiDev_.release();
-        dstOp_ = device::spinHalfComplexOperator(ctx_, model_, up);
-      }
-      dstUpBuilt_ = up;
+      const auto make = [this](int nUp) { return device::spinHalfComplexOperator(ctx_, model_, nUp); };
+      if (!ops_.src) ops_.src = make(nUp_);
+      if (!ops_.keeps(nUp_, up)) phiDev_.release();  // here the old state goes before the new operator is built, not after
+      ops_.destination(nUp_, up, make, [this] { phiDev_.release(); });
     } catch (const LanczosException& e) {
       return invalid_(std::string("invalid input: the model has no such operator: ") + e.what()), false;
     }
     // psi_0, normalised
     const Index n = psiRows_();
     VectorType u;
+    std::string why;
     if (productState_) {
-      if (L < 32 && (bits_ >> L) != 0u) return invalid_("invalid input: the product state names a site outside 0..sites-1"), false;
-      if (nUp_ >= 0 && upSites_(bits_) != nUp_) return invalid_("invalid input: the product state does not lie in the sector (its number of up sites differs)"), false;
-      const Index row = nUp_ < 0 ? static_cast<Index>(bits_) : rank_(bits_);
-      if (row < 0) return invalid_("invalid input: the product state was not found among the sector's states"), false;
+      const Index row = detail::productStateRow(L, nUp_, n, bits_, why);
+      if (row < 0) return invalid_(why), false;
       u = VectorType(n, Complex(0.0, 0.0));
       u[row] = Complex(1.0, 0.0);
     } else {
-      if (psi0_.size() != n) return invalid_("invalid input: the state must have one entry per row of the model's space or sector"), false;
-      const double nrm = psi0_.norm();
-      if (!(nrm > 0.0) || !std::isfinite(nrm)) return invalid_("invalid input: the state is zero (or not finite)"), false;
-      u = VectorType(n);
-      for (Index r = 0; r < n; ++r) u[r] = psi0_[r] / nrm;
+      double nrm = 0.0;
+      u = detail::normalised(psi0_, n, nrm, why);
+      if (!why.empty()) return invalid_(why), false;
     }
     const std::size_t K = measured_.size();
     const bool keep = eigen_ && K >= 1 && K <= static_cast<std::size_t>(kKeptOperators);
@@ -345,31 +295,22 @@ class SpinTimeCorrelationSolver {
     const Index nd = phiRows_();
     spare_ = static_cast<int>(std::min<Index>(m_, nd) + 1);
     const int capPhi = spare_ + (keep ? static_cast<int>(K) : 1);
-    psiDev_.create(ctx_, srcOp_, n, capPsi, 0, true);
-    phiDev_.create(ctx_, dstOp_, nd, capPhi, 0, true);
+    psiDev_.create(ctx_, ops_.src, n, capPsi, 0, true);
+    phiDev_.create(ctx_, ops_.dst, nd, capPhi, 0, true);
     psiDev_.upload(EIGENEX_VEC_W, u);
     if (time_ != 0.0 || applications_ > 0)  // a setting changed in the middle of a run
-      log_.push_back(headINFO() + "the run starts again at t = 0 (it stood at t = " + std::to_string(time_) + "): time, bounds and counters are cleared");
+      log_.note("the run starts again at t = 0 (it stood at t = " + std::to_string(time_) + "): time, bounds and counters are cleared");
     time_ = 0.0, epsPsi_ = 0.0, epsPhi_ = 0.0, applications_ = 0, zero_ = false, bnorm2_ = 0.0, broken_ = false;
     std::vector<double> re, im;
     split_(source_, re, im);
-    double norm2 = 0.0;
-    device::check(eigenex_spin_site_apply_z(psiDev_.handle(), EIGENEX_VEC_W, phiDev_.handle(), EIGENEX_VEC_W, kind_, re.data(), im.data(), &norm2),
-                  "eigenex_spin_site_apply_z");
-    if (!std::isfinite(norm2)) return failed_("B|psi_0> is not finite"), false;
-    // |y_r| <= L eps sum_i |b_i| |x| is what the roundings of the application alone can leave of an exact zero (Z: half of it)
-    double csum = 0.0;
-    for (const Complex& b : source_) csum += std::fabs(b.real()) + std::fabs(b.imag());
-    const double noise = static_cast<double>(L) * std::ldexp(1.0, -52) * csum * (kind_ == EIGENEX_SPIN_SITE_Z ? 0.5 : 1.0);
-    if (norm2 <= noise * noise) {
-      zeroNote_ = headINFO() + (norm2 == 0.0 ? "B|psi_0> = 0" : "B|psi_0> vanishes within the rounding of its application") +
-                  ": the response is identically zero";
+    // B psi_0 of the unit vector psi_0, to unit length unless it vanishes
+    const detail::SiteApplication b = detail::applySiteOperatorToUnit(psiDev_.handle(), EIGENEX_VEC_W, phiDev_.handle(), true, kind_, L, re, &im, 1.0);
+    if (b.outcome == detail::SiteApplication::NotFinite) return failed_("B|psi_0> is not finite"), false;
+    if (b.zero()) {
+      zeroNote_ = b.zeroNote("B|psi_0>", "the response");
       zero_ = true;
     } else {
-      bnorm2_ = norm2;
-      // to unit length through V: the scaling kernel is not an in-place one
-      device::check(eigenex_scale(phiDev_.handle(), EIGENEX_VEC_V, EIGENEX_VEC_W, 1.0 / std::sqrt(norm2)), "eigenex_scale");
-      device::check(eigenex_vec_copy(phiDev_.handle(), EIGENEX_VEC_W, EIGENEX_VEC_V), "eigenex_vec_copy");
+      bnorm2_ = b.norm2;
       if (keep) {
         kept_ = true;
         for (std::size_t k = 0; k < K; ++k) applyMeasured_(k, spare_ + static_cast<int>(k));
@@ -382,7 +323,7 @@ class SpinTimeCorrelationSolver {
   std::shared_ptr<device::Context> ctx_;
   SpinHalfModel model_;
   bool haveModel_ = false, haveState_ = false, haveSource_ = false, productState_ = false, eigen_ = false;
-  int nUp_ = -1, kind_ = -1, dstUpBuilt_ = -2;
+  int nUp_ = -1, kind_ = -1;
   std::uint32_t bits_ = 0;
   Index m_ = 30;
   double tol_ = 1e-10, E0_ = 0.0;
@@ -390,14 +331,13 @@ class SpinTimeCorrelationSolver {
   Coefficients source_;
   std::vector<Coefficients> measured_;
 
-  std::shared_ptr<device::CsrOperator> srcOp_, dstOp_;
+  detail::SectorPair ops_;
   detail::KrylovDevice psiDev_, phiDev_;
   bool prepared_ = false, zero_ = false, kept_ = false, broken_ = false;
   int spare_ = 0;
   double time_ = 0.0, bnorm2_ = 0.0, epsPsi_ = 0.0, epsPhi_ = 0.0;
   Index applications_ = 0;
-  ComputationInfo info_ = Success;
-  std::vector<std::string> log_;
+  detail::CallLog log_;
   std::string zeroNote_;
 };
 

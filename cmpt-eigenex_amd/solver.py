@@ -84,12 +84,28 @@ def lib():
             getattr(L, p + "energy_window").argtypes = [_vp, C.c_double, C.c_double, _dp]
             getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
             getattr(L, p + "log_line").restype = C.c_char_p
-        p = "eigenex_spin_dynamics_solver_"
         _ip32 = C.POINTER(C.c_int32)
-        getattr(L, p + "create").restype = _vp
-        getattr(L, p + "destroy").argtypes = [_vp]
-        getattr(L, p + "destroy").restype = None
-        getattr(L, p + "set_model").argtypes = [_vp, _vp, C.c_int, C.c_int, _ip32, _ip32, _dp, _dp, _dp, _dp, C.c_int]
+        for kind in ("dynamics", "evolution", "time_correlation", "entanglement"):
+            p = f"eigenex_spin_{kind}_solver_"
+            getattr(L, p + "create").argtypes = []
+            getattr(L, p + "create").restype = _vp
+            getattr(L, p + "destroy").argtypes = [_vp]
+            getattr(L, p + "destroy").restype = None
+            getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
+            getattr(L, p + "log_line").restype = C.c_char_p
+        for kind in ("dynamics", "evolution", "time_correlation"):
+            p = f"eigenex_spin_{kind}_solver_"
+            getattr(L, p + "set_model").argtypes = [_vp, _vp, C.c_int, C.c_int, _ip32, _ip32, _dp, _dp, _dp, _dp, C.c_int]
+        for kind in ("evolution", "time_correlation"):
+            p = f"eigenex_spin_{kind}_solver_"
+            getattr(L, p + "set_state").argtypes = [_vp, _dp, C.c_int64, C.c_int]
+            getattr(L, p + "set_product_state").argtypes = [_vp, C.c_uint32]
+            getattr(L, p + "set_krylov_dimension").argtypes = [_vp, C.c_int64]
+            getattr(L, p + "set_tolerance").argtypes = [_vp, C.c_double]
+            getattr(L, p + "evolve").argtypes = [_vp, C.c_double, _lp]
+            getattr(L, p + "status").argtypes = [_vp, _dp, _lp]
+            getattr(L, p + "fetch").argtypes = [_vp, _dp]
+        p = "eigenex_spin_dynamics_solver_"
         getattr(L, p + "set_state").argtypes = [_vp, _dp, C.c_int64]
         getattr(L, p + "set_state_energy").argtypes = [_vp, C.c_double]
         getattr(L, p + "set_site_operator").argtypes = [_vp, C.c_int, _dp, C.c_int]
@@ -104,54 +120,20 @@ def lib():
         getattr(L, p + "spectrum").argtypes = [_vp, _dp, C.c_int64, C.c_double, _dp]
         getattr(L, p + "moment").argtypes = [_vp, C.c_int, _dp]
         getattr(L, p + "static_structure_factor_z").argtypes = [_vp, C.c_double, _dp]
-        getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
-        getattr(L, p + "log_line").restype = C.c_char_p
         p = "eigenex_spin_evolution_solver_"
-        getattr(L, p + "create").argtypes = []
-        getattr(L, p + "create").restype = _vp
-        getattr(L, p + "destroy").argtypes = [_vp]
-        getattr(L, p + "destroy").restype = None
-        getattr(L, p + "set_model").argtypes = [_vp, _vp, C.c_int, C.c_int, _ip32, _ip32, _dp, _dp, _dp, _dp, C.c_int]
-        getattr(L, p + "set_state").argtypes = [_vp, _dp, C.c_int64, C.c_int]
-        getattr(L, p + "set_product_state").argtypes = [_vp, C.c_uint32]
-        getattr(L, p + "set_krylov_dimension").argtypes = [_vp, C.c_int64]
-        getattr(L, p + "set_tolerance").argtypes = [_vp, C.c_double]
-        getattr(L, p + "evolve").argtypes = [_vp, C.c_double, _lp]
-        getattr(L, p + "status").argtypes = [_vp, _dp, _lp]
         getattr(L, p + "scalar").argtypes = [_vp, C.c_int, _dp]
         getattr(L, p + "measure").argtypes = [_vp, C.c_int, _lp]
         getattr(L, p + "entanglement").argtypes = [_vp, C.c_uint32, _ip32, C.c_int, C.c_int, _lp]
-        getattr(L, p + "fetch").argtypes = [_vp, _dp]
-        getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
-        getattr(L, p + "log_line").restype = C.c_char_p
         p = "eigenex_spin_time_correlation_solver_"
-        getattr(L, p + "create").argtypes = []
-        getattr(L, p + "create").restype = _vp
-        getattr(L, p + "destroy").argtypes = [_vp]
-        getattr(L, p + "destroy").restype = None
-        getattr(L, p + "set_model").argtypes = [_vp, _vp, C.c_int, C.c_int, _ip32, _ip32, _dp, _dp, _dp, _dp, C.c_int]
-        getattr(L, p + "set_state").argtypes = [_vp, _dp, C.c_int64, C.c_int]
-        getattr(L, p + "set_product_state").argtypes = [_vp, C.c_uint32]
         getattr(L, p + "set_eigenstate").argtypes = [_vp, C.c_double]
         getattr(L, p + "set_source_operator").argtypes = [_vp, C.c_int, _dp, C.c_int]
         getattr(L, p + "add_measured_operator").argtypes = [_vp, _dp, C.c_int]
         getattr(L, p + "clear_measured_operators").argtypes = [_vp]
         getattr(L, p + "set_measured_sites").argtypes = [_vp]
         getattr(L, p + "set_momentum_z").argtypes = [_vp, C.c_double]
-        getattr(L, p + "set_krylov_dimension").argtypes = [_vp, C.c_int64]
-        getattr(L, p + "set_tolerance").argtypes = [_vp, C.c_double]
-        getattr(L, p + "evolve").argtypes = [_vp, C.c_double, _lp]
         getattr(L, p + "values").argtypes = [_vp, _lp]
-        getattr(L, p + "fetch").argtypes = [_vp, _dp]
-        getattr(L, p + "status").argtypes = [_vp, _dp, _lp]
         getattr(L, p + "operator_bounds").argtypes = [_vp, C.c_int64, _dp]
-        getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
-        getattr(L, p + "log_line").restype = C.c_char_p
         p = "eigenex_spin_entanglement_solver_"
-        getattr(L, p + "create").argtypes = []
-        getattr(L, p + "create").restype = _vp
-        getattr(L, p + "destroy").argtypes = [_vp]
-        getattr(L, p + "destroy").restype = None
         getattr(L, p + "set_device_operator").argtypes = [_vp, _vp, _vp]
         getattr(L, p + "set_state").argtypes = [_vp, _dp, C.c_int64]
         getattr(L, p + "set_subsystem").argtypes = [_vp, _ip32, C.c_int]
@@ -164,8 +146,6 @@ def lib():
         getattr(L, p + "get").argtypes = [_vp, _dp, _dp]
         getattr(L, p + "renyi").argtypes = [_vp, C.c_double, _dp]
         getattr(L, p + "schmidt_rank").argtypes = [_vp, C.c_double, _lp]
-        getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
-        getattr(L, p + "log_line").restype = C.c_char_p
         for kind in FAMILIES:
             p = f"eigenex_{kind}_solver_"
             getattr(L, p + "create").restype = _vp
@@ -694,21 +674,20 @@ class SpectralDensitySolver(_SolverBase):
         return d.value
 
 
-class SpinDynamicsSolver:
-    """SpinDynamicsSolver (spin_dynamics.hpp): dynamical spin correlations of a state by the Lanczos continued fraction.  The
-    model is (n_sites, bonds, hz, hx) with bonds = [(i, j, Jz, Jxy), ...]; n_up = None: the full space."""
+class _SpinSolverBase:
+    """What the spin front-ends share: the handle of `_prefix`, the model (where the class takes one), the log and the end."""
 
-    _names = ("npoles", "nalpha", "nbeta", "nlog", "info")
+    _prefix = ""
 
     def __init__(self):
         self._L = lib()
-        self.h = _vp(self._L.eigenex_spin_dynamics_solver_create())
+        self.h = _vp(self._f("create")())
         if not self.h:
             raise capi.EigenexError("solver create failed")
         self._keep = []
 
     def _f(self, name):
-        return getattr(self._L, "eigenex_spin_dynamics_solver_" + name)
+        return getattr(self._L, self._prefix + name)
 
     def setModel(self, ctx: capi.Context, n_sites, bonds, hz=None, hx=None, n_up=None):
         i32 = C.POINTER(C.c_int32)
@@ -719,9 +698,75 @@ class SpinDynamicsSolver:
         fz = None if hz is None else np.ascontiguousarray(hz, np.float64)
         fx = None if hx is None else np.ascontiguousarray(hx, np.float64)
         self._keep.append(ctx)
+        self._sites = int(n_sites)
         _chk(self._f("set_model")(self.h, ctx.h, int(n_sites), si.size, si.ctypes.data_as(i32), sj.ctypes.data_as(i32), _d(jz), _d(jxy),
                                   None if fz is None else _d(fz), None if fx is None else _d(fx), -1 if n_up is None else int(n_up)))
         return self
+
+    def _nlog(self):
+        return self._sizes()["nlog"]
+
+    def log(self):
+        return [self._f("log_line")(self.h, i).decode() for i in range(self._nlog())]
+
+    def close(self):
+        if self.h:
+            self._f("destroy")(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _SpinEvolvingSolverBase(_SpinSolverBase):
+    """... of the two that evolve a state: the state, the step control, evolve() and the status arrays of `_status_sizes`."""
+
+    _status_sizes = (0, 0)
+
+    def setState(self, v):
+        cplx = np.iscomplexobj(v)
+        a = np.ascontiguousarray(v, np.complex128 if cplx else np.float64)
+        _chk(self._f("set_state")(self.h, _d(a.view(np.float64)), a.size, int(cplx)))
+        return self
+
+    def setProductState(self, bits):
+        _chk(self._f("set_product_state")(self.h, int(bits)))
+        return self
+
+    def setKrylovDimension(self, m):
+        _chk(self._f("set_krylov_dimension")(self.h, int(m)))
+        return self
+
+    def setTolerance(self, tol):
+        _chk(self._f("set_tolerance")(self.h, float(tol)))
+        return self
+
+    def evolve(self, dt):
+        n = C.c_int64()
+        _chk(self._f("evolve")(self.h, float(dt), C.byref(n)))
+        return n.value
+
+    def _status(self):
+        sc, cnt = np.zeros(self._status_sizes[0]), np.zeros(self._status_sizes[1], np.int64)
+        _chk(self._f("status")(self.h, _d(sc), cnt.ctypes.data_as(_lp)))
+        return sc, cnt
+
+    def _nlog(self):
+        return int(self._status()[1][0])
+
+    def info(self):
+        return INFO[int(self._status()[1][1])]
+
+
+class SpinDynamicsSolver(_SpinSolverBase):
+    """SpinDynamicsSolver (spin_dynamics.hpp): dynamical spin correlations of a state by the Lanczos continued fraction.  The
+    model is (n_sites, bonds, hz, hx) with bonds = [(i, j, Jz, Jxy), ...]; n_up = None: the full space."""
+
+    _names = ("npoles", "nalpha", "nbeta", "nlog", "info")
+    _prefix = "eigenex_spin_dynamics_solver_"
 
     def setState(self, v):
         """a real state, or a complex one (then the run is a complex one)"""
@@ -795,76 +840,13 @@ class SpinDynamicsSolver:
         _chk(self._f("static_structure_factor_z")(self.h, float(q), C.byref(v)))
         return v.value
 
-    def log(self):
-        return [self._f("log_line")(self.h, i).decode() for i in range(self._sizes()["nlog"])]
 
-    def close(self):
-        if self.h:
-            self._f("destroy")(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SpinTimeEvolutionSolver:
+class SpinTimeEvolutionSolver(_SpinEvolvingSolverBase):
     """SpinTimeEvolutionSolver (spin_evolution.hpp): |psi(t)> = exp(-i H t)|psi_0> of a spin-1/2 model by Krylov propagation on
     the device, with an a-posteriori error bound per call.  The model is given as for SpinDynamicsSolver."""
 
-    def __init__(self):
-        self._L = lib()
-        self.h = _vp(self._L.eigenex_spin_evolution_solver_create())
-        if not self.h:
-            raise capi.EigenexError("solver create failed")
-        self._keep = []
-
-    def _f(self, name):
-        return getattr(self._L, "eigenex_spin_evolution_solver_" + name)
-
-    def setModel(self, ctx: capi.Context, n_sites, bonds, hz=None, hx=None, n_up=None):
-        i32 = C.POINTER(C.c_int32)
-        si = np.ascontiguousarray([b[0] for b in bonds], np.int32)
-        sj = np.ascontiguousarray([b[1] for b in bonds], np.int32)
-        jz = np.ascontiguousarray([b[2] for b in bonds], np.float64)
-        jxy = np.ascontiguousarray([b[3] for b in bonds], np.float64)
-        fz = None if hz is None else np.ascontiguousarray(hz, np.float64)
-        fx = None if hx is None else np.ascontiguousarray(hx, np.float64)
-        self._keep.append(ctx)
-        self._sites = int(n_sites)
-        _chk(self._f("set_model")(self.h, ctx.h, int(n_sites), si.size, si.ctypes.data_as(i32), sj.ctypes.data_as(i32), _d(jz), _d(jxy),
-                                  None if fz is None else _d(fz), None if fx is None else _d(fx), -1 if n_up is None else int(n_up)))
-        return self
-
-    def setState(self, v):
-        cplx = np.iscomplexobj(v)
-        a = np.ascontiguousarray(v, np.complex128 if cplx else np.float64)
-        _chk(self._f("set_state")(self.h, _d(a.view(np.float64)), a.size, int(cplx)))
-        return self
-
-    def setProductState(self, bits):
-        _chk(self._f("set_product_state")(self.h, int(bits)))
-        return self
-
-    def setKrylovDimension(self, m):
-        _chk(self._f("set_krylov_dimension")(self.h, int(m)))
-        return self
-
-    def setTolerance(self, tol):
-        _chk(self._f("set_tolerance")(self.h, float(tol)))
-        return self
-
-    def evolve(self, dt):
-        n = C.c_int64()
-        _chk(self._f("evolve")(self.h, float(dt), C.byref(n)))
-        return n.value
-
-    def _status(self):
-        sc, cnt = np.zeros(5), np.zeros(4, np.int64)
-        _chk(self._f("status")(self.h, _d(sc), cnt.ctypes.data_as(_lp)))
-        return sc, cnt
+    _prefix = "eigenex_spin_evolution_solver_"
+    _status_sizes = (5, 4)
 
     def time(self):
         return self._status()[0][0]
@@ -880,9 +862,6 @@ class SpinTimeEvolutionSolver:
 
     def operatorApplications(self):
         return int(self._status()[0][4])
-
-    def info(self):
-        return INFO[int(self._status()[1][1])]
 
     def _scalar(self, what):
         out = np.zeros(2)
@@ -941,58 +920,14 @@ class SpinTimeEvolutionSolver:
     def entanglementSpectrum(self, subsystem):
         return self._entanglement(subsystem, 2)
 
-    def log(self):
-        return [self._f("log_line")(self.h, i).decode() for i in range(int(self._status()[1][0]))]
 
-    def close(self):
-        if self.h:
-            self._f("destroy")(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SpinTimeCorrelationSolver:
+class SpinTimeCorrelationSolver(_SpinEvolvingSolverBase):
     """SpinTimeCorrelationSolver (spin_time_correlation.hpp): C_n(t) = <A_n psi(t) | exp(-iHt) B psi_0> of a spin-1/2 model by
     Krylov propagation of two vectors on the device.  The model is given as for SpinDynamicsSolver; coefficients are real or
     complex, one per site."""
 
-    def __init__(self):
-        self._L = lib()
-        self.h = _vp(self._L.eigenex_spin_time_correlation_solver_create())
-        if not self.h:
-            raise capi.EigenexError("solver create failed")
-        self._keep = []
-
-    def _f(self, name):
-        return getattr(self._L, "eigenex_spin_time_correlation_solver_" + name)
-
-    def setModel(self, ctx: capi.Context, n_sites, bonds, hz=None, hx=None, n_up=None):
-        i32 = C.POINTER(C.c_int32)
-        si = np.ascontiguousarray([b[0] for b in bonds], np.int32)
-        sj = np.ascontiguousarray([b[1] for b in bonds], np.int32)
-        jz = np.ascontiguousarray([b[2] for b in bonds], np.float64)
-        jxy = np.ascontiguousarray([b[3] for b in bonds], np.float64)
-        fz = None if hz is None else np.ascontiguousarray(hz, np.float64)
-        fx = None if hx is None else np.ascontiguousarray(hx, np.float64)
-        self._keep.append(ctx)
-        _chk(self._f("set_model")(self.h, ctx.h, int(n_sites), si.size, si.ctypes.data_as(i32), sj.ctypes.data_as(i32), _d(jz), _d(jxy),
-                                  None if fz is None else _d(fz), None if fx is None else _d(fx), -1 if n_up is None else int(n_up)))
-        return self
-
-    def setState(self, v):
-        cplx = np.iscomplexobj(v)
-        a = np.ascontiguousarray(v, np.complex128 if cplx else np.float64)
-        _chk(self._f("set_state")(self.h, _d(a.view(np.float64)), a.size, int(cplx)))
-        return self
-
-    def setProductState(self, bits):
-        _chk(self._f("set_product_state")(self.h, int(bits)))
-        return self
+    _prefix = "eigenex_spin_time_correlation_solver_"
+    _status_sizes = (6, 3)
 
     def setEigenstate(self, E0):
         _chk(self._f("set_eigenstate")(self.h, float(E0)))
@@ -1024,30 +959,12 @@ class SpinTimeCorrelationSolver:
         _chk(self._f("set_momentum_z")(self.h, float(q)))
         return self
 
-    def setKrylovDimension(self, m):
-        _chk(self._f("set_krylov_dimension")(self.h, int(m)))
-        return self
-
-    def setTolerance(self, tol):
-        _chk(self._f("set_tolerance")(self.h, float(tol)))
-        return self
-
-    def evolve(self, dt):
-        n = C.c_int64()
-        _chk(self._f("evolve")(self.h, float(dt), C.byref(n)))
-        return n.value
-
     def values(self):
         n = C.c_int64()
         _chk(self._f("values")(self.h, C.byref(n)))
         out = np.zeros(n.value, np.complex128)
         _chk(self._f("fetch")(self.h, _d(out.view(np.float64))))
         return out
-
-    def _status(self):
-        sc, cnt = np.zeros(6), np.zeros(3, np.int64)
-        _chk(self._f("status")(self.h, _d(sc), cnt.ctypes.data_as(_lp)))
-        return sc, cnt
 
     def time(self):
         return self._status()[0][0]
@@ -1077,40 +994,14 @@ class SpinTimeCorrelationSolver:
     def operatorApplications(self):
         return int(self._status()[0][5])
 
-    def info(self):
-        return INFO[int(self._status()[1][1])]
 
-    def log(self):
-        return [self._f("log_line")(self.h, i).decode() for i in range(int(self._status()[1][0]))]
-
-    def close(self):
-        if self.h:
-            self._f("destroy")(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SpinEntanglementSolver:
+class SpinEntanglementSolver(_SpinSolverBase):
     """SpinEntanglementSolver (spin_entanglement.hpp): the reduced density matrix of a subsystem of a state of a matrix-free
     spin-1/2 operator (capi.Csr.spin_half, capi.Csr.spin_half_sector), formed on the device, and what follows from it: the
     entanglement spectrum, the von Neumann and Renyi entropies and the Schmidt rank."""
 
     _names = ("nblocks", "neigenvalues", "nlog", "info")
-
-    def __init__(self):
-        self._L = lib()
-        self.h = _vp(self._L.eigenex_spin_entanglement_solver_create())
-        if not self.h:
-            raise capi.EigenexError("solver create failed")
-        self._keep = []
-
-    def _f(self, name):
-        return getattr(self._L, "eigenex_spin_entanglement_solver_" + name)
+    _prefix = "eigenex_spin_entanglement_solver_"
 
     def setDeviceOperator(self, csr: capi.Csr):
         self._keep.append(csr)
@@ -1175,17 +1066,3 @@ class SpinEntanglementSolver:
         r = C.c_int64()
         _chk(self._f("schmidt_rank")(self.h, float(tol), C.byref(r)))
         return r.value
-
-    def log(self):
-        return [self._f("log_line")(self.h, i).decode() for i in range(self._sizes()["nlog"])]
-
-    def close(self):
-        if self.h:
-            self._f("destroy")(self.h)
-            self.h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
