@@ -118,6 +118,57 @@ def abs_dot(a, b):
     return float((np.abs(as_doubles(a)).astype(np.longdouble) * np.abs(as_doubles(b)).astype(np.longdouble)).sum())
 
 
+# ---- the checks of a device run against the float64 restatement (tests/test_gpu_density.py and the suites that borrow them) -------
+EPS = np.finfo(np.float64).eps
+
+
+def rounded_vector_bound(err64, x):
+    """|t_k(device) - t_k(restatement)| where the operator kernel adds a row in another order than the restatement: the bound of
+    test_filter_apply_against_long_double, 4 x the restatement's own error against long double (err64) + 4 eps |x|_inf"""
+    return 4 * err64 + 4 * EPS * np.abs(x).max()
+
+
+def moment_bounds(ts, n_moments, vector_bound=None):
+    """reference moments (long double dots of the float64 vectors) and the bound of each: a float64 dot of n terms in any order
+    errs by at most n eps sum|a_i b_i|, so  |mu_dev - mu_ref| <= 2 (2 n eps sum|t_i||t'_i|) + n eps |mu_0 or mu_1| + eps |mu|,
+    and for mu_0, mu_1 themselves n eps sum|a_i b_i| + eps |mu|.  vector_bound(k), where the device's vectors are only close
+    to the restatement's (None: they are equal): the dots move by at most dt' sum|t| + dt sum|t'| more."""
+    vb = vector_bound or (lambda k: 0.0)
+    ref = moments_from_vectors(ts, n_moments, real_dot_longdouble)
+    n = as_doubles(ts[0]).size
+    one = np.ones(n)
+    bounds = []
+    for k in range(n_moments):
+        a, b = (ts[k // 2], ts[k // 2]) if k % 2 == 0 else (ts[k // 2 + 1], ts[k // 2])
+        ka, kb = (k // 2, k // 2) if k % 2 == 0 else (k // 2 + 1, k // 2)
+        moved = vb(ka) * abs_dot(one, b) + vb(kb) * abs_dot(one, a)
+        if k < 2:
+            bnd = n * EPS * abs_dot(a, b) + EPS * abs(float(ref[k])) + moved
+        else:
+            moved0 = 2 * vb(0) * abs_dot(one, ts[0]) if vector_bound is not None else 0.0
+            bnd = 2 * (2 * n * EPS * abs_dot(a, b)) + n * EPS * abs(float(ref[k % 2])) + EPS * abs(float(ref[k])) + 2 * moved + moved0
+        bounds.append(bnd)
+    return ref.astype(np.float64), np.array(bounds), ref
+
+
+def check_moments(label, mu, ts, n_moments, vector_bound=None):
+    ref64, bounds, ref = moment_bounds(ts, n_moments, vector_bound)
+    err = np.abs(mu.astype(np.longdouble) - ref).astype(np.float64)
+    worst = int(np.argmax(err / np.maximum(bounds, 1e-300)))
+    print(f"{label} n_moments={n_moments}: worst moment {worst}: device error {err[worst]:.3e}, bound {bounds[worst]:.3e} (mu = {ref64[worst]:.6e})")
+    assert np.all(err <= bounds)
+
+
+def check_vector(label, got, t_d, bound=None):
+    """the device's Chebyshev vector against the restatement's t_d: bit for bit (bound None), or within the bound"""
+    if bound is None:
+        np.testing.assert_array_equal(got, t_d)
+        return
+    e = float(np.abs(got - t_d).max())
+    print(f"{label}: device error {e:.3e}, bound {bound:.3e}")
+    assert e <= bound
+
+
 def exact_moments(lam, center, halfwidth, M):
     """mu_k = mean_i cos(k arccos x_i) of the scaled eigenvalues: tr T_k / N"""
     th = np.arccos(np.clip((np.asarray(lam, np.longdouble) - center) / halfwidth, -1, 1))

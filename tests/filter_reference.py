@@ -43,20 +43,12 @@ def csr_rowsum_matmul(rowptr, col, val, dtype):
 
 def csr_rowsum_matmul_any_rows(rowptr, col, val, dtype):
     """csr_rowsum_matmul for matrices that may have rows without entries (their result is 0): the same products and the same
-    sum of every non-empty row, np.add.reduceat over the starts of the non-empty rows alone (an empty row's start is the next
-    non-empty row's, so leaving it out cuts the products at the same places)"""
+    sum of every non-empty row (krylov_local_reference.row_sums)"""
+    from krylov_local_reference import row_sums
+
     rowptr = np.asarray(rowptr, np.int64)
     v = np.asarray(val).astype(dtype)
-    filled = np.diff(rowptr) > 0
-    starts = rowptr[:-1][filled]
-
-    def matmul(x):
-        out = np.zeros(filled.size, np.result_type(v.dtype, x.dtype))
-        if starts.size:
-            out[filled] = np.add.reduceat(v * x[col], starts)
-        return out
-
-    return matmul
+    return lambda x: row_sums(v * x[col], rowptr)
 
 
 def apply_filter(matmul, x, mu, center, halfwidth):

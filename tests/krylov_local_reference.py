@@ -14,8 +14,9 @@ hu = (H + shift) u_j in extended precision, r = hu - sum_{i <= j} (u_i^H hu) u_i
 
 which is the rounding of one application plus one combination (the form of _lowest in tests/test_gpu_spin_momentum.py).  Rounding
 does not compound from step to step, so the bound does not depend on the number of steps; a wrong gathered element, scale, phase
-or shift is of the order of the entries of u, ten orders of magnitude outside.  Every row stores its diagonal, so no row is empty
-and np.add.reduceat sums the rows.
+or shift is of the order of the entries of u, ten orders of magnitude outside.  np.add.reduceat sums the rows from the starts
+of the non-empty ones (an empty row's start is the next non-empty row's, so leaving it out cuts the products at the same
+places); an empty row's sum is zero, so that (H + shift) u is shift u there.
 
 Also the fp64 recurrences that tests/test_krylov_local_reference_host.py runs through the check beside those of
 tests/one_sweep_reference.py (which are real): a two-sweep Lanczos for complex vectors and a plain Arnoldi with one or two
@@ -29,8 +30,22 @@ LD, CLD = np.longdouble, np.clongdouble
 
 
 def norm1(n, col, val):
-    """the largest column sum of |val|"""
+    """the largest column sum of |val| (0 for an operator without entries: a column that no row stores sums to zero)"""
+    if n == 0 or np.size(val) == 0:
+        return 0.0
     return float(np.bincount(np.asarray(col, np.int64), weights=np.abs(val), minlength=n).max())
+
+
+def row_sums(prod, rowptr):
+    """the sum of every row's products, zero for a row without entries"""
+    rowptr = np.asarray(rowptr, np.int64)
+    filled = rowptr[1:] > rowptr[:-1]
+    if filled.all():
+        return np.add.reduceat(prod, rowptr[:-1])
+    out = np.zeros(filled.size, prod.dtype)
+    if filled.any():
+        out[filled] = np.add.reduceat(prod, rowptr[:-1][filled])
+    return out
 
 
 def bound(n, k, h1, shift):
@@ -48,7 +63,7 @@ def applied(rows, shift, u, T=None):
     T = T or _wide(val, u, np.asarray(shift))
     u = np.asarray(u).astype(T)
     prod = np.asarray(val).astype(T) * u[np.asarray(col, np.int64)]
-    return np.add.reduceat(prod, np.asarray(rowptr[:-1], np.int64)) + T(shift) * u
+    return row_sums(prod, rowptr) + T(shift) * u
 
 
 class Report(dict):
@@ -140,8 +155,7 @@ def dense_to_csr(A):
 def csr_matmul(rows):
     """x -> H x in fp64 (complex when val or x is)"""
     rowptr, col, val = rows
-    start = np.asarray(rowptr[:-1], np.int64)
-    return lambda x: np.add.reduceat(val * x[col], start)
+    return lambda x: row_sums(val * x[col], rowptr)
 
 
 # ---- fp64 recurrences, written like one_sweep_reference.batched --------------------------------------------------------------

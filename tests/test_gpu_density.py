@@ -74,46 +74,24 @@ def _vector_bound(name, k):
     if name not in ROUNDED:
         return 0.0
     x, _, _, _, err64 = _reference(name)
-    return 4 * err64[k] + 4 * EPS * np.abs(x).max()
+    return dr.rounded_vector_bound(err64[k], x)
+
+
+def _rounded(name):
+    """what density_reference's checks take: None where the device rounds like the restatement, else the bound of vector k"""
+    return (lambda k: _vector_bound(name, k)) if name in ROUNDED else None
 
 
 def _moment_bounds(name, ts, n_moments):
-    """reference moments (long double dots of the float64 vectors) and the bound of each: a float64 dot of n terms in any order
-    errs by at most n eps sum|a_i b_i|, so  |mu_dev - mu_ref| <= 2 (2 n eps sum|t_i||t'_i|) + n eps |mu_0 or mu_1| + eps |mu|,
-    and for mu_0, mu_1 themselves n eps sum|a_i b_i| + eps |mu|.  Where the device's vectors are only close to the
-    restatement's (ROUNDED) the dots move by at most dt' sum|t| + dt sum|t'| more."""
-    ref = dr.moments_from_vectors(ts, n_moments, dr.real_dot_longdouble)
-    n = dr.as_doubles(ts[0]).size
-    one = np.ones(n)
-    bounds = []
-    for k in range(n_moments):
-        a, b = (ts[k // 2], ts[k // 2]) if k % 2 == 0 else (ts[k // 2 + 1], ts[k // 2])
-        ka, kb = (k // 2, k // 2) if k % 2 == 0 else (k // 2 + 1, k // 2)
-        moved = _vector_bound(name, ka) * dr.abs_dot(one, b) + _vector_bound(name, kb) * dr.abs_dot(one, a)
-        if k < 2:
-            bnd = n * EPS * dr.abs_dot(a, b) + EPS * abs(float(ref[k])) + moved
-        else:
-            moved0 = 2 * _vector_bound(name, 0) * dr.abs_dot(one, ts[0]) if name in ROUNDED else 0.0
-            bnd = 2 * (2 * n * EPS * dr.abs_dot(a, b)) + n * EPS * abs(float(ref[k % 2])) + EPS * abs(float(ref[k])) + 2 * moved + moved0
-        bounds.append(bnd)
-    return ref.astype(np.float64), np.array(bounds), ref
+    return dr.moment_bounds(ts, n_moments, _rounded(name))
 
 
 def _check_moments(label, mu, name, ts, n_moments):
-    ref64, bounds, ref = _moment_bounds(name, ts, n_moments)
-    err = np.abs(mu.astype(np.longdouble) - ref).astype(np.float64)
-    worst = int(np.argmax(err / np.maximum(bounds, 1e-300)))
-    print(f"{label} n_moments={n_moments}: worst moment {worst}: device error {err[worst]:.3e}, bound {bounds[worst]:.3e} (mu = {ref64[worst]:.6e})")
-    assert np.all(err <= bounds)
+    dr.check_moments(label, mu, ts, n_moments, _rounded(name))
 
 
 def _check_vector(label, name, got, ts, d):
-    if name in ROUNDED:
-        e, bnd = float(np.abs(got - ts[d]).max()), _vector_bound(name, d)
-        print(f"{label} t_{d}: device error {e:.3e}, bound {bnd:.3e}")
-        assert e <= bnd
-    else:
-        np.testing.assert_array_equal(got, ts[d])
+    dr.check_vector(label, got, ts[d], _vector_bound(name, d) if name in ROUNDED else None)
 
 
 @pytest.mark.parametrize("shards", [1, 2, 3])

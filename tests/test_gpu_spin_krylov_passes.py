@@ -30,13 +30,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import krylov_local_reference as kl  # noqa: E402
+from krylov_pass_runs import CALLS, SCHEMES, SHIFT_Z, SHIFTS  # noqa: E402,F401
+from krylov_pass_runs import arnoldi as _arnoldi, columns as _columns, lanczos as _lanczos, state as _state, two_sweeps_forced as _two_sweeps_forced  # noqa: E402
 import spin_momentum_reference as mref  # noqa: E402
 import spin_reference as sr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-CALLS = 8
-SHIFTS = (0.0, -0.37)
-SHIFT_Z = 0.3 - 0.2j
 
 
 @pytest.fixture(scope="module")
@@ -135,57 +134,7 @@ def _start(n, cplx, seed):
 
 
 # ---- runs --------------------------------------------------------------------------------------------------------------------------
-def _state(st):
-    return st.nvec, st.iterations, st.stopped
-
-
-def _columns(capi, b, nvec):
-    return np.stack([b.download(capi.VEC_COL(c)) for c in range(nvec)]) if nvec else np.zeros((0, b.n_rows), b.dtype)
-
-
-def _lanczos(capi, ctx, op, n, x, batches, shift, mode, capacity, big=False):
-    """dict(state, alpha, beta, U, repairs, pending) after the batches of lanczos_enqueue calls; pending as the last batch left it"""
-    b = capi.Basis(ctx, op, n, capacity)
-    if big:
-        b.tune(2, 1, 0)  # one operator workgroup per CU: the tile loop goes round
-    b.configure(shift=shift, ortho_mode=mode)
-    b.upload(capi.VEC_W, x)
-    for calls in batches:
-        b.lanczos_enqueue(calls)
-    st, alpha, beta = b.lanczos_state()
-    out = dict(state=_state(st), lengths=(st.nalpha, st.nbeta), alpha=alpha, beta=beta, pending=b.close_pending(), repairs=b.repairs())
-    out["U"] = _columns(capi, b, st.nvec)
-    return out, b
-
-
-def _arnoldi(capi, ctx, op, n, x, batches, shift, mode, capacity, big=False):
-    b = capi.Basis(ctx, op, n, capacity)
-    if big:
-        b.tune(2, 1, 0)
-    b.configure(shift=shift, ortho_mode=mode)
-    b.upload(capi.VEC_W, x)
-    for calls in batches:
-        b.arnoldi_enqueue(calls)
-    st, H = b.arnoldi_projected()
-    out = dict(state=_state(st), lengths=(st.nalpha, st.nbeta), H=H, residue=st.residue, U=_columns(capi, b, st.nvec), w=b.download(capi.VEC_W))
-    return out, b
-
-
-def _two_sweeps_forced():
-    return "EIGENEX_TWO_SWEEPS" in os.environ
-
-
-SCHEMES = {  # name -> (lanczos?, ortho mode name, batches, shifts, complex handles only)
-    "a": (True, "ORTHO_BATCHED", (CALLS,), SHIFTS, False),
-    "b_twice": (True, "ORTHO_BATCHED_TWICE", (CALLS,), SHIFTS, False),
-    "b_seq": (True, "ORTHO_SEQUENTIAL", (CALLS,), SHIFTS, False),
-    "c": (False, "ORTHO_BATCHED", (CALLS,), SHIFTS, False),
-    "d": (False, "ORTHO_BATCHED_ADAPTIVE", (CALLS,), SHIFTS, False),
-    "a_split": (True, "ORTHO_BATCHED", (CALLS // 2, CALLS // 2), (-0.37,), False),
-    "d_split": (False, "ORTHO_BATCHED_ADAPTIVE", (CALLS // 2, CALLS // 2), (-0.37,), False),
-    "e_c": (False, "ORTHO_BATCHED", (CALLS,), (SHIFT_Z,), True),
-    "e_d": (False, "ORTHO_BATCHED_ADAPTIVE", (CALLS,), (SHIFT_Z,), True),
-}
+# the schemes and the two runners: tests/krylov_pass_runs.py, shared with tests/test_gpu_layout_krylov_passes.py
 
 
 def _run_scheme(capi, ctx, h, ops, scheme, batches=None, capacity=CALLS + 1, big=False, seed=7):

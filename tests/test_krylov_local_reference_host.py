@@ -164,3 +164,39 @@ def test_rejects_alpha_taken_as_the_norm_of_the_output():
         n = rows[0].size - 1
         a, b, V = kl.lanczos_fp64(kl.csr_matmul(rows), _start(n, cplx), STEPS - 1, alpha_of=lambda u, v: np.vdot(v, v).real)
         _fails(kl.check_lanczos(rows, 0.0, V, a, b), "lanczos, alpha = |hu|^2")
+
+
+# ---- rows without entries -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cplx", [False, True], ids=["real", "complex"])
+def test_empty_rows_against_a_dense_product_in_longdouble(cplx):
+    """empty first, last and interior rows (two of them adjacent), and an operator without any entry: applied(), csr_matmul() and
+    norm1() against the dense product in long double; an empty row's result is shift u.  On rows that all have entries the
+    results are those of np.add.reduceat over every row start, bit for bit (what the module computed before)."""
+    rs = np.random.RandomState(23)
+    n = 12
+    T = np.clongdouble if cplx else np.longdouble
+    A = rs.standard_normal((n, n)) + (1j * rs.standard_normal((n, n)) if cplx else 0.0)
+    A[rs.uniform(size=(n, n)) < 0.5] = 0.0
+    u = _start(n, cplx, 5)
+    for empty in ([0], [n - 1], [4], [0, 5, 6, n - 1], list(range(n))):
+        B = A.copy()
+        B[empty] = 0.0
+        keep = B != 0
+        rowptr = np.concatenate([[0], np.cumsum(keep.sum(1))]).astype(np.int64)
+        rows = (rowptr, np.nonzero(keep)[1].astype(np.int32), B[keep])
+        assert all(rowptr[i] == rowptr[i + 1] for i in empty)
+        scale = max(float(np.abs(B).sum(1).max()), 1.0) * float(np.abs(u).max())
+        for shift in (0.0, -0.37) + ((SHIFT_Z,) if cplx else ()):
+            want = B.astype(T) @ u.astype(T) + T(shift) * u.astype(T)
+            got = kl.applied(rows, shift, u)
+            assert got.shape == (n,) and got.dtype == T
+            assert np.abs(got - want).max() <= 4 * n * float(np.finfo(np.longdouble).eps) * scale
+            assert np.array_equal(got[empty], T(shift) * u[empty].astype(T))  # exactly shift u
+        got64 = kl.csr_matmul(rows)(u)
+        assert got64.shape == (n,) and not got64[empty].any()
+        assert np.abs(got64 - B @ u).max() <= 4 * n * kl.EPS * scale
+        assert kl.norm1(n, rows[1], rows[2]) == pytest.approx(float(np.abs(B).sum(0).max()), rel=1e-15, abs=0.0)
+    full = kl.dense_to_csr(A)  # every diagonal entry stored: no row is empty
+    prod = full[2].astype(T) * u.astype(T)[full[1]]
+    assert np.array_equal(kl.applied(full, -0.37, u), np.add.reduceat(prod, full[0][:-1]) + T(-0.37) * u.astype(T))
+    assert np.array_equal(kl.csr_matmul(full)(u), np.add.reduceat(full[2] * u[full[1]], full[0][:-1]))
