@@ -486,9 +486,39 @@ __device__ __forceinline__ void lag_apply8(double2 (&u)[4], double2 (&w)[4], dou
   }
 }
 
-template <bool FULL, bool CORRECT>
+// Parked stores (k_sweep<false, true>): a tile's two results wait in LDS, each lane's own eight 16-byte values in its own places
+// (so no barrier stands between parking and release), and go out while the next tile's columns stream: behind the loads of the
+// first column group at which the chip-wide clock (wall_clock64) has entered another slot of 2^shift ticks than the one the tile
+// was parked in.  All workgroups see the same boundaries, so their stores reach HBM together, as one burst per slot instead of a
+// trickle into the read stream (scripts/microbench/sweep_stores.hip, profiles/sweep_stores.md).  Nothing waits: a tile whose
+// successor ends before a boundary has passed goes out then.  The same values to the same addresses as the direct stores; rows
+// are guarded from the parked tile's base.  kernels.hpp (launch_sweep) says when a launch parks.
+struct SweepPark {
+  double2* slots;  // the workgroup's kSweepParkBytes of LDS: [0, 4) column k, [4, 8) w, each kBlock values of 16 bytes
+  int64_t tile;    // the parked tile, or -1; wave-uniform
+  uint64_t slot;   // the clock slot it was parked in
+  int shift;
+};
+__device__ __forceinline__ void sweep_release(SweepPark& pk, double* ukcol, double* w, int64_t n) {
+  const int64_t pbase = pk.tile * kTileRows + 2 * threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t row = pbase + i * (2 * kBlock);
+    if (row < n) {
+      nt_st2(ukcol + row, pk.slots[i * kBlock + threadIdx.x]);
+      nt_st2(w + row, pk.slots[(4 + i) * kBlock + threadIdx.x]);
+    }
+  }
+  pk.tile = -1;
+}
+__device__ __forceinline__ void sweep_release_at_boundary(SweepPark& pk, double* ukcol, double* w, int64_t n) {
+  if (pk.tile >= 0 && (wall_clock64() >> pk.shift) != pk.slot) sweep_release(pk, ukcol, w, n);
+}
+
+template <bool FULL, bool CORRECT, bool PARK = false>
 __device__ __forceinline__ double sweep_tile(const SweepStep& st, double scale, double a, double b, const double* cl, const double* fl,
-                                             double* wave_acc, int64_t base, int64_t n) {
+                                             double* wave_acc, int64_t base, int64_t n, SweepPark* pk = nullptr) {
+  static_assert(!(PARK && CORRECT), "the closing pass stores directly");
   const int lane = threadIdx.x & 63;
   const int k = st.k;
   const double* ukm1 = st.V + (int64_t)(k - 1) * st.ldv;  // only dereferenced for k > 0
@@ -523,6 +553,7 @@ __device__ __forceinline__ double sweep_tile(const SweepStep& st, double scale, 
     load_col<FULL>(x1, st.V + (int64_t)(ci + 1) * st.ldv, base, n);
     load_col<FULL>(x2, st.V + (int64_t)(ci + 2) * st.ldv, base, n);
     load_col<FULL>(x3, st.V + (int64_t)(ci + 3) * st.ldv, base, n);
+    if (PARK) sweep_release_at_boundary(*pk, ukcol, st.w, n);
     if (!CORRECT) {
       double r0, r1, r2, r3, im;
       dotc8<false>(w0, x0, r0, im);
@@ -540,6 +571,7 @@ __device__ __forceinline__ double sweep_tile(const SweepStep& st, double scale, 
   for (; ci < nv; ++ci) {
     double2 x0[4];
     load_col<FULL>(x0, st.V + (int64_t)ci * st.ldv, base, n);
+    if (PARK) sweep_release_at_boundary(*pk, ukcol, st.w, n);
     if (!CORRECT) {
       double r0, im;
       dotc8<false>(w0, x0, r0, im);
@@ -569,6 +601,21 @@ __device__ __forceinline__ double sweep_tile(const SweepStep& st, double scale, 
       if (k > 0) wave_acc[k - 1] += r1;
     }
   }
+  if (PARK) {
+    if (pk->tile >= 0) sweep_release(*pk, ukcol, st.w, n);  // no boundary has passed: the place is needed now
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      pk->slots[i * kBlock + threadIdx.x] = u[i];
+      pk->slots[(4 + i) * kBlock + threadIdx.x] = w[i];
+      const int64_t row = base + i * (2 * kBlock);
+      if (FULL || row < n) {
+        nrm = fma(w[i].x, w[i].x, nrm);
+        nrm = fma(w[i].y, w[i].y, nrm);
+      }
+    }
+    pk->slot = wall_clock64() >> pk->shift;
+    return nrm;  // the caller notes the tile as parked
+  }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int64_t row = base + i * (2 * kBlock);
@@ -584,12 +631,15 @@ __device__ __forceinline__ double sweep_tile(const SweepStep& st, double scale, 
   return nrm;
 }
 
-template <bool CORRECT>
+// PARK (the full sweep only, launch_sweep decides): kSweepParkBytes of parking in front of the sums; park_shift = log2 of the slot
+template <bool CORRECT, bool PARK>
 __global__ __launch_bounds__(kBlock) void k_sweep(SweepStep st, InlineFin fin, int64_t n, int64_t ntiles, double* __restrict__ dpartials,
-                                                  int pstride, double* __restrict__ npartials, const Ctrl* ctrl) {  // no __restrict__: fin.ctrl aliases it
-  extern __shared__ double lds[];  // [4 waves][k+1] sums of d, then c (k+1, c[k] = 0), then f (k+1)
+                                                  int pstride, double* __restrict__ npartials, const Ctrl* ctrl,  // no __restrict__: fin.ctrl aliases it
+                                                  int park_shift) {
+  extern __shared__ __align__(16) double lds_all[];  // PARK: the parked tile; [4 waves][k+1] sums of d, then c (k+1, c[k] = 0), then f (k+1)
   __shared__ double lds4[4];
   if (ctrl->stopped) return;
+  double* lds = lds_all + (PARK ? kSweepParkBytes / (int)sizeof(double) : 0);
   const int k = st.k, nacc = k + 1;
   double* cl = lds + 4 * nacc;
   double* fl = cl + nacc;
@@ -620,13 +670,16 @@ __global__ __launch_bounds__(kBlock) void k_sweep(SweepStep st, InlineFin fin, i
   const double b = k > 0 ? st.beta[k - 1] : 0.0;
   double* wave_acc = lds + (threadIdx.x >> 6) * nacc;
   double nrm = 0.0;
+  SweepPark pk{reinterpret_cast<double2*>(lds_all), -1, 0, park_shift};
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t base = tile * kTileRows + 2 * threadIdx.x;
     if ((tile + 1) * kTileRows <= n)
-      nrm += sweep_tile<true, CORRECT>(st, scale, a, b, cl, fl, wave_acc, base, n);
+      nrm += sweep_tile<true, CORRECT, PARK>(st, scale, a, b, cl, fl, wave_acc, base, n, &pk);
     else
-      nrm += sweep_tile<false, CORRECT>(st, scale, a, b, cl, fl, wave_acc, base, n);
+      nrm += sweep_tile<false, CORRECT, PARK>(st, scale, a, b, cl, fl, wave_acc, base, n, &pk);
+    if (PARK) pk.tile = tile;
   }
+  if (PARK && pk.tile >= 0) sweep_release(pk, const_cast<double*>(st.V) + (int64_t)k * st.ldv, st.w, n);  // nothing stays parked
   if (CORRECT) return;
   __syncthreads();
   for (int c = threadIdx.x; c < nacc; c += kBlock)
@@ -2993,10 +3046,30 @@ void launch_sweep(hipStream_t s, const SweepStep& st, const InlineFin* fin, int6
   const size_t shmem = sizeof(double) * 6 * (size_t)(st.k + 1);
   const InlineFin nofin{nullptr, 0, 0, 0.0, nullptr, nullptr, nullptr};
   const InlineFin f = fin ? *fin : nofin;
-  if (st.correct_only)
-    hipLaunchKernelGGL(k_sweep<true>, dim3(grid), dim3(kBlock), shmem, s, st, f, n, ntiles, dpartials, pstride, npartials, ctrl);
-  else
-    hipLaunchKernelGGL(k_sweep<false>, dim3(grid), dim3(kBlock), shmem, s, st, f, n, ntiles, dpartials, pstride, npartials, ctrl);
+  // EIGENEX_SWEEP_DIRECT_STORES=1: the full sweep stores at each tile's end, as the closing pass does.  EIGENEX_SWEEP_SLOT_SHIFT=s:
+  // slots of 2^s ticks instead of kSweepSlotMicroseconds (measurements; tests: with a large s no boundary ever passes).
+  static const bool direct = getenv("EIGENEX_SWEEP_DIRECT_STORES") != nullptr;
+  static const int shift = [] {
+    if (const char* e = getenv("EIGENEX_SWEEP_SLOT_SHIFT")) return std::min(62, std::max(0, atoi(e)));
+    int dev = 0, khz = 0;  // the chip-wide clock's rate
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;
+    int sh = 0;
+    while (sh < 40 && 1.5 * (double)((uint64_t)1 << sh) < kSweepSlotMicroseconds * 1e-3 * khz) ++sh;  // the nearest power of two
+    return sh;
+  }();
+  if (st.correct_only) {
+    hipLaunchKernelGGL((k_sweep<true, false>), dim3(grid), dim3(kBlock), shmem, s, st, f, n, ntiles, dpartials, pstride, npartials, ctrl, 0);
+  } else if (direct || kSweepParkBytes + shmem + kSweepStaticLds > (size_t)kSweepLdsBudget) {
+    hipLaunchKernelGGL((k_sweep<false, false>), dim3(grid), dim3(kBlock), shmem, s, st, f, n, ntiles, dpartials, pstride, npartials, ctrl, 0);
+  } else {
+    static const bool big_lds = [] {  // more than 64 KB of dynamic LDS has to be asked for once
+      return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 kSweepLdsBudget - kSweepStaticLds) == hipSuccess;
+    }();
+    (void)big_lds;  // a launch the runtime refuses shows in the caller's launch check
+    hipLaunchKernelGGL((k_sweep<false, true>), dim3(grid), dim3(kBlock), kSweepParkBytes + shmem, s, st, f, n, ntiles, dpartials, pstride, npartials,
+                       ctrl, shift);
+  }
 }
 
 void launch_lag_terms(hipStream_t s, int k, const double* dpartials, int pstride, int nblocks, const double* npartials, double* lag,

@@ -194,6 +194,17 @@ struct SweepStep {
   int correct_only;
 };
 // d partials: dpartials[j*pstride + block], j <= k (k_dots' layout); ||w||^2 partials: npartials[block]
+// The full sweep parks each tile's two results in LDS and stores them from the next tile, at a boundary of the chip-wide clock
+// (kernels.hip: SweepPark), when the parking fits beside the 6 (k + 1) doubles of sums and coefficients within kSweepLdsBudget, so
+// that two workgroups per CU still fit; otherwise, in the closing pass and under EIGENEX_SWEEP_DIRECT_STORES=1 (read once per
+// process) every tile stores at its end.  Both paths write the same bytes.
+constexpr int kSweepParkBytes = 2 * kTileRows * (int)sizeof(double);  // 32 KB: column k and w of one tile
+constexpr int kSweepLdsBudget = 80 * 1024;                            // per workgroup: half a CU's LDS
+constexpr int kSweepStaticLds = 4 * (int)sizeof(double);              // k_sweep's block_sum scratch
+// The clock slot: about 80 us (2^13 ticks of the 100 MHz clock).  Measured at 512^3 over k = 0..99 against 2^11..2^16 ticks and no
+// boundary at all (profiles/sweep_stores.md): shorter slots split the workgroups' stores into more and smaller bursts, longer ones
+// let most tiles leave unsynchronised at their successor's end, which gains nothing.  No result depends on it.
+constexpr double kSweepSlotMicroseconds = 80.0;
 void launch_sweep(hipStream_t s, const SweepStep& st, const InlineFin* fin, int64_t n, double* dpartials, int pstride, double* npartials,
                   int grid, const Ctrl* ctrl);
 // behind the full sweep of step k, one workgroup: d_j = sum of its partials (fixed order), beta_k^2 = sum of the norm partials in

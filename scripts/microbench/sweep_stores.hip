@@ -1,0 +1,215 @@
+// What do k_sweep's two stores cost, and is it the instructions or the HBM writes?  A pass with the sweep's stream shape (512 persistent
+// workgroups of 256 threads over 2048-row tiles, four 512-row slices per lane; two vectors loaded plainly at the tile start, ncols
+// columns of 1 GiB in groups of four non-temporal 16-byte loads with one FMA use per value, two vectors written at the tile end, one
+// of them in place), with the stores done in different ways.  All variants run in one process on the same allocations, alternately.
+//   hipcc --offload-arch=gfx950 -O3 scripts/microbench/sweep_stores.hip -o scripts/microbench/sweep_stores
+//   scripts/microbench/sweep_stores [rounds=12]          (runs ncols = 16 and 48; needs 51 GiB of device memory)
+//
+//   A   no stores: the values feed a branch that is never taken
+//   B   direct non-temporal stores at the tile end, as k_sweep issues them
+//   C   the same instructions into 32 KB of scratch per workgroup, which stays in L2; Cp: plain stores there
+//   D   results parked in LDS at the tile end and stored from the next tile, directly behind its first column group's loads
+//   E   parked as in D, released at the first boundary of a chip-wide clock slot that passes (slots of 10.24 us times 1, 2, 4, 8)
+//   Fu  only the column, Fw only the in-place vector, stored directly
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+#define CHK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
+
+constexpr int kBlock = 256, kTileRows = 2048, kGrid = 512;
+enum Mode { kNone, kDirect, kScratch, kParkNext, kParkSlot, kOnlyU, kOnlyW, kScratchPlain };
+
+typedef double v2d_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_cast<const double2*>(p); }
+__device__ __forceinline__ double2 nt_ld2(const double* p) {
+  const v2d_t v = __builtin_nontemporal_load(reinterpret_cast<const v2d_t*>(p));
+  return make_double2(v.x, v.y);
+}
+__device__ __forceinline__ void nt_st2(double* p, double2 v) {
+  v2d_t t;
+  t.x = v.x, t.y = v.y;
+  __builtin_nontemporal_store(t, reinterpret_cast<v2d_t*>(p));
+}
+__device__ __forceinline__ void load_col(double2 (&x)[4], const double* p, int64_t base) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) x[i] = nt_ld2(p + base + i * (2 * kBlock));
+}
+__device__ __forceinline__ void use_col(double2 (&u)[4], double c, const double2 (&x)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    u[i].x = fma(-c, x[i].x, u[i].x);
+    u[i].y = fma(-c, x[i].y, u[i].y);
+  }
+}
+// the parked tile of this lane: its own eight 16-byte values, so no barrier stands between parking and release
+__device__ __forceinline__ void release(const double2* park, double* ucol, double* w, int64_t pbase) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    nt_st2(ucol + pbase + i * (2 * kBlock), park[i * kBlock + threadIdx.x]);
+    nt_st2(w + pbase + i * (2 * kBlock), park[(4 + i) * kBlock + threadIdx.x]);
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_stream(const double* V, int64_t ldv, int ncols, const double* v, double* w, double* ucol,
+                                                   double* scratch, int64_t ntiles, int slot_shift, double* never) {
+  __shared__ double2 park[(MODE == kParkNext || MODE == kParkSlot) ? 8 * kBlock : 1];  // 32 KB
+  const double scale = 0.5, a = 0.25, c = 1e-3, f = 0.125;
+  bool parked = false;
+  int64_t pbase = 0;
+  uint64_t pslot = 0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t base = tile * kTileRows + 2 * threadIdx.x;
+    double2 u[4], s[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t row = base + i * (2 * kBlock);
+      const double2 t = ld2(w + row);
+      u[i] = make_double2(t.x * scale, t.y * scale);
+      s[i] = ld2(v + row);
+      s[i].x = fma(-a, u[i].x, s[i].x);
+      s[i].y = fma(-a, u[i].y, s[i].y);
+    }
+    for (int ci = 0; ci + 4 <= ncols; ci += 4) {
+      double2 x0[4], x1[4], x2[4], x3[4];
+      load_col(x0, V + (int64_t)(ci + 0) * ldv, base);
+      load_col(x1, V + (int64_t)(ci + 1) * ldv, base);
+      load_col(x2, V + (int64_t)(ci + 2) * ldv, base);
+      load_col(x3, V + (int64_t)(ci + 3) * ldv, base);
+      if (MODE == kParkNext && ci == 0 && parked) {
+        release(park, ucol, w, pbase);
+        parked = false;
+      }
+      if (MODE == kParkSlot && parked && (wall_clock64() >> slot_shift) != pslot) {
+        release(park, ucol, w, pbase);
+        parked = false;
+      }
+      use_col(u, c, x0);
+      use_col(u, c, x1);
+      use_col(u, c, x2);
+      use_col(u, c, x3);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      s[i].x = fma(-f, u[i].x, s[i].x);
+      s[i].y = fma(-f, u[i].y, s[i].y);
+    }
+    if (MODE == kNone) {
+      double t = 0.0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) t += (u[i].x + u[i].y) + (s[i].x + s[i].y);
+      if (t == 1.2345e300) never[threadIdx.x] = t;
+    } else if (MODE == kParkNext || MODE == kParkSlot) {
+      if (parked) release(park, ucol, w, pbase);  // never waits: a tile still parked goes out before its place is taken
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        park[i * kBlock + threadIdx.x] = u[i];
+        park[(4 + i) * kBlock + threadIdx.x] = s[i];
+      }
+      parked = true;
+      pbase = base;
+      if (MODE == kParkSlot) pslot = wall_clock64() >> slot_shift;
+    } else {
+      double* du = (MODE == kScratch || MODE == kScratchPlain) ? scratch + (int64_t)blockIdx.x * (2 * kTileRows) + 2 * threadIdx.x : ucol + base;
+      double* dw = (MODE == kScratch || MODE == kScratchPlain) ? du + kTileRows : w + base;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (MODE == kScratchPlain) {
+          *reinterpret_cast<double2*>(du + i * (2 * kBlock)) = u[i];
+          *reinterpret_cast<double2*>(dw + i * (2 * kBlock)) = s[i];
+          continue;
+        }
+        if (MODE != kOnlyW) nt_st2(du + i * (2 * kBlock), u[i]);
+        if (MODE != kOnlyU) nt_st2(dw + i * (2 * kBlock), s[i]);
+      }
+      if (MODE == kOnlyU || MODE == kOnlyW) {  // the vector that is not stored stays alive, with its loads
+        double t = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t += MODE == kOnlyU ? s[i].x + s[i].y : u[i].x + u[i].y;
+        if (t == 1.2345e300) never[threadIdx.x] = t;
+      }
+    }
+  }
+  if ((MODE == kParkNext || MODE == kParkSlot) && parked) release(park, ucol, w, pbase);
+}
+
+__global__ void k_fill(double* p, size_t n, double amp) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    p[i] = amp * (double)((i * 2654435761u >> 7) % 1021) / 1021.0;
+}
+
+struct Variant {
+  const char* name;
+  int mode, shift;
+  std::vector<float> ms;
+};
+
+int main(int argc, char** argv) {
+  const int rounds = argc > 1 ? atoi(argv[1]) : 12;
+  const int maxcols = 48;
+  const size_t col_bytes = (size_t)1 << 30;
+  const int64_t n = col_bytes / 8, ntiles = n / kTileRows;
+  int clock_khz = 0;
+  CHK(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, 0));
+  printf("wall clock %d kHz\n", clock_khz);
+  double *V, *v, *w, *ucol, *scratch, *never;
+  CHK(hipMalloc(&V, col_bytes * maxcols));
+  CHK(hipMalloc(&v, col_bytes));
+  CHK(hipMalloc(&w, col_bytes));
+  CHK(hipMalloc(&ucol, col_bytes));
+  CHK(hipMalloc(&scratch, (size_t)kGrid * 2 * kTileRows * 8));
+  CHK(hipMalloc(&never, kBlock * 8));
+  hipLaunchKernelGGL(k_fill, dim3(4096), dim3(256), 0, 0, V, (size_t)n * maxcols, 1.0);
+  hipLaunchKernelGGL(k_fill, dim3(4096), dim3(256), 0, 0, v, (size_t)n, 1.0);
+  hipLaunchKernelGGL(k_fill, dim3(4096), dim3(256), 0, 0, w, (size_t)n, 1.0);
+  CHK(hipMemset(ucol, 0, col_bytes));
+  CHK(hipDeviceSynchronize());
+  // slots of about 10, 20 and 40 us as powers of two of the clock's ticks
+  int sh10 = 0;
+  while ((1 << sh10) < clock_khz / 100) ++sh10;
+  std::vector<Variant> vs = {{"A  none", kNone, 0, {}},          {"B  direct (k_sweep)", kDirect, 0, {}},
+                             {"C  to L2 scratch", kScratch, 0, {}}, {"D  parked, next tile", kParkNext, 0, {}},
+                             {"E  parked, slot 1x", kParkSlot, sh10, {}}, {"E  parked, slot 2x", kParkSlot, sh10 + 1, {}},
+                             {"E  parked, slot 4x", kParkSlot, sh10 + 2, {}}, {"E  parked, slot 8x", kParkSlot, sh10 + 3, {}},
+                             {"Cp plain stores to L2 scratch", kScratchPlain, 0, {}}, {"Fu column only", kOnlyU, 0, {}},
+                             {"Fw in-place only", kOnlyW, 0, {}}};
+  printf("slot 1x = %.2f us\n", (double)(1 << sh10) / clock_khz * 1e3);
+  hipEvent_t e0, e1;
+  CHK(hipEventCreate(&e0));
+  CHK(hipEventCreate(&e1));
+  for (int ncols : {16, 48}) {
+    for (auto& x : vs) x.ms.clear();
+    for (int r = -2; r < rounds; ++r)  // two warm-up rounds
+      for (auto& x : vs) {
+        (void)hipEventRecord(e0);
+#define LAUNCH(M) hipLaunchKernelGGL(k_stream<M>, dim3(kGrid), dim3(kBlock), 0, 0, V, n, ncols, v, w, ucol, scratch, ntiles, x.shift, never)
+        switch (x.mode) {
+          case kNone: LAUNCH(kNone); break;
+          case kDirect: LAUNCH(kDirect); break;
+          case kScratch: LAUNCH(kScratch); break;
+          case kParkNext: LAUNCH(kParkNext); break;
+          case kParkSlot: LAUNCH(kParkSlot); break;
+          case kOnlyU: LAUNCH(kOnlyU); break;
+          case kScratchPlain: LAUNCH(kScratchPlain); break;
+          default: LAUNCH(kOnlyW); break;
+        }
+#undef LAUNCH
+        (void)hipEventRecord(e1);
+        CHK(hipEventSynchronize(e1));
+        CHK(hipGetLastError());
+        float ms;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        if (r >= 0) x.ms.push_back(ms);
+      }
+    printf("ncols = %d, %d timings each, read %.1f GB\n", ncols, rounds, (double)(ncols + 2) * col_bytes / 1e9);
+    printf("| variant | fastest ms | median ms | slowest ms |\n|---|---|---|---|\n");
+    for (auto& x : vs) {
+      std::sort(x.ms.begin(), x.ms.end());
+      printf("| %s | %.3f | %.3f | %.3f |\n", x.name, x.ms.front(), x.ms[x.ms.size() / 2], x.ms.back());
+    }
+    fflush(stdout);
+  }
+  return 0;
+}
