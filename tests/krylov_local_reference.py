@@ -20,7 +20,12 @@ places); an empty row's sum is zero, so that (H + shift) u is shift u there.
 
 Also the fp64 recurrences that tests/test_krylov_local_reference_host.py runs through the check beside those of
 tests/one_sweep_reference.py (which are real): a two-sweep Lanczos for complex vectors and a plain Arnoldi with one or two
-Gram-Schmidt passes."""
+Gram-Schmidt passes.
+
+The general step (library.hip: enq_orthogonalize over a column set first / stride / count followed by nq orthogonalizing vectors)
+has the same check with the scheme restated: lanczos_columns, check_lanczos_general and check_arnoldi_general below, and the
+fp64 recurrences lanczos_general_fp64 and arnoldi_general_fp64, which take the number-only faults (FAULTS) that
+tests/test_general_step_reference_host.py shows the check to reject."""
 from __future__ import annotations
 
 import numpy as np
@@ -215,6 +220,324 @@ def arnoldi_fp64(apply, x, m, shift=0.0, passes=1, threshold=1e-12, scaled_input
                 w = w - d[j] * V[j]
             h = h + d
         cols.append(h)
+        residue = np.sqrt(np.vdot(w, w).real)
+    nv = len(V)
+    H = np.zeros((nv + 1, nv), cols[0].dtype if cols else np.float64)
+    for k, h in enumerate(cols):
+        H[: k + 1, k] = h
+    for k, c in enumerate(couplings):
+        H[k + 1, k] = c
+    return np.array(V), H, residue, w
+
+
+# ---- the general step: a column set first / stride / count followed by nq orthogonalizing vectors ---------------------------------
+# library.hip: enq_orthogonalize.  Every step is still checked on its own from the stored columns; what is restated is which vectors
+# the step projects out and in which form.  With S vectors m_i in the step's set, c_i the coefficients of every pass and w0 the
+# vector the passes start from,
+#   bound_j = (n + k + nq) eps (|H|_1 + |shift|) max(1, sum_i |c_i| / |w0|_2)
+# (the combination r = w0 - sum c_i m_i rounds every product c_i m_i; for an orthonormal set the factor is at most sqrt(S) per pass,
+# and it is 1 on every case of the pass-mode suites within that factor).  Orthogonality is asserted only where the scheme promises
+# it: every column against every column and every orthogonalizing vector, interval 1, orthonormal Q.
+BATCHED, SEQUENTIAL, TWICE, ADAPTIVE = 0, 1, 2, 3  # capi.ORTHO_*
+ETA2 = 0.5  # the adaptive scheme takes its second pass when |r_1|^2 < ETA2 |w0|^2 (library.hip: InlineDecide.eta2)
+
+
+def lanczos_columns(k, interval, nq):
+    """(the basis columns, the number of orthogonalizing vectors) that Lanczos step k, with k + 1 existing columns, projects out:
+    library.hip, lanczos_columns"""
+    if interval <= 0:
+        return [], 0
+    kmod = (k + 1) % interval
+    return list(range(kmod, k + 1, interval)), (nq if kmod == 0 else 0)
+
+
+def _q_rows(Q, n, dtype=None):
+    Q = np.zeros((0, n)) if Q is None or len(Q) == 0 else np.asarray(Q)
+    assert Q.ndim == 2 and Q.shape[1] == n
+    return Q if dtype is None else Q.astype(dtype)
+
+
+def _norm2(r):
+    return (np.abs(r) ** 2).sum()
+
+
+def _passes(w0, M, mode):
+    """Gram-Schmidt of w0 against the rows of M in the scheme's form, in the precision of its arguments.  Sequential: one
+    projection after another in the order of the rows.  Returns r, the coefficients summed over the passes, sum |c_i| over every
+    pass, and |r_1|^2 / |w0|^2 after the first classical pass (None: sequential, no vector, or w0 = 0)."""
+    S = M.shape[0]
+    csum = np.zeros(S, w0.dtype)
+    if S == 0:
+        return w0, csum, LD(0), None
+    if mode == SEQUENTIAL:
+        r, cabs = w0.copy(), LD(0)
+        for i in range(S):
+            c = (M[i].conj() * r).sum()
+            r = r - c * M[i]
+            csum[i], cabs = c, cabs + abs(c)
+        return r, csum, cabs, None
+    c = M.conj() @ w0
+    r = w0 - c @ M
+    csum, cabs = csum + c, np.abs(c).sum()
+    before, after = _norm2(w0), _norm2(r)
+    if mode == TWICE or (mode == ADAPTIVE and after < LD(ETA2) * before):
+        c = M.conj() @ r
+        r = r - c @ M
+        csum, cabs = csum + c, cabs + np.abs(c).sum()
+    return r, csum, cabs, (float(after / before) if before > 0 else None)
+
+
+def _start_mode(mode):
+    """the start vector has no norm from before the pass: the adaptive scheme deflates it twice (library.hip: Before::Unknown)"""
+    return TWICE if mode == ADAPTIVE else mode
+
+
+class GeneralReport(Report):
+    """Report with a bound per step: steps = [(j, err_diag, err_norm, err_vec, bound, S)], ratio() the worst error / bound over the
+    steps (step_ratio) and the start vector (start_ratio); err_* and bound are those of the worst step; decisions =
+    |r_1|^2 / |w0|^2 per Arnoldi step"""
+
+    def ratio(self):
+        return max(self["step_ratio"], self["start_ratio"])
+
+    def ok(self):
+        return self.ratio() <= 1.0 and self["ortho"] <= self["ortho_bound"]
+
+    def line(self, what=""):
+        return (f"{what}: worst step {self['worst_step']} ({self['worst_set']} vectors): coefficient error {self['err_diag']:.3e}, norm error "
+                f"{self['err_norm']:.3e}, vector error {self['err_vec']:.3e}, bound {self['bound']:.3e}; start vector {self['err_start']:.3e}, bound "
+                f"{self['start_bound']:.3e}; ratio {self.ratio():.3e}; orthogonality {self['ortho']:.3e}, bound {self['ortho_bound']:.3e}")
+
+    def _ratio(self, err, bound):
+        return err / bound if bound > 0 else (0.0 if err == 0 else float("inf"))
+
+    def add(self, j, err_diag, err_norm, err_vec, bound, S):
+        self["steps"].append((j, err_diag, err_norm, err_vec, bound, S))
+        ratio = self._ratio(max(err_diag, err_norm, err_vec), bound)
+        if ratio >= self["step_ratio"]:
+            self.update(step_ratio=ratio, worst_step=j, worst_set=S, err_diag=err_diag, err_norm=err_norm, err_vec=err_vec, bound=bound)
+
+    def start(self, u0, r0, x0, nq):
+        """column 0 against the deflated start vector: max | |r_0| u_0 - r_0 | <= (n + nq) eps |x0|_2"""
+        self["err_start"] = float(np.abs(_norm(r0) * u0 - r0).max())
+        self["start_bound"] = (x0.size + nq) * EPS * float(_norm(x0))
+        self["start_ratio"] = self._ratio(self["err_start"], self["start_bound"])
+
+
+def _general_report(n, k, Uw, Qw, x0, mode, orthonormal):
+    rep = GeneralReport(err_diag=0.0, err_norm=0.0, err_vec=0.0, bound=0.0, step_ratio=0.0, start_ratio=0.0, worst_step=-1, worst_set=0, steps=[], decisions=[],
+                        err_start=0.0, start_bound=0.0, ortho=0.0, ortho_bound=(n + k) * EPS)
+    if x0 is not None and k > 0:
+        x0w = np.asarray(x0).astype(Uw.dtype)
+        rep.start(Uw[0], _passes(x0w, Qw, _start_mode(mode))[0], x0w, Qw.shape[0])
+    if orthonormal and k > 0:
+        rep["ortho"] = float(np.abs(Uw.conj() @ Uw.T - np.eye(k)).max())
+        if Qw.shape[0]:
+            rep["ortho"] = max(rep["ortho"], float(np.abs(Qw.conj() @ Uw.T).max()))
+    return rep
+
+
+def check_lanczos_general(rows, shift, U, Q, alpha, beta, interval=1, mode=BATCHED, x0=None, orthonormal=False):
+    """check_lanczos for any interval, nq orthogonalizing vectors (the rows of Q) and any scheme.  Step j: hu = (H + shift) u_j,
+    w0 = hu - alpha_j u_j - beta_{j-1} u_{j-1} with the recorded coefficients, r = w0 with lanczos_columns(j, interval, nq)
+    projected out in the scheme's form: batched one classical pass, twice a second one on r, sequential one vector after another
+    (columns ascending, then the orthogonalizing vectors), adaptive as batched (a pass with a recurrence is never adaptive).
+    x0: the start vector, for the check of column 0.  orthonormal: Q is orthonormal, so that interval 1 promises orthogonality."""
+    U = np.asarray(U)
+    k, n = U.shape
+    rowptr, col, val = rows
+    T = _wide(val, U, np.asarray(shift), *([] if Q is None else [np.asarray(Q)]), *([] if x0 is None else [np.asarray(x0)]))
+    Uw, Qw = U.astype(T), _q_rows(Q, n, T)
+    nq = Qw.shape[0]
+    base = (n + k + nq) * EPS * (norm1(n, col, val) + abs(complex(shift)))
+    rep = _general_report(n, k, Uw, Qw, x0, mode, orthonormal and interval == 1)
+    step_mode = BATCHED if mode == ADAPTIVE else mode
+    for j in range(min(k, len(alpha))):
+        hu = applied(rows, shift, U[j], T)
+        err_diag = float(abs(LD(alpha[j]) - (Uw[j].conj() * hu).sum().real))
+        err_norm, err_vec, factor, S = 0.0, 0.0, 1.0, 0
+        if j < len(beta):
+            w0 = hu - T(alpha[j]) * Uw[j]
+            if j > 0:
+                w0 = w0 - T(beta[j - 1]) * Uw[j - 1]
+            cols, nqu = lanczos_columns(j, interval, nq)
+            M = np.concatenate([Uw[np.asarray(cols, np.int64)], Qw[:nqu]])
+            r, _, cabs, _ = _passes(w0, M, step_mode)
+            S, nw = M.shape[0], _norm(w0)
+            factor = max(1.0, float(cabs / nw)) if nw > 0 else 1.0
+            err_norm = float(abs(LD(beta[j]) - _norm(r)))
+            if j + 1 < k:
+                err_vec = float(np.abs(LD(beta[j]) * Uw[j + 1] - r).max())
+        rep.add(j, err_diag, err_norm, err_vec, base * factor, S)
+    return rep
+
+
+def check_arnoldi_general(rows, shift, U, Q, H, residue=None, w=None, mode=BATCHED, x0=None, orthonormal=False):
+    """check_arnoldi with nq orthogonalizing vectors and any scheme.  Step j: w0 = hu, the set is the columns 0 .. j and every
+    orthogonalizing vector (sequential: those first); adaptive takes the second pass exactly when |r_1|^2 < 0.5 |hu|^2 in
+    extended precision; H[:j + 1, j] is the sum of the passes' coefficients of the basis columns.  The report's decisions are
+    |r_1|^2 / |hu|^2 per step."""
+    U, H = np.asarray(U), np.asarray(H)
+    k, n = U.shape
+    rowptr, col, val = rows
+    T = _wide(val, U, H, np.asarray(shift), *([] if Q is None else [np.asarray(Q)]), *([] if x0 is None else [np.asarray(x0)]))
+    Uw, Qw = U.astype(T), _q_rows(Q, n, T)
+    nq = Qw.shape[0]
+    base = (n + k + nq) * EPS * (norm1(n, col, val) + abs(complex(shift)))
+    rep = _general_report(n, k, Uw, Qw, x0, mode, orthonormal)
+    for j in range(min(k, H.shape[1])):
+        hu = applied(rows, shift, U[j], T)
+        M, basis = (np.concatenate([Qw, Uw[: j + 1]]), slice(nq, None)) if mode == SEQUENTIAL else (np.concatenate([Uw[: j + 1], Qw]), slice(0, j + 1))
+        r, csum, cabs, decision = _passes(hu, M, mode)
+        rep["decisions"].append(decision)
+        nw = _norm(hu)
+        factor = max(1.0, float(cabs / nw)) if nw > 0 else 1.0
+        err_diag = float(np.abs(H[: j + 1, j].astype(T) - csum[basis]).max())
+        err_norm, err_vec = 0.0, 0.0
+        if j + 1 < k:
+            coupling = T(H[j + 1, j])
+            err_norm = float(abs(coupling - _norm(r)))
+            err_vec = float(np.abs(coupling * Uw[j + 1] - r).max())
+        else:
+            if residue is not None:
+                err_norm = float(abs(LD(residue) - _norm(r)))
+            if w is not None:
+                err_vec = float(np.abs(np.asarray(w).astype(T) - r).max())
+        rep.add(j, err_diag, err_norm, err_vec, base * factor, M.shape[0])
+    return rep
+
+
+# ---- the fp64 recurrences of the general step, with the faults the check must reject ----------------------------------------------
+FAULTS = (
+    "first_plus_one",      # the column set's `first` moved by one (a column beyond the newest is left out)
+    "drop_newest",         # the newest selected column left out
+    "q_every_step",        # Lanczos: the orthogonalizing vectors used on every step
+    "q_no_step",           # the orthogonalizing vectors used on no step after the start
+    "q_reversed",          # sequential: the orthogonalizing vectors projected in reverse order
+    "q_first_flip",        # sequential: orthogonalizing vectors first where they come last, and the other way round
+    "skip_second",         # twice: the second pass omitted
+    "eta_quarter",         # adaptive: the decision taken with 0.25
+    "always_second",       # adaptive: the second pass always taken
+    "never_second",        # adaptive: the second pass never taken
+    "no_conj_q",           # complex: the conjugate dropped on the orthogonalizing vectors' dots
+    "swap_budget",         # a set beyond the dots budget: the coefficients at budget - 1 and budget exchanged
+    "start_not_deflated",  # the start vector not deflated
+)
+
+
+def _gs64(w0, B, Qm, mode, q_first, fault=None, budget=None):
+    """fp64 Gram-Schmidt of w0 against the rows of B (basis columns) and Qm (orthogonalizing vectors) as the device orders them.
+    Returns w and the coefficients of the rows of B summed over the passes."""
+    nb, S = B.shape[0], B.shape[0] + Qm.shape[0]
+    if S == 0:
+        return w0.copy(), np.zeros(0, w0.dtype)
+    M = np.concatenate([B, Qm]).astype(w0.dtype)
+
+    def dots(w):
+        c = M.conj() @ w
+        if fault == "no_conj_q":
+            c[nb:] = M[nb:] @ w
+        if fault == "swap_budget" and budget is not None and S > budget:
+            c[[budget - 1, budget]] = c[[budget, budget - 1]]
+        return c
+
+    if mode == SEQUENTIAL:
+        qs = list(range(nb, S))
+        if fault == "q_reversed":
+            qs.reverse()
+        order = qs + list(range(nb)) if q_first != (fault == "q_first_flip") else list(range(nb)) + qs
+        w, h = w0.copy(), np.zeros(S, w0.dtype)
+        for i in order:
+            h[i] = M[i] @ w if (fault == "no_conj_q" and i >= nb) else np.vdot(M[i], w)
+            w = w - h[i] * M[i]
+        return w, h[:nb]
+    c = dots(w0)
+    w = w0 - c @ M
+    h = c.copy()
+    if mode == TWICE:
+        second = fault != "skip_second"
+    elif mode == ADAPTIVE:
+        eta2 = 0.25 if fault == "eta_quarter" else ETA2
+        second = fault == "always_second" or (fault != "never_second" and np.vdot(w, w).real < eta2 * np.vdot(w0, w0).real)
+    else:
+        second = False
+    if second:
+        c = dots(w)
+        w = w - c @ M
+        h = h + c
+    return w, h[:nb]
+
+
+def _start64(x, Qa, mode, fault, budget):
+    """the start vector deflated by Q in the scheme's form (library.hip: enq_initial_vector)"""
+    dtype = np.result_type(np.asarray(x).dtype, Qa.dtype, np.float64)
+    w = np.asarray(x).astype(dtype)
+    if Qa.shape[0] and fault != "start_not_deflated":
+        w, _ = _gs64(w, Qa[:0], Qa, _start_mode(mode), True, fault, budget)
+    return w
+
+
+def lanczos_general_fp64(apply, x, m, shift=0.0, interval=1, Q=None, mode=BATCHED, fault=None, budget=None, threshold=1e-12):
+    """lanczos_fp64 (m steps: alpha of m + 1, beta of m, m + 1 columns) with the general column set, nq orthogonalizing vectors
+    (rows of Q), the scheme and one of FAULTS.  budget: the vectors one dots launch takes (swap_budget)."""
+    n = np.asarray(x).size
+    Qa = _q_rows(Q, n)
+    nq = Qa.shape[0]
+    step_mode = BATCHED if mode == ADAPTIVE else mode
+    w = _start64(x, Qa, mode, fault, budget)
+    nrm = np.sqrt(np.vdot(w, w).real)
+    V = [w * (1.0 / nrm)]
+    v = apply(V[0]) + shift * V[0]
+    alpha, beta = [np.vdot(V[0], v).real], []
+    for k in range(m):
+        w0 = v - alpha[k] * V[k]
+        if k > 0:
+            w0 = w0 - beta[k - 1] * V[k - 1]
+        cols, nqu = lanczos_columns(k, interval, nq)
+        if fault == "first_plus_one":
+            cols = [c + 1 for c in cols if c + 1 <= k]
+        elif fault == "drop_newest":
+            cols = cols[:-1]
+        elif fault == "q_every_step":
+            nqu = nq
+        elif fault == "q_no_step":
+            nqu = 0
+        B = np.array([V[c] for c in cols]).reshape(len(cols), n)
+        w, _ = _gs64(w0, B, Qa[:nqu], step_mode, False, fault, budget)
+        nrm = np.sqrt(np.vdot(w, w).real)
+        beta.append(nrm)
+        if nrm <= threshold:
+            break
+        V.append(w * (1.0 / nrm))
+        v = apply(V[-1]) + shift * V[-1]
+        alpha.append(np.vdot(V[-1], v).real)
+    return np.array(alpha), np.array(beta), np.array(V)
+
+
+def arnoldi_general_fp64(apply, x, m, shift=0.0, Q=None, mode=BATCHED, fault=None, budget=None, threshold=1e-12):
+    """arnoldi_fp64 (m calls) with nq orthogonalizing vectors, the scheme and one of FAULTS"""
+    n = np.asarray(x).size
+    Qa = _q_rows(Q, n)
+    w = _start64(x, Qa, mode, fault, budget)
+    residue = np.sqrt(np.vdot(w, w).real)
+    V, cols, couplings = [], [], []
+    for k in range(m):
+        if residue <= threshold or k >= n:
+            break
+        if k > 0:
+            couplings.append(residue)
+        V.append(w * (1.0 / residue))
+        v = apply(V[-1]) + shift * V[-1]
+        sel = list(range(k + 1))
+        if fault == "first_plus_one":
+            sel = sel[1:]
+        elif fault == "drop_newest":
+            sel = sel[:-1]
+        B = np.array([V[c] for c in sel]).reshape(len(sel), n)
+        w, h = _gs64(v, B, Qa[:0] if fault == "q_no_step" else Qa, mode, True, fault, budget)
+        col = np.zeros(k + 1, v.dtype)
+        col[sel] = h
+        cols.append(col)
         residue = np.sqrt(np.vdot(w, w).real)
     nv = len(V)
     H = np.zeros((nv + 1, nv), cols[0].dtype if cols else np.float64)

@@ -44,20 +44,23 @@ def two_sweeps_forced():
     return "EIGENEX_TWO_SWEEPS" in os.environ
 
 
-def _basis(capi, ctx, op, n, x, shift, mode, capacity, big, prepare):
-    b = capi.Basis(ctx, op, n, capacity)
+def _basis(capi, ctx, op, n, x, shift, mode, capacity, big, prepare, interval=1, n_ortho=0, fusion=None):
+    b = capi.Basis(ctx, op, n, capacity, n_ortho=n_ortho)
     if big:
         b.tune(2, 1, 0)  # one operator workgroup per CU: the tile loop goes round
-    b.configure(shift=shift, ortho_mode=mode)
+    b.configure(shift=shift, interval=interval, ortho_mode=mode)
+    if fusion is not None:
+        b.set_alpha_fusion(fusion)
     if prepare:
         prepare(b)  # before the start vector goes up: what a test wants in the columns beforehand
     b.upload(capi.VEC_W, x)
     return b
 
 
-def lanczos(capi, ctx, op, n, x, batches, shift, mode, capacity, big=False, prepare=None):
-    """dict(state, alpha, beta, U, repairs, pending) after the batches of lanczos_enqueue calls; pending as the last batch left it"""
-    b = _basis(capi, ctx, op, n, x, shift, mode, capacity, big, prepare)
+def lanczos(capi, ctx, op, n, x, batches, shift, mode, capacity, big=False, prepare=None, **general):
+    """dict(state, alpha, beta, U, repairs, pending) after the batches of lanczos_enqueue calls; pending as the last batch left it.
+    general: interval, n_ortho (prepare uploads VEC_ORTHO(q)) and fusion of tests/test_gpu_general_step_passes.py"""
+    b = _basis(capi, ctx, op, n, x, shift, mode, capacity, big, prepare, **general)
     for calls in batches:
         b.lanczos_enqueue(calls)
     st, alpha, beta = b.lanczos_state()
@@ -66,8 +69,8 @@ def lanczos(capi, ctx, op, n, x, batches, shift, mode, capacity, big=False, prep
     return out, b
 
 
-def arnoldi(capi, ctx, op, n, x, batches, shift, mode, capacity, big=False, prepare=None):
-    b = _basis(capi, ctx, op, n, x, shift, mode, capacity, big, prepare)
+def arnoldi(capi, ctx, op, n, x, batches, shift, mode, capacity, big=False, prepare=None, **general):
+    b = _basis(capi, ctx, op, n, x, shift, mode, capacity, big, prepare, **general)
     for calls in batches:
         b.arnoldi_enqueue(calls)
     st, H = b.arnoldi_projected()
