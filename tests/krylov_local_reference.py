@@ -25,7 +25,12 @@ Gram-Schmidt passes.
 The general step (library.hip: enq_orthogonalize over a column set first / stride / count followed by nq orthogonalizing vectors)
 has the same check with the scheme restated: lanczos_columns, check_lanczos_general and check_arnoldi_general below, and the
 fp64 recurrences lanczos_general_fp64 and arnoldi_general_fp64, which take the number-only faults (FAULTS) that
-tests/test_general_step_reference_host.py shows the check to reject."""
+tests/test_general_step_reference_host.py shows the check to reject.
+
+Restarted states (eigenex_lanczos_restart, eigenex_arnoldi_restart): check_lanczos and check_arnoldi take first = nkeep, the kept
+columns have the relations check_kept_lanczos and check_kept_arnoldi (their bound is derived above them), and thick_restart_fp64 and
+krylov_schur_fp64 are the fp64 recurrences with the number-only faults RESTART_FAULTS that
+tests/test_restart_step_reference_host.py shows the checks to reject."""
 from __future__ import annotations
 
 import numpy as np
@@ -107,15 +112,17 @@ def _norm(r):
     return np.sqrt((np.abs(r) ** 2).sum())
 
 
-def check_lanczos(rows, shift, U, alpha, beta):
+def check_lanczos(rows, shift, U, alpha, beta, first=0):
     """U: the stored columns as rows (k x n); alpha, beta: the recorded series.  Step j is checked as far as it was recorded:
-    alpha_j for j < len(alpha) (and j < k), beta_j for j < len(beta), column j + 1 for j + 1 < k."""
+    alpha_j for j < len(alpha) (and j < k), beta_j for j < len(beta), column j + 1 for j + 1 < k.  first: the steps j < first are
+    skipped (a restarted state: the columns below nkeep are Ritz vectors, and the series below nkeep are not defined);
+    orthogonality is still taken over every column and the bound is the same."""
     U = np.asarray(U)
     k, n = U.shape
     rowptr, col, val = rows
     T = _wide(val, U, np.asarray(shift))
     rep = Report(err_diag=0.0, err_norm=0.0, err_vec=0.0, bound=bound(n, k, norm1(n, col, val), shift), ortho=_orthogonality(U, T), ortho_bound=(n + k) * EPS)
-    for j in range(min(k, len(alpha))):
+    for j in range(first, min(k, len(alpha))):
         hu, c, r = _step(rows, shift, U, j, T)
         rep["err_diag"] = max(rep["err_diag"], float(abs(LD(alpha[j]) - c[j].real)))
         if j < len(beta):
@@ -125,16 +132,17 @@ def check_lanczos(rows, shift, U, alpha, beta):
     return rep
 
 
-def check_arnoldi(rows, shift, U, H, residue=None, w=None):
+def check_arnoldi(rows, shift, U, H, residue=None, w=None, first=0):
     """U: the stored columns as rows (k x n); H: the projected matrix, (k + 1) x k or larger, whose coupling H[j + 1, j] the device
     writes when step j + 1 begins: for the last column the coupling is `residue` and the next column, unnormalised, is `w`
-    (either may be None: not checked)."""
+    (either may be None: not checked).  first: the steps j < first are skipped (a restarted state: first = nkeep; column
+    j >= nkeep of H is still compared on every row i <= j, the rows below nkeep are ordinary coefficients)."""
     U, H = np.asarray(U), np.asarray(H)
     k, n = U.shape
     rowptr, col, val = rows
     T = _wide(val, U, H, np.asarray(shift))
     rep = Report(err_diag=0.0, err_norm=0.0, err_vec=0.0, bound=bound(n, k, norm1(n, col, val), shift), ortho=_orthogonality(U, T), ortho_bound=(n + k) * EPS)
-    for j in range(min(k, H.shape[1])):
+    for j in range(first, min(k, H.shape[1])):
         hu, c, r = _step(rows, shift, U, j, T)
         rep["err_diag"] = max(rep["err_diag"], float(np.abs(H[: j + 1, j].astype(T) - c).max()))
         if j + 1 < k:
@@ -546,3 +554,208 @@ def arnoldi_general_fp64(apply, x, m, shift=0.0, Q=None, mode=BATCHED, fault=Non
     for k, c in enumerate(couplings):
         H[k + 1, k] = c
     return np.array(V), H, residue, w
+
+
+# ---- restarted states: eigenex_lanczos_restart (thick restart) and eigenex_arnoldi_restart (Krylov-Schur) ---------------------
+# A restart keeps the columns Y = V_m C (C = S, eigenvectors of T_m, or Q, an orthonormal basis of an invariant subspace of H_m) and
+# continues with ordinary steps from column nkeep on.  The steps behind it are checked as before with first = nkeep.  The kept
+# columns were made by no step, but they inherit a relation from the steps of the cycle before:
+#
+#   Lanczos    (H + shift) y_e = theta_e y_e + s_e u_m,               s_e = beta_{m-1} S[m-1, e]
+#   Arnoldi    (H + shift) Y   = Y B_top + w q_last^T,                q_last = Q[m-1, :], w the unnormalised residual
+#
+# Derivation of the bound.  Every old step j holds (H + shift) v_j = sum_i T_ij v_i + f_j with a local error |f_j| <= bound
+# (the check above), and y_e = sum_j C_je v_j.  So (H + shift) y_e - sum_i (T C)_ie v_i - (coupling) = sum_j C_je f_j, which is
+# at most bound * sum_j |C_je| entry by entry; forming y_e itself rounds once more per entry (the "1 +"; tests/ritz_reference.py
+# holds that part to its own bound); and T C = C diag(theta) (or C B_top) holds to the small eigenproblem's residual m eps |T|,
+# which multiplies columns of norm one and is below n eps |H|_1, already inside `bound`.  Hence
+#
+#   kept bound = (n + k) eps (|H|_1 + |shift|) (1 + max_e sum_j |C_je|),     k = m + 1 columns of the cycle before
+#
+# (sum_j |C_je| <= sqrt(m) for a unit column).  A restart of a restarted state inherits the same relation: its old columns
+# y_e satisfy it in place of a step's, within the same order.
+class KeptReport(dict):
+    """err, bound and the factor 1 + max_e sum_j |C_je| of a kept relation"""
+
+    def ratio(self):
+        if self["bound"] == 0.0:
+            return 0.0 if self["err"] == 0.0 else float("inf")
+        return self["err"] / self["bound"]
+
+    def ok(self):
+        return self["err"] <= self["bound"]
+
+    def line(self, what=""):
+        return f"{what}: kept relation {self['err']:.3e}, bound {self['bound']:.3e} (factor {self['factor']:.3f}, ratio {self.ratio():.3e})"
+
+
+def _kept_report(err, rows, shift, n, coef, nkeep):
+    rowptr, col, val = rows
+    if coef is None:  # the weights are not known: as if every kept column were one old column
+        factor, k = 2.0, nkeep + 1
+    else:
+        coef = np.asarray(coef)
+        factor, k = 1.0 + float(np.abs(coef).sum(0).max()), coef.shape[0] + 1
+    return KeptReport(err=float(err), factor=factor, bound=bound(n, k, norm1(n, col, val), shift) * factor)
+
+
+def check_kept_lanczos(rows, shift, Y, u, theta, s, coef=None):
+    """max_e max |(H + shift) y_e - theta_e y_e - s_e u| in extended precision.  Y: the kept columns as rows (nkeep x n), u: the
+    residual direction (column nkeep after the restart), theta: their Ritz values, s: their couplings beta_{m-1} S[m-1, e];
+    coef = S (m x nkeep) gives the bound its factor (derivation above)."""
+    Y, u = np.asarray(Y), np.asarray(u)
+    nkeep, n = Y.shape
+    T = _wide(rows[2], Y, u, np.asarray(shift))
+    uw, err = u.astype(T), 0.0
+    for e in range(nkeep):
+        r = applied(rows, shift, Y[e], T) - LD(theta[e]) * Y[e].astype(T) - LD(s[e]) * uw
+        err = max(err, float(np.abs(r).max()))
+    return _kept_report(err, rows, shift, n, coef, nkeep)
+
+
+def check_kept_arnoldi(rows, shift, Y, B_top, w, q_last, coef=None):
+    """max |(H + shift) Y - Y B_top - w q_last^T| in extended precision.  Y: the kept columns as rows (nkeep x n), B_top: nkeep x
+    nkeep, w: the unnormalised residual the restart leaves untouched, q_last = Q[m-1, :] (not conjugated); coef = Q (m x nkeep)
+    gives the bound its factor (derivation above)."""
+    Y, B_top, w, q_last = np.asarray(Y), np.asarray(B_top), np.asarray(w), np.asarray(q_last)
+    nkeep, n = Y.shape
+    T = _wide(rows[2], Y, B_top, w, q_last, np.asarray(shift))
+    Yw, ww, Bw, err = Y.astype(T), w.astype(T), B_top.astype(T), 0.0
+    for e in range(nkeep):
+        r = applied(rows, shift, Y[e], T) - Bw[:, e] @ Yw - T(q_last[e]) * ww
+        err = max(err, float(np.abs(r).max()))
+    return _kept_report(err, rows, shift, n, coef, nkeep)
+
+
+RESTART_FAULTS = (
+    "alpha_from_previous",         # Lanczos: alpha[nkeep] taken from alpha[m - 1]
+    "residual_column_previous",    # Lanczos: column nkeep is u_{m-1}
+    "stale_v",                     # Lanczos: the operator output kept is that of the last kept Ritz vector, not of u_m
+    "second_chunk_repeats_first",  # kept vector E + e built from the coefficients of vector e (E = 16; complex Arnoldi: 8)
+    "last_basis_column_dropped",   # Y = V[:m - 1] C[:m - 1]
+    "kept_columns_not_projected",  # the first step orthogonalises against the columns >= nkeep - 1 only
+    "coupling_overwritten",        # Arnoldi: H[nkeep, nkeep - 1] set to the residue by the first step
+    "coupling_row_conjugated",     # complex Arnoldi: row nkeep of B stored as its conjugate
+)
+
+
+def _kept_columns(V, C, fault, chunk):
+    """Y = C^T V (V: the old columns as rows, C: m x nkeep) with the faults of the combination.  Summed in extended precision and
+    rounded once: the bound of tests/ritz_reference.py is a tight one ((m + 8) u sum |C||V| + 8 u |y| per entry), of which a plain
+    fp64 sum of 24 products uses 0.07 to 0.12 somewhere among 30 000 entries whatever the input; rounded once, at most 1/16."""
+    C = np.array(C)
+    T = _wide(C, V)
+    if fault == "second_chunk_repeats_first":
+        for e in range(chunk, C.shape[1]):
+            C[:, e] = C[:, e - chunk]
+    if fault == "last_basis_column_dropped":
+        C[-1] = 0.0
+    return (C.T.astype(T) @ np.asarray(V).astype(T)).astype(np.result_type(C.dtype, np.asarray(V).dtype))
+
+
+def _mode64(mode):
+    return BATCHED if mode == ADAPTIVE else mode  # Lanczos: a pass with a recurrence is never adaptive
+
+
+def _lanczos_extend64(apply, shift, V, v, alpha, beta, upto, mode_of, threshold, narrow_at=None):
+    """Lanczos steps k = len(V) - 1 .. upto - 1 (full re-orthogonalisation) on lists that grow in place; returns the last v"""
+    for k in range(len(V) - 1, upto):
+        w0 = v - alpha[k] * V[k]
+        if k > 0:
+            w0 = w0 - beta[k - 1] * V[k - 1]
+        lo = k - 1 if narrow_at == k else 0
+        w, _ = _gs64(w0, np.array(V[lo: k + 1]), np.zeros((0, w0.size), w0.dtype), _mode64(mode_of(k)), False)
+        nrm = np.sqrt(np.vdot(w, w).real)
+        beta.append(nrm)
+        if nrm <= threshold:
+            break
+        V.append(w * (1.0 / nrm))
+        v = apply(V[-1]) + shift * V[-1]
+        alpha.append(np.vdot(V[-1], v).real)
+    return v
+
+
+def restart_T(theta, s, alpha, beta, m):
+    """the projected matrix of a restarted cycle as the front-end builds it (thick_restart_lanczos.hpp): diag(theta), the border
+    s in row and column nkeep, and the tridiagonal tail from alpha[nkeep ..] and beta[nkeep ..]; nothing of the series below nkeep"""
+    nkeep = len(theta)
+    T = np.zeros((m, m))
+    T[np.arange(nkeep), np.arange(nkeep)] = theta
+    if 0 < nkeep < m:
+        T[nkeep, :nkeep] = T[:nkeep, nkeep] = s
+    for j in range(nkeep, m):
+        T[j, j] = alpha[j]
+        if j + 1 < m:
+            T[j + 1, j] = T[j, j + 1] = beta[j]
+    return T
+
+
+def thick_restart_fp64(apply, x, m, nkeep, cycles=1, shift=0.0, first=TWICE, rest=BATCHED, fault=None, kept=None, threshold=1e-12):
+    """What the device holds after m + 1 Lanczos calls (scheme `rest`) and then after each of `cycles` thick restarts keeping
+    nkeep Ritz vectors (kept: their indices in ascending Ritz values, default the lowest nkeep) followed by m - nkeep calls, the
+    first in the scheme `first`, the others in `rest`.  Returns a list: [0] = dict(alpha, beta, U); [c] = dict(V: the columns
+    before the restart, theta, S (m x nkeep), s, coupling_last, Y: the nkeep + 1 columns right after it, alpha, beta, U: after the
+    steps).  The series below nkeep are left stale as the device leaves them.  fault: one of RESTART_FAULTS, in every restart."""
+    x = np.asarray(x)
+    nrm = np.sqrt(np.vdot(x, x).real)
+    V = [x * (1.0 / nrm)]
+    v = apply(V[0]) + shift * V[0]
+    alpha, beta = [np.vdot(V[0], v).real], []
+    v = _lanczos_extend64(apply, shift, V, v, alpha, beta, m, lambda k: rest, threshold)
+    out = [dict(alpha=np.array(alpha), beta=np.array(beta), U=np.array(V))]
+    T = restart_T([], [], alpha, beta, m)
+    sel = np.arange(nkeep) if kept is None else np.asarray(kept)
+    for _ in range(cycles):
+        Vold = np.array(V)
+        theta_all, S_all = np.linalg.eigh(T)
+        theta, S = theta_all[sel], np.ascontiguousarray(S_all[:, sel])
+        s = beta[m - 1] * S[m - 1]
+        Y = _kept_columns(Vold[:m], S, fault, 16)
+        u = Vold[m - 1] if fault == "residual_column_previous" else Vold[m]
+        if fault == "stale_v":
+            v = apply(Y[nkeep - 1]) + shift * Y[nkeep - 1]
+        a_m = alpha[m - 1] if fault == "alpha_from_previous" else alpha[m]
+        alpha, beta = list(alpha[:nkeep]) + [a_m], list(beta[: nkeep - 1]) + [s[nkeep - 1]]
+        V = list(Y) + [u]
+        after = np.array(V)
+        v = _lanczos_extend64(apply, shift, V, v, alpha, beta, m, lambda k: first if k == nkeep else rest, threshold,
+                              nkeep if fault == "kept_columns_not_projected" else None)
+        out.append(dict(V=Vold, theta=theta, S=S, s=s, coupling_last=s[nkeep - 1], Y=after, alpha=np.array(alpha), beta=np.array(beta), U=np.array(V)))
+        if nkeep == m or len(V) < m + 1:  # the whole of T was kept (u_m then couples to every column, which no front-end asks
+            break                         # for): one restart; or a breakdown (a fault's): nothing to restart from
+        T = restart_T(theta, s, alpha, beta, m)
+    return out
+
+
+def krylov_schur_fp64(apply, x, m, nkeep, cycles=1, shift=0.0, first=BATCHED, rest=BATCHED, fault=None, threshold=1e-12, basis=None):
+    """What the device holds after m Arnoldi calls and then after each of `cycles` Krylov-Schur restarts keeping nkeep vectors
+    (basis(H_m, nkeep, residue) -> k, Q, B, theta; default krylov_schur_reference.restart_basis, which may move k by one for a
+    conjugate pair on the cut) followed by m - k calls, the first in the scheme `first`, the others in `rest`.  Returns a list:
+    [0] = dict(U, H, residue, w); [c] = dict(V: the columns before the restart, k, Q, B, w0, residue0 (untouched by the restart),
+    Y: the k columns right after it, U, H, residue, w: after the steps).  fault: one of RESTART_FAULTS, in every restart."""
+    if basis is None:
+        from krylov_schur_reference import restart_basis as basis
+    V, H, residue, w = arnoldi_general_fp64(apply, x, m, shift, None, rest, None, None, threshold)
+    out = [dict(U=V, H=H, residue=residue, w=w)]
+    cplx = np.iscomplexobj(V)
+    for _ in range(cycles):
+        Vold, w0, residue0 = V, w, residue
+        k, Q, B, _ = basis(H[:m], nkeep, residue)
+        Y = _kept_columns(Vold, Q, fault, 8 if cplx else 16)
+        Hn = np.zeros((m + 1, m), H.dtype)
+        Hn[: k + 1, :k] = B
+        if fault == "coupling_row_conjugated":
+            Hn[k, :k] = np.conj(B[k])
+        cols = list(Y)
+        for j in range(k, m):
+            if j > k or fault == "coupling_overwritten":
+                Hn[j, j - 1] = residue  # written when step j begins; the first step after a restart leaves B's entry
+            cols.append(w * (1.0 / residue))
+            hv = apply(cols[-1]) + shift * cols[-1]
+            lo = k - 1 if (fault == "kept_columns_not_projected" and j == k) else 0
+            w, h = _gs64(hv, np.array(cols[lo:]), np.zeros((0, hv.size), hv.dtype), first if j == k else rest, True)
+            Hn[lo: j + 1, j] = h
+            residue = np.sqrt(np.vdot(w, w).real)
+        V, H = np.array(cols), Hn
+        out.append(dict(V=Vold, k=k, Q=Q, B=B, w0=w0, residue0=residue0, Y=Y, U=V, H=H, residue=residue, w=w))
+    return out

@@ -63,16 +63,25 @@ def lanczos(capi, ctx, op, n, x, batches, shift, mode, capacity, big=False, prep
     b = _basis(capi, ctx, op, n, x, shift, mode, capacity, big, prepare, **general)
     for calls in batches:
         b.lanczos_enqueue(calls)
+    return lanczos_state(capi, b), b
+
+
+def lanczos_state(capi, b):
+    """the downloaded state of a Lanczos basis, as lanczos() returns it: also between the batches of a test that restarts,
+    clones or reserves in between (tests/test_gpu_restart_steps.py)"""
     st, alpha, beta = b.lanczos_state()
     out = dict(state=state(st), lengths=(st.nalpha, st.nbeta), alpha=alpha, beta=beta, pending=b.close_pending(), repairs=b.repairs())
     out["U"] = columns(capi, b, st.nvec)
-    return out, b
+    return out
 
 
 def arnoldi(capi, ctx, op, n, x, batches, shift, mode, capacity, big=False, prepare=None, **general):
     b = _basis(capi, ctx, op, n, x, shift, mode, capacity, big, prepare, **general)
     for calls in batches:
         b.arnoldi_enqueue(calls)
+    return arnoldi_state(capi, b), b
+
+
+def arnoldi_state(capi, b):
     st, H = b.arnoldi_projected()
-    out = dict(state=state(st), lengths=(st.nalpha, st.nbeta), H=H, residue=st.residue, U=columns(capi, b, st.nvec), w=b.download(capi.VEC_W))
-    return out, b
+    return dict(state=state(st), lengths=(st.nalpha, st.nbeta), H=H, residue=st.residue, U=columns(capi, b, st.nvec), w=b.download(capi.VEC_W))
