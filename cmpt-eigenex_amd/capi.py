@@ -124,6 +124,9 @@ SIGNATURES = {
     "eigenex_spin_momentum64_upload_z": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, C.POINTER(_vp)]),
     "eigenex_spin_momentum_measure": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint64), _dp, _dp]),
     "eigenex_spin_momentum_measure_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_uint64), _dp, _dp]),
+    "eigenex_spin_momentum_site_apply": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp]),
+    "eigenex_spin_momentum_site_apply_z": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "eigenex_spin_momentum_site_apply_host": (C.c_int, [C.c_int] * 7 + [_dp] * 5),
     "eigenex_spin_measure": (C.c_int, [_vp, C.c_int, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_measure_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_measure_host_z": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
@@ -477,6 +480,41 @@ def spin_momentum_measure_host(n_sites: int, n_up: int, momentum: int, x, masks,
     _chk(lib().eigenex_spin_momentum_measure_host(int(n_sites), int(n_up), int(cell), int(momentum), int(is_complex), _d(x.view(np.float64)), n, ptr,
                                                   _d(diag) if n else None, C.byref(norm2)))
     return diag, norm2.value
+
+
+def _cell_coefficients(cell_coef, imaginary="auto"):
+    """cell coefficients as (re, im or None): 48 doubles each, so that the library never reads past what the caller handed over"""
+    coef = np.asarray(cell_coef).reshape(-1)
+    with_im = np.iscomplexobj(coef) if imaginary == "auto" else bool(imaginary)
+    cr, ci = np.zeros(max(48, coef.size)), np.zeros(max(48, coef.size))
+    cr[:coef.size], ci[:coef.size] = coef.real, coef.imag
+    return cr, (ci if with_im else None)
+
+
+def spin_momentum_site_apply_host(n_sites: int, n_up: int, momentum: int, kind: int, cell_coef, p: int, x, cell: int = 1, imaginary="auto",
+                                  in_place: bool = False):
+    """eigenex_spin_momentum_site_apply_host: (y, norm2) of the sum of site operators (kind, cell_coef, p) applied to the vector x of
+    the momentum sector (n_sites, n_up, cell, momentum), n_sites up to 48; y lives in the sector (n_up', (momentum - p) mod N).  x
+    float64: the real form (real momenta and coefficients only); complex128 else.  The definition the device call is held against.
+    in_place hands x over as y (Z with p = 0 only)."""
+    is_complex = np.iscomplexobj(x)
+    x = np.ascontiguousarray(x, np.complex128 if is_complex else np.float64).reshape(-1)
+    cr, ci = _cell_coefficients(cell_coef, imaginary)
+    n_trans = n_sites // cell if cell > 0 and n_sites % cell == 0 else 0
+    dst = None
+    if n_trans and int(kind) in (0, 1, 2):
+        try:  # the library cannot see the lengths; where the sectors do not exist, its own refusal is what the caller gets
+            if x.size != spin_momentum64_dim(n_sites, n_up, momentum, cell):
+                raise ValueError("x needs one entry per row of the source sector")
+            dst = spin_momentum64_dim(n_sites, n_up + (0, 1, -1)[int(kind)], (momentum - p) % n_trans, cell)
+        except EigenexError:
+            dst = None
+    y = x if in_place else np.zeros(dst if dst is not None else 1, x.dtype)
+    norm2 = C.c_double()
+    _chk(lib().eigenex_spin_momentum_site_apply_host(int(n_sites), int(n_up), int(cell), int(momentum), int(kind), int(p), int(is_complex), _d(cr),
+                                                     _d(ci) if ci is not None else None, _d(x.view(np.float64)), _d(y.view(np.float64)),
+                                                     C.byref(norm2)))
+    return y, norm2.value
 
 
 def _mask_list(masks):
@@ -1087,6 +1125,23 @@ class Basis:
         diag, norm2 = np.zeros(n, np.float64), C.c_double()
         _chk(lib().eigenex_spin_momentum_measure(self.h, x_ref, n, ptr, _d(diag) if n else None, C.byref(norm2)))
         return diag, norm2.value
+
+    def spin_momentum_site_apply(self, x_ref, dst, y_ref, kind, cell_coef, p=0, imaginary="auto"):
+        """eigenex_spin_momentum_site_apply (real states) or eigenex_spin_momentum_site_apply_z (complex states, by this state's
+        is_complex): vector y_ref of the state dst, on the momentum sector (n_up', (m - p) mod N) of the same ring, cell and
+        word, = (sum of site operators kind with the cell coefficients cell_coef and the momentum index p) applied to vector x_ref
+        of this state; returns norm2 = |y|^2.  dst may be this state for Z with p = 0 only.  No coefficient, counter or recorded
+        step batch changes."""
+        cr, ci = _cell_coefficients(cell_coef, imaginary)
+        norm2 = C.c_double()
+        if self.is_complex:
+            _chk(lib().eigenex_spin_momentum_site_apply_z(self.h, x_ref, dst.h, y_ref, int(kind), int(p), _d(cr), _d(ci) if ci is not None else None,
+                                                          C.byref(norm2)))
+        else:
+            if ci is not None and np.any(ci != 0.0):
+                raise ValueError("real states take real cell coefficients")
+            _chk(lib().eigenex_spin_momentum_site_apply(self.h, x_ref, dst.h, y_ref, int(kind), int(p), _d(cr), C.byref(norm2)))
+        return norm2.value
 
     def spin_site_apply_z(self, x_ref, dst, y_ref, kind, coef, imaginary="auto"):
         """eigenex_spin_site_apply_z: spin_site_apply for two complex spin states, with real or complex coefficients; returns

@@ -2172,6 +2172,70 @@ __global__ __launch_bounds__(kBlock) void k_spin_momentum_expand(const SpinMomen
 }
 
 // ---------------------------------------------------------------------------
+// A sum of site operators that carries a momentum, from one momentum sector into another (spin_momentum_site.hpp has the
+// definition and SpinMomentumSiteTable; spin_rows.hpp the walk): one row of the DESTINATION sector per lane, 256-row tiles, the
+// persistent grid.  The lane's state is the destination's representative dst_reps[r], one coalesced load; its period comes from
+// one orbit walk.  Everything else is the SOURCE sector's: src_op (geometry, h, steps and the ratio and phase tables, staged in
+// LDS: 9.5 KB / 19.9 KB), src_reps and src_bucket, which the flipped states are searched in.  The coefficient table is read by
+// every lane at the same index (scalar loads).  The sites go kSpinBatch at a time: the orbits, the searches and the gathers of a
+// batch are all issued before its first fma, with the operator kernel's fixed trip counts.  A lane without the term, or whose
+// representative does not carry the source momentum, looks up the source's first row and ignores the value, as expand does, so
+// that no load is branched around and every search stays inside the source list.  Z reads one element and writes the lane's
+// own; where source and destination are one sector (p = 0) that element is the lane's own, so y may be x there -- x and y are
+// not __restrict__ -- and for everything else the caller keeps them apart.  norm2 = sum |y_r|^2 leaves through block_sum into
+// partials[workgroup]; k_spin_measure_reduce adds those in k_reduce_fin's order.  No atomics.  ctrl->stopped is not consulted:
+// this is not a Krylov step.
+// ---------------------------------------------------------------------------
+template <class E, class Word>
+__global__ __launch_bounds__(kBlock) void k_spin_momentum_site_apply(const SpinMomentumSiteTable* __restrict__ tb,
+                                                                     const SpinMomentumViewOf<Word>* __restrict__ src_op,
+                                                                     const Word* __restrict__ src_reps, const uint32_t* __restrict__ src_bucket,
+                                                                     const Word* __restrict__ dst_reps, const typename SpinElement<E>::Stored* x,
+                                                                     typename SpinElement<E>::Stored* y, int64_t n, int64_t ntiles,
+                                                                     double* __restrict__ partials) {
+  __shared__ double lds4[4];
+  __shared__ double tables[SpinMomentumLdsOf<Word>::kSize];
+  spin_stage_momentum_tables(src_op, tables);
+  __syncthreads();
+  const int kind = tb->kind, n_sites = src_op->model.n_sites;
+  const int cell = src_op->cell, n_trans = src_op->n_trans, h = src_op->h, steps = src_op->steps;
+  const Word site_mask = src_op->site_mask, compatible = (Word)tb->compatible, fallback = (Word)tb->first_rep;
+  bool real_coef = true;  // read once, here: the branches on it are uniform; a real vector has no imaginary coefficients
+  if constexpr (std::is_same<E, SpinZ>::value) real_coef = tb->real_coef != 0;
+  const SpinMomentumLookupOf<Word> lk{src_reps, src_bucket};
+  const SpinMomentumLdsOf<Word> tab{tables};
+  const typename SpinElement<E>::Vector xs{x};
+  double nrm = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + threadIdx.x;
+    if (r < n) {
+      const Word s = dst_reps[r];
+      const int period = spin_orbit(s, n_sites, cell, n_trans).period;
+      E yr = E{};
+      if (kind == kSpinSiteZ) {
+        yr = spin_momentum_site_z_row(s, period, n_sites, compatible, fallback, h, steps, lk, SpinSiteCoefficients{tb->half, tb->half_im, real_coef}, xs,
+                                      E{});
+      } else {
+        const Word has = kind == kSpinSitePlus ? s : Word(~s & site_mask);
+        for (int i0 = 0; i0 < n_sites; i0 += kSpinBatch) {
+          bool on[kSpinBatch];
+          uint32_t column[kSpinBatch];
+          int ri[kSpinBatch], li[kSpinBatch];
+          E xv[kSpinBatch];
+          spin_momentum_site_targets(i0, s, has, period, n_sites, cell, n_trans, compatible, fallback, h, steps, lk, on, column, ri, li);
+          spin_momentum_gather(xs, column, xv);
+          yr = spin_momentum_site_add(yr, SpinSiteCoefficients{tb->coef + i0, tb->coef_im + i0, real_coef}, tab, on, ri, li, xv);
+        }
+      }
+      y[r] = spin_stored(yr);
+      nrm = spin_norm_add(nrm, yr);
+    }
+  }
+  nrm = block_sum(nrm, lds4);
+  if (threadIdx.x == 0) partials[blockIdx.x] = nrm;
+}
+
+// ---------------------------------------------------------------------------
 // The reduced density matrix of one vector (spin_rdm.hpp has the definition, the work table and the slicing rule;
 // spin_rdm_rows.hpp the index arithmetic and the panel shape per element, SpinRdmGeometry): rho_A = M M^H with
 // M[a, b] = x[rank(dep_A(a) | dep_B(b))] never stored.  One workgroup per work item (block k, tile pair (ti, tj <= ti), slice
@@ -3407,6 +3471,29 @@ static void spin_momentum_expand_launch(hipStream_t s, const SpinMomentumView* o
 void launch_spin_momentum_expand(hipStream_t s, int es, const SpinMomentumView* op, const SpinSectorView* dst_op, const uint32_t* reps,
                                  const uint32_t* bucket, const double* x, double* y, int64_t n, double* partials, int grid) {
   (es == 2 ? spin_momentum_expand_launch<SpinZ> : spin_momentum_expand_launch<double>)(s, op, dst_op, reps, bucket, x, y, n, partials, grid);
+}
+
+template <class Word>
+static void spin_momentum_site_apply_launch(hipStream_t s, int es, const SpinMomentumSiteTable* table, const SpinMomentumViewOf<Word>* src_op,
+                                            const Word* src_reps, const uint32_t* src_bucket, const Word* dst_reps, const double* x, double* y,
+                                            int64_t n, double* partials, int grid) {
+  const int64_t ntiles = (n + kBlock - 1) / kBlock;
+  if (es == 2)
+    hipLaunchKernelGGL((k_spin_momentum_site_apply<SpinZ, Word>), dim3(grid), dim3(kBlock), 0, s, table, src_op, src_reps, src_bucket, dst_reps,
+                       spin_elements<SpinZ>(x), spin_elements<SpinZ>(y), n, ntiles, partials);
+  else
+    hipLaunchKernelGGL((k_spin_momentum_site_apply<double, Word>), dim3(grid), dim3(kBlock), 0, s, table, src_op, src_reps, src_bucket, dst_reps, x,
+                       y, n, ntiles, partials);
+}
+void launch_spin_momentum_site_apply(hipStream_t s, int es, const SpinMomentumSiteTable* table, const SpinMomentumView* src_op,
+                                     const uint32_t* src_reps, const uint32_t* src_bucket, const uint32_t* dst_reps, const double* x, double* y,
+                                     int64_t n, double* partials, int grid) {
+  spin_momentum_site_apply_launch<uint32_t>(s, es, table, src_op, src_reps, src_bucket, dst_reps, x, y, n, partials, grid);
+}
+void launch_spin_momentum_site_apply(hipStream_t s, int es, const SpinMomentumSiteTable* table, const SpinMomentum64View* src_op,
+                                     const uint64_t* src_reps, const uint32_t* src_bucket, const uint64_t* dst_reps, const double* x, double* y,
+                                     int64_t n, double* partials, int grid) {
+  spin_momentum_site_apply_launch<uint64_t>(s, es, table, src_op, src_reps, src_bucket, dst_reps, x, y, n, partials, grid);
 }
 
 template <class E>

@@ -10,6 +10,7 @@
 #include "spin_rdm.hpp"
 #include "spin_model.hpp"
 #include "spin_momentum.hpp"
+#include "spin_momentum_site.hpp"
 #include "spin_rows.hpp"
 #include "spin_sector.hpp"
 #include "spin_site.hpp"
@@ -425,6 +426,16 @@ void launch_spin_momentum_measure(hipStream_t s, int es, const SpinMomentumMeasu
 // launch_spin_site_apply.  Always runs.
 void launch_spin_momentum_expand(hipStream_t s, int es, const SpinMomentumView* op, const SpinSectorView* dst_op, const uint32_t* reps,
                                  const uint32_t* bucket, const double* x, double* y, int64_t n, double* partials, int grid);
+// A sum of site operators between two momentum sectors (eigenex_spin_momentum_site_apply(_z); spin_momentum_site.hpp has the
+// definition and the table): y, the n rows of the destination sector whose representatives dst_reps are, from x on the rows of
+// the source sector (src_op, src_reps, src_bucket), of either word.  y may be x for Z where the two sectors are one.  The grid's
+// partial sums of |y_r|^2 go to partials[workgroup]; second stage as for launch_spin_site_apply.  Always runs.
+void launch_spin_momentum_site_apply(hipStream_t s, int es, const SpinMomentumSiteTable* table, const SpinMomentumView* src_op,
+                                     const uint32_t* src_reps, const uint32_t* src_bucket, const uint32_t* dst_reps, const double* x, double* y,
+                                     int64_t n, double* partials, int grid);
+void launch_spin_momentum_site_apply(hipStream_t s, int es, const SpinMomentumSiteTable* table, const SpinMomentum64View* src_op,
+                                     const uint64_t* src_reps, const uint32_t* src_bucket, const uint64_t* dst_reps, const double* x, double* y,
+                                     int64_t n, double* partials, int grid);
 // host-operator path: u_out = x*scale
 void launch_scale(hipStream_t s, const double* x, const double* scale_dev, double scale_host, double* out, int64_t n,
                   const Ctrl* ctrl);

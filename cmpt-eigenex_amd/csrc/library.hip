@@ -305,6 +305,7 @@ struct SpinMomentumShard {
   int64_t table_words = 0;  // 4-byte words of reps and bucket together
   int n_sites = 0, n_up = 0, cell = 0, momentum = 0;
   bool wide = false;
+  uint64_t first_rep = 0;  // the state of row 0, which eigenex_spin_momentum_site_apply's table names as the row nobody needs
   bool on() const { return n_sites > 0; }
   SpinMomentumPart<uint32_t>& part(uint32_t) { return part32; }
   SpinMomentumPart<uint64_t>& part(uint64_t) { return part64; }
@@ -3282,6 +3283,7 @@ static int spin_momentum_upload(const std::string& who, int es, eigenex_context_
   s.gshard = c->local[0];
   s.momentum.n_sites = n_sites, s.momentum.n_up = n_up, s.momentum.cell = cell, s.momentum.momentum = momentum;
   s.momentum.wide = sizeof(Word) == 8;
+  s.momentum.first_rep = b.reps[0];
   partition(m->n_global, c->P, s.gshard, &s.rb, &s.re);
   s.nloc = s.re - s.rb;
   s.npad = pad_rows(s.nloc);
@@ -3572,6 +3574,11 @@ static int spin_site_apply_call(const std::string& who, int es, const char* wron
   CHK(enter_settled(src));
   CHK(enter_settled(dst));
   for (eigenex_basis_t b : {src, dst})
+    if (b->csr && b->sh.size() == 1 && b->sh[0].csr && b->sh[0].csr->momentum.on())
+      return fail(EIGENEX_ERR_STATE, who + ": the operator of a state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload) "
+                                           "but a momentum-sector operator, whose rows are orbits: eigenex_spin_momentum_site_apply(_z) applies site "
+                                           "operators there");
+  for (eigenex_basis_t b : {src, dst})
     if (!spin_state_shard(b))
       return fail(EIGENEX_ERR_STATE, who + (b->csr ? ": the operator of a state is not a matrix-free spin operator (eigenex_spin_upload, eigenex_spin_sector_upload)"
                                                    : ": a state has no device operator (a host callback knows no sites)"));
@@ -3617,6 +3624,119 @@ int eigenex_spin_site_apply_z(eigenex_basis_t src, int x_ref, eigenex_basis_t ds
   return spin_site_apply_call("eigenex_spin_site_apply_z", 2,
                               ": complex states only, both of them (eigenex_spin_upload_z, eigenex_spin_sector_upload_z); real states take eigenex_spin_site_apply",
                               src, x_ref, dst, y_ref, kind, coef_re, coef_im, norm2);
+}
+
+// ---- site operators between momentum sectors (spin_momentum_site.hpp), written once for both state words ----
+}  // extern "C"
+// the two sectors of a valid call: the source and the destination the definition wants
+template <class Word>
+static int spin_momentum_site_host(const std::string& who, const SpinMomentumSiteArgs& a, int is_complex, const double* x, double* y, double* norm2) {
+  const std::string why = spin_momentum_site_error<Word>(a);
+  if (!why.empty()) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  if (!is_complex && !spin_momentum_site_is_real(a))
+    return fail(EIGENEX_ERR_ARG, who + ": a real vector takes real source and destination momenta (0 or half the number of translations) and real "
+                                       "coefficients only");
+  if (!x || !y) return fail(EIGENEX_ERR_ARG, who + ": x or y is NULL");
+  if (x == y && !(a.kind == kSpinSiteZ && a.p == 0))
+    return fail(EIGENEX_ERR_ARG, who + ": y may be x for EIGENEX_SPIN_SITE_Z with p = 0 only (everything else reads rows it would have written)");
+  const int n_trans = a.n_sites / a.cell;
+  SpinMomentumBasisOf<Word> src, dst;
+  CHK(spin_momentum_rows(who, a.n_sites, a.n_up, a.cell, a.momentum, &src, nullptr));
+  CHK(spin_momentum_rows(who + " (destination)", a.n_sites, spin_momentum_site_dst_up(a.n_up, a.kind), a.cell,
+                         spin_momentum_site_dst_momentum(n_trans, a.momentum, a.p), &dst, nullptr));
+  std::unique_ptr<SpinMomentumTablesOf<Word>> t(new SpinMomentumTablesOf<Word>());
+  spin_momentum_build_tables(n_trans, a.momentum, *t);
+  SpinMomentumSiteTable table;
+  spin_momentum_site_build_table<Word>(a, src.reps[0], table);
+  spin_momentum_site_apply_host(src, dst, *t, table, is_complex != 0, x, y, norm2);
+  return 0;
+}
+
+// eigenex_spin_momentum_site_apply (es = 1, cell_im NULL) and eigenex_spin_momentum_site_apply_z (es = 2) under the name `who`;
+// `wrong_scalar` is what a state of the other scalar type is told
+static int spin_momentum_site_apply_call(const std::string& who, int es, const char* wrong_scalar, eigenex_basis_t src, int x_ref, eigenex_basis_t dst,
+                                         int y_ref, int kind, int p, const double* cell_re, const double* cell_im, double* norm2) {
+  if (!src || !dst) return fail(EIGENEX_ERR_ARG, who + ": a state is NULL");
+  CHK(enter_settled(src));
+  CHK(enter_settled(dst));
+  for (eigenex_basis_t b : {src, dst}) {
+    if (!b->csr || b->sh.empty() || !b->sh[0].csr || !b->sh[0].csr->momentum.on())
+      return fail(EIGENEX_ERR_STATE, who + ": the operator of a state is not a momentum-sector operator (eigenex_spin_momentum_upload, "
+                                           "eigenex_spin_momentum64_upload); states on Sz-sector operators take eigenex_spin_site_apply");
+    if (b->sh.size() != 1) return fail(EIGENEX_ERR_STATE, who + ": a state has more than one shard; the momentum-sector operators are one shard");
+  }
+  if (src->ctx != dst->ctx) return fail(EIGENEX_ERR_STATE, who + ": the two states live on different contexts");
+  BasisShard &ss = src->sh[0], &sd = dst->sh[0];
+  const SpinMomentumShard &ms = ss.csr->momentum, &md = sd.csr->momentum;
+  if (ms.wide != md.wide)
+    return fail(EIGENEX_ERR_STATE, who + ": one operator has 32-bit states (eigenex_spin_momentum_upload) and the other 64-bit states "
+                                         "(eigenex_spin_momentum64_upload): both must be of one word");
+  if (src->es != es || dst->es != es) return fail(EIGENEX_ERR_STATE, who + wrong_scalar);
+  if (src == dst && !(kind == kSpinSiteZ && p == 0))
+    return fail(EIGENEX_ERR_STATE, who + ": the destination must be a different state: y may be x, or a vector of the same state, for "
+                                         "EIGENEX_SPIN_SITE_Z with p = 0 only");
+  const SpinMomentumSiteArgs a{ms.n_sites, ms.n_up, ms.cell, ms.momentum, kind, p, cell_re, cell_im};
+  const std::string why = ms.wide ? spin_momentum_site_error<uint64_t>(a) : spin_momentum_site_error<uint32_t>(a);
+  if (!why.empty()) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  const int n_trans = ms.n_sites / ms.cell;
+  if (md.n_sites != ms.n_sites || md.cell != ms.cell || md.n_up != spin_momentum_site_dst_up(ms.n_up, kind) ||
+      md.momentum != spin_momentum_site_dst_momentum(n_trans, ms.momentum, p))
+    return fail(EIGENEX_ERR_ARG, who + ": source and destination do not belong together: the destination is the sector of the same n_sites and cell with "
+                                       "n_up (Z), n_up + 1 (PLUS) or n_up - 1 (MINUS) sites up and the momentum (m - p) mod N");
+  const double* x = vec_ptr(ss, src->cap, src->nq, x_ref);
+  double* y = vec_ptr(sd, dst->cap, dst->nq, y_ref);
+  if (!x || !y) return fail(EIGENEX_ERR_ARG, who + ": bad vector reference");
+  eigenex_context_s* c = dst->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  // scratch of this call alone: the table, the grid's partial sums and norm2.  The states' own partials may hold a pending alpha.
+  const int grid = sd.g_spmv;
+  DeviceBuffer<SpinMomentumSiteTable> d_table;
+  DeviceBuffer<double> d_part, d_out;
+  double out = 0.0;
+  HIPCHK(d_table.alloc(1));
+  HIPCHK(d_part.alloc((size_t)grid));
+  HIPCHK(d_out.alloc(1));
+  SpinMomentumSiteTable table;
+  if (ms.wide)
+    spin_momentum_site_build_table<uint64_t>(a, ms.first_rep, table);
+  else
+    spin_momentum_site_build_table<uint32_t>(a, (uint32_t)ms.first_rep, table);
+  HIPCHK(hipMemcpyAsync(d_table, &table, sizeof(SpinMomentumSiteTable), hipMemcpyHostToDevice, c->stream));
+  if (ms.wide)
+    launch_spin_momentum_site_apply(c->stream, es, d_table, ms.part64.view.get(), ms.part64.reps.get(), ms.bucket.get(), md.part64.reps.get(), x, y,
+                                    sd.nloc, d_part, grid);
+  else
+    launch_spin_momentum_site_apply(c->stream, es, d_table, ms.part32.view.get(), ms.part32.reps.get(), ms.bucket.get(), md.part32.reps.get(), x, y,
+                                    sd.nloc, d_part, grid);
+  launch_spin_measure_reduce(c->stream, d_part, grid, grid, 0, 0, nullptr, nullptr, d_out);
+  HIPCHK(hipMemcpyAsync(&out, d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the table and the scratch live until here
+  if (norm2) *norm2 = out;
+  return 0;
+}
+extern "C" {
+
+int eigenex_spin_momentum_site_apply_host(int n_sites, int n_up_src, int cell, int momentum_src, int kind, int p, int is_complex, const double* cell_re,
+                                          const double* cell_im, const double* x, double* y, double* norm2) {
+  const std::string who = "eigenex_spin_momentum_site_apply_host";
+  const SpinMomentumSiteArgs a{n_sites, n_up_src, cell, momentum_src, kind, p, cell_re, cell_im};
+  return n_sites <= SpinWord<uint32_t>::kMaxSites ? spin_momentum_site_host<uint32_t>(who, a, is_complex, x, y, norm2)
+                                                  : spin_momentum_site_host<uint64_t>(who, a, is_complex, x, y, norm2);
+}
+
+int eigenex_spin_momentum_site_apply(eigenex_basis_t src, int x_ref, eigenex_basis_t dst, int y_ref, int kind, int p, const double* cell_coef,
+                                     double* norm2) {
+  return spin_momentum_site_apply_call("eigenex_spin_momentum_site_apply", 1,
+                                       ": real states only, both of them (complex states take eigenex_spin_momentum_site_apply_z)", src, x_ref, dst,
+                                       y_ref, kind, p, cell_coef, nullptr, norm2);
+}
+
+int eigenex_spin_momentum_site_apply_z(eigenex_basis_t src, int x_ref, eigenex_basis_t dst, int y_ref, int kind, int p, const double* cell_re,
+                                       const double* cell_im, double* norm2) {
+  return spin_momentum_site_apply_call("eigenex_spin_momentum_site_apply_z", 2,
+                                       ": complex states only, both of them (eigenex_spin_momentum_upload_z, eigenex_spin_momentum64_upload_z); real "
+                                       "states take eigenex_spin_momentum_site_apply",
+                                       src, x_ref, dst, y_ref, kind, p, cell_re, cell_im, norm2);
 }
 
 int eigenex_spin_rdm_layout(int n_sites, int n_up, uint32_t mask_a, int* n_blocks, int* k_first, int64_t* dims, int64_t* offsets) {

@@ -11,7 +11,8 @@
 //   eigenex_zarnoldi_solver_*  ArnoldiEigenSolver<std::complex<double>>
 // plus eigenex_[z]trlanczos_solver_* (ThickRestartLanczosEigenSolver), eigenex_[z]kschur_solver_* (KrylovSchurEigenSolver) and
 // eigenex_[z]flanczos_solver_* (FilteredLanczosEigenSolver); eigenex_[z]density_solver_* (SpectralDensitySolver);
-// eigenex_spin_dynamics_solver_* (SpinDynamicsSolver); eigenex_spin_entanglement_solver_* (SpinEntanglementSolver);
+// eigenex_spin_dynamics_solver_* (SpinDynamicsSolver); eigenex_spin_momentum_dynamics_solver_* (SpinMomentumDynamicsSolver);
+// eigenex_spin_entanglement_solver_* (SpinEntanglementSolver);
 // eigenex_spin_evolution_solver_* (SpinTimeEvolutionSolver); eigenex_spin_time_correlation_solver_* (SpinTimeCorrelationSolver).
 // Complex data cross this boundary as interleaved (re, im) doubles.
 #include <complex>
@@ -29,6 +30,7 @@
 #include "cmpt/eigen_ex/spectral_density.hpp"
 #include "cmpt/eigen_ex/spin_correlations.hpp"
 #include "cmpt/eigen_ex/spin_dynamics.hpp"
+#include "cmpt/eigen_ex/spin_momentum_dynamics.hpp"
 #include "cmpt/eigen_ex/spin_entanglement.hpp"
 #include "cmpt/eigen_ex/spin_evolution.hpp"
 #include "cmpt/eigen_ex/spin_time_correlation.hpp"
@@ -865,6 +867,7 @@ struct SpinBox {
 struct SpinDynamicsBox : SpinBox<SpinDynamicsSolver> {
   DenseVector<double> state;  // for static_structure_factor_z
 };
+typedef SpinBox<SpinMomentumDynamicsSolver> SpinMomentumDynamicsBox;
 struct SpinEvolutionBox : SpinBox<SpinTimeEvolutionSolver> {
   std::vector<double> out;  // the last vector-valued result, until the next one
 };
@@ -1036,6 +1039,67 @@ int eigenex_spin_dynamics_solver_static_structure_factor_z(void* p, double q, do
     if (sc.info() != Success) throw LanczosException("static_structure_factor_z: " + (sc.log().empty() ? std::string("failed") : sc.log().back()));
     *out = sc.structureFactorZ(q);
   });
+}
+
+// ---- SpinMomentumDynamicsSolver: the model crosses as the arrays of eigenex_spin_momentum_upload
+EIGENEX_SPIN_COMMON(eigenex_spin_momentum_dynamics_solver_, SpinMomentumDynamicsBox)
+int eigenex_spin_momentum_dynamics_solver_set_model(void* p, eigenex_context_t ctx, int n_sites, int n_bonds, const int32_t* site_i, const int32_t* site_j,
+                                                    const double* jz, const double* jxy, const double* hz_or_null, int n_up, int momentum, int cell) {
+  return guard([&] {
+    auto* b = static_cast<SpinMomentumDynamicsBox*>(p);
+    b->ctx = device::Context::borrow(ctx);
+    b->model = spin_model_from_arrays(n_sites, n_bonds, site_i, site_j, jz, jxy, hz_or_null, nullptr);
+    b->n_up = n_up;
+    b->es.setModel(b->ctx, b->model, n_up, momentum, cell);
+  });
+}
+int eigenex_spin_momentum_dynamics_solver_set_state(void* p, const double* v, int64_t n, int is_complex) {
+  return sp_set_state<SpinMomentumDynamicsBox>(p, v, n, is_complex);
+}
+int eigenex_spin_momentum_dynamics_solver_set_state_energy(void* p, double E0) {
+  return guard([&] { static_cast<SpinMomentumDynamicsBox*>(p)->es.setStateEnergy(E0); });
+}
+int eigenex_spin_momentum_dynamics_solver_set_site_operator(void* p, int kind, const double* cell_re, const double* cell_im, int n, int mp) {
+  return guard([&] {
+    std::vector<std::complex<double>> c((size_t)(n > 0 ? n : 0));
+    for (size_t i = 0; i < c.size(); ++i) c[i] = std::complex<double>(cell_re[i], cell_im ? cell_im[i] : 0.0);
+    static_cast<SpinMomentumDynamicsBox*>(p)->es.setSiteOperator(kind, c, mp);
+  });
+}
+int eigenex_spin_momentum_dynamics_solver_set_lanczos_steps(void* p, int64_t m) {
+  return guard([&] { static_cast<SpinMomentumDynamicsBox*>(p)->es.setLanczosSteps((Index)m); });
+}
+int eigenex_spin_momentum_dynamics_solver_compute(void* p) { return guard([&] { static_cast<SpinMomentumDynamicsBox*>(p)->es.compute(); }); }
+int eigenex_spin_momentum_dynamics_solver_compute_structure_factor_z(void* p, int q_index) {
+  return guard([&] { static_cast<SpinMomentumDynamicsBox*>(p)->es.computeStructureFactorZ(q_index); });
+}
+// out[9]: poles, alpha, beta, log lines, info, destination n_up, destination momentum, destination dimension, complex run
+int eigenex_spin_momentum_dynamics_solver_sizes(void* p, int64_t* out) {
+  return guard([&] {
+    auto& es = static_cast<SpinMomentumDynamicsBox*>(p)->es;
+    out[0] = (int64_t)es.poles().size(), out[1] = (int64_t)es.lanczosAlpha().size(), out[2] = (int64_t)es.lanczosBeta().size();
+    out[3] = (int64_t)es.log().size(), out[4] = (int64_t)es.info();
+    out[5] = es.destinationSitesUp(), out[6] = es.destinationMomentum(), out[7] = (int64_t)es.destinationDimension(), out[8] = es.complexRun() ? 1 : 0;
+  });
+}
+// any pointer may be NULL; scalars[3] = (totalWeight, stateEnergy, stateNormSquared)
+int eigenex_spin_momentum_dynamics_solver_get(void* p, double* poles, double* weights, double* alpha, double* beta, double* scalars) {
+  return guard([&] {
+    auto& es = static_cast<SpinMomentumDynamicsBox*>(p)->es;
+    if (poles) std::copy(es.poles().begin(), es.poles().end(), poles);
+    if (weights) std::copy(es.weights().begin(), es.weights().end(), weights);
+    if (alpha) std::copy(es.lanczosAlpha().begin(), es.lanczosAlpha().end(), alpha);
+    if (beta) std::copy(es.lanczosBeta().begin(), es.lanczosBeta().end(), beta);
+    if (scalars) scalars[0] = es.totalWeight(), scalars[1] = es.stateEnergy(), scalars[2] = es.stateNormSquared();
+  });
+}
+int eigenex_spin_momentum_dynamics_solver_spectrum(void* p, const double* omega, int64_t n, double eta, double* out) {
+  return guard([&] {
+    for (int64_t i = 0; i < n; ++i) out[i] = static_cast<SpinMomentumDynamicsBox*>(p)->es.spectrum(omega[i], eta);
+  });
+}
+int eigenex_spin_momentum_dynamics_solver_moment(void* p, int k, double* out) {
+  return guard([&] { *out = static_cast<SpinMomentumDynamicsBox*>(p)->es.moment(k); });
 }
 
 // ---- SpinTimeEvolutionSolver

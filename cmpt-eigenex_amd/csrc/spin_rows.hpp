@@ -1,8 +1,8 @@
 // The row walk of the matrix-free spin-1/2 kernels (kernels.hip: k_spin_spmv<SECTOR, E> and k_spin_measure<SECTOR, E>, each
 // written once for real (E = double) and complex (E = SpinZ) vectors, as k_spin_site_apply<SECTOR, E> is, and through spin_rdm_rows.hpp
-// k_spin_rdm<SECTOR, TILE, E>; at the end of this file the walk of k_spin_momentum_spmv<E> and k_spin_momentum_expand<E>), shared by
-// the device code and by the host replays
-// tests/cpp/spin_{model,sector,measure,site,site_z,rdm,rdm_z,complex,momentum}_sanitize.cpp, which run it under AddressSanitizer +
+// k_spin_rdm<SECTOR, TILE, E>; at the end of this file the walk of k_spin_momentum_spmv<E>, k_spin_momentum_expand<E> and
+// k_spin_momentum_site_apply<E, Word>), shared by the device code and by the host replays
+// tests/cpp/spin_{model,sector,measure,site,site_z,rdm,rdm_z,complex,momentum,momentum_site}_sanitize.cpp, which run it under AddressSanitizer +
 // UBSan.  The kernels and the replays call THESE functions, so what a replay proves about them (every load inside its array, the
 // state equal to spin_sector_unrank, the sums equal to the CSR row loop and to spin_measure_host bit for bit) holds for the
 // kernels' rows as compiled.  No device construct in here: plain C++11.  spin_write_rows, spin_sector_unrank, spin_sector_rank
@@ -193,8 +193,10 @@ struct SpinSiteCoefficients {
   bool real_coef;
 };
 
-// w(s) of Z from the halved coefficients half[i] = c[i] * 0.5: plain additions of sign-flipped constants, sites ascending
-EIGENEX_HD double spin_site_weight(const double* half, int n_sites, uint32_t s) {
+// w(s) of Z from the halved coefficients half[i] = c[i] * 0.5: plain additions of sign-flipped constants, sites ascending.  The
+// state word is a parameter for the 64-bit representatives of a momentum sector (below); uint32_t is the function as it was.
+template <class Word>
+EIGENEX_HD double spin_site_weight(const double* half, int n_sites, Word s) {
   double w = 0.0;
   for (int i = 0; i < n_sites; ++i) {
     const double k = half[i];
@@ -247,8 +249,10 @@ EIGENEX_HD double spin_site_add(double yr, const SpinSiteCoefficients& c, const 
 // Z: the row's weight, of a complex vector the pair (wr, wi) of the two halves of the halved coefficients (wi = 0.0 and not summed
 // with real_coef), then its product with the row's own element, which the caller loads after the weight is formed.  The last
 // argument of spin_site_weights only selects the element.
-EIGENEX_HD double spin_site_weights(const SpinSiteCoefficients& half, int n_sites, uint32_t s, double) { return spin_site_weight(half.re, n_sites, s); }
-EIGENEX_HD SpinZ spin_site_weights(const SpinSiteCoefficients& half, int n_sites, uint32_t s, SpinZ) {
+template <class Word>
+EIGENEX_HD double spin_site_weights(const SpinSiteCoefficients& half, int n_sites, Word s, double) { return spin_site_weight(half.re, n_sites, s); }
+template <class Word>
+EIGENEX_HD SpinZ spin_site_weights(const SpinSiteCoefficients& half, int n_sites, Word s, SpinZ) {
   return SpinZ{spin_site_weight(half.re, n_sites, s), half.real_coef ? 0.0 : spin_site_weight(half.im, n_sites, s)};
 }
 EIGENEX_HD double spin_site_product(double w, bool, double x) { return w * x; }
@@ -439,6 +443,53 @@ EIGENEX_HD void spin_momentum_measure_diagonals(double w, Word s, const uint64_t
   }
   EIGENEX_UNROLL
   for (int t = 0; t < kSpinBatch; ++t) dg[t] = std::fma((double)c[t], w, dg[t]);
+}
+
+// A sum of site operators between two momentum sectors (spin_momentum_site.hpp; kernels.hip: k_spin_momentum_site_apply<E, Word>),
+// one row of the DESTINATION sector per lane: the lane's state is the destination's representative b = reps_dst[r], its period
+// R_b comes from one orbit walk.  Everything that is looked up -- the list of representatives and its buckets (src), h, steps,
+// `compatible`, the ratio and phase tables -- is the SOURCE sector's.  Z is one search and one product
+// (spin_momentum_site_z_row).  PLUS and MINUS take the sites kSpinBatch at a time in the three phases of the operator walk: the
+// row has term i where bit i of `has` is set (has = b for PLUS, ~b & site_mask for MINUS); the flipped state b ^ 1<<i is a state
+// of the source's magnetisation, its orbit is walked -- n_trans rotations on every lane -- and its representative searched with
+// the fixed trip count.  A lane without the term, or whose flipped state has a period that does not carry the source momentum,
+// searches for `fallback`, the source's first row, and its sum ignores what it loaded: no load is branched around, and every
+// state handed to spin_momentum_index is a row of the source list.  (The lane's own state will not do: it is a row of the
+// other sector.)  A lane without the term walks the orbit of its own state, so that ri and li are valid table indices on
+// every lane.  Phase 3 is spin_momentum_expanded on what was loaded -- x times the source phase, then times sqrt(R_b / R_s') --
+// and the fmas of spin_site_add with the site's coefficient.
+template <class Lookup, class Word>
+EIGENEX_HD void spin_momentum_site_targets(int i0, Word s, Word has, int period, int n_sites, int cell, int n_trans, Word compatible, Word fallback,
+                                           int h, int steps, const Lookup& src, bool* on, uint32_t* column, int* ri, int* li) {
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) {
+    const Word bit = Word(1) << (i0 + t);  // i0 < n_sites is a multiple of kSpinBatch: the shift is below the word's bits
+    const bool term = (has & bit) != 0;
+    const SpinOrbitOf<Word> o = spin_orbit(term ? Word(s ^ bit) : s, n_sites, cell, n_trans);
+    on[t] = term && ((compatible >> (o.period - 1)) & 1u) != 0;
+    column[t] = spin_momentum_index(src, on[t] ? o.rep : fallback, h, steps);
+    ri[t] = period * SpinWord<Word>::kRatioPitch + o.period;
+    li[t] = o.j == 0 ? 0 : n_trans - o.j;
+  }
+}
+
+// phase 3, sites ascending
+template <class Tables, class E>
+EIGENEX_HD E spin_momentum_site_add(E yr, const SpinSiteCoefficients& c, const Tables& tb, const bool* on, const int* ri, const int* li, const E* xv) {
+  E xt[kSpinBatch];
+  EIGENEX_UNROLL
+  for (int t = 0; t < kSpinBatch; ++t) xt[t] = spin_momentum_expanded(xv[t], tb.phase_re(li[t]), tb.phase_im(li[t]), tb.ratio(ri[t]));
+  return spin_site_add(yr, c, on, xt);
+}
+
+// Z: w(b) x[idx_src(b)] where b is a row of the source sector too (its period carries the source momentum), else zero
+template <class Lookup, class Vector, class Word, class E>
+EIGENEX_HD E spin_momentum_site_z_row(Word s, int period, int n_sites, Word compatible, Word fallback, int h, int steps, const Lookup& src,
+                                      const SpinSiteCoefficients& half, const Vector& x, E zero) {
+  const bool on = ((compatible >> (period - 1)) & 1u) != 0;
+  const E w = spin_site_weights(half, n_sites, s, zero);
+  const E xv = x(spin_momentum_index(src, on ? s : fallback, h, steps));
+  return on ? spin_site_product(w, half.real_coef, xv) : zero;
 }
 
 }  // namespace eigenex

@@ -164,8 +164,8 @@ class SpinDynamicsSolver {
     return s;
   }
   // the coefficients of the last Lanczos run (of the sin part after computeStructureFactorZ, if it ran)
-  const std::vector<double>& lanczosAlpha() const { return alpha_; }
-  const std::vector<double>& lanczosBeta() const { return beta_; }
+  const std::vector<double>& lanczosAlpha() const { return fraction_.alpha(); }
+  const std::vector<double>& lanczosBeta() const { return fraction_.beta(); }
   int sites() const { return haveModel_ ? model_.sites() : 0; }
   int sitesUp() const { return nUp_; }
   ComputationInfo info() const { return log_.info(); }
@@ -174,7 +174,7 @@ class SpinDynamicsSolver {
  private:
   void begin_(const char* who) {
     log_.begin("SpinDynamicsSolver", who);
-    poles_.clear(), weights_.clear(), alpha_.clear(), beta_.clear();
+    poles_.clear(), weights_.clear(), fraction_.clear();
     total_ = 0.0, E0_ = 0.0, vv_ = 0.0;
   }
   Index invalid_(const std::string& what) {
@@ -255,38 +255,10 @@ class SpinDynamicsSolver {
         detail::applySiteOperatorToUnit(srcDev_.handle(), EIGENEX_VEC_COL(0), dstDev_.handle(), z, kind, model_.sites(), coef, coefIm, vv_);
     if (phi.outcome == detail::SiteApplication::NotFinite) return void(failed_("O|v> is not finite"));
     if (phi.zero()) return log_.note(phi.zeroNote("O|v>", "this part of the response"));
-    const double norm2 = phi.norm2;
-    device::check(eigenex_lanczos_enqueue(dstDev_.handle(), static_cast<int>(m)), "eigenex_lanczos_enqueue");
-    eigenex_state_t st;
-    alpha_.assign(static_cast<std::size_t>(m) + 4, 0.0), beta_.assign(static_cast<std::size_t>(m) + 4, 0.0);
-    device::check(eigenex_lanczos_state(dstDev_.handle(), &st, alpha_.data(), beta_.data()), "eigenex_lanczos_state");
-    const int k = std::min<int>(st.nalpha, static_cast<int>(m));  // a breakdown leaves fewer: the fraction ends there
-    if (k < 1) {
-      failed_("the start vector O|v> failed the breakdown threshold of the Lanczos run");
-      alpha_.clear(), beta_.clear();
-      return;
-    }
-    alpha_.resize(static_cast<std::size_t>(k)), beta_.resize(static_cast<std::size_t>(k - 1));
-    std::vector<double> theta, S;
-    if (!small_eigen::tridiagonal(alpha_.data(), beta_.data(), k, theta, &S)) return void(failed_("the tridiagonal eigenproblem did not converge"));
-    for (int j = 0; j < k; ++j) {
-      const double s0 = S[static_cast<std::size_t>(j) * static_cast<std::size_t>(k)];  // row 0 of column j
-      found_.push_back(std::make_pair(theta[static_cast<std::size_t>(j)] - E0_, norm2 / vv_ * s0 * s0));
-    }
-    parts_ += norm2 / vv_;
-    log_.note("lanczos steps: " + std::to_string(k) + (st.stopped ? " (breakdown: the fraction is complete)" : "") +
-              ", <O^dagger O> of this part: " + std::to_string(norm2 / vv_));
+    fraction_.run(dstDev_.handle(), m, phi.norm2, vv_, E0_, log_);  // the tail every continued fraction shares (spin_frontend.hpp)
   }
 
-  void finish_() {
-    if (info() == Success) {
-      std::stable_sort(found_.begin(), found_.end(), [](const std::pair<double, double>& a, const std::pair<double, double>& b) { return a.first < b.first; });
-      for (const auto& pw : found_) poles_.push_back(pw.first), weights_.push_back(pw.second);
-      total_ = parts_;
-    }
-    found_.clear();
-    parts_ = 0.0;
-  }
+  void finish_() { fraction_.finish(info() == Success, poles_, weights_, total_); }
 
   std::shared_ptr<device::Context> ctx_;
   SpinHalfModel model_;
@@ -303,9 +275,8 @@ class SpinDynamicsSolver {
   const device::CsrOperator* dstDevOp_ = nullptr;
   detail::KrylovDevice srcDev_, dstDev_;
 
-  std::vector<std::pair<double, double>> found_;
-  double parts_ = 0.0;
-  std::vector<double> poles_, weights_, alpha_, beta_;
+  detail::ContinuedFraction fraction_;
+  std::vector<double> poles_, weights_;
   double total_ = 0.0, E0_ = 0.0, vv_ = 0.0;
   detail::CallLog log_;
 };

@@ -4,14 +4,17 @@
 // NOT part of the reference.  Like every public header it calls the C ABI only (eigenex_hip.h).
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "lanczos.hpp"
+#include "small_eigen.hpp"
 #include "spin_operator.hpp"
 
 namespace cmpt {
@@ -140,6 +143,16 @@ struct SiteApplication {
 // an exact zero (Z: half of it; a complex coefficient counts |Re| + |Im|, which bounds what each part of a row sums): a y no
 // larger is a zero, and W is left as it is.  Otherwise W is scaled to unit length -- through V, the scaling kernel is not an
 // in-place one --, whatever the scale of the coefficients: the breakdown threshold of a Lanczos run is an absolute number.
+// what became of y = O x in W of `dst`, |y|^2 in out.norm2, csum the sum of the moduli of the site coefficients: the zero rule
+// and the scaling to unit length
+inline SiteApplication unitOrZero(eigenex_basis_t dst, SiteApplication out, int kind, int sites, double csum, double xNorm2) {
+  if (!std::isfinite(out.norm2)) return out.outcome = SiteApplication::NotFinite, out;
+  const double noise = static_cast<double>(sites) * std::ldexp(1.0, -52) * csum * (kind == EIGENEX_SPIN_SITE_Z ? 0.5 : 1.0);
+  if (out.norm2 <= noise * noise * xNorm2) return out.outcome = out.norm2 == 0.0 ? SiteApplication::ExactZero : SiteApplication::RoundingZero, out;
+  device::check(eigenex_scale(dst, EIGENEX_VEC_V, EIGENEX_VEC_W, 1.0 / std::sqrt(out.norm2)), "eigenex_scale");
+  device::check(eigenex_vec_copy(dst, EIGENEX_VEC_W, EIGENEX_VEC_V), "eigenex_vec_copy");
+  return out;
+}
 inline SiteApplication applySiteOperatorToUnit(eigenex_basis_t src, int xRef, eigenex_basis_t dst, bool complexRun, int kind, int sites,
                                                const std::vector<double>& re, const std::vector<double>* im, double xNorm2) {
   SiteApplication out = {SiteApplication::Unit, 0.0};
@@ -147,17 +160,79 @@ inline SiteApplication applySiteOperatorToUnit(eigenex_basis_t src, int xRef, ei
     device::check(eigenex_spin_site_apply_z(src, xRef, dst, EIGENEX_VEC_W, kind, re.data(), im ? im->data() : nullptr, &out.norm2), "eigenex_spin_site_apply_z");
   else
     device::check(eigenex_spin_site_apply(src, xRef, dst, EIGENEX_VEC_W, kind, re.data(), &out.norm2), "eigenex_spin_site_apply");
-  if (!std::isfinite(out.norm2)) return out.outcome = SiteApplication::NotFinite, out;
   double csum = 0.0;
   for (double c : re) csum += std::fabs(c);
   if (im)
     for (double c : *im) csum += std::fabs(c);
-  const double noise = static_cast<double>(sites) * std::ldexp(1.0, -52) * csum * (kind == EIGENEX_SPIN_SITE_Z ? 0.5 : 1.0);
-  if (out.norm2 <= noise * noise * xNorm2) return out.outcome = out.norm2 == 0.0 ? SiteApplication::ExactZero : SiteApplication::RoundingZero, out;
-  device::check(eigenex_scale(dst, EIGENEX_VEC_V, EIGENEX_VEC_W, 1.0 / std::sqrt(out.norm2)), "eigenex_scale");
-  device::check(eigenex_vec_copy(dst, EIGENEX_VEC_W, EIGENEX_VEC_V), "eigenex_vec_copy");
-  return out;
+  return unitOrZero(dst, out, kind, sites, csum, xNorm2);
 }
+
+// The same between two momentum sectors (eigenex_spin_momentum_site_apply, or _z for a complex run): the operator is a kind, `cell`
+// cell coefficients and the momentum index p (eigenex_hip.h), its site coefficients have the moduli of the cell's, once per
+// translation, so the sum of their moduli is (sites / cell) times the cell's.
+inline SiteApplication applyMomentumSiteOperatorToUnit(eigenex_basis_t src, int xRef, eigenex_basis_t dst, bool complexRun, int kind, int p, int sites,
+                                                       const std::vector<double>& cellRe, const std::vector<double>& cellIm, double xNorm2) {
+  SiteApplication out = {SiteApplication::Unit, 0.0};
+  if (complexRun)
+    device::check(eigenex_spin_momentum_site_apply_z(src, xRef, dst, EIGENEX_VEC_W, kind, p, cellRe.data(), cellIm.data(), &out.norm2),
+                  "eigenex_spin_momentum_site_apply_z");
+  else
+    device::check(eigenex_spin_momentum_site_apply(src, xRef, dst, EIGENEX_VEC_W, kind, p, cellRe.data(), &out.norm2), "eigenex_spin_momentum_site_apply");
+  double csum = 0.0;
+  for (double c : cellRe) csum += std::fabs(c);
+  for (double c : cellIm) csum += std::fabs(c);
+  return unitOrZero(dst, out, kind, sites, csum * static_cast<double>(sites / static_cast<int>(cellRe.size())), xNorm2);
+}
+
+// What follows the start vector of a continued fraction, for every class that runs one (SpinDynamicsSolver,
+// SpinMomentumDynamicsSolver): the unit vector phi / |phi| is in the work vector of `dst`, a state of capacity m + 1 on the
+// destination operator; m Lanczos steps in the library's default scheme, T = S diag(theta) S^T (small_eigen.hpp), and the poles
+// theta_n - E0 with the weights |phi|^2 / <v|v> S(0, n)^2 appended to what earlier parts of the response found.
+class ContinuedFraction {
+ public:
+  void clear() { found_.clear(), alpha_.clear(), beta_.clear(), parts_ = 0.0; }
+  // one part: norm2 = |phi|^2 before it was scaled, vv = <v|v>
+  void run(eigenex_basis_t dst, Index m, double norm2, double vv, double E0, CallLog& log) {
+    device::check(eigenex_lanczos_enqueue(dst, static_cast<int>(m)), "eigenex_lanczos_enqueue");
+    eigenex_state_t st;
+    alpha_.assign(static_cast<std::size_t>(m) + 4, 0.0), beta_.assign(static_cast<std::size_t>(m) + 4, 0.0);
+    device::check(eigenex_lanczos_state(dst, &st, alpha_.data(), beta_.data()), "eigenex_lanczos_state");
+    const int k = std::min<int>(st.nalpha, static_cast<int>(m));  // a breakdown leaves fewer: the fraction ends there
+    if (k < 1) {
+      log.failed("the start vector O|v> failed the breakdown threshold of the Lanczos run");
+      alpha_.clear(), beta_.clear();
+      return;
+    }
+    alpha_.resize(static_cast<std::size_t>(k)), beta_.resize(static_cast<std::size_t>(k - 1));
+    std::vector<double> theta, S;
+    if (!small_eigen::tridiagonal(alpha_.data(), beta_.data(), k, theta, &S)) return void(log.failed("the tridiagonal eigenproblem did not converge"));
+    for (int j = 0; j < k; ++j) {
+      const double s0 = S[static_cast<std::size_t>(j) * static_cast<std::size_t>(k)];  // row 0 of column j
+      found_.push_back(std::make_pair(theta[static_cast<std::size_t>(j)] - E0, norm2 / vv * s0 * s0));
+    }
+    parts_ += norm2 / vv;
+    log.note("lanczos steps: " + std::to_string(k) + (st.stopped ? " (breakdown: the fraction is complete)" : "") +
+             ", <O^dagger O> of this part: " + std::to_string(norm2 / vv));
+  }
+  // the parts merged into ascending poles, if the call succeeded; what was found is dropped either way
+  void finish(bool success, std::vector<double>& poles, std::vector<double>& weights, double& total) {
+    if (success) {
+      std::stable_sort(found_.begin(), found_.end(), [](const std::pair<double, double>& a, const std::pair<double, double>& b) { return a.first < b.first; });
+      for (const auto& pw : found_) poles.push_back(pw.first), weights.push_back(pw.second);
+      total = parts_;
+    }
+    found_.clear();
+    parts_ = 0.0;
+  }
+  // the coefficients of the last run
+  const std::vector<double>& alpha() const { return alpha_; }
+  const std::vector<double>& beta() const { return beta_; }
+
+ private:
+  std::vector<std::pair<double, double>> found_;
+  double parts_ = 0.0;
+  std::vector<double> alpha_, beta_;
+};
 
 // The masks of the sites, and of the pairs i < j with i ascending and j ascending within i, appended to `masks`
 template <class Word>

@@ -85,7 +85,19 @@ def lib():
             getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
             getattr(L, p + "log_line").restype = C.c_char_p
         _ip32 = C.POINTER(C.c_int32)
-        for kind in ("dynamics", "evolution", "time_correlation", "entanglement"):
+        p = "eigenex_spin_momentum_dynamics_solver_"
+        getattr(L, p + "set_model").argtypes = [_vp, _vp, C.c_int, C.c_int, _ip32, _ip32, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int]
+        getattr(L, p + "set_state").argtypes = [_vp, _dp, C.c_int64, C.c_int]
+        getattr(L, p + "set_state_energy").argtypes = [_vp, C.c_double]
+        getattr(L, p + "set_site_operator").argtypes = [_vp, C.c_int, _dp, _dp, C.c_int, C.c_int]
+        getattr(L, p + "set_lanczos_steps").argtypes = [_vp, C.c_int64]
+        getattr(L, p + "compute").argtypes = [_vp]
+        getattr(L, p + "compute_structure_factor_z").argtypes = [_vp, C.c_int]
+        getattr(L, p + "sizes").argtypes = [_vp, _lp]
+        getattr(L, p + "get").argtypes = [_vp, _dp, _dp, _dp, _dp, _dp]
+        getattr(L, p + "spectrum").argtypes = [_vp, _dp, C.c_int64, C.c_double, _dp]
+        getattr(L, p + "moment").argtypes = [_vp, C.c_int, _dp]
+        for kind in ("dynamics", "momentum_dynamics", "evolution", "time_correlation", "entanglement"):
             p = f"eigenex_spin_{kind}_solver_"
             getattr(L, p + "create").argtypes = []
             getattr(L, p + "create").restype = _vp
@@ -839,6 +851,53 @@ class SpinDynamicsSolver(_SpinSolverBase):
         v = C.c_double()
         _chk(self._f("static_structure_factor_z")(self.h, float(q), C.byref(v)))
         return v.value
+
+
+class SpinMomentumDynamicsSolver(SpinDynamicsSolver):
+    """SpinMomentumDynamicsSolver (spin_momentum_dynamics.hpp): dynamical spin correlations of a state of one momentum sector, the
+    continued fraction run in the momentum sector the site operator leads to (rings of up to 48 sites).  The model is
+    (n_sites, bonds, hz) with bonds = [(i, j, Jz, Jxy), ...], the state lives in the sector (n_up, momentum, cell)."""
+
+    _names = ("npoles", "nalpha", "nbeta", "nlog", "info", "destinationSitesUp", "destinationMomentum", "destinationDimension", "complexRun")
+    _prefix = "eigenex_spin_momentum_dynamics_solver_"
+
+    def setModel(self, ctx: capi.Context, n_sites, bonds, n_up, momentum, hz=None, cell=1):
+        i32 = C.POINTER(C.c_int32)
+        si = np.ascontiguousarray([b[0] for b in bonds], np.int32)
+        sj = np.ascontiguousarray([b[1] for b in bonds], np.int32)
+        jz = np.ascontiguousarray([b[2] for b in bonds], np.float64)
+        jxy = np.ascontiguousarray([b[3] for b in bonds], np.float64)
+        fz = None if hz is None else np.ascontiguousarray(hz, np.float64)
+        self._keep.append(ctx)
+        self._sites = int(n_sites)
+        _chk(self._f("set_model")(self.h, ctx.h, int(n_sites), si.size, si.ctypes.data_as(i32), sj.ctypes.data_as(i32), _d(jz), _d(jxy),
+                                  None if fz is None else _d(fz), int(n_up), int(momentum), int(cell)))
+        return self
+
+    def setState(self, v):
+        """a real or a complex state over the rows of the momentum sector"""
+        cplx = np.iscomplexobj(v)
+        a = np.ascontiguousarray(v, np.complex128 if cplx else np.float64)
+        _chk(self._f("set_state")(self.h, _d(a.view(np.float64)), a.size, int(cplx)))
+        return self
+
+    def setSiteOperator(self, kind, cell_coef, p):
+        """one real or complex coefficient per site of the cell, and the momentum index p of the operator"""
+        c = np.asarray(cell_coef).reshape(-1)
+        cr, ci = np.ascontiguousarray(c.real, np.float64), np.ascontiguousarray(c.imag, np.float64)
+        _chk(self._f("set_site_operator")(self.h, int(kind), _d(cr), _d(ci), cr.size, int(p)))
+        return self
+
+    def computeStructureFactorZ(self, q_index):
+        """Szz(q, w) at q = 2 pi q_index / n_sites"""
+        _chk(self._f("compute_structure_factor_z")(self.h, int(q_index)))
+        return self
+
+    def computeStructureFactorZSingleRun(self, q):
+        raise AttributeError("SpinMomentumDynamicsSolver runs one fraction per call: computeStructureFactorZ(q_index)")
+
+    def staticStructureFactorZ(self, q):
+        raise AttributeError("SpinMomentumDynamicsSolver: the static value is SpinMomentumCorrelationSolver's, or totalWeight")
 
 
 class SpinTimeEvolutionSolver(_SpinEvolvingSolverBase):

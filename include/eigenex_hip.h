@@ -375,7 +375,8 @@ int eigenex_spin_sector_upload_z(eigenex_context_t ctx, int n_sites, int n_up, i
  *                                   is reduced in a fixed order without atomics.  Synchronises once.
  * All argument checks -- geometry, model, and a complex momentum given to eigenex_spin_momentum_upload -- happen before the context
  * is touched.  A row of a momentum handle is an orbit, not a state: eigenex_spin_geometry, eigenex_spin_measure, eigenex_spin_rdm(_z)
- * and eigenex_spin_site_apply(_z) refuse it as they refuse every handle that is not theirs; expand first. */
+ * and eigenex_spin_site_apply(_z) refuse it as they refuse every handle that is not theirs; expand first, or apply site operators
+ * in the momentum basis (eigenex_spin_momentum_site_apply, below). */
 int eigenex_spin_momentum_dim(int n_sites, int n_up, int cell, int momentum, int64_t* dim);
 int eigenex_spin_momentum_states(int n_sites, int n_up, int cell, int momentum, int64_t first, int64_t count, uint32_t* states,
                                  uint8_t* periods_or_null);
@@ -445,6 +446,49 @@ int eigenex_spin_momentum64_upload_z(eigenex_context_t ctx, int n_sites, int n_u
 int eigenex_spin_momentum_measure(eigenex_basis_t basis, int x_ref, int n_diag, const uint64_t* masks, double* diag_out, double* norm2);
 int eigenex_spin_momentum_measure_host(int n_sites, int n_up, int cell, int momentum, int is_complex, const double* x, int n_diag,
                                        const uint64_t* masks, double* diag_out, double* norm2);
+/* A sum of site operators that carries a momentum, from one momentum sector into another, without expanding: O_q |psi_k> lies in
+ * the sector k - q.  NOT part of the reference.  Conventions as above: L = n_sites, cell a, N = L / a, sector (L, n_up, a, m).
+ *   input       the source sector, a kind (EIGENEX_SPIN_SITE_Z / _PLUS / _MINUS), p in 0..N-1 and `cell` complex cell coefficients
+ *               cc[j] = (cell_re[j], cell_im[j]); cell_im NULL means zeros.
+ *   sites       c[j + a r] = cc[j] * u[r] (a plain complex multiply without contraction), u[r] = e^{+2 pi i ((p r) mod N) / N}, taken
+ *               from the phase table of momentum p: exactly 1, i, -1, -i at quarter turns.  O = sum_i c[i] S^kind_i obeys
+ *               T O T^-1 = e^{-2 pi i p / N} O.  Site coefficients are never given one by one.
+ *   destination n_up' = n_up (Z), n_up + 1 (PLUS), n_up - 1 (MINUS); m' = (m - p + N) mod N.  Both sectors must have rows.
+ *   row b       of the destination, b a representative with period R_b; idx, ratio = sqrt(R / R') and phase are the SOURCE's.
+ *               Z: y_b = w(b) x[idx(b)] if (m R_b) mod N == 0, else 0; w(b) as in eigenex_spin_site_apply(_z) from c[i] * 0.5.
+ *               PLUS / MINUS: y_b = 0, then for i ascending over the sites up (PLUS) or down (MINUS) in b, with s' = b ^ (1 << i),
+ *               T^{j*} s' = rep(s'), l = (N - j*) mod N, and only if (m R_s') mod N == 0:
+ *               xt = (x[idx(rep(s'))] * phase[l]) * sqrt((double)R_b / (double)R_s') -- the product a plain complex multiply (of a real
+ *               vector x * phase.re), then each part scaled -- and y_b takes eigenex_spin_site_apply_z's fmas with c[i]:
+ *               y.re = fma(c.re, xt.re, y.re), y.re = fma(-c.im, xt.im, y.re), y.im = fma(c.re, xt.im, y.im), y.im = fma(c.im, xt.re,
+ *               y.im), the second of each pair not when every c[i].im is zero.
+ *   norm2       sum_b |y_b|^2, the fma of the real part, then of the imaginary part, rows ascending (may be NULL)
+ *   identity    expand(y) = (sum_i c[i] S^kind_i) expand(x), with the per-site c[i] given to eigenex_spin_site_apply_z.
+ *   real form   m and m' real momenta and every coefficient real: every phase is +-1 or 0 and x and y may be real vectors; each part
+ *               of the complex result equals the real call on that part.
+ *   eigenex_spin_momentum_site_apply_host  the definition in host code (n_sites 2..48; 32-bit states up to 32 sites, 64-bit
+ *                                   above, with equal results): x holds 1 (is_complex = 0; the real form only) or 2 doubles per
+ *                                   row of the source, y per row of the destination.  y may be x for Z with p = 0 only.
+ *   eigenex_spin_momentum_site_apply     on the device, for two real states; cell_coef holds `cell` doubles.
+ *   eigenex_spin_momentum_site_apply_z   on the device, for two complex states; cell_im may be NULL.
+ *                                   src and dst are states of one context, both on handles of eigenex_spin_momentum_upload(_z) or
+ *                                   both on handles of eigenex_spin_momentum64_upload(_z), with the same n_sites and cell and
+ *                                   dst's (n_up, momentum) = (n_up', m'), all read from eigenex_spin_momentum_geometry; the two
+ *                                   models need not agree.  The intended y_ref is EIGENEX_VEC_W of dst.  EIGENEX_ERR_STATE: a
+ *                                   handle that is no momentum handle, two contexts, two word widths, a state of the other scalar
+ *                                   type (the message names the other call), and dst == src for anything but Z with p = 0, where
+ *                                   y may be x.  EIGENEX_ERR_ARG: a kind or p out of range, a non-finite coefficient, a
+ *                                   destination n_up outside 0..n_sites, sectors that do not belong together.  All of it before
+ *                                   anything is allocated.  One launch and a fixed-order reduction without atomics:
+ *                                   y is bit-identical to the host function's.  Synchronises once.  No coefficient, counter or
+ *                                   recorded step batch of either state is touched.
+ * eigenex_spin_site_apply(_z) keep refusing momentum handles; their message names these calls. */
+int eigenex_spin_momentum_site_apply(eigenex_basis_t src_basis, int x_ref, eigenex_basis_t dst_basis, int y_ref, int kind, int p,
+                                     const double* cell_coef, double* norm2);
+int eigenex_spin_momentum_site_apply_z(eigenex_basis_t src_basis, int x_ref, eigenex_basis_t dst_basis, int y_ref, int kind, int p,
+                                       const double* cell_re, const double* cell_im, double* norm2);
+int eigenex_spin_momentum_site_apply_host(int n_sites, int n_up_src, int cell, int momentum_src, int kind, int p, int is_complex,
+                                          const double* cell_re, const double* cell_im, const double* x, double* y, double* norm2);
 /* Spin correlations of a real vector x over the rows of a matrix-free spin operator, all terms in one sweep: x is read once
  * per 16 terms of each list and nothing is written but the sums.  A measurement is two lists of 32-bit site masks (bit i = site
  * i); with sigma_i(s) as above it yields the raw, unnormalised sums
