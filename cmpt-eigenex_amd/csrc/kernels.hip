@@ -486,38 +486,60 @@ __device__ __forceinline__ void lag_apply8(double2 (&u)[4], double2 (&w)[4], dou
   }
 }
 
-// Parked stores (k_sweep<false, true>): a tile's two results wait in LDS, each lane's own eight 16-byte values in its own places
-// (so no barrier stands between parking and release), and go out while the next tile's columns stream: behind the loads of the
-// first column group at which the chip-wide clock (wall_clock64) has entered another slot of 2^shift ticks than the one the tile
-// was parked in.  All workgroups see the same boundaries, so their stores reach HBM together, as one burst per slot instead of a
-// trickle into the read stream (scripts/microbench/sweep_stores.hip, profiles/sweep_stores.md).  Nothing waits: a tile whose
-// successor ends before a boundary has passed goes out then.  The same values to the same addresses as the direct stores; rows
-// are guarded from the parked tile's base.  kernels.hpp (launch_sweep) says when a launch parks.
+// Parked stores (k_sweep<false, DEPTH> with DEPTH 1 or 2): a tile's two results wait in LDS, each lane's own eight 16-byte values in
+// its own places (so no barrier stands between parking and release), and go out while later tiles' columns stream: behind the loads
+// of the first column group at which the chip-wide clock (wall_clock64) has entered another slot of 2^shift ticks than the one the
+// oldest parked tile was parked in.  All workgroups see the same boundaries, so their stores reach HBM together, as one burst per
+// slot instead of a trickle into the read stream (scripts/microbench/sweep_stores.hip, profiles/sweep_stores.md,
+// profiles/sweep_park_depth.md).  The parking is a queue of DEPTH tiles: a boundary releases all of them, oldest first; nothing
+// waits: a tile that finds the queue full at its end sends the oldest out then.  The same values to the same addresses as the
+// direct stores; rows are guarded from each parked tile's own base.  kernels.hpp (launch_sweep) says when and how deep a launch parks.
+template <int DEPTH>
 struct SweepPark {
-  double2* slots;  // the workgroup's kSweepParkBytes of LDS: [0, 4) column k, [4, 8) w, each kBlock values of 16 bytes
-  int64_t tile;    // the parked tile, or -1; wave-uniform
-  uint64_t slot;   // the clock slot it was parked in
+  static_assert(DEPTH == 1 || DEPTH == 2, "one or two parked tiles");
+  double2* slots;     // the workgroup's DEPTH * kSweepParkBytes of LDS: [DEPTH][8][kBlock], per place [0, 4) column k, [4, 8) w
+  int64_t tile[2];    // the parked tiles, oldest first, or -1; wave-uniform, as everything below
+  uint64_t slot[2];   // the clock slots they were parked in; the oldest's decides for all
+  int head;           // the place of the oldest; the newer one (DEPTH 2) lies at the other place
   int shift;
+  __device__ __forceinline__ bool full() const { return tile[DEPTH - 1] >= 0; }
+  __device__ __forceinline__ double2* free_place() const { return slots + (tile[0] < 0 ? head : head ^ 1) * (8 * kBlock); }
+  __device__ __forceinline__ void note(int64_t t, uint64_t sl) {  // behind the values written to free_place()
+    if (tile[0] < 0)
+      tile[0] = t, slot[0] = sl;
+    else
+      tile[1] = t, slot[1] = sl;
+  }
 };
-__device__ __forceinline__ void sweep_release(SweepPark& pk, double* ukcol, double* w, int64_t n) {
-  const int64_t pbase = pk.tile * kTileRows + 2 * threadIdx.x;
+template <int DEPTH>
+__device__ __forceinline__ void sweep_release_oldest(SweepPark<DEPTH>& pk, double* ukcol, double* w, int64_t n) {
+  const double2* from = pk.slots + pk.head * (8 * kBlock);
+  const int64_t pbase = pk.tile[0] * kTileRows + 2 * threadIdx.x;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int64_t row = pbase + i * (2 * kBlock);
     if (row < n) {
-      nt_st2(ukcol + row, pk.slots[i * kBlock + threadIdx.x]);
-      nt_st2(w + row, pk.slots[(4 + i) * kBlock + threadIdx.x]);
+      nt_st2(ukcol + row, from[i * kBlock + threadIdx.x]);
+      nt_st2(w + row, from[(4 + i) * kBlock + threadIdx.x]);
     }
   }
-  pk.tile = -1;
+  pk.tile[0] = pk.tile[1], pk.slot[0] = pk.slot[1], pk.tile[1] = -1;
+  if (DEPTH == 2) pk.head ^= 1;
 }
-__device__ __forceinline__ void sweep_release_at_boundary(SweepPark& pk, double* ukcol, double* w, int64_t n) {
-  if (pk.tile >= 0 && (wall_clock64() >> pk.shift) != pk.slot) sweep_release(pk, ukcol, w, n);
+template <int DEPTH>
+__device__ __forceinline__ void sweep_release_all(SweepPark<DEPTH>& pk, double* ukcol, double* w, int64_t n) {
+  if (pk.tile[0] >= 0) sweep_release_oldest(pk, ukcol, w, n);
+  if (DEPTH == 2 && pk.tile[0] >= 0) sweep_release_oldest(pk, ukcol, w, n);
+}
+template <int DEPTH>
+__device__ __forceinline__ void sweep_release_at_boundary(SweepPark<DEPTH>& pk, double* ukcol, double* w, int64_t n) {
+  if (pk.tile[0] >= 0 && (wall_clock64() >> pk.shift) != pk.slot[0]) sweep_release_all(pk, ukcol, w, n);
 }
 
-template <bool FULL, bool CORRECT, bool PARK = false>
+template <bool FULL, bool CORRECT, int PARK = 0>  // PARK: the depth of the parking, 0 = direct stores
 __device__ __forceinline__ double sweep_tile(const SweepStep& st, double scale, double a, double b, const double* cl, const double* fl,
-                                             double* wave_acc, int64_t base, int64_t n, SweepPark* pk = nullptr) {
+                                             double* wave_acc, int64_t base, int64_t n, SweepPark<PARK ? PARK : 1>* pk = nullptr,
+                                             int64_t tile = 0) {
   static_assert(!(PARK && CORRECT), "the closing pass stores directly");
   const int lane = threadIdx.x & 63;
   const int k = st.k;
@@ -602,19 +624,20 @@ __device__ __forceinline__ double sweep_tile(const SweepStep& st, double scale, 
     }
   }
   if (PARK) {
-    if (pk->tile >= 0) sweep_release(*pk, ukcol, st.w, n);  // no boundary has passed: the place is needed now
+    if (pk->full()) sweep_release_oldest(*pk, ukcol, st.w, n);  // no boundary has passed: the place is needed now
+    double2* place = pk->free_place();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      pk->slots[i * kBlock + threadIdx.x] = u[i];
-      pk->slots[(4 + i) * kBlock + threadIdx.x] = w[i];
+      place[i * kBlock + threadIdx.x] = u[i];
+      place[(4 + i) * kBlock + threadIdx.x] = w[i];
       const int64_t row = base + i * (2 * kBlock);
       if (FULL || row < n) {
         nrm = fma(w[i].x, w[i].x, nrm);
         nrm = fma(w[i].y, w[i].y, nrm);
       }
     }
-    pk->slot = wall_clock64() >> pk->shift;
-    return nrm;  // the caller notes the tile as parked
+    pk->note(tile, wall_clock64() >> pk->shift);
+    return nrm;
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -631,15 +654,16 @@ __device__ __forceinline__ double sweep_tile(const SweepStep& st, double scale, 
   return nrm;
 }
 
-// PARK (the full sweep only, launch_sweep decides): kSweepParkBytes of parking in front of the sums; park_shift = log2 of the slot
-template <bool CORRECT, bool PARK>
+// PARK (the full sweep only, launch_sweep decides): parking for PARK tiles of kSweepParkBytes in front of the sums; park_shift =
+// log2 of the slot
+template <bool CORRECT, int PARK>
 __global__ __launch_bounds__(kBlock) void k_sweep(SweepStep st, InlineFin fin, int64_t n, int64_t ntiles, double* __restrict__ dpartials,
                                                   int pstride, double* __restrict__ npartials, const Ctrl* ctrl,  // no __restrict__: fin.ctrl aliases it
                                                   int park_shift) {
-  extern __shared__ __align__(16) double lds_all[];  // PARK: the parked tile; [4 waves][k+1] sums of d, then c (k+1, c[k] = 0), then f (k+1)
+  extern __shared__ __align__(16) double lds_all[];  // PARK parked tiles; [4 waves][k+1] sums of d, then c (k+1, c[k] = 0), then f (k+1)
   __shared__ double lds4[4];
   if (ctrl->stopped) return;
-  double* lds = lds_all + (PARK ? kSweepParkBytes / (int)sizeof(double) : 0);
+  double* lds = lds_all + PARK * (kSweepParkBytes / (int)sizeof(double));
   const int k = st.k, nacc = k + 1;
   double* cl = lds + 4 * nacc;
   double* fl = cl + nacc;
@@ -670,16 +694,15 @@ __global__ __launch_bounds__(kBlock) void k_sweep(SweepStep st, InlineFin fin, i
   const double b = k > 0 ? st.beta[k - 1] : 0.0;
   double* wave_acc = lds + (threadIdx.x >> 6) * nacc;
   double nrm = 0.0;
-  SweepPark pk{reinterpret_cast<double2*>(lds_all), -1, 0, park_shift};
+  SweepPark<PARK ? PARK : 1> pk{reinterpret_cast<double2*>(lds_all), {-1, -1}, {0, 0}, 0, park_shift};
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t base = tile * kTileRows + 2 * threadIdx.x;
     if ((tile + 1) * kTileRows <= n)
-      nrm += sweep_tile<true, CORRECT, PARK>(st, scale, a, b, cl, fl, wave_acc, base, n, &pk);
+      nrm += sweep_tile<true, CORRECT, PARK>(st, scale, a, b, cl, fl, wave_acc, base, n, &pk, tile);
     else
-      nrm += sweep_tile<false, CORRECT, PARK>(st, scale, a, b, cl, fl, wave_acc, base, n, &pk);
-    if (PARK) pk.tile = tile;
+      nrm += sweep_tile<false, CORRECT, PARK>(st, scale, a, b, cl, fl, wave_acc, base, n, &pk, tile);
   }
-  if (PARK && pk.tile >= 0) sweep_release(pk, const_cast<double*>(st.V) + (int64_t)k * st.ldv, st.w, n);  // nothing stays parked
+  if (PARK) sweep_release_all(pk, const_cast<double*>(st.V) + (int64_t)k * st.ldv, st.w, n);  // nothing stays parked, oldest first
   if (CORRECT) return;
   __syncthreads();
   for (int c = threadIdx.x; c < nacc; c += kBlock)
@@ -3110,29 +3133,49 @@ void launch_sweep(hipStream_t s, const SweepStep& st, const InlineFin* fin, int6
   const size_t shmem = sizeof(double) * 6 * (size_t)(st.k + 1);
   const InlineFin nofin{nullptr, 0, 0, 0.0, nullptr, nullptr, nullptr};
   const InlineFin f = fin ? *fin : nofin;
-  // EIGENEX_SWEEP_DIRECT_STORES=1: the full sweep stores at each tile's end, as the closing pass does.  EIGENEX_SWEEP_SLOT_SHIFT=s:
-  // slots of 2^s ticks instead of kSweepSlotMicroseconds (measurements; tests: with a large s no boundary ever passes).
+  // EIGENEX_SWEEP_DIRECT_STORES=1: the full sweep stores at each tile's end, as the closing pass does.  EIGENEX_SWEEP_PARK_TILES=1|2
+  // caps the depth of the parking.  EIGENEX_SWEEP_SLOT_SHIFT=s: slots of 2^s ticks instead of the depth's measured default
+  // (measurements; tests: with a large s no boundary ever passes).  All read once per process.
   static const bool direct = getenv("EIGENEX_SWEEP_DIRECT_STORES") != nullptr;
-  static const int shift = [] {
-    if (const char* e = getenv("EIGENEX_SWEEP_SLOT_SHIFT")) return std::min(62, std::max(0, atoi(e)));
-    int dev = 0, khz = 0;  // the chip-wide clock's rate
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;
-    int sh = 0;
-    while (sh < 40 && 1.5 * (double)((uint64_t)1 << sh) < kSweepSlotMicroseconds * 1e-3 * khz) ++sh;  // the nearest power of two
-    return sh;
+  static const int max_depth = [] {
+    const char* e = getenv("EIGENEX_SWEEP_PARK_TILES");
+    return e ? std::min(2, std::max(1, atoi(e))) : 2;
   }();
+  static const struct Shifts {
+    int of_depth[3];
+    Shifts() {
+      int dev = 0, khz = 0;  // the chip-wide clock's rate
+      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;
+      const char* e = getenv("EIGENEX_SWEEP_SLOT_SHIFT");
+      const double us[3] = {0.0, kSweepSlotMicroseconds, kSweepSlotMicroseconds2};
+      of_depth[0] = 0;
+      for (int d = 1; d <= 2; ++d) {
+        int sh = 0;
+        while (sh < 40 && 1.5 * (double)((uint64_t)1 << sh) < us[d] * 1e-3 * khz) ++sh;  // the nearest power of two
+        of_depth[d] = e ? std::min(62, std::max(0, atoi(e))) : sh;
+      }
+    }
+  } shifts;
+  // the deepest parking that fits beside the sums within the budget, so that two workgroups per CU still fit
+  int depth = direct ? 0 : max_depth;
+  while (depth > 0 && (size_t)depth * kSweepParkBytes + shmem + kSweepStaticLds > (size_t)kSweepLdsBudget) --depth;
+  auto big_lds = [](const void* fn) {  // more than 64 KB of dynamic LDS has to be asked for once per instantiation
+    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kSweepLdsBudget - kSweepStaticLds) == hipSuccess;
+  };
   if (st.correct_only) {
-    hipLaunchKernelGGL((k_sweep<true, false>), dim3(grid), dim3(kBlock), shmem, s, st, f, n, ntiles, dpartials, pstride, npartials, ctrl, 0);
-  } else if (direct || kSweepParkBytes + shmem + kSweepStaticLds > (size_t)kSweepLdsBudget) {
-    hipLaunchKernelGGL((k_sweep<false, false>), dim3(grid), dim3(kBlock), shmem, s, st, f, n, ntiles, dpartials, pstride, npartials, ctrl, 0);
+    hipLaunchKernelGGL((k_sweep<true, 0>), dim3(grid), dim3(kBlock), shmem, s, st, f, n, ntiles, dpartials, pstride, npartials, ctrl, 0);
+  } else if (depth == 0) {
+    hipLaunchKernelGGL((k_sweep<false, 0>), dim3(grid), dim3(kBlock), shmem, s, st, f, n, ntiles, dpartials, pstride, npartials, ctrl, 0);
+  } else if (depth == 1) {
+    static const bool asked = big_lds(reinterpret_cast<const void*>(&k_sweep<false, 1>));
+    (void)asked;  // a launch the runtime refuses shows in the caller's launch check
+    hipLaunchKernelGGL((k_sweep<false, 1>), dim3(grid), dim3(kBlock), kSweepParkBytes + shmem, s, st, f, n, ntiles, dpartials, pstride, npartials,
+                       ctrl, shifts.of_depth[1]);
   } else {
-    static const bool big_lds = [] {  // more than 64 KB of dynamic LDS has to be asked for once
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 kSweepLdsBudget - kSweepStaticLds) == hipSuccess;
-    }();
-    (void)big_lds;  // a launch the runtime refuses shows in the caller's launch check
-    hipLaunchKernelGGL((k_sweep<false, true>), dim3(grid), dim3(kBlock), kSweepParkBytes + shmem, s, st, f, n, ntiles, dpartials, pstride, npartials,
-                       ctrl, shift);
+    static const bool asked = big_lds(reinterpret_cast<const void*>(&k_sweep<false, 2>));
+    (void)asked;
+    hipLaunchKernelGGL((k_sweep<false, 2>), dim3(grid), dim3(kBlock), 2 * kSweepParkBytes + shmem, s, st, f, n, ntiles, dpartials, pstride,
+                       npartials, ctrl, shifts.of_depth[2]);
   }
 }
 

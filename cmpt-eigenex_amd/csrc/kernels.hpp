@@ -195,10 +195,11 @@ struct SweepStep {
   int correct_only;
 };
 // d partials: dpartials[j*pstride + block], j <= k (k_dots' layout); ||w||^2 partials: npartials[block]
-// The full sweep parks each tile's two results in LDS and stores them from the next tile, at a boundary of the chip-wide clock
-// (kernels.hip: SweepPark), when the parking fits beside the 6 (k + 1) doubles of sums and coefficients within kSweepLdsBudget, so
-// that two workgroups per CU still fit; otherwise, in the closing pass and under EIGENEX_SWEEP_DIRECT_STORES=1 (read once per
-// process) every tile stores at its end.  Both paths write the same bytes.
+// The full sweep parks each tile's two results in LDS and stores them from a later tile, at a boundary of the chip-wide clock
+// (kernels.hip: SweepPark).  launch_sweep takes the deepest parking, two tiles or one, that fits beside the 6 (k + 1) doubles of
+// sums and coefficients within kSweepLdsBudget, so that two workgroups per CU still fit: two tiles up to k = 339, one up to
+// k = 1022 (EIGENEX_SWEEP_PARK_TILES=1 keeps it at one).  Otherwise, in the closing pass and under EIGENEX_SWEEP_DIRECT_STORES=1
+// every tile stores at its end.  The switches are read once per process.  All paths write the same bytes.
 constexpr int kSweepParkBytes = 2 * kTileRows * (int)sizeof(double);  // 32 KB: column k and w of one tile
 constexpr int kSweepLdsBudget = 80 * 1024;                            // per workgroup: half a CU's LDS
 constexpr int kSweepStaticLds = 4 * (int)sizeof(double);              // k_sweep's block_sum scratch
@@ -206,6 +207,9 @@ constexpr int kSweepStaticLds = 4 * (int)sizeof(double);              // k_sweep
 // boundary at all (profiles/sweep_stores.md): shorter slots split the workgroups' stores into more and smaller bursts, longer ones
 // let most tiles leave unsynchronised at their successor's end, which gains nothing.  No result depends on it.
 constexpr double kSweepSlotMicroseconds = 80.0;
+// The slot with two parked tiles, chosen the same way against 2^14 and 2^15 ticks (profiles/sweep_park_depth.md): the same 2^13.
+// The second tile pays where a tile is shorter than a slot (k below about 58), not by allowing a longer slot.
+constexpr double kSweepSlotMicroseconds2 = 80.0;
 void launch_sweep(hipStream_t s, const SweepStep& st, const InlineFin* fin, int64_t n, double* dpartials, int pstride, double* npartials,
                   int grid, const Ctrl* ctrl);
 // behind the full sweep of step k, one workgroup: d_j = sum of its partials (fixed order), beta_k^2 = sum of the norm partials in
