@@ -22,11 +22,47 @@ namespace cmpt {
 namespace EigenEx {
 namespace small_eigen {
 
+using cplx = std::complex<double>;
+
+// What the dense routines below look at before they square an entry.  A NaN or an infinite entry makes the routine return
+// false: it still runs to its (bounded) end on the entries as they are, so a caller that ignores the return sees what it saw
+// before.  Entries whose largest magnitude lies outside [2^-300, 2^300] have squares and products that overflow, or underflow
+// below the bits that count; they are multiplied by the power of two that brings the largest into [1/2, 1) -- exact -- and
+// the eigenvalues are multiplied back; the vectors do not depend on the scale.  Inside the range nothing is touched, so every
+// result there keeps its bits.
+struct EntryRange {
+  double largest = 0.0;
+  bool finite = true;
+  void see(double x) {
+    if (!std::isfinite(x))
+      finite = false;
+    else
+      largest = std::max(largest, std::fabs(x));
+  }
+  void see(const cplx& x) { see(x.real()), see(x.imag()); }
+  // e != 0: multiply the entries by 2^-e and the eigenvalues by 2^e
+  int exponent() const {
+    if (!finite || largest == 0.0 || (largest >= std::ldexp(1.0, -300) && largest <= std::ldexp(1.0, 300))) return 0;
+    int e = 0;
+    std::frexp(largest, &e);
+    return e;
+  }
+};
+inline double times_two_to(double x, int e) { return std::ldexp(x, e); }
+inline cplx times_two_to(const cplx& x, int e) { return cplx(std::ldexp(x.real(), e), std::ldexp(x.imag(), e)); }
+// the eigenvalues of the scaled problem back at the caller's scale; false if one of them is beyond the largest double
+template <class T>
+bool values_times_two_to(std::vector<T>& values, int e) {
+  EntryRange after;
+  for (T& v : values) after.see(v = times_two_to(v, e));
+  return after.finite;
+}
+
 // Symmetric tridiagonal eigenproblem by the implicit-shift QL iteration.
 // diag[n], sub[n-1] (extra entries of `sub` are ignored, cf. the surplus beta the
 // reference leaves behind on breakdown, lanczos.hpp:433-436).
 // values: ascending.  vectors (optional): column-major n x n, column k belongs to values[k].
-// Returns false if an eigenvalue failed to converge in 60 sweeps.
+// Returns false if an eigenvalue failed to converge in 60 sweeps, or if an entry is not finite.
 inline bool tridiagonal(const double* diag, const double* sub, int n, std::vector<double>& values,
                         std::vector<double>* vectors) {
   values.assign(diag, diag + n);
@@ -34,13 +70,16 @@ inline bool tridiagonal(const double* diag, const double* sub, int n, std::vecto
     vectors->assign(static_cast<std::size_t>(n) * n, 0.0);
     for (int i = 0; i < n; ++i) (*vectors)[static_cast<std::size_t>(i) * n + i] = 1.0;
   }
-  if (n <= 1) return true;
+  EntryRange seen;
+  for (int i = 0; i < n; ++i) seen.see(diag[i]);
+  for (int i = 0; i + 1 < n; ++i) seen.see(sub[i]);
+  if (n <= 1) return seen.finite;
   std::vector<double> e(sub, sub + (n - 1));
   e.push_back(0.0);
   double* d = values.data();
   double* z = vectors ? vectors->data() : nullptr;  // z[row + col*n]
   const double eps = std::numeric_limits<double>::epsilon();
-  bool ok = true;
+  bool ok = seen.finite;
   for (int l = 0; l < n; ++l) {
     int iter = 0;
     for (;;) {
@@ -110,9 +149,15 @@ inline bool tridiagonal(const double* diag, const double* sub, int n, std::vecto
 // Dense real symmetric eigenproblem (column-major n x n in A, destroyed): Householder reduction to
 // tridiagonal form with accumulated reflectors, then the QL iteration above; eigenvectors = Q * Z.
 // Used by the thick-restart solver, whose projected matrix is diag(theta) bordered by one row of
-// couplings plus a tridiagonal tail.  values ascending; vectors column-major n x n.
+// couplings plus a tridiagonal tail.  values ascending; vectors column-major n x n.  Returns false if the QL iteration did
+// not converge, if an entry is not finite, or if an eigenvalue is beyond the largest double (EntryRange above).
 inline bool symmetric(std::vector<double>& A, int n, std::vector<double>& values, std::vector<double>& vectors) {
   auto a = [&](int r, int c) -> double& { return A[static_cast<std::size_t>(r) + static_cast<std::size_t>(c) * n]; };
+  EntryRange seen;
+  for (std::size_t i = 0; i < static_cast<std::size_t>(n) * n; ++i) seen.see(A[i]);
+  const int scale = seen.exponent();
+  if (scale != 0)
+    for (std::size_t i = 0; i < static_cast<std::size_t>(n) * n; ++i) A[i] = times_two_to(A[i], -scale);
   std::vector<double> Q(static_cast<std::size_t>(n) * n, 0.0);
   auto q = [&](int r, int c) -> double& { return Q[static_cast<std::size_t>(r) + static_cast<std::size_t>(c) * n]; };
   for (int i = 0; i < n; ++i) q(i, i) = 1.0;
@@ -120,7 +165,10 @@ inline bool symmetric(std::vector<double>& A, int n, std::vector<double>& values
   for (int k = 0; k + 2 < n; ++k) {
     double nrm2 = 0.0;
     for (int i = k + 1; i < n; ++i) nrm2 += a(i, k) * a(i, k);
-    double tail2 = nrm2 - a(k + 1, k) * a(k + 1, k);
+    // the entries below the sub-diagonal, summed on their own: nrm2 - a(k+1,k)^2 cancels to 0 once they are below 1.5e-8
+    // |a(k+1,k)|, and a column skipped on that account kept entries that nothing looked at again
+    double tail2 = 0.0;
+    for (int i = k + 2; i < n; ++i) tail2 += a(i, k) * a(i, k);
     if (tail2 <= 0.0) continue;  // column already tridiagonal
     const double nrm = std::sqrt(nrm2);
     const double alpha = a(k + 1, k) > 0.0 ? -nrm : nrm;
@@ -155,7 +203,8 @@ inline bool symmetric(std::vector<double>& A, int n, std::vector<double>& values
   std::vector<double> d(static_cast<std::size_t>(n)), e(static_cast<std::size_t>(n > 0 ? n : 1), 0.0), Z;
   for (int i = 0; i < n; ++i) d[static_cast<std::size_t>(i)] = a(i, i);
   for (int i = 0; i + 1 < n; ++i) e[static_cast<std::size_t>(i)] = a(i + 1, i);
-  const bool ok = tridiagonal(d.data(), e.data(), n, values, &Z);
+  bool ok = tridiagonal(d.data(), e.data(), n, values, &Z) && seen.finite;
+  if (scale != 0) ok = values_times_two_to(values, scale) && ok;
   vectors.assign(static_cast<std::size_t>(n) * n, 0.0);
   for (int c = 0; c < n; ++c)
     for (int j = 0; j < n; ++j) {
@@ -165,8 +214,6 @@ inline bool symmetric(std::vector<double>& A, int n, std::vector<double>& values
     }
   return ok;
 }
-
-using cplx = std::complex<double>;
 
 // Complex Hermitian eigenproblem (column-major n x n in A, read only; the strict upper triangle is not looked at), in the
 // simple form: the real symmetric embedding B = [[Re A, -Im A], [Im A, Re A]] of order 2n goes through symmetric() above.
@@ -221,10 +268,18 @@ inline bool hermitian(const std::vector<cplx>& A, int n, std::vector<double>& va
 // overwritten) by the single-shift QR iteration to Schur form T = Z^H H Z, then
 // back-substitution for the eigenvectors of T and X = Z*Y with unit-norm columns.
 // values[k] = T_kk in Schur order (the caller sorts, arnoldi.hpp:813-822).
-// vectors (optional): column-major n x n.
+// vectors (optional): column-major n x n.  Returns false if the iteration did not converge, if an entry on or above the
+// sub-diagonal is not finite, or if an eigenvalue is beyond the largest double (EntryRange above).
 inline bool hessenberg(std::vector<cplx>& H, int n, std::vector<cplx>& values, std::vector<cplx>* vectors) {
   values.assign(static_cast<std::size_t>(n), cplx(0.0));
   auto h = [&](int r, int c) -> cplx& { return H[static_cast<std::size_t>(r) + static_cast<std::size_t>(c) * n]; };
+  EntryRange seen;
+  for (int c = 0; c < n; ++c)
+    for (int r = 0; r <= std::min(c + 1, n - 1); ++r) seen.see(h(r, c));
+  const int scale = seen.exponent();
+  if (scale != 0)
+    for (int c = 0; c < n; ++c)
+      for (int r = 0; r <= std::min(c + 1, n - 1); ++r) h(r, c) = times_two_to(h(r, c), -scale);
   std::vector<cplx> Z;
   const bool wantz = vectors != nullptr;
   if (wantz) {
@@ -237,7 +292,7 @@ inline bool hessenberg(std::vector<cplx>& H, int n, std::vector<cplx>& values, s
   for (int c = 0; c < n; ++c)
     for (int r = 0; r <= std::min(c + 1, n - 1); ++r) hnorm = std::max(hnorm, std::abs(h(r, c)));
   if (hnorm == 0.0) hnorm = 1.0;
-  bool ok = true;
+  bool ok = seen.finite;
   int iu = n - 1, iter = 0, total = 0;
   while (iu > 0) {
     // look for a negligible sub-diagonal entry
@@ -314,6 +369,7 @@ inline bool hessenberg(std::vector<cplx>& H, int n, std::vector<cplx>& values, s
     }
   }
   for (int i = 0; i < n; ++i) values[static_cast<std::size_t>(i)] = h(i, i);
+  if (scale != 0) ok = values_times_two_to(values, scale) && ok;
   if (!wantz) return ok;
   // eigenvectors of the triangular factor, column by column
   vectors->assign(static_cast<std::size_t>(n) * n, cplx(0.0));
@@ -361,12 +417,19 @@ inline bool hessenberg_real_values(std::vector<double>& H, int n, std::vector<cp
   if (n == 0) return true;
   auto a = [&](int r, int c) -> double& { return H[static_cast<std::size_t>(r) + static_cast<std::size_t>(c) * n]; };
   auto sign = [](double x, double y) { return y >= 0.0 ? std::abs(x) : -std::abs(x); };
+  EntryRange seen;  // false on an entry that is not finite, a power of two outside the safe range: as in hessenberg()
+  for (int c = 0; c < n; ++c)
+    for (int r = 0; r <= std::min(c + 1, n - 1); ++r) seen.see(a(r, c));
+  const int scale = seen.exponent();
+  if (scale != 0)
+    for (int c = 0; c < n; ++c)
+      for (int r = 0; r <= std::min(c + 1, n - 1); ++r) a(r, c) = times_two_to(a(r, c), -scale);
   double anorm = 0.0;
   for (int i = 0; i < n; ++i)
     for (int j = std::max(i - 1, 0); j < n; ++j) anorm += std::abs(a(i, j));
   int nn = n - 1;
   double t = 0.0, p = 0.0, q = 0.0, r = 0.0, s = 0.0, w, x, y, z;
-  bool ok = true;
+  bool ok = seen.finite;
   while (nn >= 0) {
     int its = 0, l;
     do {
@@ -486,6 +549,7 @@ inline bool hessenberg_real_values(std::vector<double>& H, int n, std::vector<cp
       }
     } while (l < nn - 1);
   }
+  if (scale != 0) ok = values_times_two_to(values, scale) && ok;
   return ok;
 }
 
@@ -495,6 +559,11 @@ inline bool hessenberg_real_values(std::vector<double>& H, int n, std::vector<cp
 // Krylov-Schur run and the general case for the later ones, whose leading block is full.
 inline bool general(std::vector<cplx>& A, int n, std::vector<cplx>& values, std::vector<cplx>* vectors) {
   auto a = [&](int r, int c) -> cplx& { return A[static_cast<std::size_t>(r) + static_cast<std::size_t>(c) * n]; };
+  EntryRange seen;  // false on an entry that is not finite, a power of two outside the safe range: hessenberg() then finds
+  for (std::size_t i = 0; i < static_cast<std::size_t>(n) * n; ++i) seen.see(A[i]);  // its input inside the range
+  const int scale = seen.exponent();
+  if (scale != 0)
+    for (std::size_t i = 0; i < static_cast<std::size_t>(n) * n; ++i) A[i] = times_two_to(A[i], -scale);
   std::vector<cplx> U;
   bool reflected = false;
   std::vector<cplx> v(static_cast<std::size_t>(n));
@@ -542,7 +611,8 @@ inline bool general(std::vector<cplx>& A, int n, std::vector<cplx>& values, std:
     reflected = true;
   }
   std::vector<cplx> X;
-  const bool ok = hessenberg(A, n, values, vectors ? &X : nullptr);
+  bool ok = hessenberg(A, n, values, vectors ? &X : nullptr) && seen.finite;
+  if (scale != 0) ok = values_times_two_to(values, scale) && ok;
   if (!vectors) return ok;
   if (!reflected) {
     vectors->swap(X);

@@ -122,3 +122,22 @@ def entropy_tolerance(d, n_b):
     delta = (n_b + d) * float(EPS)
     assert delta <= 0.5
     return d * (-delta * log(delta))
+
+
+def t_plus_e(d, complex_entries=False):
+    """tridiag(1, 3 + 0.1 i, 1) + E, E = +-1e-9 (or +-1e-9 i) on every entry with |i - j| >= 2 (the signs from a fixed seed), brought
+    to unit trace: a positive definite rho whose columns are tridiagonal up to 1e-9 of the sub-diagonal.  Shared by
+    tests/test_small_eigen_hard_cases_host.py and the GPU tests of the entanglement spectrum."""
+    T = np.diag(3.0 + 0.1 * np.arange(d)) + np.diag(np.ones(d - 1), 1) + np.diag(np.ones(d - 1), -1)
+    low = 1e-9 * np.where(np.random.default_rng(100 + d).random((d, d)) < 0.5, -1.0, 1.0) * np.tril(np.ones((d, d)), -2)
+    if complex_entries:
+        low = 1j * low
+    A = T + low + low.conj().T
+    return A / np.trace(A).real
+
+
+def t_plus_e_state(d, complex_entries=False):
+    """psi[a + d e] = M[a, e] with M the Cholesky factor of t_plus_e(d): the state of 2 log2(d) sites whose reduced density matrix
+    on the low log2(d) sites is M M^H = t_plus_e(d) up to rounding"""
+    M = np.linalg.cholesky(t_plus_e(d, complex_entries))
+    return np.ascontiguousarray(M.T).ravel()

@@ -264,3 +264,37 @@ def test_cpp_program_spin_entanglement(tmp_path):
     assert abs(o["renyi_near_one"] - o["entropy"]) < 1e-4 and 1 <= o["schmidt_rank"] <= 64 and 0 < o["largest"] < 1
     assert (o["refused_csr"], o["refused_empty"], o["refused_twice"], o["refused_length"], o["refused_no_operator"], o["refused_all"], o["no_result_throws"]) == (1,) * 7
     assert o["uniform_info"] == 1 and o["uniform_blocks"] == 2 and abs(o["uniform_entropy"] - log(2)) < 1e-12
+
+
+@pytest.mark.parametrize("L,mask", [(6, 0b000111), (12, 0b000000111111)])
+def test_spectrum_of_a_rho_that_is_tridiagonal_up_to_1e_9(mods, L, mask):
+    """Full space, A = the low half of the sites: d = 8 with an environment of 8 rows, d = 64 with tiles of 64 rows.  The state is
+    psi[a + d e] = M[a, e] with M the Cholesky factor of rr.t_plus_e(d), so rho_A = M M^T is tridiagonal plus entries of 1e-9 of the
+    sub-diagonal: the columns on which small_eigen::symmetric decides whether a Householder step is needed.  The raw blocks
+    against M M^T in long double within the bound of this file; the spectrum of SpinEntanglementSolver against
+    numpy.linalg.eigvalsh of the solver's own unit-trace block within delta = (n_b + d) eps, the eigenvalue bound of
+    rr.entropy_tolerance (the n_b part is not even needed: both sides start from the same block).  Before symmetric() summed the
+    column tail directly it skipped every one of these columns without zeroing it, and on the MI355X the spectrum was off by
+    7.3e-11 at d = 8 and 9.0e-12 at d = 64 -- 20000 and 315 times delta; it is now off by 2.8e-17 and 4.5e-17."""
+    capi, solver = mods
+    d = 1 << bin(mask).count("1")
+    n_b = (1 << L) // d
+    psi = rr.t_plus_e_state(d)
+    ctx = capi.Context()
+    S = _operator(capi, ctx, L, None)
+    b = capi.Basis(ctx, S, 1 << L, 1)
+    b.upload(capi.VEC_COL(0), psi)
+    rr.check(f"device T + E ({L},{mask:#x})", b.spin_rdm(capi.VEC_COL(0), mask), rr.rdm(L, None, psi, mask))
+    se = solver.SpinEntanglementSolver()
+    se.setDeviceOperator(S).setState(psi).setSubsystemMask(mask).compute()
+    r = se.results()
+    assert r["info_name"] == "Success", se.log()
+    (k, block), = r["blocks"]
+    assert k == 0 and block.shape == (d, d) and r["spectrum"].shape == (d,)
+    own = np.sort(np.linalg.eigvalsh(block))[::-1]
+    delta = (n_b + d) * float(rr.EPS)
+    off = float(np.abs(r["spectrum"] - own).max())
+    print(f"d = {d}: spectrum off LAPACK's of the same block by {off:.3e}, delta {delta:.3e}; block off T + E by {np.abs(block - rr.t_plus_e(d)).max():.3e}")
+    assert own[-1] > 0 and off <= delta
+    for h in (se, b, S, ctx):
+        h.close()

@@ -358,3 +358,36 @@ def test_cpp_program_spin_entanglement_z(tmp_path):
     assert o["class_blocks"] == 6 and abs(o["class_norm2"] - 1.0) <= 1e-12 and abs(o["trace"] - 1.0) <= 2 * d * EPS
     assert o["asymmetry"] == 0.0 and o["diagonal_imag"] == 0.0
     assert (o["real_block_throws"], o["refused_zero"], o["refused_twice"], o["refused_all"], o["refused_no_state"], o["refused_real_operator"], o["still_works"]) == (1,) * 7
+
+
+@pytest.mark.parametrize("L,mask", [(6, 0b000111), (12, 0b000000111111)])
+def test_spectrum_of_a_rho_that_is_tridiagonal_up_to_1e_9_i(mods, L, mask):
+    """test_spectrum_of_a_rho_that_is_tridiagonal_up_to_1e_9 of tests/test_gpu_spin_rdm.py with the Hermitian T + E (rr.t_plus_e(d, True): +-1e-9 i beyond the
+    sub-diagonal) and its complex Cholesky factor, rho_A = M M^H: d = 8 with an environment of 8 rows, d = 64 with tiles of 64 rows.
+    The raw blocks against the long double restatement within the bound of this file; the spectrum of SpinEntanglementSolver against
+    numpy.linalg.eigvalsh of the solver's own unit-trace block within delta = (3 n_b + 2 d) eps, the eigenvalue bound of
+    rz.entropy_tolerance_z.  small_eigen::hermitian goes through symmetric() on the embedding of order 2d and inherited its skipped
+    columns: before the fix the spectrum on the MI355X was off by 3.2e-11 at d = 8 and 9.9e-13 at d = 64, 3600 and 14 times delta;
+    it is now off by 5.6e-17 and 4.2e-17."""
+    capi, solver = mods
+    d = 1 << bin(mask).count("1")
+    n_b = (1 << L) // d
+    psi = rr.t_plus_e_state(d, True)
+    ctx = capi.Context()
+    S = _operator(capi, ctx, L, None)
+    b = capi.Basis(ctx, S, 1 << L, 1)
+    b.upload(capi.VEC_COL(0), psi)
+    rz.check_z(f"device_z T + E ({L},{mask:#x})", b.spin_rdm_z(capi.VEC_COL(0), mask), rz.rdm_z(L, None, psi, mask))
+    se = solver.SpinEntanglementSolver()
+    se.setDeviceOperator(S).setState(psi).setSubsystemMask(mask).compute()
+    r = se.results()
+    assert r["info_name"] == "Success", se.log()
+    (k, block), = r["blocks"]
+    assert k == 0 and block.shape == (d, d) and block.dtype == np.complex128 and r["spectrum"].shape == (d,)
+    own = np.sort(np.linalg.eigvalsh(block))[::-1]
+    delta = (3 * n_b + 2 * d) * EPS
+    off = float(np.abs(r["spectrum"] - own).max())
+    print(f"d = {d}: spectrum off LAPACK's of the same block by {off:.3e}, delta {delta:.3e}; block off T + E by {np.abs(block - rr.t_plus_e(d, True)).max():.3e}")
+    assert own[-1] > 0 and off <= delta
+    for h in (se, b, S, ctx):
+        h.close()
