@@ -130,6 +130,8 @@ SIGNATURES = {
     "eigenex_spin_measure": (C.c_int, [_vp, C.c_int, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_measure_host": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
     "eigenex_spin_measure_host_z": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _up, C.c_int, _up, _dp, _dp, _dp]),
+    "eigenex_spin_measure_columns": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _up, C.c_int, _up, _dp, _dp]),
+    "eigenex_spin_measure_columns_host": (C.c_int, [C.c_int, C.c_int, _dp, _dp, C.c_int64, C.c_int, C.c_int, _up, C.c_int, _up, _dp, _dp]),
     "eigenex_spin_geometry": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "eigenex_spin_site_apply": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _dp, _dp]),
     "eigenex_spin_site_apply_host": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
@@ -544,6 +546,22 @@ def spin_measure_host_z(n_sites: int, n_up, x, diag_masks, flip_masks):
     """eigenex_spin_measure_host_z: the Hermitian raw sums (diag, flip, norm2) of the masks over the complex vector x, in host code
     (no GPU); n_up as for spin_measure_host."""
     return _spin_measure_host(lib().eigenex_spin_measure_host_z, np.complex128, n_sites, n_up, x, diag_masks, flip_masks)
+
+
+def spin_measure_columns_host(n_sites: int, n_up, x, columns, diag_masks, flip_masks):
+    """eigenex_spin_measure_columns_host: the raw sums (diag[n_diag, count], flip[n_flip, count]) = <V_j| A_t |x> of the masks, in
+    host code (no GPU).  columns[j] is column V_j, a (count, rows) array; n_up as for spin_measure_host."""
+    x = np.ascontiguousarray(x, np.float64)
+    v = np.ascontiguousarray(columns, np.float64)
+    if v.ndim != 2 or x.ndim != 1 or v.shape[1] != x.size:
+        raise ValueError("columns must be a (count, rows) array with the rows of x")
+    count = int(v.shape[0])
+    dm, nd, dp = _mask_list(diag_masks)
+    fm, nf, fp = _mask_list(flip_masks)
+    diag, flip = np.zeros((nd, count)), np.zeros((nf, count))
+    _chk(lib().eigenex_spin_measure_columns_host(int(n_sites), -1 if n_up is None else int(n_up), _d(x), _d(v), int(v.shape[1]), count, nd, dp, nf, fp,
+                                                 _d(diag) if diag.size else None, _d(flip) if flip.size else None))
+    return diag, flip
 
 
 def spin_rdm_layout(n_sites: int, n_up, mask_a: int):
@@ -1071,6 +1089,18 @@ class Basis:
         diag, flip, norm2 = np.zeros(nd), np.zeros(nf), C.c_double()
         _chk(lib().eigenex_spin_measure(self.h, x_ref, nd, dp, nf, fp, _d(diag) if nd else None, _d(flip) if nf else None, C.byref(norm2)))
         return diag, flip, norm2.value
+
+    def spin_measure_columns(self, x_ref, first, count, diag_masks, flip_masks):
+        """eigenex_spin_measure_columns: (diag[n_diag, count], flip[n_flip, count]) = <V_j| A_t |x_ref> against the basis columns
+        first .. first + count - 1, the basis streaming past once per 16 terms; real states of matrix-free spin operators.  A pending
+        newest column is closed first if the call reads it; nothing else of the state changes."""
+        dm, nd, dp = _mask_list(diag_masks)
+        fm, nf, fp = _mask_list(flip_masks)
+        count = int(count)
+        diag, flip = np.zeros((nd, max(count, 0))), np.zeros((nf, max(count, 0)))
+        _chk(lib().eigenex_spin_measure_columns(self.h, x_ref, int(first), count, nd, dp, nf, fp, _d(diag) if diag.size else None,
+                                                _d(flip) if flip.size else None))
+        return diag, flip
 
     def _spin_rdm(self, entry, dtype, x_ref, mask_a):
         """spin_rdm and spin_rdm_z: the result is handed over as doubles and returned as blocks of dtype"""

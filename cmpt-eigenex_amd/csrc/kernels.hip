@@ -1939,6 +1939,100 @@ __global__ __launch_bounds__(kBlock) void k_spin_measure_reduce(const double* __
 }
 
 // ---------------------------------------------------------------------------
+// The observables of one vector against basis columns (spin_measure_columns.hpp has the definition, spin_rows.hpp the row:
+// spin_measure_columns_row): out[t][j] = <V_j| A_t |x> for one chunk of kSpinMeasureChunk diagonal and as many flip masks
+// (SpinMeasureChunk, read by every lane at the same index and never written) and ncols <= J = kSpinMeasureColumns columns
+// V, V + ldv, ...  k_spin_measure's persistent grid, 256-row tiles, LDS binomials and batches.  Per row the lane's state, its
+// own element of x, the rank-table gathers and the gathered x are taken once and meet J column elements, loaded non-temporally
+// as the basis is in k_dots.  A column beyond ncols is read as column ncols - 1 (inside the basis; its sums have no destination),
+// so a sum's bits do not depend on what else shares the launch.  The 2 C J sums stay in registers across the tile loop and leave
+// through block_sum into partials[sum * pstride + workgroup], sum = t * J + j (diag) and (C + t) * J + j (flip);
+// k_spin_measure_columns_reduce adds those in k_reduce_fin's order.  No atomics.  ctrl->stopped is not consulted.
+// The column chunk J.  Per row and launch the basis contributes 8 J bytes, and whatever J is the basis streams past
+// ceil(terms / C) times in all.  What falls with J is the rest of the row, which is paid once per launch: the own element (8
+// bytes from HBM or L2), up to 16 gathers of x (128 bytes, L2 at best) and in a sector 32 rank-table gathers (128 bytes, L2),
+// and the unranking.  At J = 1 that is 264 bytes of gathers per 8 basis bytes, at J = 4 per 32.  The sums cost 2 C J = 128
+// doubles = 256 VGPRs at J = 4, next to one batch (on, base, low, xv: about 40) and the row: J = 8 would need 512 for the sums
+// alone and cannot be had without spilling.  J = 4 compiles to 256 VGPRs + 32 (sector) or 38 (full space) AGPRs, one wave per
+// SIMD, without scratch.  The fmas are 2 C = 32 per basis element whatever J is, 0.7 of the columns' HBM time at 64 fp64 fmas
+// per clock and CU.  Measured (profiles/spin_thermal.md), neither bounds the kernel: at one wave per SIMD nothing hides the chain
+// load - unrank - gather - gather of a row, and a pass of the basis takes 9 (diagonal terms only) to 18 (16 + 16 terms) times
+// eigenex_dots' sweep of the same columns.  A smaller J buys occupancy with as many more launches: the sums per SIMD, J times the
+// waves, stay what the register file holds.  What would help is more rows in flight per lane (the sums are shared between them,
+// only the row's own 50 registers multiply); not done here.
+// ---------------------------------------------------------------------------
+template <bool SECTOR>
+__global__ __launch_bounds__(kBlock) void k_spin_measure_columns(const SpinMeasureChunk* __restrict__ ch, const SpinSectorView* __restrict__ op,
+                                                                 const uint32_t* __restrict__ lo_rank, const uint32_t* __restrict__ hi_base,
+                                                                 const double* __restrict__ x, const double* __restrict__ V, int64_t ldv,
+                                                                 int ncols, int64_t n, int64_t ntiles, double* __restrict__ partials,
+                                                                 int pstride) {
+  constexpr int C = kSpinMeasureChunk, J = kSpinMeasureColumns;
+  __shared__ double lds4[4];
+  __shared__ uint32_t binom[SECTOR ? kSectorMaxSites * (kSectorMaxSites + 1) : 1];
+  int n_sites = 0, n_up = 0, h = 0;
+  uint32_t lo_mask = 0;
+  if constexpr (SECTOR) {
+    spin_stage_binomials(op, binom);
+    __syncthreads();
+    n_sites = op->model.n_sites, n_up = op->n_up, h = op->h, lo_mask = op->lo_mask;
+  }
+  const int ndiag = ch->ndiag, nflip = ch->nflip;
+  const SpinRankTables tab{lo_rank, hi_base};
+  const double* col[J];
+#pragma unroll
+  for (int j = 0; j < J; ++j) col[j] = V + (int64_t)(j < ncols ? j : ncols - 1) * ldv;
+  double dg[C * J], fl[C * J];
+#pragma unroll
+  for (int i = 0; i < C * J; ++i) dg[i] = 0.0, fl[i] = 0.0;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + threadIdx.x;
+    if (r < n) {
+      double v[J];
+#pragma unroll
+      for (int j = 0; j < J; ++j) v[j] = __builtin_nontemporal_load(col[j] + r);
+      const uint32_t s = SECTOR ? spin_unrank_row(SpinBinomials32{binom}, n_sites, n_up, (uint32_t)r).s : (uint32_t)r;
+      spin_measure_columns_row<SECTOR>(ch->dmask, ndiag, ch->fmask, nflip, s, x[r], SpinVector{x}, tab, h, lo_mask, v, dg, fl);
+    }
+  }
+  const auto put = [&](int a, double mine) {
+    const double sum = block_sum(mine, lds4);
+    if (threadIdx.x == 0) partials[(int64_t)a * pstride + blockIdx.x] = sum;
+  };
+  // a batch without a term has nothing but zeros: its sums are not reduced, and the second stage does not read them
+#pragma unroll
+  for (int t0 = 0; t0 < C; t0 += kSpinBatch)
+    if (t0 < ndiag) {
+#pragma unroll
+      for (int i = t0 * J; i < (t0 + kSpinBatch) * J; ++i) put(i, dg[i]);
+    }
+#pragma unroll
+  for (int t0 = 0; t0 < C; t0 += kSpinBatch)
+    if (t0 < nflip) {
+#pragma unroll
+      for (int i = t0 * J; i < (t0 + kSpinBatch) * J; ++i) put(C * J + i, fl[i]);
+    }
+}
+
+// Second stage of k_spin_measure_columns, one workgroup per sum a = (kind * C + t) * J + j, the partials of the nblocks workgroups
+// added in k_reduce_fin's order and stored to diag_out[t * ldo + j] (kind 0) or flip_out[t * ldo + j] (kind 1).  A sum beyond the
+// chunk's live terms or the launch's live columns has no destination and is dropped.
+__global__ __launch_bounds__(kBlock) void k_spin_measure_columns_reduce(const double* __restrict__ partials, int pstride, int nblocks, int ndiag,
+                                                                        int nflip, int ncols, int ldo, double* __restrict__ diag_out,
+                                                                        double* __restrict__ flip_out) {
+  constexpr int C = kSpinMeasureChunk, J = kSpinMeasureColumns;
+  __shared__ double lds4[4];
+  const int a = blockIdx.x, kind = a / (C * J), t = (a % (C * J)) / J, j = a % J;
+  if (j >= ncols || t >= (kind == 0 ? ndiag : nflip)) return;  // the same for the whole workgroup
+  double* dst = (kind == 0 ? diag_out : flip_out) + (int64_t)t * ldo + j;
+  const double* p = partials + (int64_t)a * pstride;
+  double s = 0.0;
+  for (int b = threadIdx.x; b < nblocks; b += kBlock) s += p[b];
+  s = block_sum(s, lds4);
+  if (threadIdx.x == 0) *dst = s;
+}
+
+// ---------------------------------------------------------------------------
 // A sum of site operators applied to a vector (spin_site.hpp has the definition and SpinSiteTable; spin_rows.hpp the walk): one
 // row of the DESTINATION per lane, 256-row tiles, the operator kernels' persistent grid and LDS binomials.  dst_op is the
 // destination operator's view (its binomials and n_up unrank the row; not read in the full space), src_lo and src_hi are the
@@ -3451,6 +3545,20 @@ void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstri
                                 double* flip_out, double* norm_out) {
   hipLaunchKernelGGL(k_spin_measure_reduce, dim3(2 * kSpinMeasureChunk + 1), dim3(kBlock), 0, s, partials, pstride, nblocks, ndiag, nflip,
                      diag_out, flip_out, norm_out);
+}
+
+void launch_spin_measure_columns(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
+                                 const uint32_t* hi_base, const double* x, const double* V, int64_t ldv, int ncols, int64_t n, double* partials,
+                                 int pstride, int grid) {
+  const auto kernel = lo_rank ? k_spin_measure_columns<true> : k_spin_measure_columns<false>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, chunk, op, lo_rank, hi_base, x, V, ldv, ncols, n, (n + kBlock - 1) / kBlock, partials,
+                     pstride);
+}
+
+void launch_spin_measure_columns_reduce(hipStream_t s, const double* partials, int pstride, int nblocks, int ndiag, int nflip, int ncols, int ldo,
+                                        double* diag_out, double* flip_out) {
+  hipLaunchKernelGGL(k_spin_measure_columns_reduce, dim3(2 * kSpinMeasureChunk * kSpinMeasureColumns), dim3(kBlock), 0, s, partials, pstride,
+                     nblocks, ndiag, nflip, ncols, ldo, diag_out, flip_out);
 }
 
 template <class E>

@@ -385,6 +385,19 @@ void launch_spin_measure(hipStream_t s, int es, const SpinMeasureChunk* chunk, c
 // diag_out[t] and flip_out[t], norm2 to *norm_out unless that is NULL
 void launch_spin_measure_reduce(hipStream_t s, const double* partials, int pstride, int nblocks, int ndiag, int nflip, double* diag_out,
                                 double* flip_out, double* norm_out);
+// The observables of the real vector x against ncols = 1 .. kSpinMeasureColumns columns V, V + ldv, ... (eigenex_spin_measure_columns;
+// spin_measure_columns.hpp has the definition): one chunk of terms and one chunk of columns per launch; chunk, op, lo_rank and
+// hi_base as for launch_spin_measure.  x and V are only read and may overlap.  The grid's partial sums go to partials[sum *
+// pstride + workgroup], sum = t * J + j (diag) and (kSpinMeasureChunk + t) * J + j (flip), J = kSpinMeasureColumns: 2 *
+// kSpinMeasureChunk * J * pstride doubles, pstride >= grid; the sums of a batch of kSpinBatch terms without a live term are not
+// written.  Always runs.
+void launch_spin_measure_columns(hipStream_t s, const SpinMeasureChunk* chunk, const SpinSectorView* op, const uint32_t* lo_rank,
+                                 const uint32_t* hi_base, const double* x, const double* V, int64_t ldv, int ncols, int64_t n, double* partials,
+                                 int pstride, int grid);
+// its second stage: the partials of nblocks workgroups added in a fixed order, the live sums stored to diag_out[t * ldo + j] and
+// flip_out[t * ldo + j], t below the chunk's ndiag or nflip, j below ncols
+void launch_spin_measure_columns_reduce(hipStream_t s, const double* partials, int pstride, int nblocks, int ndiag, int nflip, int ncols, int ldo,
+                                        double* diag_out, double* flip_out);
 // A sum of site operators applied to x, y = O x (eigenex_spin_site_apply; spin_site.hpp has the definition and the table): one
 // launch.  table, dst_op, src_lo and src_hi live in device memory.  y has n rows, those of the DESTINATION operator, whose view
 // dst_op is; src_lo and src_hi are the rank tables of the SOURCE operator, on whose rows x lives (full space: null tables, dst_op

@@ -2420,7 +2420,9 @@ void fill_state(const Ctrl& ct, eigenex_state_t* st) {
 //   eigenex_basis_capacity, eigenex_basis_is_complex, eigenex_basis_graph_info, eigenex_basis_close_pending      getters
 //   eigenex_basis_clear              drops the pending close with the state it belonged to
 //   eigenex_basis_destroy
-// A new entry point is not on the list, so it settles.
+// A new entry point is not on the list, so it settles.  (One settles only where it must: the columns measurement of
+// spin_measure_columns.hpp reads vectors and writes nothing, so it closes the pending column when that column is among those it
+// reads and leaves the state as the batch left it otherwise.)
 // ===========================================================================
 extern "C" {
 
@@ -3539,6 +3541,76 @@ int eigenex_spin_measure(eigenex_basis_t b, int x_ref, int n_diag, const uint32_
   if (norm2) *norm2 = out[0];
   for (int t = 0; t < n_diag; ++t) diag_out[t] = out[(size_t)(1 + t)];
   for (int t = 0; t < n_flip; ++t) flip_out[t] = out[(size_t)(1 + n_diag + t)];
+  return 0;
+}
+
+int eigenex_spin_measure_columns_host(int n_sites, int n_up, const double* x, const double* V, int64_t ldv, int count, int n_diag,
+                                      const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks, double* diag_out, double* flip_out) {
+  const std::string who = "eigenex_spin_measure_columns_host";
+  const SpinMeasureArgs a{n_sites, n_up, n_diag, diag_masks, n_flip, flip_masks};
+  if (const char* why = spin_measure_error(a)) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  if (!x || !V) return fail(EIGENEX_ERR_ARG, who + ": x or V is NULL");
+  if (count < 1) return fail(EIGENEX_ERR_ARG, who + ": count must be at least 1");
+  if (ldv < spin_measure_rows(a)) return fail(EIGENEX_ERR_ARG, who + ": ldv is smaller than the number of rows");
+  if ((n_diag > 0 && !diag_out) || (n_flip > 0 && !flip_out)) return fail(EIGENEX_ERR_ARG, who + ": an output list is NULL but its count is not zero");
+  spin_measure_columns_host(a, x, V, ldv, count, diag_out, flip_out);
+  return 0;
+}
+
+int eigenex_spin_measure_columns(eigenex_basis_t b, int x_ref, int first, int count, int n_diag, const uint32_t* diag_masks, int n_flip,
+                                 const uint32_t* flip_masks, double* diag_out, double* flip_out) {
+  const std::string who = "eigenex_spin_measure_columns";
+  if (!b) return fail(EIGENEX_ERR_ARG, who + ": basis is NULL");
+  const std::string served = " (served: real states of eigenex_spin_upload and eigenex_spin_sector_upload handles)";
+  if (!b->csr) return fail(EIGENEX_ERR_STATE, who + ": the state has no device operator: a host callback knows no sites" + served);
+  if (b->sh.size() != 1 || !b->sh[0].csr || !b->sh[0].csr->spin.on())
+    return fail(EIGENEX_ERR_STATE, who + (b->sh.size() == 1 && b->sh[0].csr && b->sh[0].csr->momentum.on()
+                                              ? ": the operator of this state is a momentum-sector operator, whose rows are orbits and not states"
+                                              : ": the operator of this state is a stored operator, not a matrix-free spin operator") + served);
+  if (b->es != 1) return fail(EIGENEX_ERR_STATE, who + ": real states only, this one is complex" + served);
+  BasisShard& s = b->sh[0];
+  const CsrShard* m = s.csr;
+  const SpinMeasureArgs a{m->spin.n_sites, m->spin.n_up, n_diag, diag_masks, n_flip, flip_masks};
+  if (const char* why = spin_measure_error(a)) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  if (const char* why = spin_measure_columns_error(first, count, b->cap)) return fail(EIGENEX_ERR_ARG, who + ": " + why);
+  if ((n_diag > 0 && !diag_out) || (n_flip > 0 && !flip_out)) return fail(EIGENEX_ERR_ARG, who + ": an output list is NULL but its count is not zero");
+  const double* x = vec_ptr(s, b->cap, b->nq, x_ref);
+  if (!x) return fail(EIGENEX_ERR_ARG, who + ": bad vector reference");
+  // A pending close is about the newest column alone.  It is closed, through the path every other entry point takes, only where
+  // this call reads that column; otherwise the state stays exactly as the batch left it.
+  const int pending = b->cur.close_pending;
+  if (pending >= 0 && (x_ref == pending || (pending >= first && pending < first + count))) CHK(enter_settled(b));
+  if (n_diag + n_flip == 0) return 0;
+  eigenex_context_s* c = b->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  // scratch of this call alone, as in eigenex_spin_measure: the chunk table, the grid's partial sums of one launch (reused from
+  // launch to launch: they are ordered on the stream) and the results [diag, flip].  The state's own partials may hold a pending alpha.
+  std::vector<SpinMeasureChunk> chunks;
+  spin_measure_build_chunks(a, chunks);
+  const int grid = s.g_spmv, nsums = 2 * kSpinMeasureChunk * kSpinMeasureColumns;
+  DeviceBuffer<SpinMeasureChunk> d_chunks;
+  DeviceBuffer<double> d_part, d_out;
+  const size_t nd = (size_t)n_diag * (size_t)count, nf = (size_t)n_flip * (size_t)count;
+  std::vector<double> out(nd + nf, 0.0);
+  HIPCHK(d_chunks.alloc(chunks.size()));
+  HIPCHK(d_part.alloc((size_t)nsums * grid));
+  HIPCHK(d_out.alloc(out.size()));
+  HIPCHK(hipMemcpyAsync(d_chunks, chunks.data(), sizeof(SpinMeasureChunk) * chunks.size(), hipMemcpyHostToDevice, c->stream));
+  for (size_t k = 0; k < chunks.size(); ++k) {
+    const size_t tfirst = k * kSpinMeasureChunk;  // a list that ends before `tfirst` has no live sum in this chunk
+    const size_t dfirst = std::min(tfirst, (size_t)n_diag), ffirst = std::min(tfirst, (size_t)n_flip);
+    for (int j0 = 0; j0 < count; j0 += kSpinMeasureColumns) {
+      const int ncols = std::min(kSpinMeasureColumns, count - j0);
+      launch_spin_measure_columns(c->stream, d_chunks + k, m->spin.view, m->spin.lo, m->spin.hi, x, s.V + (int64_t)(first + j0) * s.ldd, s.ldd, ncols,
+                                  s.nloc, d_part, grid, grid);
+      launch_spin_measure_columns_reduce(c->stream, d_part, grid, grid, chunks[k].ndiag, chunks[k].nflip, ncols, count, d_out + dfirst * count + j0,
+                                         d_out + nd + ffirst * count + j0);
+    }
+  }
+  HIPCHK(hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // the one synchronisation: the staging buffers and the scratch live until here
+  for (size_t i = 0; i < nd; ++i) diag_out[i] = out[i];
+  for (size_t i = 0; i < nf; ++i) flip_out[i] = out[nd + i];
   return 0;
 }
 

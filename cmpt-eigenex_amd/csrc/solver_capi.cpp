@@ -11,6 +11,7 @@
 //   eigenex_zarnoldi_solver_*  ArnoldiEigenSolver<std::complex<double>>
 // plus eigenex_[z]trlanczos_solver_* (ThickRestartLanczosEigenSolver), eigenex_[z]kschur_solver_* (KrylovSchurEigenSolver) and
 // eigenex_[z]flanczos_solver_* (FilteredLanczosEigenSolver); eigenex_[z]density_solver_* (SpectralDensitySolver);
+// eigenex_[z]thermal_solver_* (ThermalLanczosSolver) and eigenex_thermal_ensemble_* (ThermalEnsemble);
 // eigenex_spin_dynamics_solver_* (SpinDynamicsSolver); eigenex_spin_momentum_dynamics_solver_* (SpinMomentumDynamicsSolver);
 // eigenex_spin_entanglement_solver_* (SpinEntanglementSolver);
 // eigenex_spin_evolution_solver_* (SpinTimeEvolutionSolver); eigenex_spin_time_correlation_solver_* (SpinTimeCorrelationSolver).
@@ -34,6 +35,7 @@
 #include "cmpt/eigen_ex/spin_entanglement.hpp"
 #include "cmpt/eigen_ex/spin_evolution.hpp"
 #include "cmpt/eigen_ex/spin_time_correlation.hpp"
+#include "cmpt/eigen_ex/thermal_lanczos.hpp"
 #include "cmpt/eigen_ex/thick_restart_lanczos.hpp"
 #include "cmpt/eigen_ex/triplets_operator.hpp"
 
@@ -833,6 +835,111 @@ int eigenex_solver_kpm_window(const double* mu, int M, double center, double hal
   return guard([&] {
     if (M < 1 || !mu || !(halfwidth > 0.0)) throw LanczosException("kpm_window: mu[M], M >= 1 and halfwidth > 0 are required");
     *out = kpmWindow(mu, M, center, halfwidth, tau, count, N);
+  });
+}
+
+// ThermalLanczosSolver (thermal_lanczos.hpp): _set takes "lanczosSteps" and "randomVectors"; _set_seed the seed and the first
+// stream; _set_sample_vectors R vectors of n entries (NULL: random vectors again); _set_spin_observables the two mask lists
+// (n_diag = -1: setAllSitesAndPairs) and writes the returned ComputationInfo to *info.  _sizes: dimension, samples, operator
+// applications, log lines, info, diagonal terms, flip terms, sites of setAllSitesAndPairs (0: other masks).  _value: quantity
+// 0 log Z, 1 E, 2 C, 3 S, 4 F, 5 observable t (diagonal list, then flip list); value and its jackknife error (either may be NULL).
+// _correlation: kind 0 ZZ, 1 XY, 2 SS of sites i, j.  _sample: theta and weight of sample r (*n entries; pointers may be NULL).
+#define EIGENEX_THERMAL_FAMILY(PFX, SOLVER)                                                                                              \
+  void* PFX##create(void) {                                                                                                              \
+    try {                                                                                                                                \
+      return new Box<SOLVER>();                                                                                                          \
+    } catch (const std::exception& e) {                                                                                                  \
+      g_serr = e.what();                                                                                                                 \
+      return nullptr;                                                                                                                    \
+    }                                                                                                                                    \
+  }                                                                                                                                      \
+  void PFX##destroy(void* p) { delete static_cast<Box<SOLVER>*>(p); }                                                                    \
+  int PFX##set_device_operator(void* p, eigenex_context_t ctx, eigenex_csr_t csr) { return sv_set_device_operator<SOLVER>(p, ctx, csr); } \
+  int PFX##set(void* p, const char* key, double v, double) {                                                                             \
+    return guard([&] {                                                                                                                   \
+      auto& es = static_cast<Box<SOLVER>*>(p)->es;                                                                                       \
+      const std::string k(key);                                                                                                          \
+      if (k == "lanczosSteps") es.setLanczosSteps((Index)v);                                                                             \
+      else if (k == "randomVectors") es.setRandomVectors((Index)v);                                                                      \
+      else throw LanczosException("unknown setting: " + k);                                                                              \
+    });                                                                                                                                  \
+  }                                                                                                                                      \
+  int PFX##set_seed(void* p, uint64_t seed, uint64_t first_stream) {                                                                     \
+    return guard([&] { static_cast<Box<SOLVER>*>(p)->es.setSeed(seed).setFirstStream(first_stream); });                                  \
+  }                                                                                                                                      \
+  int PFX##set_sample_vectors(void* p, const double* v, int64_t n, int64_t count) {                                                      \
+    return guard([&] { static_cast<Box<SOLVER>*>(p)->es.setSampleVectors(reinterpret_cast<const SOLVER::Scalar*>(v), (Index)n, (Index)count); }); \
+  }                                                                                                                                      \
+  int PFX##set_spin_observables(void* p, int n_diag, const uint32_t* diag, int n_flip, const uint32_t* flip, int* info) {                \
+    return guard([&] {                                                                                                                   \
+      auto& es = static_cast<Box<SOLVER>*>(p)->es;                                                                                       \
+      const ComputationInfo r = n_diag < 0 ? es.setAllSitesAndPairs()                                                                    \
+                                           : es.setSpinObservables(std::vector<uint32_t>(diag, diag + n_diag), std::vector<uint32_t>(flip, flip + n_flip)); \
+      if (info) *info = (int)r;                                                                                                          \
+    });                                                                                                                                  \
+  }                                                                                                                                      \
+  int PFX##compute(void* p) { return guard([&] { static_cast<Box<SOLVER>*>(p)->es.compute(); }); }                                       \
+  int PFX##sizes(void* p, int64_t* out) {                                                                                                \
+    return guard([&] {                                                                                                                   \
+      auto& es = static_cast<Box<SOLVER>*>(p)->es;                                                                                       \
+      out[0] = (int64_t)es.dimension(), out[1] = (int64_t)es.samples(), out[2] = (int64_t)es.operatorApplications();                     \
+      out[3] = (int64_t)es.log().size(), out[4] = (int64_t)es.info(), out[5] = (int64_t)es.diagonalTerms();                              \
+      out[6] = (int64_t)es.flipTerms(), out[7] = (int64_t)es.sitesWithAllPairs();                                                        \
+    });                                                                                                                                  \
+  }                                                                                                                                      \
+  int PFX##value(void* p, int quantity, int64_t t, double beta, double* value, double* standard_error) {                                 \
+    return guard([&] {                                                                                                                   \
+      if (quantity < 0 || quantity > 5) throw LanczosException("thermal solver: quantity must be 0..5");                                 \
+      auto& es = static_cast<Box<SOLVER>*>(p)->es;                                                                                       \
+      if (value) *value = es.sums().value((ThermalQuantity)quantity, beta, (std::size_t)t);                                              \
+      if (standard_error) *standard_error = es.standardError((ThermalQuantity)quantity, beta, (Index)t);                                 \
+    });                                                                                                                                  \
+  }                                                                                                                                      \
+  int PFX##correlation(void* p, int kind, int i, int j, double beta, double* value) {                                                    \
+    return guard([&] {                                                                                                                   \
+      auto& es = static_cast<Box<SOLVER>*>(p)->es;                                                                                       \
+      *value = kind == 0 ? es.correlationZZ(i, j, beta) : kind == 1 ? es.correlationXY(i, j, beta) : es.correlationSS(i, j, beta);       \
+    });                                                                                                                                  \
+  }                                                                                                                                      \
+  int PFX##sample(void* p, int64_t r, int64_t* n, double* theta, double* weight) {                                                       \
+    return guard([&] {                                                                                                                   \
+      const ThermalSample& s = static_cast<Box<SOLVER>*>(p)->es.sums().sample((std::size_t)r);                                           \
+      if (n) *n = (int64_t)s.theta.size();                                                                                               \
+      if (theta) std::copy(s.theta.begin(), s.theta.end(), theta);                                                                       \
+      if (weight) std::copy(s.weight.begin(), s.weight.end(), weight);                                                                   \
+    });                                                                                                                                  \
+  }                                                                                                                                      \
+  int PFX##add_to_ensemble(void* p, void* ensemble, double multiplicity, double magnetisation) {                                         \
+    return guard([&] { static_cast<ThermalEnsemble*>(ensemble)->add(static_cast<Box<SOLVER>*>(p)->es, multiplicity, magnetisation); });  \
+  }                                                                                                                                      \
+  const char* PFX##log_line(void* p, int64_t i) { return sv_log_line<SOLVER>(p, i); }
+
+EIGENEX_THERMAL_FAMILY(eigenex_thermal_solver_, ThermalLanczosSolver<double>)
+EIGENEX_THERMAL_FAMILY(eigenex_zthermal_solver_, ThermalLanczosSolver<std::complex<double>>)
+
+// ThermalEnsemble (thermal_lanczos.hpp); sectors are added by eigenex_[z]thermal_solver_add_to_ensemble.  _value: quantity 0 log Z,
+// 1 E, 2 C, 3 S, 4 susceptibility per site, 5 observable t.
+void* eigenex_thermal_ensemble_create(int sites) {
+  try {
+    return new ThermalEnsemble(sites);
+  } catch (const std::exception& e) {
+    g_serr = e.what();
+    return nullptr;
+  }
+}
+void eigenex_thermal_ensemble_destroy(void* e) { delete static_cast<ThermalEnsemble*>(e); }
+int eigenex_thermal_ensemble_value(void* e, int quantity, int64_t t, double beta, double* value) {
+  return guard([&] {
+    const ThermalEnsemble& en = *static_cast<ThermalEnsemble*>(e);
+    switch (quantity) {
+      case 0: *value = en.logPartitionFunction(beta); break;
+      case 1: *value = en.energy(beta); break;
+      case 2: *value = en.specificHeat(beta); break;
+      case 3: *value = en.entropy(beta); break;
+      case 4: *value = en.susceptibility(beta); break;
+      case 5: *value = en.observable((std::size_t)t, beta); break;
+      default: throw LanczosException("thermal ensemble: quantity must be 0..5");
+    }
   });
 }
 

@@ -1,8 +1,8 @@
 // The row walk of the matrix-free spin-1/2 kernels (kernels.hip: k_spin_spmv<SECTOR, E> and k_spin_measure<SECTOR, E>, each
 // written once for real (E = double) and complex (E = SpinZ) vectors, as k_spin_site_apply<SECTOR, E> is, and through spin_rdm_rows.hpp
-// k_spin_rdm<SECTOR, TILE, E>; at the end of this file the walk of k_spin_momentum_spmv<E>, k_spin_momentum_expand<E> and
+// k_spin_rdm<SECTOR, TILE, E>; k_spin_measure_columns<SECTOR> for real vectors: spin_measure_columns_row; at the end of this file the walk of k_spin_momentum_spmv<E>, k_spin_momentum_expand<E> and
 // k_spin_momentum_site_apply<E, Word>), shared by the device code and by the host replays
-// tests/cpp/spin_{model,sector,measure,site,site_z,rdm,rdm_z,complex,momentum,momentum_site}_sanitize.cpp, which run it under AddressSanitizer +
+// tests/cpp/spin_{model,sector,measure,measure_columns,site,site_z,rdm,rdm_z,complex,momentum,momentum_site}_sanitize.cpp, which run it under AddressSanitizer +
 // UBSan.  The kernels and the replays call THESE functions, so what a replay proves about them (every load inside its array, the
 // state equal to spin_sector_unrank, the sums equal to the CSR row loop and to spin_measure_host bit for bit) holds for the
 // kernels' rows as compiled.  No device construct in here: plain C++11.  spin_write_rows, spin_sector_unrank, spin_sector_rank
@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "spin_measure.hpp"
+#include "spin_measure_columns.hpp"
 #include "spmv_index.hpp"
 
 #if defined(__clang__)
@@ -173,6 +174,43 @@ EIGENEX_HD void spin_measure_diagonals(SpinZ xs, uint32_t s, const uint32_t* dma
     dg[t] = std::fma(neg ? -xs.re : xs.re, xs.re, dg[t]);
     dg[t] = std::fma(neg ? -xs.im : xs.im, xs.im, dg[t]);
   }
+}
+
+// One row of a chunk's observables against kSpinMeasureColumns columns (spin_measure_columns.hpp; kernels.hip:
+// k_spin_measure_columns<SECTOR>): the values w_t = (A_t x)(s) of a batch are formed once -- a sign times the row's own element
+// xs, or the gathered x of phases 1 and 2 above, zero where the row has no entry -- and then meet every column's element v[j] in
+// one fma each: sum[t * kSpinMeasureColumns + j] = fma(v[j], w_t, sum[..]).  A batch is skipped as a whole where the chunk has no
+// term in it (ndiag and nflip are the same for every lane); a padded term (mask 0) sums into a slot nobody reads.
+template <bool SECTOR, class Tables, class Vector>
+EIGENEX_HD void spin_measure_columns_row(const uint32_t* dmask, int ndiag, const uint32_t* fmask, int nflip, uint32_t s, double xs, const Vector& x,
+                                         const Tables& tab, int h, uint32_t lo_mask, const double* v, double* dg, double* fl) {
+  EIGENEX_UNROLL
+  for (int t0 = 0; t0 < kSpinMeasureChunk; t0 += kSpinBatch)
+    if (t0 < ndiag) {
+      EIGENEX_UNROLL
+      for (int t = 0; t < kSpinBatch; ++t) {
+        const double w = spin_odd(~s & dmask[t0 + t]) ? -xs : xs;
+        EIGENEX_UNROLL
+        for (int j = 0; j < kSpinMeasureColumns; ++j)
+          dg[(t0 + t) * kSpinMeasureColumns + j] = std::fma(v[j], w, dg[(t0 + t) * kSpinMeasureColumns + j]);
+      }
+    }
+  EIGENEX_UNROLL
+  for (int t0 = 0; t0 < kSpinMeasureChunk; t0 += kSpinBatch)
+    if (t0 < nflip) {
+      bool on[kSpinBatch];
+      uint32_t base[kSpinBatch], low[kSpinBatch];
+      double xv[kSpinBatch];
+      spin_flip_targets<SECTOR>(fmask + t0, s, tab, h, lo_mask, on, base, low);
+      spin_gather(x, base, low, xv);
+      EIGENEX_UNROLL
+      for (int t = 0; t < kSpinBatch; ++t) {
+        const double w = on[t] ? xv[t] : 0.0;
+        EIGENEX_UNROLL
+        for (int j = 0; j < kSpinMeasureColumns; ++j)
+          fl[(t0 + t) * kSpinMeasureColumns + j] = std::fma(v[j], w, fl[(t0 + t) * kSpinMeasureColumns + j]);
+      }
+    }
 }
 
 // ---- a sum of site operators (spin_site.hpp; kernels.hip: k_spin_site_apply<SECTOR, E>), one row of the DESTINATION per lane ----

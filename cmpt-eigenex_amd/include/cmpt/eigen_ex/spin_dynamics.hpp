@@ -35,7 +35,7 @@
 //
 // Out of scope: products of site operators as O; a basis-free three-term recurrence for
 // very long fractions (the run keeps m + 1 columns, like every Lanczos run here); more than one GPU (the matrix-free spin
-// operators are one shard); finite temperature.
+// operators are one shard); finite temperature (static quantities: thermal_lanczos.hpp).
 #pragma once
 
 #include <algorithm>

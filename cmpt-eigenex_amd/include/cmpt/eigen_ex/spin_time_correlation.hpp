@@ -33,7 +33,7 @@
 // changes sets the run up again.
 //
 // Out of scope: operators of different kinds in one run (A of another kind than B changes the sector of psi and of phi
-// differently); products of site operators; finite temperature; more than one GPU.
+// differently); products of site operators; finite temperature (static quantities: thermal_lanczos.hpp); more than one GPU.
 #pragma once
 
 #include <algorithm>

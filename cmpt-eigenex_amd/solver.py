@@ -84,6 +84,30 @@ def lib():
             getattr(L, p + "energy_window").argtypes = [_vp, C.c_double, C.c_double, _dp]
             getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
             getattr(L, p + "log_line").restype = C.c_char_p
+        _up32 = C.POINTER(C.c_uint32)
+        for kind in ("thermal", "zthermal"):
+            p = f"eigenex_{kind}_solver_"
+            getattr(L, p + "create").restype = _vp
+            getattr(L, p + "destroy").argtypes = [_vp]
+            getattr(L, p + "destroy").restype = None
+            getattr(L, p + "set_device_operator").argtypes = [_vp, _vp, _vp]
+            getattr(L, p + "set").argtypes = [_vp, C.c_char_p, C.c_double, C.c_double]
+            getattr(L, p + "set_seed").argtypes = [_vp, C.c_uint64, C.c_uint64]
+            getattr(L, p + "set_sample_vectors").argtypes = [_vp, _dp, C.c_int64, C.c_int64]
+            getattr(L, p + "set_spin_observables").argtypes = [_vp, C.c_int, _up32, C.c_int, _up32, C.POINTER(C.c_int)]
+            getattr(L, p + "compute").argtypes = [_vp]
+            getattr(L, p + "sizes").argtypes = [_vp, _lp]
+            getattr(L, p + "value").argtypes = [_vp, C.c_int, C.c_int64, C.c_double, _dp, _dp]
+            getattr(L, p + "correlation").argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _dp]
+            getattr(L, p + "sample").argtypes = [_vp, C.c_int64, _lp, _dp, _dp]
+            getattr(L, p + "add_to_ensemble").argtypes = [_vp, _vp, C.c_double, C.c_double]
+            getattr(L, p + "log_line").argtypes = [_vp, C.c_int64]
+            getattr(L, p + "log_line").restype = C.c_char_p
+        L.eigenex_thermal_ensemble_create.argtypes = [C.c_int]
+        L.eigenex_thermal_ensemble_create.restype = _vp
+        L.eigenex_thermal_ensemble_destroy.argtypes = [_vp]
+        L.eigenex_thermal_ensemble_destroy.restype = None
+        L.eigenex_thermal_ensemble_value.argtypes = [_vp, C.c_int, C.c_int64, C.c_double, _dp]
         _ip32 = C.POINTER(C.c_int32)
         p = "eigenex_spin_momentum_dynamics_solver_"
         getattr(L, p + "set_model").argtypes = [_vp, _vp, C.c_int, C.c_int, _ip32, _ip32, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int]
@@ -684,6 +708,184 @@ class SpectralDensitySolver(_SolverBase):
         d = C.c_double()
         _chk(self._f("energy_window")(self.h, tau, count, C.byref(d)))
         return d.value
+
+
+class ThermalLanczosSolver(_SolverBase):
+    """ThermalLanczosSolver<S> (thermal_lanczos.hpp): the finite-temperature Lanczos method on one Hermitian device operator --
+    log Z, E, C, S, F from R runs of M steps, and thermal averages of spin observables (real states of matrix-free spin operators)
+    through eigenex_spin_measure_columns.  Settings: lanczosSteps, randomVectors, seed, firstStream; setSampleVectors for explicit
+    start vectors; setSpinObservables / setAllSitesAndPairs for the observables (they return the ComputationInfo's name)."""
+
+    _base = "thermal"
+    _names = ("dimension", "samples", "operatorApplications", "nlog", "info", "ndiag", "nflip", "sites")
+    QUANTITIES = ("logPartitionFunction", "energy", "specificHeat", "entropy", "freeEnergy", "observable")
+
+    def __init__(self, dtype=np.float64):
+        super().__init__(dtype)
+        self._seed = [0, 0]
+
+    def set(self, **kw):
+        for k, v in kw.items():
+            if k in ("seed", "firstStream"):
+                self._seed[k == "firstStream"] = int(v)
+                _chk(self._f("set_seed")(self.h, *self._seed))
+            else:
+                _chk(self._f("set")(self.h, k.encode(), float(v), 0.0))
+        return self
+
+    def setSampleVectors(self, vectors):
+        """vectors: (R, N), one start vector per row; None returns to random sign vectors"""
+        if vectors is None:
+            _chk(self._f("set_sample_vectors")(self.h, None, 0, 0))
+        else:
+            a = np.ascontiguousarray(vectors, self.dtype)
+            _chk(self._f("set_sample_vectors")(self.h, _d(a.view(np.float64)), a.shape[1], a.shape[0]))
+        return self
+
+    def _observables(self, nd, dp, nf, fp):
+        info = C.c_int()
+        _chk(self._f("set_spin_observables")(self.h, nd, dp, nf, fp, C.byref(info)))
+        return INFO[info.value]
+
+    def setSpinObservables(self, diag_masks, flip_masks):
+        u = C.POINTER(C.c_uint32)
+        d, f = np.ascontiguousarray(diag_masks, np.uint32).reshape(-1), np.ascontiguousarray(flip_masks, np.uint32).reshape(-1)
+        return self._observables(d.size, d.ctypes.data_as(u) if d.size else None, f.size, f.ctypes.data_as(u) if f.size else None)
+
+    def setAllSitesAndPairs(self):
+        return self._observables(-1, None, 0, None)
+
+    def _sizes(self):
+        out = np.zeros(len(self._names), np.int64)
+        _chk(self._f("sizes")(self.h, out.ctypes.data_as(_lp)))
+        return dict(zip(self._names, (int(x) for x in out)))
+
+    def results(self):
+        s = self._sizes()
+        s["info_name"] = INFO[s["info"]]
+        return s
+
+    def sample(self, r):
+        """(theta, weight) of sample r: the Ritz values of its tridiagonal matrix and their weights in the start vector"""
+        n = C.c_int64()
+        _chk(self._f("sample")(self.h, r, C.byref(n), None, None))
+        th, w = np.zeros(n.value), np.zeros(n.value)
+        _chk(self._f("sample")(self.h, r, None, _d(th), _d(w)))
+        return th, w
+
+    def _value(self, q, beta, t=0, error=False):
+        v = C.c_double()
+        _chk(self._f("value")(self.h, q, int(t), float(beta), None if error else C.byref(v), C.byref(v) if error else None))
+        return v.value
+
+    def logPartitionFunction(self, beta):
+        return self._value(0, beta)
+
+    def energy(self, beta):
+        return self._value(1, beta)
+
+    def specificHeat(self, beta):
+        return self._value(2, beta)
+
+    def entropy(self, beta):
+        return self._value(3, beta)
+
+    def freeEnergy(self, beta):
+        return self._value(4, beta)
+
+    def diagonal(self, t, beta):
+        s = self._sizes()
+        if not 0 <= t < s["ndiag"]:
+            raise capi.EigenexError("no such diagonal observable")
+        return self._value(5, beta, t)
+
+    def flip(self, t, beta):
+        s = self._sizes()
+        if not 0 <= t < s["nflip"]:
+            raise capi.EigenexError("no such flip observable")
+        return self._value(5, beta, s["ndiag"] + t)
+
+    def _correlation(self, kind, i, j, beta):
+        v = C.c_double()
+        _chk(self._f("correlation")(self.h, kind, int(i), int(j), float(beta), C.byref(v)))
+        return v.value
+
+    def correlationZZ(self, i, j, beta):
+        return self._correlation(0, i, j, beta)
+
+    def correlationXY(self, i, j, beta):
+        return self._correlation(1, i, j, beta)
+
+    def correlationSS(self, i, j, beta):
+        return self._correlation(2, i, j, beta)
+
+    def observableIndex(self, which, i, j=None):
+        """the index `t` that standardError takes for an observable: which = "diagonal" or "flip" with the list index i, or "ZZ"
+        / "XY" with the sites i, j after setAllSitesAndPairs"""
+        s = self._sizes()
+        if which in ("diagonal", "flip"):
+            return i if which == "diagonal" else s["ndiag"] + i
+        L = s["sites"]
+        if L == 0 or i == j or not (0 <= i < L and 0 <= j < L):
+            raise capi.EigenexError("the correlations need setAllSitesAndPairs() and two different sites of the model")
+        a, b = min(i, j), max(i, j)
+        p = a * L - a * (a + 1) // 2 + (b - a - 1)
+        return L + p if which == "ZZ" else s["ndiag"] + p
+
+    def standardError(self, quantity, beta, t=0):
+        """the delete-one jackknife error over the samples of quantity (a name of QUANTITIES); t as observableIndex gives it"""
+        return self._value(self.QUANTITIES.index(quantity), beta, t, error=True)
+
+
+class ThermalEnsemble:
+    """ThermalEnsemble (thermal_lanczos.hpp): sectors added up with multiplicities; multiplicity 2 stands for a sector and its
+    image under spin inversion at +M and -M.  observable(t, beta) is valid for terms invariant under that symmetry."""
+
+    _quantities = ("logPartitionFunction", "energy", "specificHeat", "entropy", "susceptibility", "observable")
+
+    def __init__(self, sites=0):
+        self._L = lib()
+        self.h = _vp(self._L.eigenex_thermal_ensemble_create(int(sites)))
+        if not self.h:
+            raise capi.EigenexError("ensemble create failed")
+
+    def add(self, solver: ThermalLanczosSolver, multiplicity=1.0, magnetisation=0.0):
+        _chk(solver._f("add_to_ensemble")(solver.h, self.h, float(multiplicity), float(magnetisation)))
+        return self
+
+    def _value(self, q, beta, t=0):
+        v = C.c_double()
+        _chk(self._L.eigenex_thermal_ensemble_value(self.h, q, int(t), float(beta), C.byref(v)))
+        return v.value
+
+    def logPartitionFunction(self, beta):
+        return self._value(0, beta)
+
+    def energy(self, beta):
+        return self._value(1, beta)
+
+    def specificHeat(self, beta):
+        return self._value(2, beta)
+
+    def entropy(self, beta):
+        return self._value(3, beta)
+
+    def susceptibility(self, beta):
+        return self._value(4, beta)
+
+    def observable(self, t, beta):
+        return self._value(5, beta, t)
+
+    def close(self):
+        if self.h:
+            self._L.eigenex_thermal_ensemble_destroy(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class _SpinSolverBase:

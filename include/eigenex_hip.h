@@ -529,6 +529,33 @@ int eigenex_spin_measure_host_z(int n_sites, int n_up /* -1: full space */, cons
                                 const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks, double* diag_out,
                                 double* flip_out, double* norm2);
 int eigenex_spin_geometry(eigenex_csr_t csr, int* n_sites, int* n_up);
+/* The observables of one real vector x against basis columns, <V_j| A_t |x>, for the mask lists and rules of eigenex_spin_measure.
+ * With V_j the columns first .. first + count - 1 of the state, raw and unnormalised, rows ascending, one fma per row and sum:
+ *   diag_out[t * count + j] = sum_s (prod_{i in mask_t} sigma_i(s)) V_j(s) x_s             <V_j| prod sigma |x>
+ *   flip_out[t * count + j] = sum_s [sigma_a(s) != sigma_b(s)] V_j(s) x_{s ^ mask_t}       two bits: <V_j| S+_a S-_b + S-_a S+_b |x>
+ *   flip_out[t * count + j] = sum_s V_j(s) x_{s ^ mask_t}                                  one bit, full space only: <V_j| 2 Sx_a |x>
+ * With x = column 0 of a Lanczos basis these are the g_i = <v_i| A |v_0> that thermal expectation values by the finite-temperature
+ * Lanczos method need; products of site operators, which eigenex_spin_site_apply does not form, are diagonal masks here.
+ *   eigenex_spin_measure_columns       x_ref = any vector reference of the state, a basis column included; first and count
+ *                              address basis columns as eigenex_dots does with stride 1: count >= 1, first >= 0, first + count <=
+ *                              the capacity.  Needs a real state whose operator handle came from eigenex_spin_upload or
+ *                              eigenex_spin_sector_upload; a complex state, a momentum handle, a stored operator or a host
+ *                              callback is EIGENEX_ERR_STATE, and the message names the handles that are served.  The mask
+ *                              errors are eigenex_spin_measure's (EIGENEX_ERR_ARG).  The basis streams past once per 16 terms of
+ *                              the longer list; per row the state, the rank-table gathers and the gathered x are taken once for
+ *                              every 4 columns.  Runs on the context's stream and synchronises once.  If a batch of one-sweep
+ *                              steps has left its newest column pending (eigenex_basis_close_pending) and that column is x_ref or
+ *                              lies in the range, it is closed first, as every other entry point would; nothing else of the
+ *                              state changes: no vector, coefficient, counter or recorded batch.  No atomics: out[t][j] has
+ *                              the same bits whatever other terms and columns share the call, and from run to run.
+ *   eigenex_spin_measure_columns_host  the definition in host code: no context, no GPU.  x has the rows of (n_sites, n_up) as
+ *                              for eigenex_spin_measure_host, column j is V + j * ldv, ldv >= rows.  With V_j = x a diagonal
+ *                              sum has the bits of eigenex_spin_measure_host's diag_out[t]. */
+int eigenex_spin_measure_columns(eigenex_basis_t b, int x_ref, int first, int count, int n_diag, const uint32_t* diag_masks,
+                                 int n_flip, const uint32_t* flip_masks, double* diag_out, double* flip_out);
+int eigenex_spin_measure_columns_host(int n_sites, int n_up /* -1: full space */, const double* x, const double* V, int64_t ldv,
+                                      int count, int n_diag, const uint32_t* diag_masks, int n_flip, const uint32_t* flip_masks,
+                                      double* diag_out, double* flip_out);
 /* A sum of single-site spin operators applied to a real vector, y = O x: the start vector of a dynamical correlation function
  * (Lanczos continued fraction) formed on the device, also where O changes the magnetisation.  NOT part of the reference.  O is a
  * kind and n_sites real coefficients c[i]; x lives on the rows of the source geometry (n_sites, n_up_src; n_up = -1: the full
